@@ -18,10 +18,13 @@ resident in HBM before the timed region.  Before the timed steps the GPU is kept
 `value` = algorithmic bytes of all ranks per step / max-over-ranks step time.
 Algorithmic bytes per layer: n*k/2 + (k/g)*n*4 + 32*n + m*k*2 + m*n*2 = 9 060 352 B.
 
-After the timed region rank 0 (a) checks three layers of the timed launch's output against the CPU oracle,
+A plain run stops there: set-up, warm-up, the timed steps, the outputs (--dump-outputs DIR: the last timed step's
+output as DIR/y.npy in float32, same inputs on every run with the same arguments) and the result line.
+With --full, rank 0 then (a) checks three layers of the timed launch's output against the CPU oracle,
 (b) times the other BASELINE configs as extra keys (m = 8; config 3 = m = 8, 8192^2, weights on the A side;
 config 4 = int4 / nf4-style global LUT / mx4 at m = 1), (c) times single-layer launches (what one
-Any4Linear.forward issues), (d) times the reference's CPU path on the host cores.
+Any4Linear.forward issues), (d) times the reference's CPU path on the host cores, (e) the decode leg, the
+rocprofv3 PMC passes and (N > 1) the other exchanges and the weak-scaling protocol.
 
 N > 1 (north_star / SURVEY.md 8e): ONE stack of L layers of n rows, row-sharded -- rank r owns rows
 [r*n/N, (r+1)*n/N) of every layer (packed codes, LUT rows, scale/zero columns); the activations are
@@ -135,6 +138,24 @@ def attach_workspace(lib, aa, device):
     ws = torch.empty(need, dtype=torch.uint8, device=device)
     aa.workspace, aa.workspace_bytes = ws.data_ptr(), need
     return ws
+
+
+DUMP_CAP_BYTES = 48 << 20  # --dump-outputs stays under 64 MB
+
+
+def dump_outputs(directory, y):
+    """--dump-outputs: `y` (what a caller of the timed path receives) as float32 DIR/y.npy; larger than DUMP_CAP_BYTES, a fixed
+    sample of its elements (seed 0, flat indices in increasing order) as DIR/y_sample.npy.  Returns {file name: shape}."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    if y.numel() * 4 <= DUMP_CAP_BYTES:
+        name, arr = "y", y.float().cpu().numpy()
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(y.numel(), DUMP_CAP_BYTES // 4, replace=False))
+        name, arr = "y_sample", y.reshape(-1)[torch.from_numpy(idx).to(y.device)].float().cpu().numpy()
+    np.save(os.path.join(directory, name + ".npy"), arr)
+    return {name + ".npy": list(arr.shape)}
 
 
 def check_layers(w, x, q, lut, y, g, qtype, on_right, inner, plan, layers=(0, 1, -1), rows=256, native=False):
@@ -525,7 +546,15 @@ def main():
     ap.add_argument("--roofline-only", action="store_true",
                     help="skip the informational legs (other configs, single-layer, cpu): every launch of the stacked "
                          "kernel is then a timed-shape launch, which is what the rocprofv3 --stats pass wants")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline figure, also the oracle check, the other configs, single-layer launches, many-rows GEMM, "
+                         "decode leg, PMC passes, CPU baselines and (N > 1) the other exchanges; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's output (the whole problem's [layers, m, n]) to DIR/y.npy in float32; "
+                         f"above {DUMP_CAP_BYTES >> 20} MiB a fixed, seeded sample of its elements to DIR/y_sample.npy instead")
     a = ap.parse_args()
+    if a.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -604,6 +633,7 @@ def main():
 
     def gather_rccl():
         dist.all_gather_into_tensor(y_all, y)
+        return y_all
 
     def gather_peer():
         return pg.gather(y.view(L * m, n))
@@ -641,6 +671,7 @@ def main():
     #  because the all-gather sits between the launches)
     per_launch = world > 1
     ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.steps if per_launch else 1)]
+    gathered = None
     t0 = time.perf_counter()
     if not per_launch:
         ev[0][0].record(stream)
@@ -650,7 +681,7 @@ def main():
         launch(args)
         if per_launch:
             ev[s][1].record(stream)
-            gather()
+            gathered = gather()
     if not per_launch:
         ev[0][1].record(stream)
     fence()
@@ -658,6 +689,17 @@ def main():
     kern_ms = sum(e0.elapsed_time(e1) for e0, e1 in ev) / a.steps
 
     elapsed, kern_ms = all_max([elapsed, kern_ms])
+
+    # what a caller of the timed path receives from its last step: [L][m][n_full] (N > 1: the gathered outputs of every rank)
+    dumped = None
+    if a.dump_outputs and rank == 0:
+        if world == 1:
+            y_out = y
+        elif rccl:
+            y_out = gathered.permute(1, 2, 0, 3).reshape(L, m, n_full)   # rank-major [N][L][m][n] -> rows of rank r at [r n, (r+1) n)
+        else:
+            y_out = gathered.view(L, m, n_full)                           # the peer-write gather's [L m][n_full], feature order
+        dumped = dump_outputs(a.dump_outputs, y_out)
 
     bytes_layer = alg_bytes(m, n, k, g)              # this rank's shard of one layer (x is read by every rank)
     bytes_layer_full = alg_bytes(m, n_full, k, g)    # the layer of the whole problem (x counted once)
@@ -688,7 +730,7 @@ def main():
         return e0.elapsed_time(e1) * 1e3 / reps  # us per launch
 
     slope_us = main_check = m1_ab = None
-    if rank == 0 and not a.roofline_only:
+    if rank == 0 and a.full and not a.roofline_only:
         # marginal rate: slope of launch time over the number of stacked layers -- measured first, while the
         # clock is still in the steady state of the timed region
         half = make_args(_lib, w, x, sz, lut, y, m, n, k, g, "any4_rowwise", on_right, inner, L // 2, native=True)
@@ -700,7 +742,7 @@ def main():
         main_check = check_layers(w, x, sz, lut, y, g, "any4_rowwise", on_right, inner, plan, native=True)
 
     exchange = strong_extra = weak = None
-    if world > 1 and not a.roofline_only:
+    if world > 1 and a.full and not a.roofline_only:
         # the same strong-scaling step with the other exchange, and with none (what the exchange costs)
         side = min(a.steps, 50)
         strong_extra = {"ms_per_step_no_exchange": round(timed_steps(lambda: launch(args), side), 5)}
@@ -770,7 +812,7 @@ def main():
 
         # N > 1: the other configs, the single-launch figures, the decode leg and the CPU baselines are N = 1 facts (the driver's
         # N = 1 run carries them): rank 0 does not keep the other ranks waiting in the final barrier for them
-        legs = {} if world > 1 else {
+        legs = {} if world > 1 or not a.full else {
             "m8": leg("any4_rowwise", 8, n, k, g, True, L, f"the metric's second point: m=8, n=k={n}, g={g}, Bint4"),
             "m16": leg("any4_rowwise", 16, n, k, g, True, L // 2, f"m=16 (the reference's full 16-row tile, TinyGemmImpl.cuh:53-54), n=k={n}, g={g}, Bint4"),
             "config3": leg("any4_rowwise", 8, 8192, 8192, 128, False, 128, "BASELINE config 3: m=8, n=k=8192, g=128, weights on the A side (weightOnRight=False ops), in the packed format convert_matrix_to_m16n8k16_Aint4_layout returns (row-per-lane order, TG_WFMT_ROWS)"),
@@ -837,7 +879,7 @@ def main():
                     "note": "one layer per launch, distinct weights per launch; the reference walks m in 16-row blocks (TinyGemmImpl.cuh:379-392), "
                             "this kernel dequantises once per 128-row tile; a 16-bit GEMM of the vendor library on the dequantised weights is an opt-in route (ANY4_LARGE_M_GEMM=library)"}
 
-        many_rows = {} if world > 1 else {"m64": many_rows_leg(64, n, k, g), "m128": many_rows_leg(128, n, k, g), "m512": many_rows_leg(512, n, k, g),
+        many_rows = {} if world > 1 or not a.full else {"m64": many_rows_leg(64, n, k, g), "m128": many_rows_leg(128, n, k, g), "m512": many_rows_leg(512, n, k, g),
                                           "m2048": many_rows_leg(2048, n, k, g, layers=4)}
 
         # (c) single-layer launches: what one module forward issues (the reference's microbenchmark shape) -- Any4Linear's
@@ -890,35 +932,41 @@ def main():
                     "us_per_launch_in_hipgraph": round(graph_us, 3), "frac_in_hipgraph": round(bl / graph_us / 1e3 / HBM_PEAK_GBPS, 4),
                     "kernel_plan": ops.gemm_w4_plan(m, n, k, g, QT[qtype], on_right, inner, torch.bfloat16, 1, "fast", weight_format="native")}
 
-        single_b = single_layer("any4_rowwise", True, (w, x, sz, lut, y)) if world == 1 else {}
-        single_a = single_layer("int4", False) if world == 1 else {}
+        full1 = a.full and world == 1
+        single_b = single_layer("any4_rowwise", True, (w, x, sz, lut, y)) if full1 else {}
+        single_a = single_layer("int4", False) if full1 else {}
         # ... and at a few rows (a prefill of a few tokens through the module; what the reference's microbenchmark.py:20-59 times)
-        single_m8 = single_layer("any4_rowwise", True, m=8) if world == 1 else {}
-        single_m16 = single_layer("any4_rowwise", True, m=16) if world == 1 else {}
+        single_m8 = single_layer("any4_rowwise", True, m=8) if full1 else {}
+        single_m16 = single_layer("any4_rowwise", True, m=16) if full1 else {}
         # ... and a gate+up-shaped layer (28672 x 4096, Llama-3-8B) at 16 rows: one workgroup per 64-row item on w4_gemm_xr_kernel
-        single_m16_gate_up = single_layer("any4_rowwise", True, m=16, n=28672, k=4096, layers=16) if world == 1 and (n, k) == (4096, 4096) else {}
+        single_m16_gate_up = single_layer("any4_rowwise", True, m=16, n=28672, k=4096, layers=16) if full1 and (n, k) == (4096, 4096) else {}
         # the host floor of the entry point: back-to-back launches of a 16 x 512 problem (5.9 KB) through the same C-ABI call
-        tw_, tx_, tq_, tl_, ty_ = make_batch(1, 1, 16, 512, g, inner, device, 5)
-        tiny = make_args(_lib, tw_, tx_, tq_, tl_, ty_, 1, 16, 512, g, "any4_rowwise", True, inner, 1)
-        for _ in range(20):
-            launch(tiny)
-        torch.cuda.synchronize()
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record(stream)
-        for _ in range(L):
-            launch(tiny)
-        e1.record(stream)
-        torch.cuda.synchronize()
-        floor_us = e0.elapsed_time(e1) * 1e3 / L
+        floor_us = None
+        if a.full:
+            tw_, tx_, tq_, tl_, ty_ = make_batch(1, 1, 16, 512, g, inner, device, 5)
+            tiny = make_args(_lib, tw_, tx_, tq_, tl_, ty_, 1, 16, 512, g, "any4_rowwise", True, inner, 1)
+            for _ in range(20):
+                launch(tiny)
+            torch.cuda.synchronize()
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record(stream)
+            for _ in range(L):
+                launch(tiny)
+            e1.record(stream)
+            torch.cuda.synchronize()
+            floor_us = e0.elapsed_time(e1) * 1e3 / L
 
         # (d) BASELINE config 5 (TP = 1) and the live PMC traffic of the timed kernel; the bench tensors are released first
         decode = None
-        if not a.no_decode and world == 1:
+        if full1 and not a.no_decode:
             try:
                 decode = decode_leg(device)
             except Exception as e:  # noqa: BLE001  (an informational leg must not take the metric line down with it)
                 decode = {"error": f"{type(e).__name__}: {e}"}
-        traffic, traffic_note = (None, "skipped (--no-pmc or N > 1)") if (a.no_pmc or world > 1) else pmc_traffic(L, bytes_step_rank)
+        if not a.full:
+            traffic, traffic_note = None, "not measured in a plain run (--full)"
+        else:
+            traffic, traffic_note = (None, "skipped (--no-pmc or N > 1)") if (a.no_pmc or world > 1) else pmc_traffic(L, bytes_step_rank)
 
         out = {
             "metric": "any4 W4A16 GEMM achieved GB/s (m=1, n=k=4096, g=128)",
@@ -948,7 +996,7 @@ def main():
                             "and `reference_numerics` for the kernels with the reference's own arithmetic)",
             },
             # 3 layers x 256 rows of the TIMED launch's y against both CPU oracles (see check_layers)
-            "numerics_check": main_check,
+            **({"numerics_check": main_check} if a.full else {}),
             "roofline": {
                 "bound": "hbm",
                 "kernel": {"pair": ("w4_gemm_xr_kernel<BF16> / w4_gemm_pair_kernel<BF16, I=4> (persistent work items, pair-table lookups, m = 1 contraction on the matrix core: "
@@ -966,42 +1014,48 @@ def main():
                 "launch_us": round(kern_ms * 1e3, 3),
                 "bytes_per_launch": bytes_step_rank,
             },
-            "marginal": {
-                "us_per_layer": round(slope_us, 4),
-                "GBps": round(bytes_layer / slope_us / 1e3, 2),
-                "frac": round(bytes_layer / slope_us / 1e3 / HBM_PEAK_GBPS, 4),
-                "note": f"dT/dL between stacked launches of {L // 2} and {L} layers (launch overhead cancels)",
-            },
-            **legs,
-            "single_layer_launch": {
-                **single_b,
-                "us_launch_floor_back_to_back": round(floor_us, 3),
-                "int4_a_side": single_a,
-                "m8": single_m8,
-                "m16": single_m16,
-                "m16_28672x4096": single_m16_gate_up,
-                "note": "one 4096x4096 GEMV per launch: top level = any4 per-row LUT, weights on the B side (what Any4Linear.forward issues); "
-                        "int4_a_side = uniform int4, weights on the A side (Int4Linear's default kernel, modules.py:21); m8 / m16 = the top-level layer at 8 / 16 activation rows.  back_to_back = launches of "
-                        "distinct cold layers on one stream (event time / launches); cold = median HIP-event time of an isolated launch (event pair "
-                        "floor on this stack: ~4.3 us); in_hipgraph = the same launches replayed from one captured graph; launch_floor = a 16 x 512 "
-                        "problem through the same entry point, back to back: the host/runtime cost per launch that back_to_back cannot go below",
-            },
-            "many_rows_gemm": many_rows,
-            "decode_llama3_8b": decode,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        if a.full:
+            out.update({
+                "marginal": {
+                    "us_per_layer": round(slope_us, 4),
+                    "GBps": round(bytes_layer / slope_us / 1e3, 2),
+                    "frac": round(bytes_layer / slope_us / 1e3 / HBM_PEAK_GBPS, 4),
+                    "note": f"dT/dL between stacked launches of {L // 2} and {L} layers (launch overhead cancels)",
+                },
+                **legs,
+                "single_layer_launch": {
+                    **single_b,
+                    "us_launch_floor_back_to_back": round(floor_us, 3),
+                    "int4_a_side": single_a,
+                    "m8": single_m8,
+                    "m16": single_m16,
+                    "m16_28672x4096": single_m16_gate_up,
+                    "note": "one 4096x4096 GEMV per launch: top level = any4 per-row LUT, weights on the B side (what Any4Linear.forward issues); "
+                            "int4_a_side = uniform int4, weights on the A side (Int4Linear's default kernel, modules.py:21); m8 / m16 = the top-level layer at 8 / 16 activation rows.  back_to_back = launches of "
+                            "distinct cold layers on one stream (event time / launches); cold = median HIP-event time of an isolated launch (event pair "
+                            "floor on this stack: ~4.3 us); in_hipgraph = the same launches replayed from one captured graph; launch_floor = a 16 x 512 "
+                            "problem through the same entry point, back to back: the host/runtime cost per launch that back_to_back cannot go below",
+                },
+                "many_rows_gemm": many_rows,
+                "decode_llama3_8b": decode,
+            })
         if m1_ab is not None:
             out["m1_contraction_ab"] = m1_ab
         if world > 1:
             out["strong_scaling"] = {"value": round(value, 2), "unit": "GB/s", "ms_per_step": round(ms_per_step, 5), "exchange": exchange_kind,
                                      "rows_per_rank": n, "per_rank_roofline_frac": round(achieved / HBM_PEAK_GBPS, 4),
                                      "per_rank_kernel_us": round(kern_ms * 1e3, 3), **(strong_extra or {})}
-            out["weak_scaling"] = weak
+            if weak is not None:
+                out["weak_scaling"] = weak
         if exchange is not None:
             out["decode_shaped_exchange"] = exchange
-        if world == 1 and not a.no_cpu_baseline:
+        if full1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_torch(m, n, k, g)
             out["cpu_baseline_c_oracle"] = cpu_baseline_oracle(m, n, k, g)
-        if world == 1:
+        if full1:
             # the LAST key of the line: what a reader of its tail needs -- the metric's second point (m = 8), the other BASELINE
             # configs as fractions of the 8 TB/s HBM roofline, MFMA utilisation where the metric asks for it, the decode step
             fr = lambda name, sub=None: (legs.get(name, {}) if sub is None else legs.get(name, {}).get(sub, {})).get("frac")  # noqa: E731

@@ -1281,3 +1281,30 @@ def test_module_launch_plan_is_the_full_path_and_follows_its_inputs():
             assert torch.equal(y_ref, full(xs[0]))
         assert torch.equal(lin(xs[0]), y_new)
 
+
+
+@pytest.mark.timeout(240)
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full): one result line with the headline keys, exactly --steps timed steps, and --dump-outputs:
+    the timed launch's output [layers][m][n] as float32, finite, with max|y| where calibrate_x puts it."""
+    import json
+    import os
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--layers", "16",
+           "--settle-s", "0", "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=200)
+    assert r.returncode == 0, r.stdout[-1500:] + "\n" + r.stderr[-3000:]
+    lines = [json.loads(ln) for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout[-1500:]
+    line = lines[0]
+    assert line["unit"] == "GB/s" and line["higher_is_better"] is True and line["dtype"] == "bf16" and "metric" in line
+    assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert abs(line["value"] - 16 * 9060352 / (line["ms_per_step"] * 1e-3) / 1e9) <= 0.02 * line["value"]
+    assert "numerics_check" not in line and "legs_summary" not in line          # the other legs are --full only
+    assert line["dumped_outputs"] == {"y.npy": [16, 1, 4096]}
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and y.shape == (16, 1, 4096) and np.isfinite(y).all()
+    assert 0.95 < float(np.abs(y).max()) <= 1.9

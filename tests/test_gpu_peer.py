@@ -310,7 +310,7 @@ def _run_bench_two_ranks(backend, extra=(), timeout=420):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     multi = torch.cuda.device_count() >= 2
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "2",
+           "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--steps", "4", "--warmup", "2",
            "--layers", "64", "--settle-s", "0", "--no-pmc", "--no-decode", "--no-cpu-baseline", "--dist-backend", backend,
            *([] if multi else ["--same-device"]), *extra]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
@@ -325,18 +325,19 @@ def _run_bench_two_ranks(backend, extra=(), timeout=420):
     return r.returncode, line, (r.stdout[-1500:] + "\n" + r.stderr[-3000:])
 
 
-def test_bench_strong_scaling_leg_two_ranks():
+def test_bench_strong_scaling_leg_two_ranks(tmp_path):
     """SURVEY.md 8(e) / north_star: `bench.py --gpus 2` partitions ONE stack of n = 4096 layers into rows [r n/2, (r+1) n/2) per rank,
     gathers the layer batch's outputs once per step and reports the WHOLE problem's GB/s ("scaling": "strong") with the per-rank
     roofline fraction, the weak-scaling protocol as an extra key and the decode-shaped (latency) exchange.  Two ranks: on two GPUs over
     RCCL where the box has them; on a one-GPU box RCCL is tried first (it refuses two ranks on one device) and the same code path then
     runs with the gloo control plane and the peer-write gather over IPC -- so the first run on a real node is not the first run of this
     code."""
-    rc, line, tail = _run_bench_two_ranks("nccl", timeout=420 if torch.cuda.device_count() >= 2 else 150)
+    dump = ("--dump-outputs", str(tmp_path))
+    rc, line, tail = _run_bench_two_ranks("nccl", dump, timeout=420 if torch.cuda.device_count() >= 2 else 150)
     used = "nccl"
     if rc != 0 or line is None:
         assert torch.cuda.device_count() < 2, f"RCCL run failed on a multi-GPU box:\n{tail}"
-        rc, line, tail = _run_bench_two_ranks("gloo")
+        rc, line, tail = _run_bench_two_ranks("gloo", dump)
         used = "gloo"
     assert rc == 0 and line is not None, tail
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["unit"] == "GB/s" and line["value"] > 0
@@ -354,4 +355,10 @@ def test_bench_strong_scaling_leg_two_ranks():
     assert ex["us_per_layer_gemv_only"] > 0 and ("us_per_layer_gemv_plus_peer_write_gather" in ex or "peer_write_gather_error" in ex)
     if used == "nccl":
         assert ex["us_per_layer_gemv_plus_rccl_all_gather"] > 0
+    # --dump-outputs: the gathered output of the whole problem (both ranks' rows), as a caller of the sharded layer batch receives it
+    import numpy as np
+
+    assert line["dumped_outputs"] == {"y.npy": [64, 1, 4096]}
+    y = np.load(tmp_path / "y.npy")
+    assert y.dtype == np.float32 and np.isfinite(y).all() and np.abs(y[..., :2048]).max() > 0 and np.abs(y[..., 2048:]).max() > 0
     print(f"bench.py --gpus 2 ran with backend {used}: value {line['value']} GB/s, per-rank frac {ss['per_rank_roofline_frac']}")

@@ -277,6 +277,27 @@ def test_bench_cpu_baseline_leg_and_byte_formula():
     assert co["value"] > 0 and co["cores"] >= 1
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: the whole output as float32 under the cap, a fixed sample of its elements above it."""
+    import importlib.util
+
+    import numpy as np
+
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    y = torch.randn(4, 2, 64, generator=torch.Generator().manual_seed(0)).bfloat16()
+    assert bench.dump_outputs(str(tmp_path / "all"), y) == {"y.npy": [4, 2, 64]}
+    got = np.load(tmp_path / "all" / "y.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, y.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_CAP_BYTES", 4 * 100)
+    assert bench.dump_outputs(str(tmp_path / "s1"), y) == {"y_sample.npy": [100]}
+    assert bench.dump_outputs(str(tmp_path / "s2"), y) == {"y_sample.npy": [100]}
+    s1, s2 = np.load(tmp_path / "s1" / "y_sample.npy"), np.load(tmp_path / "s2" / "y_sample.npy")
+    assert s1.dtype == np.float32 and np.array_equal(s1, s2)          # the same sample every run
+    assert np.isin(s1, y.float().numpy().ravel()).all()
+
+
 def test_xr_kernel_routing():
     """Which stacked launches the xr kernel takes (tg_gemm_w4_plan, no GPU work): Bint4, k = 4096 / 8192 / 14336, innerKTiles 4, rows a
     multiple of 64, 2 <= m <= 16, every group size (k = 4096), at least two work items per CU; everything else stays where it was."""
