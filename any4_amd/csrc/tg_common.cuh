@@ -10,6 +10,7 @@
 //   tg_xr.hip          w4_gemm_xr_kernel         (w4_gemm_xr.cuh)
 //   tg_gemv.hip        w4_gemv_kernel            (w4_gemv.cuh)
 //   tg_tile.hip        w4_gemm_tile_kernel       (w4_gemm_tile.cuh)
+//   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once
@@ -177,6 +178,7 @@ int splitk(int dt, bool layout_a, int canon, bool qmx, int waves, const GemmPara
 int gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
 int tile(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);  // w4_gemm_tile.cuh: many activation rows
 int tile_w8(int dt, bool on_right, int I, GemmParams& p, int64_t batch, hipStream_t st);  // ... int8 weights (tg_gemm_w8)
+int gemm_dx(int dt, int I, bool qmx, GemmParams& p, hipStream_t st);  // w4_gemm_dx.cuh: dX = dY . W (tg_gemm_w4_dx)
 inline int pair(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
   return dt == TG_BF16 ? pair_bf16(I, qmx, p, batch, st) : pair_f16(I, qmx, p, batch, st);
 }

@@ -938,6 +938,70 @@ int64_t tg_gemm_w4_workspace_bytes(const tg_w4_gemm* a) {
   return rc < 0 ? rc : need;
 }
 
+// ---- input gradient dX = dY . W (tg_gemm_w4_dx; the kernel and its launch path: w4_gemm_dx.cuh, tg_dx.hip) ----
+// dry: 0 launch, 2 report the workspace of the split.  Every check runs before any HIP call.
+static int gemm_dx_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
+  tg_w4_gemm full;
+  const int src = take_args(caller, &full);
+  if (src != 0) return src;
+  const tg_w4_gemm* a = &full;
+  if (!a->x || !a->w || !a->qinfo || !a->y) return TG_E_NULL;
+  if (a->qtype < TG_Q_INT4 || a->qtype > TG_Q_MX4) return TG_E_QTYPE;
+  if ((a->qtype == TG_Q_ANY4_GLOBAL || a->qtype == TG_Q_ANY4_ROWWISE) && !a->lut) return TG_E_NULL;
+  if (!(a->dtype == TG_BF16 || a->dtype == TG_F16)) return TG_E_DTYPE;
+  if (a->qtype == TG_Q_MX4 && a->dtype != TG_BF16) return TG_E_DTYPE;
+  if (a->batch > 1) return TG_E_SHAPE;
+  if (a->bias || a->bias_row_stride || a->norm_weight || a->epilogue) return TG_E_FUSION;
+  if (a->x_layout != TG_LAYOUT_RM || a->y_layout != TG_LAYOUT_RM) return TG_E_LAYOUT;
+  if (!(a->w_format == TG_WFMT_M16N8K16 || a->w_format == TG_WFMT_ROWS) || (a->w_format && a->w_on_right) || a->reserved6 != 0) return TG_E_SHAPE;
+  if (!a->w_on_right && a->w_format != TG_WFMT_ROWS) return TG_E_LAYOUT;   // the reference's Aint4 words: repack to the native format
+  if (!(a->numerics == TG_NUM_FAST || a->numerics == TG_NUM_REFERENCE || a->numerics == TG_NUM_FAST_MFMA || a->numerics == TG_NUM_FAST_DOT2) || a->reserved != 0) return TG_E_SHAPE;
+  if (a->m <= 0 || a->wrows <= 0 || a->k <= 0 || a->m > INT32_MAX || a->wrows > INT32_MAX || a->k > INT32_MAX) return TG_E_SHAPE;
+  int I = a->inner_k_tiles;
+  if (a->w_on_right ? !(I == 2 || I == 4 || I == 8) : !(I == 1 || I == 2 || I == 4)) return TG_E_INNER_K;
+  if (a->k % 32 != 0 || a->k % (16 * I) != 0) return TG_E_K_DIV;
+  const int g = a->group;
+  if (!(g == 32 || g == 64 || g == 128 || g == 256) || a->k % g != 0) return TG_E_GROUP;
+  if (a->wrows % (a->w_on_right ? 8 : 16) != 0) return TG_E_SHAPE;
+  if (!a->w_on_right) I = a->k % 64 == 0 ? 4 : 2;   // TG_WFMT_ROWS: Bint4 words of the rows padded to 16
+  if (!aligned16(a->x) || !aligned16(a->w) || !aligned16(a->y) || (reinterpret_cast<uintptr_t>(a->qinfo) & 3u)) return TG_E_ALIGN;
+  if (a->lut && !aligned16(a->lut)) return TG_E_ALIGN;
+  if (a->workspace && (!aligned16(a->workspace) || a->workspace_bytes < 0)) return TG_E_ALIGN;
+  if (a->m * a->wrows * 2 >= (int64_t)1 << 31 || a->m * a->k * 2 >= (int64_t)1 << 31 || a->wrows * a->k / 2 >= (int64_t)1 << 31 ||
+      (a->k / g) * a->wrows * 4 >= (int64_t)1 << 31)
+    return TG_E_SIZE;
+
+  GemmParams p;
+  memset(&p, 0, sizeof p);
+  p.x = (const char*)a->x;
+  p.w = (const char*)a->w;
+  p.qinfo = (const char*)a->qinfo;
+  p.lut = (const char*)a->lut;
+  p.y = (char*)a->y;
+  p.m = (int32_t)a->m;
+  p.wrows = (int32_t)a->wrows;
+  p.k = (int32_t)a->k;
+  p.gshift = g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8;
+  p.qtype = a->qtype;
+  p.dry = dry != 0;
+  p.ws = (char*)a->workspace;
+  p.ws_bytes = a->workspace ? a->workspace_bytes : 0;
+  p.ws_query = dry == 2;
+  DeviceScope ds(dry ? -1 : device);
+  if (!dry && !ds.ok) return TG_E_DEVICE;
+  const int rc = tgx::gemm_dx(a->dtype, I, a->qtype == TG_Q_MX4, p, (hipStream_t)stream);
+  if (ws_need) *ws_need = p.ws_need;
+  return rc;
+}
+
+int tg_gemm_w4_dx(const tg_w4_gemm* a, int device, tg_stream_t stream) { return gemm_dx_impl(a, device, stream, 0); }
+
+int64_t tg_gemm_w4_dx_workspace_bytes(const tg_w4_gemm* a) {
+  int64_t need = 0;
+  const int rc = gemm_dx_impl(a, -1, nullptr, 2, &need);
+  return rc < 0 ? rc : need;
+}
+
 int tg_convert_to_Bint8(const int32_t* in, int64_t n, int64_t k, int I, int32_t* out, int device, tg_stream_t stream) {
   if (!in || !out) return TG_E_NULL;
   if (!(I == 1 || I == 2 || I == 4)) return TG_E_INNER_K;  // ConvertB.cu:428

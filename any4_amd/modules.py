@@ -19,6 +19,27 @@ from . import ops as _ops
 _T = torch.ops.tinygemm
 
 
+class _Linear4Fn(torch.autograd.Function):
+    """Autograd of a 4-bit module on its row-major kernels.  The forward is the module's own GEMM with the bias offered to the kernel
+    (the same launches and bits as without autograd); the backward is dX = dY . W through the module's dx op and dbias = sum over the
+    rows of dY.  The quantisation parameters are constants: they get no gradient."""
+
+    @staticmethod
+    def forward(ctx, mod, x2d, bias):
+        ctx.mod, ctx.has_bias = mod, bias is not None
+        if bias is None:
+            return mod._gemm(x2d)
+        with _ops.fused_bias(bias) as fb:
+            y = mod._gemm(x2d)
+        return y if fb.consumed else y + bias
+
+    @staticmethod
+    def backward(ctx, dy):
+        dx = ctx.mod._input_grad(dy) if ctx.needs_input_grad[1] else None
+        db = dy.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return None, dx, db
+
+
 class _PackedLinear(torch.nn.Module):
     """Shared machinery: parameter creation, one-off packing and the forward epilogue."""
 
@@ -137,6 +158,27 @@ class _PackedLinear(torch.nn.Module):
     def _gemm(self, x2d: torch.Tensor) -> torch.Tensor:
         raise NotImplementedError
 
+    def _gemm_eager(self, x2d: torch.Tensor) -> torch.Tensor:
+        if torch.is_grad_enabled():
+            return self._gemm(x2d)
+        # no graph to record: straight to the ops' device kernels, past their Autograd kernels (a Python redispatch per call)
+        with torch._C._AutoDispatchBelowAutograd():
+            return self._gemm(x2d)
+
+    # row-major 4-bit kernels with an input gradient (ops.AUTOGRAD_OPS) -> weightOnRight
+    _DX_KERNELS: dict = {}
+    _DX_OP = None
+
+    def _input_grad(self, dy: torch.Tensor) -> torch.Tensor:
+        """dX [rows][in_features] = dY . W on the packed weight (the op of ops.AUTOGRAD_OPS this module's kernel runs)."""
+        return getattr(_T, self._DX_OP)(dy, self.weight, self.group_size, self._qinfo(), *self._luts(), self._DX_KERNELS[self.kernel])
+
+    def _qinfo(self):
+        return self.scales_and_zeros
+
+    def _luts(self):
+        return ()
+
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         return self._forward(input)
 
@@ -153,7 +195,8 @@ class _PackedLinear(torch.nn.Module):
         d = self.__dict__
         plan = d.get("_plan")
         p = self._parameters
-        if plan is not None and p.get("bias") is None:   # (a bias assigned after the recording: the full path, which offers it to the kernel)
+        if plan is not None and p.get("bias") is None and not (input.requires_grad and torch.is_grad_enabled()):
+            # (a bias assigned after the recording: the full path, which offers it to the kernel; an input that wants a gradient: below)
             # the validated launch of this (module, activation shape) re-issued with new pointers (ops.LaunchPlan.try_run): the eager hot path
             y = plan.try_run(input, p["weight"], p.get("scales_and_zeros") if "scales_and_zeros" in p else p.get("exponents"), p.get("lut"),
                              (self.kernel, self.group_size, self.w_inner_k))
@@ -162,6 +205,11 @@ class _PackedLinear(torch.nn.Module):
         if d.get("_relayout_pending") and self.weight.is_cuda:
             self._auto_relayout()    # (a checkpoint in the reference's Aint4 words that was loaded on the CPU: repacked once, see above)
         lead = input.shape[:-1]
+        if (torch.is_grad_enabled() and self.kernel in self._DX_KERNELS and self.weight_reshaped and
+                (input.requires_grad or (self.bias is not None and self.bias.requires_grad))):
+            # training through the quantised layer: no recorded plan (its output has no graph); the same launches, with a grad_fn
+            y = _Linear4Fn.apply(self, input.reshape(-1, input.shape[-1]), self.bias)
+            return y.view(*lead, y.shape[-1])
         if input.is_cuda and self.bias is None and self.weight_reshaped and d.get("_no_plan") != (input.shape, _ops.get_numerics()):
             # a packed weight only: the plan points at the parameters themselves
             x2d = input.view(-1, input.shape[-1])
@@ -175,12 +223,12 @@ class _PackedLinear(torch.nn.Module):
                     d["_no_plan"] = (input.shape, _ops.get_numerics())   # (this flavour has no single-launch plan: remembered, not retried per call)
                 return y.view(*lead, y.shape[-1])
         if self.bias is None:
-            y = self._gemm(input.view(-1, input.shape[-1]))
+            y = self._gemm_eager(input.view(-1, input.shape[-1]))
         else:
             # the row-major GEMM kernels add the bias in their output store (same bits as the reference's separate
             # `y + bias`, modules.py:221-222, one launch fewer); layouts that cannot take it get the separate add
             with _ops.fused_bias(self.bias) as fb:
-                y = self._gemm(input.view(-1, input.shape[-1]))
+                y = self._gemm_eager(input.view(-1, input.shape[-1]))
             if not fb.consumed:
                 y = y + self.bias
         return y.view(*lead, y.shape[-1])
@@ -198,6 +246,9 @@ class Int4Linear(_PackedLinear):
     }
     _KERNELS = ("linear_y_f16RM_x_f16RM_W_int4TC", "linear_y_f16RM_W_int4TC_x_f16RM",
                 "linear_y_f16TC_W_int4TC_x_f16TC", "linear_y_f16TC_x_f16TC_W_int4TC")
+
+    _DX_KERNELS = {"linear_y_f16RM_x_f16RM_W_int4TC": True, "linear_y_f16RM_W_int4TC_x_f16RM": False}
+    _DX_OP = "tinygemm_dx_f16RM_dy_f16RM_w_int4TC"
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
                  group_size: int = 128, kernel: str = "linear_y_f16RM_W_int4TC_x_f16RM", w_inner_k: int = 4) -> None:
@@ -238,6 +289,12 @@ class Any4Linear(_PackedLinear):
         "linear_y_f16RM_x_f16RM_W_any4TC": "convert_matrix_to_m16n8k16_Bint4_layout",
         "linear_y_f16RM_W_any4TC_x_f16RM": "convert_matrix_to_m16n8k16_Aint4_layout",
     }
+
+    _DX_KERNELS = {"linear_y_f16RM_x_f16RM_W_any4TC": True, "linear_y_f16RM_W_any4TC_x_f16RM": False}
+    _DX_OP = "tinygemm_dx_f16RM_dy_f16RM_w_any4TC"
+
+    def _luts(self):
+        return (self.lut,)
 
     @property
     def N_BIT(self):
@@ -289,6 +346,11 @@ class MX4Linear(_PackedLinear):
         "linear_y_f16RM_x_f16RM_W_mx4TC": "convert_matrix_to_m16n8k16_Bint4_layout",
         "linear_y_f16RM_W_mx4TC_x_f16RM": "convert_matrix_to_m16n8k16_Aint4_layout",
     }
+    _DX_KERNELS = {"linear_y_f16RM_x_f16RM_W_mx4TC": True, "linear_y_f16RM_W_mx4TC_x_f16RM": False}
+    _DX_OP = "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC"
+
+    def _qinfo(self):
+        return self.exponents
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
                  group_size: int = 32, kernel: str = "linear_y_f16RM_x_f16RM_W_mx4TC", w_inner_k: int = 4) -> None:

@@ -45,6 +45,11 @@ SCHEMAS = {
     "tinygemm_y_f16TC_x_f16TC_w_f16TC": "(Tensor A, Tensor B, bool weightOnRight) -> Tensor",
     "tinygemm_y_f16RM_x_f16RM_w_f16TC": "(Tensor A, Tensor B, bool weightOnRight) -> Tensor",
     "tinygemm_dequant_int4": "(Tensor t) -> Tensor",
+    # the input gradient of the row-major 4-bit GEMMs (no reference counterpart: its library is inference-only).  Arguments mirror the
+    # forward op with dY in place of the activations; k is read off the packed weight's shape.
+    "tinygemm_dx_f16RM_dy_f16RM_w_int4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, bool weightOnRight) -> Tensor",
+    "tinygemm_dx_f16RM_dy_f16RM_w_any4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, Tensor int4DequantValues, bool weightOnRight) -> Tensor",
+    "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor mx4Exponents, bool weightOnRight) -> Tensor",
 }
 
 _F16_TYPES = (torch.bfloat16, torch.float16)
@@ -792,6 +797,150 @@ def tinygemm_y_f16TC_x_f16TC_w_mx4TC(A, B, qGroupSize, mx4Exponents, weightOnRig
 
 
 # ---------------------------------------------------------------------------------------------
+# autograd of the row-major 4-bit GEMMs: the input gradient dX = dY . W (tg_gemm_w4_dx)
+# ---------------------------------------------------------------------------------------------
+
+_DX_WS_BYTES: dict = {}  # tg_gemm_w4_dx_workspace_bytes per problem shape
+
+_RELAYOUT_HINT = ("the input gradient needs the native packed format of weights on the left; this tensor holds the reference's Aint4 "
+                  "words: call module.relayout(\"native\") (or any4_amd.ops.relayout_Aint4(w, k, \"native\")) once")
+
+
+def _dx_rm(dY, w, q_group, qinfo, lut, qtype, weight_on_right, opname):
+    """dX [m][k] = dY [m][wrows] . W: the input gradient of _w4_rm (weights as the forward op took them)."""
+    _check(dY.device == w.device, "dY and the weights must be on the same device")
+    _check(dY.dim() == 2, "dY must be a 2-D matrix [activation rows][weight rows]")
+    _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous() and w.size(2) == 32, "weights must be a contiguous 4-D int32 tensor")
+    _check(dY.dtype in _F16_TYPES, "dY dtype must be bfloat16 or float16")
+    if weight_on_right:
+        inner, wrows, w_format = w.size(3) * 2, w.size(0) * 8, _lib.TG_WFMT_M16N8K16
+        _check(inner in (2, 4, 8), "Bint4 weights: innermost dim must be 1, 2 or 4")
+    else:
+        # the native tensor (Bint4 words of the rows padded to 16) covers size(0) * 8 rows; the reference's Aint4 words size(0) * 16
+        _check(dY.size(1) != w.size(0) * 16, _RELAYOUT_HINT)
+        inner, wrows, w_format = w.size(3) * 2, w.size(0) * 8, _lib.TG_WFMT_ROWS
+        _check(wrows % 16 == 0 and inner in (2, 4), _RELAYOUT_HINT)
+    k = w.size(1) * inner * 16
+    _check(weight_on_right or inner == _rows_inner(k), _RELAYOUT_HINT)
+    m = dY.size(0)
+    _check(dY.size(1) == wrows, "dY.size(1) must equal the tile-padded weight rows")
+    _check(q_group in (32, 64, 128, 256) and k % q_group == 0, "qGroupSize must be 32, 64, 128 or 256 and divide k")
+    _check(qinfo.device == dY.device, "quantization info must be on dY's device")
+    if qtype == TG_Q_MX4:
+        _check(dY.dtype == torch.bfloat16, "mx4 supports bfloat16 only")
+        _check(qinfo.dtype == torch.uint8 and qinfo.dim() == 2 and qinfo.size(0) == wrows and qinfo.size(1) == k // q_group,
+               "mx4Exponents must be [weight rows (tile padded)][k / qGroupSize] uint8")
+    else:
+        _check(qinfo.dim() == 3 and tuple(qinfo.shape) == (k // q_group, wrows, 2) and qinfo.dtype == dY.dtype,
+               "qScaleAndZeros must be [k / qGroupSize][weight rows][2] of dY's dtype")
+    if lut is not None:
+        _check(lut.device == dY.device and lut.dtype == dY.dtype, "int4DequantValues must be on dY's device, of dY's dtype")
+        if lut.dim() == 1:
+            _check(lut.size(0) == 16, "int4DequantValues must have 16 entries")
+            qtype = TG_Q_ANY4_GLOBAL
+        else:
+            _check(lut.dim() == 2 and lut.size(0) == wrows and lut.size(1) == 16, "row-wise int4DequantValues must be [weight rows (tile padded)][16]")
+            qtype = TG_Q_ANY4_ROWWISE
+        lut = lut.contiguous()
+        if lut.data_ptr() % 16:
+            lut = lut.clone()
+    qinfo = qinfo.contiguous()
+    dx = torch.empty((m, k), dtype=dY.dtype, device=dY.device)
+    if m == 0:
+        return dx
+    # any dY: autograd hands in views and expanded (stride-0) tensors, e.g. from y.sum().backward()
+    dy = dY.contiguous()
+    if dy.data_ptr() % 16:
+        dy = dy.clone()
+    args = W4Gemm(x=dy.data_ptr(), w=w.data_ptr(), qinfo=qinfo.data_ptr(), lut=(lut.data_ptr() if lut is not None else None), y=dx.data_ptr(),
+                  m=m, wrows=wrows, k=k, group=q_group, qtype=qtype, dtype=_dt(dy), w_on_right=1 if weight_on_right else 0,
+                  inner_k_tiles=inner, batch=1, w_format=w_format)
+    key = (m, wrows, k, q_group, qtype, args.dtype, args.w_on_right, inner, _dev(dy))
+    ws_bytes = _DX_WS_BYTES.get(key)
+    if ws_bytes is None:
+        ws_bytes = _L.tg_gemm_w4_dx_workspace_bytes(ctypes.byref(args))
+        if ws_bytes >= 0 and len(_DX_WS_BYTES) < 4096:
+            _DX_WS_BYTES[key] = ws_bytes
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, opname)
+    if ws_bytes > 0:  # f32 partials of the split over the weight rows, from torch's caching allocator (stream-ordered)
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
+    _lib.check(_L.tg_gemm_w4_dx(ctypes.byref(args), _dev(dy), _stream(dy)), opname)
+    return dx
+
+
+def tinygemm_dx_f16RM_dy_f16RM_w_int4TC(dY, W, qGroupSize, qScaleAndZeros, weightOnRight):
+    return _dx_rm(dY, W, qGroupSize, qScaleAndZeros, None, TG_Q_INT4, weightOnRight, "tinygemm_dx_f16RM_dy_f16RM_w_int4TC")
+
+
+def tinygemm_dx_f16RM_dy_f16RM_w_any4TC(dY, W, qGroupSize, qScaleAndZeros, int4DequantValues, weightOnRight):
+    return _dx_rm(dY, W, qGroupSize, qScaleAndZeros, int4DequantValues, TG_Q_ANY4_ROWWISE, weightOnRight, "tinygemm_dx_f16RM_dy_f16RM_w_any4TC")
+
+
+def tinygemm_dx_f16RM_dy_f16RM_w_mx4TC(dY, W, qGroupSize, mx4Exponents, weightOnRight):
+    return _dx_rm(dY, W, qGroupSize, mx4Exponents, None, TG_Q_MX4, weightOnRight, "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC")
+
+
+# forward op -> its dx op.  Only the activations get a gradient: the packed weight, scales_and_zeros, LUT and exponents are constants
+# of the graph (None; learning them -- the reference's learn_anyq -- is not covered).
+AUTOGRAD_OPS = {
+    "tinygemm_y_f16RM_x_f16RM_w_int4TC": "tinygemm_dx_f16RM_dy_f16RM_w_int4TC",
+    "tinygemm_y_f16RM_x_f16RM_w_any4TC": "tinygemm_dx_f16RM_dy_f16RM_w_any4TC",
+    "tinygemm_y_f16RM_x_f16RM_w_mx4TC": "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC",
+}
+
+
+def w4_input_grad(dx_op, dY, args):
+    """dX of a row-major 4-bit GEMM call `args` = (A, B, qGroupSize, qinfo[, lut], weightOnRight) (the forward op's arguments)."""
+    on_right = args[-1]
+    w = args[1] if on_right else args[0]
+    return dx_op(dY, w, *args[2:])
+
+
+class _W4GemmFn(torch.autograd.Function):
+    """The autograd node of one row-major 4-bit GEMM call.  setup_context keeps references only (no copies, no version checks): the
+    kernel runs on every call in grad mode whose inputs require grad, and scales_and_zeros / lut are Parameters that do by default."""
+
+    @staticmethod
+    def forward(op, dx_op, *args):
+        with torch._C._AutoDispatchBelowAutograd():
+            return op(*args)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        ctx.dx_op, ctx.args = inputs[1], inputs[2:]
+
+    @staticmethod
+    def backward(ctx, dy):
+        args = ctx.args
+        on_right = args[-1]
+        dx = w4_input_grad(ctx.dx_op, dy, args) if ctx.needs_input_grad[2 if on_right else 3] else None
+        return (None, None) + ((dx, None) if on_right else (None, dx)) + (None,) * (len(args) - 2)
+
+
+_grad_on = torch.is_grad_enabled
+_AFTER_AUTOGRAD = torch._C._after_autograd_keyset
+
+
+def _autograd_kernel(name):
+    """Autograd-key kernel of a row-major 4-bit GEMM op.  Hand-written rather than torch.library.register_autograd's generic one: the
+    module's eager forward with a bias calls the op on every step, and the generic kernel costs ~9 us per call even under no_grad
+    (pytree walks, a metadata object) against ~2 us for this one (measured on a CPU stand-in op)."""
+    op = getattr(torch.ops.tinygemm, name).default
+    dx_op = getattr(torch.ops.tinygemm, AUTOGRAD_OPS[name]).default
+    lut_at = 4 if len(op._schema.arguments) == 6 else None
+
+    def kernel(keyset, *args):
+        if _grad_on() and (args[0].requires_grad or args[1].requires_grad or args[3].requires_grad or
+                           (lut_at is not None and args[lut_at].requires_grad)):
+            return _W4GemmFn.apply(op, dx_op, *args)
+        return op.redispatch(keyset & _AFTER_AUTOGRAD, *args)
+
+    return kernel
+
+
+# ---------------------------------------------------------------------------------------------
 # 16-bit weights (TinyGemm_bf16.cu)
 # ---------------------------------------------------------------------------------------------
 
@@ -962,6 +1111,9 @@ _IMPLS = {
     "tinygemm_y_f16TC_x_f16TC_w_f16TC": tinygemm_y_f16TC_x_f16TC_w_f16TC,
     "tinygemm_y_f16RM_x_f16RM_w_f16TC": tinygemm_y_f16RM_x_f16RM_w_f16TC,
     "tinygemm_dequant_int4": tinygemm_dequant_int4,
+    "tinygemm_dx_f16RM_dy_f16RM_w_int4TC": tinygemm_dx_f16RM_dy_f16RM_w_int4TC,
+    "tinygemm_dx_f16RM_dy_f16RM_w_any4TC": tinygemm_dx_f16RM_dy_f16RM_w_any4TC,
+    "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC": tinygemm_dx_f16RM_dy_f16RM_w_mx4TC,
 }
 
 _library = None
@@ -976,6 +1128,8 @@ def register() -> None:
     for name, schema in SCHEMAS.items():
         lib.define(name + schema)
         lib.impl(name, _IMPLS[name], "CUDA")
+    for name in AUTOGRAD_OPS:   # (after every define: a kernel resolves its dx op)
+        lib.impl(name, _autograd_kernel(name), "Autograd", with_keyset=True)
     _library = lib
 
 

@@ -260,6 +260,20 @@ TG_API int tg_gemm_w4_plan(const tg_w4_gemm* args, int device);
  * once per call (w4_xprep_kernel) so that the waves can stream them like the weights.  Needs no GPU. */
 TG_API int64_t tg_gemm_w4_workspace_bytes(const tg_w4_gemm* args);
 
+/* The input gradient of the row-major 4-bit GEMM (no counterpart in the reference, which is inference-only):
+ *   dX[a][j] = RNE16( sum_r dY[a][r] * w[r][j] ),  w = RNE16(fma(lut[code], scale, zero)) as tg_gemm_w4's reference numerics /
+ *   tg_dequant_w4 compute it (mx4: fp4[code] * 2^(e - 127), e = 255: NaN); products summed in f32, one rounding.
+ * Same struct as tg_gemm_w4: x = dY [m][wrows], y = dX [m][k]; w / qinfo / lut / qtype / group / inner_k_tiles / w_on_right / w_format
+ * mean what they mean there.  Bint4 words (w_on_right = 1) or the native weights-on-the-left format (w_on_right = 0, TG_WFMT_ROWS); the
+ * reference's Aint4 words (TG_WFMT_M16N8K16) are TG_E_LAYOUT (repack with tg_unpack_int4 + tg_convert_to_Bint4), as are fragment-order
+ * layouts.  One problem (batch > 1: TG_E_SHAPE), no bias / norm_weight / epilogue (TG_E_FUSION); `numerics` is accepted and ignored (the
+ * weights are the reference's in every setting).  `workspace`: f32 partial tiles of a split over the weight rows when the (m x k) tiles do
+ * not fill the chip, summed in a fixed order (the same bits call to call); with less than tg_gemm_w4_dx_workspace_bytes the call runs
+ * unsplit (slower, same result contract).  Added without an ABI version bump: callers probe for the symbol. */
+TG_API int tg_gemm_w4_dx(const tg_w4_gemm* args, int device, tg_stream_t stream);
+/* Bytes of workspace with which tg_gemm_w4_dx splits (0: it does not; negative: the TG_E_* code tg_gemm_w4_dx would return).  No GPU. */
+TG_API int64_t tg_gemm_w4_dx_workspace_bytes(const tg_w4_gemm* args);
+
 /* out[wrows][k] (16-bit, row-major) = the dequantised weights of a Bint4-packed tensor (also the native weights-on-the-left format,
  * which holds the same words): w = RNE16(fma(lut[row][code], scale[g][row], zero[g][row])), the reference's per-element formula
  * (MatrixLayoutB.cuh:1042-1046; int4: code - 8) -- what quantize.py:612-637 (anyq_dequantize_tensor) computes op by op on unpacked codes.  For MANY
