@@ -2,7 +2,9 @@
 // C ABI fills in (GemmParams) and the entry points of the kernel families' launch paths (namespace tgx).
 //
 // The library is built from one translation unit per kernel family (any4_amd/build.py compiles them in parallel):
-//   tinygemm_hip.hip   the C ABI, validation, dispatch (launch_w4), packers / converters, 16-bit and 8-bit weights, decode glue
+//   tinygemm_hip.hip   the C ABI, validation (check_gemm), GemmParams (make_params), dispatch (launch_w4, launch_w8); its kernels:
+//                        w8_gemm_kernel (w8_gemm.cuh), f16_gemm_kernel (f16_gemm.cuh), packers / converters / dequantisers (tg_convert.cuh),
+//                        decode glue (decode_glue.cuh), peer gather (peer_gather.cuh)
 //   tg_splitk.hip      w4_gemm_kernel            (w4_gemm.cuh)
 //   tg_stream.hip      w4_gemm_stream_kernel     (w4_gemm_stream.cuh)      compiled once per 16-bit type (-DTG_TU_F16)
 //   tg_pair.hip        w4_gemm_pair_kernel       (w4_gemm_pair.cuh)        compiled once per 16-bit type
@@ -298,6 +300,25 @@ inline int launch_status() {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
+inline int group_shift(int g) { return g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8; }  // log2 of a validated qGroupSize
+
+// Every kernel family has a parameter block of its own (its layout is that kernel's ABI), and each repeats part of GemmParams under the
+// same names.  copy_call assigns, of the fields listed, those the destination has: the operands, the problem's sizes and group geometry,
+// the batch strides, the bias, the fused stages, the fragment-order flags and `dry`.  What a family derives or overrides it sets afterwards.
+template <typename D, typename F>
+auto assign_if_member(D& d, F f, int) -> decltype(f(d)) { f(d); }
+template <typename D, typename F>
+void assign_if_member(D&, F, long) {}
+template <typename D>
+void copy_call(D& d, const GemmParams& p) {
+#define TG_COPY(f) assign_if_member(d, [&](auto& t) -> decltype((void)(t.f = p.f)) { t.f = p.f; }, 0)
+  TG_COPY(x); TG_COPY(w); TG_COPY(qinfo); TG_COPY(lut); TG_COPY(y);
+  TG_COPY(m); TG_COPY(wrows); TG_COPY(k); TG_COPY(ntiles); TG_COPY(ksuper); TG_COPY(gshift); TG_COPY(ngroups); TG_COPY(qtype);
+  TG_COPY(stride_x); TG_COPY(stride_w); TG_COPY(stride_qinfo); TG_COPY(stride_lut); TG_COPY(stride_y);
+  TG_COPY(bias); TG_COPY(stride_bias); TG_COPY(bias_row_stride);
+  TG_COPY(norm_w); TG_COPY(norm_eps); TG_COPY(epilogue); TG_COPY(x_tc); TG_COPY(y_tc); TG_COPY(dry);
+#undef TG_COPY
+}
 
 // Kernels that address LDS from offset 0 (lookup tables at the start of the dynamic region) and / or need more than 64 KiB
 // of dynamic LDS: once per device, check that the kernel has no static LDS (the dynamic region then starts at 0) and raise

@@ -96,12 +96,9 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
   const int g = 1 << p.gshift;
   const int gps = g == 32 ? 2 : 1;
   GemvParams gp;
-  gp.x = p.x; gp.w = p.w; gp.qinfo = p.qinfo; gp.lut = p.lut; gp.y = p.y; gp.bias = p.bias; gp.norm_w = p.norm_w;
-  gp.stride_x = p.stride_x; gp.stride_w = p.stride_w; gp.stride_qinfo = p.stride_qinfo; gp.stride_lut = p.stride_lut;
-  gp.stride_y = p.stride_y; gp.stride_bias = p.stride_bias; gp.bias_row_stride = p.bias_row_stride;
-  gp.m = p.m; gp.wrows = p.wrows; gp.k = p.k; gp.ntiles = p.ntiles; gp.ksuper = p.ksuper; gp.qtype = p.qtype;
+  copy_call(gp, p);
   gp.sg_shift = g <= 64 ? 0 : g == 128 ? 1 : 2;
-  gp.norm_eps = p.norm_eps; gp.epilogue = p.epilogue; gp.trace = nullptr;
+  gp.trace = nullptr;
 #ifndef TG_GEMV_CM
 #define TG_GEMV_CM 1
 #endif

@@ -95,40 +95,79 @@ int launch_pair_m(PairParams& pp, unsigned lds, hipStream_t st, bool xg, int m, 
   }
 }
 
+// ---- what the three launch paths below share: how PairParams is filled from a call ---------------------------------------------
+
+// Group geometry.  A group covers nsg whole super-tiles (g >= 16 I k) or a super-tile holds gps groups; a wave's slice of k (spw
+// super-tiles: an eighth of the units of nsg) never cuts a group.
+struct PairGroups {
+  int gps, nsg;
+};
+template <int I>
+PairGroups pair_groups(const GemmParams& p, PairParams& pp) {
+  const int g = 1 << p.gshift;
+  const PairGroups r = {g >= 16 * I ? 1 : (16 * I) / g, g >= 16 * I ? g / (16 * I) : 1};
+  const int units = p.ksuper / r.nsg;
+  pp.spw = ((units + 7) / 8) * r.nsg;
+  pp.nsg_shift = 0;
+  while ((1 << pp.nsg_shift) < r.nsg) ++pp.nsg_shift;
+  pp.gch_mask = g / 32 - 1;
+  return r;
+}
+
+// mx4: exponent blocks of 16 bytes per row, read at 4-byte alignment (w4_gemm_pair.cuh, e_request)
+// (a slice that starts off a 4-byte boundary loses up to 3 bytes of its one block)
+inline bool mx4_blocks_fit(const GemmParams& p, const PairParams& pp, int gps) {
+  return !(p.ngroups < 16 || p.ngroups % 4 != 0 || ((pp.spw * gps) % 4 != 0 && pp.spw * gps > 12));
+}
+
+// LDS plan, in this order: the pair table (64 KiB; mx4 converts its weights in registers, v_cvt_scalef32_pk_bf16_fp4: no table, the
+// LDS starts with the activations) | x_bytes of activations and a zero piece of one super-tile | the activation sums per group (mx4:
+// no zero point, no sums) | the waves' partial sums.  red_alias: the partial sums reuse the table's LDS instead (`alias`: always;
+// `alias_if_large`: when the plan would not leave room for two workgroups per CU, 80 KiB).  Returns the dynamic LDS of the launch.
+template <int I, bool QMX>
+unsigned pair_lds_plan(const GemmParams& p, PairParams& pp, int x_bytes, bool alias, bool alias_if_large) {
+  pp.lds_x = QMX ? 0 : 65536;
+  pp.lds_xs = (pp.lds_x + x_bytes + 32 * I + 15) & ~15;
+  pp.lds_red = (pp.lds_xs + (QMX ? 0 : p.ngroups * pp.xs_rows * 4) + 15) & ~15;
+  unsigned lds = (unsigned)pp.lds_red + (unsigned)(8 * 2 * pp.rused * pp.red_lanes * 4);
+  pp.red_alias = alias || (alias_if_large && lds > 80u * 1024u);
+  if (pp.red_alias) {
+    lds = (unsigned)pp.lds_red;
+    pp.lds_red = 0;
+  }
+  return lds;
+}
+
+// Workspace = [batch][xrows k 2 bytes] arranged activations, then [batch][groups][xs_rows] f32 sums (w4_xprep_kernel writes both).
+// Reports the bytes in p.ws_need; false: the caller did not bring them.
+inline bool pair_workspace(GemmParams& p, PairParams& pp, int xrows, int64_t batch) {
+  pp.stride_xp = (int64_t)xrows * p.k * 2;
+  pp.stride_xsum = ((int64_t)p.ngroups * pp.xs_rows * 4 + 15) & ~(int64_t)15;
+  const int64_t need = batch * (pp.stride_xp + pp.stride_xsum);
+  p.ws_need = need;
+  if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return false;
+  pp.xp = p.ws;
+  pp.xsum = p.ws + batch * pp.stride_xp;
+  return true;
+}
+
 template <typename DT, int I, bool QMX>
 int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
   constexpr int RW = 64;
-  const int g = 1 << p.gshift;
-  const int gps = g >= 16 * I ? 1 : (16 * I) / g;
   const int mregs = p.m <= 8 ? 4 : 16;  // accumulator registers of a row set (8 or 32 activation rows per pass)
   const int ma = 2 * mregs;
   PairParams pp;
-  pp.x = p.x; pp.w = p.w; pp.qinfo = p.qinfo; pp.lut = p.lut; pp.y = p.y;
-  pp.m = p.m; pp.wrows = p.wrows; pp.k = p.k; pp.ntiles = p.ntiles; pp.ksuper = p.ksuper;
-  pp.gshift = p.gshift; pp.ngroups = p.ngroups; pp.qtype = p.qtype;
-  const int nsg = g >= 16 * I ? g / (16 * I) : 1;  // super-tiles per group
-  const int units = p.ksuper / nsg;
-  pp.spw = ((units + 7) / 8) * nsg;
-  pp.nsg_shift = 0;
-  while ((1 << pp.nsg_shift) < nsg) ++pp.nsg_shift;
-  pp.gch_mask = g / 32 - 1;
+  copy_call(pp, p);
+  pp.y_tiles = (p.wrows + 15) / 16;
+  const auto [gps, nsg] = pair_groups<I>(p, pp);
   const int mrows = p.m < ma ? p.m : ma;
   pp.rused = mrows < 4 ? mrows : mregs;
   pp.xs_rows = mrows <= 4 ? 4 : ma;
   pp.red_lanes = mrows <= 4 ? 32 : 64;
   pp.x_pitch = p.k * 2 + 16;
-  pp.lds_x = QMX ? 0 : 65536;  // mx4 converts its weights in registers (v_cvt_scalef32_pk_bf16_fp4): no table, the LDS starts with the activations
-  pp.lds_xs = (pp.lds_x + mrows * pp.x_pitch + 32 * I + 15) & ~15;  // staged rows + a zero piece of one super-tile
-  pp.lds_red = (pp.lds_xs + (QMX ? 0 : p.ngroups * pp.xs_rows * 4) + 15) & ~15;  // mx4: no zero point, no activation sums
-  pp.red_alias = !QMX && mrows > 4;  // 16 KiB and more of partial sums: reuse the table's LDS instead
-  unsigned lds = (unsigned)pp.lds_red + (unsigned)(8 * 2 * pp.rused * pp.red_lanes * 4);
-  if (pp.red_alias) {
-    lds = (unsigned)pp.lds_red;
-    pp.lds_red = 0;
-  }
-  // mx4: exponent blocks of 16 bytes per row, read at 4-byte alignment (w4_gemm_pair.cuh, e_request)
-  // (a slice that starts off a 4-byte boundary loses up to 3 bytes of its one block)
-  if (QMX && (p.ngroups < 16 || p.ngroups % 4 != 0 || ((pp.spw * gps) % 4 != 0 && pp.spw * gps > 12))) return TG_PAIR_NA;
+  // the staged rows; 16 KiB and more of partial sums (more than four rows) reuse the table's LDS
+  unsigned lds = pair_lds_plan<I, QMX>(p, pp, mrows * pp.x_pitch, !QMX && mrows > 4, false);
+  if (QMX && !mx4_blocks_fit(p, pp, gps)) return TG_PAIR_NA;
   // fused RMSNorm: done in the workgroup's own staging of the whole activation block (its partial sums borrow the activation-sum
   // area, which mx4 does not have); the workspace variant would need it in the pre-pass
   if (p.norm_w && (QMX || lds > 80u * 1024u || p.m > ma)) return TG_PAIR_NA;
@@ -141,23 +180,10 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
     if (mregs != 4 || p.m > ma) return TG_PAIR_NA;
     pp.xw_pitch = 32 * I + 16;
     pp.xw_bytes = (I == 2 ? 16 : 8) * pp.xw_pitch;  // a row for every 2 I lanes of the wave's (unmasked) store
-    pp.lds_xs = (pp.lds_x + 8 * pp.xw_bytes + 32 * I + 15) & ~15;  // 8 buffers + the zero piece
-    pp.lds_red = (pp.lds_xs + (QMX ? 0 : p.ngroups * pp.xs_rows * 4) + 15) & ~15;  // mx4: no zero point, no activation sums
-    lds = (unsigned)pp.lds_red + (unsigned)(8 * 2 * pp.rused * pp.red_lanes * 4);
-    if (lds > 80u * 1024u) pp.red_alias = 1;
+    lds = pair_lds_plan<I, QMX>(p, pp, 8 * pp.xw_bytes, pp.red_alias, true);  // 8 buffers
     if (QMX && pp.red_alias) return TG_PAIR_NA;  // (no table to put the partial sums over; cannot happen: 8 one-KiB buffers + 16 KiB)
-    if (pp.red_alias) {
-      lds = (unsigned)pp.lds_red;
-      pp.lds_red = 0;
-    }
     if (lds > 80u * 1024u) return TG_PAIR_NA;
-    pp.stride_xp = (int64_t)p.m * p.k * 2;
-    pp.stride_xsum = ((int64_t)p.ngroups * pp.xs_rows * 4 + 15) & ~(int64_t)15;
-    const int64_t need = batch * (pp.stride_xp + pp.stride_xsum);
-    p.ws_need = need;
-    if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return TG_PAIR_NA;
-    pp.xp = p.ws;
-    pp.xsum = p.ws + batch * pp.stride_xp;
+    if (!pair_workspace(p, pp, p.m, batch)) return TG_PAIR_NA;
     xg = true;
   }
   pp.rblocks = (p.wrows + RW - 1) / RW;
@@ -171,11 +197,6 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
   pp.items = (int32_t)items;
   // XG item dealing: chunks of consecutive items once every workgroup still gets several chunks
   pp.chunk = items >= (int64_t)TG_PAIR_WGS * TG_XG_CHUNK * 4 ? TG_XG_CHUNK : 1;
-  pp.stride_x = p.stride_x; pp.stride_w = p.stride_w; pp.stride_qinfo = p.stride_qinfo;
-  pp.stride_lut = p.stride_lut; pp.stride_y = p.stride_y;
-  pp.bias = p.bias; pp.stride_bias = p.stride_bias; pp.dry = p.dry;
-  pp.bias_row_stride = p.bias_row_stride; pp.norm_w = p.norm_w; pp.norm_eps = p.norm_eps; pp.epilogue = p.epilogue;
-  pp.x_tc = p.x_tc; pp.y_tc = p.y_tc; pp.y_tiles = (p.wrows + 15) / 16;
   if (xg && !p.dry) {
     const int rc = launch_xprep<DT>(pp, I, ma, batch, st);
     if (rc != 0) return rc;
@@ -218,161 +239,64 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
   return TG_PAIR_NA;
 }
 
-// Aint4 weights (weightOnRight = false) on the pair-table kernel: 32 weight rows per work item, v_mfma_f32_16x16x32,
-// activations always through the workspace (one pass of at most 8 rows).
-template <typename DT, int I, bool QMX>
-int launch_pair_a(GemmParams& p, int64_t batch, hipStream_t st) {
-  if constexpr (I < 2) return TG_PAIR_NA;  // one 16-k tile per word set: no word pair for a 32-k MFMA step
+// The 16x16x32 structure: 32 weight rows per work item, v_mfma_f32_16x16x32, a duplicated table, the activations of ONE pass -- all
+// m <= 16 rows -- always through the workspace and from there straight into the MFMA operand (LDS only holds a zero piece).
+//   LA = 1  Aint4 weights (weightOnRight = false): row-major operands only.
+//   LA = 2  Bint4 weights with 9 ... 16 activation rows: one packed word is one B operand, 4 vector ops per word.  (The 32x32x16
+//           kernel holds 8 rows per pass; a second pass would stream the weights twice.)
+template <typename DT, int I, bool QMX, int LA>
+int launch_pair_la(GemmParams& p, int64_t batch, hipStream_t st) {
+  if constexpr (LA == 1 && I < 2) return TG_PAIR_NA;  // one 16-k tile per word set: no word pair for a 32-k MFMA step
   else {
-  if (p.m > 16 || p.x_tc || p.y_tc || p.norm_w || p.epilogue) return TG_PAIR_NA;
-  const int g = 1 << p.gshift;
-  const int gps = g >= 16 * I ? 1 : (16 * I) / g;
+  constexpr bool B = LA == 2;
+  constexpr int RING = B ? TG_PAIR_RB16 : TG_PAIR_R;  // the group length with fixed boundaries in the unrolled round
+  if (p.m > 16 || p.norm_w || p.epilogue || (!B && (p.x_tc || p.y_tc))) return TG_PAIR_NA;
   PairParams pp;
-  pp.x_tc = pp.y_tc = 0; pp.y_tiles = 0;
-  pp.bias_row_stride = p.bias_row_stride; pp.norm_w = nullptr; pp.norm_eps = 0.f; pp.epilogue = 0;
-  pp.x = p.x; pp.w = p.w; pp.qinfo = p.qinfo; pp.lut = p.lut; pp.y = p.y;
-  pp.m = p.m; pp.wrows = p.wrows; pp.k = p.k; pp.ntiles = p.ntiles; pp.ksuper = p.ksuper;
-  pp.gshift = p.gshift; pp.ngroups = p.ngroups; pp.qtype = p.qtype;
-  const int nsg = g >= 16 * I ? g / (16 * I) : 1;
-  const int units = p.ksuper / nsg;
-  pp.spw = ((units + 7) / 8) * nsg;
-  pp.nsg_shift = 0;
-  while ((1 << pp.nsg_shift) < nsg) ++pp.nsg_shift;
-  pp.gch_mask = g / 32 - 1;
-  if (QMX && (p.ngroups < 16 || p.ngroups % 4 != 0 || ((pp.spw * gps) % 4 != 0 && pp.spw * gps > 12))) return TG_PAIR_NA;
+  copy_call(pp, p);
+  pp.y_tiles = (p.wrows + 15) / 16;
+  const auto [gps, nsg] = pair_groups<I>(p, pp);
+  if (QMX && !mx4_blocks_fit(p, pp, gps)) return TG_PAIR_NA;
   const int mrows = p.m;
   pp.rused = mrows < 4 ? mrows : 4;
   pp.xs_rows = mrows <= 4 ? 4 : mrows <= 8 ? 8 : 16;
   pp.red_lanes = mrows <= 8 ? 32 : 64;  // lanes 0..31 hold activation rows 0..7
   pp.x_pitch = 0;
-  pp.lds_x = QMX ? 0 : 65536;
-  pp.xw_pitch = 0;  // the lanes' MFMA operands come straight from the workspace: LDS only holds a zero piece here
-  pp.xw_bytes = 0;
-  pp.lds_xs = (pp.lds_x + 32 * I + 15) & ~15;
-  pp.lds_red = (pp.lds_xs + (QMX ? 0 : p.ngroups * pp.xs_rows * 4) + 15) & ~15;  // mx4: no zero point, no activation sums
-  unsigned lds = (unsigned)pp.lds_red + (unsigned)(8 * 2 * pp.rused * pp.red_lanes * 4);
-  pp.red_alias = lds > 80u * 1024u;
-  if (pp.red_alias) {
-    lds = (unsigned)pp.lds_red;
-    pp.lds_red = 0;
-  }
-  if (lds > 80u * 1024u) return TG_PAIR_NA;
-  pp.stride_xp = (int64_t)(p.m + 1) * p.k * 2;  // + a zero row
-  pp.stride_xsum = ((int64_t)p.ngroups * pp.xs_rows * 4 + 15) & ~(int64_t)15;
-  const int64_t need = batch * (pp.stride_xp + pp.stride_xsum);
-  pp.rblocks = (p.wrows + 31) / 32;
-  pp.cblocks = 1;
-  const int64_t items = (int64_t)pp.rblocks * batch;
-  if (items > INT32_MAX || items < TG_PAIR_MIN_ITEMS) return TG_PAIR_NA;
-  p.ws_need = need;
-  if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return TG_PAIR_NA;
-  pp.xp = p.ws;
-  pp.xsum = p.ws + batch * pp.stride_xp;
-  pp.items = (int32_t)items;
-  pp.chunk = 1;  // plain round-robin dealing (chunks of consecutive items measured slower for the 32-row items of this layout)
-  pp.stride_x = p.stride_x; pp.stride_w = p.stride_w; pp.stride_qinfo = p.stride_qinfo;
-  pp.stride_lut = p.stride_lut; pp.stride_y = p.stride_y;
-  pp.bias = p.bias; pp.stride_bias = p.stride_bias; pp.dry = p.dry;
-  if (!p.dry) {
-    const int rc = launch_xprep<DT>(pp, I, 16, batch, st, 1);
-    if (rc != 0) return rc;
-  }
-  if (gps == 1) {
-    if (TG_PAIR_NSG2 && nsg == 1) return launch_pair_k<DT, I, 1, 4, QMX, 1, true, true>(pp, lds, st);
-    if (TG_PAIR_NSG2 && nsg == TG_PAIR_R) return launch_pair_k<DT, I, 1, 4, QMX, TG_PAIR_R, true, true>(pp, lds, st);
-    return launch_pair_k<DT, I, 1, 4, QMX, 0, true, true>(pp, lds, st);
-  }
-  if constexpr (I >= 4) {
-    if (gps == 2) return launch_pair_k<DT, I, 2, 4, QMX, 0, true, true>(pp, lds, st);
-  }
-  return TG_PAIR_NA;
-  }
-}
-
-// Bint4 weights with 9 ... 16 activation rows: the 16x16x32 structure of the A-side kernel (32-row work items, duplicated
-// table, activations of one pass -- all m <= 16 rows -- straight from the workspace into the MFMA operand) on B-layout words:
-// one packed word is one B operand, 4 vector ops per word.  (The 32x32x16 kernel holds 8 rows per pass; a second pass would
-// stream the weights twice.)
-template <typename DT, int I, bool QMX>
-int launch_pair_b16(GemmParams& p, int64_t batch, hipStream_t st) {
-  if (p.m > 16 || p.norm_w || p.epilogue) return TG_PAIR_NA;
-  const int g = 1 << p.gshift;
-  const int gps = g >= 16 * I ? 1 : (16 * I) / g;
-  PairParams pp;
-  pp.x_tc = p.x_tc; pp.y_tc = p.y_tc; pp.y_tiles = (p.wrows + 15) / 16;
-  pp.bias_row_stride = p.bias_row_stride; pp.norm_w = nullptr; pp.norm_eps = 0.f; pp.epilogue = 0;
-  pp.x = p.x; pp.w = p.w; pp.qinfo = p.qinfo; pp.lut = p.lut; pp.y = p.y;
-  pp.m = p.m; pp.wrows = p.wrows; pp.k = p.k; pp.ntiles = p.ntiles; pp.ksuper = p.ksuper;
-  pp.gshift = p.gshift; pp.ngroups = p.ngroups; pp.qtype = p.qtype;
-  const int nsg = g >= 16 * I ? g / (16 * I) : 1;
-  const int units = p.ksuper / nsg;
-  pp.spw = ((units + 7) / 8) * nsg;
-  pp.nsg_shift = 0;
-  while ((1 << pp.nsg_shift) < nsg) ++pp.nsg_shift;
-  pp.gch_mask = g / 32 - 1;
-  if (QMX && (p.ngroups < 16 || p.ngroups % 4 != 0 || ((pp.spw * gps) % 4 != 0 && pp.spw * gps > 12))) return TG_PAIR_NA;
-  const int mrows = p.m;
-  pp.rused = mrows < 4 ? mrows : 4;
-  pp.xs_rows = mrows <= 4 ? 4 : mrows <= 8 ? 8 : 16;
-  pp.red_lanes = mrows <= 8 ? 32 : 64;  // lanes 0..31 hold activation rows 0..7
-  pp.x_pitch = 0;
-  pp.lds_x = QMX ? 0 : 65536;
   pp.xw_pitch = 0;
   pp.xw_bytes = 0;
-  pp.lds_xs = (pp.lds_x + 32 * I + 15) & ~15;
-  pp.lds_red = (pp.lds_xs + (QMX ? 0 : p.ngroups * pp.xs_rows * 4) + 15) & ~15;
-  unsigned lds = (unsigned)pp.lds_red + (unsigned)(8 * 2 * pp.rused * pp.red_lanes * 4);
-  pp.red_alias = lds > 80u * 1024u;
-  if (pp.red_alias) {
-    lds = (unsigned)pp.lds_red;
-    pp.lds_red = 0;
-  }
+  const unsigned lds = pair_lds_plan<I, QMX>(p, pp, 0, false, true);
   if (lds > 80u * 1024u) return TG_PAIR_NA;
-  pp.stride_xp = (int64_t)(p.m + 1) * p.k * 2;  // + a zero row
-  pp.stride_xsum = ((int64_t)p.ngroups * pp.xs_rows * 4 + 15) & ~(int64_t)15;
-  const int64_t need = batch * (pp.stride_xp + pp.stride_xsum);
   pp.rblocks = (p.wrows + 31) / 32;
   pp.cblocks = 1;
   const int64_t items = (int64_t)pp.rblocks * batch;
-  if (items > INT32_MAX || items < 2 * TG_PAIR_MIN_ITEMS) return TG_PAIR_NA;  // (32-row items: two per 64-row item of the other kernel)
-  p.ws_need = need;
-  if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return TG_PAIR_NA;
-  pp.xp = p.ws;
-  pp.xsum = p.ws + batch * pp.stride_xp;
+  // (LA = 2: 32-row items, two per 64-row item of the 32x32x16 kernel that TG_PAIR_MIN_ITEMS was measured on)
+  if (items > INT32_MAX || items < (B ? 2 : 1) * TG_PAIR_MIN_ITEMS) return TG_PAIR_NA;
+  if (!pair_workspace(p, pp, p.m + 1, batch)) return TG_PAIR_NA;  // + a zero row
   pp.items = (int32_t)items;
-  pp.chunk = items >= (int64_t)TG_PAIR_WGS * TG_B16_CHUNK * 4 ? TG_B16_CHUNK : 1;
-  pp.stride_x = p.stride_x; pp.stride_w = p.stride_w; pp.stride_qinfo = p.stride_qinfo;
-  pp.stride_lut = p.stride_lut; pp.stride_y = p.stride_y;
-  pp.bias = p.bias; pp.stride_bias = p.stride_bias; pp.dry = p.dry;
+  // Aint4: plain round-robin dealing (chunks of consecutive items measured slower for the 32-row items of this layout)
+  pp.chunk = B && items >= (int64_t)TG_PAIR_WGS * TG_B16_CHUNK * 4 ? TG_B16_CHUNK : 1;
   if (!p.dry) {
     const int rc = launch_xprep<DT>(pp, I, 16, batch, st, 1);
     if (rc != 0) return rc;
   }
   if (gps == 1) {
-    if (TG_PAIR_NSG2 && nsg == 1) return launch_pair_k<DT, I, 1, 4, QMX, 1, true, 2>(pp, lds, st);
-    if (TG_PAIR_NSG2 && nsg == TG_PAIR_RB16) return launch_pair_k<DT, I, 1, 4, QMX, TG_PAIR_RB16, true, 2>(pp, lds, st);
-    return launch_pair_k<DT, I, 1, 4, QMX, 0, true, 2>(pp, lds, st);
+    if (TG_PAIR_NSG2 && nsg == 1) return launch_pair_k<DT, I, 1, 4, QMX, 1, true, LA>(pp, lds, st);
+    if (TG_PAIR_NSG2 && nsg == RING) return launch_pair_k<DT, I, 1, 4, QMX, RING, true, LA>(pp, lds, st);
+    return launch_pair_k<DT, I, 1, 4, QMX, 0, true, LA>(pp, lds, st);
   }
   if constexpr (I >= 4) {
-    if (gps == 2) return launch_pair_k<DT, I, 2, 4, QMX, 0, true, 2>(pp, lds, st);
+    if (gps == 2) return launch_pair_k<DT, I, 2, 4, QMX, 0, true, LA>(pp, lds, st);
   }
-  if constexpr (I >= 8) {
-    if (gps == 4) return launch_pair_k<DT, I, 4, 4, QMX, 0, true, 2>(pp, lds, st);
+  return TG_PAIR_NA;  // (four groups per super-tile are innerKTiles 8, which has no 16x16x32 instantiation: tgx::pair_b16)
   }
-  return TG_PAIR_NA;
 }
 
 template <typename DT, int I>
 int pair_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
   return qmx ? launch_pair<DT, I, true>(p, batch, st) : launch_pair<DT, I, false>(p, batch, st);
 }
-template <typename DT, int I>
-int pair_a_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return qmx ? launch_pair_a<DT, I, true>(p, batch, st) : launch_pair_a<DT, I, false>(p, batch, st);
-}
-template <typename DT, int I>
-int pair_b16_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return qmx ? launch_pair_b16<DT, I, true>(p, batch, st) : launch_pair_b16<DT, I, false>(p, batch, st);
+template <typename DT, int I, int LA>
+int pair_la_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
+  return qmx ? launch_pair_la<DT, I, true, LA>(p, batch, st) : launch_pair_la<DT, I, false, LA>(p, batch, st);
 }
 }  // namespace
 namespace tgx {
@@ -380,10 +304,10 @@ int TG_TU_SUF(pair)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t s
   return I == 2 ? pair_q<TG_TU_DT, 2>(qmx, p, batch, st) : I == 4 ? pair_q<TG_TU_DT, 4>(qmx, p, batch, st) : pair_q<TG_TU_DT, 8>(qmx, p, batch, st);
 }
 int TG_TU_SUF(pair_a)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return I == 1 ? pair_a_q<TG_TU_DT, 1>(qmx, p, batch, st) : I == 2 ? pair_a_q<TG_TU_DT, 2>(qmx, p, batch, st) : pair_a_q<TG_TU_DT, 4>(qmx, p, batch, st);
+  return I == 1 ? pair_la_q<TG_TU_DT, 1, 1>(qmx, p, batch, st) : I == 2 ? pair_la_q<TG_TU_DT, 2, 1>(qmx, p, batch, st) : pair_la_q<TG_TU_DT, 4, 1>(qmx, p, batch, st);
 }
 int TG_TU_SUF(pair_b16)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
   // (innerKTiles 8 on the 16x16x32 tiles compiled with > 100 bytes of scratch per lane: not instantiated)
-  return I == 2 ? pair_b16_q<TG_TU_DT, 2>(qmx, p, batch, st) : I == 4 ? pair_b16_q<TG_TU_DT, 4>(qmx, p, batch, st) : (int)TG_PAIR_NA;
+  return I == 2 ? pair_la_q<TG_TU_DT, 2, 2>(qmx, p, batch, st) : I == 4 ? pair_la_q<TG_TU_DT, 4, 2>(qmx, p, batch, st) : (int)TG_PAIR_NA;
 }
 }  // namespace tgx

@@ -30,9 +30,7 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
   const int g = 1 << p.gshift;
   const int nsg = g >= 16 * I ? g / (16 * I) : 1;
   Pair16Params pp;
-  pp.x = p.x; pp.w = p.w; pp.qinfo = p.qinfo; pp.lut = p.lut; pp.y = p.y;
-  pp.m = p.m; pp.wrows = p.wrows; pp.k = p.k; pp.ntiles = p.ntiles; pp.ksuper = p.ksuper;
-  pp.gshift = p.gshift; pp.ngroups = p.ngroups; pp.qtype = p.qtype;
+  copy_call(pp, p);
   pp.gch_mask = g / 32 - 1;
   pp.lds_x = 65536;
   const int64_t wgs = (int64_t)((p.wrows + 15) / 16) * batch;
@@ -62,11 +60,7 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
   pp.phases = phases;
   pp.ksuper_p = p.ksuper / phases;
   pp.spw = ((pp.ksuper_p / nsg + 15) / 16) * nsg;
-  pp.stride_x = p.stride_x; pp.stride_w = p.stride_w; pp.stride_qinfo = p.stride_qinfo;
-  pp.stride_lut = p.stride_lut; pp.stride_y = p.stride_y;
-  pp.bias = p.bias; pp.stride_bias = p.stride_bias;
-  pp.bias_row_stride = p.bias_row_stride; pp.norm_w = p.norm_w; pp.norm_eps = p.norm_eps; pp.epilogue = p.epilogue;
-  pp.x_tc = p.x_tc; pp.y_tc = p.y_tc; pp.y_tiles = (p.wrows + 15) / 16;
+  pp.y_tiles = (p.wrows + 15) / 16;
   if (p.dry) return TG_PLAN_PAIR;
   const dim3 grid((unsigned)((p.wrows + 15) / 16), (unsigned)batch);
 #if GEMV_TRACE
@@ -126,11 +120,8 @@ int launch_pair16_loop(const GemmParams& p, int64_t batch, hipStream_t st) {
   const int per = (tiles + cus - 1) / cus;
   if (per > TG_P16_LOOP_MAX_TILES || per > 32) return TG_PAIR_NA;
   Pair16LoopParams pp;
-  pp.x = p.x; pp.w = p.w; pp.qinfo = p.qinfo; pp.lut = p.lut; pp.y = p.y; pp.bias = p.bias; pp.bias_row_stride = p.bias_row_stride;
-  pp.m = p.m; pp.wrows = p.wrows; pp.k = p.k; pp.ntiles = p.ntiles; pp.ksuper = p.ksuper; pp.gshift = p.gshift; pp.ngroups = p.ngroups; pp.qtype = p.qtype;
+  copy_call(pp, p);
   pp.tbase = tiles / cus; pp.trem = tiles % cus;
-  pp.epilogue = p.epilogue;
-  pp.norm_w = p.norm_w; pp.norm_eps = p.norm_eps;
   pp.lds_red = 65536;
   pp.lds_lut = 65536 + 2 * 16384;
   pp.lds_nrm = pp.lds_lut + (p.qtype == TG_Q_ANY4_ROWWISE ? per * 544 : 0);

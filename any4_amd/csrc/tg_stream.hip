@@ -115,14 +115,9 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
   constexpr int UNIT = LAYOUT_A ? 64 : 128;
   constexpr int RPW = 16;  // weight rows per wave
   StreamParams sp;
-  sp.x = p.x; sp.w = p.w; sp.qinfo = p.qinfo; sp.lut = p.lut; sp.y = p.y;
-  sp.m = p.m; sp.wrows = p.wrows; sp.k = p.k; sp.ntiles = p.ntiles; sp.ksuper = p.ksuper;
-  sp.gshift = p.gshift; sp.ngroups = p.ngroups; sp.qtype = p.qtype;
+  copy_call(sp, p);
   sp.rowtiles = (p.wrows + RPW - 1) / RPW;
   sp.tiles_per_wave = 1;
-  sp.stride_x = p.stride_x; sp.stride_w = p.stride_w; sp.stride_qinfo = p.stride_qinfo;
-  sp.stride_lut = p.stride_lut; sp.stride_y = p.stride_y;
-  sp.bias = p.bias; sp.stride_bias = p.stride_bias; sp.bias_row_stride = p.bias_row_stride; sp.dry = p.dry;
   const int mrows = p.m < 16 ? p.m : 16;
   const int nunits = (p.k + UNIT - 1) / UNIT;
   const int upg = (1 << p.gshift) / UNIT;

@@ -52,9 +52,7 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   if (QMX && p.ngroups % 16 != 0) return TG_PAIR_NA;  // 16-byte exponent blocks
   if (NCH > 24 && cpg == 2 && !PK) return TG_PAIR_NA;   // (k = 8192, g = 64, unpacked: that instantiation spills four registers)
   XrParams xp;
-  xp.w = p.w; xp.qinfo = p.qinfo; xp.lut = p.lut; xp.y = p.y;
-  xp.m = p.m; xp.wrows = p.wrows; xp.k = p.k; xp.ntiles = p.ntiles; xp.ksuper = p.ksuper;
-  xp.gshift = p.gshift; xp.ngroups = p.ngroups; xp.qtype = p.qtype;
+  copy_call(xp, p);  // (x too: no pre-pass, no workspace -- the kernel arranges the activations itself)
   xp.rblocks = (p.wrows + 63) / 64;
   const int64_t items = (int64_t)xp.rblocks * batch;
 #ifndef TG_XR_MIN_ITEMS_PER_WG
@@ -86,11 +84,8 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   // two tables (WV = 4: one, and the 8 KiB hand-over region behind the sums), the activation sums (mx4: the partial sums only)
   const unsigned lds = QMX ? 32768u : (unsigned)xp.lds_xs + (unsigned)(win ? win->ngroups : p.ngroups) * 64u + (WV == 4 ? 8192u : 0u);
   if (lds > 160u * 1024u) return TG_PAIR_NA;
-  xp.x = p.x; xp.stride_x = p.stride_x; xp.x_tc = p.x_tc;  // (no pre-pass, no workspace: the kernel arranges the activations itself)
   p.ws_need = 0;
-  xp.stride_w = p.stride_w; xp.stride_qinfo = p.stride_qinfo; xp.stride_lut = p.stride_lut; xp.stride_y = p.stride_y;
-  xp.bias = p.bias; xp.stride_bias = p.stride_bias; xp.bias_row_stride = p.bias_row_stride;
-  xp.y_tc = p.y_tc; xp.y_tiles = (p.wrows + 15) / 16; xp.dry = p.dry;
+  xp.y_tiles = (p.wrows + 15) / 16;
   xp.y_f32 = 0;
   if (win) {
     if (p.x_tc || p.y_tc) return TG_PAIR_NA;

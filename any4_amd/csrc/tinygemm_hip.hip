@@ -33,393 +33,8 @@ namespace {
 
 #include "w8_gemm.cuh"
 
-// ---- 16-bit weights (reference TinyGemm_bf16.cu) ---------------------------------------------
-// Same tile/split-K structure; the A operand is gathered dword-wise from the fragment-order
-// tensor (each dword = two adjacent k of one row), no dequantisation.
-struct F16GemmParams {
-  const char* x;
-  const char* w;
-  char* y;
-  int32_t m, wrows, k;
-  int32_t ktiles_padded;  // k-tiles present in the TC tensor (size(1) * I)
-  int32_t inner;          // I
-};
-
-template <typename DT, bool LAYOUT_A, int WAVES, int I>
-__global__ void __launch_bounds__(WAVES * 64) f16_gemm_kernel(const F16GemmParams p) {
-  __shared__ f32x4 s_red[WAVES * 64];
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int i = lane & 15, Q = lane >> 4, r = i & 7;
-  const int rt = blockIdx.x, ct = blockIdx.y;
-  const int row0 = rt * 16, row = row0 + i;
-  const bool row_ok = row < p.wrows;
-  // Lane (i, Q) reads the fragment words of ITS OWN lane slot t = 4 (i & 7) + Q of the m16n8k16 layouts, as stored:
-  // per k-tile the dwords (k0,k1) and (k0+8,k0+9) with k0 = 2Q, so one K-slot (two k-tiles) is the 8 k values
-  // {2Q, 2Q+1, 2Q+8, 2Q+9} + {0, 16} and the X fragment is four dwords at byte offsets 4Q + {0, 16, 32, 48} of the slot
-  // (the mapping of w8_gemm.cuh).  One 16-byte (A16, B16 I = 2) or 8-byte (B16 I = 1) load per k-tile pair / k-tile.
-  const uint32_t* wd = reinterpret_cast<const uint32_t*>(p.w);
-  const int xrow = min(ct * 16 + i, p.m - 1);
-  const bool xcol = ct * 16 + i < p.m;
-  const int ktiles = p.k >> 4;  // k % 32 == 0
-  const int nsteps_total = ktiles >> 1;
-  const int t = 4 * r + Q;
-  f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-  // A ring of F16_RING steps in flight per wave.  Every load is unconditional per lane with clamped addresses and nothing of a step is touched
-  // before it is consumed (round 6: a load under a lane mask makes hipcc wait vmcnt(0) right behind it -- every step then exposed the whole
-  // memory latency); rows / columns beyond the problem are masked at the consumer.
-  constexpr int F16_RING = 4;
-  struct Step { u32x4 w0, w1, x; };
-  const int rt_c = rt;  // (row tiles are never out of range: the grid is exact; rows beyond wrows within the last tile are masked below)
-  auto load_step = [&](int s, Step& st) {
-    const int sc = min(s, nsteps_total - 1);
-    if constexpr (LAYOUT_A) {
-      // [mT][kT][32][8 halfs] = 4 dwords per lane slot: (m0;k0,k1) (m1;k0,k1) (m0;k8,k9) (m1;k8,k9)
-      st.w0 = *reinterpret_cast<const u32x4*>(wd + (((int64_t)rt_c * p.ktiles_padded + 2 * sc) * 32 + t) * 4);
-      st.w1 = *reinterpret_cast<const u32x4*>(wd + (((int64_t)rt_c * p.ktiles_padded + 2 * sc + 1) * 32 + t) * 4);
-    } else {
-      // [nT][kT/I][32][4 I halfs]: per k-tile the dwords (k0,k1) (k8,k9)
-      const int tile = min(2 * rt + (i >> 3), (p.wrows + 7) / 8 - 1);
-      if constexpr (I == 2) {
-        st.w0 = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wd + (((int64_t)tile * (p.ktiles_padded / 2) + sc) * 32 + t) * 4));
-        st.w1 = st.w0;
-      } else {
-        const u32x2 v0 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wd + (((int64_t)tile * p.ktiles_padded + 2 * sc) * 32 + t) * 2));
-        const u32x2 v1 = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(wd + (((int64_t)tile * p.ktiles_padded + 2 * sc + 1) * 32 + t) * 2));
-        st.w0 = u32x4{v0[0], v0[1], v1[0], v1[1]};
-        st.w1 = st.w0;
-      }
-    }
-    st.x = *reinterpret_cast<const u32x4*>(p.x + ((int64_t)xrow * p.k + 32 * sc) * 2 + 16 * Q);   // dwords 4Q ... 4Q + 3: transposed at the consumer
-  };
-  auto compute_step = [&](const Step& st) {
-    u32x4 a;
-    if constexpr (LAYOUT_A) {
-      const int h = i >> 3;
-      a = u32x4{h ? st.w0[1] : st.w0[0], h ? st.w0[3] : st.w0[2], h ? st.w1[1] : st.w1[0], h ? st.w1[3] : st.w1[2]};
-    } else {
-      a = st.w0;
-    }
-#pragma unroll
-    for (int e = 0; e < 4; ++e) a[e] = row_ok ? a[e] : 0u;
-    const u32x4 xt = transpose_rows4(st.x);
-    const u32x4 xv = {xcol ? xt[0] : 0u, xcol ? xt[1] : 0u, xcol ? xt[2] : 0u, xcol ? xt[3] : 0u};
-    acc = DT::mfma(a, xv, acc);
-  };
-  {
-    // this wave's steps: wave, wave + WAVES, ...: nw of them.  Rounds of F16_RING steps whose refills are all in range run without a branch
-    // around a load (exact vmcnt); the last round(s) only consume (a refill past the end would be real work for the vector-memory path).
-    const int nw = (nsteps_total - wave + WAVES - 1) / WAVES;
-    Step ring[F16_RING];
-#pragma unroll
-    for (int j = 0; j < F16_RING; ++j) load_step(wave + j * WAVES, ring[j]);   // (clamped: a wave with fewer steps loads its last one again)
-    int base = 0;
-    for (; base + 2 * F16_RING <= nw; base += F16_RING) {
-#pragma unroll
-      for (int j = 0; j < F16_RING; ++j) {
-        compute_step(ring[j]);
-        load_step(wave + (base + F16_RING + j) * WAVES, ring[j]);
-      }
-    }
-    // the remainder: fewer than two rounds; refills only where a step exists
-#pragma unroll
-    for (int r = 0; r < 2; ++r) {
-#pragma unroll
-      for (int j = 0; j < F16_RING; ++j) {
-        const int jj = base + r * F16_RING + j;
-        if (jj < nw) {
-          compute_step(ring[j]);
-          if (jj + F16_RING < nw) load_step(wave + (jj + F16_RING) * WAVES, ring[j]);
-        }
-      }
-    }
-  }
-  s_red[wave * 64 + lane] = acc;
-  __syncthreads();
-  if (tid < 256) {
-    const int c = tid >> 4, rr = tid & 15;
-    const float* red = reinterpret_cast<const float*>(s_red);
-    const int src = (((rr >> 2) * 16 + c) << 2) + (rr & 3);
-    float sum = 0.f;
-#pragma unroll
-    for (int wv = 0; wv < WAVES; ++wv) sum += red[wv * 256 + src];
-    const int col = ct * 16 + c, rowg = row0 + rr;
-    if (col < p.m && rowg < p.wrows) reinterpret_cast<uint16_t*>(p.y)[(int64_t)col * p.wrows + rowg] = DT::from_f32(sum);
-  }
-}
-
-// ---- packing kernels (integer only, bit-exact) -----------------------------------------------
-// One workgroup stages a [ROWS x KB] tile of codes as bytes in LDS with fully coalesced 16-byte
-// reads of the int32 input, then every thread assembles output words from four 2-byte LDS reads
-// and writes them contiguously (the packed tile is contiguous in the output tensor).
-
-// Bint4: tile = 8 rows (one n-tile) x KB k.   ref TinyGemmConvertB.cu:252-308
-template <int I>
-__global__ void __launch_bounds__(256) pack_Bint4_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
-                                                        int64_t n, int64_t k, int64_t ksuper) {
-  constexpr int KB = 512;  // k per workgroup; multiple of 16*I for I <= 8
-  // codes are staged as full 32-bit values: the reference ORs the shifted UNMASKED inputs (TinyGemmConvertB.cu:302-303),
-  // so out-of-range codes must reach the pack expression untouched for the words to stay bit-identical
-  __shared__ uint32_t s_codes[8][KB + 4];
-  const int tid = threadIdx.x;
-  const int64_t nT = blockIdx.y;
-  const int64_t kb0 = (int64_t)blockIdx.x * KB;
-  // load: 8 rows x 512 ints = 1024 x int4
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int idx = it * 256 + tid;
-    const int rr = idx >> 7, c4 = idx & 127;
-    const int64_t row = nT * 8 + rr, kk = kb0 + c4 * 4;
-    int4 v = {0, 0, 0, 0};
-    if (row < n && kk < k) v = *reinterpret_cast<const int4*>(in + row * k + kk);  // k % 32 == 0 -> whole int4 in range
-    *reinterpret_cast<int4*>(&s_codes[rr][c4 * 4]) = v;
-  }
-  __syncthreads();
-  // words of this tile: [kS_local][t][j], KB/(16 I) super-tiles x 32 x I/2 = KB words
-  constexpr int WORDS = KB;  // 8 rows * KB / 8
-#pragma unroll
-  for (int it = 0; it < WORDS / 256; ++it) {
-    const int wi = it * 256 + tid;
-    const int j = wi % (I / 2);
-    const int t = (wi / (I / 2)) & 31;
-    const int ksl = wi / (16 * I);
-    const int64_t ks = kb0 / (16 * I) + ksl;
-    if (ks >= ksuper) continue;
-    const int rr = t >> 2, q = t & 3;
-    const int kl = (ksl * I + 2 * j) * 16 + 2 * q;
-    const uint32_t* src = &s_codes[rr][kl];
-    uint32_t v[8];
-#pragma unroll
-    for (int pr = 0; pr < 4; ++pr) {
-      v[2 * pr] = src[8 * pr];
-      v[2 * pr + 1] = src[8 * pr + 1];
-    }
-    const uint32_t pack = (v[7] << 28) | (v[5] << 24) | (v[3] << 20) | (v[1] << 16) | (v[6] << 12) | (v[4] << 8) | (v[2] << 4) | v[0];
-    out[((nT * ksuper + ks) * 32 + t) * (I / 2) + j] = (int32_t)pack;
-  }
-}
-
-// Aint4: tile = 16 rows (one m-tile) x KB k.   ref TinyGemmConvertA.cu:226-285
-template <int I>
-__global__ void __launch_bounds__(256) pack_Aint4_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out,
-                                                        int64_t m, int64_t k, int64_t ksuper) {
-  constexpr int KB = 256;
-  __shared__ uint32_t s_codes[16][KB + 4];  // full 32-bit codes, see pack_Bint4_kernel
-  const int tid = threadIdx.x;
-  const int64_t mT = blockIdx.y;
-  const int64_t kb0 = (int64_t)blockIdx.x * KB;
-  const bool vec_ok = (k & 3) == 0;
-#pragma unroll
-  for (int it = 0; it < 4; ++it) {
-    const int idx = it * 256 + tid;
-    const int rr = idx >> 6, c4 = idx & 63;
-    const int64_t row = mT * 16 + rr, kk = kb0 + c4 * 4;
-    int4 v = {0, 0, 0, 0};
-    if (row < m) {
-      if (vec_ok && kk + 3 < k) {
-        v = *reinterpret_cast<const int4*>(in + row * k + kk);
-      } else {
-        if (kk < k) v.x = in[row * k + kk];
-        if (kk + 1 < k) v.y = in[row * k + kk + 1];
-        if (kk + 2 < k) v.z = in[row * k + kk + 2];
-        if (kk + 3 < k) v.w = in[row * k + kk + 3];
-      }
-    }
-    *reinterpret_cast<int4*>(&s_codes[rr][c4 * 4]) = v;
-  }
-  __syncthreads();
-  // words of this tile: [kS_local][t][inner]: KB/16 k-tiles x 32 = 512 words
-  constexpr int WORDS = KB * 2;
-#pragma unroll
-  for (int it = 0; it < WORDS / 256; ++it) {
-    const int wi = it * 256 + tid;
-    const int inner = wi % I;
-    const int t = (wi / I) & 31;
-    const int ksl = wi / (32 * I);
-    const int64_t ks = kb0 / (16 * I) + ksl;
-    if (ks >= ksuper) continue;
-    const int m0 = t >> 2, q = t & 3;
-    const int kl = (ksl * I + inner) * 16 + 2 * q;
-    const uint32_t v0 = s_codes[m0][kl], v1 = s_codes[m0][kl + 1];              // (m0,k0) (m0,k1)
-    const uint32_t v2 = s_codes[m0 + 8][kl], v3 = s_codes[m0 + 8][kl + 1];      // (m1,k0) (m1,k1)
-    const uint32_t v4 = s_codes[m0][kl + 8], v5 = s_codes[m0][kl + 9];          // (m0,k2) (m0,k3)
-    const uint32_t v6 = s_codes[m0 + 8][kl + 8], v7 = s_codes[m0 + 8][kl + 9];  // (m1,k2) (m1,k3)
-    const uint32_t pack = (v7 << 28) | (v5 << 24) | (v3 << 20) | (v1 << 16) | (v6 << 12) | (v4 << 8) | (v2 << 4) | v0;
-    out[((mT * ksuper + ks) * 32 + t) * I + inner] = (int32_t)pack;
-  }
-}
-
-// ---- unpack: one thread per code; the index arithmetic is the packers' read backwards (TinyGemmConvertA.cu:226-285,
-// TinyGemmConvertB.cu:252-308: pack = v7<<28 | v5<<24 | v3<<20 | v1<<16 | v6<<12 | v4<<8 | v2<<4 | v0) ----
-__global__ void __launch_bounds__(256) unpack_int4_kernel(const uint32_t* __restrict__ packed, int32_t* __restrict__ codes, int layout_a,
-                                                          int64_t rows, int64_t k, int I, int64_t ksuper) {
-  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (idx >= rows * k) return;
-  const int64_t r = idx / k, kk = idx - r * k;
-  const int64_t kt = kk >> 4;
-  const int kq = (int)(kk & 15);
-  int64_t word;
-  int v;
-  if (layout_a) {  // v = [(m0,k0),(m0,k1),(m1,k0),(m1,k1),(m0,k2),(m0,k3),(m1,k2),(m1,k3)], k0 = 2 (t % 4), k2 = k0 + 8
-    const int rr = (int)(r & 15), m0 = rr & 7, hi = rr >> 3;
-    const int t = 4 * m0 + ((kq & 7) >> 1);
-    v = (kq >> 3) * 4 + hi * 2 + (kq & 1);
-    word = (((r >> 4) * ksuper + kt / I) * 32 + t) * I + kt % I;
-  } else {         // word j of a lane: k-tiles 2j (v0..v3) and 2j + 1 (v4..v7) of the super-tile, k = base + 2 (t % 4) + {0, 1, 8, 9}
-    const int t = 4 * (int)(r & 7) + ((kq & 7) >> 1);
-    const int ktl = (int)(kt % I);
-    v = (ktl & 1) * 4 + (kq & 1) + 2 * (kq >> 3);
-    word = (((r >> 3) * ksuper + kt / I) * 32 + t) * (I / 2) + (ktl >> 1);
-  }
-  const int shift = (v & 1) * 16 + (v >> 1) * 4;
-  codes[idx] = (int32_t)((packed[word] >> shift) & 15u);
-}
-
-// ---- dequantise a Bint4-packed weight matrix into row-major 16-bit values (what a GEMM library multiplies for MANY activation rows) ----
-// w[r][k] = RNE16(fma(f32(lut[r][code]), f32(scale[g][r]), f32(zero[g][r]))) -- the reference's dequantisation, element for element
-// (MatrixLayoutB.cuh:1042-1046; int4: lut = code - 8, Dequantization.cuh:136-178).  Thread = (row, 64-k super-tile of innerKTiles 4 /
-// 32-k of 2 / 128-k of 8): its words are 4 lanes x I / 2 words = 8 I contiguous bytes of the packed layout (ConvertB.cu:252-308), its
-// output 32 I contiguous bytes of the row.
-template <typename DT, int I, int CHK>
-__global__ void __launch_bounds__(256) dequant_w4_kernel(const uint32_t* __restrict__ packed, const uint16_t* __restrict__ qinfo, const uint16_t* __restrict__ lut,
-                                                        uint16_t* __restrict__ out, int64_t rows, int64_t wrows_q, int64_t k, int64_t ksuper, int gshift, int qtype) {
-  constexpr int W = I / 2;   // words per lane of the packed layout = 32-k runs per super-tile
-  // lane = (super-tile, word column j, run h of 8 consecutive k) of a 512-k chunk: a quad of lanes writes 64 contiguous bytes, the 4 W lanes
-  // of a super-tile 32 I contiguous bytes, consecutive super-tiles follow: whole lines per wave-store; the 4 words a lane needs (lanes
-  // 0 ... 3 of its row, column j) are the same for the four h -- one request per quad.
-  // A WAVE is CHK consecutive 512-k chunks of ONE row (host: k a multiple of 512 CHK): at most 16 quantisation groups per chunk.  Their
-  // dequantised tables -- 16 values RNE16(fma(lut[e], scale, zero)) per group, one fma per lane and round of 64 -- go to the wave's own LDS,
-  // and every weight is then ONE 2-byte LDS read at table + 2 code (a 32-byte table is 8 banks: different entries never collide, equal
-  // ones broadcast) instead of an 8-way select and an fma per element (~150 vector ops per 16 bytes of output: 31 us for a 4096 x 4096
-  // matrix against 14 with one chunk per wave; CHK = 4: every load of the wave's 2048 k in flight before the first table is built).
-  __shared__ uint16_t tables[4][CHK][16][16];  // [wave][chunk][group of the chunk][entry]
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  // blockIdx.y (+ 65535 blockIdx.z) = the row, blockIdx.x = a 256-thread piece of it: no 64-bit division by the run-time row length
-  const int per_row = (int)(k >> 3) / CHK;             // threads per row (a multiple of 64)
-  const int64_t r = (int64_t)blockIdx.y + (int64_t)blockIdx.z * 65535;
-  const int tr = (int)blockIdx.x * 256 + (int)threadIdx.x;
-  if (r >= rows || tr - lane >= per_row) return;       // (wave-uniform)
-  const int64_t k0w = (int64_t)(tr - lane) * 8 * CHK;  // first k of the wave
-  const int ngw = (512 >> gshift) > 0 ? (512 >> gshift) : 1;   // groups of a chunk (g = 256 / 128 / 64 / 32: 2 / 4 / 8 / 16)
-  // ---- requests: the packed words of every chunk, then the table inputs ----
-  uint32_t wd[CHK][4];
-  int hh[CHK];
-  const uint16_t* tb[CHK];
-#pragma unroll
-  for (int c = 0; c < CHK; ++c) {
-    const int t = (int)((k0w >> 3) + c * 64 + lane);   // this lane's 8-k run of the row
-    const int h = t & 3, j = (t >> 2) % W;
-    const int64_t s = t / (4 * W);
-    const uint32_t* src = packed + (((r >> 3) * ksuper + s) * 32 + 4 * (r & 7)) * W + j;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) wd[c][i] = src[i * W];
-    hh[c] = h;
-    const int64_t k0 = s * (16 * I) + j * 32;
-    tb[c] = &tables[wave][c][(int)((k0 >> gshift) - ((k0w + c * 512) >> gshift))][0];
-  }
-  for (int t = lane; t < CHK * ngw * 16; t += 64) {
-    const int e = t & 15, cg = t >> 4, c = cg / ngw, gw = cg - c * ngw;
-    float lv;
-    if (qtype == TG_Q_INT4) lv = (float)(e - 8);
-    else lv = DT::lo_f32((uint32_t)lut[(qtype == TG_Q_ANY4_ROWWISE ? r * 16 : 0) + e]);
-    const uint32_t sz = reinterpret_cast<const uint32_t*>(qinfo)[(((k0w + c * 512) >> gshift) + gw) * wrows_q + r];
-    tables[wave][c][gw][e] = DT::from_f32(__builtin_fmaf(lv, DT::lo_f32(sz), DT::hi_f32(sz)));
-  }
-  // (the region is the wave's own and a wave's LDS operations execute in order: no barrier)
-  // word i holds k = 2 i + {0, 1, 8, 9, 16, 17, 24, 25} of the run of 32 in the nibbles (v & 1) * 16 + (v >> 1) * 4, v = 0 ... 7: the pair
-  // (k, k + 1) = (2 i + 8 h, 2 i + 8 h + 1) sits at bits 4 h and 16 + 4 h
-#pragma unroll
-  for (int c = 0; c < CHK; ++c) {
-    u32x4 o;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const uint32_t c0 = (wd[c][i] >> (hh[c] * 4)) & 15u, c1 = (wd[c][i] >> (16 + hh[c] * 4)) & 15u;
-      o[i] = (uint32_t)tb[c][c0] | ((uint32_t)tb[c][c1] << 16);
-    }
-    *reinterpret_cast<u32x4*>(out + r * k + k0w + (int64_t)(c * 64 + lane) * 8) = o;
-  }
-}
-
-// ---- 16-bit fragment-order conversions (pure data movement) ------------------------------------
-// ref TinyGemmConvertA.cu:19-141 / 442-546 and TinyGemmConvertB.cu:20-66 / 136-176
-__global__ void __launch_bounds__(256) to_A16_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                    int64_t m, int64_t k, int64_t mTiles, int64_t kTiles) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= mTiles * kTiles * 32) return;
-  const int t = gid & 31;
-  const int64_t kT = (gid >> 5) % kTiles, mT = (gid >> 5) / kTiles;
-  const int64_t m0 = mT * 16 + (t >> 2), m1 = m0 + 8;
-  const int64_t k0 = kT * 16 + (t & 3) * 2;
-  uint16_t v[8];
-  auto at = [&](int64_t rr, int64_t cc) -> uint16_t { return (rr < m && cc < k) ? in[rr * k + cc] : (uint16_t)0; };
-  v[0] = at(m0, k0); v[1] = at(m0, k0 + 1); v[2] = at(m1, k0); v[3] = at(m1, k0 + 1);
-  v[4] = at(m0, k0 + 8); v[5] = at(m0, k0 + 9); v[6] = at(m1, k0 + 8); v[7] = at(m1, k0 + 9);
-  u32x4 o = {v[0] | ((uint32_t)v[1] << 16), v[2] | ((uint32_t)v[3] << 16), v[4] | ((uint32_t)v[5] << 16), v[6] | ((uint32_t)v[7] << 16)};
-  *reinterpret_cast<u32x4*>(out + gid * 8) = o;
-}
-
-__global__ void __launch_bounds__(256) from_A16_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                      int64_t m, int64_t k, int64_t mTiles, int64_t kTiles) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= mTiles * kTiles * 32) return;
-  const int t = gid & 31;
-  const int64_t kT = (gid >> 5) % kTiles, mT = (gid >> 5) / kTiles;
-  const u32x4 o = *reinterpret_cast<const u32x4*>(in + gid * 8);
-#pragma unroll
-  for (int e = 0; e < 8; ++e) {
-    const int64_t rr = mT * 16 + (t >> 2) + 8 * ((e >> 1) & 1);
-    const int64_t cc = kT * 16 + (t & 3) * 2 + 8 * (e >> 2) + (e & 1);
-    const uint16_t val = (uint16_t)(o[e >> 1] >> (16 * (e & 1)));
-    if (rr < m && cc < k) out[rr * k + cc] = val;
-  }
-}
-
-__global__ void __launch_bounds__(256) to_B16_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                    int64_t n, int64_t k, int64_t nTiles, int64_t totalK, int inner) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= nTiles * totalK * 32) return;
-  const int t = gid & 31;
-  const int64_t kT = (gid >> 5) % totalK, nT = (gid >> 5) / totalK;
-  const int64_t n0 = nT * 8 + (t >> 2);
-  const int64_t k0 = kT * 16 + (t & 3) * 2;
-  auto at = [&](int64_t cc) -> uint32_t { return (n0 < n && cc < k) ? in[n0 * k + cc] : 0u; };
-  u32x2 o = {at(k0) | (at(k0 + 1) << 16), at(k0 + 8) | (at(k0 + 9) << 16)};
-  uint16_t* dst = out + ((nT * (totalK / inner) + kT / inner) * 32 + t) * (4 * inner) + (kT % inner) * 4;
-  *reinterpret_cast<u32x2*>(dst) = o;
-}
-
-__global__ void __launch_bounds__(256) from_B16_kernel(const uint16_t* __restrict__ in, uint16_t* __restrict__ out,
-                                                      int64_t n, int64_t k, int64_t nTiles, int64_t kTiles,
-                                                      int64_t outerK, int inner) {
-  const int64_t gid = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (gid >= nTiles * kTiles * 32) return;
-  const int t = gid & 31;
-  const int64_t kT = (gid >> 5) % kTiles, nT = (gid >> 5) / kTiles;
-  const int64_t n0 = nT * 8 + (t >> 2);
-  if (n0 >= n) return;
-  const uint16_t* src = in + ((nT * outerK + kT / inner) * 32 + t) * (4 * inner) + (kT % inner) * 4;
-  const u32x2 o = *reinterpret_cast<const u32x2*>(src);
-  const int64_t k0 = kT * 16 + (t & 3) * 2;
-  const int64_t ks[4] = {k0, k0 + 1, k0 + 8, k0 + 9};
-#pragma unroll
-  for (int e = 0; e < 4; ++e)
-    if (ks[e] < k) out[n0 * k + ks[e]] = (uint16_t)(o[e >> 1] >> (16 * (e & 1)));
-}
-
-// debug op, ref TinyGemmDequantize.cu:19-34 (grid-stride, one word -> 8 bf16 = 16 bytes)
-__global__ void __launch_bounds__(256) dequant_int4_kernel(const int32_t* __restrict__ in, u32x4* __restrict__ out, int64_t count) {
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < count; idx += (int64_t)gridDim.x * 256) {
-    const uint32_t w = (uint32_t)in[idx];
-    u32x4 o;
-#pragma unroll
-    for (int ii = 0; ii < 4; ++ii) {
-      const float lo = (float)((int)((w >> (4 * ii)) & 0xfu) - 8);
-      const float hi = (float)((int)((w >> (4 * ii + 16)) & 0xfu) - 8);
-      o[ii] = BF16::pack2(lo, hi);
-    }
-    out[idx] = o;
-  }
-}
+#include "f16_gemm.cuh"
+#include "tg_convert.cuh"
 
 
 #ifdef TG_DEV  // developer builds only (-DTG_DEV): geometry override through the environment, never in the shipped library
@@ -457,44 +72,6 @@ inline Geometry pick_geometry(int64_t rowtiles, int64_t coltiles, int64_t batch,
   return g;
 }
 
-
-// ---- int8 packers (reference TinyGemmConvertB.cu:366-411, TinyGemmConvertA.cu:337-397): one thread per output word.
-// The OR of the shifted 32-bit inputs is kept exactly as written there (inputs above 255 bleed into higher bytes).
-template <int I>
-__global__ void __launch_bounds__(256) pack_Bint8_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t n,
-                                                         int64_t k, int64_t ksuper, int64_t total) {
-  for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-    const int j = (int)(o % I), t = (int)((o / I) % 32);
-    const int64_t ks_ = (o / (I * 32)) % ksuper, nt = o / (I * 32 * ksuper);
-    const int64_t n0 = nt * 8 + t / 4, kb = (ks_ * I + j) * 16 + (t % 4) * 2;
-    uint32_t v[4] = {0u, 0u, 0u, 0u};
-    if (n0 < n) {
-      const int32_t* r = in + n0 * k;
-      if (kb < k) v[0] = (uint32_t)r[kb];
-      if (kb + 1 < k) v[1] = (uint32_t)r[kb + 1];
-      if (kb + 8 < k) v[2] = (uint32_t)r[kb + 8];
-      if (kb + 9 < k) v[3] = (uint32_t)r[kb + 9];
-    }
-    out[o] = (int32_t)((v[3] << 24) | (v[1] << 16) | (v[2] << 8) | v[0]);
-  }
-}
-
-template <int I>
-__global__ void __launch_bounds__(256) pack_Aint8_kernel(const int32_t* __restrict__ in, int32_t* __restrict__ out, int64_t m,
-                                                         int64_t k, int64_t kouter, int64_t total) {
-  for (int64_t o = (int64_t)blockIdx.x * 256 + threadIdx.x; o < total; o += (int64_t)gridDim.x * 256) {
-    const int w = (int)(o % 2), j = (int)((o / 2) % I), t = (int)((o / (2 * I)) % 32);
-    const int64_t ko = (o / (2 * I * 32)) % kouter, mt = o / (2 * I * 32 * kouter);
-    const int64_t m0 = mt * 16 + t / 4, m1 = m0 + 8;
-    const int64_t ka = (ko * I + j) * 16 + (t % 4) * 2 + 8 * w;  // word 0: k0, k0+1; word 1: k0+8, k0+9
-    uint32_t v0 = 0u, v1 = 0u, v2 = 0u, v3 = 0u;                 // (m0,ka) (m0,ka+1) (m1,ka) (m1,ka+1)
-    if (m0 < m && ka < k) v0 = (uint32_t)in[m0 * k + ka];
-    if (m0 < m && ka + 1 < k) v1 = (uint32_t)in[m0 * k + ka + 1];
-    if (m1 < m && ka < k) v2 = (uint32_t)in[m1 * k + ka];
-    if (m1 < m && ka + 1 < k) v3 = (uint32_t)in[m1 * k + ka + 1];
-    out[o] = (int32_t)((v3 << 24) | (v1 << 16) | (v2 << 8) | v0);
-  }
-}
 
 template <typename DT, bool LAYOUT_A, int I>
 int launch_w8(GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
@@ -674,7 +251,7 @@ int tg_dequant_w4_panel(const void* packed, const void* qinfo, const void* lut, 
   DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
   const int64_t ksuper = k / (16 * I);
-  const int gshift = group == 32 ? 5 : group == 64 ? 6 : group == 128 ? 7 : 8;
+  const int gshift = group_shift(group);
   const int chk = k % 2048 == 0 ? 4 : 1;   // chunks of 512 k per wave
   const unsigned bs = k / 8 / chk < 256 ? (unsigned)(k / 8 / chk) : 256u;   // (a row's threads: a multiple of 64)
   const dim3 grid((unsigned)cdiv(k / 8 / chk, 256), (unsigned)(wrows < 65535 ? wrows : 65535), (unsigned)cdiv(wrows, 65535));
@@ -763,57 +340,119 @@ static int take_args(const tg_w4_gemm* a, tg_w4_gemm* full) {
   return 0;
 }
 
-// dry: 0 launch, 1 report the kernel family (tg_gemm_w4_plan), 2 report the workspace the fastest kernel wants
-static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
-  tg_w4_gemm full;
-  const int src = take_args(caller, &full);
-  if (src != 0) return src;
-  const tg_w4_gemm* a = &full;
+// ---- the preconditions of a tg_w4_gemm, for the three entry points that take one -----------------------------------------------
+// `a` is the zero-extended struct (take_args).  Return codes AND their precedence are ABI: a struct that breaks several preconditions
+// gets the code of the first check below that fails.  Where an entry point's order differs from tg_gemm_w4's (dx says what it does not
+// do before it looks at the sizes; w8 looks at the sizes before the batch stride of the bias and the workspace), its checks sit at
+// that entry's own place.
+enum GemmEntry { ENTRY_W4, ENTRY_DX, ENTRY_W8 };
+
+static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
+
+static bool bad_w_format(const tg_w4_gemm* a) {
+  return !(a->w_format == TG_WFMT_M16N8K16 || a->w_format == TG_WFMT_ROWS) || (a->w_format && a->w_on_right) || a->reserved6 != 0;
+}
+static bool bad_numerics(const tg_w4_gemm* a) {
+  return !(a->numerics == TG_NUM_FAST || a->numerics == TG_NUM_REFERENCE || a->numerics == TG_NUM_FAST_MFMA || a->numerics == TG_NUM_FAST_DOT2) ||
+         a->reserved != 0;
+}
+static bool bad_workspace(const tg_w4_gemm* a) { return a->workspace && (!aligned16(a->workspace) || a->workspace_bytes < 0); }
+static bool bad_bias_row_stride(const tg_w4_gemm* a) { return a->bias_row_stride < 0 || (a->bias_row_stride && !a->bias) || (a->bias_row_stride & 3); }
+
+// the kernels address one problem's operands with 32-bit byte offsets
+static bool too_large(const tg_w4_gemm* a, GemmEntry e) {
+  const int64_t lim = (int64_t)1 << 31;
+  const int64_t w_bytes = e == ENTRY_W8 ? a->wrows * a->k : a->wrows * a->k / 2;
+  if (a->m * a->k * 2 >= lim || w_bytes >= lim || (a->k / a->group) * a->wrows * 4 >= lim) return true;
+  // dx: its output is addressed that way as well, and its grid has no dimension of 16-row activation tiles
+  return e == ENTRY_DX ? a->m * a->wrows * 2 >= lim : cdiv(a->m, 16) > 65535;
+}
+
+static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
+  const bool dx = e == ENTRY_DX, w8 = e == ENTRY_W8;
   if (!a->x || !a->w || !a->qinfo || !a->y) return TG_E_NULL;
-  if (a->qtype < TG_Q_INT4 || a->qtype > TG_Q_MX4) return TG_E_QTYPE;
+  // w8: its own quantisation type -- no LUT, not mx4, so the LUT and mx4 checks below cannot fail for it
+  if (w8 ? a->qtype != TG_Q_INT8 : (a->qtype < TG_Q_INT4 || a->qtype > TG_Q_MX4)) return TG_E_QTYPE;
   if ((a->qtype == TG_Q_ANY4_GLOBAL || a->qtype == TG_Q_ANY4_ROWWISE) && !a->lut) return TG_E_NULL;
   if (!(a->dtype == TG_BF16 || a->dtype == TG_F16)) return TG_E_DTYPE;
   if (a->qtype == TG_Q_MX4 && a->dtype != TG_BF16) return TG_E_DTYPE;  // TinyGemm_int4.cu:758,782
+  if (dx) {
+    // one problem, no fused stage, row-major dY / dX, Bint4 words; `numerics` is accepted and ignored, but must be a valid value
+    if (a->batch > 1) return TG_E_SHAPE;
+    if (a->bias || a->bias_row_stride || a->norm_weight || a->epilogue) return TG_E_FUSION;
+    if (a->x_layout != TG_LAYOUT_RM || a->y_layout != TG_LAYOUT_RM) return TG_E_LAYOUT;
+    if (bad_w_format(a)) return TG_E_SHAPE;
+    if (!a->w_on_right && a->w_format != TG_WFMT_ROWS) return TG_E_LAYOUT;   // the reference's Aint4 words: repack to the native format
+    if (bad_numerics(a)) return TG_E_SHAPE;
+  }
   if (a->m <= 0 || a->wrows <= 0 || a->k <= 0 || a->m > INT32_MAX || a->wrows > INT32_MAX || a->k > INT32_MAX) return TG_E_SHAPE;
-  int I = a->inner_k_tiles;
-  bool on_right = a->w_on_right != 0;
-  if (on_right ? !(I == 2 || I == 4 || I == 8) : !(I == 1 || I == 2 || I == 4)) return TG_E_INNER_K;
+  // innerKTiles of the packed layout.  Bint4: 2, 4, 8; Aint4: 1, 2, 4 (TinyGemm_int4.cu); Bint8: 1, 2, 4; Aint8: 1, 2 (TinyGemm_int8.cu:262, 286)
+  const int I = a->inner_k_tiles;
+  const bool right = a->w_on_right != 0;
+  const int i_min = !w8 && right ? 2 : 1, i_max = w8 ? (right ? 4 : 2) : (right ? 8 : 4);
+  if (!(I == 1 || I == 2 || I == 4 || I == 8) || I < i_min || I > i_max) return TG_E_INNER_K;
   // TinyGemmImpl.cuh:370-376: kTiles % innerKTiles == 0, k % 32 == 0
   if (a->k % 32 != 0 || a->k % (16 * I) != 0) return TG_E_K_DIV;
   const int g = a->group;
-  if (!(g == 32 || g == 64 || g == 128 || g == 256) || a->k % g != 0) return TG_E_GROUP;  // TinyGemm_int4.cu:379-387
-  if (a->wrows % (on_right ? 8 : 16) != 0) return TG_E_SHAPE;
-  if (!(a->w_format == TG_WFMT_M16N8K16 || a->w_format == TG_WFMT_ROWS) || (a->w_format && on_right) || a->reserved6 != 0) return TG_E_SHAPE;
-  if (a->w_format == TG_WFMT_ROWS) {
-    // the A-shaped tensor holds Bint4 words (rows padded to 16): from here on this IS a weights-on-the-right call -- both sides
-    // produce [activation row][weight row] (TinyGemm_int4.cu:450-456)
-    on_right = true;
-    I = a->k % 64 == 0 ? 4 : 2;
+  if (!(g == 32 || g == 64 || g == 128 || g == 256) || a->k % g != 0) return TG_E_GROUP;  // TinyGemm_int4.cu:379-387, TinyGemm_int8.cu:293-301
+  if (a->wrows % (right ? 8 : 16) != 0) return TG_E_SHAPE;                                 // whole tiles of the packed tensor
+  if (e == ENTRY_W4 && bad_w_format(a)) return TG_E_SHAPE;   // (w8 has one format per side and does not read the field)
+  // x: 16-byte loads of the activation fragments (rows are k * 2 bytes with k % 32 == 0).  w: 16-byte loads of the 4-bit words, 4-byte
+  // loads of the 8-bit ones.  y: dx stores 16 bytes per lane, w8 four rows (8 bytes), the 4-bit kernels' stores need the element's own
+  // alignment only.  qinfo: (scale, zero) pairs.  LUT rows are read as two 16-byte vectors (w8 has none and ignores the pointer).
+  if (misaligned(a->x, 16) || misaligned(a->w, w8 ? 4 : 16) || misaligned(a->qinfo, 4) || misaligned(a->y, dx ? 16 : w8 ? 8 : 1)) return TG_E_ALIGN;
+  if (w8 && a->batch > 1 && (a->stride_x & 15)) return TG_E_ALIGN;   // (w4 checks its batch strides further down, behind the fused stages)
+  if (!w8 && a->lut && misaligned(a->lut, 16)) return TG_E_ALIGN;
+  if (a->bias && misaligned(a->bias, 8)) return TG_E_ALIGN;          // (dx: no bias got this far)
+  switch (e) {
+    case ENTRY_W4: {
+      const bool on_right = right || a->w_format == TG_WFMT_ROWS;    // (gemm_layout)
+      if (bad_numerics(a)) return TG_E_SHAPE;
+      if (bad_workspace(a)) return TG_E_ALIGN;
+      if (!(a->x_layout == TG_LAYOUT_RM || a->x_layout == TG_LAYOUT_TC_A) || !(a->y_layout == TG_LAYOUT_RM || a->y_layout == TG_LAYOUT_TC_A)) return TG_E_LAYOUT;
+      if ((a->x_layout || a->y_layout) && (!on_right || a->m % 16 != 0 || a->bias)) return TG_E_LAYOUT;
+      if (bad_bias_row_stride(a)) return TG_E_SHAPE;
+      if (!(a->epilogue == TG_EPI_NONE || a->epilogue == TG_EPI_SWIGLU)) return TG_E_SHAPE;
+      if (a->norm_weight && !aligned16(a->norm_weight)) return TG_E_ALIGN;
+      // the fused stages exist in the TG_NUM_FAST pair-table kernels only (row-major operands)
+      if ((a->norm_weight || a->epilogue) && (a->numerics == TG_NUM_REFERENCE || a->x_layout || a->y_layout)) return TG_E_FUSION;
+      if (a->norm_weight && a->k % 2048 != 0) return TG_E_FUSION;
+      if (a->epilogue == TG_EPI_SWIGLU && (!on_right || a->bias || a->wrows % 16 != 0)) return TG_E_FUSION;
+      if (a->batch > 1 && ((a->stride_x | a->stride_w | a->stride_lut) & 15)) return TG_E_ALIGN;
+      if (a->batch > 1 && a->bias && (a->stride_bias & 7)) return TG_E_ALIGN;
+      return too_large(a, e) ? (int)TG_E_SIZE : 0;
+    }
+    case ENTRY_DX:
+      if (bad_workspace(a)) return TG_E_ALIGN;
+      return too_large(a, e) ? (int)TG_E_SIZE : 0;
+    case ENTRY_W8:
+      // the fields later ABI versions added for the 4-bit kernels (numerics, layouts, w_format) are not read; a fused stage is refused
+      if (a->reserved != 0) return TG_E_SHAPE;
+      if (a->norm_weight || a->epilogue) return TG_E_FUSION;
+      if (bad_bias_row_stride(a)) return TG_E_SHAPE;
+      if (too_large(a, e)) return TG_E_SIZE;
+      if (a->batch > 1 && a->bias && (a->stride_bias & 7)) return TG_E_ALIGN;
+      return bad_workspace(a) ? (int)TG_E_ALIGN : 0;
   }
-  const int rows_per_tile = on_right ? 8 : 16;
-  if (!aligned16(a->x) || !aligned16(a->w) || (reinterpret_cast<uintptr_t>(a->qinfo) & 3u)) return TG_E_ALIGN;
-  if (a->lut && !aligned16(a->lut)) return TG_E_ALIGN;          // LUT rows are read as two 16-byte vectors
-  if (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 7u)) return TG_E_ALIGN;
-  if (!(a->numerics == TG_NUM_FAST || a->numerics == TG_NUM_REFERENCE || a->numerics == TG_NUM_FAST_MFMA || a->numerics == TG_NUM_FAST_DOT2) || a->reserved != 0) return TG_E_SHAPE;
-  if (a->workspace && (!aligned16(a->workspace) || a->workspace_bytes < 0)) return TG_E_ALIGN;
-  if (!(a->x_layout == TG_LAYOUT_RM || a->x_layout == TG_LAYOUT_TC_A) || !(a->y_layout == TG_LAYOUT_RM || a->y_layout == TG_LAYOUT_TC_A)) return TG_E_LAYOUT;
-  if ((a->x_layout || a->y_layout) && (!on_right || a->m % 16 != 0 || a->bias)) return TG_E_LAYOUT;
-  if (a->bias_row_stride < 0 || (a->bias_row_stride && !a->bias) || (a->bias_row_stride & 3)) return TG_E_SHAPE;
-  if (!(a->epilogue == TG_EPI_NONE || a->epilogue == TG_EPI_SWIGLU)) return TG_E_SHAPE;
-  if (a->norm_weight && !aligned16(a->norm_weight)) return TG_E_ALIGN;
-  // the fused stages exist in the TG_NUM_FAST pair-table kernels only (row-major operands)
-  if ((a->norm_weight || a->epilogue) && (a->numerics == TG_NUM_REFERENCE || a->x_layout || a->y_layout)) return TG_E_FUSION;
-  if (a->norm_weight && a->k % 2048 != 0) return TG_E_FUSION;
-  if (a->epilogue == TG_EPI_SWIGLU && (!on_right || a->bias || a->wrows % 16 != 0)) return TG_E_FUSION;
-  const int batch = a->batch > 1 ? a->batch : 1;
-  if (batch > 1 && ((a->stride_x | a->stride_w | a->stride_lut) & 15)) return TG_E_ALIGN;
-  if (batch > 1 && a->bias && (a->stride_bias & 7)) return TG_E_ALIGN;
-  // the kernels address one problem's operands with 32-bit byte offsets
-  if (a->m * a->k * 2 >= (int64_t)1 << 31 || a->wrows * a->k / 2 >= (int64_t)1 << 31 ||
-      (a->k / a->group) * a->wrows * 4 >= (int64_t)1 << 31 || cdiv(a->m, 16) > 65535)
-    return TG_E_SIZE;
+  return TG_E_INTERNAL;
+}
 
+// The packed words a validated 4-bit call holds.  TG_WFMT_ROWS: the A-shaped tensor holds Bint4 words (rows padded to 16), so from
+// here on this IS a weights-on-the-right call -- both sides produce [activation row][weight row] (TinyGemm_int4.cu:450-456).
+struct PackedLayout {
+  bool on_right;
+  int I;  // innerKTiles
+};
+static PackedLayout gemm_layout(const tg_w4_gemm* a) {
+  if (a->w_format == TG_WFMT_ROWS) return {true, a->k % 64 == 0 ? 4 : 2};
+  return {a->w_on_right != 0, a->inner_k_tiles};
+}
+
+// GemmParams of a validated call.  dry: 0 launch, 1 report the kernel family, 2 report the workspace the fastest kernel wants.
+static GemmParams make_params(const tg_w4_gemm* a, PackedLayout l, int dry) {
+  const bool batched = a->batch > 1;
   GemmParams p;
+  memset(&p, 0, sizeof p);   // (splitk / sk_shift: the launch path's; ws_need: the planner's answer; dbg: developer builds)
   p.x = (const char*)a->x;
   p.w = (const char*)a->w;
   p.qinfo = (const char*)a->qinfo;
@@ -822,21 +461,45 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
   p.m = (int32_t)a->m;
   p.wrows = (int32_t)a->wrows;
   p.k = (int32_t)a->k;
-  p.ntiles = (int32_t)(a->wrows / rows_per_tile);
-  p.ksuper = (int32_t)(a->k / (16 * I));
-  p.gshift = g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8;
-  p.ngroups = (int32_t)(a->k / g);
+  p.ntiles = (int32_t)(a->wrows / (l.on_right ? 8 : 16));
+  p.ksuper = (int32_t)(a->k / (16 * l.I));
+  p.gshift = group_shift(a->group);
+  p.ngroups = (int32_t)(a->k / a->group);
   p.qtype = a->qtype;
-  p.dbg = 0;
-  p.dry = dry != 0;
+  p.rowtiles = (int32_t)cdiv(a->wrows, 16);
   p.numerics = a->numerics == TG_NUM_FAST_DOT2 ? (int)TG_NUM_FAST : a->numerics;
   p.dot2 = a->numerics == TG_NUM_FAST_DOT2;
+  p.dry = dry != 0;
+  p.stride_x = batched ? a->stride_x : 0;
+  p.stride_w = batched ? a->stride_w : 0;
+  p.stride_qinfo = batched ? a->stride_qinfo : 0;
+  p.stride_lut = batched ? a->stride_lut : 0;
+  p.stride_y = batched ? a->stride_y : 0;
+  p.bias = (const char*)a->bias;
+  p.stride_bias = batched ? a->stride_bias : 0;
+  p.bias_row_stride = a->bias_row_stride;
+  p.norm_w = (const char*)a->norm_weight;
+  p.norm_eps = a->norm_eps;
+  p.epilogue = a->epilogue;
   p.ws = (char*)a->workspace;
   p.ws_bytes = a->workspace ? a->workspace_bytes : 0;
   p.ws_query = dry == 2;
-  p.ws_need = 0;
   p.x_tc = a->x_layout == TG_LAYOUT_TC_A;
   p.y_tc = a->y_layout == TG_LAYOUT_TC_A;
+  return p;
+}
+
+// dry: 0 launch, 1 report the kernel family (tg_gemm_w4_plan), 2 report the workspace the fastest kernel wants
+static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
+  tg_w4_gemm full;
+  const tg_w4_gemm* a = &full;
+  int rc0 = take_args(caller, &full);
+  if (rc0 == 0) rc0 = check_gemm(a, ENTRY_W4);
+  if (rc0 != 0) return rc0;
+  const PackedLayout lay = gemm_layout(a);
+  const bool on_right = lay.on_right;
+  const int I = lay.I, batch = a->batch > 1 ? a->batch : 1;
+  GemmParams p = make_params(a, lay, dry);
 #ifdef TG_DEV
   {
     static const int env_dbg = getenv("TG_DBG") ? atoi(getenv("TG_DBG")) : 0;
@@ -845,22 +508,9 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
     g_dbg_variant = env_var;
   }
 #endif
-  p.bias = (const char*)a->bias;
-  p.stride_bias = batch > 1 ? a->stride_bias : 0;
-  p.bias_row_stride = a->bias_row_stride;
-  p.norm_w = (const char*)a->norm_weight;
-  p.norm_eps = a->norm_eps;
-  p.epilogue = a->epilogue;
-  p.stride_x = batch > 1 ? a->stride_x : 0;
-  p.stride_w = batch > 1 ? a->stride_w : 0;
-  p.stride_qinfo = batch > 1 ? a->stride_qinfo : 0;
-  p.stride_lut = batch > 1 ? a->stride_lut : 0;
-  p.stride_y = batch > 1 ? a->stride_y : 0;
-
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
   hipStream_t st = (hipStream_t)stream;
-  p.rowtiles = (int32_t)cdiv(a->wrows, 16);
   const int64_t coltiles = cdiv(a->m, 16);
   // packed words per lane-quad in the layout decide the in-register transpose
   const int canon = on_right ? (I == 2 ? CANON_NONE : I == 4 ? CANON_PAIR : CANON_QUAD)
@@ -942,54 +592,15 @@ int64_t tg_gemm_w4_workspace_bytes(const tg_w4_gemm* a) {
 // dry: 0 launch, 2 report the workspace of the split.  Every check runs before any HIP call.
 static int gemm_dx_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
   tg_w4_gemm full;
-  const int src = take_args(caller, &full);
-  if (src != 0) return src;
   const tg_w4_gemm* a = &full;
-  if (!a->x || !a->w || !a->qinfo || !a->y) return TG_E_NULL;
-  if (a->qtype < TG_Q_INT4 || a->qtype > TG_Q_MX4) return TG_E_QTYPE;
-  if ((a->qtype == TG_Q_ANY4_GLOBAL || a->qtype == TG_Q_ANY4_ROWWISE) && !a->lut) return TG_E_NULL;
-  if (!(a->dtype == TG_BF16 || a->dtype == TG_F16)) return TG_E_DTYPE;
-  if (a->qtype == TG_Q_MX4 && a->dtype != TG_BF16) return TG_E_DTYPE;
-  if (a->batch > 1) return TG_E_SHAPE;
-  if (a->bias || a->bias_row_stride || a->norm_weight || a->epilogue) return TG_E_FUSION;
-  if (a->x_layout != TG_LAYOUT_RM || a->y_layout != TG_LAYOUT_RM) return TG_E_LAYOUT;
-  if (!(a->w_format == TG_WFMT_M16N8K16 || a->w_format == TG_WFMT_ROWS) || (a->w_format && a->w_on_right) || a->reserved6 != 0) return TG_E_SHAPE;
-  if (!a->w_on_right && a->w_format != TG_WFMT_ROWS) return TG_E_LAYOUT;   // the reference's Aint4 words: repack to the native format
-  if (!(a->numerics == TG_NUM_FAST || a->numerics == TG_NUM_REFERENCE || a->numerics == TG_NUM_FAST_MFMA || a->numerics == TG_NUM_FAST_DOT2) || a->reserved != 0) return TG_E_SHAPE;
-  if (a->m <= 0 || a->wrows <= 0 || a->k <= 0 || a->m > INT32_MAX || a->wrows > INT32_MAX || a->k > INT32_MAX) return TG_E_SHAPE;
-  int I = a->inner_k_tiles;
-  if (a->w_on_right ? !(I == 2 || I == 4 || I == 8) : !(I == 1 || I == 2 || I == 4)) return TG_E_INNER_K;
-  if (a->k % 32 != 0 || a->k % (16 * I) != 0) return TG_E_K_DIV;
-  const int g = a->group;
-  if (!(g == 32 || g == 64 || g == 128 || g == 256) || a->k % g != 0) return TG_E_GROUP;
-  if (a->wrows % (a->w_on_right ? 8 : 16) != 0) return TG_E_SHAPE;
-  if (!a->w_on_right) I = a->k % 64 == 0 ? 4 : 2;   // TG_WFMT_ROWS: Bint4 words of the rows padded to 16
-  if (!aligned16(a->x) || !aligned16(a->w) || !aligned16(a->y) || (reinterpret_cast<uintptr_t>(a->qinfo) & 3u)) return TG_E_ALIGN;
-  if (a->lut && !aligned16(a->lut)) return TG_E_ALIGN;
-  if (a->workspace && (!aligned16(a->workspace) || a->workspace_bytes < 0)) return TG_E_ALIGN;
-  if (a->m * a->wrows * 2 >= (int64_t)1 << 31 || a->m * a->k * 2 >= (int64_t)1 << 31 || a->wrows * a->k / 2 >= (int64_t)1 << 31 ||
-      (a->k / g) * a->wrows * 4 >= (int64_t)1 << 31)
-    return TG_E_SIZE;
-
-  GemmParams p;
-  memset(&p, 0, sizeof p);
-  p.x = (const char*)a->x;
-  p.w = (const char*)a->w;
-  p.qinfo = (const char*)a->qinfo;
-  p.lut = (const char*)a->lut;
-  p.y = (char*)a->y;
-  p.m = (int32_t)a->m;
-  p.wrows = (int32_t)a->wrows;
-  p.k = (int32_t)a->k;
-  p.gshift = g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8;
-  p.qtype = a->qtype;
-  p.dry = dry != 0;
-  p.ws = (char*)a->workspace;
-  p.ws_bytes = a->workspace ? a->workspace_bytes : 0;
-  p.ws_query = dry == 2;
+  int rc0 = take_args(caller, &full);
+  if (rc0 == 0) rc0 = check_gemm(a, ENTRY_DX);
+  if (rc0 != 0) return rc0;
+  const PackedLayout lay = gemm_layout(a);
+  GemmParams p = make_params(a, lay, dry);
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
-  const int rc = tgx::gemm_dx(a->dtype, I, a->qtype == TG_Q_MX4, p, (hipStream_t)stream);
+  const int rc = tgx::gemm_dx(a->dtype, lay.I, a->qtype == TG_Q_MX4, p, (hipStream_t)stream);
   if (ws_need) *ws_need = p.ws_need;
   return rc;
 }
@@ -1035,53 +646,18 @@ int tg_convert_to_Aint8(const int32_t* in, int64_t m, int64_t k, int I, int32_t*
 // dry: 0 launch, 2 report the workspace the fastest kernel wants (tg_gemm_w8_workspace_bytes)
 static int gemm_w8_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need) {
   tg_w4_gemm full;
-  const int src = take_args(caller, &full);
-  if (src != 0) return src;
   const tg_w4_gemm* a = &full;
-  if (!a->x || !a->w || !a->qinfo || !a->y) return TG_E_NULL;
-  if (a->qtype != TG_Q_INT8) return TG_E_QTYPE;
-  if (!(a->dtype == TG_BF16 || a->dtype == TG_F16)) return TG_E_DTYPE;
-  if (a->m <= 0 || a->wrows <= 0 || a->k <= 0 || a->m > INT32_MAX || a->wrows > INT32_MAX || a->k > INT32_MAX) return TG_E_SHAPE;
-  const int I = a->inner_k_tiles;
-  const bool on_right = a->w_on_right != 0;
-  if (on_right ? !(I == 1 || I == 2 || I == 4) : !(I == 1 || I == 2)) return TG_E_INNER_K;  // TinyGemm_int8.cu:262, 286
-  if (a->k % 32 != 0 || a->k % (16 * I) != 0) return TG_E_K_DIV;                            // TinyGemmImpl.cuh:370-376
-  const int g = a->group;
-  if (!(g == 32 || g == 64 || g == 128 || g == 256) || a->k % g != 0) return TG_E_GROUP;     // TinyGemm_int8.cu:293-301
-  const int rows_per_tile = on_right ? 8 : 16;
-  if (a->wrows % rows_per_tile != 0) return TG_E_SHAPE;
-  // (x: 16-byte loads of the activation fragments / LDS-DMA of the tile flavour; rows are k * 2 bytes with k % 32 == 0)
-  if ((reinterpret_cast<uintptr_t>(a->x) & 15u) || (a->batch > 1 && (a->stride_x & 15)) || (reinterpret_cast<uintptr_t>(a->w) & 3u) ||
-      (reinterpret_cast<uintptr_t>(a->qinfo) & 3u) || (reinterpret_cast<uintptr_t>(a->y) & 7u))
-    return TG_E_ALIGN;
-  if (a->bias && (reinterpret_cast<uintptr_t>(a->bias) & 7u)) return TG_E_ALIGN;
-  if (a->reserved != 0) return TG_E_SHAPE;
-  if (a->norm_weight || a->epilogue) return TG_E_FUSION;
-  if (a->bias_row_stride < 0 || (a->bias_row_stride && !a->bias) || (a->bias_row_stride & 3)) return TG_E_SHAPE;
-  if (a->m * a->k * 2 >= (int64_t)1 << 31 || a->wrows * a->k >= (int64_t)1 << 31 ||
-      (a->k / a->group) * a->wrows * 4 >= (int64_t)1 << 31 || cdiv(a->m, 16) > 65535)
-    return TG_E_SIZE;
-  const int batch = a->batch > 1 ? a->batch : 1;
-  if (batch > 1 && a->bias && (a->stride_bias & 7)) return TG_E_ALIGN;
-  GemmParams p;
-  p.x = (const char*)a->x; p.w = (const char*)a->w; p.qinfo = (const char*)a->qinfo; p.lut = nullptr; p.y = (char*)a->y;
-  p.bias = (const char*)a->bias; p.stride_bias = batch > 1 ? a->stride_bias : 0; p.numerics = TG_NUM_REFERENCE;
-  p.bias_row_stride = a->bias_row_stride; p.norm_w = nullptr; p.norm_eps = 0.f; p.epilogue = 0;
-  p.m = (int32_t)a->m; p.wrows = (int32_t)a->wrows; p.k = (int32_t)a->k;
-  p.ntiles = (int32_t)(a->wrows / rows_per_tile);
-  p.ksuper = (int32_t)(a->k / (16 * I));
-  p.gshift = g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8;
-  p.ngroups = (int32_t)(a->k / g);
-  p.qtype = a->qtype; p.dbg = 0; p.dry = dry != 0;
-  p.stride_x = batch > 1 ? a->stride_x : 0; p.stride_w = batch > 1 ? a->stride_w : 0;
-  p.stride_qinfo = batch > 1 ? a->stride_qinfo : 0; p.stride_lut = 0; p.stride_y = batch > 1 ? a->stride_y : 0;
-  if (a->workspace && (!aligned16(a->workspace) || a->workspace_bytes < 0)) return TG_E_ALIGN;
-  p.ws = (char*)a->workspace; p.ws_bytes = a->workspace ? a->workspace_bytes : 0; p.ws_need = 0; p.ws_query = dry == 2;
-  p.x_tc = p.y_tc = 0;
+  int rc0 = take_args(caller, &full);
+  if (rc0 == 0) rc0 = check_gemm(a, ENTRY_W8);
+  if (rc0 != 0) return rc0;
+  const bool on_right = a->w_on_right != 0;   // (one packed format per side: w_format is not read)
+  const int I = a->inner_k_tiles, batch = a->batch > 1 ? a->batch : 1;
+  GemmParams p = make_params(a, {on_right, I}, dry);
+  // what the struct says for the 4-bit kernels only was not validated and does not reach an int8 kernel
+  p.lut = nullptr; p.stride_lut = 0; p.numerics = TG_NUM_REFERENCE; p.dot2 = 0; p.norm_eps = 0.f; p.x_tc = p.y_tc = 0;
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
   hipStream_t st = (hipStream_t)stream;
-  p.rowtiles = (int32_t)cdiv(a->wrows, 16);
   const int64_t coltiles = cdiv(a->m, 16);
 #ifdef TG_DEV_MIN
   (void)coltiles; (void)st;

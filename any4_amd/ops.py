@@ -57,11 +57,43 @@ _F16_TYPES = (torch.bfloat16, torch.float16)
 # ---------------------------------------------------------------------------------------------
 # call-side state the reference's op schemas have no argument for: GEMM numerics and a fused bias
 # ---------------------------------------------------------------------------------------------
-_NUMERICS = {"fast": _lib.TG_NUM_FAST, "reference": _lib.TG_NUM_REFERENCE, "fast_mfma": _lib.TG_NUM_FAST_MFMA, "fast_dot2": _lib.TG_NUM_FAST_DOT2}
-_numerics = os.environ.get("ANY4_NUMERICS", "fast")
-if _numerics not in _NUMERICS:
-    raise ImportError(f"ANY4_NUMERICS must be one of {sorted(_NUMERICS)}, got {_numerics!r}")
 _tls = threading.local()
+
+
+class _Setting:
+    """One call-side setting: its initial value from the environment (a bad one fails the import), a process-wide default (`set`) and a
+    thread-local override (`override`, a context manager).  get_numerics / get_weight_format read `_tls.<slot>`, then `default`."""
+
+    def __init__(self, env: str, default: str, values: dict, what: str, slot: str):
+        self.values, self.what, self.slot = values, what, slot
+        self.default = os.environ.get(env, default)
+        if self.default not in values:
+            raise ImportError(f"{env} must be one of {sorted(values)}, got {self.default!r}")
+
+    def check(self, name: str) -> None:
+        if name not in self.values:
+            raise ValueError(f"{self.what} must be one of {sorted(self.values)}")
+
+    def set(self, name: str) -> None:
+        self.check(name)
+        self.default = name
+
+    @contextlib.contextmanager
+    def override(self, name: str):
+        self.check(name)
+        prev = getattr(_tls, self.slot, None)
+        setattr(_tls, self.slot, name)
+        try:
+            yield
+        finally:
+            if prev is None:
+                delattr(_tls, self.slot)
+            else:
+                setattr(_tls, self.slot, prev)
+
+
+_NUMERICS = {"fast": _lib.TG_NUM_FAST, "reference": _lib.TG_NUM_REFERENCE, "fast_mfma": _lib.TG_NUM_FAST_MFMA, "fast_dot2": _lib.TG_NUM_FAST_DOT2}
+_numerics = _Setting("ANY4_NUMERICS", "fast", _NUMERICS, "numerics", "numerics")
 
 
 def get_numerics() -> str:
@@ -69,40 +101,24 @@ def get_numerics() -> str:
     every weight (include/tinygemm_hip.h, TG_NUM_FAST: no per-weight rounding, results within the reference's own weight
     rounding).  'reference': bit-identical dequantised weights (w = RNE16(fma(lut, scale, zero))), as the reference kernels.
     'fast_mfma': 'fast' with the m = 1 contraction of stacked launches on the MFMA instead of v_dot2 (TG_NUM_FAST_MFMA)."""
-    return getattr(_tls, "numerics", _numerics)
+    return getattr(_tls, "numerics", _numerics.default)
 
 
 def set_numerics(name: str) -> None:
     """Process-wide default (ANY4_NUMERICS in the environment sets the initial value)."""
-    global _numerics
-    if name not in _NUMERICS:
-        raise ValueError(f"numerics must be one of {sorted(_NUMERICS)}")
-    _numerics = name
+    _numerics.set(name)
 
 
-@contextlib.contextmanager
 def numerics(name: str):
     """Thread-local override: `with any4_amd.numerics("reference"): ...`"""
-    if name not in _NUMERICS:
-        raise ValueError(f"numerics must be one of {sorted(_NUMERICS)}")
-    prev = getattr(_tls, "numerics", None)
-    _tls.numerics = name
-    try:
-        yield
-    finally:
-        if prev is None:
-            del _tls.numerics
-        else:
-            _tls.numerics = prev
+    return _numerics.override(name)
 
 
 # ---------------------------------------------------------------------------------------------
 # packed format of weights-on-the-left (Aint4) tensors
 # ---------------------------------------------------------------------------------------------
 _WFORMATS = {"native": _lib.TG_WFMT_ROWS, "reference": _lib.TG_WFMT_M16N8K16}
-_wformat = os.environ.get("ANY4_WEIGHT_FORMAT", "native")
-if _wformat not in _WFORMATS:
-    raise ImportError(f"ANY4_WEIGHT_FORMAT must be one of {sorted(_WFORMATS)}, got {_wformat!r}")
+_wformat = _Setting("ANY4_WEIGHT_FORMAT", "native", _WFORMATS, "weight format", "wformat")
 
 
 def get_weight_format() -> str:
@@ -114,30 +130,16 @@ def get_weight_format() -> str:
     == 0) or 2 -- row-per-lane order, a packed word holds 8 codes of ONE weight row instead of 4 + 4 of rows r and r + 8; the
     A-side ops then run the B-side kernels (tg_w4_gemm.w_format = TG_WFMT_ROWS).  'reference': the reference's Aint4 tensor
     [ceil(m/16)][k/(16 I)][32][I], bit for bit (`relayout_Aint4` converts either way, losslessly)."""
-    return getattr(_tls, "wformat", _wformat)
+    return getattr(_tls, "wformat", _wformat.default)
 
 
 def set_weight_format(name: str) -> None:
-    global _wformat
-    if name not in _WFORMATS:
-        raise ValueError(f"weight format must be one of {sorted(_WFORMATS)}")
-    _wformat = name
+    _wformat.set(name)
 
 
-@contextlib.contextmanager
 def weight_format(name: str):
     """Thread-local override: `with any4_amd.weight_format("reference"): ...`"""
-    if name not in _WFORMATS:
-        raise ValueError(f"weight format must be one of {sorted(_WFORMATS)}")
-    prev = getattr(_tls, "wformat", None)
-    _tls.wformat = name
-    try:
-        yield
-    finally:
-        if prev is None:
-            del _tls.wformat
-        else:
-            _tls.wformat = prev
+    return _wformat.override(name)
 
 
 _auto_relayout = os.environ.get("ANY4_AUTO_RELAYOUT", "1") not in ("0", "false", "False", "")
@@ -402,9 +404,6 @@ class _FragX:
         return self.t.data_ptr()
 
 
-_WS_BYTES: dict = {}  # tg_gemm_w4_workspace_bytes per problem shape (pure function of the key below)
-
-
 _LARGE_M = None
 
 
@@ -459,39 +458,40 @@ def _library_gemm_w4(x, w, qinfo, lut, q_group, qtype, k, inner, wrows):
     return y
 
 
-def _w4_rm(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname, frag=False):
-    """Row-major activations / output.  Mirrors tinygemm_y_FT16RM_x_FT16RM_w_int4TC
-    (TinyGemm_int4.cu:294-548).  frag=True (weights on the right only): A is a _FragX, the output comes back in A-fragment
-    order [m/16][ceil(wrows/16)][32][8], or None when the library has no kernel that reads / writes fragment order itself
-    for this problem (TG_E_LAYOUT: the caller converts around a row-major call)."""
-    _check(A.device == B.device, "A and B must be on the same device")
+_RELAYOUT_HINT = ("the input gradient needs the native packed format of weights on the left; this tensor holds the reference's Aint4 "
+                  "words: call module.relayout(\"native\") (or any4_amd.ops.relayout_Aint4(w, k, \"native\")) once")
+_W_MSG = "weights must be a contiguous 4-D int32 tensor"
+
+
+def _w4_operands(t, k, w, q_group, qinfo, lut, qtype, weight_on_right, *, copies=True, aint4=True):
+    """The operand checks of a row-major 4-bit GEMM op, in one place: they mirror the TORCH_CHECKs of tinygemm_y_FT16RM_x_FT16RM_w_int4TC
+    (TinyGemm_int4.cu:294-548).  t: the call's 16-bit matrix (the activations; dY for the input gradient), its own shape checked by the
+    caller; k: the contraction length the packed weights have to cover.  Returns (inner, wrows, w_format, qtype, qinfo, lut) with
+    qinfo / lut contiguous and the LUT 16-byte aligned (the kernels read a LUT row as two 16-byte vectors).
+      copies=False  a non-contiguous qinfo / lut is an error instead of being copied (the fused op: it is called per decode step)
+      aint4=False   the reference's Aint4 words are refused with the relayout hint (the input gradient has no kernel for them)"""
+    _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous(), _W_MSG)
     if weight_on_right:
-        x, w = A, B
-        _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
-        _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous(), "weights must be a contiguous 4-D int32 tensor")
         inner = w.size(3) * 2
         _check(inner in (2, 4, 8), "Bint4 weights: innermost dim must be 1, 2 or 4")
         wrows = w.size(0) * 8
     else:
-        w, x = A, B
-        _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous(), "weights must be a contiguous 4-D int32 tensor")
-        _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
         inner = w.size(3)
         _check(inner in (1, 2, 4), "Aint4 weights: innermost dim must be 1, 2 or 4")
         wrows = w.size(0) * 16
-    m, k = x.shape
     k_tiles = _cdiv(k, 16)
     w_format = _lib.TG_WFMT_M16N8K16
     if not weight_on_right and w.size(1) != _cdiv(k_tiles, inner) and aside_format(w, k) == "native":
         # the tensor is the Bint4 tensor of the 16-row-padded weights (what the convert op returns by default): its shape says so
         w_format, inner, wrows = _lib.TG_WFMT_ROWS, w.size(3) * 2, w.size(0) * 8
+    _check(aint4 or weight_on_right or w_format == _lib.TG_WFMT_ROWS, _RELAYOUT_HINT)
     _check(w.size(1) == _cdiv(k_tiles, inner), "weights: k super-tiles do not match the activations' k")
     _check(w.size(2) == 32, "weights: dim 2 must be 32")
-    _check(x.dtype in _F16_TYPES, "activation dtype must be bfloat16 or float16")
+    _check(t.dtype in _F16_TYPES, "activation dtype must be bfloat16 or float16")
     _check(q_group in (32, 64, 128, 256), "qGroupSize must be 32, 64, 128 or 256")
-    _check(qinfo.device == x.device, "quantization info must be on the activations' device")
+    _check(qinfo.device == t.device, "quantization info must be on the activations' device")
     if qtype == TG_Q_MX4:
-        _check(x.dtype == torch.bfloat16, "mx4 supports bfloat16 activations only")
+        _check(t.dtype == torch.bfloat16, "mx4 supports bfloat16 activations only")
         _check(k % q_group == 0, "qGroupSize must divide k")
         _check(qinfo.dtype == torch.uint8 and qinfo.dim() == 2, "mx4Exponents must be a 2-D uint8 tensor")
         _check(qinfo.size(0) == wrows and qinfo.size(1) == k // q_group, "mx4Exponents must be [weight rows (tile padded)][k / qGroupSize]")
@@ -502,10 +502,10 @@ def _w4_rm(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname, frag=False
         _check(k // n_groups == q_group, "qScaleAndZeros.size(0) must equal k / qGroupSize")
         _check(qinfo.size(1) == wrows, "qScaleAndZeros.size(1) must equal the tile-padded weight rows")
         _check(qinfo.size(2) == 2, "qScaleAndZeros.size(2) must be 2")
-        _check(qinfo.dtype == x.dtype, "qScaleAndZeros dtype must match the activations")
+        _check(qinfo.dtype == t.dtype, "qScaleAndZeros dtype must match the activations")
     if lut is not None:
-        _check(lut.device == x.device, "int4DequantValues must be on the activations' device")
-        _check(lut.dtype == x.dtype, "int4DequantValues dtype must match the activations")
+        _check(lut.device == t.device, "int4DequantValues must be on the activations' device")
+        _check(lut.dtype == t.dtype, "int4DequantValues dtype must match the activations")
         if lut.dim() == 1:
             _check(lut.size(0) == 16, "int4DequantValues must have 16 entries")
             qtype = TG_Q_ANY4_GLOBAL
@@ -513,11 +513,58 @@ def _w4_rm(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname, frag=False
             _check(lut.dim() == 2 and lut.size(0) == wrows and lut.size(1) == 16,
                    "row-wise int4DequantValues must be [weight rows (tile padded)][16]")
             qtype = TG_Q_ANY4_ROWWISE
+        _check(copies or lut.is_contiguous(), "int4DequantValues must be contiguous")
         lut = lut.contiguous()
+    _check(copies or qinfo.is_contiguous(), "quantization info must be contiguous")
     qinfo = qinfo.contiguous()
     _check(k % 32 == 0 and k_tiles % inner == 0, "k must be a multiple of 32 and of innerKTiles * 16")
     if lut is not None and lut.data_ptr() % 16:
         lut = lut.clone()
+    return inner, wrows, w_format, qtype, qinfo, lut
+
+
+_WS_BYTES: dict = {}  # (entry point, problem shape) -> its tg_gemm_*_workspace_bytes (a pure function of the key)
+
+
+def _launch(entry, args, t, opname, key=None, soft=()):
+    """One call of the entry point tg_gemm_<entry> with the workspace it asks for: the bytes from the cache (`key`: what the planner's
+    answer depends on; None: ask every time) or from tg_gemm_<entry>_workspace_bytes, scratch from torch's caching allocator
+    (stream-ordered like every other temporary of the op), the launch on t's device and current stream, _lib.check.  Returns the
+    workspace bytes, or None when the library answers one of the codes in `soft` (no kernel of that kind: the caller does without)."""
+    ref = ctypes.byref(args)
+    key = None if key is None else (entry, *key)
+    ws_bytes = None if key is None else _WS_BYTES.get(key)
+    if ws_bytes is None:
+        ws_bytes = getattr(_L, f"tg_gemm_{entry}_workspace_bytes")(ref)
+        # (any other error code may come from THIS call's pointers -- a misaligned view -- and must not stick to the shape)
+        if key is not None and len(_WS_BYTES) < 4096 and (ws_bytes >= 0 or ws_bytes in soft):
+            _WS_BYTES[key] = ws_bytes
+    if ws_bytes in soft:
+        return None
+    if ws_bytes < 0:
+        _lib.check(ws_bytes, opname)
+    if ws_bytes > 0:
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=t.device)
+        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
+    rc = getattr(_L, f"tg_gemm_{entry}")(ref, _dev(t), _stream(t))
+    if rc in soft:
+        return None
+    _lib.check(rc, opname)
+    return ws_bytes
+
+
+def _w4_rm(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname, frag=False):
+    """Row-major activations / output.  Mirrors tinygemm_y_FT16RM_x_FT16RM_w_int4TC
+    (TinyGemm_int4.cu:294-548).  frag=True (weights on the right only): A is a _FragX, the output comes back in A-fragment
+    order [m/16][ceil(wrows/16)][32][8], or None when the library has no kernel that reads / writes fragment order itself
+    for this problem (TG_E_LAYOUT: the caller converts around a row-major call)."""
+    _check(A.device == B.device, "A and B must be on the same device")
+    x, w = (A, B) if weight_on_right else (B, A)
+    if not weight_on_right:  # (the op's arguments are looked at in its order: A first)
+        _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous(), _W_MSG)
+    _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
+    m, k = x.shape
+    inner, wrows, w_format, qtype, qinfo, lut = _w4_operands(x, k, w, q_group, qinfo, lut, qtype, weight_on_right)
     if not frag and m >= large_m_rows(wrows * k) and qtype != TG_Q_MX4 and k % 512 == 0 and (weight_on_right or w_format == _lib.TG_WFMT_ROWS):
         # OPT-IN (ANY4_LARGE_M_GEMM=library / ANY4_LARGE_M): dequantise in bounded row panels and hand the product to the GEMM library
         # (hipBLASLt behind torch.matmul).  The default keeps every call on this library's own kernels (tg_gemm_w4 -> plan 'tile').
@@ -551,26 +598,14 @@ def _w4_rm(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname, frag=False
     # (m = 1 latency path: one planner pass and no allocation when no scratch is needed).
     key = (m, wrows, k, q_group, qtype, args.dtype, args.w_on_right, inner, args.numerics, layout, bias is not None, args.w_format,
            _dev(x))
-    ws_bytes = _WS_BYTES.get(key)
+    ws_bytes = _launch("w4", args, x, opname, key, soft=(_lib.TG_E_LAYOUT,) if frag else ())
     if ws_bytes is None:
-        ws_bytes = _L.tg_gemm_w4_workspace_bytes(ctypes.byref(args))
-        # (an error code may come from THIS call's pointers -- a misaligned view -- and must not stick to the shape)
-        if len(_WS_BYTES) < 4096 and (ws_bytes >= 0 or ws_bytes == _lib.TG_E_LAYOUT):
-            _WS_BYTES[key] = ws_bytes
-    if frag and ws_bytes == _lib.TG_E_LAYOUT:
         return None
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, opname)
-    if ws_bytes > 0:  # scratch from torch's caching allocator: stream-ordered like every other temporary of the op
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
-    _lib.check(_L.tg_gemm_w4(ctypes.byref(args), _dev(x), _stream(x)), opname)
     sink = getattr(_tls, "plan_sink", None)
     if sink is not None and not frag:
         # a caller (modules._PackedLinear) keeps the validated argument struct to re-issue the same launch with new x / y (/ scratch) pointers
-        sink.append((W4Gemm.from_buffer_copy(args), x, (w, qinfo, lut, bias), opname, max(ws_bytes, 0)))
+        sink.append((W4Gemm.from_buffer_copy(args), x, (w, qinfo, lut, bias), opname, ws_bytes))
     return y
-
 
 
 class LaunchPlan:
@@ -674,33 +709,13 @@ def w4_linear_fused(x, w, q_group, qinfo, lut=None, *, residual=None, norm_weigh
 
     Returns y, or None when the library has no kernel with these stages for this problem (TG_E_FUSION: e.g. reference numerics,
     k % 2048 != 0, an activation block too large to stage on chip): the caller then runs the stage as its own launch."""
-    _check(x.dim() == 2 and x.is_contiguous() and x.dtype in _F16_TYPES, "activations must be a contiguous 2-D bf16 / fp16 matrix")
-    _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous() and w.size(2) == 32, "weights must be a contiguous Bint4 tensor")
-    inner, wrows = w.size(3) * 2, w.size(0) * 8
+    _check(w.device == x.device, "A and B must be on the same device")
+    _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
     m, k = x.shape
-    _check(w.size(1) * inner * 16 == k, "weights: k super-tiles do not match the activations' k")
-    _check(m > 0, "activations must have at least one row")
-    _check(inner in (2, 4, 8), "Bint4 weights: innermost dim must be 1, 2 or 4")
-    _check(q_group in (32, 64, 128, 256) and k % q_group == 0, "qGroupSize must be 32, 64, 128 or 256 and divide k")
-    _check(w.device == x.device, "weights must be on the activations' device")
     # the operand shapes the kernels index by (a mismatched tensor would be read out of bounds, not rejected): the checks of _w4_rm
-    qtype = TG_Q_INT4
-    if lut is not None:
-        _check(lut.dtype == x.dtype and lut.is_contiguous() and lut.device == x.device, "LUT must be contiguous, of the activations' dtype, on their device")
-        _check((lut.dim() == 1 and lut.size(0) == 16) or (lut.dim() == 2 and lut.size(0) == wrows and lut.size(1) == 16),
-               "int4DequantValues must be [16] or [weight rows (tile padded)][16]")
-        qtype = TG_Q_ANY4_GLOBAL if lut.dim() == 1 else TG_Q_ANY4_ROWWISE
-        if lut.data_ptr() % 16:
-            lut = lut.clone()
-    elif qinfo.dtype == torch.uint8:
-        qtype = TG_Q_MX4
-    _check(qinfo.is_contiguous() and qinfo.device == x.device, "quantization info must be contiguous on the activations' device")
-    if qtype == TG_Q_MX4:
-        _check(x.dtype == torch.bfloat16, "mx4 supports bfloat16 activations only")
-        _check(qinfo.dim() == 2 and qinfo.size(0) == wrows and qinfo.size(1) == k // q_group, "mx4Exponents must be [weight rows (tile padded)][k / qGroupSize]")
-    else:
-        _check(qinfo.dim() == 3 and qinfo.dtype == x.dtype and tuple(qinfo.shape) == (k // q_group, wrows, 2),
-               "qScaleAndZeros must be [k / qGroupSize][weight rows (tile padded)][2] of the activations' dtype")
+    qtype = TG_Q_MX4 if lut is None and qinfo.dtype == torch.uint8 else TG_Q_INT4
+    inner, wrows, _, qtype, qinfo, lut = _w4_operands(x, k, w, q_group, qinfo, lut, qtype, True, copies=False)
+    _check(m > 0, "activations must have at least one row")
     ycols = wrows // 2 if swiglu else wrows
     if out is None:
         out = torch.empty((m, ycols), dtype=x.dtype, device=x.device)
@@ -721,17 +736,8 @@ def w4_linear_fused(x, w, q_group, qinfo, lut=None, *, residual=None, norm_weigh
         norm_weight=(norm_weight.data_ptr() if norm_weight is not None else None), norm_eps=float(norm_eps),
         epilogue=_lib.TG_EPI_SWIGLU if swiglu else _lib.TG_EPI_NONE,
     )
-    ws_bytes = _L.tg_gemm_w4_workspace_bytes(ctypes.byref(args))
-    if ws_bytes == _lib.TG_E_FUSION:
-        return None
-    if ws_bytes > 0:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
-    rc = _L.tg_gemm_w4(ctypes.byref(args), _dev(x), _stream(x))
-    if rc == _lib.TG_E_FUSION:
-        return None
-    _lib.check(rc, "w4_linear_fused")
-    return out
+    # (no cache: the answer depends on the fused stages and the residual's row stride as well)
+    return None if _launch("w4", args, x, "w4_linear_fused", soft=(_lib.TG_E_FUSION,)) is None else out
 
 
 def _w4_tc(A, B, q_group, qinfo, lut, qtype, weight_on_right, opname):
@@ -800,51 +806,20 @@ def tinygemm_y_f16TC_x_f16TC_w_mx4TC(A, B, qGroupSize, mx4Exponents, weightOnRig
 # autograd of the row-major 4-bit GEMMs: the input gradient dX = dY . W (tg_gemm_w4_dx)
 # ---------------------------------------------------------------------------------------------
 
-_DX_WS_BYTES: dict = {}  # tg_gemm_w4_dx_workspace_bytes per problem shape
-
-_RELAYOUT_HINT = ("the input gradient needs the native packed format of weights on the left; this tensor holds the reference's Aint4 "
-                  "words: call module.relayout(\"native\") (or any4_amd.ops.relayout_Aint4(w, k, \"native\")) once")
-
-
 def _dx_rm(dY, w, q_group, qinfo, lut, qtype, weight_on_right, opname):
     """dX [m][k] = dY [m][wrows] . W: the input gradient of _w4_rm (weights as the forward op took them)."""
-    _check(dY.device == w.device, "dY and the weights must be on the same device")
+    _check(dY.device == w.device, "A and B must be on the same device")
     _check(dY.dim() == 2, "dY must be a 2-D matrix [activation rows][weight rows]")
-    _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous() and w.size(2) == 32, "weights must be a contiguous 4-D int32 tensor")
-    _check(dY.dtype in _F16_TYPES, "dY dtype must be bfloat16 or float16")
-    if weight_on_right:
-        inner, wrows, w_format = w.size(3) * 2, w.size(0) * 8, _lib.TG_WFMT_M16N8K16
-        _check(inner in (2, 4, 8), "Bint4 weights: innermost dim must be 1, 2 or 4")
-    else:
-        # the native tensor (Bint4 words of the rows padded to 16) covers size(0) * 8 rows; the reference's Aint4 words size(0) * 16
-        _check(dY.size(1) != w.size(0) * 16, _RELAYOUT_HINT)
-        inner, wrows, w_format = w.size(3) * 2, w.size(0) * 8, _lib.TG_WFMT_ROWS
-        _check(wrows % 16 == 0 and inner in (2, 4), _RELAYOUT_HINT)
+    _check(w.dim() == 4 and w.dtype == torch.int32 and w.is_contiguous(), _W_MSG)
+    # k is read off the packed tensor, in Bint4 words on either side: the native weights-on-the-left tensor is the Bint4 tensor of the rows
+    # padded to 16 and covers size(0) * 8 rows; the reference's Aint4 words (size(0) * 16 rows) have no dx kernel
+    inner = w.size(3) * 2
     k = w.size(1) * inner * 16
-    _check(weight_on_right or inner == _rows_inner(k), _RELAYOUT_HINT)
+    if not weight_on_right:
+        _check(dY.size(1) != w.size(0) * 16 and w.size(0) % 2 == 0 and inner in (2, 4) and inner == _rows_inner(k), _RELAYOUT_HINT)
+    inner, wrows, w_format, qtype, qinfo, lut = _w4_operands(dY, k, w, q_group, qinfo, lut, qtype, weight_on_right, aint4=False)
     m = dY.size(0)
     _check(dY.size(1) == wrows, "dY.size(1) must equal the tile-padded weight rows")
-    _check(q_group in (32, 64, 128, 256) and k % q_group == 0, "qGroupSize must be 32, 64, 128 or 256 and divide k")
-    _check(qinfo.device == dY.device, "quantization info must be on dY's device")
-    if qtype == TG_Q_MX4:
-        _check(dY.dtype == torch.bfloat16, "mx4 supports bfloat16 only")
-        _check(qinfo.dtype == torch.uint8 and qinfo.dim() == 2 and qinfo.size(0) == wrows and qinfo.size(1) == k // q_group,
-               "mx4Exponents must be [weight rows (tile padded)][k / qGroupSize] uint8")
-    else:
-        _check(qinfo.dim() == 3 and tuple(qinfo.shape) == (k // q_group, wrows, 2) and qinfo.dtype == dY.dtype,
-               "qScaleAndZeros must be [k / qGroupSize][weight rows][2] of dY's dtype")
-    if lut is not None:
-        _check(lut.device == dY.device and lut.dtype == dY.dtype, "int4DequantValues must be on dY's device, of dY's dtype")
-        if lut.dim() == 1:
-            _check(lut.size(0) == 16, "int4DequantValues must have 16 entries")
-            qtype = TG_Q_ANY4_GLOBAL
-        else:
-            _check(lut.dim() == 2 and lut.size(0) == wrows and lut.size(1) == 16, "row-wise int4DequantValues must be [weight rows (tile padded)][16]")
-            qtype = TG_Q_ANY4_ROWWISE
-        lut = lut.contiguous()
-        if lut.data_ptr() % 16:
-            lut = lut.clone()
-    qinfo = qinfo.contiguous()
     dx = torch.empty((m, k), dtype=dY.dtype, device=dY.device)
     if m == 0:
         return dx
@@ -855,18 +830,8 @@ def _dx_rm(dY, w, q_group, qinfo, lut, qtype, weight_on_right, opname):
     args = W4Gemm(x=dy.data_ptr(), w=w.data_ptr(), qinfo=qinfo.data_ptr(), lut=(lut.data_ptr() if lut is not None else None), y=dx.data_ptr(),
                   m=m, wrows=wrows, k=k, group=q_group, qtype=qtype, dtype=_dt(dy), w_on_right=1 if weight_on_right else 0,
                   inner_k_tiles=inner, batch=1, w_format=w_format)
-    key = (m, wrows, k, q_group, qtype, args.dtype, args.w_on_right, inner, _dev(dy))
-    ws_bytes = _DX_WS_BYTES.get(key)
-    if ws_bytes is None:
-        ws_bytes = _L.tg_gemm_w4_dx_workspace_bytes(ctypes.byref(args))
-        if ws_bytes >= 0 and len(_DX_WS_BYTES) < 4096:
-            _DX_WS_BYTES[key] = ws_bytes
-    if ws_bytes < 0:
-        _lib.check(ws_bytes, opname)
-    if ws_bytes > 0:  # f32 partials of the split over the weight rows, from torch's caching allocator (stream-ordered)
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dy.device)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
-    _lib.check(_L.tg_gemm_w4_dx(ctypes.byref(args), _dev(dy), _stream(dy)), opname)
+    # (the workspace: f32 partials of the split over the weight rows)
+    _launch("w4_dx", args, dy, opname, (m, wrows, k, q_group, qtype, args.dtype, args.w_on_right, inner, _dev(dy)))
     return dx
 
 
@@ -1054,16 +1019,7 @@ def tinygemm_y_f16RM_x_f16RM_w_int8TC(A, B, qGroupSize, qScaleAndZeros, weightOn
                   group=qGroupSize, qtype=_lib.TG_Q_INT8, dtype=_dt(x), w_on_right=1 if weightOnRight else 0,
                   inner_k_tiles=inner, batch=1, bias=(bias.data_ptr() if bias is not None else None))
     # many activation rows of innerKTiles-2 words: the tile GEMM's int8 flavour, split-K with a scratch from the caching allocator
-    key = ("w8", m, wrows, k, qGroupSize, args.dtype, args.w_on_right, inner, bias is not None, _dev(x))
-    ws_bytes = _WS_BYTES.get(key)
-    if ws_bytes is None:
-        ws_bytes = _L.tg_gemm_w8_workspace_bytes(ctypes.byref(args))
-        if len(_WS_BYTES) < 4096 and ws_bytes >= 0:
-            _WS_BYTES[key] = ws_bytes
-    if ws_bytes > 0:
-        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=x.device)
-        args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
-    _lib.check(_L.tg_gemm_w8(ctypes.byref(args), _dev(x), _stream(x)), opname)
+    _launch("w8", args, x, opname, (m, wrows, k, qGroupSize, args.dtype, args.w_on_right, inner, bias is not None, _dev(x)))
     return y
 
 

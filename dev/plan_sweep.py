@@ -1,0 +1,153 @@
+"""What the C ABI answers over a grid of calls, as a digest (developer tool; needs no GPU: the planner and all validation run before any HIP call):
+    python dev/plan_sweep.py [--lib PATH/libtinygemm_hip.so] [--quick]     the planner: workspace bytes and kernel family of every case
+    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...]           return codes of N broken structs per entry point
+Prints the number of cases, a histogram of the answers and a sha256 over their sequence.  Two builds route / validate alike when they
+print the same digest for the same script; run it before and after a change of the host launch path (or with --lib on an older build).
+No digest is recorded anywhere: a performance change may move the routing on purpose.
+"""
+import argparse
+import collections
+import ctypes
+import hashlib
+import itertools
+import os
+import random
+import sys
+from array import array
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+from any4_amd import _lib as L  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--lib", default=L.LIB_PATH)
+ap.add_argument("--quick", action="store_true", help="a 1/96 sub-grid of the planner sweep")
+ap.add_argument("--errors", nargs="?", type=int, const=100000, default=0, metavar="N")
+ap.add_argument("--seed", type=int, default=0)
+opt = ap.parse_args()
+lib = ctypes.CDLL(opt.lib)
+P = ctypes.POINTER(L.W4Gemm)
+for name in ("tg_gemm_w4", "tg_gemm_w4_dx", "tg_gemm_w8"):
+    getattr(lib, name).argtypes = [P, ctypes.c_int, ctypes.c_void_p]
+    getattr(lib, name + "_workspace_bytes").argtypes = [P]
+    getattr(lib, name + "_workspace_bytes").restype = ctypes.c_int64
+lib.tg_gemm_w4_plan.argtypes = [P, ctypes.c_int]
+
+BASE = 1 << 20          # dummy pointers, 64-byte aligned: nothing is launched, so nothing reads them
+NO_DEVICE = 1 << 20     # a device index no machine has: a launch entry point with a valid struct answers TG_E_DEVICE instead of launching
+
+
+def report(title, answers):
+    """answers: array('q') of everything recorded, in order"""
+    hist = collections.Counter(answers[1::2]) if title.startswith("planner") else collections.Counter(answers)
+    print(f"{title}: {len(answers) // 2 if title.startswith('planner') else len(answers)} cases")
+    shown = sorted(hist.items())[:24]
+    print("  answers: " + ", ".join(f"{k}: {v}" for k, v in shown) + (f", ... ({len(hist)} different)" if len(hist) > len(shown) else ""))
+    print("  sha256 " + hashlib.sha256(answers.tobytes()).hexdigest())
+
+
+def valid(**kw):
+    a = L.W4Gemm(x=BASE, w=2 * BASE, qinfo=3 * BASE, lut=4 * BASE, y=5 * BASE, m=1, wrows=4096, k=4096, group=128, qtype=0, dtype=0,
+                 w_on_right=1, inner_k_tiles=4, batch=1)
+    for k, v in kw.items():
+        setattr(a, k, v)
+    return a
+
+
+def planner():
+    """(workspace bytes, plan) of tg_gemm_w4 over the main grid, then the smaller legs: fused stages, dx, w8"""
+    a = valid(stride_x=16, stride_w=16, stride_qinfo=16, stride_lut=16, stride_y=16)
+    ref = ctypes.byref(a)
+    wsb, plan = lib.tg_gemm_w4_workspace_bytes, lib.tg_gemm_w4_plan
+    out = array("q")
+    ms = (1, 2, 4, 5, 8, 9, 16, 17, 33, 64, 65, 512)
+    rows = (16, 4096, 4104, 14336, 28672, 32832)
+    ks = (64, 512, 4096, 8192, 14336)
+    if opt.quick:
+        ms, rows, ks = ms[::4], rows[::4], ks[::2] + (14336,)
+
+    def pair():
+        a.workspace, a.workspace_bytes = None, 0
+        need = wsb(ref)
+        out.append(need)
+        out.append(plan(ref, -1))
+        if need > 0:  # ... and with the workspace it asked for
+            a.workspace, a.workspace_bytes = 6 * BASE, need
+        out.append(need)
+        out.append(plan(ref, -1))
+
+    inner = list(itertools.product((1, 16, 64), range(4), (0, 1), (0, 1)))
+    for a.m, a.wrows, a.k, a.group, a.qtype, a.dtype, a.w_on_right, a.inner_k_tiles in itertools.product(
+            ms, rows, ks, (32, 64, 128, 256), range(4), (0, 1), (1, 0), (1, 2, 4, 8)):
+        for a.batch, a.numerics, a.w_format, frag in inner:
+            a.x_layout = a.y_layout = frag
+            pair()
+    report("planner, tg_gemm_w4", out)
+
+    # fused stages on the same entry point: norm_weight / SwiGLU / a bias with a row stride
+    out = array("q")
+    a = valid()
+    ref = ctypes.byref(a)
+    for a.m, a.wrows, a.k, a.group, a.qtype, a.w_on_right, a.inner_k_tiles, a.batch, a.numerics in itertools.product(
+            (1, 4, 8, 16, 17, 64), (4096, 4104, 14336, 28672), (512, 4096, 8192), (32, 64, 128), range(4), (1, 0), (2, 4), (1, 16), range(4)):
+        for norm, a.epilogue, bias in itertools.product((0, 1), (0, 1), (0, 1, 2)):
+            a.norm_weight = 7 * BASE if norm else None
+            a.bias, a.bias_row_stride = (8 * BASE if bias else None), (a.wrows if bias == 2 else 0)
+            pair()
+    report("planner, tg_gemm_w4 with fused stages", out)
+
+    # the other two entry points report workspace bytes only
+    out = array("q")
+    a = valid()
+    ref = ctypes.byref(a)
+    for a.m, a.wrows, a.k, a.group, a.dtype, a.w_on_right, a.inner_k_tiles in itertools.product(
+            (1, 16, 17, 33, 64, 65, 512, 4096), rows, ks, (32, 64, 128, 256), (0, 1), (1, 0), (1, 2, 4, 8)):
+        for a.qtype, a.w_format in itertools.product(range(4), (0, 1)):
+            out.append(lib.tg_gemm_w4_dx_workspace_bytes(ref))
+        a.qtype, a.w_format = L.TG_Q_INT8, 0
+        for a.batch in (1, 16):
+            out.append(lib.tg_gemm_w8_workspace_bytes(ref))
+        a.batch = 1
+    report("workspace bytes, tg_gemm_w4_dx / tg_gemm_w8", out)
+
+
+# ---- error codes: start from a valid struct, break one, two or three fields ----
+_PTR = (None, BASE + 4, BASE + 8, BASE)
+_SIZE = (0, -1, 1 << 31, (1 << 31) - 1, 1 << 20, 17, 4104, 96, 4096)
+_STRIDE = (0, 16, 8, 4, 2)
+_FULL, _PREFIX = ctypes.sizeof(L.W4Gemm), L.W4Gemm.stride_y.offset + 8
+BREAKS = {
+    "x": _PTR, "w": _PTR, "qinfo": _PTR + (BASE + 2,), "lut": _PTR, "y": _PTR + (BASE + 2,), "bias": _PTR, "norm_weight": _PTR, "workspace": _PTR,
+    "m": _SIZE, "wrows": _SIZE, "k": _SIZE,
+    "group": (0, 16, 32, 64, 128, 256, 512, 48, -32), "qtype": (-1, 0, 1, 2, 3, 4, 5), "dtype": (-1, 0, 1, 2), "w_on_right": (0, 1, 2),
+    "inner_k_tiles": (-1, 0, 1, 2, 3, 4, 8, 16), "batch": (-1, 0, 1, 2, 16),
+    "stride_x": _STRIDE, "stride_w": _STRIDE, "stride_qinfo": _STRIDE, "stride_lut": _STRIDE, "stride_y": _STRIDE, "stride_bias": _STRIDE,
+    "numerics": (-1, 0, 1, 2, 3, 4), "reserved": (0, 1), "reserved6": (0, 1), "workspace_bytes": (-1, 0, 1 << 20),
+    "x_layout": (0, 1, 2), "y_layout": (0, 1, 2), "bias_row_stride": (-4, 0, 2, 4, 4096), "epilogue": (0, 1, 2), "w_format": (0, 1, 2),
+    "struct_bytes": (0, _PREFIX - 8, _PREFIX, _FULL - 8, _FULL, _FULL + 8), "struct_reserved": (0, 1),
+}
+
+
+def errors(n):
+    names = sorted(BREAKS)
+    entries = [("tg_gemm_w4", lambda r: lib.tg_gemm_w4(r, NO_DEVICE, None), 0),
+               ("tg_gemm_w4_plan", lambda r: lib.tg_gemm_w4_plan(r, -1), 0),
+               ("tg_gemm_w4_workspace_bytes", lib.tg_gemm_w4_workspace_bytes, 0),
+               ("tg_gemm_w4_dx", lambda r: lib.tg_gemm_w4_dx(r, NO_DEVICE, None), 0),
+               ("tg_gemm_w4_dx_workspace_bytes", lib.tg_gemm_w4_dx_workspace_bytes, 0),
+               ("tg_gemm_w8", lambda r: lib.tg_gemm_w8(r, NO_DEVICE, None), L.TG_Q_INT8),
+               ("tg_gemm_w8_workspace_bytes", lib.tg_gemm_w8_workspace_bytes, L.TG_Q_INT8)]
+    for e, (name, fn, qtype) in enumerate(entries):
+        rng = random.Random(1000 * opt.seed + e)
+        out = array("q")
+        for _ in range(n):
+            a = valid(qtype=qtype, m=rng.choice((1, 8, 16, 64)), inner_k_tiles=rng.choice((2, 4)))
+            for f in rng.sample(names, rng.choice((1, 2, 3))):
+                setattr(a, f, rng.choice(BREAKS[f]))
+            out.append(fn(ctypes.byref(a)))
+        report(name, out)
+
+
+if opt.errors:
+    errors(opt.errors)
+else:
+    planner()

@@ -249,7 +249,9 @@ TG_API int tg_gemm_w4(const tg_w4_gemm* args, int device, tg_stream_t stream);
  *                                          v_dot2 contraction, fused norm / residual / SwiGLU stages
  *   TG_PLAN_TILE    w4_gemm_tile_kernel    more than 64 activation rows (Bint4 innerKTiles 4, int4 / any4): an LDS-tiled MFMA GEMM
  *                                          (128 x 64 / 128 tiles) whose weight tile is dequantised on the way in -- the reference's
- *                                          weights bit for bit (both numerics settings), no workspace  */
+ *                                          weights bit for bit (both numerics settings).  With the caller's workspace
+ *                                          (tg_gemm_w4_workspace_bytes) a launch of fewer tiles than compute units is split over k,
+ *                                          f32 partial tiles in the workspace; that way ONE layer takes this kernel from 17 rows  */
 enum { TG_PLAN_SPLITK = 1, TG_PLAN_STREAM = 2, TG_PLAN_PAIR = 3, TG_PLAN_PAIR_XR = 4, TG_PLAN_GEMV = 5, TG_PLAN_TILE = 6 };
 enum { TG_LAYOUT_RM = 0, TG_LAYOUT_TC_A = 1 };
 TG_API int tg_gemm_w4_plan(const tg_w4_gemm* args, int device);

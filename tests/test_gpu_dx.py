@@ -23,7 +23,7 @@ def T():
 
 
 class _NoWorkspace(dict):
-    """stands in for ops._DX_WS_BYTES: every call asks for no workspace, so the dx kernel runs unsplit"""
+    """stands in for ops._WS_BYTES (the cache of workspace bytes per entry point and shape): every call asks for no workspace, so the dx kernel runs unsplit"""
 
     def get(self, key, default=None):
         return 0
@@ -95,7 +95,7 @@ def test_dx_inner_and_split(T, oracle, inner, split, monkeypatch):
     from any4_amd import ops
 
     if not split:
-        monkeypatch.setattr(ops, "_DX_WS_BYTES", _NoWorkspace())
+        monkeypatch.setattr(ops, "_WS_BYTES", _NoWorkspace())
     # many k tiles (k = 1024) and 2048 weight rows: with the workspace the launch splits over the weight rows (m = 16 fills few CUs)
     _check_grad(T, oracle, 2048, 1024, 128, 16, "int4", torch.bfloat16, True, inner)
     _check_grad(T, oracle, 2048, 96 if inner == 2 else 1024, 32, 16, "any4_global", torch.float16, True, inner if inner == 2 else 4)

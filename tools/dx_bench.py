@@ -86,7 +86,7 @@ def bench_layers(ms, iters, rounds, emit):
             emit({"what": "layer", "layer": name, "wrows": n, "k": k, "m": m, **{f"{a}_us": round(b, 2) for a, b in t.items()},
                   "dx_over_fwd": round(t["dx"] / t["fwd"], 3), "dx_tflops": round(2 * m * n * k / t["dx"] / 1e6, 1),
                   "max_rel_err_dx": err_dx, "max_rel_err_deq_mm": err_mm,
-                  "dx_workspace_bytes": ops._DX_WS_BYTES.get((m, n, k, g, ops.TG_Q_ANY4_ROWWISE, 0, 1, 4, dev.index))})
+                  "dx_workspace_bytes": ops._WS_BYTES.get(("w4_dx", m, n, k, g, ops.TG_Q_ANY4_ROWWISE, 0, 1, 4, dev.index))})
 
 
 def bench_module(iters, rounds, emit):
