@@ -33,6 +33,7 @@ UNITS = [
     ("tg_gemv", "tg_gemv.hip", []),
     ("tg_tile", "tg_tile.hip", []),
     ("tg_dx", "tg_dx.hip", []),
+    ("tg_prefill", "tg_prefill.hip", []),
     ("tinygemm_hip", "tinygemm_hip.hip", []),
 ]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-comment", "-Wno-int-to-pointer-cast"]

@@ -13,6 +13,7 @@
 //   tg_gemv.hip        w4_gemv_kernel            (w4_gemv.cuh)
 //   tg_tile.hip        w4_gemm_tile_kernel       (w4_gemm_tile.cuh)
 //   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
+//   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once

@@ -1,11 +1,13 @@
-"""Batch-1 decode harness around the quantized linears (BASELINE config 5).
+"""Decode harness around the quantized linears (BASELINE config 5): prompt prefill and one-token decode steps.
 
 The reference measures model-level speed with `benchmark.py:113-215`: a HuggingFace causal LM, every
 `nn.Linear` except the LM head swapped for the quantized module by `quantize_model` (quantize.py:32-85),
 forward on random `input_ids[bs, seqlen]`.  Neither checkpoints nor the hub are reachable here, so this
 module builds the same *shape* of work from scratch -- a Llama-architecture decoder (RMSNorm, rotary
 embeddings, grouped-query attention over a static KV cache, SwiGLU MLP) with random-initialised weights of
-the named configuration -- and runs ONE decode step (one new token per sequence) through it.  Everything
+the named configuration -- and runs ONE decode step (one new token per sequence) through it; `DecodeStack.prefill` feeds a whole
+prompt (T tokens per sequence at once: the linears at bs * T rows, causal flash attention that appends T cache rows) so that the cache
+holds a real context before a step is timed or tested, and `DecodeStack.generate` chains the two.  Everything
 except the linears is plain torch (plumbing); the linears are whatever the `linear_factory` returns:
 `Any4Factory` (the product: `Any4Linear` on the HIP kernels) or `DenseFactory` (bf16 `nn.Linear`, the
 baseline the reference's README quotes speedups against).
@@ -179,6 +181,28 @@ def _rope(x, cos, sin):
     return (x.float() * cos + rot.float() * sin).to(x.dtype)
 
 
+def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl: int, kvl: int, d: int, T: int):
+    """Plain-torch formulation of a prefill chunk's attention (what dg_prefill_attn is tested against; also the CPU path).
+    qkv [bs * T, (hl + 2 kvl) d], row b * T + t = token t of sequence b at position p0 + t.  Ropes q and k with the table rows
+    [p0, p0 + T), writes the T k / v rows into the caches and attends over cache[:, :, :p0 + T] with the mask s > p0 + t; rounding
+    points as in DecodeLayer.forward: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit P.V.
+    Returns the context [bs * T, hl * d]."""
+    bs, rep, S = qkv.shape[0] // T, hl // kvl, p0 + T
+    rows = torch.arange(p0, S, device=qkv.device)
+    cos, sin = cos_tab[p0:S].view(1, T, 1, d), sin_tab[p0:S].view(1, T, 1, d)
+    q = _rope(qkv[:, : hl * d].reshape(bs, T, hl, d), cos, sin)
+    k = _rope(qkv[:, hl * d: (hl + kvl) * d].reshape(bs, T, kvl, d), cos, sin)
+    v = qkv[:, (hl + kvl) * d:].reshape(bs, T, kvl, d)
+    k_cache.index_copy_(2, rows, k.transpose(1, 2))
+    v_cache.index_copy_(2, rows, v.transpose(1, 2))
+    qg = q.reshape(bs, T, kvl, rep, d).permute(0, 2, 3, 1, 4).reshape(bs, kvl, rep * T, d)
+    att = torch.matmul(qg, k_cache[:, :, :S].transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep * T, S]
+    mask = torch.arange(S, device=qkv.device).view(1, S) > rows.view(T, 1)                    # [T, S]: s > p0 + t
+    att = att.view(bs, kvl, rep, T, S).masked_fill(mask, float("-inf")).softmax(-1).to(qkv.dtype).view(bs, kvl, rep * T, S)
+    ctx = torch.matmul(att, v_cache[:, :, :S])                                                  # [bs, kvl, rep * T, d]
+    return ctx.view(bs, kvl, rep, T, d).permute(0, 3, 1, 2, 4).reshape(bs * T, hl * d)
+
+
 class DecodeLayer(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int):
         super().__init__()
@@ -234,6 +258,29 @@ class DecodeLayer(torch.nn.Module):
         h, y = G.add_rmsnorm(h, gather(self.o(gather(ctx))), self.norm2.weight, self.norm2.eps)
         return h, gather(self.down(gather(G.swiglu(self._split_gate_up(self.gate_up(y)).contiguous()))))
 
+    def forward_prefill(self, h, pos, T, cos_tab, sin_tab, gather, fused=False, delta=None, p0=None):
+        """A chunk of T tokens per sequence: `h` [bs * T, hidden] (row b * T + t), `pos` [1] int64 = position of token 0.  The T
+        rows of k / v are appended to the caches and every token attends causally over cache + chunk.  Returns (h, delta) as
+        forward_fused does (`delta` = this layer's not-yet-added MLP output; None on the plain path, which adds it itself).
+        fused: forward_fused's sequence at bs * T rows -- add_rmsnorm, qkv linear, prefill_attn (include/decode_glue_hip.h), o linear,
+        add_rmsnorm, gate_up linear, swiglu, down linear; the linears are called as modules, so the library routes them (the LDS-tiled
+        GEMM above 64 rows).  Otherwise plain torch (`prefill_attention_torch`), which needs the position on the host: `p0`."""
+        cfg, d = self.cfg, self.cfg.head_dim
+        if fused:
+            from . import decode_ops as G
+
+            h, y = G.add_rmsnorm(h, delta, self.norm1.weight, self.norm1.eps)
+            ctx = G.prefill_attn(self.qkv(y), cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d,
+                                 1.0 / math.sqrt(d), T)
+            h, y = G.add_rmsnorm(h, gather(self.o(gather(ctx))), self.norm2.weight, self.norm2.eps)
+            return h, gather(self.down(gather(G.swiglu(self._split_gate_up(self.gate_up(y)).contiguous()))))
+        p0 = int(pos) if p0 is None else int(p0)
+        ctx = prefill_attention_torch(self.qkv(self.norm1(h)), cos_tab, sin_tab, p0, self.k_cache, self.v_cache, self.hl, self.kvl, d, T)
+        h = h + gather(self.o(gather(ctx)))
+        gu = self._split_gate_up(self.gate_up(self.norm2(h)))
+        il = cfg.inter // self.world
+        act = torch.nn.functional.silu(gu[:, :il]) * gu[:, il:]
+        return h + gather(self.down(gather(act))), None
 
     # ---- five launches per layer: every element-wise stage rides in a GEMM launch (tg_w4_gemm ABI 5) ----
     def _w4(self, lin, x, **kw):
@@ -365,6 +412,8 @@ class DecodeStack(torch.nn.Module):
         # static inputs (so a captured graph can be replayed with new values)
         self.register_buffer("tokens", torch.zeros(bs, dtype=torch.long, device=device), persistent=False)
         self.register_buffer("pos", torch.zeros(1, dtype=torch.long, device=device), persistent=False)
+        # prefill's own position (a captured decode graph reads `pos`; a prefill between two replays must not move it)
+        self.register_buffer("prefill_pos", torch.zeros(1, dtype=torch.long, device=device), persistent=False)
         self._graph = None
         self._out = None
         self._decodes = 0
@@ -387,13 +436,13 @@ class DecodeStack(torch.nn.Module):
                 self._attn_scratch = G.rope_attn_split_scratch(bs, hl, cfg.head_dim, self._attn_split, device)
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
-    def _gather(self, y):
+    def _gather(self, y, peer_ok=True):
         if self.world == 1:
             return y
         y = y.contiguous()
         if self.emulate_gather:
             return y.repeat(1, self.world)
-        if self.gather_mode == "peer":
+        if self.gather_mode == "peer" and peer_ok:
             from .shard import PeerWriteGather
 
             pg = self._peer.get(y.shape[1])
@@ -488,6 +537,80 @@ class DecodeStack(torch.nn.Module):
             for pg in self._peer.values():
                 pg.poll()
         return out
+
+    # ---- prompt prefill ----
+    def _gather_rows(self, y):
+        """_gather for bs * T rows: always the all_gather branch (the peer-write buffers are sized for `bs` rows)."""
+        return self._gather(y, peer_ok=False)
+
+    def _prefill_chunk(self, toks, p0, want_logits):
+        T = toks.shape[1]
+        h = self.embed(toks.reshape(-1))  # [bs * T, hidden], row b * T + t
+        delta = None
+        for layer in self.layers:
+            h, delta = layer.forward_prefill(h, self.prefill_pos, T, self.cos, self.sin, self._gather_rows, fused=self.fused,
+                                             delta=delta, p0=p0)
+        if not want_logits:
+            return None
+        # the LM head runs on the last token of every sequence only
+        h = h.view(self.bs, T, -1)[:, -1].contiguous()
+        if self.fused:
+            from . import decode_ops as G
+
+            _, y = G.add_rmsnorm(h, delta.view(self.bs, T, -1)[:, -1].contiguous(), self.norm.weight, self.norm.eps)
+            if self.lm_head is None:
+                return y
+            logits = G.linear16(y, self.lm_head.weight) if self.lm_head.bias is None else None
+            return logits if logits is not None else self.lm_head(y)
+        h = self.norm(h)
+        return self.lm_head(h) if self.lm_head is not None else h
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, position: Optional[int] = 0, chunk: Optional[int] = None) -> torch.Tensor:
+        """Feed a prompt: `tokens` [bs, T] at sequence positions position ... position + T - 1.  Every layer's KV cache receives the T
+        rows a token-by-token `decode()` would have written (bit for bit on the fused path), and the logits [bs, vocab] of the LAST
+        token are returned (the final hidden state when built without LM head) -- `decode()` continues at position + T.
+        chunk: tokens per pass (default: the whole prompt up to 2048 tokens, longer prompts in pieces of 2048); later pieces attend
+        over the cache rows of the earlier ones, which bounds activation memory at bs * chunk rows.
+        Eager.  It is also legal inside `torch.cuda.graph` for a fixed T; the position lives in `self.prefill_pos` (not `self.pos`, so a
+        captured decode graph is not disturbed): pass position=None to leave that buffer as the caller set it (single chunk, fused
+        path only; the kernel itself ignores tokens whose position is outside the cache).
+        world > 1: attention stays local (heads are split across ranks); the four exchanges of a layer are all_gathers at bs * T
+        rows, also with gather="peer" (the peer-write buffers are sized for the `bs` rows of a decode step)."""
+        if tokens.dim() != 2 or tokens.shape[0] != self.bs or tokens.shape[1] < 1:
+            raise ValueError(f"tokens must be [bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
+        T = tokens.shape[1]
+        if position is None:
+            if not self.fused or (chunk is not None and int(chunk) < T):
+                raise ValueError("position=None (the caller owns prefill_pos) needs the fused path and a single chunk")
+            return self._prefill_chunk(tokens, None, True)
+        position = int(position)
+        if position < 0 or position + T > self.cfg.max_seq:
+            raise ValueError(f"positions [{position}, {position + T}) outside the KV cache [0, {self.cfg.max_seq})")
+        chunk = min(T, 2048) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        out = None
+        for c0 in range(0, T, chunk):
+            self.prefill_pos.fill_(position + c0)
+            out = self._prefill_chunk(tokens[:, c0: c0 + chunk], position + c0, c0 + chunk >= T)
+        return out
+
+    @torch.no_grad()
+    def generate(self, prompt: torch.Tensor, new_tokens: int) -> torch.Tensor:
+        """Greedy continuation: `prefill(prompt)` [bs, T], then `decode` (graph replay if captured) from position T.
+        Returns the `new_tokens` generated token ids [bs, new_tokens]."""
+        if self.lm_head is None:
+            raise ValueError("generate needs the LM head")
+        if new_tokens < 1:
+            raise ValueError(f"new_tokens must be >= 1, got {new_tokens}")
+        T = prompt.shape[1] if prompt.dim() == 2 else 0
+        tok = self.prefill(prompt).argmax(-1)
+        out = [tok.clone()]
+        for i in range(new_tokens - 1):
+            tok = self.decode(tok, T + i).argmax(-1)
+            out.append(tok.clone())
+        return torch.stack(out, dim=1)
 
 
 def memory_allocated_mb(device=None) -> float:

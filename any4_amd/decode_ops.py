@@ -1,4 +1,5 @@
-"""ctypes front-end of include/decode_glue_hip.h: the non-GEMM kernels of a batch-1 decode step.
+"""ctypes front-end of include/decode_glue_hip.h: the non-GEMM kernels of a decode step (one new token per sequence) and of the
+prompt prefill in front of it (`prefill_attn`: a chunk of tokens per sequence).
 
 Every function takes torch tensors on a ROCm device, allocates the output with `torch.empty` (caching
 allocator, current stream) and launches on `torch.cuda.current_stream()`; they are legal inside
@@ -119,6 +120,29 @@ def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos
                                               v_cache.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, bs, hl,
                                               kvl, d, max_seq, float(scale), nsplit, _dt(qkv), qkv.device.index, _stream(qkv)),
                "dg_rope_attn_split")
+    return out
+
+
+def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
+                 v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None) -> torch.Tensor:
+    """A chunk of T tokens per sequence: qkv [bs * T, (hl + 2 kvl) d] (row b * T + t) -> context [bs * T, hl * d]; the T roped k rows and
+    the v rows are appended to the caches at positions pos ... pos + T - 1 (`pos` [1] int64 on the device = position of token 0), and
+    token t attends causally over cache rows 0 ... pos + t.  A token whose position is outside the cache writes nothing and leaves its
+    row of `out` (allocated here unless given) as it was."""
+    _gpu(qkv, cos, sin, pos, k_cache, v_cache, out)
+    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
+        raise RuntimeError("rope tables must be float32 and pos int64")
+    T = int(T)
+    if T < 1 or qkv.dim() != 2 or qkv.shape[0] % T or qkv.shape[0] // T != k_cache.shape[0]:
+        raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {k_cache.shape[0]} (the caches'), got {tuple(qkv.shape)}")
+    bs, max_seq = qkv.shape[0] // T, k_cache.shape[2]
+    if out is None:
+        out = torch.empty((bs * T, hl * d), dtype=qkv.dtype, device=qkv.device)
+    elif out.shape != (bs * T, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"prefill_attn: out must be [{bs * T}, {hl * d}] {qkv.dtype}")
+    _lib.check(_lib.load().dg_prefill_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
+                                           v_cache.data_ptr(), out.data_ptr(), bs, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                           qkv.device.index, _stream(qkv)), "dg_prefill_attn")
     return out
 
 

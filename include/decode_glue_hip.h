@@ -1,4 +1,5 @@
-/* decode_glue_hip.h -- C ABI of the non-GEMM kernels of one batch-1 decode step.
+/* decode_glue_hip.h -- C ABI of the non-GEMM kernels of the decode stack: one decode step (one new token per sequence,
+ * SURVEY.md 8f row N2) and the prompt prefill in front of it (dg_prefill_attn: a chunk of tokens per sequence).
  *
  * Not part of the tinygemm drop-in boundary (include/tinygemm_hip.h).  The reference times model-level
  * decode through HuggingFace `transformers` (benchmark.py:113-215 -> LlamaDecoderLayer, an external
@@ -11,6 +12,7 @@
  *   dg_decode_attn   grouped-query attention of one new token against cache[0 .. *pos]
  *   dg_rope_attn     the two above fused (what the decode harness launches)
  *   dg_swiglu        silu(gate) * up
+ *   dg_prefill_attn  a chunk of T tokens: rotary embedding, T cache rows appended, causal flash attention over cache + chunk
  *
  * Conventions are those of include/tinygemm_hip.h: raw device pointers, caller-owned outputs, explicit
  * stream, no allocation, no host sync, graph-capturable (`pos` is read on the device, so a captured graph
@@ -82,6 +84,21 @@ TG_API int dg_swiglu(const void* gu, void* out, int64_t bs, int64_t il, int dtyp
  * which the reference leaves un-quantised (quantize.py:34-36).  m = 1 ... 4 at k = 2048 / 4096, 1 ... 2 at k = 8192 (TG_E_SHAPE otherwise: the caller
  * keeps its GEMM); x and w 16-byte aligned. */
 TG_API int dg_linear16(const void* x, const void* w, void* y, int64_t m, int64_t n, int64_t k, int dtype, int device, tg_stream_t stream);
+
+/* A chunk of T new tokens per sequence.  qkv [bs * T][(hl + 2 kvl) * d], row b * T + t = token t of sequence b (q heads, k heads,
+ * v heads, as in dg_rope_kv); *pos = p0 = sequence position of token 0 (int64 on the device, read by the kernel).
+ *   k_cache[b][kv][p0 + t][:] = rope(k, p0 + t);  v_cache[b][kv][p0 + t][:] = v          -- the bits dg_rope_kv writes
+ *   out[b * T + t][h * d ...] = softmax_{s <= p0 + t}( (rope(q) . k_cache[b][h / (hl/kvl)][s]) * scale ) applied to v_cache
+ * i.e. token t sees the cache rows [0, p0) that earlier calls wrote and rows [p0, p0 + t] of its own chunk.  q is roped and rounded
+ * to 16 bit like k; scores and softmax statistics in f32 (online softmax over 64-position tiles), probabilities rounded to 16 bit
+ * for the value product, f32 accumulation, normalised once, one rounding of the output (dg_rope_attn_online's recipe).  Two
+ * launches (cache append, then attention), no scratch memory, no atomics: a call repeated gives the same bits.
+ * A token whose position p0 + t is outside [0, max_seq) writes no cache row, is seen by nobody and leaves its output row unwritten;
+ * cache rows outside [p0, p0 + T) are not written, rows above a token's own position are not read.
+ * d = 64 / 128, hl % kvl == 0, max_seq <= 8192, bs <= 65535 (TG_E_SHAPE otherwise); qkv, the tables, the caches and out 16-byte aligned. */
+TG_API int dg_prefill_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                           void* out, int64_t bs, int64_t T, int hl, int kvl, int d, int64_t max_seq, float scale,
+                           int dtype, int device, tg_stream_t stream);
 
 #ifdef __cplusplus
 }
