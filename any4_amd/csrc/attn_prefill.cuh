@@ -25,6 +25,7 @@
 // nobody (every token only reads rows <= its own position) and leaves its output row unwritten; rows of a tile beyond the workgroup's
 // last valid position are zero-filled in LDS instead of being read, so NaN-filled or unallocated tails are never touched.
 #pragma once
+#include "rope_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 
 struct PrefillParams {
   const uint16_t* qkv;
@@ -39,16 +40,6 @@ struct PrefillParams {
   int32_t hgroups; // ceil((hl / kvl) / RG)
   float scale;
 };
-
-// x * cos + rotate_half(x) * sin with each product and the sum rounded separately, as the torch ops do (decode._rope).  Contraction is
-// switched off here: the compiler otherwise fuses one product of each sum into an FMA (also through __fmul_rn / __fadd_rn), which
-// differs from the torch bits in about one element of 1e5.
-__device__ __forceinline__ float pf_rope(float a, float c, float b, float s) {
-#pragma clang fp contract(off)
-  const float ac = a * c;
-  const float bs = b * s;
-  return ac + bs;
-}
 
 // ---- rope + cache append: block = one token of one sequence; a thread walks (kv head, rotation pair) items, k first, then v ----
 template <typename DT>
@@ -69,8 +60,8 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
     } else {
       const float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
       const float c1 = P.cos[pos * d + j], c2 = P.cos[pos * d + j + d2], s1 = P.sin[pos * d + j], s2 = P.sin[pos * d + j + d2];
-      dst[j] = DT::from_f32(pf_rope(x1, c1, -x2, s1));
-      dst[j + d2] = DT::from_f32(pf_rope(x2, c2, x1, s2));
+      dst[j] = DT::from_f32(rope_mul_add(x1, c1, -x2, s1));
+      dst[j + d2] = DT::from_f32(rope_mul_add(x2, c2, x1, s2));
     }
   }
 }
@@ -150,8 +141,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
           const f32x4 s1 = *reinterpret_cast<const f32x4*>(sp + e), s2 = *reinterpret_cast<const f32x4*>(sp + D / 2 + e);
 #pragma unroll
           for (int i = 0; i < 4; ++i) {  // the cache rows' arithmetic: each product and the sum rounded separately
-            o1[e + i] = pf_rope(x1[e + i], c1[i], -x2[e + i], s1[i]);
-            o2[e + i] = pf_rope(x2[e + i], c2[i], x1[e + i], s2[i]);
+            o1[e + i] = rope_mul_add(x1[e + i], c1[i], -x2[e + i], s1[i]);
+            o2[e + i] = rope_mul_add(x2[e + i], c2[i], x1[e + i], s2[i]);
           }
         }
         qf[u][kd] = u32x4{DT::pack2(o1[0], o1[1]), DT::pack2(o1[2], o1[3]), DT::pack2(o1[4], o1[5]), DT::pack2(o1[6], o1[7])};

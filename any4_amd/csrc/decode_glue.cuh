@@ -5,6 +5,7 @@
 // there are 5 of them per layer instead of ~45 torch launches, not their individual bandwidth.  Rounding points
 // mirror the torch formulation in any4_amd/decode.py so the two paths can be compared in tests.
 #include "../../include/decode_glue_hip.h"
+#include "rope_math.cuh"
 
 namespace {
 
@@ -144,9 +145,9 @@ __global__ void rope_kv_kernel(const uint16_t* __restrict__ qkv, const float* __
   }
   const float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
   const float c1 = cos[pos * d + j], c2 = cos[pos * d + j + d2], s1 = sin[pos * d + j], s2 = sin[pos * d + j + d2];
-  // x * cos + rotate_half(x) * sin with each product and the sum rounded separately (as the torch ops do)
-  const float o1 = __fadd_rn(__fmul_rn(x1, c1), __fmul_rn(-x2, s1));
-  const float o2 = __fadd_rn(__fmul_rn(x2, c2), __fmul_rn(x1, s2));
+  // x * cos + rotate_half(x) * sin with each product and the sum rounded separately, as the torch ops do (rope_math.cuh: no FMA)
+  const float o1 = rope_mul_add(x1, c1, -x2, s1);
+  const float o2 = rope_mul_add(x2, c2, x1, s2);
   uint16_t* dst = head < hl ? q_out + ((int64_t)b * hl + head) * d
                             : k_cache + (((int64_t)b * kvl + (head - hl)) * max_seq + pos) * d;
   dst[j] = DT::from_f32(o1);
@@ -248,8 +249,8 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
     const uint16_t* src = row + (isk ? (hl + kv) * d : h * d);
     const float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
     const float c1 = cos[pos * d + j], c2 = cos[pos * d + j + d2], s1 = sin[pos * d + j], s2 = sin[pos * d + j + d2];
-    const uint16_t o1 = DT::from_f32(__fadd_rn(__fmul_rn(x1, c1), __fmul_rn(-x2, s1)));
-    const uint16_t o2 = DT::from_f32(__fadd_rn(__fmul_rn(x2, c2), __fmul_rn(x1, s2)));
+    const uint16_t o1 = DT::from_f32(rope_mul_add(x1, c1, -x2, s1));
+    const uint16_t o2 = DT::from_f32(rope_mul_add(x2, c2, x1, s2));
     float* dstf = isk ? kn : qf;
     dstf[j] = DT::to_f32(o1);
     dstf[j + d2] = DT::to_f32(o2);
@@ -353,8 +354,8 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
     const uint16_t* src = row + (isk ? (hl + kv) * d : h * d);
     const float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
     const float cs1 = cos[pos * d + j], cs2 = cos[pos * d + j + d2], s1 = sin[pos * d + j], s2 = sin[pos * d + j + d2];
-    const uint16_t o1 = DT::from_f32(__fadd_rn(__fmul_rn(x1, cs1), __fmul_rn(-x2, s1)));
-    const uint16_t o2 = DT::from_f32(__fadd_rn(__fmul_rn(x2, cs2), __fmul_rn(x1, s2)));
+    const uint16_t o1 = DT::from_f32(rope_mul_add(x1, cs1, -x2, s1));
+    const uint16_t o2 = DT::from_f32(rope_mul_add(x2, cs2, x1, s2));
     float* dstf = isk ? kn : qf;
     dstf[j] = DT::to_f32(o1);
     dstf[j + d2] = DT::to_f32(o2);
