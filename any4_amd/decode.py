@@ -17,6 +17,9 @@ Launch structure, chosen for the hardware rather than copied from HF:
     gate/up likewise -> 4 GEMM launches per layer instead of 7;
   * the whole step is captured in a hipGraph (`DecodeStack.capture`): at batch 1 a layer's GEMMs take a few
     microseconds each, so launch gaps would otherwise dominate;
+  * `DecodeLayer` states the layer once per schedule -- plain torch (`forward`, `forward_prefill`), eight launches (`forward_fused`),
+    five launches (`forward_fused5`: the element-wise stages ride in the GEMMs) -- and the fused schedules take the attention launch as
+    an argument: `decode_attention` (one token per sequence) or `prefill_attention` (a chunk; so far on the eight launches only);
   * tensor parallelism = row-sharding of every linear (any4_amd/shard.py): heads are split across ranks so
     attention and the KV cache stay local; per layer 4 all-gathers of [bs, n/G] partial outputs (attention
     output, o_proj, SwiGLU activation, down_proj) over RCCL.  One process per GPU.
@@ -222,9 +225,12 @@ class DecodeLayer(torch.nn.Module):
         self.register_buffer("v_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
         # forward_fused5: which stages the library fused (None: not tried yet; set by the first step)
         self._fuse = {"norm1": None, "norm2": None, "mlp": None}
+        # decode_attention: the stack's split count and its scratch buffer (DecodeStack sets both once, when it is built)
+        self._attn_scratch, self._attn_split = None, 1
 
     def forward(self, h, pos, cos, sin, mask, gather):
-        cfg, d, bs = self.cfg, self.cfg.head_dim, h.shape[0]
+        """Plain torch, one token per sequence (the formulation the fused schedules are tested against)."""
+        d, bs = self.cfg.head_dim, h.shape[0]
         qkv = self.qkv(self.norm1(h))
         q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
         k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
@@ -236,51 +242,52 @@ class DecodeLayer(torch.nn.Module):
         att = torch.matmul(qg, self.k_cache.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
         att = att.masked_fill(mask, float("-inf")).softmax(-1).to(h.dtype)
         ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
-        h = h + gather(self.o(gather(ctx)))
+        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+
+    def forward_prefill(self, h, p0: int, T: int, cos_tab, sin_tab, gather):
+        """Plain torch, a chunk of T tokens per sequence: `h` [bs * T, hidden] (row b * T + t), token 0 at position `p0` (on the
+        host).  The T rows of k / v are appended to the caches and every token attends causally over cache + chunk."""
+        d = self.cfg.head_dim
+        ctx = prefill_attention_torch(self.qkv(self.norm1(h)), cos_tab, sin_tab, p0, self.k_cache, self.v_cache, self.hl, self.kvl, d, T)
+        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+
+    def _mlp_torch(self, h, gather):
+        """The plain-torch MLP block behind either attention: h + down(silu(gate) * up) of norm2(h)."""
         gu = self._split_gate_up(self.gate_up(self.norm2(h)))
-        il = cfg.inter // self.world
+        il = self.cfg.inter // self.world
         act = torch.nn.functional.silu(gu[:, :il]) * gu[:, il:]
         return h + gather(self.down(gather(act)))
 
-    def forward_fused(self, h, delta, pos, cos_tab, sin_tab, gather, attn_scratch=None, attn_split=1):
-        """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs.  `h` is the
-        residual stream (updated in place), `delta` the previous layer's not-yet-added MLP output."""
+    # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context
+    def decode_attention(self, qkv, pos, cos_tab, sin_tab):
+        """One token per sequence at `pos` [1]: split over the sequence when the stack gave this layer a scratch buffer, else the
+        latency kernel (head_dim 64 / 128), else the general one."""
         from . import decode_ops as G
 
-        cfg, d = self.cfg, self.cfg.head_dim
+        d = self.cfg.head_dim
+        args = (qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+        if self._attn_scratch is not None:
+            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split)
+        return (G.rope_attn_online if d in (64, 128) else G.rope_attn)(*args)
+
+    def prefill_attention(self, qkv, pos, cos_tab, sin_tab):
+        """A chunk of T = rows / bs tokens per sequence (row b * T + t), token 0 at `pos` [1]: T cache rows appended, causal."""
+        from . import decode_ops as G
+
+        d = self.cfg.head_dim
+        return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d),
+                              qkv.shape[0] // self.k_cache.shape[0])
+
+    def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather):
+        """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
+        (the linears are called as modules, so the library routes them by row count).  `h` is the residual stream (updated in
+        place), `delta` the previous layer's not-yet-added MLP output; returns (h, this layer's delta)."""
+        from . import decode_ops as G
+
         h, y = G.add_rmsnorm(h, delta, self.norm1.weight, self.norm1.eps)
-        if attn_scratch is not None:
-            ctx = G.rope_attn_split(self.qkv(y), cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d,
-                                    1.0 / math.sqrt(d), attn_scratch, attn_split)
-        else:
-            attn = G.rope_attn_online if d in (64, 128) else G.rope_attn
-            ctx = attn(self.qkv(y), cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+        ctx = attention(self.qkv(y), pos, cos_tab, sin_tab)
         h, y = G.add_rmsnorm(h, gather(self.o(gather(ctx))), self.norm2.weight, self.norm2.eps)
         return h, gather(self.down(gather(G.swiglu(self._split_gate_up(self.gate_up(y)).contiguous()))))
-
-    def forward_prefill(self, h, pos, T, cos_tab, sin_tab, gather, fused=False, delta=None, p0=None):
-        """A chunk of T tokens per sequence: `h` [bs * T, hidden] (row b * T + t), `pos` [1] int64 = position of token 0.  The T
-        rows of k / v are appended to the caches and every token attends causally over cache + chunk.  Returns (h, delta) as
-        forward_fused does (`delta` = this layer's not-yet-added MLP output; None on the plain path, which adds it itself).
-        fused: forward_fused's sequence at bs * T rows -- add_rmsnorm, qkv linear, prefill_attn (include/decode_glue_hip.h), o linear,
-        add_rmsnorm, gate_up linear, swiglu, down linear; the linears are called as modules, so the library routes them (the LDS-tiled
-        GEMM above 64 rows).  Otherwise plain torch (`prefill_attention_torch`), which needs the position on the host: `p0`."""
-        cfg, d = self.cfg, self.cfg.head_dim
-        if fused:
-            from . import decode_ops as G
-
-            h, y = G.add_rmsnorm(h, delta, self.norm1.weight, self.norm1.eps)
-            ctx = G.prefill_attn(self.qkv(y), cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d,
-                                 1.0 / math.sqrt(d), T)
-            h, y = G.add_rmsnorm(h, gather(self.o(gather(ctx))), self.norm2.weight, self.norm2.eps)
-            return h, gather(self.down(gather(G.swiglu(self._split_gate_up(self.gate_up(y)).contiguous()))))
-        p0 = int(pos) if p0 is None else int(p0)
-        ctx = prefill_attention_torch(self.qkv(self.norm1(h)), cos_tab, sin_tab, p0, self.k_cache, self.v_cache, self.hl, self.kvl, d, T)
-        h = h + gather(self.o(gather(ctx)))
-        gu = self._split_gate_up(self.gate_up(self.norm2(h)))
-        il = cfg.inter // self.world
-        act = torch.nn.functional.silu(gu[:, :il]) * gu[:, il:]
-        return h + gather(self.down(gather(act))), None
 
     # ---- five launches per layer: every element-wise stage rides in a GEMM launch (tg_w4_gemm ABI 5) ----
     def _w4(self, lin, x, **kw):
@@ -290,6 +297,17 @@ class DecodeLayer(torch.nn.Module):
 
         lut = getattr(lin, "lut", None)
         return ops.w4_linear_fused(x, lin.weight, lin.group_size, lin.scales_and_zeros, lut, **kw)
+
+    def _try_fused(self, stage, lin, x, **kw):
+        """_w4 for a stage the library may not be able to fuse: its first answer settles `_fuse[stage]`, and a stage settled False
+        is not asked again (None at once; the caller then runs the stage as its own launch)."""
+        f = self._fuse
+        if f.get(stage) is False:
+            return None
+        y = self._w4(lin, x, **kw)
+        if f.get(stage) is None:
+            f[stage] = y is not None
+        return y
 
     def launches(self) -> int:
         """Kernel launches of one decode step of this layer on the fused path (after the first step has settled `_fuse`)."""
@@ -314,55 +332,39 @@ class DecodeLayer(torch.nn.Module):
             return gu
         return gu.view(gu.shape[0], -1, 2, b).transpose(1, 2).reshape(gu.shape[0], -1)
 
-    def forward_fused5(self, h, pos, cos_tab, sin_tab, attn_scratch=None, attn_split=1):
-        """TP = 1.  qkv GEMM (RMSNorm in its activation staging) -> RoPE + KV write + attention -> o GEMM (residual add in its
-        store) -> gate_up GEMM (RMSNorm in its staging, SwiGLU in its store) -> down GEMM (residual add in its store): 5 launches
-        instead of 8.  `h` [bs, hidden] is the residual stream, updated in place.  A stage the library cannot fuse for this
-        problem (w4_linear_fused returns None) runs as its own launch, as in forward_fused."""
+    def forward_fused5(self, h, attention, pos, cos_tab, sin_tab):
+        """TP = 1.  qkv GEMM (RMSNorm in its activation staging) -> `attention` -> o GEMM (residual add in its store) -> gate_up
+        GEMM (RMSNorm in its staging, SwiGLU in its store) -> down GEMM (residual add in its store): 5 launches instead of 8.
+        `h` [bs, hidden] is the residual stream, updated in place.  A stage the library cannot fuse for this problem
+        (w4_linear_fused returns None) runs as its own launch, as in forward_fused."""
         from . import decode_ops as G
 
-        cfg, d = self.cfg, self.cfg.head_dim
-        f = self._fuse
-        # ---- attention block
-        qkv = self._w4(self.qkv, h, norm_weight=self.norm1.weight, norm_eps=self.norm1.eps) if f["norm1"] is not False else None
-        if f["norm1"] is None:
-            f["norm1"] = qkv is not None
+        n1, n2 = self.norm1, self.norm2
+        qkv = self._try_fused("norm1", self.qkv, h, norm_weight=n1.weight, norm_eps=n1.eps)
         if qkv is None:
-            qkv = self.qkv(G.add_rmsnorm(h, None, self.norm1.weight, self.norm1.eps)[1])
-        if attn_scratch is not None:
-            ctx = G.rope_attn_split(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d,
-                                    1.0 / math.sqrt(d), attn_scratch, attn_split)
-        else:
-            attn = G.rope_attn_online if d in (64, 128) else G.rope_attn
-            ctx = attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+            qkv = self.qkv(G.add_rmsnorm(h, None, n1.weight, n1.eps)[1])
+        ctx = attention(qkv, pos, cos_tab, sin_tab)
         if self._w4(self.o, ctx, residual=h, out=h) is None:       # (a residual add is available in every 4-bit kernel)
-            G.add_rmsnorm(h, self.o(ctx), self.norm2.weight, self.norm2.eps, want_norm=False)
-        # ---- MLP block: norm2 + SwiGLU inside the gate_up launch; else whichever of the two the library can fuse (a block too
-        # large to stage on chip, e.g. 8 sequences at k = 4096, has no fused norm but still the SwiGLU store)
-        il8 = cfg.gate_up_interleave == 8
-        act = None
-        if f["mlp"] is not False and il8:
-            act = self._w4(self.gate_up, h, norm_weight=self.norm2.weight, norm_eps=self.norm2.eps, swiglu=True)
-        if f["mlp"] is None:
-            f["mlp"] = act is not None
-        if act is None:
-            gu = None
-            if f["norm2"] is not False and not il8:
-                gu = self._w4(self.gate_up, h, norm_weight=self.norm2.weight, norm_eps=self.norm2.eps)
-                if f["norm2"] is None:
-                    f["norm2"] = gu is not None
-            if gu is None:
-                y = G.add_rmsnorm(h, None, self.norm2.weight, self.norm2.eps)[1]
-                if il8 and f.get("swiglu") is not False:
-                    act = self._w4(self.gate_up, y, swiglu=True)
-                    if f.get("swiglu") is None:
-                        f["swiglu"] = act is not None
-                if act is None:
-                    gu = self.gate_up(y)
+            G.add_rmsnorm(h, self.o(ctx), n2.weight, n2.eps, want_norm=False)
+        # MLP block: norm2 + SwiGLU inside the gate_up launch ("mlp"; the store needs the 8 + 8 row order); else whichever of the two
+        # the library can fuse (a block too large to stage on chip has no fused norm, "norm2", but still the SwiGLU store, "swiglu")
+        il8 = self.cfg.gate_up_interleave == 8
+        act = gu = None
+        if il8:
+            act = self._try_fused("mlp", self.gate_up, h, norm_weight=n2.weight, norm_eps=n2.eps, swiglu=True)
+        else:
+            self._fuse["mlp"] = False
+            gu = self._try_fused("norm2", self.gate_up, h, norm_weight=n2.weight, norm_eps=n2.eps)
+        if act is None and gu is None:
+            y = G.add_rmsnorm(h, None, n2.weight, n2.eps)[1]
+            if il8:
+                act = self._try_fused("swiglu", self.gate_up, y, swiglu=True)
             if act is None:
-                act = G.swiglu(self._split_gate_up(gu).contiguous())
+                gu = self.gate_up(y)
+        if act is None:
+            act = G.swiglu(self._split_gate_up(gu).contiguous())
         if self._w4(self.down, act, residual=h, out=h) is None:
-            G.add_rmsnorm(h, self.down(act), self.norm2.weight, self.norm2.eps, want_norm=False)
+            G.add_rmsnorm(h, self.down(act), n2.weight, n2.eps, want_norm=False)
         return h
 
 
@@ -434,6 +436,8 @@ class DecodeStack(torch.nn.Module):
                 self._attn_split = max(1, int(os.environ["ANY4_ATTN_SPLIT"]))
             if self._attn_split > 1:
                 self._attn_scratch = G.rope_attn_split_scratch(bs, hl, cfg.head_dim, self._attn_split, device)
+            for layer in self.layers:
+                layer._attn_scratch, layer._attn_split = self._attn_scratch, self._attn_split
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
     def _gather(self, y, peer_ok=True):
@@ -473,32 +477,40 @@ class DecodeStack(torch.nn.Module):
             return out
         return self._step()
 
+    def _five_launch(self) -> bool:
+        """This stack takes DecodeLayer.forward_fused5 (asked at every step: a linear may be swapped after construction)."""
+        return self.fused and self.fuse_gemm_stages and self.world == 1 and all(layer.fusable() for layer in self.layers)
+
+    def _head(self, h, delta=None):
+        """Final norm (on the fused path it first adds `delta`, the last layer's not-yet-added MLP output) and the LM head."""
+        if not self.fused:
+            h = self.norm(h)
+            return self.lm_head(h) if self.lm_head is not None else h
+        from . import decode_ops as G
+
+        _, y = G.add_rmsnorm(h, delta, self.norm.weight, self.norm.eps)
+        if self.lm_head is None:
+            return y
+        # the un-quantised LM head (quantize.py:34-36 skips it): a streaming GEMV for up to four rows, else torch's GEMM
+        logits = G.linear16(y, self.lm_head.weight) if self.lm_head.bias is None else None
+        return logits if logits is not None else self.lm_head(y)
+
     def _step(self) -> torch.Tensor:
         pos = self.pos
-        if self.fused:
-            from . import decode_ops as G
-
-            h, delta = self.embed(self.tokens), None
-            if self.fuse_gemm_stages and self.world == 1 and all(layer.fusable() for layer in self.layers):
-                for layer in self.layers:
-                    h = layer.forward_fused5(h, pos, self.cos, self.sin, self._attn_scratch, self._attn_split)
-            else:
-                for layer in self.layers:
-                    h, delta = layer.forward_fused(h, delta, pos, self.cos, self.sin, self._gather, self._attn_scratch, self._attn_split)
-            _, y = G.add_rmsnorm(h, delta, self.norm.weight, self.norm.eps)
-            if self.lm_head is None:
-                return y
-            # the un-quantised LM head (quantize.py:34-36 skips it): a streaming GEMV for up to four rows, else torch's GEMM
-            logits = G.linear16(y, self.lm_head.weight) if self.lm_head.bias is None else None
-            return logits if logits is not None else self.lm_head(y)
-        cos = self.cos.index_select(0, pos).view(1, 1, -1)
-        sin = self.sin.index_select(0, pos).view(1, 1, -1)
-        mask = (self.arange > pos).view(1, 1, 1, -1)
-        h = self.embed(self.tokens)
-        for layer in self.layers:
-            h = layer(h, pos, cos, sin, mask, self._gather)
-        h = self.norm(h)
-        return self.lm_head(h) if self.lm_head is not None else h
+        h, delta = self.embed(self.tokens), None
+        if not self.fused:
+            cos = self.cos.index_select(0, pos).view(1, 1, -1)
+            sin = self.sin.index_select(0, pos).view(1, 1, -1)
+            mask = (self.arange > pos).view(1, 1, 1, -1)
+            for layer in self.layers:
+                h = layer(h, pos, cos, sin, mask, self._gather)
+        elif self._five_launch():
+            for layer in self.layers:
+                h = layer.forward_fused5(h, layer.decode_attention, pos, self.cos, self.sin)
+        else:
+            for layer in self.layers:
+                h, delta = layer.forward_fused(h, delta, layer.decode_attention, pos, self.cos, self.sin, self._gather)
+        return self._head(h, delta)
 
     @torch.no_grad()
     def capture(self, warmup: int = 3) -> None:
@@ -513,7 +525,7 @@ class DecodeStack(torch.nn.Module):
         with torch.cuda.graph(g):
             self._out = self.step()
         self._graph = g
-        if self.fused and self.fuse_gemm_stages and self.world == 1 and all(layer.fusable() for layer in self.layers):
+        if self._five_launch():
             self.kernels_per_layer = self.layers[0].launches()
             # + embedding gather, final norm, LM head
             self.graph_nodes = sum(layer.launches() for layer in self.layers) + 2 + (1 if self.lm_head is not None else 0)
@@ -548,22 +560,15 @@ class DecodeStack(torch.nn.Module):
         h = self.embed(toks.reshape(-1))  # [bs * T, hidden], row b * T + t
         delta = None
         for layer in self.layers:
-            h, delta = layer.forward_prefill(h, self.prefill_pos, T, self.cos, self.sin, self._gather_rows, fused=self.fused,
-                                             delta=delta, p0=p0)
+            if self.fused:  # the eight launches of a decode step at bs * T rows, with the chunk's attention
+                h, delta = layer.forward_fused(h, delta, layer.prefill_attention, self.prefill_pos, self.cos, self.sin, self._gather_rows)
+            else:           # plain torch needs the position on the host (prefill() refuses position=None on this path)
+                h = layer.forward_prefill(h, p0, T, self.cos, self.sin, self._gather_rows)
         if not want_logits:
             return None
         # the LM head runs on the last token of every sequence only
-        h = h.view(self.bs, T, -1)[:, -1].contiguous()
-        if self.fused:
-            from . import decode_ops as G
-
-            _, y = G.add_rmsnorm(h, delta.view(self.bs, T, -1)[:, -1].contiguous(), self.norm.weight, self.norm.eps)
-            if self.lm_head is None:
-                return y
-            logits = G.linear16(y, self.lm_head.weight) if self.lm_head.bias is None else None
-            return logits if logits is not None else self.lm_head(y)
-        h = self.norm(h)
-        return self.lm_head(h) if self.lm_head is not None else h
+        last = [None if t is None else t.view(self.bs, T, -1)[:, -1].contiguous() for t in (h, delta)]
+        return self._head(*last)
 
     @torch.no_grad()
     def prefill(self, tokens: torch.Tensor, position: Optional[int] = 0, chunk: Optional[int] = None) -> torch.Tensor:

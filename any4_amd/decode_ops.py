@@ -47,18 +47,25 @@ def add_rmsnorm(h: torch.Tensor, delta, weight: torch.Tensor, eps: float, want_n
     return h, y
 
 
+def _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, *more, out=None):
+    """What the rope / attention wrappers share: the device check (`more`: further tensors of the call), the dtype check of the
+    tables and `pos`, and the output [rows of qkv, hl * d] (allocated unless given).  Returns (out, rows of qkv, max_seq)."""
+    _gpu(qkv, cos, sin, pos, k_cache, v_cache, *more, out)
+    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
+        raise RuntimeError("rope tables must be float32 and pos int64")
+    if out is None:
+        out = torch.empty((qkv.shape[0], hl * d), dtype=qkv.dtype, device=qkv.device)
+    return out, qkv.shape[0], k_cache.shape[2]
+
+
 def rope_kv(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
             v_cache: torch.Tensor, hl: int, kvl: int, d: int) -> torch.Tensor:
     """qkv [bs, (hl + 2 kvl) d] -> rotated q [bs, hl, d]; rotated k and v are written into the caches at `pos`."""
-    _gpu(qkv, cos, sin, pos, k_cache, v_cache)
-    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
-        raise RuntimeError("rope tables must be float32 and pos int64")
-    bs, max_seq = qkv.shape[0], k_cache.shape[2]
-    q = torch.empty((bs, hl, d), dtype=qkv.dtype, device=qkv.device)
+    q, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d)
     _lib.check(_lib.load().dg_rope_kv(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), q.data_ptr(),
                                       k_cache.data_ptr(), v_cache.data_ptr(), bs, hl, kvl, d, max_seq, _dt(qkv),
                                       qkv.device.index, _stream(qkv)), "dg_rope_kv")
-    return q
+    return q.view(bs, hl, d)
 
 
 def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, pos: torch.Tensor, scale: float) -> torch.Tensor:
@@ -73,33 +80,26 @@ def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, p
     return out
 
 
+def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale):
+    """rope_attn / rope_attn_online: two kernels behind one argument list."""
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d)
+    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
+                                           v_cache.data_ptr(), out.data_ptr(), bs, hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                           qkv.device.index, _stream(qkv)), entry)
+    return out
+
+
 def rope_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
               v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float) -> torch.Tensor:
     """rope_kv + decode_attn in one launch: qkv [bs, (hl + 2 kvl) d] -> context [bs, hl * d]; caches updated at `pos`."""
-    _gpu(qkv, cos, sin, pos, k_cache, v_cache)
-    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
-        raise RuntimeError("rope tables must be float32 and pos int64")
-    bs, max_seq = qkv.shape[0], k_cache.shape[2]
-    out = torch.empty((bs, hl * d), dtype=qkv.dtype, device=qkv.device)
-    _lib.check(_lib.load().dg_rope_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                        v_cache.data_ptr(), out.data_ptr(), bs, hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                        qkv.device.index, _stream(qkv)), "dg_rope_attn")
-    return out
+    return _rope_attn("dg_rope_attn", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale)
 
 
 def rope_attn_online(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                      v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float) -> torch.Tensor:
     """rope_attn built for latency (head_dim 64 / 128): one barrier, every load issued up front, softmax statistics combined
     flash-decoding style -- the same caches bit for bit, the output within 16-bit rounding of rope_attn's."""
-    _gpu(qkv, cos, sin, pos, k_cache, v_cache)
-    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
-        raise RuntimeError("rope tables must be float32 and pos int64")
-    bs, max_seq = qkv.shape[0], k_cache.shape[2]
-    out = torch.empty((bs, hl * d), dtype=qkv.dtype, device=qkv.device)
-    _lib.check(_lib.load().dg_rope_attn_online(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                               v_cache.data_ptr(), out.data_ptr(), bs, hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                               qkv.device.index, _stream(qkv)), "dg_rope_attn_online")
-    return out
+    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale)
 
 
 def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> torch.Tensor:
@@ -111,11 +111,7 @@ def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> to
 def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int) -> torch.Tensor:
     """rope_attn with the sequence split over `nsplit` blocks per head (fills the GPU at batch 1 / long contexts)."""
-    _gpu(qkv, cos, sin, pos, k_cache, v_cache, scratch)
-    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
-        raise RuntimeError("rope tables must be float32 and pos int64")
-    bs, max_seq = qkv.shape[0], k_cache.shape[2]
-    out = torch.empty((bs, hl * d), dtype=qkv.dtype, device=qkv.device)
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch)
     _lib.check(_lib.load().dg_rope_attn_split(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, bs, hl,
                                               kvl, d, max_seq, float(scale), nsplit, _dt(qkv), qkv.device.index, _stream(qkv)),
@@ -129,19 +125,14 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     the v rows are appended to the caches at positions pos ... pos + T - 1 (`pos` [1] int64 on the device = position of token 0), and
     token t attends causally over cache rows 0 ... pos + t.  A token whose position is outside the cache writes nothing and leaves its
     row of `out` (allocated here unless given) as it was."""
-    _gpu(qkv, cos, sin, pos, k_cache, v_cache, out)
-    if cos.dtype != torch.float32 or pos.dtype != torch.int64:
-        raise RuntimeError("rope tables must be float32 and pos int64")
+    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, out=out)
     T = int(T)
-    if T < 1 or qkv.dim() != 2 or qkv.shape[0] % T or qkv.shape[0] // T != k_cache.shape[0]:
+    if T < 1 or qkv.dim() != 2 or rows % T or rows // T != k_cache.shape[0]:
         raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {k_cache.shape[0]} (the caches'), got {tuple(qkv.shape)}")
-    bs, max_seq = qkv.shape[0] // T, k_cache.shape[2]
-    if out is None:
-        out = torch.empty((bs * T, hl * d), dtype=qkv.dtype, device=qkv.device)
-    elif out.shape != (bs * T, hl * d) or out.dtype != qkv.dtype:
-        raise RuntimeError(f"prefill_attn: out must be [{bs * T}, {hl * d}] {qkv.dtype}")
+    if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"prefill_attn: out must be [{rows}, {hl * d}] {qkv.dtype}")
     _lib.check(_lib.load().dg_prefill_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), out.data_ptr(), bs, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                           v_cache.data_ptr(), out.data_ptr(), rows // T, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
                                            qkv.device.index, _stream(qkv)), "dg_prefill_attn")
     return out
 

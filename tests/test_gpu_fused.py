@@ -186,3 +186,71 @@ def test_five_launch_layer_matches_eight_launch_layer(bs):
     for i, t in enumerate(toks[3:], start=3):
         ya, yb = a.decode(t, i).float().clone(), b.decode(t, i).float()
         assert (ya - yb).abs().max() <= 0.02 * yb.abs().max() + 1e-3, (i, (ya - yb).abs().max(), yb.abs().max())
+
+
+_BASE = dict(hidden=2048, inter=4096, layers=2, heads=16, kv_heads=4, head_dim=128, vocab=512, max_seq=64, gate_up_interleave=8)
+# (config, bs, numerics, the settled DecodeLayer._fuse, DecodeLayer.launches(), DecodeStack._attn_split): the branches of the fusion
+# negotiation that the all-fused test above does not walk.  Dicts and counts as the commit before the layer was restated gave them.
+_NEGOTIATION = {
+    # rows in [gate; up] order: no SwiGLU store, the norm still rides in gate_up's staging
+    "gate_up_not_interleaved": (dict(_BASE, gate_up_interleave=0), 1, "fast",
+                                {"norm1": True, "norm2": True, "mlp": False}, 6, 1),
+    # the reference-numerics kernels carry no stage: every probe is refused, every fallback and both unfused residual adds run
+    "reference_numerics": (_BASE, 1, "reference", {"norm1": False, "norm2": None, "mlp": False, "swiglu": False}, 8, 1),
+    "reference_numerics_not_interleaved": (dict(_BASE, gate_up_interleave=0), 1, "reference",
+                                           {"norm1": False, "norm2": False, "mlp": False}, 8, 1),
+    # 16 rows of k = 4096 behind a gate_up of 128 row tiles (fewer than CUs): too large a block for the fused norm, the SwiGLU store alone
+    "swiglu_store_without_norm": (dict(_BASE, hidden=4096, inter=1024, heads=32, kv_heads=8), 16, "fast",
+                                  {"norm1": True, "norm2": None, "mlp": False, "swiglu": True}, 6, 1),
+    # a cache of 2048 positions: the attention launch is the one split over the sequence
+    "split_attention": (dict(_BASE, max_seq=2048), 1, "fast", {"norm1": True, "norm2": None, "mlp": True}, 5, 4),
+}
+
+
+@pytest.mark.parametrize("case", list(_NEGOTIATION))
+def test_five_launch_layer_fallbacks_match_eight_launch_layer(case):
+    """The five-launch layer where the library fuses only some stages (or none), and with the split-sequence attention, against
+    the same stack on the separate glue kernels: same tolerance as above, three eager and three replayed steps; which stages
+    settled fused, and the launch count that follows, are pinned."""
+    import any4_amd
+    from any4_amd.decode import Any4Factory, DecodeConfig, DecodeStack
+
+    kw, bs, numerics, fuse, launches, split = _NEGOTIATION[case]
+    cfg = DecodeConfig(**kw)
+    with any4_amd.numerics(numerics):
+        a = DecodeStack(cfg, Any4Factory(cfg, DEV, seed=3), DEV, bs=bs, seed=9)
+        b = DecodeStack(cfg, Any4Factory(cfg, DEV, seed=3), DEV, bs=bs, seed=9, fuse_gemm_stages=False)
+        assert a._attn_split == b._attn_split == split
+        toks = torch.randint(0, cfg.vocab, (6, bs), generator=torch.Generator().manual_seed(1)).to(DEV)
+        for i, t in enumerate(toks[:3]):
+            ya, yb = a.decode(t, i).float(), b.decode(t, i).float()
+            assert torch.isfinite(ya).all()
+            assert (ya - yb).abs().max() <= 0.02 * yb.abs().max() + 1e-3, (i, (ya - yb).abs().max(), yb.abs().max())
+        for layer in a.layers:
+            assert layer._fuse == fuse, layer._fuse
+            assert layer.launches() == launches
+        a.capture()
+        assert (a.kernels_per_layer, a.graph_nodes) == (launches, 2 * launches + 3)
+        for i, t in enumerate(toks[3:], start=3):
+            ya, yb = a.decode(t, i).float().clone(), b.decode(t, i).float()
+            assert (ya - yb).abs().max() <= 0.02 * yb.abs().max() + 1e-3, (i, (ya - yb).abs().max(), yb.abs().max())
+        assert all(layer._fuse == fuse for layer in a.layers)  # settled by the first step, not moved by later ones
+
+
+def test_eight_launch_layer_with_split_attention_matches_plain_torch():
+    """The split-sequence attention on the eight-launch path (cache of 2048 positions: four blocks per head) against the
+    plain-torch stack on the same linears; the tolerance of test_gpu_decode.py::test_decode_any4_vs_dense_dequantised."""
+    from any4_amd.decode import Any4Factory, DecodeConfig, DecodeStack
+
+    cfg = DecodeConfig(**dict(_BASE, max_seq=2048))
+    a = DecodeStack(cfg, Any4Factory(cfg, DEV, seed=3), DEV, bs=1, seed=9, fuse_gemm_stages=False)
+    b = DecodeStack(cfg, Any4Factory(cfg, DEV, seed=3), DEV, bs=1, seed=9, fused=False)
+    assert a._attn_split == 4 and a._attn_scratch is not None
+    toks = torch.randint(0, cfg.vocab, (6, 1), generator=torch.Generator().manual_seed(1)).to(DEV)
+    for i, t in enumerate(toks):
+        if i == 3:
+            a.capture()
+        ya, yb = a.decode(t, i).float().clone(), b.decode(t, i).float()
+        assert torch.isfinite(ya).all()
+        assert (ya - yb).abs().max() <= 0.03 * yb.abs().max() + 1e-3, (i, (ya - yb).abs().max(), yb.abs().max())
+    assert all(layer._fuse == {"norm1": None, "norm2": None, "mlp": None} for layer in a.layers)  # the negotiation never ran
