@@ -482,10 +482,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   // fetches the rows once instead of once per XCD the group is spread over.
   const int b = blockIdx.x / hl, rep = hl / kvl;
   const int hb = blockIdx.x % hl;
-#ifndef DG_ATTN_XCD_HEADS
-#define DG_ATTN_XCD_HEADS 1
-#endif
-  const int h = (DG_ATTN_XCD_HEADS && kvl == 8 && hl == 8 * rep) ? rep * (hb & 7) + (hb >> 3) : hb;
+  const int h = (kvl == 8 && hl == 8 * rep) ? rep * (hb & 7) + (hb >> 3) : hb;
   const int kv = h / rep;
   const uint16_t* row = qkv + (int64_t)b * (hl + 2 * kvl) * D;
   // (row r, piece i) of this head's K / V at byte ((r * LPR + i) << 4): a 32-bit offset on a scalar base (host: max_seq * d * 2 < 4 GiB)
@@ -576,19 +573,11 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       d2 = dot2_16<DT>(kr[1], qp[1], d2);
       d2 = dot2_16<DT>(kr[2], qp[2], d2);
       d2 = dot2_16<DT>(kr[3], qp[3], d2);
-#ifdef DG_ATTN_SHFL
-#pragma unroll
-      for (int o = 1; o < LPR; o <<= 1) d2 += __shfl_xor(d2, o, 64);
-#else
       d2 = dpp_add(d2, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
       d2 = dpp_add(d2, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
       d2 = dpp_add(d2, std::integral_constant<int, 0x141>{});   // row_half_mirror: the other quad of the 8 lanes
       if constexpr (LPR == 16) d2 = dpp_add(d2, std::integral_constant<int, 0x140>{});  // row_mirror: the other half of the 16 lanes
-#endif
       x[it] = r < S ? round16<DT>(d2) * scale : -INFINITY;
-#ifdef DG_ATTN_DUMP
-      if (blockIdx.x == 0 && i == 0 && r < S) reinterpret_cast<float*>(v_cache + (((int64_t)kvl - 1) * max_seq + (max_seq - 1)) * D)[r] = x[it];
-#endif
       cm = fmaxf(cm, x[it]);
     }
     const float mn = fmaxf(m, cm);

@@ -45,7 +45,7 @@ struct GemmParams {
   int32_t splitk;    // waves per tile (power of two, <= WAVES)
   int32_t sk_shift;  // log2(splitk)
   int32_t rowtiles;  // ceil(wrows / 16)
-  int32_t dbg;       // developer ablation flags (0 in production)
+  int32_t dbg;       // always 0, read by no kernel (kept: removing it moves the kernel-argument offsets behind it)
   int32_t numerics;  // TG_NUM_* (host-side dispatch only)
   int32_t dot2;      // host-side only: TG_NUM_FAST_DOT2 was asked for (never promote a stacked m = 1 launch to the matrix-core contraction)
   int32_t dry;       // host-side only: report the kernel family instead of launching (tg_gemm_w4_plan)
@@ -67,10 +67,6 @@ struct GemmParams {
 // register, lgkmcnt wait, ~100 cycles) -- and a butterfly is four to six of them back to back, usually on a launch's critical path in
 // front of its first barrier (dev/gemv_trace.py: the 16-lane step sums were 0.6 us of a 5.8 us launch).  gfx950 has the data paths in
 // the vector ALU: DPP operands (quad permutes, rotations within a 16-lane row) and v_permlane16_swap / v_permlane32_swap across rows.
-// TG_LANE_SHFL=1 (developer A/B) restores the shuffles.
-#ifndef TG_LANE_SHFL
-#define TG_LANE_SHFL 0
-#endif
 namespace tgl {
 template <int CTRL>
 __device__ __forceinline__ float dpp(float v) {
@@ -91,70 +87,40 @@ __device__ __forceinline__ void halves32(float v, float& lo, float& hi) {
 template <int O>
 __device__ __forceinline__ float lane_xor(float v, int lane) {
   static_assert(O == 1 || O == 2 || O == 8 || O == 16 || O == 32, "xor by 4 has no DPP form on gfx9: rotate (row_sum) or shuffle");
-#if TG_LANE_SHFL
-  return __shfl_xor(v, O, 64);
-#else
   if constexpr (O == 1) return dpp<0xB1>(v);        // quad_perm [1,0,3,2]
   else if constexpr (O == 2) return dpp<0x4E>(v);   // quad_perm [2,3,0,1]
   else if constexpr (O == 8) return dpp<0x128>(v);  // row_ror:8
   else if constexpr (O == 16) { float a, b; rows16(v, a, b); return (lane & 16) ? a : b; }
   else { float a, b; halves32(v, a, b); return (lane & 32) ? a : b; }
-#endif
 }
 // every lane of a 16-lane row gets the row's sum (rotations by 8, 4, 2, 1: the same bits in all 16 lanes)
 __device__ __forceinline__ float row_sum(float v) {
-#if TG_LANE_SHFL
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v += __shfl_xor(v, o, 64);
-  return v;
-#else
   v += dpp<0x128>(v);
   v += dpp<0x124>(v);
   v += dpp<0x122>(v);
   v += dpp<0x121>(v);
   return v;
-#endif
 }
 __device__ __forceinline__ float row_max(float v) {
-#if TG_LANE_SHFL
-#pragma unroll
-  for (int o = 1; o < 16; o <<= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-#else
   v = fmaxf(v, dpp<0x128>(v));
   v = fmaxf(v, dpp<0x124>(v));
   v = fmaxf(v, dpp<0x122>(v));
   v = fmaxf(v, dpp<0x121>(v));
   return v;
-#endif
 }
 // ... of the rows 2 j, 2 j + 1 / of the whole wave (every lane the same bits)
 __device__ __forceinline__ float rows16_sum(float v) {
-#if TG_LANE_SHFL
-  return v + __shfl_xor(v, 16, 64);
-#else
   float a, b; rows16(v, a, b); return a + b;
-#endif
 }
 __device__ __forceinline__ float halves32_sum(float v) {
-#if TG_LANE_SHFL
-  return v + __shfl_xor(v, 32, 64);
-#else
   float a, b; halves32(v, a, b); return a + b;
-#endif
 }
 __device__ __forceinline__ float wave_sum(float v) { return halves32_sum(rows16_sum(row_sum(v))); }
 __device__ __forceinline__ float wave_max(float v) {
-#if TG_LANE_SHFL
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-  return v;
-#else
   v = row_max(v);
   float a, b;
   rows16(v, a, b); v = fmaxf(a, b);
   halves32(v, a, b); return fmaxf(a, b);
-#endif
 }
 }  // namespace tgl
 
@@ -357,17 +323,14 @@ inline int cu_count() {
 // Tuning constants of the pair-table launches, each with the measurement that set it.  The shipped library
 // always uses these values; only developer builds (-DTG_DEV / -DTG_DEV_MIN, dev/build_variant.sh) may override one with -D<NAME>=<v>.
 #if !defined(TG_DEV) && !defined(TG_DEV_MIN)
-#if defined(TG_PAIR_R) || defined(TG_PAIR_ABL) || defined(TG_PAIR_MR1) || defined(TG_PAIR_NSG2) || defined(TG_PAIR_MR1_GPS) || defined(TG_PAIR_RA) ||   \
+#if defined(TG_PAIR_R) || defined(TG_PAIR_MR1) || defined(TG_PAIR_NSG2) || defined(TG_PAIR_MR1_GPS) || defined(TG_PAIR_RA) ||   \
     defined(TG_PAIR_RA1) || defined(TG_PAIR_RB16) || defined(TG_B16_CHUNK) || defined(TG_PAIR_MIN_ITEMS) || defined(TG_XG_CHUNK) || defined(TG_PAIR_WGS) || \
-    defined(TG_PAIR_NSG2_M1) || defined(TG_PAIR_FORCE_XG) || defined(TG_XR_MIN_M) || defined(TG_XR_R) || defined(TG_XR_R8K) || defined(TG_XR_RMX)
+    defined(TG_PAIR_NSG2_M1) || defined(TG_XR_MIN_M) || defined(TG_XR_R) || defined(TG_XR_R8K) || defined(TG_XR_RMX)
 #error "the TG_PAIR_* / TG_XG_* / TG_B16_* tuning constants can only be overridden in developer builds (-DTG_DEV or -DTG_DEV_MIN)"
 #endif
 #endif
 #ifndef TG_PAIR_R
 #define TG_PAIR_R 2            // super-tiles a wave keeps in flight (2, 3, 4 measured equal; 5 spills)
-#endif
-#ifndef TG_PAIR_ABL
-#define TG_PAIR_ABL 0          // ablation stub of w4_gemm_pair.cuh (its header lists them)
 #endif
 #ifndef TG_PAIR_MR1
 #define TG_PAIR_MR1 1          // 1: m = 1 runs the one-register specialisation (+2-3 %), 4: the general m <= 8 kernel

@@ -90,8 +90,8 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
 #ifndef TG_GEMV_MF_MAX_M
 #define TG_GEMV_MF_MAX_M 8  // (developer A/B against w4_gemm_pair16_kernel / the loop kernel at 5 ... 8 rows)
 #endif
-  const bool mf0 = p.m >= TG_GEMV_MF_MIN_M && p.m <= TG_GEMV_MF_MAX_M && (g0 == 128 || g0 == 256) && (p.k <= 4096 || p.m <= 4) && p.ksuper % 2 == 0;
-  if (I != 4 || qmx || (p.m > 4 && !mf0) || p.x_tc || p.y_tc || batch != 1) return TG_PAIR_NA;
+  const bool mf = p.m >= TG_GEMV_MF_MIN_M && p.m <= TG_GEMV_MF_MAX_M && (g0 == 128 || g0 == 256) && (p.k <= 4096 || p.m <= 4) && p.ksuper % 2 == 0;
+  if (I != 4 || qmx || (p.m > 4 && !mf) || p.x_tc || p.y_tc || batch != 1) return TG_PAIR_NA;
   if (p.ksuper * 64 != p.k || p.ntiles * 8 != p.wrows || p.ntiles > TG_GEMV_MAX_TILES) return TG_PAIR_NA;
   const int g = 1 << p.gshift;
   const int gps = g == 32 ? 2 : 1;
@@ -99,12 +99,9 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
   copy_call(gp, p);
   gp.sg_shift = g <= 64 ? 0 : g == 128 ? 1 : 2;
   gp.trace = nullptr;
-#ifndef TG_GEMV_CM
-#define TG_GEMV_CM 1
-#endif
   // (per graph node, same box: 4096^2 m = 8 6.74 -> 6.50 us, 6144 rows 9.2 -> 8.7, m = 6 + 1.6 %, m = 5 - 2 %: from six rows on;
   //  profiles/r05_ab_gemv_chunk_staging.txt)
-  gp.cm = (TG_GEMV_CM && mf0 && p.m >= 6 && (p.k == 4096 || p.k == 2048)) ? 1 : 0;
+  gp.cm = (mf && p.m >= 6 && (p.k == 4096 || p.k == 2048)) ? 1 : 0;
   gp.unit = p.epilogue == TG_EPI_SWIGLU ? 2 : 1;
   if (p.ntiles % gp.unit != 0) return TG_PAIR_NA;
   const int units = p.ntiles / gp.unit;
@@ -120,7 +117,7 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
   // (both workgroups of a CU must fit its 160 KiB of LDS together: the formula of `lds` below for the halved ranges)
   auto lds_two_per_cu = [&]() -> int64_t {
     const int tpw2 = ((units + 2 * cus - 1) / (2 * cus)) * gp.unit;
-    const int64_t xs = (int64_t)p.m * (p.k / 4), xsmf = mf0 ? (int64_t)(p.k / 128) * 64 : 0;
+    const int64_t xs = (int64_t)p.m * (p.k / 4), xsmf = mf ? (int64_t)(p.k / 128) * 64 : 0;
     return 65536 + (p.qtype == TG_Q_ANY4_ROWWISE ? tpw2 * 8 * 32 : 0) + (int64_t)p.m * (p.k * 2 + (p.m > 1 ? 16 : 0)) + (xsmf > xs ? xsmf : xs) +
            2 * 8 * p.m * 32 * 4 + 8 * p.m * 4;
   };
@@ -153,20 +150,11 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
     gp.urem = cus;
     gp.uextra = TG_GEMV_WG2_EXTRA;
   }
-  gp.uh = 0;
-#ifndef TG_GEMV_WG2_HALF
-#define TG_GEMV_WG2_HALF 0  // (developer A/B) with E = 1: this many of the CUs run 5 + 2 instead of 4 + 3
-#endif
-  if (TG_GEMV_WG2_HALF > 0 && gp.uextra == 1 && two_per_cu && wgs == 2 * cus && gp.urem == cus && gp.ubase >= 2) gp.uh = TG_GEMV_WG2_HALF < cus ? TG_GEMV_WG2_HALF : cus;
-  const int tpw = (gp.ubase + (gp.urem ? gp.uextra : 0) + (gp.uh ? 1 : 0)) * gp.unit;  // tiles of the largest range
-  // Ranges of THREE tiles at one activation row (q/k/v of Llama-3-8B: 6144 rows over 256 CUs): two 16-row passes carry a padding
-  // tile (4 tile slots for 3 tiles); three 8-row passes of the v_dot2 contraction would stream exactly the range -- measured SLOWER
-  // (6144 x 4096 per graph node 6.8 -> 7.2 us, the decode step unchanged; profiles/r05_ab_gemv_odd_p8.txt): developer knob only
-#ifndef TG_GEMV_ODD_P8
-#define TG_GEMV_ODD_P8 0
-#endif
-  const bool odd3 = TG_GEMV_ODD_P8 && p.m == 1 && tpw == 3 && gp.unit == 1 && p.ksuper % 4 == 0;
-  const bool mf = mf0 && !odd3;
+  gp.uh = 0;  // (always: 64 / 128 / 192 of the CUs on 5 + 2 and the rest on 4 + 3 measured slower than 5 + 2 everywhere, the decode step 1.486-1.50 against 1.470-1.479 ms; profiles/r05_ab_gemv_wg2_half.txt)
+  const int tpw = (gp.ubase + (gp.urem ? gp.uextra : 0)) * gp.unit;  // tiles of the largest range
+  // Ranges of THREE tiles at one activation row (q/k/v of Llama-3-8B: 6144 rows over 256 CUs) keep the matrix-core contraction: two
+  // 16-row passes carry a padding tile (4 tile slots for 3 tiles), but three 8-row passes of the v_dot2 contraction, which would stream
+  // exactly the range, measured SLOWER (6144 x 4096 per graph node 6.8 -> 7.2 us, the decode step unchanged; profiles/r05_ab_gemv_odd_p8.txt)
   // rows per pass of ranges longer than two tiles: 16 (two super-tiles of k per ring step), not 32 -- a range is rarely a multiple of
   // four tiles (Llama-3-8B: gate_up 14, q/k/v 3) and the padding tiles of its last pass cost what real ones do.  Same box, per graph
   // node, 32 -> 16: 28672 x 4096 17.6 -> 16.2-16.6 us, 8192 rows 7.6 -> 6.4, 10240 11.2 -> 8.9, 12288 10.8 -> 8.4, 32768 (a multiple
@@ -174,7 +162,7 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
 #ifndef TG_GEMV_P_BIG
 #define TG_GEMV_P_BIG 16
 #endif
-  gp.P = mf ? 16 : (tpw <= 1 || odd3) ? 8 : tpw <= 2 ? 16 : TG_GEMV_P_BIG;
+  gp.P = mf ? 16 : tpw <= 1 ? 8 : tpw <= 2 ? 16 : TG_GEMV_P_BIG;
   // a step covers SS = 32 / P consecutive super-tiles: they must all lie inside the matrix (the kernel's addressing has no per-lane
   // clamp), so k = 64 x odd runs 32-row passes whatever the range, k = 128 x odd at least 16-row passes
   if (p.ksuper % 2 != 0) gp.P = 32;

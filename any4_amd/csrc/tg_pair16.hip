@@ -100,9 +100,6 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
 
 // ONE layer per launch with more 16-row tiles than compute units (w4_gemm_pair16_loop.cuh): 5 ... 16 activation rows, k = 4096, innerKTiles 4,
 // row-major operands, no fused stage; a workgroup owns up to 32 tiles.
-#ifndef TG_P16_LOOP
-#define TG_P16_LOOP 1
-#endif
 #ifndef TG_P16_LOOP_MAX_TILES
 #define TG_P16_LOOP_MAX_TILES 8   // tiles per workgroup up to which this path takes the launch.  Per graph node at m = 16, rows 5120 / 8192 / 11008 / 12288 /
                                   // 14336 / 16384 / 20480 / 28672: 8.5 / 9.0 / 10.8 / 10.9 / 13.0 / 13.1 / 15.2 / 19.5 us here; w4_gemm_xr_kernel with one workgroup per
@@ -110,7 +107,7 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
 #endif
 template <typename DT>
 int launch_pair16_loop(const GemmParams& p, int64_t batch, hipStream_t st) {
-  if (!TG_P16_LOOP || batch != 1 || p.m < TG_P16_XREG_MIN_M || p.m > 16 || p.k != 4096 || p.ksuper != 64 || (p.epilogue && (p.epilogue != TG_EPI_SWIGLU || p.bias || p.wrows % 16 != 0)) || p.x_tc || p.y_tc ||
+  if (batch != 1 || p.m < TG_P16_XREG_MIN_M || p.m > 16 || p.k != 4096 || p.ksuper != 64 || (p.epilogue && (p.epilogue != TG_EPI_SWIGLU || p.bias || p.wrows % 16 != 0)) || p.x_tc || p.y_tc ||
       p.qtype == TG_Q_MX4)
     return TG_PAIR_NA;
   if (p.norm_w && p.gshift == 5) return TG_PAIR_NA;  // (groups of 32 with the fused norm: not instantiated, see the kernel)

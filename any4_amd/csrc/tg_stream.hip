@@ -55,7 +55,7 @@ int launch_stream_sw(StreamParams& sp, int sk, int64_t coltiles, int64_t batch, 
   dim3 grid((unsigned)((sp.rowtiles + tpb - 1) / tpb), (unsigned)coltiles, (unsigned)batch);
 #define TG_LAUNCH_STREAM_LK(XL, LK_)                                                                      \
   do {                                                                                                    \
-    constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, 0, false, LK_>; \
+    constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, false, LK_>; \
     if (sp.dry) return TG_PLAN_STREAM;                                                                    \
     const int prc = prepare_lds_kernel<kern>();                                                           \
     if (prc != 0) return prc;                                                                             \
@@ -96,14 +96,14 @@ int launch_stream_xres(StreamParams& sp, int64_t coltiles, int64_t batch, unsign
   dim3 grid((unsigned)((sp.rowtiles + 16 * tpw - 1) / (16 * tpw)), (unsigned)coltiles, (unsigned)batch);
   if constexpr (!LAYOUT_A) {
     if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15) {
-      constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, 0, true, 1>;
+      constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 1>;
       const int prc = prepare_lds_kernel<kern>();
       if (prc != 0) return prc;
       hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lds, st, sp);
       return launch_status();
     }
   }
-  constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, 0, true, 0>;
+  constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 0>;
   const int prc = prepare_lds_kernel<kern>();
   if (prc != 0) return prc;
   hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lds, st, sp);
@@ -127,17 +127,8 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
   // (m = 1, private slabs: one round of 16 waves per CU is enough -- measured on the Llama-3-8B shapes)
   const int64_t want = mrows == 1 ? 256 * 16 : 2 * 256 * 16;
   while (sk < 8 && wave_tiles * sk < want && nunits >= 8 * sk * upg && mrows * sk * 2 <= 16) sk *= 2;
-#ifdef TG_DEV
-  static const int sk_env = getenv("TG_SK") ? atoi(getenv("TG_SK")) : 0;  // developer override
-  if (sk_env > 0) sk = sk_env;
-#endif
   // m == 1: every wave stages its own X slab (no barrier in the main loop); a workgroup is the sk waves of one tile
-#ifdef TG_DEV
-  static const int xres_env = getenv("TG_XRES") ? atoi(getenv("TG_XRES")) : 1;  // developer knob: 0 off, 2 also for m = 1
-#else
-  constexpr int xres_env = 1;
-#endif
-  if (mrows == 1 && xres_env != 2) {
+  if (mrows == 1) {
     switch (sk) {
       case 1: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 1>(sp, 1, coltiles, batch, st);
       case 2: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 2, true>(sp, 2, coltiles, batch, st);
@@ -149,7 +140,7 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
   // tables (m = 8 at k = 4096 does: 66 KiB + 64 KiB) -- one barrier per workgroup instead of one per unit
   // (measured: wins for m >= 8 at k = 4096 and for m >= 2 at k = 8192; the 16-wave workgroup costs ~15 % in tile-granularity
   //  tail against 4-wave workgroups, which the small slabs of m <= 4 at k = 4096 do not pay back)
-  if (sk == 1 && xres_env && (mrows * UNIT >= 1024 || sp.k >= 8192 || xres_env == 2)) {
+  if (sk == 1 && (mrows * UNIT >= 1024 || sp.k >= 8192)) {
     const int nu = (int)(((nunits + 3) / 4 + upg - 1) / upg * upg);
     const unsigned xrow = (unsigned)(nu * UNIT * 2 + 16);
     const unsigned lds = 16u * 4096u + (unsigned)(mrows * 4) * xrow + (unsigned)(UNIT * 2 + 16);

@@ -5,23 +5,11 @@ namespace {
 #include "w4_gemm_xr.cuh"
 // Bint4 weights, stacked launches, TG_XR_MIN_M ... 16 activation rows, k = 4096: w4_gemm_xr_kernel (one 8-wave workgroup per CU, the
 // activations of a wave's k-slice resident in its registers, 64-row work items, two tables).  No workspace, no pre-pass.
-#ifndef TG_XR_WV16
-#define TG_XR_WV16 0  // 1 (developer builds): k = 4096, not mx4, on sixteen k-slices per workgroup (w4_gemm_xr.cuh, WV) -- four waves per
-                      // SIMD instead of two, measured EQUAL at m = 8 (71.5 vs 71.3 %) and slower at m = 16 (67.1 vs 69.0 %): not shipped
-#endif
-#ifndef TG_XR_R16
-#define TG_XR_R16 2   // ring depth of the sixteen-slice variant (a slice is four super-tiles)
-#endif
-#ifndef TG_XR_WV4
-#define TG_XR_WV4 0   // 1 (developer builds): k = 4096 with at most 8 rows on two 4-slice workgroups per CU, packed rows, one table each (w4_gemm_xr.cuh,
-                      // WV = 4) -- the tail of one workgroup under the main loop of the other.  Measured SLOWER, same box: m = 8 72.3 vs 73.3 %, m = 4 72.7 vs
-                      // 75.4 %, m = 2 75.2 vs 77.1 % (profiles/r05_ab_xr_wv4.txt): it is not the stall of the tail that costs, not shipped
-#endif
+// Always eight k-slices per workgroup: sixteen (four waves per SIMD instead of two) measured equal at m = 8 (71.5 vs 71.3 %) and slower at
+// m = 16 (67.1 vs 69.0 %); two 4-slice workgroups per CU (the tail of one under the main loop of the other) measured slower, m = 8 72.3 vs
+// 73.3 %, m = 2 75.2 vs 77.1 % (profiles/r05_ab_xr_wv4.txt): it is not the stall of the tail that costs.
 #ifndef TG_XR_WINDOWS_14336
 #define TG_XR_WINDOWS_14336 16, 16, 24   // k = 14336 at 9 ... 16 rows as k-windows of 256 x these chunk counts (launch_pair_xr_windows)
-#endif
-#ifndef TG_XR_PK_K4096
-#define TG_XR_PK_K4096 0  // 1 (developer builds): k = 4096 with at most 8 rows on the packed-rows variant too (32 instead of 64 activation registers)
 #endif
 // a k-window [k0, k0 + 256 NCH) of a longer contraction: the kernel runs on the window's pointers (the packed layout keeps the whole
 // matrix's tile stride and the activations the whole row pitch) and leaves its UNROUNDED f32 sums in y32 (launch_pair_xr_windows)
@@ -31,7 +19,7 @@ struct XrWindow {
   char* y32;
   int64_t stride_y32;
 };
-template <typename DT, int I, bool QMX, int NCH, int WV = 8, bool PK = false>
+template <typename DT, int I, bool QMX, int NCH, bool PK = false>
 int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindow* win = nullptr) {
   if constexpr (I != 4 || (QMX && (NCH != 16 || !std::is_same<DT, BF16>::value))) return TG_PAIR_NA;  // (mx4: bf16, k = 4096)
   else {
@@ -75,14 +63,14 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   //  row-major operands, not mx4: 5120 / 8192 / 12288 / 16384 / 28672 rows at m = 16 8.5 / 9.0 / 10.9 / 13.1 / 19.5 us against 12.3 / 12.4 / 12.9 /
   //  13.7 / 19.4 here; this route keeps fragment-order operands, mx4 and longer layers)
   const bool p16_loop = !p.x_tc && !p.y_tc && !QMX && I == 4 && p.m >= 5 && (int64_t)((p.wrows + 15) / 16) <= 8 * (int64_t)(p.dry ? 256 : cu_count());
-  const bool single = batch == 1 && NCH == 16 && !PK && WV == 8 && !win && !p16_loop &&
+  const bool single = batch == 1 && NCH == 16 && !PK && !win && !p16_loop &&
                       ((p.m >= 9 && items >= TG_XR_SINGLE_MIN_ITEMS) || (p.m >= 5 && items >= TG_XR_SINGLE_MIN_ITEMS_M8));
   if (items > INT32_MAX) return TG_PAIR_NA;
-  if (!single && items < TG_XR_MIN_ITEMS_PER_WG * 256 * (WV == 4 ? 2 : 1)) return TG_PAIR_NA;
+  if (!single && items < TG_XR_MIN_ITEMS_PER_WG * 256) return TG_PAIR_NA;
   xp.items = (int32_t)items;
-  xp.lds_xs = WV == 4 ? 65536 : 2 * 65536;
-  // two tables (WV = 4: one, and the 8 KiB hand-over region behind the sums), the activation sums (mx4: the partial sums only)
-  const unsigned lds = QMX ? 32768u : (unsigned)xp.lds_xs + (unsigned)(win ? win->ngroups : p.ngroups) * 64u + (WV == 4 ? 8192u : 0u);
+  xp.lds_xs = 2 * 65536;
+  // two tables, the activation sums (mx4: the partial sums only)
+  const unsigned lds = QMX ? 32768u : (unsigned)xp.lds_xs + (unsigned)(win ? win->ngroups : p.ngroups) * 64u;
   if (lds > 160u * 1024u) return TG_PAIR_NA;
   p.ws_need = 0;
   xp.y_tiles = (p.wrows + 15) / 16;
@@ -93,15 +81,15 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
     xp.y = win->y32; xp.stride_y = win->stride_y32; xp.y_f32 = 1; xp.bias = nullptr;
   }
   if (p.dry) return TG_PLAN_PAIR_XR;
-  unsigned wgs = (unsigned)cu_count() * (WV == 4 ? 2u : 1u);  // one 8-wave (two 4-wave) workgroup(s) per compute unit, whatever the part has
+  unsigned wgs = (unsigned)cu_count();  // one 8-wave workgroup per compute unit, whatever the part has
   if (single) wgs = items < (int64_t)wgs ? (unsigned)items : wgs;
   else if (items < TG_XR_MIN_ITEMS_PER_WG * (int64_t)wgs) return TG_PAIR_NA;
 #define TG_XR_LAUNCH(CPG_)                                                  \
   do {                                                                      \
-    constexpr auto kern = w4_gemm_xr_kernel<DT, I, NCH, CPG_, (WV == 16 ? TG_XR_R16 : ((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R), false, WV, PK>; \
+    constexpr auto kern = w4_gemm_xr_kernel<DT, I, NCH, CPG_, (((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R), false, PK>; \
     const int prc = prepare_lds_kernel<kern>();                             \
     if (prc != 0) return prc == TG_E_INTERNAL ? prc : TG_PAIR_NA; /* (a part with less LDS: the older kernels take over) */ \
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3(WV * 64), lds, st, xp);        \
+    hipLaunchKernelGGL(kern, dim3(wgs), dim3(512), lds, st, xp);            \
   } while (0)
   if constexpr (QMX) {
     constexpr auto kern = w4_gemm_xr_kernel<DT, I, NCH, 1, TG_XR_RMX, true>;
@@ -221,29 +209,15 @@ int launch_pair_xr_windows(GemmParams& p, int64_t batch, hipStream_t st) {
 
 template <typename DT, int I, bool QMX>
 int launch_pair_xr(GemmParams& p, int64_t batch, hipStream_t st) {
-  if constexpr (!QMX && TG_XR_WV16) {
-    if (p.k == 4096 && (1 << p.gshift) <= 256) return launch_pair_xr_n<DT, I, QMX, 8, 16>(p, batch, st);
-  }
-  if constexpr (!QMX && TG_XR_WV4) {
-    if (p.k == 4096 && p.m <= 8) {
-      const int rc = launch_pair_xr_n<DT, I, QMX, 32, 4, true>(p, batch, st);
-      if (rc != TG_PAIR_NA) return rc;  // (fewer than four items per CU: the 8-wave kernel below)
-    }
-  }
-  if constexpr (!QMX && TG_XR_PK_K4096) {
-    if (p.k == 4096 && p.m <= 8) return launch_pair_xr_n<DT, I, QMX, 16, 8, true>(p, batch, st);
-  }
   if (p.k == 4096) return launch_pair_xr_n<DT, I, QMX, 16>(p, batch, st);
   // k = 8192, 9 ... 16 rows: 128 registers of activations per lane leave room for two super-tiles in flight only -- faster than
   // the 16x16x32 workspace kernel it replaces (8192^2, m = 16: 62 vs 47-51 %).  Up to 8 rows: two chunks per register set (PK),
   // 64 registers, four super-tiles in flight like k = 4096
   if constexpr (!QMX) {
-    if (p.k == 8192 && p.m <= 8) return launch_pair_xr_n<DT, I, QMX, 32, 8, true>(p, batch, st);
+    if (p.k == 8192 && p.m <= 8) return launch_pair_xr_n<DT, I, QMX, 32, true>(p, batch, st);
   }
-#ifndef TG_XR_WINDOWS_8192
-#define TG_XR_WINDOWS_8192 1   // 1: k = 8192 at 9 ... 16 rows as two k-windows of 4096 (the ring stays four deep) when the caller brings the workspace
-#endif
-  if constexpr (!QMX && TG_XR_WINDOWS_8192) {
+  // k = 8192 at 9 ... 16 rows as two k-windows of 4096 (the ring stays four deep) when the caller brings the workspace
+  if constexpr (!QMX) {
     if (p.k == 8192 && p.m >= 9) {
       const int rc = launch_pair_xr_windows<DT, I, 16, 16>(p, batch, st);
       if (rc != TG_PAIR_NA) return rc;
@@ -254,7 +228,7 @@ int launch_pair_xr(GemmParams& p, int64_t batch, hipStream_t st) {
   if constexpr (!QMX) {
     // (same box, 4096 x 14336 against the workspace variant of w4_gemm_pair_kernel: m = 8 67.9 -> 70.0 %, but m = 4 72.9 -> 69.1 and
     //  m = 2 76.5 -> 72.3, m = 6 71.1 -> 68.8 -- profiles/r05_ab_xr_k14336.txt: eight rows only)
-    if (p.k == 14336 && p.m == 8) return launch_pair_xr_n<DT, I, QMX, 56, 8, true>(p, batch, st);
+    if (p.k == 14336 && p.m == 8) return launch_pair_xr_n<DT, I, QMX, 56, true>(p, batch, st);
     if (p.k == 14336 && p.m >= 9) return launch_pair_xr_windows<DT, I, TG_XR_WINDOWS_14336>(p, batch, st);
   }
   return TG_PAIR_NA;

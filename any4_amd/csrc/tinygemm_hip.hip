@@ -37,12 +37,6 @@ namespace {
 #include "tg_convert.cuh"
 
 
-#ifdef TG_DEV  // developer builds only (-DTG_DEV): geometry override through the environment, never in the shipped library
-int g_dbg_variant = 0;
-#else
-constexpr int g_dbg_variant = 0;
-#endif
-
 // Launch geometry.  Streaming shapes (many tiles) use 8-wave workgroups, two per CU, and the
 // smallest split-K that still puts >= ~16 waves on every CU; a single small matrix (one tile per
 // CU) uses one 16-wave workgroup per tile with split-K 16.
@@ -54,10 +48,7 @@ inline Geometry pick_geometry(int64_t rowtiles, int64_t coltiles, int64_t batch,
   const int64_t tiles = rowtiles * coltiles * batch;
   const int64_t want_waves = 256 * 16;  // 256 CUs x 16 waves
   Geometry g;
-  if (g_dbg_variant > 0) {  // developer override: variant = 100 * waves + splitk
-    g.waves = g_dbg_variant / 100;
-    g.splitk = g_dbg_variant % 100;
-  } else if (tiles * 8 <= want_waves) {
+  if (tiles * 8 <= want_waves) {
     g.waves = 16;
     g.splitk = 16;
   } else {
@@ -100,12 +91,7 @@ int launch_w4(int dt, bool LAYOUT_A, int canon, bool QMX, GemmParams& p, int64_t
   const int tpb = g.waves / g.splitk;
   dim3 grid((unsigned)((p.rowtiles + tpb - 1) / tpb), (unsigned)coltiles, (unsigned)batch);
   // Streaming shapes go to the lane-owns-group kernel when the quantisation group covers at least one
-  // unit of its walk (Bint4: g >= 128, Aint4: g >= 64).  TG_STREAM=0 forces the split-K kernel.
-#ifdef TG_DEV
-  static const int use_stream = getenv("TG_STREAM") ? atoi(getenv("TG_STREAM")) : 1;
-#else
-  constexpr int use_stream = 1;
-#endif
+  // unit of its walk (Bint4: g >= 128, Aint4: g >= 64).
   const int WPL = canon == CANON_NONE ? 1 : (canon == CANON_PAIR ? 2 : 4);
   // TG_NUM_FAST, weights on the B side: the pair-table kernel (group-scaled numerics) whenever its LDS plan fits
   // (mx4 in BOTH numerics: its dequantised weights, fp4 * 2^(e - 127), are exact 16-bit values however they are formed, so the
@@ -147,7 +133,7 @@ int launch_w4(int dt, bool LAYOUT_A, int canon, bool QMX, GemmParams& p, int64_t
   return TG_E_SHAPE;
 #else
   // m = 1 always streams: with private X slabs its split-K variants beat the latency kernel down to one matrix
-  if (use_stream && (g.waves == 8 || p.m == 1 || use_stream == 2) && (1 << p.gshift) >= (LAYOUT_A ? 64 : 128)) {
+  if ((g.waves == 8 || p.m == 1) && (1 << p.gshift) >= (LAYOUT_A ? 64 : 128)) {
     return tgx::stream(dt, LAYOUT_A, WPL, QMX, p, coltiles, batch, st);
   }
   if (p.dry) return TG_PLAN_SPLITK;
@@ -452,7 +438,7 @@ static PackedLayout gemm_layout(const tg_w4_gemm* a) {
 static GemmParams make_params(const tg_w4_gemm* a, PackedLayout l, int dry) {
   const bool batched = a->batch > 1;
   GemmParams p;
-  memset(&p, 0, sizeof p);   // (splitk / sk_shift: the launch path's; ws_need: the planner's answer; dbg: developer builds)
+  memset(&p, 0, sizeof p);   // (splitk / sk_shift: the launch path's; ws_need: the planner's answer; dbg: always 0)
   p.x = (const char*)a->x;
   p.w = (const char*)a->w;
   p.qinfo = (const char*)a->qinfo;
@@ -500,14 +486,6 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
   const bool on_right = lay.on_right;
   const int I = lay.I, batch = a->batch > 1 ? a->batch : 1;
   GemmParams p = make_params(a, lay, dry);
-#ifdef TG_DEV
-  {
-    static const int env_dbg = getenv("TG_DBG") ? atoi(getenv("TG_DBG")) : 0;
-    static const int env_var = getenv("TG_VARIANT") ? atoi(getenv("TG_VARIANT")) : 0;
-    p.dbg = env_dbg;
-    g_dbg_variant = env_var;
-  }
-#endif
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
   hipStream_t st = (hipStream_t)stream;
@@ -535,13 +513,10 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
   // Up to 64 rows: from 128 rows on the stream kernel's ONE launch (its 16-row tiles of m run concurrently and share the weights in
   // L2) wins -- one 4096^2 layer per graph node at m = 128 / 256 / 1024: 37.8 / 44.5 / 166 us against 55 / 102 / 427 in blocks
   // (profiles/r05_row_blocks_large_m.txt).
-#ifndef TG_ROW_BLOCKS
-#define TG_ROW_BLOCKS 1
-#endif
 #ifndef TG_ROW_BLOCKS_MAX_M
 #define TG_ROW_BLOCKS_MAX_M 64
 #endif
-  if (TG_ROW_BLOCKS && on_right && a->m > 16 && a->m <= TG_ROW_BLOCKS_MAX_M && (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA) && !p.x_tc && !p.y_tc &&
+  if (on_right && a->m > 16 && a->m <= TG_ROW_BLOCKS_MAX_M && (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA) && !p.x_tc && !p.y_tc &&
       !p.norm_w && !p.epilogue) {
     // decided on a dry pass over the two block shapes of the call (16 rows, the ragged last block): both on a group-scaled kernel, or the
     // whole call stays on the path below

@@ -50,7 +50,7 @@ struct Slot {
   u32x4 x[NMMA];  // X fragments
 };
 
-template <typename DT, bool LAYOUT_A, int CANON, bool QMX, int WAVES, int DEPTH, int MINW, int ABL = 0>
+template <typename DT, bool LAYOUT_A, int CANON, bool QMX, int WAVES, int DEPTH, int MINW>
 __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmParams p) {
   constexpr int CHUNK = LAYOUT_A ? 16 : 32;  // k covered by one lane per step
   constexpr int KSTEP = 4 * CHUNK;           // k covered by one wave per step
@@ -111,9 +111,8 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmPar
     else if constexpr (CANON == CANON_PAIR) ks = 2 * s + (Q >> 1);
     else ks = s;
     ks = min(ks, p.ksuper - 1);
-    if constexpr (ABL == 3 || ABL == 9) sl.w = u32x4{(uint32_t)ks, 1u, 2u, 3u};  // ablation: no weight stream
     // (Aint4: lanes i and i + 8 read the same words -- keep them cacheable, see w4_gemm_stream.cuh)
-    else if constexpr (LAYOUT_A) sl.w = *reinterpret_cast<const u32x4*>(wb + (wlane + (uint32_t)ks * wstep));
+    if constexpr (LAYOUT_A) sl.w = *reinterpret_cast<const u32x4*>(wb + (wlane + (uint32_t)ks * wstep));
     else sl.w = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wb + (wlane + (uint32_t)ks * wstep)));
     const int kk = s * KSTEP + Q * CHUNK;  // first k of this lane's canonical chunk
     const bool ok = tile_ok && row_ok && kk < p.k;
@@ -131,8 +130,7 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmPar
     const uint32_t xo = xlane + (uint32_t)((s * KSTEP - (kk - kk_c)) * 2);
 #pragma unroll
     for (int h = 0; h < NMMA; ++h) {
-      if constexpr (ABL == 2) sl.x[h] = u32x4{xo, 1u, 2u, 3u};  // ablation: no X loads
-      else if (xcol) sl.x[h] = *reinterpret_cast<const u32x4*>(xb + (xo + 16u * h));
+      if (xcol) sl.x[h] = *reinterpret_cast<const u32x4*>(xb + (xo + 16u * h));
       else sl.x[h] = u32x4{0u, 0u, 0u, 0u};  // unused MFMA column: zero operand (its output is never stored)
     }
   };
@@ -179,15 +177,10 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmPar
 
   auto lookup = [&](uint32_t src, int byte) -> float {
     const uint32_t addr = __builtin_amdgcn_perm(src, lane4, 0x03020400u + ((uint32_t)byte << 8));
-    if constexpr (ABL == 1) return u2f(addr);  // ablation: no LDS lookup
     return *(lds_cfptr)(addr);
   };
 
   auto process = [&](const Slot<NMMA>& sl) {
-    if constexpr (ABL == 4) {  // ablation: stream only, no dequant / MFMA
-      acc[0] += u2f(sl.w[0] ^ sl.w[1] ^ sl.w[2] ^ sl.w[3] ^ sl.q ^ sl.x[0][0] ^ sl.x[NMMA - 1][3]);
-      return;
-    }
     u32x4 w = sl.w;
     canonicalize<CANON>(w);
     float s, z;
@@ -208,29 +201,6 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmPar
       for (int q = 0; q < 4; ++q) {
         wa[q] = (w[q] & 0x0f0f0f0fu) | kmask;          // bytes: v0 v4 v1 v5
         wb4[q] = ((w[q] >> 4) & 0x0f0f0f0fu) | kmask;  // bytes: v2 v6 v3 v7
-      }
-      if constexpr (ABL >= 8) {
-        // experiment: all 32 lookups in flight before the first fma
-        float f[32];
-#pragma unroll
-        for (int h = 0; h < 4; ++h)
-#pragma unroll
-          for (int q = 0; q < 4; ++q) {
-            const uint32_t src = (h & 1) ? wb4[q] : wa[q];
-            f[h * 8 + q * 2] = lookup(src, h >> 1);
-            f[h * 8 + q * 2 + 1] = lookup(src, (h >> 1) + 2);
-          }
-        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          u32x4 a;
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            a[q] = DT::pack2(__builtin_fmaf(f[h * 8 + q * 2], s, z), __builtin_fmaf(f[h * 8 + q * 2 + 1], s, z));
-          acc = DT::mfma(a, sl.x[h], acc);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        return;
       }
 #pragma unroll
       for (int h = 0; h < 4; ++h) {

@@ -50,11 +50,6 @@
 //                the register ring of R super-tiles of packed words (+ scale|zero words) a wave keeps in flight from HBM
 //                runs across item boundaries, and the LUT rows of the next item are requested at the start of the current
 //                one, so the weight stream never drains while a table is rebuilt.  Two barriers per item.
-//
-// ABL (template parameter, always 0 in the shipped library; developer builds set it with -DTG_PAIR_ABL=<n>, dev/README.md) stubs one
-// stage out so that its cost can be read off a same-box A/B: 1 no table lookups, 3 no weight loads, 4 no MFMA, 5 no activation
-// reads from LDS, 6 stream only (loads, table build, staging, barriers), 7 no per-group work, 8 no scale | zero loads,
-// 9 / 10 workspace variant without the activation loads / their LDS store, 11 no activation-sum staging.
 #pragma once
 
 // Element (r, c) of a matrix kept in the reference's m16n8k16 A-fragment order [ceil(rows/16)][ctiles = ceil(cols/16)][32][8]
@@ -95,9 +90,6 @@ __device__ __forceinline__ uint32_t mx4_cvt_byte(uint32_t w, float scale, int se
   }
 }
 
-#ifndef TG_PAIR_M1_DOT
-#define TG_PAIR_M1_DOT 1  // the m = 1 specialisation contracts with v_dot2_f32_bf16 per lane instead of the MFMA (0: MFMA, for A/B builds)
-#endif
 template <typename DT>
 __device__ __forceinline__ float dot2_pair(uint32_t a, uint32_t b, float acc) {
   if constexpr (std::is_same<DT, BF16>::value)
@@ -238,7 +230,8 @@ __device__ __forceinline__ uint16_t swiglu16(float gsum, float usum) {
 //         The pair bytes are (code k, code k + 8): v_bfi of the word with itself shifted by one nibble.  Two lanes of a
 //         32-lane LDS access group share a weight row, so the table holds every row twice (32 rows x 2 copies = the same
 //         64 columns), the copy chosen by kb & 1: conflict-free.
-template <typename DT, int I, int GPS, int MR, bool QMX, int R, int NSG = 0, int ABL = 0, bool XG = false, int LAY = 0, bool NORM = false>
+// M1_MFMA = the m = 1 specialisation keeps the 32x32x16 MFMA as its contraction (tg_w4_gemm.numerics = TG_NUM_FAST_MFMA) instead of the per-lane v_dot2
+template <typename DT, int I, int GPS, int MR, bool QMX, int R, int NSG = 0, bool M1_MFMA = false, bool XG = false, int LAY = 0, bool NORM = false>
 __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p) {
   // LAY: 0 = Bint4 weights on 32x32x16 tiles (the description above), 1 = Aint4 weights (LA), 2 = Bint4 weights on 16x16x32 tiles (LB)
   constexpr bool LA = LAY == 1, LB = LAY == 2, T16 = LAY != 0;
@@ -246,8 +239,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
   // multiplier slots on 512 useful products and, under the 1400 W cap, clock -- 4 v_dot2 per word instead: 76.3 -> 80.6 % on the
   // headline shape, int4 82.6 -> 84.4 %, global LUT 79.4 -> 84.0 % same-box.  Only with fixed group boundaries (NSG > 0): the
   // run-time group test around it compiles to 128 VGPRs + 200-500 bytes of scratch.
-  // ABL == 100 (the one non-zero value in the shipped library: tg_w4_gemm.numerics = TG_NUM_FAST_MFMA) keeps the MFMA at m = 1
-  constexpr bool DOT = TG_PAIR_M1_DOT && ABL != 100 && MR == 1 && !T16 && (QMX || NSG > 0);  // (mx4 has no group updates: any NSG)
+  constexpr bool DOT = !M1_MFMA && MR == 1 && !T16 && (QMX || NSG > 0);  // (mx4 has no group updates: any NSG)
   constexpr bool MXC = QMX;  // mx4: weights converted by v_cvt_scalef32_pk_bf16_fp4 (mx4_cvt_word), no table, no group updates
   static_assert(!NORM || (!XG && !T16 && !QMX), "fused RMSNorm: the workgroup stages the whole activation block itself");
   constexpr int WAVES = 8;
@@ -429,13 +421,10 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
 #pragma unroll
       for (int i = 0; i < NXW; ++i) {
         if constexpr (T16) {  // chunk s CPS + i: a block of 4 k-quads x (rows + the zero row) pieces
-          if constexpr (ABL == 9 || ABL == 13) sl.xw[i] = u32x4{rw.xoff[0], (uint32_t)s, 0x3f803f80u, 0x3f803f80u};  // ablation: no activation loads
-          else if constexpr (ABL == 12) sl.xw[i] = *reinterpret_cast<const u32x4*>(rw.xpb + uni((uint32_t)i * rw.xblk) + pin(rw.xoff[0]));  // ablation: every chunk reads the first block (L1 hits)
-          else sl.xw[i] = *reinterpret_cast<const u32x4*>(rw.xpb + uni((sv * CPS + (uint32_t)i) * rw.xblk) + pin(rw.xoff[0]));
+          sl.xw[i] = *reinterpret_cast<const u32x4*>(rw.xpb + uni((sv * CPS + (uint32_t)i) * rw.xblk) + pin(rw.xoff[0]));
           continue;
         }
-        if constexpr (ABL == 9) sl.xw[i] = u32x4{rw.xoff[i], (uint32_t)s, 0x3f803f80u, 0x3f803f80u};  // ablation: no activation loads
-        else sl.xw[i] = *reinterpret_cast<const u32x4*>(rw.xpb + uni(sv * rw.xblk) + pin(rw.xoff[i]));
+        sl.xw[i] = *reinterpret_cast<const u32x4*>(rw.xpb + uni(sv * rw.xblk) + pin(rw.xoff[i]));
       }
     }
 #pragma unroll
@@ -443,10 +432,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
       if (t < WT) {  // (compile-time; the A side's two tiles share one set of words)
         const int tw = t < WT ? t : 0;
         const char* src = rw.wb + uni(sv * (uint32_t)((LA ? 128 : 64) * I)) + pin(rw.wbase[tw]);
-        if constexpr (ABL == 3 || ABL == 13) {
-#pragma unroll
-          for (int j = 0; j < NW; ++j) sl.w[tw][j] = (uint32_t)(s * 7 + j + t);
-        } else if constexpr (NW == 1) {
+        if constexpr (NW == 1) {
           sl.w[tw][0] = __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(src));
         } else if constexpr (NW == 2) {
           const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(src));
@@ -464,8 +450,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
       for (int gg = 0; gg < GPS; ++gg) {
         if (!needq) continue;  // (compile-time per call site) not the first super-tile of its group
         const uint32_t g = (uint32_t)(((sv * CPS + gg * CPG) * 32) >> p.gshift);
-        if constexpr (ABL == 8) sl.q[t][gg] = 0x3c003c00u + (uint32_t)s;  // ablation: no scale | zero loads
-        else if constexpr (QMX) sl.q[t][gg] = 0u;  // mx4: the exponents come in 16-byte blocks per row, see e_request
+        if constexpr (QMX) sl.q[t][gg] = 0u;  // mx4: the exponents come in 16-byte blocks per row, see e_request
         else sl.q[t][gg] = *reinterpret_cast<const uint32_t*>(rw.qb + uni(g * (uint32_t)p.wrows * 4u) + pin(rw.qrow4[t]));
       }
     }
@@ -688,7 +673,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
       staged_b = cur.b;
       staged_ct = cur.ct;
       if constexpr (XG) {
-        if (ABL != 11) xs_stage(cur.b, cur.ct, mrows);
+        xs_stage(cur.b, cur.ct, mrows);
       } else {
         uint32_t xd[16];
         x_stage(cur.b, a0, mrows, false, xd);
@@ -804,15 +789,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
         // is control flow, and around it the compiler copied the accumulator tuples
 #pragma unroll
         for (int i = 0; i < NXW; ++i)
-          if constexpr (ABL != 10) *(lds_u32x4ptr)(xw_dst + (uint32_t)(i * (64 / (2 * I)) * p.xw_pitch)) = sl.xw[i];
-      }
-      if constexpr (ABL == 6) {  // ablation: stream only
-#pragma unroll
-        for (int t = 0; t < WT; ++t)
-#pragma unroll
-          for (int j = 0; j < I; ++j) acc[t][0] += u2f(sl.w[t][j]);
-        acc[0][1] += u2f(sl.q[0][0] ^ sl.q[1][0]);
-        return;
+          *(lds_u32x4ptr)(xw_dst + (uint32_t)(i * (64 / (2 * I)) * p.xw_pitch)) = sl.xw[i];
       }
 #pragma unroll
       // B side: a step = half a 32-k chunk (quads 2 h + qq); A side: a whole chunk (one word pair = two 16-k tiles)
@@ -827,8 +804,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
         const bool glast = qlast && (GPS > 1 ? jc % CPG == CPG - 1 : NSG > 0 ? (gpos == NSG - 1 && jc == CPS - 1) : (chunk & p.gch_mask) == p.gch_mask);
         u32x4 xf;
         u32x4 bf[TILES];
-        if constexpr (ABL == 5) xf = u32x4{xrow, (uint32_t)s, (uint32_t)jc, (uint32_t)qq};  // ablation: no X reads
-        else if constexpr (T16) xf = sl.xw[jc];
+        if constexpr (T16) xf = sl.xw[jc];
         else xf = *(lds_cu32x4ptr)(xst + (uint32_t)(jc * 64 + 16 * qq));
 #pragma unroll
         for (int t = 0; t < TILES; ++t) {
@@ -859,8 +835,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
                 continue;
               }
               const uint32_t addr = __builtin_amdgcn_perm(uw[j & 1], colreg[t], 0x0c0c0400u + ((uint32_t)(t + 2 * (j >> 1)) << 8));
-              if constexpr (ABL == 1) bf[t][j] = addr;
-              else bf[t][j] = *(lds_cu32ptr)(addr);
+              bf[t][j] = *(lds_cu32ptr)(addr);
             }
           } else if constexpr (LB) {
             // one packed word = the 8 codes of this lane's row at k = 2 q + {0, 16, 1, 17, 8, 24, 9, 25} of the chunk = one B
@@ -872,8 +847,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
 #pragma unroll
               for (int j = 0; j < 4; ++j) {
                 const uint32_t addr = __builtin_amdgcn_perm(w, colreg[t], 0x0c0c0400u + ((uint32_t)j << 8));
-                if constexpr (ABL == 1) bf[t][j] = addr;
-                else bf[t][j] = *(lds_cu32ptr)(addr);
+                bf[t][j] = *(lds_cu32ptr)(addr);
               }
             }
           } else if constexpr (MXC) {
@@ -883,8 +857,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
               const uint32_t addr = __builtin_amdgcn_perm(w, colreg[t], 0x0c0c0400u + ((uint32_t)j << 8));
-              if constexpr (ABL == 1) bf[t][j] = addr;  // ablation: no lookups
-              else bf[t][j] = *(lds_cu32ptr)(addr);
+              bf[t][j] = *(lds_cu32ptr)(addr);
             }
           }
         }
@@ -902,7 +875,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
         // the finished group's accumulators must be dead before the next group's first MFMA: if the scheduler sinks the
         // finalize below it, the two groups need two accumulator tuples (32 VGPRs more)
         __builtin_amdgcn_sched_barrier(0);
-        if (ABL != 7 && gfirst && !MXC) {  // a group starts: its scale | zero and (not mx4) its activation sums
+        if (gfirst && !MXC) {  // a group starts: its scale | zero and (not mx4) its activation sums
           const int gg = GPS == 1 ? 0 : jc / CPG;
 #pragma unroll
           for (int t = 0; t < TILES; ++t) {
@@ -936,17 +909,15 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
           if constexpr (DOT) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) dacc[t] = dot2_pair<DT>(bf[t][j], xf[j], dacc[t]);
-          } else
-          if constexpr (ABL == 4) acc[t][0] += u2f(bf[t][0] ^ bf[t][1] ^ bf[t][2] ^ bf[t][3] ^ xf[0] ^ xf[1] ^ xf[2] ^ xf[3]);  // ablation: no MFMA
-          else if constexpr (T16) acc[t] = mfma16<DT>(xf, bf[t], (ABL != 7 && gfirst && !MXC) ? zero16 : acc[t]);
-          else if (ABL != 7 && !DIFF && gfirst && !MXC) acc[t] = mfma32<DT>(xf, bf[t], zero16);
+          } else if constexpr (T16) acc[t] = mfma16<DT>(xf, bf[t], (gfirst && !MXC) ? zero16 : acc[t]);
+          else if (!DIFF && gfirst && !MXC) acc[t] = mfma32<DT>(xf, bf[t], zero16);
           else acc[t] = mfma32<DT>(xf, bf[t], acc[t]);
         }
         if constexpr (STATIC_G && !DOT) {
 #pragma unroll
           for (int t = 0; t < TILES; ++t) asm volatile("" : "+v"(acc[t]));  // see finalize()
         }
-        if (ABL != 7 && !STATIC_G && glast && !MXC) pending = true;
+        if (!STATIC_G && glast && !MXC) pending = true;
         // keep the scheduler from hoisting the lookups of later steps above this point: it would trade the 4-waves-per-SIMD
         // register budget for instruction-level parallelism the other waves already provide
         __builtin_amdgcn_sched_barrier(0);
@@ -994,8 +965,6 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
 #pragma unroll
       for (int t = 0; t < TILES; ++t) yacc[t][0] += __shfl_xor(yacc[t][0], 32);
     }
-    if constexpr (ABL == 6) yacc[0][0] += acc[0][0] + acc[0][1] + acc[1][0];
-    if constexpr (ABL == 7) { yacc[0][0] = acc[0][0]; yacc[1][0] = acc[1][0]; }
 
     // ---- split-K tail: the partial sums of the 8 waves meet in LDS and are added in wave order ----
     if (p.red_alias) __syncthreads();  // the partial sums overwrite the table: every wave must be done with its lookups

@@ -35,9 +35,6 @@
 #ifndef P16_XSCHED
 #define P16_XSCHED 2
 #endif
-#ifndef P16_ABL
-#define P16_ABL 0  // developer ablations (0 in the product)
-#endif
 
 struct Pair16Params {
   const char* x;
@@ -192,10 +189,7 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
   // 4.74 vs 2.47 us per node -- rows per wave-load, order within the quad, XCD-private copies, rotations: all irrelevant).  Two more bit
   // exchanges in x_arrange then put quarter b into register b of lane (b' = dword, row), and the A operand's row index becomes a ROTATED
   // row number: lane i holds activation row 4 (i & 3) + (i >> 2), so accumulator register r of lane (n, q) is row 4 r + q (not 4 q + r).
-#ifndef P16_XQUAD
-#define P16_XQUAD 1
-#endif
-  constexpr bool XQ = XREG && !XTC && P16_XQUAD;
+  constexpr bool XQ = XREG && !XTC;
   uint32_t xoff = XQ ? (uint32_t)((min(lane >> 2, p.m - 1) * p.k + 8 * (lane & 3)) * 2) : (uint32_t)((min(n, p.m - 1) * p.k + 8 * q) * 2);
   auto x_request = [&](u32x4 (&xf)[NXF], int l0) {
     if constexpr (XREG) {
@@ -285,21 +279,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
   // the 128 KiB of activations a workgroup needs at 16 rows (four times its 32 KiB of weights) are ~1 us of that path.  Requested behind
   // the weights they could only be delivered after the weights' HBM latency; in front of them they arrive while the weights are in flight:
   // 4096^2 per graph node at m = 16 / 12 / 9: 8.09 -> 7.71 / 7.36 -> 6.98 / 6.79 -> 6.49 us (profiles/r05_ab_p16_prologue.txt).
-#ifndef P16_XFIRST
-#define P16_XFIRST 1
-#endif
-  if (P16_ABL != 1) {
-    if constexpr (XREG && P16_XFIRST) { x_request(xfA, 0); w_request(wregA, qregA, 0); }
-    else { w_request(wregA, qregA, 0); x_request(xfA, 0); }
-  }
-  else {
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int jc = 0; jc < CPS; ++jc) { wregA[t][j][jc] = (uint32_t)(tid * 977 + j * 13 + jc + t); qregA[t][j][jc] = 0x3c003c00u; }
-  }
+  if constexpr (XREG) { x_request(xfA, 0); w_request(wregA, qregA, 0); }
+  else { w_request(wregA, qregA, 0); x_request(xfA, 0); }
 
   // ---- stage the activations (byte order) and their group sums; build the table ----
   auto x_store = [&](int xi, bool on) {
@@ -351,7 +332,7 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
       if (on) chunk_rmsnorm<DT>(xd, rsqrtf(ss * (1.0f / (float)p.k) + p.norm_eps), gw);
       x_store(tid, on);
     } else
-    for (int it0 = 0; it0 < (P16_ABL == 3 ? 0 : xtotal); it0 += NT) {
+    for (int it0 = 0; it0 < xtotal; it0 += NT) {
       const int xi = it0 + tid;
       const bool on = xi < xtotal;
       if (it0 > 0 || !pre) {
@@ -385,31 +366,18 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
 #pragma unroll
     for (int j = 0; j < 4; ++j) lq[j] = (lp[t][4 + j] & hm) | (lp[t][j] & ~hm);
 #pragma unroll
-    for (int a = 0; a < (P16_ABL == 4 ? 1 : 8); ++a) {
+    for (int a = 0; a < 8; ++a) {
       const uint32_t e = __builtin_amdgcn_perm(hw, lq[a >> 1], hsel | ((a & 1) ? 0x0302u : 0x0100u));
       ((lds_u32ptr)base)[a * 64] = e;  // (one LDS pointer + constant offsets: immediate offset fields, no address arithmetic per store)
     }
   }
-#ifndef P16_ARRANGE_EARLY
-#define P16_ARRANGE_EARLY 0
-#endif
-  // (developer A/B) XREG, the whole slice in one block: the fragment transposes in front of the barrier instead of behind it -- no
-  // difference (7.71 vs 7.67 us): the stamps say the LAST wave's activations land ~3.8 us after the requests whatever the order. Every
-  // CU of an XCD pulls the same 128 KiB of x out of that XCD's L2 -- 4 MiB per XCD and launch at ~2 TB/s: the launch is bound by that
-  // broadcast, not by the weights (profiles/r05_p16_trace_xfirst.txt)
-  constexpr bool ARRANGE_EARLY = XREG && CH == 4 && P16_XFIRST && P16_ARRANGE_EARLY && P16_ABL != 6;
-  if constexpr (ARRANGE_EARLY) x_arrange(xfA);
+  // XREG: the fragment transposes (x_arrange) stay behind the barrier: in front of it no difference (7.71 vs 7.67 us) -- the stamps say the
+  // LAST wave's activations land ~3.8 us after the requests whatever the order.  Every CU of an XCD pulls the same 128 KiB of x out of that
+  // XCD's L2 -- 4 MiB per XCD and launch at ~2 TB/s: the launch is bound by that broadcast, not by the weights (profiles/r05_p16_trace_xfirst.txt)
   P16_STAMP(2);
-#ifndef P16_ASM_BARRIER
-#define P16_ASM_BARRIER 0
-#endif
-  if constexpr (XREG && P16_ASM_BARRIER) {
-    // (developer A/B: `__syncthreads()` waits vmcnt(0) -- for every weight and activation request of the wave -- where only the table's LDS
-    //  stores have to be done; spelled out without that wait the launch measured 0.35 us SLOWER in either request order: not used)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
-  } else {
-    __syncthreads();
-  }
+  // (`__syncthreads()` waits vmcnt(0) -- for every weight and activation request of the wave -- where only the table's LDS stores have to be
+  //  done; a barrier spelled out without that wait measured 0.35 us SLOWER in either request order)
+  __syncthreads();
   P16_STAMP(3);
 
   // ---- main loop ----
@@ -439,14 +407,6 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
   const uint32_t one2 = DT::pack2(1.f, 1.f);
   const u32x4 ones = {one2, one2, one2, one2};
 
-  if (P16_ABL == 2) {  // loads consumed, nothing computed
-#pragma unroll
-    for (int t = 0; t < TPW; ++t)
-#pragma unroll
-      for (int j = 0; j < CH; ++j)
-#pragma unroll
-        for (int jc = 0; jc < CPS; ++jc) yacc[t][0] += u2f(wregA[t][j][jc] ^ qregA[t][j][jc]);
-  }
   int chunk_ph = 0;  // first chunk of the current phase: LDS holds chunks / groups relative to it
   // one 32-k chunk of every tile: 4 lookups + one MFMA per tile, the X fragment read once
   auto step = [&](const uint32_t (&wreg)[TPW][CH][CPS], const uint32_t (&qreg)[TPW][CH][CPS], const u32x4 (&xfr)[NXF], int j, int jc, int chunk, bool gfirst, bool glast) {
@@ -488,7 +448,7 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
     }
 #pragma unroll
     for (int t = 0; t < TPW; ++t) acc[t] = mfma16<DT>(xf, bf[t], gfirst ? zero4 : acc[t]);
-    if constexpr (XREG && !QMX && P16_ABL != 5) {  // (ablation 5: no activation sums)
+    if constexpr (XREG && !QMX) {
       xsacc = mfma16<DT>(xf, ones, gfirst ? zero4 : xsacc);
       if (glast) xsv = f32x4{xsacc[0], xsacc[1], xsacc[2], xsacc[3]};
     }
@@ -541,9 +501,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
       __syncthreads();
     }
     chunk_ph = ph * p.ksuper_p * CPS;
-    if (P16_ABL == 2) continue;
     if (nl <= CH || (XREG && CH == 4)) {  // (wave-uniform) the whole slice was requested up front (XREG, CH = 4: always -- the host's choice)
-      if (P16_ABL != 6 && !ARRANGE_EARLY) x_arrange(xfA);  // (ablation 6: fragments used as loaded)
+      x_arrange(xfA);
 #if GEMV_TRACE
       asm volatile("" ::"v"(xfA[0]), "v"(xfA[NXF - 1]));
 #endif
@@ -554,15 +513,12 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
     if constexpr (PIPE) {
       // long slices: two blocks per turn, the next block always requested before the current one is consumed
       for (int l0 = 0; l0 < nl; l0 += 2 * CH) {
-#ifndef P16_XFIRST_PIPE
-#define P16_XFIRST_PIPE 0
-#endif
-        if constexpr (XREG && P16_XFIRST_PIPE) { x_request(xfB, l0 + CH); w_request(wregB, qregB, l0 + CH); }
-        else { w_request(wregB, qregB, l0 + CH); x_request(xfB, l0 + CH); }
+        // (weights first here: the activations first, as in the prologue, measured no difference -- 17.0 vs 17.0 us, 21.8 vs 21.8;
+        //  profiles/r05_ab_p16_xfirst_pipe.txt)
+        w_request(wregB, qregB, l0 + CH); x_request(xfB, l0 + CH);
         x_arrange(xfA);
         consume_block(wregA, qregA, xfA, l0);
-        if constexpr (XREG && P16_XFIRST_PIPE) { x_request(xfA, l0 + 2 * CH); w_request(wregA, qregA, l0 + 2 * CH); }
-        else { w_request(wregA, qregA, l0 + 2 * CH); x_request(xfA, l0 + 2 * CH); }
+        w_request(wregA, qregA, l0 + 2 * CH); x_request(xfA, l0 + 2 * CH);
         x_arrange(xfB);
         if (l0 + CH < nl) consume_block(wregB, qregB, xfB, l0 + CH);
       }

@@ -34,9 +34,6 @@
 // and a lookup address is just (nibble << 8 | lane << 2); otherwise address bits 12..15 (the table
 // select) are OR-ed into the nibble bytes before the v_perm_b32.
 #pragma once
-#ifndef TG_STREAM_UNCOND
-#define TG_STREAM_UNCOND 0
-#endif
 
 
 struct StreamParams {
@@ -71,7 +68,7 @@ struct StreamParams {
 //       is read under an EXEC mask of the lanes whose MFMA column is a real activation row (m = 1: 4 of 64 lanes; the others keep
 //       the zeros their fragment registers were initialised with): a 16-byte LDS read of all 64 lanes costs eight LDS cycles,
 //       a third of this kernel's LDS time at m = 1 (SQ_LDS_IDX_ACTIVE: 2.8 cycles per wave and weight, of which 2 are the lookups).
-template <typename DT, bool LAYOUT_A, int WPL, bool QMX, int WAVES, int MINW, int XL, bool PRIVX, int ABL = 0, bool XRES = false, int LK = 0>
+template <typename DT, bool LAYOUT_A, int WPL, bool QMX, int WAVES, int MINW, int XL, bool PRIVX, bool XRES = false, int LK = 0>
 __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_stream_kernel(const StreamParams p) {
   static_assert(LK == 0 || !LAYOUT_A, "the hand-written lookup block exists for Bint4 weights");
   constexpr int CHUNK = LAYOUT_A ? 16 : 32;  // k per chunk (one packed word per q)
@@ -235,10 +232,9 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_stream_kernel(const 
       const char* src = wb + (wrow + (uint32_t)ks * wks);
 #pragma unroll
       for (int v = 0; v < WPL; ++v) {
-        if constexpr (ABL == 3) L[pc * WPL + v] = u32x4{(uint32_t)ks, 1u, 2u, (uint32_t)v};  // ablation: no weight stream
         // Aint4: lanes i and i + 8 read the same words (rows m0 / m0 + 8 share a word), the second read must hit the
         // cache -- a non-temporal load would go to HBM twice (measured: 2.65 -> 2.11 us per 4096^2 layer)
-        else if constexpr (LAYOUT_A) L[pc * WPL + v] = *reinterpret_cast<const u32x4*>(src + 16 * v);
+        if constexpr (LAYOUT_A) L[pc * WPL + v] = *reinterpret_cast<const u32x4*>(src + 16 * v);
         else L[pc * WPL + v] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src + 16 * v));
       }
     }
@@ -291,7 +287,6 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_stream_kernel(const 
     auto look2 = [&](uint32_t src, int byte_lo, int byte_hi) -> uint32_t {
       const uint32_t a0 = __builtin_amdgcn_perm(src, lane4, 0x0c0c0400u + ((uint32_t)byte_lo << 8));
       const uint32_t a1 = __builtin_amdgcn_perm(src, lane4, 0x0c0c0400u + ((uint32_t)byte_hi << 8));
-      if constexpr (ABL == 1) return a0 ^ a1;  // ablation: no LDS lookups
       const uint32_t lo = *(lds_cu16ptr)(a0 + 2u);
       const uint32_t hi = *(lds_cu32ptr)(a1);
       return lo | hi;
@@ -300,10 +295,6 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_stream_kernel(const 
     // chunk c of the unit whose words are in L; X fragments come from the staged slab `xbuf`
     auto do_chunk = [&](const u32x4 (&L)[4], int c, uint32_t xbuf) {
       const uint32_t xa = xbuf + (uint32_t)(c * CHUNK * 2);
-      if constexpr (ABL == 4) {  // ablation: stream only
-        acc[0] += u2f(L[c][0] ^ L[c][1] ^ L[c][2] ^ L[c][3] ^ (*(lds_cu32ptr)(xa)));
-        return;
-      }
       if constexpr (!LAYOUT_A) {
         uint32_t wa[4], wb4[4];
 #pragma unroll
@@ -392,18 +383,11 @@ __global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_stream_kernel(const 
     // All control flow below is workgroup-uniform (NU, splitk, group size), barriers included.
     auto do_unit = [&](int u, const u32x4 (&Lc)[4], uint32_t qc, u32x4 (&Ln)[4], uint32_t& qn) {
       const int U = u_first + u;
-#if TG_STREAM_UNCOND
-      // (the next unit's words and scale are requested unconditionally -- load_unit / load_q clamp their addresses, the unit past the end is
-      //  never consumed: with the requests under the branch hipcc cannot count them and waits vmcnt(0) in front of build_table below,
-      //  i.e. for the requests it has just issued)
-      load_unit(U + 1, Ln);
-      qn = load_q(U + 1);
-#endif
+      // (the next unit's words and scale stay under the branch: requested unconditionally, so that hipcc can count them instead of waiting
+      //  vmcnt(0) in front of build_table below, measured slower -- 57.5 / 51.5 % -> 53.4 / 50.8 % at m = 1 / 8)
       if (u + 1 < NU) {
-#if !TG_STREAM_UNCOND
         load_unit(U + 1, Ln);
         qn = load_q(U + 1);
-#endif
         if constexpr (!XRES) {
           stage_store((u + 1) & 1, XR);           // slab u+1 (requested one unit ago) -> LDS
           if (u + 2 < NU) stage_load(u + 2, XR);  // request slab u+2

@@ -41,9 +41,6 @@
 //   mx4        template flag QMX: the table entries are fp4[code] * 2^(e - 127) (exact in bf16; e = 255: NaN), the exponents one byte per row
 //              and 32-k group.  A flavour of its own because as a run-time branch it cost the other formats registers (128 x 128 tile: spill).
 #pragma once
-#ifndef TILE_ABL
-#define TILE_ABL 0  // developer ablations (timing only, wrong results), bit mask: 1 no dequantisation, 2 no MFMA stage, 4 no LDS-DMA, 8 no table builds, 16 no lookups, 32 no w-tile writes, 64 no word loads
-#endif
 
 struct TileParams {
   const char* x;       // [m][k] 16-bit, row-major
@@ -293,8 +290,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
       for (int u = 0; u < WPT; ++u)
 #pragma unroll
         for (int pl = 0; pl < KS; ++pl) {
-          if constexpr (TILE_ABL & 64) dst[u * KS + pl] = (uint32_t)(c * 0x9e3779b9u) + (uint32_t)(uintptr_t)wsrc[u];
-          else dst[u * KS + pl] = __builtin_nontemporal_load(wsrc[u] + (int64_t)(c * KS + pl) * 64);
+          dst[u * KS + pl] = __builtin_nontemporal_load(wsrc[u] + (int64_t)(c * KS + pl) * 64);
         }
     };
     auto dequant = [&](int step, const uint32_t (&wd)[NW]) {   // the words of step `step` -> w stage step & 1
@@ -307,8 +303,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
 #pragma unroll
         for (int h = 0; h < 4; ++h) {
           const uint32_t c0 = (wd[u] >> (4 * h)) & 15u, c1 = (wd[u] >> (16 + 4 * h)) & 15u;
-          if constexpr (TILE_ABL & 16) v[u][h] = c0 | (c1 << 16) | (uint32_t)(uintptr_t)tab;
-          else v[u][h] = (uint32_t) * reinterpret_cast<const uint16_t*>(tab + 2 * c0) | ((uint32_t) * reinterpret_cast<const uint16_t*>(tab + 2 * c1) << 16);
+          v[u][h] = (uint32_t) * reinterpret_cast<const uint16_t*>(tab + 2 * c0) | ((uint32_t) * reinterpret_cast<const uint16_t*>(tab + 2 * c1) << 16);
         }
       }
 #pragma unroll
@@ -317,8 +312,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
         for (int pl = 0; pl < KS; ++pl)
 #pragma unroll
           for (int h = 0; h < 4; ++h) {
-            if constexpr (TILE_ABL & 32) { if (v[u * KS + pl][h] == 0x12345u) *reinterpret_cast<uint32_t*>(bst) = 1u; }
-            else *reinterpret_cast<uint32_t*>(bst + pl * L::B_PLANE + dst0[u][h]) = v[u * KS + pl][h];
+            *reinterpret_cast<uint32_t*>(bst + pl * L::B_PLANE + dst0[u][h]) = v[u * KS + pl][h];
           }
     };
 #pragma unroll
@@ -332,7 +326,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
       for (int j = 0; j < PWD; ++j) {
         if (s + j >= ksteps) break;
         // step t = s + j: the words of step t + 1 are in slot (j + 1) % PWD; refilled with step t + 1 + PWD
-        if (!(TILE_ABL & 1) && s + j + 1 < ksteps) dequant(s + j + 1, ring[(j + 1) % PWD]);
+        if (s + j + 1 < ksteps) dequant(s + j + 1, ring[(j + 1) % PWD]);
         load_words(s + j + 1 + PWD, ring[(j + 1) % PWD]);
         tile_barrier();
       }
@@ -369,10 +363,8 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
     tile_barrier();
     tile_barrier();
     for (int s = 0; s < ksteps; ++s) {
-      if (!(TILE_ABL & 4)) {
-        dma(s + DX);
-        tile_wait_vm<(DX - 1) * XPW * KS>();
-      }
+      dma(s + DX);
+      tile_wait_vm<(DX - 1) * XPW * KS>();
       tile_barrier();
     }
     tile_wait_vm<0>();
@@ -515,9 +507,9 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
     for (int j = 0; j < PW; ++j) {
       if (s + j >= ksteps) break;
       // step t = s + j: the MFMAs of step t; the tables of step t + 2 (slot (j + 2) % PW), refilled with step t + 2 + PW
-      if (!(TILE_ABL & 2)) mma(s + j);
+      mma(s + j);
       if constexpr (W8 == 0) {
-        if (!(TILE_ABL & 8) && s + j + 2 < ksteps && new_group(s + j + 2)) build_tables(s + j + 2, szr[(j + 2) % PW]);
+        if (s + j + 2 < ksteps && new_group(s + j + 2)) build_tables(s + j + 2, szr[(j + 2) % PW]);
         load_sz(s + j + 2 + PW, szr[(j + 2) % PW]);
       }
       tile_barrier();

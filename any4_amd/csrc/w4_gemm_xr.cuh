@@ -30,9 +30,6 @@
 //                wave, refilled with the next item's positions) keeps streaming through it.
 //   mx4        = template flag QMX below: no table at all.
 #pragma once
-#ifndef XR_ABL
-#define XR_ABL 0  // developer ablations (dev/README.md): 1 no table lookups, 3 no weight loads, 5 no table build, 6 no split-K tail, 7 no output stores, 8 no third barrier (a race: timing only); 0 in the product
-#endif
 
 // f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N - 1>{}): the stage loop of the kernel as a fold expression
 // (`#pragma unroll` gives up on the 64 stages of k = 8192 -- and every register array becomes scratch)
@@ -74,26 +71,15 @@ struct XrParams {
 //       scale 2^(e - 127) inside the conversion: no table, no lookups, no per-group accumulator updates; the word pair of a lane is
 //       swapped BEFORE the conversion (one v_permlane16_swap per stage); the e8m0 exponents of a lane's four rows over its k-slice
 //       are one 16-byte load per row and item, requested one item ahead.  CPG is 1 (a group is one 32-k chunk).
-// WV  = waves per workgroup = k-slices (8: two waves per SIMD with 256 registers each; 16: four per SIMD with 128 -- a slice is half
-//       as long, so the activation registers are 32 instead of 64 and the ring two super-tiles deep: the same bytes in flight per CU,
-//       twice the waves to hide LDS and MFMA latency behind)
 // PK  = at most 8 activation rows: the A operand's rows 8 ... 15 would be zeros, so a register set holds TWO chunks -- lanes of
 //       rows 0 ... 7 the piece of chunk 2 c, lanes of rows 8 ... 15 the piece of chunk 2 c + 1 (of row i - 8).  The even chunk's MFMAs
 //       take the registers as they are, the odd chunk's a copy rotated by 8 lanes within every 16-lane row (four v_mov_b32_dpp
 //       row_ror:8 per chunk, shared by the stage's two tile pairs); what the other eight rows of the operand then hold only reaches
 //       accumulator rows 8 ... 15, which are never stored.  Half the activation registers: k = 8192 in the 64 registers k = 4096
 //       takes unpacked, so its ring is four super-tiles deep like there (unpacked, k = 8192 leaves room for two: 66 % at m = 8).
-// WV = 4 (with PK: at most 8 rows): TWO workgroups of four k-slices per CU instead of one of eight.  The same registers per wave
-//       (a slice is twice as long, packed rows halve it again) and the same two waves per SIMD -- but the split-K tail and the
-//       table build of one workgroup, which stall the whole CU when it is alone on it (same-box ablation: the tail costs 8-10
-//       points), run under the other workgroup's main loop.  Each workgroup has ONE table (64 KiB, rebuilt between two barriers
-//       after the item's sums are handed over) and its own 8 KiB hand-over region: 2 x 74 KiB of LDS.
-template <typename DT, int I, int NCH, int CPG, int R, bool QMX = false, int WV = 8, bool PK = false>
-__global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(const XrParams p) {
-  constexpr int WAVES = WV;
-  constexpr bool ONE_TABLE = WV == 4;
-  static_assert(WV == 8 || (WV == 16 && !QMX) || (WV == 4 && PK), "8 or 16 k-slices (mx4: 8); 4 with packed rows");
-  static_assert(!PK || (!QMX && WV <= 8 && NCH % 2 == 0), "packed rows: the lookup kernel, chunk pairs");
+template <typename DT, int I, int NCH, int CPG, int R, bool QMX = false, bool PK = false>
+__global__ void __launch_bounds__(512, 2) w4_gemm_xr_kernel(const XrParams p) {
+  static_assert(!PK || (!QMX && NCH % 2 == 0), "packed rows: the lookup kernel, chunk pairs");
   constexpr int NXR = PK ? NCH / 2 : NCH;          // activation register sets of a wave
   // ZM: the zero-point term sum_g zero[g, row] X[g][a] (X = the group's sum of activations) on the MATRIX CORE, once per item and tile,
   // instead of one FMA per accumulator register and group (64 of the ~680 vector instructions of a wave and item, plus the LDS reads
@@ -102,10 +88,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
   // (R = 8 / NG repeats of the NG groups per k-quad) of X[gidx][i], B operand = zero[gidx][row n] in every k-quad (lane-uniform
   // in kb: no selects), C = the item's sums: y += A B directly.
   constexpr int NG = NCH / CPG;                    // quantisation groups of a wave's slice
-#ifndef TG_XR_ZM
-#define TG_XR_ZM 1
-#endif
-  constexpr bool ZM = TG_XR_ZM && !QMX && WV == 8 && NG <= 8 && (PK ? (CPG > 1 && NCH <= 32) : NCH <= 24);  // (32 unpacked chunks: its extra registers spill)
+  constexpr bool ZM = !QMX && NG <= 8 && (PK ? (CPG > 1 && NCH <= 32) : NCH <= 24);  // (32 unpacked chunks: its extra registers spill)
   constexpr int ZR = NG <= 8 ? 8 / NG : 1;         // repeats of the group pattern inside a k-quad's 8 slots
   constexpr int CPS = I / 2;                       // 32-k chunks per super-tile
   constexpr int NST = NCH / CPS;                   // super-tiles of a wave's slice
@@ -168,10 +151,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       const char* src = rw.wb + uni(sv * (uint32_t)(64 * I) + (uint32_t)u * pair_stride) + pin(rw.wbase);
-      if constexpr (XR_ABL == 3) {  // ablation: no weight loads
-#pragma unroll
-        for (int j = 0; j < NWL; ++j) sl.w[u][j] = (uint32_t)(l * 0x01030507 + j * 0x11 + u) + rw.wbase;
-      } else if constexpr (NWL == 2) {
+      if constexpr (NWL == 2) {
         const u32x2 v = __builtin_nontemporal_load(reinterpret_cast<const u32x2*>(src));
         sl.w[u][0] = v[0]; sl.w[u][1] = v[1];
       } else {
@@ -196,7 +176,6 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
 
   // ---- LUT rows of this thread's table column (= row of the item), requested one item ahead ----
   u32x4 lpa, lpb;  // (two register vectors, every element index a constant: a private ARRAY here was promoted to static LDS)
-  uint32_t lhw2 = 0u;  // WV = 4: the LUT values 4 wave + 2, 4 wave + 3 (lhw: 4 wave, 4 wave + 1)
   uint32_t lhw;    // the LUT values 2 wave, 2 wave + 1 of the column: its own load (a select chain over the eight dwords by the wave
                    // index became a dynamically indexed stack object: scratch loads behind vmcnt(0) in the main loop)
   auto lpe = [&](int i) -> uint32_t { return i < 4 ? lpa[i & 3] : lpb[i & 3]; };
@@ -207,12 +186,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
     const char* lsrc = p.lut + (int64_t)e.b * p.stride_lut + (p.qtype == TG_Q_ANY4_ROWWISE ? (int64_t)lrow * 32 : 0);
     lpa = reinterpret_cast<const u32x4*>(lsrc)[0];
     lpb = reinterpret_cast<const u32x4*>(lsrc)[1];
-    if constexpr (WAVES == 4) {
-      lhw = reinterpret_cast<const uint32_t*>(lsrc)[2 * wave];
-      lhw2 = reinterpret_cast<const uint32_t*>(lsrc)[2 * wave + 1];
-    } else {
-      lhw = reinterpret_cast<const uint32_t*>(lsrc)[WAVES == 8 ? wave : wave >> 1];
-    }
+    lhw = reinterpret_cast<const uint32_t*>(lsrc)[wave];
   };
   // mx4: the 16 exponent bytes of row 16 t + (lane & 15) over this wave's slice, tile t = 0 ... 3, current and next item
   u32x4 ecur[4], enext[4];
@@ -238,32 +212,10 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
       if (e < 8) lpa[(e >> 1) & 3] = v;
       else lpb[(e >> 1) & 3] = v;
     }
-    if constexpr (WAVES == 4) {
-      lhw = DT::pack2((float)(4 * wave - 8), (float)(4 * wave - 7));
-      lhw2 = DT::pack2((float)(4 * wave - 6), (float)(4 * wave - 5));
-    } else {
-      lhw = DT::pack2((float)(2 * (WAVES == 8 ? wave : wave >> 1) - 8), (float)(2 * (WAVES == 8 ? wave : wave >> 1) - 7));
-    }
+    lhw = DT::pack2((float)(2 * wave - 8), (float)(2 * wave - 7));
   }
   // table build: thread = (column, high nibbles 2 wave and 2 wave + 1); step a = low nibble a: entries (lut[a], lut[2 wave (+1)])
   auto build_step = [&](uint32_t buf, int a, uint32_t hw) {
-    if constexpr (WAVES == 4) {  // thread = (column, high nibbles 4 wave ... 4 wave + 3): four entries per step
-      const uint32_t lo = lpe(a >> 1);
-      const uint32_t ls = (a & 1) ? 0x0302u : 0x0100u;
-      const lds_u32ptr tb = (lds_u32ptr)((uint32_t)(wave * 4 * 16 * 256 + tcol * 4));
-      tb[a * 64] = __builtin_amdgcn_perm(hw, lo, 0x05040000u | ls);
-      tb[(16 + a) * 64] = __builtin_amdgcn_perm(hw, lo, 0x07060000u | ls);
-      tb[(32 + a) * 64] = __builtin_amdgcn_perm(lhw2, lo, 0x05040000u | ls);
-      tb[(48 + a) * 64] = __builtin_amdgcn_perm(lhw2, lo, 0x07060000u | ls);
-      return;
-    }
-    if constexpr (WAVES == 16) {  // thread = (column, high nibble `wave`): one entry per step
-      const uint32_t hsel = (wave & 1) ? 0x07060000u : 0x05040000u;
-      const uint32_t e = __builtin_amdgcn_perm(hw, lpe(a >> 1), hsel | ((a & 1) ? 0x0302u : 0x0100u));
-      const lds_u32ptr tb = (lds_u32ptr)(buf * TABLE + (uint32_t)(wave * 16 * 256 + tcol * 4));
-      tb[a * 64] = e;
-      return;
-    }
     const uint32_t e0 = __builtin_amdgcn_perm(hw, lpe(a >> 1), (a & 1) ? 0x05040302u : 0x05040100u);
     const uint32_t e1 = __builtin_amdgcn_perm(hw, lpe(a >> 1), (a & 1) ? 0x07060302u : 0x07060100u);
     const lds_u32ptr tb = (lds_u32ptr)(buf * TABLE + (uint32_t)(wave * 2 * 16 * 256 + tcol * 4));
@@ -288,13 +240,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
   // row -- lanes (row i, k-quad kq) of a 4-byte read then hit 8 x 4 distinct banks, rows 8 ... 15 of the OTHER round read their
   // partner's address (a broadcast) --, and picks its dwords up from there: rows 0 ... 7, then rows 8 ... 15.  No barrier: the
   // region is the wave's own and LDS operations of a wave execute in order.
-#ifndef TG_XR_XLDS
-#define TG_XR_XLDS 1
-#endif
-#ifndef TG_XR_XT
-#define TG_XR_XT 1   // the later problems' activations by 16-byte loads + a lane transpose (0: four 4-byte loads per chunk; developer A/B)
-#endif
-  constexpr bool XLDS = TG_XR_XLDS && !PK && !QMX && WV == 8 && NCH == 16;  // (mx4: its eight-deep ring plus the 64 staging registers spill)
+  constexpr bool XLDS = !PK && !QMX && NCH == 16;  // (mx4: its eight-deep ring plus the 64 staging registers spill)
   u32x4 xg[XLDS ? 16 : 1];
   auto x_prepare = [&](int b, auto STAGED) {
     constexpr bool staged = decltype(STAGED)::value;
@@ -337,10 +283,10 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
       if constexpr (staged) {
 #pragma unroll
         for (int e = 0; e < 4; ++e) d[e] = on ? xr[cx][e] : 0u;
-      } else if (!TG_XR_XT || p.x_tc) {
+      } else if (p.x_tc) {  // fragment-order x: four 4-byte loads per chunk
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-          const int64_t idx = p.x_tc ? tc_a_index(xi, k0 + 8 * e, p.k >> 4) : (int64_t)xi * p.k + k0 + 8 * e;
+          const int64_t idx = tc_a_index(xi, k0 + 8 * e, p.k >> 4);
           const uint32_t v = *reinterpret_cast<const uint32_t*>(xb + idx * 2);
           d[e] = on ? v : 0u;
         }
@@ -480,9 +426,6 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
           yacc[t][r] = __builtin_fmaf(gz, xsv[r], __builtin_fmaf(gs, acc[t][r], yacc[t][r]));
-          // (one table: no LDS store is left in the main loop, and without one the compiler sinks every group's update -- its LDS
-          //  read of the sums first -- behind the loop and keeps all the groups' accumulators alive until then: 500 bytes of scratch)
-          if constexpr (ONE_TABLE) asm volatile("" : "+v"(yacc[t][r]));
         }
       }
     };
@@ -502,11 +445,10 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
       for (int j = 0; j < 4; ++j) {
         const uint32_t av = __builtin_amdgcn_perm(wv, colreg[u], 0x0c010400u + ((uint32_t)j << 8));
         const uint32_t aw = __builtin_amdgcn_perm(ww, colreg[u], 0x0c010400u + ((uint32_t)j << 8));
-        if constexpr (XR_ABL == 1) { pv[st & 1][j] = av; pw[st & 1][j] = aw; }  // ablation: no lookups
-        else { pv[st & 1][j] = *(lds_cu32ptr)(av); pw[st & 1][j] = *(lds_cu32ptr)(aw); }
+        pv[st & 1][j] = *(lds_cu32ptr)(av);
+        pw[st & 1][j] = *(lds_cu32ptr)(aw);
       }
     };
-    constexpr bool AHEAD = WAVES != 16;  // (sixteen waves: four per SIMD hide the lookup latency; one stage's registers less)
     u32x4 xodd;                         // PK: the odd chunk's A operand (the register set rotated by 8 lanes within every 16-lane row)
     auto x_of = [&](int ci, int u) -> u32x4 {
       if constexpr (!PK) return xr[ci];
@@ -519,7 +461,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
         return xodd;
       }
     };
-    if constexpr (!QMX && AHEAD) look(0);
+    if constexpr (!QMX) look(0);
     xr_static_for<NSTG>([&](auto ST) {
       constexpr int st = decltype(ST)::value;
       constexpr int ci = st >> 1, u = st & 1, l = ci / CPS, c = ci % CPS;
@@ -540,11 +482,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
       }
       const bool gfirst = ci % CPG == 0;
       const int gi = ci / CPG;
-      if constexpr (AHEAD) {
-        if (st + 1 < NSTG) look(st + 1);
-      } else {
-        look(st);
-      }
+      if (st + 1 < NSTG) look(st + 1);
       __builtin_amdgcn_sched_barrier(0);
       if (gfirst) {
         if (ci > 0) finalize_pair(u, gi - 1);  // the previous group of this pair's tiles, behind the next stage's lookups
@@ -556,11 +494,6 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
         u32x4 b0, b1;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          if constexpr (XR_ABL == 9) {  // ablation: no lane swaps (wrong operands: timing only)
-            b0[j] = pv[st & 1][j];
-            b1[j] = pw[st & 1][j];
-            continue;
-          }
           const auto sw = __builtin_amdgcn_permlane16_swap(pv[st & 1][j], pw[st & 1][j], false, false);
           b0[j] = sw[0];
           b1[j] = sw[1];
@@ -571,7 +504,7 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
       }
       if (u == 1) {
         // the next item's table, one step per chunk of the slice's second half
-        if (!ONE_TABLE && ci >= NCH / 2 && XR_ABL != 5) {
+        if (ci >= NCH / 2) {
           if (ci == NCH / 2) hw = lhw;
           // the 16 build steps spread evenly over the NCH / 2 chunks of the half (k = 4096: two per chunk, 8192: one, 14336: 16 over 28)
           constexpr int J = ci - NCH / 2, S0 = (J * 16) / (NCH / 2), S1 = ((J + 1) * 16) / (NCH / 2);
@@ -627,192 +560,88 @@ __global__ void __launch_bounds__(WV * 64, WV == 16 ? 1 : 2) w4_gemm_xr_kernel(c
     const bool new_problem = has_next && inext.b != cur.b;
 
     // ---- split-K tail: the partial sums of the 8 waves meet in LDS (over the finished table) and are added in wave order ----
-    if constexpr (XR_ABL == 6) {  // ablation: no split-K tail (one barrier per item, nothing stored)
-      __syncthreads();
-      if (yacc[0][0] == 123.f) *reinterpret_cast<float*>(p.y) = yacc[1][1] + yacc[2][2] + yacc[3][3];
-      if (new_problem) x_prepare(inext.b, std::false_type{});
-      rcur = rnext; cur = inext; buf ^= 1u; colreg[0] ^= 0x100u; colreg[1] ^= 0x100u;
-      continue;
-    }
     // The tail's per-thread indices are re-derived from a lane id read HERE (v_mbcnt, opaque): derived from the kernel's `tid` they
     // are loop-invariant, get hoisted in front of the item loop, spilled around the 256-register main loop and reloaded from
     // scratch behind s_waitcnt vmcnt(0) -- which drains the weight ring once per item.
     uint32_t lane_t;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane_t));
-    const int tid_t = wave * 64 + (int)lane_t;
-    if constexpr (ONE_TABLE) {
-      // ---- WV = 4 (at most 8 rows): the sums of rows 0 ... 7 sit in lanes 0 ... 31 (k-quads 0, 1); handed over through a region of
-      // their own, [wave][r][t][32 lanes rotated by 16 t] f32 = 8 KiB, so that the table can be rebuilt while they are summed ----
-      const uint32_t lds_dump = lds_xs + (uint32_t)p.ngroups * 64u;
-      if (lane_t < 32u) {
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-          const uint32_t pl = lds_dump + (uint32_t)(wave * 2048) + ((lane_t + 16u * (uint32_t)t) & 31u) * 4u;
-#pragma unroll
-          for (int r = 0; r < 4; ++r) *(lds_fptr)(pl + (uint32_t)((r * 4 + t) * 128)) = yacc[t][r];
-        }
-      }
-      __syncthreads();  // every wave is done with the table and has handed over its sums
-      {
-        // wave W: activation rows W and W + 4 (register r = W of k-quads 0 and 1), lane = weight row of the item: four 4-byte reads
-        // per output in k-slice order, one 128-byte line of y per wave and row
-        const int t2 = (int)(lane_t >> 4), n2 = (int)(lane_t & 15u);
-        const uint32_t pa = lds_dump + (uint32_t)(((wave * 4 + t2) * 32 + ((n2 + 16 * t2) & 31)) * 4);
-        const uint32_t pb = lds_dump + (uint32_t)(((wave * 4 + t2) * 32 + ((16 + n2 + 16 * t2) & 31)) * 4);
-        f32x2 a0, a1, b0, b1;
-        asm volatile(
-            "ds_read2st64_b32 %0, %4 offset1:8\n\t"
-            "ds_read2st64_b32 %1, %4 offset0:16 offset1:24\n\t"
-            "ds_read2st64_b32 %2, %5 offset1:8\n\t"
-            "ds_read2st64_b32 %3, %5 offset0:16 offset1:24\n\t"
-            "s_waitcnt lgkmcnt(0)"
-            : "=&v"(a0), "=&v"(a1), "=&v"(b0), "=&v"(b1)
-            : "v"(pa), "v"(pb)
-            : "memory");
-        const float sums[2] = {((a0[0] + a0[1]) + a1[0]) + a1[1], ((b0[0] + b0[1]) + b1[0]) + b1[1]};
-        char* yb = p.y + (int64_t)cur.b * p.stride_y;
-        const int row = row0 + (int)lane_t;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-          const int a2 = wave + 4 * h;
-          if (a2 < p.m && (XR_ABL != 7 || sums[h] == 123.456f)) {
-            uint16_t oa = DT::from_f32(sums[h]);
-            if (p.bias)
-              oa = DT::from_f32(DT::lo_f32(oa) + DT::lo_f32(*reinterpret_cast<const uint16_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a2 * p.bias_row_stride + row) * 2)));
-            *reinterpret_cast<uint16_t*>(yb + (p.y_tc ? tc_a_index(a2, row, p.y_tiles) : (int64_t)a2 * p.wrows + row) * 2) = oa;
-          }
-        }
-      }
-      // the next item's table (its LUT rows were requested when this item started) and, at a problem boundary, its activations
-      if (has_next && XR_ABL != 5) {
-        const uint32_t hwn = lhw;
-#pragma unroll
-        for (int a = 0; a < 16; ++a) build_step(0u, a, hwn);
-      }
-      if (new_problem) x_prepare(inext.b, std::false_type{});
-      __syncthreads();  // table, sums and hand-over region are free / ready for the next item
-      rcur = rnext;
-      cur = inext;
-      continue;
-    }
     if constexpr (!QMX) __syncthreads();  // every wave is done with this item's table; the next item's table is complete (mx4: no table)
     const uint32_t lds_red = QMX ? 0u : buf * TABLE;
-    if constexpr (WAVES == 8) {
-      // dump layout [wave][r][t][64 lanes, rotated by 16 t]: the tail below reads whole 64-row lines of one activation row with
-      // 32 / 64 lanes at a time, and the rotation puts the four tiles' 64-byte runs on different banks
+    // dump layout [wave][r][t][64 lanes, rotated by 16 t]: the tail below reads whole 64-row lines of one activation row with
+    // 32 / 64 lanes at a time, and the rotation puts the four tiles' 64-byte runs on different banks
 #pragma unroll
-      for (int t = 0; t < 4; ++t) {
-        const uint32_t pl = lds_red + (uint32_t)(wave * 4096) + ((lane_t + 16u * (uint32_t)t) & 63u) * 4u;
+    for (int t = 0; t < 4; ++t) {
+      const uint32_t pl = lds_red + (uint32_t)(wave * 4096) + ((lane_t + 16u * (uint32_t)t) & 63u) * 4u;
 #pragma unroll
-        for (int r = 0; r < 4; ++r) *(lds_fptr)(pl + (uint32_t)((r * 4 + t) * 256)) = yacc[t][r];
-      }
-    } else {
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) *(lds_fptr)(lds_red + (uint32_t)((((wave * 4 + t) * 4 + r) * 64 + (int)lane_t) * 4)) = yacc[t][r];
+      for (int r = 0; r < 4; ++r) *(lds_fptr)(pl + (uint32_t)((r * 4 + t) * 256)) = yacc[t][r];
     }
     if (new_problem) x_prepare(inext.b, std::false_type{});  // (every wave is behind its last use of the old registers and sums)
     __syncthreads();
     {
-      // this thread's two outputs o = tid, tid + 512: (tile t, register r, lane l) -> activation row a, weight row; their eight
-      // partial sums each: eight ds_read2st64_b32 issued together, spelled out (at the kernel's register limit the compiler's own
+      // the partial sums of an output: LDS reads issued together, spelled out (at the kernel's register limit the compiler's own
       // schedule was a dependent read -> wait -> add round per partial sum: sixteen LDS round trips with the CU otherwise idle)
-      const int l = tid_t & 63, q0 = tid_t >> 6;  // (o + 512 >> 6 = q0 + 8: tile t + 2, the same r and l)
-      const int t0 = q0 >> 2, r = q0 & 3;
-      const int a = r + 4 * (l >> 4);
-      const uint32_t pa = lds_red + (uint32_t)(((t0 * 4 + r) * 64 + l) * 4);
-      f32x2 v0, v1, v2, v3, w0, w1, w2, w3;
-      if constexpr (WAVES == 16) {
-        // 1024 threads, ONE output each (tile t0 = q0 >> 2 covers all four tiles): its sixteen partial sums, 4096 bytes apart
+      // 512 threads; every wave stores WHOLE 128-byte lines of y (the 64 weight rows of the item in one activation row): a partial
+      // line costs the memory side what a whole one does, and the tile-per-wave mapping this replaces wrote 64 32-byte pieces per
+      // item -- m = 4 / 8 / 16 differed by nothing but these stores (same-box 73.2 / 71.7 / 69.0 %).  The sums are the same additions
+      // in the same (wave) order as before: the same bits.
+      char* yb = p.y + (int64_t)cur.b * p.stride_y;
+      if (p.m > 8) {
+        // wave W: activation rows 2 W, 2 W + 1; lane: row pair rp = lane & 31 of row a = 2 W + (lane >> 5): two adjacent weight
+        // rows = adjacent lanes of the dump = one 8-byte LDS read per k-slice, one 4-byte store
+        const int rp = (int)(lane_t & 31u), a2 = 2 * wave + (int)(lane_t >> 5);
+        const int t2 = rp >> 3, n2 = 2 * (rp & 7), r2 = a2 & 3, kb2 = a2 >> 2;
+        const uint32_t pa2 = lds_red + (uint32_t)(((r2 * 4 + t2) * 64 + ((16 * kb2 + n2 + 16 * t2) & 63)) * 4);
+        f32x4 q0v, q1v, q2v, q3v;  // (k-slice w: [0], [1] = the two rows; slice w + 1: [2], [3])
         asm volatile(
-            "ds_read2st64_b32 %0, %8 offset1:16\n\t"
-            "ds_read2st64_b32 %1, %8 offset0:32 offset1:48\n\t"
-            "ds_read2st64_b32 %2, %8 offset0:64 offset1:80\n\t"
-            "ds_read2st64_b32 %3, %8 offset0:96 offset1:112\n\t"
-            "ds_read2st64_b32 %4, %8 offset0:128 offset1:144\n\t"
-            "ds_read2st64_b32 %5, %8 offset0:160 offset1:176\n\t"
-            "ds_read2st64_b32 %6, %8 offset0:192 offset1:208\n\t"
-            "ds_read2st64_b32 %7, %8 offset0:224 offset1:240\n\t"
+            "ds_read2st64_b64 %0, %4 offset1:8\n\t"
+            "ds_read2st64_b64 %1, %4 offset0:16 offset1:24\n\t"
+            "ds_read2st64_b64 %2, %4 offset0:32 offset1:40\n\t"
+            "ds_read2st64_b64 %3, %4 offset0:48 offset1:56\n\t"
             "s_waitcnt lgkmcnt(0)"
-            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3), "=&v"(w0), "=&v"(w1), "=&v"(w2), "=&v"(w3)
-            : "v"(pa)
+            : "=&v"(q0v), "=&v"(q1v), "=&v"(q2v), "=&v"(q3v)
+            : "v"(pa2)
             : "memory");
-        float sum = ((((((v0[0] + v0[1]) + v1[0]) + v1[1]) + v2[0]) + v2[1]) + v3[0]) + v3[1];
-        sum = ((((((((sum + w0[0]) + w0[1]) + w1[0]) + w1[1]) + w2[0]) + w2[1]) + w3[0]) + w3[1]);
-        char* yb = p.y + (int64_t)cur.b * p.stride_y;
-        const int row = row0 + 16 * t0 + (l & 15);
-        if (a < p.m && (XR_ABL != 7 || sum == 123.456f)) {
-          uint16_t o16 = DT::from_f32(sum);
-          if (p.bias)
-            o16 = DT::from_f32(DT::lo_f32(o16) + DT::lo_f32(*reinterpret_cast<const uint16_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a * p.bias_row_stride + row) * 2)));
-          *reinterpret_cast<uint16_t*>(yb + (p.y_tc ? tc_a_index(a, row, p.y_tiles) : (int64_t)a * p.wrows + row) * 2) = o16;
+        const float sa = ((((((q0v[0] + q0v[2]) + q1v[0]) + q1v[2]) + q2v[0]) + q2v[2]) + q3v[0]) + q3v[2];
+        const float sb = ((((((q0v[1] + q0v[3]) + q1v[1]) + q1v[3]) + q2v[1]) + q2v[3]) + q3v[1]) + q3v[3];
+        const int row = row0 + 2 * rp;  // (even; the host guarantees wrows % 64 == 0)
+        if (a2 < p.m && p.y_f32) {  // a k-window of a longer contraction: the unrounded sums
+          *reinterpret_cast<f32x2*>(yb + ((int64_t)a2 * p.wrows + row) * 4) = f32x2{sa, sb};
+        } else if (a2 < p.m) {
+          uint16_t oa = DT::from_f32(sa), ob = DT::from_f32(sb);
+          if (p.bias) {  // rounded sum + bias, rounded again: bit-identical to the reference module's separate `y + bias`
+            const uint32_t bv = *reinterpret_cast<const uint32_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a2 * p.bias_row_stride + row) * 2);
+            oa = DT::from_f32(DT::lo_f32(oa) + DT::lo_f32(bv));
+            ob = DT::from_f32(DT::lo_f32(ob) + DT::hi_f32(bv));
+          }
+          *reinterpret_cast<uint32_t*>(yb + (p.y_tc ? tc_a_index(a2, row, p.y_tiles) : (int64_t)a2 * p.wrows + row) * 2) = (uint32_t)oa | ((uint32_t)ob << 16);
         }
       } else {
-        // 512 threads; every wave stores WHOLE 128-byte lines of y (the 64 weight rows of the item in one activation row): a partial
-        // line costs the memory side what a whole one does, and the tile-per-wave mapping this replaces wrote 64 32-byte pieces per
-        // item -- m = 4 / 8 / 16 differed by nothing but these stores (same-box 73.2 / 71.7 / 69.0 %).  The sums are the same additions
-        // in the same (wave) order as before: the same bits.
-        char* yb = p.y + (int64_t)cur.b * p.stride_y;
-        if (p.m > 8) {
-          // wave W: activation rows 2 W, 2 W + 1; lane: row pair rp = lane & 31 of row a = 2 W + (lane >> 5): two adjacent weight
-          // rows = adjacent lanes of the dump = one 8-byte LDS read per k-slice, one 4-byte store
-          const int rp = (int)(lane_t & 31u), a2 = 2 * wave + (int)(lane_t >> 5);
-          const int t2 = rp >> 3, n2 = 2 * (rp & 7), r2 = a2 & 3, kb2 = a2 >> 2;
-          const uint32_t pa2 = lds_red + (uint32_t)(((r2 * 4 + t2) * 64 + ((16 * kb2 + n2 + 16 * t2) & 63)) * 4);
-          f32x4 q0v, q1v, q2v, q3v;  // (k-slice w: [0], [1] = the two rows; slice w + 1: [2], [3])
-          asm volatile(
-              "ds_read2st64_b64 %0, %4 offset1:8\n\t"
-              "ds_read2st64_b64 %1, %4 offset0:16 offset1:24\n\t"
-              "ds_read2st64_b64 %2, %4 offset0:32 offset1:40\n\t"
-              "ds_read2st64_b64 %3, %4 offset0:48 offset1:56\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(q0v), "=&v"(q1v), "=&v"(q2v), "=&v"(q3v)
-              : "v"(pa2)
-              : "memory");
-          const float sa = ((((((q0v[0] + q0v[2]) + q1v[0]) + q1v[2]) + q2v[0]) + q2v[2]) + q3v[0]) + q3v[2];
-          const float sb = ((((((q0v[1] + q0v[3]) + q1v[1]) + q1v[3]) + q2v[1]) + q2v[3]) + q3v[1]) + q3v[3];
-          const int row = row0 + 2 * rp;  // (even; the host guarantees wrows % 64 == 0)
-          if (a2 < p.m && p.y_f32) {  // a k-window of a longer contraction: the unrounded sums
-            *reinterpret_cast<f32x2*>(yb + ((int64_t)a2 * p.wrows + row) * 4) = f32x2{sa, sb};
-          } else if (a2 < p.m && (XR_ABL != 7 || sa == 123.456f)) {  // (ablation 7: no output stores)
-            uint16_t oa = DT::from_f32(sa), ob = DT::from_f32(sb);
-            if (p.bias) {  // rounded sum + bias, rounded again: bit-identical to the reference module's separate `y + bias`
-              const uint32_t bv = *reinterpret_cast<const uint32_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a2 * p.bias_row_stride + row) * 2);
-              oa = DT::from_f32(DT::lo_f32(oa) + DT::lo_f32(bv));
-              ob = DT::from_f32(DT::lo_f32(ob) + DT::hi_f32(bv));
-            }
-            *reinterpret_cast<uint32_t*>(yb + (p.y_tc ? tc_a_index(a2, row, p.y_tiles) : (int64_t)a2 * p.wrows + row) * 2) = (uint32_t)oa | ((uint32_t)ob << 16);
-          }
-        } else {
-          // at most 8 activation rows: wave W owns row W, lane = weight row of the item: eight 4-byte LDS reads, one 2-byte store per
-          // lane = one 128-byte line per wave
-          const int a2 = wave, t2 = (int)(lane_t >> 4), n2 = (int)(lane_t & 15u), r2 = a2 & 3, kb2 = a2 >> 2;
-          const uint32_t pa2 = lds_red + (uint32_t)(((r2 * 4 + t2) * 64 + ((16 * kb2 + n2 + 16 * t2) & 63)) * 4);
-          f32x2 v0, v1, v2, v3;
-          asm volatile(
-              "ds_read2st64_b32 %0, %4 offset1:16\n\t"
-              "ds_read2st64_b32 %1, %4 offset0:32 offset1:48\n\t"
-              "ds_read2st64_b32 %2, %4 offset0:64 offset1:80\n\t"
-              "ds_read2st64_b32 %3, %4 offset0:96 offset1:112\n\t"
-              "s_waitcnt lgkmcnt(0)"
-              : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
-              : "v"(pa2)
-              : "memory");
-          const float sa = ((((((v0[0] + v0[1]) + v1[0]) + v1[1]) + v2[0]) + v2[1]) + v3[0]) + v3[1];
-          const int row = row0 + (int)lane_t;
-          if (a2 < p.m && p.y_f32) {
-            *reinterpret_cast<float*>(yb + ((int64_t)a2 * p.wrows + row) * 4) = sa;
-          } else if (a2 < p.m && (XR_ABL != 7 || sa == 123.456f)) {
-            uint16_t oa = DT::from_f32(sa);
-            if (p.bias)
-              oa = DT::from_f32(DT::lo_f32(oa) + DT::lo_f32(*reinterpret_cast<const uint16_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a2 * p.bias_row_stride + row) * 2)));
-            *reinterpret_cast<uint16_t*>(yb + (p.y_tc ? tc_a_index(a2, row, p.y_tiles) : (int64_t)a2 * p.wrows + row) * 2) = oa;
-          }
+        // at most 8 activation rows: wave W owns row W, lane = weight row of the item: eight 4-byte LDS reads, one 2-byte store per
+        // lane = one 128-byte line per wave
+        const int a2 = wave, t2 = (int)(lane_t >> 4), n2 = (int)(lane_t & 15u), r2 = a2 & 3, kb2 = a2 >> 2;
+        const uint32_t pa2 = lds_red + (uint32_t)(((r2 * 4 + t2) * 64 + ((16 * kb2 + n2 + 16 * t2) & 63)) * 4);
+        f32x2 v0, v1, v2, v3;
+        asm volatile(
+            "ds_read2st64_b32 %0, %4 offset1:16\n\t"
+            "ds_read2st64_b32 %1, %4 offset0:32 offset1:48\n\t"
+            "ds_read2st64_b32 %2, %4 offset0:64 offset1:80\n\t"
+            "ds_read2st64_b32 %3, %4 offset0:96 offset1:112\n\t"
+            "s_waitcnt lgkmcnt(0)"
+            : "=&v"(v0), "=&v"(v1), "=&v"(v2), "=&v"(v3)
+            : "v"(pa2)
+            : "memory");
+        const float sa = ((((((v0[0] + v0[1]) + v1[0]) + v1[1]) + v2[0]) + v2[1]) + v3[0]) + v3[1];
+        const int row = row0 + (int)lane_t;
+        if (a2 < p.m && p.y_f32) {
+          *reinterpret_cast<float*>(yb + ((int64_t)a2 * p.wrows + row) * 4) = sa;
+        } else if (a2 < p.m) {
+          uint16_t oa = DT::from_f32(sa);
+          if (p.bias)
+            oa = DT::from_f32(DT::lo_f32(oa) + DT::lo_f32(*reinterpret_cast<const uint16_t*>(p.bias + (int64_t)cur.b * p.stride_bias + ((int64_t)a2 * p.bias_row_stride + row) * 2)));
+          *reinterpret_cast<uint16_t*>(yb + (p.y_tc ? tc_a_index(a2, row, p.y_tiles) : (int64_t)a2 * p.wrows + row) * 2) = oa;
         }
-      }  // WAVES == 8
+      }
     }
-    if constexpr (XR_ABL != 8)  // (ablation 8: without this barrier -- a race, timing only)
     __syncthreads();  // the partial sums are consumed before the next item's build steps write into this buffer
     rcur = rnext;
     cur = inext;

@@ -86,18 +86,16 @@ struct GemvParams {
 //       row lane & 15 (rows >= M read row M - 1: their accumulator rows are never stored), so ONE LDS read per word serves all rows.
 //       D[a][n]: lane (n, sub) holds rows 4 sub + r.  A step (two super-tiles) lies inside one quantisation group (g >= 128, the host
 //       checks): one scale / zero update per step, the step's activation sums [step][16 rows] come from the staging.
-#ifndef TG_GEMV_MF_ONES
-#define TG_GEMV_MF_ONES 1  // MF: a step's activation sums (the zero-point term) from the matrix core -- four more MFMAs per step against an all-ones B operand leave sum_k x[4 sub + r][k] in
-                           // the lane that needs it -- instead of from the staging (8 two-element dot products per piece, a 16-lane butterfly per row = four LDS-latency
-                           // shuffles on the launch's critical path in front of the first barrier, an LDS write, and a 16-byte LDS read per step); 0: developer A/B
-#endif
 template <typename DT, int M, int GPS, int D, bool NORM, bool MF = false>
 __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
   static_assert(!MF || GPS == 1, "matrix-core contraction: groups of at least two super-tiles");
 #ifndef TG_GEMV_MF_ONES_MIN_M
 #define TG_GEMV_MF_ONES_MIN_M 5  // (one row in a long layer: the four extra MFMAs per step cost more than the staging saves -- 28672 x 4096 15.6 vs 15.0 us)
 #endif
-  constexpr bool MFS = MF && TG_GEMV_MF_ONES && M >= TG_GEMV_MF_ONES_MIN_M;
+  // MFS: a step's activation sums (the zero-point term) from the matrix core -- four more MFMAs per step against an all-ones B operand leave sum_k x[4 sub + r][k] in
+  // the lane that needs it -- instead of from the staging (8 two-element dot products per piece, a 16-lane butterfly per row = four LDS-latency
+  // shuffles on the launch's critical path in front of the first barrier, an LDS write, and a 16-byte LDS read per step)
+  constexpr bool MFS = MF && M >= TG_GEMV_MF_ONES_MIN_M;
   constexpr int NW = 8, NT = NW * 64;
   const int tid = threadIdx.x;
   const int lane = tid & 63;
@@ -191,18 +189,6 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
     }
   };
 
-#ifndef TG_GEMV_PRE_BARRIER
-#define TG_GEMV_PRE_BARRIER 1  // 1: the first weight requests behind the staging requests AND a workgroup barrier (below); developer A/B: 0 = no barrier
-                               // (every wave requests its weights right behind its own staging requests), 2 = the weights FIRST
-#endif
-#if TG_GEMV_PRE_BARRIER == 2
-#pragma unroll
-  for (int j = 0; j < D; ++j) {
-    __builtin_amdgcn_sched_barrier(0);
-    issue(ring[j]);
-  }
-  __builtin_amdgcn_sched_barrier(0);
-#endif
   // ---- requests: this thread's share of the activations, norm weights, LUT rows, bias values -- then, behind a workgroup barrier,
   // the first D steps of the weight stream (the CU's vector-memory path takes requests in arrival order: 64 KiB of weight
   // requests of the waves that got there first would sit in front of the last wave's 16 bytes of activations) ----
@@ -300,24 +286,13 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
   }
   // the first D steps of the weight stream, behind everything the staging in front of the first barrier waits for (vector
   // memory returns in order: requested first, the staging would wait for HBM instead of L2) -- on every wave of the workgroup
-#ifndef TG_GEMV_ASM_BARRIER
-#define TG_GEMV_ASM_BARRIER 1
-#endif
-#if TG_GEMV_PRE_BARRIER == 1
-#if TG_GEMV_ASM_BARRIER
   asm volatile("s_barrier" ::: "memory");  // (spelled out: in front of the builtin hipcc waits vmcnt(0) -- the staging loads would have to RETURN before the first weight request)
-#else
-  __builtin_amdgcn_s_barrier();
-#endif
-#endif
-#if TG_GEMV_PRE_BARRIER != 2
 #pragma unroll
   for (int j = 0; j < D; ++j) {
     __builtin_amdgcn_sched_barrier(0);
     issue(ring[j]);
   }
   __builtin_amdgcn_sched_barrier(0);
-#endif
 #if GEMV_TRACE
   tr[1] = __builtin_amdgcn_s_memrealtime();
 #endif
