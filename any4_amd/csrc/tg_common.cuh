@@ -1,5 +1,6 @@
-// tg_common.cuh -- what every translation unit of libtinygemm_hip.so shares: type traits, host helpers, the parameter block the
-// C ABI fills in (GemmParams) and the entry points of the kernel families' launch paths (namespace tgx).
+// tg_common.cuh -- what every translation unit of libtinygemm_hip.so shares: type traits, host helpers, the description of one validated
+// call (GemmParams: host-only, no kernel receives it), the pieces of the planning protocol every launch path repeats (has_workspace,
+// plan_cu_count, launch_lds_kernel) and the entry points of the kernel families' launch paths (namespace tgx).
 //
 // The library is built from one translation unit per kernel family (any4_amd/build.py compiles them in parallel):
 //   tinygemm_hip.hip   the C ABI, validation (check_gemm), GemmParams (make_params), dispatch (launch_w4, launch_w8); its kernels:
@@ -30,6 +31,8 @@
 
 #include "../../include/tinygemm_hip.h"
 
+// One validated call, complete: everything a launch path needs to plan and launch it (make_params fills it once).  Host-only -- every
+// kernel has an argument block of its own (copy_call).
 struct GemmParams {
   const char* x;
   const char* w;
@@ -42,25 +45,47 @@ struct GemmParams {
   int32_t gshift;    // log2(group)
   int32_t ngroups;   // k / group
   int32_t qtype;
-  int32_t splitk;    // waves per tile (power of two, <= WAVES)
-  int32_t sk_shift;  // log2(splitk)
   int32_t rowtiles;  // ceil(wrows / 16)
-  int32_t dbg;       // always 0, read by no kernel (kept: removing it moves the kernel-argument offsets behind it)
-  int32_t numerics;  // TG_NUM_* (host-side dispatch only)
-  int32_t dot2;      // host-side only: TG_NUM_FAST_DOT2 was asked for (never promote a stacked m = 1 launch to the matrix-core contraction)
-  int32_t dry;       // host-side only: report the kernel family instead of launching (tg_gemm_w4_plan)
+  int32_t dt;        // TG_BF16 / TG_F16
+  int32_t on_right;  // the side and ...
+  int32_t inner;     // ... innerKTiles the packed words actually hold (make_params)
+  int32_t qmx;       // qtype == TG_Q_MX4
+  int32_t batch;     // problems of the call (>= 1)
+  hipStream_t st;
+  int32_t numerics;  // TG_NUM_* (dispatch)
+  int32_t dot2;      // TG_NUM_FAST_DOT2 was asked for (never promote a stacked m = 1 launch to the matrix-core contraction)
+  int32_t dry;       // report the kernel family instead of launching (tg_gemm_w4_plan)
   int64_t stride_x, stride_w, stride_qinfo, stride_lut, stride_y;
   const char* bias;   // optional [wrows] 16-bit, added after the first rounding (see store_rows4)
   int64_t stride_bias;
   int64_t bias_row_stride;  // elements between the bias rows of consecutive activation rows (0: one row for all; wrows: a residual)
-  const char* norm_w;       // fused RMSNorm of the activations (pair-table kernels only) / host-side dispatch
+  const char* norm_w;       // fused RMSNorm of the activations (pair-table kernels only)
   float norm_eps;
   int32_t epilogue;         // TG_EPI_* (pair-table kernels only)
-  // host-side only: the caller's workspace (pair kernel, XG variant) and the planner's answer to "how much would help"
+  // The caller's workspace and the planner's answer to "how much would help".  ws_need: the dispatcher zeroes it when it offers the call
+  // to a family, a family assigns it only where it accepts the call.
   char* ws;
   int64_t ws_bytes, ws_need;
-  int32_t ws_query;
+  int32_t ws_query;    // tg_gemm_*_workspace_bytes: plan as if the caller had brought whatever is asked for
   int32_t x_tc, y_tc;  // fragment-order activations / output (pair-table kernels only)
+};
+
+// Argument block of w4_gemm_kernel (w4_gemm.cuh) and w8_gemm_kernel (w8_gemm.cuh): splitk_params.
+struct SplitKParams {
+  const char* x;
+  const char* w;
+  const char* qinfo;
+  const char* lut;
+  char* y;
+  int32_t m, wrows, k;
+  int32_t ntiles, ksuper, gshift, ngroups, qtype;  // as in GemmParams
+  int32_t splitk;    // waves per tile (power of two, <= WAVES)
+  int32_t sk_shift;  // log2(splitk)
+  int32_t rowtiles;  // ceil(wrows / 16)
+  int64_t stride_x, stride_w, stride_qinfo, stride_lut, stride_y;
+  const char* bias;
+  int64_t stride_bias;
+  int64_t bias_row_stride;
 };
 
 // Lane exchanges WITHOUT the LDS crossbar.  hipcc turns every `__shfl_xor` into ds_bpermute_b32 -- an LDS-pipeline round trip (address
@@ -129,37 +154,29 @@ enum { CANON_NONE = 0, CANON_PAIR = 1, CANON_QUAD = 2 };
 // Returned by a family's launch path when the shape does not fit its plan (the caller then takes another kernel).
 enum { TG_PAIR_NA = -100 };
 
-// launch paths of the kernel families (dt = TG_BF16 / TG_F16; the other arguments as in the templates they wrap).  The two largest
-// families are compiled once per 16-bit type.
+// Launch paths of the kernel families: each takes the call and answers a TG_PLAN_* code (p.dry), 0 / an error code (launched), or
+// TG_PAIR_NA.  The two largest families are compiled once per 16-bit type.
 namespace tgx {
-int pair_bf16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair_f16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair_a_bf16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair_a_f16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair_b16_bf16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair_b16_f16(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int stream_bf16(bool layout_a, int wpl, bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st);
-int stream_f16(bool layout_a, int wpl, bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st);
-int pair_xr(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int pair16(int dt, int I, bool qmx, const GemmParams& p, int64_t batch, hipStream_t st);
-int pair16_loop(int dt, int I, bool qmx, const GemmParams& p, int64_t batch, hipStream_t st);  // w4_gemm_pair16_loop.cuh: one layer, more 16-row tiles than CUs
-int splitk(int dt, bool layout_a, int canon, bool qmx, int waves, const GemmParams& p, dim3 grid, hipStream_t st);
-int gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);
-int tile(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st);  // w4_gemm_tile.cuh: many activation rows
-int tile_w8(int dt, bool on_right, int I, GemmParams& p, int64_t batch, hipStream_t st);  // ... int8 weights (tg_gemm_w8)
-int gemm_dx(int dt, int I, bool qmx, GemmParams& p, hipStream_t st);  // w4_gemm_dx.cuh: dX = dY . W (tg_gemm_w4_dx)
-inline int pair(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? pair_bf16(I, qmx, p, batch, st) : pair_f16(I, qmx, p, batch, st);
-}
-inline int pair_a(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? pair_a_bf16(I, qmx, p, batch, st) : pair_a_f16(I, qmx, p, batch, st);
-}
-inline int pair_b16(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? pair_b16_bf16(I, qmx, p, batch, st) : pair_b16_f16(I, qmx, p, batch, st);
-}
-inline int stream(int dt, bool layout_a, int wpl, bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? stream_bf16(layout_a, wpl, qmx, p, coltiles, batch, st) : stream_f16(layout_a, wpl, qmx, p, coltiles, batch, st);
-}
+int pair_bf16(GemmParams& p);
+int pair_f16(GemmParams& p);
+int pair_a_bf16(GemmParams& p);
+int pair_a_f16(GemmParams& p);
+int pair_b16_bf16(GemmParams& p);
+int pair_b16_f16(GemmParams& p);
+int stream_bf16(const GemmParams& p);
+int stream_f16(const GemmParams& p);
+int pair_xr(GemmParams& p);
+int pair16(const GemmParams& p);
+int pair16_loop(const GemmParams& p);  // w4_gemm_pair16_loop.cuh: one layer, more 16-row tiles than CUs
+int splitk(const GemmParams& p, int waves, int splitk);  // (the dispatcher routes on pick_geometry's answer, and passes it on)
+int gemv(const GemmParams& p);
+int tile(GemmParams& p);     // w4_gemm_tile.cuh: many activation rows
+int tile_w8(GemmParams& p);  // ... int8 weights (tg_gemm_w8)
+int gemm_dx(GemmParams& p);  // w4_gemm_dx.cuh: dX = dY . W (tg_gemm_w4_dx)
+inline int pair(GemmParams& p) { return p.dt == TG_BF16 ? pair_bf16(p) : pair_f16(p); }
+inline int pair_a(GemmParams& p) { return p.dt == TG_BF16 ? pair_a_bf16(p) : pair_a_f16(p); }
+inline int pair_b16(GemmParams& p) { return p.dt == TG_BF16 ? pair_b16_bf16(p) : pair_b16_f16(p); }
+inline int stream(const GemmParams& p) { return p.dt == TG_BF16 ? stream_bf16(p) : stream_f16(p); }
 }  // namespace tgx
 
 namespace {
@@ -268,8 +285,11 @@ inline int launch_status() {
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 inline int group_shift(int g) { return g == 32 ? 5 : g == 64 ? 6 : g == 128 ? 7 : 8; }  // log2 of a validated qGroupSize
+inline int64_t coltiles(const GemmParams& p) { return cdiv(p.m, 16); }                    // 16-row tiles of activations
+// packed words per (k super-tile, lane-row) entry of the layout (1 / 2 / 4 = CANON_NONE / _PAIR / _QUAD: the in-register transpose)
+inline int words_per_lane(const GemmParams& p) { return p.on_right ? p.inner / 2 : p.inner; }
 
-// Every kernel family has a parameter block of its own (its layout is that kernel's ABI), and each repeats part of GemmParams under the
+// Every kernel has a parameter block of its own (its layout is that kernel's ABI), and each repeats part of GemmParams under the
 // same names.  copy_call assigns, of the fields listed, those the destination has: the operands, the problem's sizes and group geometry,
 // the batch strides, the bias, the fused stages, the fragment-order flags and `dry`.  What a family derives or overrides it sets afterwards.
 template <typename D, typename F>
@@ -286,6 +306,18 @@ void copy_call(D& d, const GemmParams& p) {
   TG_COPY(norm_w); TG_COPY(norm_eps); TG_COPY(epilogue); TG_COPY(x_tc); TG_COPY(y_tc); TG_COPY(dry);
 #undef TG_COPY
 }
+inline SplitKParams splitk_params(const GemmParams& p, int splitk) {
+  SplitKParams kp;
+  copy_call(kp, p);
+  kp.rowtiles = p.rowtiles;
+  kp.splitk = splitk;
+  kp.sk_shift = 0;
+  while ((1 << kp.sk_shift) < splitk) ++kp.sk_shift;
+  return kp;
+}
+
+// The workspace half of the planning protocol: does the caller have `need` bytes -- or is this the workspace query, which plans as if?
+inline bool has_workspace(const GemmParams& p, int64_t need) { return p.ws_query || (p.ws != nullptr && p.ws_bytes >= need); }
 
 // Kernels that address LDS from offset 0 (lookup tables at the start of the dynamic region) and / or need more than 64 KiB
 // of dynamic LDS: once per device, check that the kernel has no static LDS (the dynamic region then starts at 0) and raise
@@ -305,7 +337,15 @@ int prepare_lds_kernel() {
   if (dev >= 0 && dev < 64) done.fetch_or(1ull << dev, std::memory_order_relaxed);
   return 0;
 }
-
+// ... and launch it.  A failed preparation is either passed on, or (decline_on_failure: a part with less LDS) answered with TG_PAIR_NA --
+// the older kernels take over -- unless it is TG_E_INTERNAL.
+template <auto KERN, typename P>
+int launch_lds_kernel(dim3 grid, dim3 block, unsigned lds, hipStream_t st, const P& params, bool decline_on_failure) {
+  const int prc = prepare_lds_kernel<KERN>();
+  if (prc != 0) return decline_on_failure && prc != TG_E_INTERNAL ? (int)TG_PAIR_NA : prc;
+  hipLaunchKernelGGL(KERN, grid, block, lds, st, params);
+  return launch_status();
+}
 
 // compute units of the current device (write-once cache per device index; racing threads store the same value)
 inline int cu_count() {
@@ -318,6 +358,8 @@ inline int cu_count() {
   cache[dev].store(v, std::memory_order_relaxed);
   return v;
 }
+// ... a plan is made without a device: for 256
+inline int plan_cu_count(const GemmParams& p) { return p.dry ? 256 : cu_count(); }
 
 
 // Tuning constants of the pair-table launches, each with the measurement that set it.  The shipped library

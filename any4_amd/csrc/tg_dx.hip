@@ -9,16 +9,11 @@ constexpr int kDxCUs = 256;
 
 template <typename DT, int BM, bool QMX>
 int go(const DxParams& dp, hipStream_t st) {
-  constexpr auto kern = w4_gemm_dx_kernel<DT, BM, QMX>;
-  const int prc = prepare_lds_kernel<kern>();
-  if (prc != 0) return prc;
   const int ns = dp.splits > 1 ? dp.splits : 1;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)dp.tiles_m * dp.tiles_k * ns)), dim3(256), DxLds<BM>::BYTES, st, dp);
-  if (ns > 1) {
-    const int64_t quads = (int64_t)dp.m * dp.k / 4;
-    hipLaunchKernelGGL(dx_split_sum_kernel<DT>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, dp.part, ns, (int64_t)dp.m * dp.k, dp.dx,
-                       quads);
-  }
+  const int rc = launch_lds_kernel<w4_gemm_dx_kernel<DT, BM, QMX>>(dim3((unsigned)((int64_t)dp.tiles_m * dp.tiles_k * ns)), dim3(256), DxLds<BM>::BYTES, st, dp, false);
+  if (rc != 0 || ns == 1) return rc;
+  const int64_t quads = (int64_t)dp.m * dp.k / 4;
+  hipLaunchKernelGGL(dx_split_sum_kernel<DT>, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, dp.part, ns, (int64_t)dp.m * dp.k, dp.dx, quads);
   return launch_status();
 }
 template <typename DT, bool QMX>
@@ -36,11 +31,11 @@ namespace tgx {
 // Split over the weight rows: a tile's steps are a chain of dependent LDS round trips, so a launch with fewer tiles than CUs leaves the
 // chip idle for as long as a full one takes.  With the caller's workspace the row steps are cut into 2 ... 16 splits (as many as keep
 // tiles x splits <= 256 and at least four 64-row steps per split); without one the launch runs unsplit (slower, same contract as tg_gemm_w8).
-int gemm_dx(int dt, int I, bool qmx, GemmParams& p, hipStream_t st) {
+int gemm_dx(GemmParams& p) {
   const int bm = p.m <= 32 ? 32 : p.m <= 64 ? 64 : 128;
   DxParams dp;
   dp.dy = p.x; dp.w = p.w; dp.qinfo = p.qinfo; dp.lut = p.lut; dp.dx = p.y;
-  dp.m = p.m; dp.wrows = p.wrows; dp.k = p.k; dp.ksuper = p.k / (16 * I); dp.inner = I; dp.gshift = p.gshift; dp.qtype = p.qtype;
+  dp.m = p.m; dp.wrows = p.wrows; dp.k = p.k; dp.ksuper = p.ksuper; dp.inner = p.inner; dp.gshift = p.gshift; dp.qtype = p.qtype;
   dp.tiles_m = (int32_t)cdiv(p.m, bm);
   dp.tiles_k = (int32_t)cdiv(p.k, DX_BK);
   const int nsteps = (int)cdiv(p.wrows, DX_BR);
@@ -48,13 +43,13 @@ int gemm_dx(int dt, int I, bool qmx, GemmParams& p, hipStream_t st) {
   int splits = 1;
   while (splits < 16 && tiles * splits * 2 <= kDxCUs && nsteps >= splits * 2 * 4) splits *= 2;
   const int64_t need = splits > 1 ? (int64_t)splits * p.m * p.k * 4 : 0;
-  if (splits > 1 && !p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) splits = 1;   // (the caller did not bring the workspace)
+  if (!has_workspace(p, need)) splits = 1;
   p.ws_need = splits > 1 ? need : 0;
   if (p.dry) return 0;
   dp.splits = splits;
   dp.sps = (nsteps + splits - 1) / splits;
   dp.part = splits > 1 ? reinterpret_cast<float*>(p.ws) : nullptr;
-  if (qmx) return go_bm<BF16, true>(dp, bm, st);
-  return dt == TG_BF16 ? go_bm<BF16, false>(dp, bm, st) : go_bm<F16, false>(dp, bm, st);
+  if (p.qmx) return go_bm<BF16, true>(dp, bm, p.st);
+  return p.dt == TG_BF16 ? go_bm<BF16, false>(dp, bm, p.st) : go_bm<F16, false>(dp, bm, p.st);
 }
 }  // namespace tgx

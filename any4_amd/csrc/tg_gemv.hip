@@ -17,11 +17,7 @@ namespace {
 
 template <typename DT, int M, int GPS, int D, bool NORM, bool MF = false>
 int go(const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  constexpr auto kern = w4_gemv_kernel<DT, M, GPS, D, NORM, MF>;
-  const int prc = prepare_lds_kernel<kern>();
-  if (prc != 0) return prc == TG_E_INTERNAL ? prc : TG_PAIR_NA;  // (a part with less LDS: the older kernels take over)
-  hipLaunchKernelGGL(kern, grid, dim3(512), lds, st, gp);
-  return launch_status();
+  return launch_lds_kernel<w4_gemv_kernel<DT, M, GPS, D, NORM, MF>>(grid, dim3(512), lds, st, gp, true);  // (a part with less LDS: the older kernels take over)
 }
 template <typename DT, int M, int GPS, int D>
 int go_n(bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
@@ -84,14 +80,14 @@ extern "C" TG_API void tg_dev_gemv_trace(unsigned long long* buf, int slots) {
 }
 #endif
 
-int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
+int tgx::gemv(const GemmParams& p) {
   const int g0 = 1 << p.gshift;
   // matrix-core contraction: 16-row passes of two super-tiles per step inside ONE group, a piece per thread in the staging
 #ifndef TG_GEMV_MF_MAX_M
 #define TG_GEMV_MF_MAX_M 8  // (developer A/B against w4_gemm_pair16_kernel / the loop kernel at 5 ... 8 rows)
 #endif
   const bool mf = p.m >= TG_GEMV_MF_MIN_M && p.m <= TG_GEMV_MF_MAX_M && (g0 == 128 || g0 == 256) && (p.k <= 4096 || p.m <= 4) && p.ksuper % 2 == 0;
-  if (I != 4 || qmx || (p.m > 4 && !mf) || p.x_tc || p.y_tc || batch != 1) return TG_PAIR_NA;
+  if (p.inner != 4 || p.qmx || (p.m > 4 && !mf) || p.x_tc || p.y_tc || p.batch != 1) return TG_PAIR_NA;
   if (p.ksuper * 64 != p.k || p.ntiles * 8 != p.wrows || p.ntiles > TG_GEMV_MAX_TILES) return TG_PAIR_NA;
   const int g = 1 << p.gshift;
   const int gps = g == 32 ? 2 : 1;
@@ -105,7 +101,7 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
   gp.unit = p.epilogue == TG_EPI_SWIGLU ? 2 : 1;
   if (p.ntiles % gp.unit != 0) return TG_PAIR_NA;
   const int units = p.ntiles / gp.unit;
-  const int cus = p.dry ? 256 : cu_count();
+  const int cus = plan_cu_count(p);
   // one workgroup per CU (two per CU were measured on gate_up of Llama-3-8B: the second workgroup of a CU trails the first by 3 us
   // through its prologue and the launch ends no earlier -- the CU's instruction issue, not latency, bounds the main loop)
   // ... except for the longest layers: a dependent graph node that streams 64 MiB takes 14.3 us from one workgroup per CU and 13.1 us
@@ -189,12 +185,12 @@ int tgx::gemv(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t
   const unsigned lds = (unsigned)gp.lds_nrm + (unsigned)(8 * p.m * 4);
   if (lds > 160u * 1024u) return TG_PAIR_NA;
   if (p.dry) return TG_PLAN_GEMV;
-  const dim3 grid((unsigned)wgs, (unsigned)batch);
+  const dim3 grid((unsigned)wgs, (unsigned)p.batch);
 #if GEMV_TRACE
   if (g_trace && g_trace_slots > 0) gp.trace = g_trace + (size_t)(g_trace_launch++ % g_trace_slots) * 512 * 8;
 #endif
-  if (mf) return dt == TG_BF16 ? go_mf_m<BF16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, st)
-                               : go_mf_m<F16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, st);
-  return dt == TG_BF16 ? go_m<BF16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, st)
-                       : go_m<F16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, st);
+  if (mf) return p.dt == TG_BF16 ? go_mf_m<BF16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, p.st)
+                                 : go_mf_m<F16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, p.st);
+  return p.dt == TG_BF16 ? go_m<BF16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, p.st)
+                         : go_m<F16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, p.st);
 }

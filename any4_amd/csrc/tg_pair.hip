@@ -11,7 +11,7 @@
 namespace {
 #include "w4_gemm_pair.cuh"
 template <typename DT, int I, int GPS, int MR, bool QMX, int NSG, bool XG = false, int LA = 0, bool NORM = false, bool M1_MFMA = false>
-int launch_pair_k(PairParams& pp, unsigned lds, hipStream_t st) {
+int launch_pair_k(const GemmParams& p, PairParams& pp, unsigned lds) {
 #ifdef TG_DEV_MIN  // developer builds: only the headline instantiation (fast A/B builds)
 #ifndef TG_DEV_GPS
 #define TG_DEV_GPS 1
@@ -34,13 +34,9 @@ int launch_pair_k(PairParams& pp, unsigned lds, hipStream_t st) {
   // 128-VGPR budget without spills (ring depth measured irrelevant between 2 and 4)
   // (mx4 on the 32x32x16 tiles converts its weights in registers and has no per-group state in the slots: the usual depth)
   constexpr int RING = (QMX && LA == 0) ? TG_PAIR_R : (MR == 1 && NSG == 4 && LA == 0) ? 4 : GPS > 1 ? (LA ? TG_PAIR_RA1 : 1) : LA == 1 ? TG_PAIR_RA : LA == 2 ? TG_PAIR_RB16 : TG_PAIR_R;
-  constexpr auto kern = w4_gemm_pair_kernel<DT, I, GPS, MR, QMX, RING, NSG, M1_MFMA, XG, LA, NORM>;
-  if (pp.dry) return TG_PLAN_PAIR;
-  const int prc = prepare_lds_kernel<kern>();
-  if (prc != 0) return prc;
+  if (p.dry) return TG_PLAN_PAIR;
   const unsigned wgs = (unsigned)(pp.items < TG_PAIR_WGS ? pp.items : TG_PAIR_WGS);
-  hipLaunchKernelGGL(kern, dim3(wgs), dim3(512), lds, st, pp);
-  return launch_status();
+  return launch_lds_kernel<w4_gemm_pair_kernel<DT, I, GPS, MR, QMX, RING, NSG, M1_MFMA, XG, LA, NORM>>(dim3(wgs), dim3(512), lds, p.st, pp, false);
   }
 #ifdef TG_DEV_MIN
   }
@@ -51,16 +47,16 @@ int launch_pair_k(PairParams& pp, unsigned lds, hipStream_t st) {
 // takes the activations pre-arranged from a caller-provided workspace (w4_xprep_kernel, one small launch in front).
 // Workspace = [batch][m k 2 bytes] arranged activations, then [batch][passes][groups][xs_rows] f32 sums.
 template <typename DT>
-int launch_xprep(const PairParams& pp, int I, int ma, int64_t batch, hipStream_t st, int la = 0) {
+int launch_xprep(const GemmParams& p, const PairParams& pp, int ma, int la = 0) {
   XPrepParams xq;
   xq.la = la;
   xq.x = pp.x; xq.xp = const_cast<char*>(pp.xp); xq.xsum = const_cast<char*>(pp.xsum);
   xq.x_tc = pp.x_tc;
-  xq.m = pp.m; xq.k = pp.k; xq.ma = ma; xq.cps = I / 2; xq.gshift = pp.gshift; xq.gch_mask = pp.gch_mask;
+  xq.m = pp.m; xq.k = pp.k; xq.ma = ma; xq.cps = p.inner / 2; xq.gshift = pp.gshift; xq.gch_mask = pp.gch_mask;
   xq.ngroups = pp.ngroups; xq.xs_rows = pp.xs_rows;
   xq.stride_x = pp.stride_x; xq.stride_xp = pp.stride_xp; xq.stride_xsum = pp.stride_xsum;
   const int64_t chunks = (int64_t)pp.m * (pp.k / 32);
-  hipLaunchKernelGGL(w4_xprep_kernel<DT>, dim3((unsigned)cdiv(chunks, 256), (unsigned)batch), dim3(256), 0, st, xq);
+  hipLaunchKernelGGL(w4_xprep_kernel<DT>, dim3((unsigned)cdiv(chunks, 256), (unsigned)p.batch), dim3(256), 0, p.st, xq);
   return launch_status();
 }
 
@@ -68,8 +64,9 @@ int launch_xprep(const PairParams& pp, int I, int ma, int64_t batch, hipStream_t
 // with several groups per super-tile, where the general kernel's zero-C group starts compile without spills; `norm`: the
 // instantiations with LlamaRMSNorm fused into the activation staging (staged activations, m <= 8, not mx4)
 template <typename DT, int I, int GPS, bool QMX, int NSG>
-int launch_pair_m(PairParams& pp, unsigned lds, hipStream_t st, bool xg, int m, int mregs, bool norm) {
-  const bool m1 = m == 1 && TG_PAIR_MR1 == 1 && (QMX || GPS <= TG_PAIR_MR1_GPS);  // (mx4: no per-group state, the specialisation fits at any GPS)
+int launch_pair_m(const GemmParams& p, PairParams& pp, unsigned lds, bool xg, int mregs) {
+  const bool norm = p.norm_w != nullptr;
+  const bool m1 = p.m == 1 && TG_PAIR_MR1 == 1 && (QMX || GPS <= TG_PAIR_MR1_GPS);  // (mx4: no per-group state, the specialisation fits at any GPS)
   // Not instantiated (round 4: every one of them compiled with 70 ... 1100 bytes of scratch per lane, and a scratch reload drains
   // the weight ring behind vmcnt(0)): the 32-activation-row accumulator sets (m > 8 on staged activations), innerKTiles 8 beyond the
   // m = 1 kernel of int4 / any4, the fused norm with several groups per super-tile.  Those calls take the next kernel family
@@ -79,19 +76,19 @@ int launch_pair_m(PairParams& pp, unsigned lds, hipStream_t st, bool xg, int m, 
     if constexpr (QMX) return TG_PAIR_NA;
     else {
       if (!m1 || norm) return TG_PAIR_NA;
-      return xg ? launch_pair_k<DT, I, GPS, 1, false, NSG, true>(pp, lds, st) : launch_pair_k<DT, I, GPS, 1, false, NSG>(pp, lds, st);
+      return xg ? launch_pair_k<DT, I, GPS, 1, false, NSG, true>(p, pp, lds) : launch_pair_k<DT, I, GPS, 1, false, NSG>(p, pp, lds);
     }
   } else {
-  if (xg) return m1 ? launch_pair_k<DT, I, GPS, 1, QMX, NSG, true>(pp, lds, st) : launch_pair_k<DT, I, GPS, 4, QMX, NSG, true>(pp, lds, st);
+  if (xg) return m1 ? launch_pair_k<DT, I, GPS, 1, QMX, NSG, true>(p, pp, lds) : launch_pair_k<DT, I, GPS, 4, QMX, NSG, true>(p, pp, lds);
   if (norm) {
     if constexpr (QMX || GPS > 1) return TG_PAIR_NA;
     else {
-      return m1 ? launch_pair_k<DT, I, GPS, 1, false, NSG, false, false, true>(pp, lds, st)
-                : launch_pair_k<DT, I, GPS, 4, false, NSG, false, false, true>(pp, lds, st);
+      return m1 ? launch_pair_k<DT, I, GPS, 1, false, NSG, false, false, true>(p, pp, lds)
+                : launch_pair_k<DT, I, GPS, 4, false, NSG, false, false, true>(p, pp, lds);
     }
   }
-  if (m1) return launch_pair_k<DT, I, GPS, 1, QMX, NSG>(pp, lds, st);
-  return launch_pair_k<DT, I, GPS, 4, QMX, NSG>(pp, lds, st);
+  if (m1) return launch_pair_k<DT, I, GPS, 1, QMX, NSG>(p, pp, lds);
+  return launch_pair_k<DT, I, GPS, 4, QMX, NSG>(p, pp, lds);
   }
 }
 
@@ -139,20 +136,19 @@ unsigned pair_lds_plan(const GemmParams& p, PairParams& pp, int x_bytes, bool al
 }
 
 // Workspace = [batch][xrows k 2 bytes] arranged activations, then [batch][groups][xs_rows] f32 sums (w4_xprep_kernel writes both).
-// Reports the bytes in p.ws_need; false: the caller did not bring them.
-inline bool pair_workspace(GemmParams& p, PairParams& pp, int xrows, int64_t batch) {
+// Returns the bytes; 0: the caller did not bring them.
+inline int64_t pair_workspace(const GemmParams& p, PairParams& pp, int xrows) {
   pp.stride_xp = (int64_t)xrows * p.k * 2;
   pp.stride_xsum = ((int64_t)p.ngroups * pp.xs_rows * 4 + 15) & ~(int64_t)15;
-  const int64_t need = batch * (pp.stride_xp + pp.stride_xsum);
-  p.ws_need = need;
-  if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return false;
+  const int64_t need = p.batch * (pp.stride_xp + pp.stride_xsum);
+  if (!has_workspace(p, need)) return 0;
   pp.xp = p.ws;
-  pp.xsum = p.ws + batch * pp.stride_xp;
-  return true;
+  pp.xsum = p.ws + p.batch * pp.stride_xp;
+  return need;
 }
 
 template <typename DT, int I, bool QMX>
-int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
+int launch_pair(GemmParams& p) {
   constexpr int RW = 64;
   const int mregs = p.m <= 8 ? 4 : 16;  // accumulator registers of a row set (8 or 32 activation rows per pass)
   const int ma = 2 * mregs;
@@ -171,7 +167,7 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
   // fused RMSNorm: done in the workgroup's own staging of the whole activation block (its partial sums borrow the activation-sum
   // area, which mx4 does not have); the workspace variant would need it in the pre-pass
   if (p.norm_w && (QMX || lds > 80u * 1024u || p.m > ma)) return TG_PAIR_NA;
-  bool xg = false;
+  int64_t need = 0;  // XG: the workspace of the launch
   if (lds > 80u * 1024u) {  // two workgroups per CU
     // XG: every wave keeps one super-tile of the pass's activations (<= 8 rows) in a private buffer
     if (mregs != 4 || p.m > ma) return TG_PAIR_NA;
@@ -180,25 +176,27 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
     lds = pair_lds_plan<I, QMX>(p, pp, 8 * pp.xw_bytes, pp.red_alias, true);  // 8 buffers
     if (QMX && pp.red_alias) return TG_PAIR_NA;  // (no table to put the partial sums over; cannot happen: 8 one-KiB buffers + 16 KiB)
     if (lds > 80u * 1024u) return TG_PAIR_NA;
-    if (!pair_workspace(p, pp, p.m, batch)) return TG_PAIR_NA;
-    xg = true;
+    need = pair_workspace(p, pp, p.m);
+    if (!need) return TG_PAIR_NA;
   }
+  const bool xg = need != 0;
   pp.rblocks = (p.wrows + RW - 1) / RW;
   pp.cblocks = (p.m + ma - 1) / ma;
-  const int64_t items = (int64_t)pp.rblocks * pp.cblocks * batch;
+  const int64_t items = (int64_t)pp.rblocks * pp.cblocks * p.batch;
   if (items > INT32_MAX) return TG_PAIR_NA;
   // The kernel's unit of work is a 64-row block over the whole k (8 waves): a launch needs about one item per workgroup slot
   // (2 per CU) to fill the chip.  Smaller launches (one 4096-row layer = 64 items) are latency-bound and stay on the
   // split-K kernels, which spread one 16-row tile over up to 16 waves.
-  if (items < TG_PAIR_MIN_ITEMS) { p.ws_need = 0; return TG_PAIR_NA; }
+  if (items < TG_PAIR_MIN_ITEMS) return TG_PAIR_NA;
   pp.items = (int32_t)items;
   // XG item dealing: chunks of consecutive items once every workgroup still gets several chunks
   pp.chunk = items >= (int64_t)TG_PAIR_WGS * TG_XG_CHUNK * 4 ? TG_XG_CHUNK : 1;
+  p.ws_need = need;  // (the call is this family's from here on, but for the gaps in the tables of instantiations below)
   if (xg && !p.dry) {
-    const int rc = launch_xprep<DT>(pp, I, ma, batch, st);
+    const int rc = launch_xprep<DT>(p, pp, ma);
     if (rc != 0) return rc;
   }
-#define TG_PAIR_M(GPS_, NSG_) launch_pair_m<DT, I, GPS_, QMX, NSG_>(pp, lds, st, xg, p.m, mregs, p.norm_w != nullptr)
+#define TG_PAIR_M(GPS_, NSG_) launch_pair_m<DT, I, GPS_, QMX, NSG_>(p, pp, lds, xg, mregs)
   if (gps == 1) {
     // group boundaries at fixed places of the unrolled round when a group is one super-tile or one whole round
     // (the m = 1 specialisation too since its group update is spelled out instruction by instruction: before that, fixed
@@ -210,7 +208,7 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
     // in-register and fed to bf16 MFMA") instead of the per-lane v_dot2 the default takes -- one instantiation, g = 128 at innerKTiles 4
     if constexpr (I == 4 && !QMX) {
       if (p.numerics == TG_NUM_FAST_MFMA && p.m == 1 && !xg && !p.norm_w && fixed && nsg == TG_PAIR_R)
-        return launch_pair_k<DT, I, 1, 1, false, TG_PAIR_R, false, 0, false, true>(pp, lds, st);
+        return launch_pair_k<DT, I, 1, 1, false, TG_PAIR_R, false, 0, false, true>(p, pp, lds);
     }
     if (fixed && nsg == TG_PAIR_R) return TG_PAIR_M(1, TG_PAIR_R);
     // m = 1, a group of ONE super-tile (g = 64 at innerKTiles 4): fixed boundaries too since the dot2 contraction freed the registers
@@ -219,9 +217,9 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
     // instantiated for these (launch_pair_k directly: launch_pair_m would drag the general kernels in as well).
     if constexpr (!QMX) {
       if (fixed && p.m == 1 && TG_PAIR_MR1 == 1 && !p.norm_w && (nsg == 1 || nsg == 4)) {
-        if (nsg == 1) return xg ? launch_pair_k<DT, I, 1, 1, false, 1, true>(pp, lds, st) : launch_pair_k<DT, I, 1, 1, false, 1>(pp, lds, st);
+        if (nsg == 1) return xg ? launch_pair_k<DT, I, 1, 1, false, 1, true>(p, pp, lds) : launch_pair_k<DT, I, 1, 1, false, 1>(p, pp, lds);
         if constexpr (I <= 4)  // (innerKTiles 8: four super-tiles would be g = 512)
-          return xg ? launch_pair_k<DT, I, 1, 1, false, 4, true>(pp, lds, st) : launch_pair_k<DT, I, 1, 1, false, 4>(pp, lds, st);
+          return xg ? launch_pair_k<DT, I, 1, 1, false, 4, true>(p, pp, lds) : launch_pair_k<DT, I, 1, 1, false, 4>(p, pp, lds);
       }
     }
     return TG_PAIR_M(1, 0);
@@ -242,7 +240,7 @@ int launch_pair(GemmParams& p, int64_t batch, hipStream_t st) {
 //   LA = 2  Bint4 weights with 9 ... 16 activation rows: one packed word is one B operand, 4 vector ops per word.  (The 32x32x16
 //           kernel holds 8 rows per pass; a second pass would stream the weights twice.)
 template <typename DT, int I, bool QMX, int LA>
-int launch_pair_la(GemmParams& p, int64_t batch, hipStream_t st) {
+int launch_pair_la(GemmParams& p) {
   if constexpr (LA == 1 && I < 2) return TG_PAIR_NA;  // one 16-k tile per word set: no word pair for a 32-k MFMA step
   else {
   constexpr bool B = LA == 2;
@@ -264,47 +262,46 @@ int launch_pair_la(GemmParams& p, int64_t batch, hipStream_t st) {
   if (lds > 80u * 1024u) return TG_PAIR_NA;
   pp.rblocks = (p.wrows + 31) / 32;
   pp.cblocks = 1;
-  const int64_t items = (int64_t)pp.rblocks * batch;
+  const int64_t items = (int64_t)pp.rblocks * p.batch;
   // (LA = 2: 32-row items, two per 64-row item of the 32x32x16 kernel that TG_PAIR_MIN_ITEMS was measured on)
   if (items > INT32_MAX || items < (B ? 2 : 1) * TG_PAIR_MIN_ITEMS) return TG_PAIR_NA;
-  if (!pair_workspace(p, pp, p.m + 1, batch)) return TG_PAIR_NA;  // + a zero row
+  p.ws_need = pair_workspace(p, pp, p.m + 1);  // + a zero row
+  if (!p.ws_need) return TG_PAIR_NA;
   pp.items = (int32_t)items;
   // Aint4: plain round-robin dealing (chunks of consecutive items measured slower for the 32-row items of this layout)
   pp.chunk = B && items >= (int64_t)TG_PAIR_WGS * TG_B16_CHUNK * 4 ? TG_B16_CHUNK : 1;
   if (!p.dry) {
-    const int rc = launch_xprep<DT>(pp, I, 16, batch, st, 1);
+    const int rc = launch_xprep<DT>(p, pp, 16, 1);
     if (rc != 0) return rc;
   }
   if (gps == 1) {
-    if (TG_PAIR_NSG2 && nsg == 1) return launch_pair_k<DT, I, 1, 4, QMX, 1, true, LA>(pp, lds, st);
-    if (TG_PAIR_NSG2 && nsg == RING) return launch_pair_k<DT, I, 1, 4, QMX, RING, true, LA>(pp, lds, st);
-    return launch_pair_k<DT, I, 1, 4, QMX, 0, true, LA>(pp, lds, st);
+    if (TG_PAIR_NSG2 && nsg == 1) return launch_pair_k<DT, I, 1, 4, QMX, 1, true, LA>(p, pp, lds);
+    if (TG_PAIR_NSG2 && nsg == RING) return launch_pair_k<DT, I, 1, 4, QMX, RING, true, LA>(p, pp, lds);
+    return launch_pair_k<DT, I, 1, 4, QMX, 0, true, LA>(p, pp, lds);
   }
   if constexpr (I >= 4) {
-    if (gps == 2) return launch_pair_k<DT, I, 2, 4, QMX, 0, true, LA>(pp, lds, st);
+    if (gps == 2) return launch_pair_k<DT, I, 2, 4, QMX, 0, true, LA>(p, pp, lds);
   }
   return TG_PAIR_NA;  // (four groups per super-tile are innerKTiles 8, which has no 16x16x32 instantiation: tgx::pair_b16)
   }
 }
 
 template <typename DT, int I>
-int pair_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return qmx ? launch_pair<DT, I, true>(p, batch, st) : launch_pair<DT, I, false>(p, batch, st);
+int pair_q(GemmParams& p) {
+  return p.qmx ? launch_pair<DT, I, true>(p) : launch_pair<DT, I, false>(p);
 }
 template <typename DT, int I, int LA>
-int pair_la_q(bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return qmx ? launch_pair_la<DT, I, true, LA>(p, batch, st) : launch_pair_la<DT, I, false, LA>(p, batch, st);
+int pair_la_q(GemmParams& p) {
+  return p.qmx ? launch_pair_la<DT, I, true, LA>(p) : launch_pair_la<DT, I, false, LA>(p);
 }
 }  // namespace
 namespace tgx {
-int TG_TU_SUF(pair)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return I == 2 ? pair_q<TG_TU_DT, 2>(qmx, p, batch, st) : I == 4 ? pair_q<TG_TU_DT, 4>(qmx, p, batch, st) : pair_q<TG_TU_DT, 8>(qmx, p, batch, st);
+int TG_TU_SUF(pair)(GemmParams& p) { return p.inner == 2 ? pair_q<TG_TU_DT, 2>(p) : p.inner == 4 ? pair_q<TG_TU_DT, 4>(p) : pair_q<TG_TU_DT, 8>(p); }
+int TG_TU_SUF(pair_a)(GemmParams& p) {
+  return p.inner == 1 ? pair_la_q<TG_TU_DT, 1, 1>(p) : p.inner == 2 ? pair_la_q<TG_TU_DT, 2, 1>(p) : pair_la_q<TG_TU_DT, 4, 1>(p);
 }
-int TG_TU_SUF(pair_a)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return I == 1 ? pair_la_q<TG_TU_DT, 1, 1>(qmx, p, batch, st) : I == 2 ? pair_la_q<TG_TU_DT, 2, 1>(qmx, p, batch, st) : pair_la_q<TG_TU_DT, 4, 1>(qmx, p, batch, st);
-}
-int TG_TU_SUF(pair_b16)(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
+int TG_TU_SUF(pair_b16)(GemmParams& p) {
   // (innerKTiles 8 on the 16x16x32 tiles compiled with > 100 bytes of scratch per lane: not instantiated)
-  return I == 2 ? pair_la_q<TG_TU_DT, 2, 2>(qmx, p, batch, st) : I == 4 ? pair_la_q<TG_TU_DT, 4, 2>(qmx, p, batch, st) : (int)TG_PAIR_NA;
+  return p.inner == 2 ? pair_la_q<TG_TU_DT, 2, 2>(p) : p.inner == 4 ? pair_la_q<TG_TU_DT, 4, 2>(p) : (int)TG_PAIR_NA;
 }
 }  // namespace tgx

@@ -15,7 +15,8 @@ unsigned long long* g_p16_trace = nullptr;  // developer builds only (-DGEMV_TRA
 int g_p16_slots = 0, g_p16_launch = 0;
 #endif
 template <typename DT, int I, bool QMX>
-int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
+int launch_pair16(const GemmParams& p) {
+  const int64_t batch = p.batch;
   if constexpr (QMX && !std::is_same<DT, BF16>::value) return TG_E_DTYPE;  // mx4 is bf16-only (TinyGemm_int4.cu:758)
   else {
 #ifdef TG_DEV_MIN
@@ -67,22 +68,17 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
   pp.trace = (g_p16_trace && g_p16_slots > 0 && grid.x <= 512) ? g_p16_trace + (size_t)(g_p16_launch++ % g_p16_slots) * 512 * 8 : nullptr;
 #endif
 #define TG_P16K(CPG_, NORM_, XREG_, CH_) do { if (XREG_ && p.x_tc) TG_P16KX(CPG_, NORM_, XREG_, CH_, XREG_); else TG_P16KX(CPG_, NORM_, XREG_, CH_, false); } while (0)
-#define TG_P16KX(CPG_, NORM_, XREG_, CH_, XTC_)                                         \
-  do {                                                                                  \
-    constexpr auto kern = w4_gemm_pair16_kernel<DT, I, QMX, CPG_, 1, NORM_, XREG_, CH_, XTC_>; \
-    const int prc = prepare_lds_kernel<kern>();                                         \
-    if (prc != 0) return prc;                                                           \
-    hipLaunchKernelGGL(kern, grid, dim3(1024), lds, st, pp);                            \
-  } while (0)
+#define TG_P16KX(CPG_, NORM_, XREG_, CH_, XTC_) \
+  return launch_lds_kernel<w4_gemm_pair16_kernel<DT, I, QMX, CPG_, 1, NORM_, XREG_, CH_, XTC_>>(grid, dim3(1024), lds, p.st, pp, false)
 #define TG_P16(CPG_)                                              \
   do {                                                            \
     if constexpr (!QMX) {                                         \
-      if (p.norm_w) { TG_P16K(CPG_, true, false, 4); break; }     \
+      if (p.norm_w) TG_P16K(CPG_, true, false, 4);                \
     }                                                             \
-    if (xreg && pp.spw <= 4) { TG_P16K(CPG_, false, true, 4); break; }  /* the whole slice in one block */ \
+    if (xreg && pp.spw <= 4) TG_P16K(CPG_, false, true, 4);  /* the whole slice in one block */ \
     /* (groups of 32 at innerKTiles 4 with slices longer than a block: 84 ... 128 bytes of scratch -- not instantiated, the LDS path) */ \
     if constexpr (!(CPG_ == 1 && I == 4)) {                       \
-      if (xreg) { TG_P16K(CPG_, false, true, 2); break; }         \
+      if (xreg) TG_P16K(CPG_, false, true, 2);                    \
     }                                                             \
     TG_P16K(CPG_, false, false, 4);                               \
   } while (0)
@@ -94,7 +90,6 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
 #undef TG_P16K
 #undef TG_P16KX
 #undef TG_P16
-  return launch_status();
   }
 }
 
@@ -106,13 +101,13 @@ int launch_pair16(const GemmParams& p, int64_t batch, hipStream_t st) {
                                   // 64-row item: 12.3 / 12.4 / 12.6 / - / 13.2 / 13.7 / - / 19.4 (profiles/r05_ab_p16_loop.txt, r05_p16_loop_sweep.txt)
 #endif
 template <typename DT>
-int launch_pair16_loop(const GemmParams& p, int64_t batch, hipStream_t st) {
-  if (batch != 1 || p.m < TG_P16_XREG_MIN_M || p.m > 16 || p.k != 4096 || p.ksuper != 64 || (p.epilogue && (p.epilogue != TG_EPI_SWIGLU || p.bias || p.wrows % 16 != 0)) || p.x_tc || p.y_tc ||
+int launch_pair16_loop(const GemmParams& p) {
+  if (p.batch != 1 || p.m < TG_P16_XREG_MIN_M || p.m > 16 || p.k != 4096 || p.ksuper != 64 || (p.epilogue && (p.epilogue != TG_EPI_SWIGLU || p.bias || p.wrows % 16 != 0)) || p.x_tc || p.y_tc ||
       p.qtype == TG_Q_MX4)
     return TG_PAIR_NA;
   if (p.norm_w && p.gshift == 5) return TG_PAIR_NA;  // (groups of 32 with the fused norm: not instantiated, see the kernel)
   const int tiles = (p.wrows + 15) / 16;
-  const int cus = p.dry ? 256 : cu_count();
+  const int cus = plan_cu_count(p);
   if (tiles <= cus) return TG_PAIR_NA;  // (one tile per workgroup: w4_gemm_pair16_kernel)
   const int per = (tiles + cus - 1) / cus;
   if (per > TG_P16_LOOP_MAX_TILES || per > 32) return TG_PAIR_NA;
@@ -125,36 +120,28 @@ int launch_pair16_loop(const GemmParams& p, int64_t batch, hipStream_t st) {
   const unsigned lds = (unsigned)pp.lds_nrm + 16u * 16u * 4u;
   if (p.dry) return TG_PLAN_PAIR;
   const int g = 1 << p.gshift;
-#define TG_P16L(CPG_, NORM_)                                                  \
-  do {                                                                        \
-    constexpr auto kern = w4_gemm_pair16_loop_kernel<DT, CPG_, NORM_>;        \
-    const int prc = prepare_lds_kernel<kern>();                               \
-    if (prc != 0) return prc;                                                 \
-    hipLaunchKernelGGL(kern, dim3((unsigned)cus), dim3(1024), lds, st, pp);   \
-  } while (0)
+#define TG_P16L(CPG_, NORM_) return launch_lds_kernel<w4_gemm_pair16_loop_kernel<DT, CPG_, NORM_>>(dim3((unsigned)cus), dim3(1024), lds, p.st, pp, false)
   if (p.norm_w) {
     if (g == 64) TG_P16L(2, true);
-    else if (g == 128) TG_P16L(4, true);
-    else TG_P16L(8, true);
-  } else {
-    if (g == 32) TG_P16L(1, false);
-    else if (g == 64) TG_P16L(2, false);
-    else if (g == 128) TG_P16L(4, false);
-    else TG_P16L(8, false);
+    if (g == 128) TG_P16L(4, true);
+    TG_P16L(8, true);
   }
+  if (g == 32) TG_P16L(1, false);
+  if (g == 64) TG_P16L(2, false);
+  if (g == 128) TG_P16L(4, false);
+  TG_P16L(8, false);
 #undef TG_P16L
-  return launch_status();
 }
 
 template <typename DT, int I>
-int p16_q(bool qmx, const GemmParams& p, int64_t batch, hipStream_t st) {
-  return qmx ? launch_pair16<DT, I, true>(p, batch, st) : launch_pair16<DT, I, false>(p, batch, st);
+int p16_q(const GemmParams& p) {
+  return p.qmx ? launch_pair16<DT, I, true>(p) : launch_pair16<DT, I, false>(p);
 }
 template <typename DT>
-int p16_i(int I, bool qmx, const GemmParams& p, int64_t batch, hipStream_t st) {
+int p16_i(const GemmParams& p) {
   // (innerKTiles 8: every instantiation compiled with 76 ... 308 bytes of scratch per lane at the 128-VGPR budget of a 1024-thread
   //  workgroup -- not instantiated; those layers take the streaming kernels)
-  return I == 2 ? p16_q<DT, 2>(qmx, p, batch, st) : I == 4 ? p16_q<DT, 4>(qmx, p, batch, st) : (int)TG_PAIR_NA;
+  return p.inner == 2 ? p16_q<DT, 2>(p) : p.inner == 4 ? p16_q<DT, 4>(p) : (int)TG_PAIR_NA;
 }
 }  // namespace
 #if GEMV_TRACE
@@ -164,10 +151,8 @@ extern "C" TG_API void tg_dev_p16_trace(unsigned long long* buf, int slots) {
   g_p16_launch = 0;
 }
 #endif
-int tgx::pair16_loop(int dt, int I, bool qmx, const GemmParams& p, int64_t batch, hipStream_t st) {
-  if (I != 4 || qmx) return TG_PAIR_NA;
-  return dt == TG_BF16 ? launch_pair16_loop<BF16>(p, batch, st) : launch_pair16_loop<F16>(p, batch, st);
+int tgx::pair16_loop(const GemmParams& p) {
+  if (p.inner != 4 || p.qmx) return TG_PAIR_NA;
+  return p.dt == TG_BF16 ? launch_pair16_loop<BF16>(p) : launch_pair16_loop<F16>(p);
 }
-int tgx::pair16(int dt, int I, bool qmx, const GemmParams& p, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? p16_i<BF16>(I, qmx, p, batch, st) : p16_i<F16>(I, qmx, p, batch, st);
-}
+int tgx::pair16(const GemmParams& p) { return p.dt == TG_BF16 ? p16_i<BF16>(p) : p16_i<F16>(p); }

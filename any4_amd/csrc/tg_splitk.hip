@@ -3,30 +3,33 @@
 namespace {
 #include "w4_gemm.cuh"
 template <typename DT, bool LAYOUT_A, int CANON, bool QMX>
-int go(int waves, const GemmParams& p, dim3 grid, hipStream_t st) {
-  if (waves == 16) hipLaunchKernelGGL((w4_gemm_kernel<DT, LAYOUT_A, CANON, QMX, 16, 2, 4>), grid, dim3(16 * 64), 0, st, p);
-  else hipLaunchKernelGGL((w4_gemm_kernel<DT, LAYOUT_A, CANON, QMX, 8, 2, 4>), grid, dim3(8 * 64), 0, st, p);
+int go(const GemmParams& p, int waves, int splitk) {
+  const int tpb = waves / splitk;
+  const dim3 grid((unsigned)((p.rowtiles + tpb - 1) / tpb), (unsigned)coltiles(p), (unsigned)p.batch);
+  const SplitKParams kp = splitk_params(p, splitk);
+  if (waves == 16) hipLaunchKernelGGL((w4_gemm_kernel<DT, LAYOUT_A, CANON, QMX, 16, 2, 4>), grid, dim3(16 * 64), 0, p.st, kp);
+  else hipLaunchKernelGGL((w4_gemm_kernel<DT, LAYOUT_A, CANON, QMX, 8, 2, 4>), grid, dim3(8 * 64), 0, p.st, kp);
   return launch_status();
 }
 template <typename DT, bool LAYOUT_A, int CANON>
-int go_q(bool qmx, int waves, const GemmParams& p, dim3 grid, hipStream_t st) {
+int go_q(const GemmParams& p, int waves, int splitk) {
   if constexpr (!std::is_same<DT, BF16>::value) {
-    if (qmx) return TG_E_DTYPE;
-    return go<DT, LAYOUT_A, CANON, false>(waves, p, grid, st);
+    if (p.qmx) return TG_E_DTYPE;
+    return go<DT, LAYOUT_A, CANON, false>(p, waves, splitk);
   } else {
-    return qmx ? go<DT, LAYOUT_A, CANON, true>(waves, p, grid, st) : go<DT, LAYOUT_A, CANON, false>(waves, p, grid, st);
+    return p.qmx ? go<DT, LAYOUT_A, CANON, true>(p, waves, splitk) : go<DT, LAYOUT_A, CANON, false>(p, waves, splitk);
   }
 }
 template <typename DT, bool LAYOUT_A>
-int go_c(int canon, bool qmx, int waves, const GemmParams& p, dim3 grid, hipStream_t st) {
-  switch (canon) {
-    case CANON_NONE: return go_q<DT, LAYOUT_A, CANON_NONE>(qmx, waves, p, grid, st);
-    case CANON_PAIR: return go_q<DT, LAYOUT_A, CANON_PAIR>(qmx, waves, p, grid, st);
-    default: return go_q<DT, LAYOUT_A, CANON_QUAD>(qmx, waves, p, grid, st);
+int go_c(const GemmParams& p, int waves, int splitk) {
+  switch (words_per_lane(p)) {  // (the in-register transpose of the packed words)
+    case 1: return go_q<DT, LAYOUT_A, CANON_NONE>(p, waves, splitk);
+    case 2: return go_q<DT, LAYOUT_A, CANON_PAIR>(p, waves, splitk);
+    default: return go_q<DT, LAYOUT_A, CANON_QUAD>(p, waves, splitk);
   }
 }
 }  // namespace
-int tgx::splitk(int dt, bool layout_a, int canon, bool qmx, int waves, const GemmParams& p, dim3 grid, hipStream_t st) {
-  if (dt == TG_BF16) return layout_a ? go_c<BF16, true>(canon, qmx, waves, p, grid, st) : go_c<BF16, false>(canon, qmx, waves, p, grid, st);
-  return layout_a ? go_c<F16, true>(canon, qmx, waves, p, grid, st) : go_c<F16, false>(canon, qmx, waves, p, grid, st);
+int tgx::splitk(const GemmParams& p, int waves, int splitk) {
+  if (p.dt == TG_BF16) return !p.on_right ? go_c<BF16, true>(p, waves, splitk) : go_c<BF16, false>(p, waves, splitk);
+  return !p.on_right ? go_c<F16, true>(p, waves, splitk) : go_c<F16, false>(p, waves, splitk);
 }

@@ -30,7 +30,7 @@ inline unsigned stream_lds_bytes(int sw, int mrows, int sk, bool privx = false) 
 }
 
 template <typename DT, bool LAYOUT_A, int WPL, bool QMX, int SW, bool privx = (SW == 1)>
-int launch_stream_sw(StreamParams& sp, int sk, int64_t coltiles, int64_t batch, hipStream_t st) {
+int launch_stream_sw(const GemmParams& p, StreamParams& sp, int sk) {
   constexpr int UNIT = LAYOUT_A ? 64 : 128;
   constexpr unsigned NR = 1u;
   const int nunits = (sp.k + UNIT - 1) / UNIT;
@@ -52,24 +52,21 @@ int launch_stream_sw(StreamParams& sp, int sk, int64_t coltiles, int64_t batch, 
   const int xl = pieces <= nstage ? 1 : (pieces <= 2 * nstage ? 2 : 4);
   const unsigned lds = stream_lds_bytes<LAYOUT_A>(SW, mrows, sk, privx);
   const int tpb = SW / sk;
-  dim3 grid((unsigned)((sp.rowtiles + tpb - 1) / tpb), (unsigned)coltiles, (unsigned)batch);
-#define TG_LAUNCH_STREAM_LK(XL, LK_)                                                                      \
-  do {                                                                                                    \
-    constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, false, LK_>; \
-    if (sp.dry) return TG_PLAN_STREAM;                                                                    \
-    const int prc = prepare_lds_kernel<kern>();                                                           \
-    if (prc != 0) return prc;                                                                             \
-    hipLaunchKernelGGL(kern, grid, dim3(SW * 64), lds, st, sp);                                           \
-  } while (0)
-#define TG_LAUNCH_STREAM(XL)                                                                              \
-  do {                                                                                                    \
-    if constexpr (!LAYOUT_A && !privx) {                                                                  \
-      if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15) { TG_LAUNCH_STREAM_LK(XL, 1); break; }                  \
-    }                                                                                                     \
-    TG_LAUNCH_STREAM_LK(XL, 0);                                                                           \
-  } while (0)
+  const dim3 grid((unsigned)((sp.rowtiles + tpb - 1) / tpb), (unsigned)coltiles(p), (unsigned)p.batch);
   if constexpr (privx && SW > 1) {
     if (xl != 1) return TG_E_SHAPE;  // private slabs with split-K are only instantiated for one piece per lane (m = 1)
+  }
+  if (p.dry) return TG_PLAN_STREAM;
+#define TG_LAUNCH_STREAM_LK(XL, LK_) \
+  return launch_lds_kernel<w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, false, LK_>>(grid, dim3(SW * 64), lds, p.st, sp, false)
+#define TG_LAUNCH_STREAM(XL)                                                               \
+  do {                                                                                     \
+    if constexpr (!LAYOUT_A && !privx) {                                                   \
+      if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15) TG_LAUNCH_STREAM_LK(XL, 1);              \
+    }                                                                                      \
+    TG_LAUNCH_STREAM_LK(XL, 0);                                                            \
+  } while (0)
+  if constexpr (privx && SW > 1) {
     TG_LAUNCH_STREAM(1);
   } else if constexpr (SW == 1) {
     if (xl == 1) TG_LAUNCH_STREAM(1);
@@ -81,37 +78,27 @@ int launch_stream_sw(StreamParams& sp, int sk, int64_t coltiles, int64_t batch, 
   }
 #undef TG_LAUNCH_STREAM
 #undef TG_LAUNCH_STREAM_LK
-  return launch_status();
 }
 
 // Resident-X launch: 16-wave workgroups, the whole [mrows][k] activation block staged once per workgroup.
 template <typename DT, bool LAYOUT_A, int WPL, bool QMX>
-int launch_stream_xres(StreamParams& sp, int64_t coltiles, int64_t batch, unsigned lds, hipStream_t st) {
+int launch_stream_xres(const GemmParams& p, StreamParams& sp, unsigned lds) {
   // one workgroup walks up to 4 consecutive groups of 16 tiles of its layer (X staged once, tile-granularity tail
   // amortised) as long as that leaves at least two workgroups per CU
   int tpw = 4;
-  while (tpw > 1 && ((sp.rowtiles + 16 * tpw - 1) / (16 * tpw)) * coltiles * batch < 512) tpw >>= 1;
+  while (tpw > 1 && ((sp.rowtiles + 16 * tpw - 1) / (16 * tpw)) * coltiles(p) * p.batch < 512) tpw >>= 1;
   sp.tiles_per_wave = tpw;
-  if (sp.dry) return TG_PLAN_STREAM;
-  dim3 grid((unsigned)((sp.rowtiles + 16 * tpw - 1) / (16 * tpw)), (unsigned)coltiles, (unsigned)batch);
+  if (p.dry) return TG_PLAN_STREAM;
+  const dim3 grid((unsigned)((sp.rowtiles + 16 * tpw - 1) / (16 * tpw)), (unsigned)coltiles(p), (unsigned)p.batch);
   if constexpr (!LAYOUT_A) {
-    if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15) {
-      constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 1>;
-      const int prc = prepare_lds_kernel<kern>();
-      if (prc != 0) return prc;
-      hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lds, st, sp);
-      return launch_status();
-    }
+    if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15)
+      return launch_lds_kernel<w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 1>>(grid, dim3(16 * 64), lds, p.st, sp, false);
   }
-  constexpr auto kern = w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 0>;
-  const int prc = prepare_lds_kernel<kern>();
-  if (prc != 0) return prc;
-  hipLaunchKernelGGL(kern, grid, dim3(16 * 64), lds, st, sp);
-  return launch_status();
+  return launch_lds_kernel<w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, 16, STREAM_MINW, 1, false, true, 0>>(grid, dim3(16 * 64), lds, p.st, sp, false);
 }
 
 template <typename DT, bool LAYOUT_A, int WPL, bool QMX>
-int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
+int launch_stream(const GemmParams& p) {
   constexpr int UNIT = LAYOUT_A ? 64 : 128;
   constexpr int RPW = 16;  // weight rows per wave
   StreamParams sp;
@@ -122,7 +109,7 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
   const int nunits = (p.k + UNIT - 1) / UNIT;
   const int upg = (1 << p.gshift) / UNIT;
   // split-K: aim for at least two rounds of 16 waves on every CU; the X slab limits act rows * splitk to 16
-  const int64_t wave_tiles = (int64_t)sp.rowtiles * coltiles * batch;
+  const int64_t wave_tiles = (int64_t)sp.rowtiles * coltiles(p) * p.batch;
   int sk = 1;
   // (m = 1, private slabs: one round of 16 waves per CU is enough -- measured on the Llama-3-8B shapes)
   const int64_t want = mrows == 1 ? 256 * 16 : 2 * 256 * 16;
@@ -130,10 +117,10 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
   // m == 1: every wave stages its own X slab (no barrier in the main loop); a workgroup is the sk waves of one tile
   if (mrows == 1) {
     switch (sk) {
-      case 1: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 1>(sp, 1, coltiles, batch, st);
-      case 2: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 2, true>(sp, 2, coltiles, batch, st);
-      case 4: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 4, true>(sp, 4, coltiles, batch, st);
-      default: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8, true>(sp, 8, coltiles, batch, st);
+      case 1: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 1>(p, sp, 1);
+      case 2: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 2, true>(p, sp, 2);
+      case 4: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 4, true>(p, sp, 4);
+      default: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8, true>(p, sp, 8);
     }
   }
   // m >= 2, one tile per wave: keep the whole activation block resident in LDS when it fits next to 16 lookup
@@ -147,37 +134,33 @@ int launch_stream(const GemmParams& p, int64_t coltiles, int64_t batch, hipStrea
     if (lds <= 160u * 1024u) {
       sp.splitk = 1; sp.sk_shift = 0; sp.units_per_lane = nu; sp.upg_mask = upg - 1;
       sp.xslab_bytes = (int32_t)xrow; sp.red_off = 0;
-      return launch_stream_xres<DT, LAYOUT_A, WPL, QMX>(sp, coltiles, batch, lds, st);
+      return launch_stream_xres<DT, LAYOUT_A, WPL, QMX>(p, sp, lds);
     }
   }
   // otherwise 4-wave workgroups while their LDS footprint lets 16 waves live on a CU and the X slab is small;
   // X slabs of 8 KiB or more per unit (Bint4: m >= 8, Aint4: m = 16): 8-wave workgroups halve the staging work per wave
   const int sk4 = sk < 4 ? sk : 4;
   if (mrows * UNIT < 1024 && 160u * 1024u / stream_lds_bytes<LAYOUT_A>(4, mrows, sk4) >= 4)
-    return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 4>(sp, sk4, coltiles, batch, st);
-  return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8>(sp, sk, coltiles, batch, st);
+    return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 4>(p, sp, sk4);
+  return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8>(p, sp, sk);
 }
 
 template <typename DT, bool LAYOUT_A, int WPL>
-int stream_q(bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
+int stream_q(const GemmParams& p) {
   if constexpr (!std::is_same<DT, BF16>::value) {
-    if (qmx) return TG_E_DTYPE;
-    return launch_stream<DT, LAYOUT_A, WPL, false>(p, coltiles, batch, st);
+    if (p.qmx) return TG_E_DTYPE;
+    return launch_stream<DT, LAYOUT_A, WPL, false>(p);
   } else {
-    return qmx ? launch_stream<DT, LAYOUT_A, WPL, true>(p, coltiles, batch, st) : launch_stream<DT, LAYOUT_A, WPL, false>(p, coltiles, batch, st);
+    return p.qmx ? launch_stream<DT, LAYOUT_A, WPL, true>(p) : launch_stream<DT, LAYOUT_A, WPL, false>(p);
   }
 }
 template <typename DT, bool LAYOUT_A>
-int stream_w(int wpl, bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
-  switch (wpl) {
-    case 1: return stream_q<DT, LAYOUT_A, 1>(qmx, p, coltiles, batch, st);
-    case 2: return stream_q<DT, LAYOUT_A, 2>(qmx, p, coltiles, batch, st);
-    default: return stream_q<DT, LAYOUT_A, 4>(qmx, p, coltiles, batch, st);
+int stream_w(const GemmParams& p) {
+  switch (words_per_lane(p)) {
+    case 1: return stream_q<DT, LAYOUT_A, 1>(p);
+    case 2: return stream_q<DT, LAYOUT_A, 2>(p);
+    default: return stream_q<DT, LAYOUT_A, 4>(p);
   }
 }
 }  // namespace
-namespace tgx {
-int TG_TU_FN(bool layout_a, int wpl, bool qmx, const GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
-  return layout_a ? stream_w<TG_TU_DT, true>(wpl, qmx, p, coltiles, batch, st) : stream_w<TG_TU_DT, false>(wpl, qmx, p, coltiles, batch, st);
-}
-}  // namespace tgx
+int tgx::TG_TU_FN(const GemmParams& p) { return !p.on_right ? stream_w<TG_TU_DT, true>(p) : stream_w<TG_TU_DT, false>(p); }

@@ -20,7 +20,7 @@ struct XrWindow {
   int64_t stride_y32;
 };
 template <typename DT, int I, bool QMX, int NCH, bool PK = false>
-int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindow* win = nullptr) {
+int launch_pair_xr_n(const GemmParams& p, const XrWindow* win = nullptr) {
   if constexpr (I != 4 || (QMX && (NCH != 16 || !std::is_same<DT, BF16>::value))) return TG_PAIR_NA;  // (mx4: bf16, k = 4096)
   else {
 #ifdef TG_DEV_MIN
@@ -42,7 +42,7 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   XrParams xp;
   copy_call(xp, p);  // (x too: no pre-pass, no workspace -- the kernel arranges the activations itself)
   xp.rblocks = (p.wrows + 63) / 64;
-  const int64_t items = (int64_t)xp.rblocks * batch;
+  const int64_t items = (int64_t)xp.rblocks * p.batch;
 #ifndef TG_XR_MIN_ITEMS_PER_WG
 #define TG_XR_MIN_ITEMS_PER_WG 2  // work items per workgroup from which this kernel takes a launch (developer builds: 1 for one large layer per launch)
 #endif
@@ -62,8 +62,8 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   // (... and up to eight 16-row tiles per CU -- 32768 rows on 256 CUs -- w4_gemm_pair16_loop_kernel is faster or equal where it applies:
   //  row-major operands, not mx4: 5120 / 8192 / 12288 / 16384 / 28672 rows at m = 16 8.5 / 9.0 / 10.9 / 13.1 / 19.5 us against 12.3 / 12.4 / 12.9 /
   //  13.7 / 19.4 here; this route keeps fragment-order operands, mx4 and longer layers)
-  const bool p16_loop = !p.x_tc && !p.y_tc && !QMX && I == 4 && p.m >= 5 && (int64_t)((p.wrows + 15) / 16) <= 8 * (int64_t)(p.dry ? 256 : cu_count());
-  const bool single = batch == 1 && NCH == 16 && !PK && !win && !p16_loop &&
+  const bool p16_loop = !p.x_tc && !p.y_tc && !QMX && I == 4 && p.m >= 5 && (int64_t)((p.wrows + 15) / 16) <= 8 * (int64_t)plan_cu_count(p);
+  const bool single = p.batch == 1 && NCH == 16 && !PK && !win && !p16_loop &&
                       ((p.m >= 9 && items >= TG_XR_SINGLE_MIN_ITEMS) || (p.m >= 5 && items >= TG_XR_SINGLE_MIN_ITEMS_M8));
   if (items > INT32_MAX) return TG_PAIR_NA;
   if (!single && items < TG_XR_MIN_ITEMS_PER_WG * 256) return TG_PAIR_NA;
@@ -72,7 +72,6 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   // two tables, the activation sums (mx4: the partial sums only)
   const unsigned lds = QMX ? 32768u : (unsigned)xp.lds_xs + (unsigned)(win ? win->ngroups : p.ngroups) * 64u;
   if (lds > 160u * 1024u) return TG_PAIR_NA;
-  p.ws_need = 0;
   xp.y_tiles = (p.wrows + 15) / 16;
   xp.y_f32 = 0;
   if (win) {
@@ -84,31 +83,23 @@ int launch_pair_xr_n(GemmParams& p, int64_t batch, hipStream_t st, const XrWindo
   unsigned wgs = (unsigned)cu_count();  // one 8-wave workgroup per compute unit, whatever the part has
   if (single) wgs = items < (int64_t)wgs ? (unsigned)items : wgs;
   else if (items < TG_XR_MIN_ITEMS_PER_WG * (int64_t)wgs) return TG_PAIR_NA;
-#define TG_XR_LAUNCH(CPG_)                                                  \
-  do {                                                                      \
-    constexpr auto kern = w4_gemm_xr_kernel<DT, I, NCH, CPG_, (((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R), false, PK>; \
-    const int prc = prepare_lds_kernel<kern>();                             \
-    if (prc != 0) return prc == TG_E_INTERNAL ? prc : TG_PAIR_NA; /* (a part with less LDS: the older kernels take over) */ \
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3(512), lds, st, xp);            \
-  } while (0)
+  // (a failed preparation -- a part with less LDS: the older kernels take over)
+#define TG_XR_LAUNCH(CPG_) \
+  return launch_lds_kernel<w4_gemm_xr_kernel<DT, I, NCH, CPG_, (((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R), false, PK>>(dim3(wgs), dim3(512), lds, p.st, xp, true)
   if constexpr (QMX) {
-    constexpr auto kern = w4_gemm_xr_kernel<DT, I, NCH, 1, TG_XR_RMX, true>;
-    const int prc = prepare_lds_kernel<kern>();
-    if (prc != 0) return prc == TG_E_INTERNAL ? prc : TG_PAIR_NA;
-    hipLaunchKernelGGL(kern, dim3(wgs), dim3(512), lds, st, xp);
+    return launch_lds_kernel<w4_gemm_xr_kernel<DT, I, NCH, 1, TG_XR_RMX, true>>(dim3(wgs), dim3(512), lds, p.st, xp, true);
   } else {
 #ifdef TG_DEV_MIN
   TG_XR_LAUNCH(4);
 #else
   if (cpg == 1) TG_XR_LAUNCH(1);
-  else if (cpg == 2) TG_XR_LAUNCH(2);
-  else if (cpg == 4) TG_XR_LAUNCH(4);
-  else if constexpr (NCH % 8 == 0) TG_XR_LAUNCH(8);
-  else return TG_PAIR_NA;  // (a wave's slice must hold whole groups)
+  if (cpg == 2) TG_XR_LAUNCH(2);
+  if (cpg == 4) TG_XR_LAUNCH(4);
+  if constexpr (NCH % 8 == 0) TG_XR_LAUNCH(8);
+  return TG_PAIR_NA;  // (a wave's slice must hold whole groups)
 #endif
   }
 #undef TG_XR_LAUNCH
-  return launch_status();
 #ifdef TG_DEV_MIN
   }
 #endif
@@ -147,7 +138,7 @@ __global__ void __launch_bounds__(256) xr_window_sum_kernel(const float* __restr
 // f32 partial sums in the caller's workspace (NP x batch x m x wrows x 4 bytes: 3.4 % of the weight bytes at m = 16), one small
 // kernel adds the windows in order.  The 16x16x32 workspace kernel this replaces re-reads the activations per work item: 45 %.
 template <typename DT, int I, int... NCHS>
-int launch_pair_xr_windows(GemmParams& p, int64_t batch, hipStream_t st) {
+int launch_pair_xr_windows(GemmParams& p) {
   if constexpr (I != 4) return TG_PAIR_NA;
   else {
   constexpr int NP = sizeof...(NCHS);
@@ -159,9 +150,9 @@ int launch_pair_xr_windows(GemmParams& p, int64_t batch, hipStream_t st) {
     ktot += 256 * nch[i];
   }
   if (p.k != ktot || p.x_tc || p.y_tc || p.m < 9 || p.m > 16 || p.wrows % 64 != 0 || p.norm_w || p.epilogue) return TG_PAIR_NA;
-  const int64_t part_elems = batch * p.m * (int64_t)p.wrows;
+  const int64_t part_elems = p.batch * p.m * (int64_t)p.wrows;
   const int64_t need = NP * part_elems * 4;
-  if (!p.ws_query && (p.ws == nullptr || p.ws_bytes < need)) return TG_PAIR_NA;  // (the caller did not bring the workspace: the older kernels)
+  if (!has_workspace(p, need)) return TG_PAIR_NA;  // (the older kernels)
   XrWindow win;
   win.stride_y32 = (int64_t)p.m * p.wrows * 4;
   int k0 = 0, part = 0, rc_all = 0;
@@ -174,71 +165,65 @@ int launch_pair_xr_windows(GemmParams& p, int64_t batch, hipStream_t st) {
     win.x_off = (int64_t)k0 * 2;
     win.q_off = (int64_t)(k0 / g) * p.wrows * 4;
     win.y32 = p.ws + part * part_elems * 4;
-    const int rc = launch_pair_xr_n<DT, I, false, NCH>(p, batch, st, &win);
+    const int rc = launch_pair_xr_n<DT, I, false, NCH>(p, &win);
     if (rc != 0) rc_all = rc;  // (TG_PAIR_NA, a TG_E_* code, a hipError_t, or TG_PLAN_PAIR_XR from a dry run)
     k0 += kw;
     ++part;
   };
-  // every window must have a kernel BEFORE the first one is launched (a dry pass: validation only)
-  const auto dry0 = p.dry;
-  p.dry = 1;
+  // every window must have a kernel BEFORE the first one is launched (a dry pass over a copy of the call: validation only)
+  GemmParams plan = p;
+  plan.dry = 1;
   int planned = 0;
   auto check = [&](auto NCH_) {
     XrWindow w0 = win;
     w0.ngroups = 256 * decltype(NCH_)::value / g;
     w0.w_off = w0.x_off = w0.q_off = 0;
     w0.y32 = p.ws;
-    planned += launch_pair_xr_n<DT, I, false, decltype(NCH_)::value>(p, batch, st, &w0) == TG_PLAN_PAIR_XR;
+    planned += launch_pair_xr_n<DT, I, false, decltype(NCH_)::value>(plan, &w0) == TG_PLAN_PAIR_XR;
   };
   (check(std::integral_constant<int, NCHS>{}), ...);
-  p.dry = dry0;
-  if (planned != NP) { p.ws_need = 0; return TG_PAIR_NA; }
-  if (p.dry) { p.ws_need = need; return TG_PLAN_PAIR_XR; }
-  (one(std::integral_constant<int, NCHS>{}), ...);
-  if (rc_all != 0) {
-    p.ws_need = 0;
-    return rc_all;
-  }
+  if (planned != NP) return TG_PAIR_NA;
   p.ws_need = need;
+  if (p.dry) return TG_PLAN_PAIR_XR;
+  (one(std::integral_constant<int, NCHS>{}), ...);
+  if (rc_all != 0) return rc_all;
   const int64_t pairs = (int64_t)p.m * (p.wrows / 2);
-  hipLaunchKernelGGL((xr_window_sum_kernel<DT, NP>), dim3((unsigned)((pairs + 255) / 256), (unsigned)batch), dim3(256), 0, st,
+  hipLaunchKernelGGL((xr_window_sum_kernel<DT, NP>), dim3((unsigned)((pairs + 255) / 256), (unsigned)p.batch), dim3(256), 0, p.st,
                      reinterpret_cast<const float*>(p.ws), part_elems, p.y, p.stride_y, p.bias, p.stride_bias, p.bias_row_stride, p.m, p.wrows, pairs);
   return launch_status();
   }
 }
 
 template <typename DT, int I, bool QMX>
-int launch_pair_xr(GemmParams& p, int64_t batch, hipStream_t st) {
-  if (p.k == 4096) return launch_pair_xr_n<DT, I, QMX, 16>(p, batch, st);
+int launch_pair_xr(GemmParams& p) {
+  if (p.k == 4096) return launch_pair_xr_n<DT, I, QMX, 16>(p);
   // k = 8192, 9 ... 16 rows: 128 registers of activations per lane leave room for two super-tiles in flight only -- faster than
   // the 16x16x32 workspace kernel it replaces (8192^2, m = 16: 62 vs 47-51 %).  Up to 8 rows: two chunks per register set (PK),
   // 64 registers, four super-tiles in flight like k = 4096
   if constexpr (!QMX) {
-    if (p.k == 8192 && p.m <= 8) return launch_pair_xr_n<DT, I, QMX, 32, true>(p, batch, st);
+    if (p.k == 8192 && p.m <= 8) return launch_pair_xr_n<DT, I, QMX, 32, true>(p);
   }
   // k = 8192 at 9 ... 16 rows as two k-windows of 4096 (the ring stays four deep) when the caller brings the workspace
   if constexpr (!QMX) {
     if (p.k == 8192 && p.m >= 9) {
-      const int rc = launch_pair_xr_windows<DT, I, 16, 16>(p, batch, st);
+      const int rc = launch_pair_xr_windows<DT, I, 16, 16>(p);
       if (rc != TG_PAIR_NA) return rc;
     }
   }
-  if (p.k == 8192 && p.m >= 9) return launch_pair_xr_n<DT, I, QMX, 32>(p, batch, st);
+  if (p.k == 8192 && p.m >= 9) return launch_pair_xr_n<DT, I, QMX, 32>(p);
   // k = 14336 (Llama-3-8B's down-projection) with at most 8 rows: 56 chunks per slice, packed: 112 activation registers, ring of two
   if constexpr (!QMX) {
     // (same box, 4096 x 14336 against the workspace variant of w4_gemm_pair_kernel: m = 8 67.9 -> 70.0 %, but m = 4 72.9 -> 69.1 and
     //  m = 2 76.5 -> 72.3, m = 6 71.1 -> 68.8 -- profiles/r05_ab_xr_k14336.txt: eight rows only)
-    if (p.k == 14336 && p.m == 8) return launch_pair_xr_n<DT, I, QMX, 56, true>(p, batch, st);
-    if (p.k == 14336 && p.m >= 9) return launch_pair_xr_windows<DT, I, TG_XR_WINDOWS_14336>(p, batch, st);
+    if (p.k == 14336 && p.m == 8) return launch_pair_xr_n<DT, I, QMX, 56, true>(p);
+    if (p.k == 14336 && p.m >= 9) return launch_pair_xr_windows<DT, I, TG_XR_WINDOWS_14336>(p);
   }
   return TG_PAIR_NA;
 }
 template <typename DT>
-int xr_i(int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  if (I != 4) return TG_PAIR_NA;
-  return qmx ? launch_pair_xr<DT, 4, true>(p, batch, st) : launch_pair_xr<DT, 4, false>(p, batch, st);
+int xr_i(GemmParams& p) {
+  if (p.inner != 4) return TG_PAIR_NA;
+  return p.qmx ? launch_pair_xr<DT, 4, true>(p) : launch_pair_xr<DT, 4, false>(p);
 }
 }  // namespace
-int tgx::pair_xr(int dt, int I, bool qmx, GemmParams& p, int64_t batch, hipStream_t st) {
-  return dt == TG_BF16 ? xr_i<BF16>(I, qmx, p, batch, st) : xr_i<F16>(I, qmx, p, batch, st);
-}
+int tgx::pair_xr(GemmParams& p) { return p.dt == TG_BF16 ? xr_i<BF16>(p) : xr_i<F16>(p); }

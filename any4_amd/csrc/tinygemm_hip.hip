@@ -41,7 +41,7 @@ namespace {
 // smallest split-K that still puts >= ~16 waves on every CU; a single small matrix (one tile per
 // CU) uses one 16-wave workgroup per tile with split-K 16.
 struct Geometry {
-  int waves, splitk, sk_shift;
+  int waves, splitk;
 };
 
 inline Geometry pick_geometry(int64_t rowtiles, int64_t coltiles, int64_t batch, int64_t nsteps) {
@@ -58,72 +58,63 @@ inline Geometry pick_geometry(int64_t rowtiles, int64_t coltiles, int64_t batch,
     g.splitk = sk;
   }
   while (g.splitk > 1 && g.splitk > nsteps) g.splitk >>= 1;
-  g.sk_shift = 0;
-  while ((1 << g.sk_shift) < g.splitk) ++g.sk_shift;
   return g;
 }
 
 
 template <typename DT, bool LAYOUT_A, int I>
-int launch_w8(GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
+int launch_w8(const GemmParams& p) {
   constexpr int WAVES = 8;
-  const int64_t tiles = (int64_t)p.rowtiles * coltiles * batch;
+  const int64_t tiles = (int64_t)p.rowtiles * coltiles(p) * p.batch;
   const int nsteps = (p.k / 16 + 3) / 4;
   int sk = 1;
   while (sk < WAVES && tiles * sk < 256 * 16 && sk * 2 <= nsteps) sk *= 2;
-  p.splitk = sk;
-  p.sk_shift = 0;
-  while ((1 << p.sk_shift) < sk) ++p.sk_shift;
   const int tpb = WAVES / sk;
-  dim3 grid((unsigned)((p.rowtiles + tpb - 1) / tpb), (unsigned)coltiles, (unsigned)batch);
-  hipLaunchKernelGGL((w8_gemm_kernel<DT, LAYOUT_A, I, WAVES>), grid, dim3(WAVES * 64), 0, st, p);
+  dim3 grid((unsigned)((p.rowtiles + tpb - 1) / tpb), (unsigned)coltiles(p), (unsigned)p.batch);
+  hipLaunchKernelGGL((w8_gemm_kernel<DT, LAYOUT_A, I, WAVES>), grid, dim3(WAVES * 64), 0, p.st, splitk_params(p, sk));
   return launch_status();
 }
 
 
+// The dispatcher's half of the workspace protocol: a family is offered the call with ws_need = 0, and assigns it only where it accepts.
+template <typename F>
+int offer(F& family, GemmParams& p) {
+  p.ws_need = 0;
+  return family(p);
+}
+
 // Dispatch of one validated 4-bit GEMM call to a kernel family (each family's launch path is its own translation unit, tg_common.cuh).
-// dt = TG_BF16 / TG_F16, canon = words per lane-quad of the packed layout (CANON_*), qmx = mx4.
-int launch_w4(int dt, bool LAYOUT_A, int canon, bool QMX, GemmParams& p, int64_t coltiles, int64_t batch, hipStream_t st) {
+int launch_w4(GemmParams& p) {
+  const bool LAYOUT_A = !p.on_right;
   const int KSTEP = LAYOUT_A ? 64 : 128;
-  const Geometry g = pick_geometry(p.rowtiles, coltiles, batch, (p.k + KSTEP - 1) / KSTEP);
-  p.splitk = g.splitk;
-  p.sk_shift = g.sk_shift;
-  const int tpb = g.waves / g.splitk;
-  dim3 grid((unsigned)((p.rowtiles + tpb - 1) / tpb), (unsigned)coltiles, (unsigned)batch);
-  // Streaming shapes go to the lane-owns-group kernel when the quantisation group covers at least one
-  // unit of its walk (Bint4: g >= 128, Aint4: g >= 64).
-  const int WPL = canon == CANON_NONE ? 1 : (canon == CANON_PAIR ? 2 : 4);
+  const Geometry g = pick_geometry(p.rowtiles, coltiles(p), p.batch, (p.k + KSTEP - 1) / KSTEP);
   // TG_NUM_FAST, weights on the B side: the pair-table kernel (group-scaled numerics) whenever its LDS plan fits
   // (mx4 in BOTH numerics: its dequantised weights, fp4 * 2^(e - 127), are exact 16-bit values however they are formed, so the
   //  pair-table kernels -- which convert them with v_cvt_scalef32_pk_bf16_fp4 -- ARE the reference arithmetic for it)
-  if (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA || QMX) {
+  if (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA || p.qmx) {
     int rc;
     if (!LAYOUT_A) {
       // one layer per launch with up to 4 activation rows (a decode step's GEMMs): its own kernel (w4_gemv.cuh)
-      rc = p.numerics == TG_NUM_FAST_MFMA ? (int)TG_PAIR_NA : tgx::gemv(dt, 2 * WPL, QMX, p, batch, st);  // (w4_gemv contracts with v_dot2)
+      rc = p.numerics == TG_NUM_FAST_MFMA ? (int)TG_PAIR_NA : offer(tgx::gemv, p);  // (w4_gemv contracts with v_dot2)
       if (rc != TG_PAIR_NA) return rc;
       // STACKED launches of one activation row in the default numerics: the contraction tg_m1_default_contraction() names
       // (TG_M1_DEFAULT_MFMA; TG_NUM_FAST_DOT2 / TG_NUM_FAST_MFMA pin either one for A/B runs -- p.dot2 is set by the entry point)
-      if (TG_M1_DEFAULT_MFMA && p.numerics == TG_NUM_FAST && p.m == 1 && !p.dot2 && !QMX) p.numerics = TG_NUM_FAST_MFMA;
-      rc = tgx::pair_xr(dt, 2 * WPL, QMX, p, batch, st);
+      if (TG_M1_DEFAULT_MFMA && p.numerics == TG_NUM_FAST && p.m == 1 && !p.dot2 && !p.qmx) p.numerics = TG_NUM_FAST_MFMA;
+      rc = offer(tgx::pair_xr, p);
       if (rc != TG_PAIR_NA) return rc;
-      p.ws_need = 0;
       // one layer per launch with more 16-row tiles than CUs (5 ... 16 rows, k = 4096): in front of the persistent kernel, which would
       // take it from 192 64-row items on (12288 rows: 15.6 us per graph node)
-      rc = tgx::pair16_loop(dt, 2 * WPL, QMX, p, batch, st);
+      rc = offer(tgx::pair16_loop, p);
       if (rc != TG_PAIR_NA) return rc;
     }
-    if (LAYOUT_A) rc = tgx::pair_a(dt, WPL, QMX, p, batch, st);
-    else rc = tgx::pair(dt, 2 * WPL, QMX, p, batch, st);
+    rc = LAYOUT_A ? offer(tgx::pair_a, p) : offer(tgx::pair, p);
     if (rc != TG_PAIR_NA) return rc;
-    p.ws_need = 0;
     if (!LAYOUT_A) {
       if (p.m > 8) {
-        rc = tgx::pair_b16(dt, 2 * WPL, QMX, p, batch, st);
+        rc = offer(tgx::pair_b16, p);
         if (rc != TG_PAIR_NA) return rc;
-        p.ws_need = 0;
       }
-      rc = tgx::pair16(dt, 2 * WPL, QMX, p, batch, st);
+      rc = offer(tgx::pair16, p);
       if (rc != TG_PAIR_NA) return rc;
     }
   }
@@ -132,12 +123,12 @@ int launch_w4(int dt, bool LAYOUT_A, int canon, bool QMX, GemmParams& p, int64_t
 #ifdef TG_DEV_MIN  // developer A/B builds carry the pair-table kernels only (a third of the build time)
   return TG_E_SHAPE;
 #else
+  // Streaming shapes go to the lane-owns-group kernel when the quantisation group covers at least one
+  // unit of its walk (Bint4: g >= 128, Aint4: g >= 64).
   // m = 1 always streams: with private X slabs its split-K variants beat the latency kernel down to one matrix
-  if ((g.waves == 8 || p.m == 1) && (1 << p.gshift) >= (LAYOUT_A ? 64 : 128)) {
-    return tgx::stream(dt, LAYOUT_A, WPL, QMX, p, coltiles, batch, st);
-  }
+  if ((g.waves == 8 || p.m == 1) && (1 << p.gshift) >= (LAYOUT_A ? 64 : 128)) return tgx::stream(p);
   if (p.dry) return TG_PLAN_SPLITK;
-  return tgx::splitk(dt, LAYOUT_A, canon, QMX, g.waves, p, grid, st);
+  return tgx::splitk(p, g.waves, g.splitk);
 #endif
 }
 
@@ -392,7 +383,7 @@ static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
   if (a->bias && misaligned(a->bias, 8)) return TG_E_ALIGN;          // (dx: no bias got this far)
   switch (e) {
     case ENTRY_W4: {
-      const bool on_right = right || a->w_format == TG_WFMT_ROWS;    // (gemm_layout)
+      const bool on_right = right || a->w_format == TG_WFMT_ROWS;    // (make_params)
       if (bad_numerics(a)) return TG_E_SHAPE;
       if (bad_workspace(a)) return TG_E_ALIGN;
       if (!(a->x_layout == TG_LAYOUT_RM || a->x_layout == TG_LAYOUT_TC_A) || !(a->y_layout == TG_LAYOUT_RM || a->y_layout == TG_LAYOUT_TC_A)) return TG_E_LAYOUT;
@@ -423,22 +414,11 @@ static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
   return TG_E_INTERNAL;
 }
 
-// The packed words a validated 4-bit call holds.  TG_WFMT_ROWS: the A-shaped tensor holds Bint4 words (rows padded to 16), so from
-// here on this IS a weights-on-the-right call -- both sides produce [activation row][weight row] (TinyGemm_int4.cu:450-456).
-struct PackedLayout {
-  bool on_right;
-  int I;  // innerKTiles
-};
-static PackedLayout gemm_layout(const tg_w4_gemm* a) {
-  if (a->w_format == TG_WFMT_ROWS) return {true, a->k % 64 == 0 ? 4 : 2};
-  return {a->w_on_right != 0, a->inner_k_tiles};
-}
-
 // GemmParams of a validated call.  dry: 0 launch, 1 report the kernel family, 2 report the workspace the fastest kernel wants.
-static GemmParams make_params(const tg_w4_gemm* a, PackedLayout l, int dry) {
+static GemmParams make_params(const tg_w4_gemm* a, GemmEntry e, tg_stream_t stream, int dry) {
   const bool batched = a->batch > 1;
   GemmParams p;
-  memset(&p, 0, sizeof p);   // (splitk / sk_shift: the launch path's; ws_need: the planner's answer; dbg: always 0)
+  memset(&p, 0, sizeof p);   // (ws_need: the planner's answer)
   p.x = (const char*)a->x;
   p.w = (const char*)a->w;
   p.qinfo = (const char*)a->qinfo;
@@ -447,12 +427,22 @@ static GemmParams make_params(const tg_w4_gemm* a, PackedLayout l, int dry) {
   p.m = (int32_t)a->m;
   p.wrows = (int32_t)a->wrows;
   p.k = (int32_t)a->k;
-  p.ntiles = (int32_t)(a->wrows / (l.on_right ? 8 : 16));
-  p.ksuper = (int32_t)(a->k / (16 * l.I));
+  // The packed words the call holds.  TG_WFMT_ROWS: the A-shaped tensor holds Bint4 words (rows padded to 16), so from here on this IS
+  // a weights-on-the-right call -- both sides produce [activation row][weight row] (TinyGemm_int4.cu:450-456).
+  // (w8 has one packed format per side and does not read w_format)
+  const bool rows = e != ENTRY_W8 && a->w_format == TG_WFMT_ROWS;
+  p.on_right = rows || a->w_on_right != 0;
+  p.inner = rows ? (a->k % 64 == 0 ? 4 : 2) : a->inner_k_tiles;
+  p.ntiles = (int32_t)(a->wrows / (p.on_right ? 8 : 16));
+  p.ksuper = (int32_t)(a->k / (16 * p.inner));
   p.gshift = group_shift(a->group);
   p.ngroups = (int32_t)(a->k / a->group);
   p.qtype = a->qtype;
   p.rowtiles = (int32_t)cdiv(a->wrows, 16);
+  p.dt = a->dtype;
+  p.qmx = a->qtype == TG_Q_MX4;
+  p.batch = batched ? a->batch : 1;
+  p.st = (hipStream_t)stream;
   p.numerics = a->numerics == TG_NUM_FAST_DOT2 ? (int)TG_NUM_FAST : a->numerics;
   p.dot2 = a->numerics == TG_NUM_FAST_DOT2;
   p.dry = dry != 0;
@@ -478,32 +468,22 @@ static GemmParams make_params(const tg_w4_gemm* a, PackedLayout l, int dry) {
 // dry: 0 launch, 1 report the kernel family (tg_gemm_w4_plan), 2 report the workspace the fastest kernel wants
 static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
   tg_w4_gemm full;
-  const tg_w4_gemm* a = &full;
   int rc0 = take_args(caller, &full);
-  if (rc0 == 0) rc0 = check_gemm(a, ENTRY_W4);
+  if (rc0 == 0) rc0 = check_gemm(&full, ENTRY_W4);
   if (rc0 != 0) return rc0;
-  const PackedLayout lay = gemm_layout(a);
-  const bool on_right = lay.on_right;
-  const int I = lay.I, batch = a->batch > 1 ? a->batch : 1;
-  GemmParams p = make_params(a, lay, dry);
+  GemmParams p = make_params(&full, ENTRY_W4, stream, dry);
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t coltiles = cdiv(a->m, 16);
-  // packed words per lane-quad in the layout decide the in-register transpose
-  const int canon = on_right ? (I == 2 ? CANON_NONE : I == 4 ? CANON_PAIR : CANON_QUAD)
-                             : (I == 1 ? CANON_NONE : I == 2 ? CANON_PAIR : CANON_QUAD);
   // MANY activation rows (a prefill through the modules, a wide decode batch): the LDS-tiled MFMA GEMM that dequantises the weights once per
   // 128-row tile of m instead of once per 16 rows (w4_gemm_tile.cuh; the reference's weights bit for bit, so it serves both numerics
   // settings).  From 65 rows; ONE layer from 17 rows when the caller's workspace allows a split-K launch (tg_tile.hip).  4096^2 at m = 128 / 256 / 1024:
   // 17.9 / 25.5 / 52 us against 37.8 / 44.5 / 166 on the stream kernel and 55 / 102 / 427 in 16-row blocks.
-  if (on_right && a->m >= TG_TILE_MIN_M_SPLIT) {
-    const int trc = tgx::tile(a->dtype, I, a->qtype == TG_Q_MX4, p, batch, st);
+  if (p.on_right && p.m >= TG_TILE_MIN_M_SPLIT) {
+    const int trc = offer(tgx::tile, p);
     if (trc != TG_PAIR_NA) {
       if (ws_need) *ws_need = p.ws_need;
       return trc;
     }
-    p.ws_need = 0;
   }
   // More than 16 activation rows in the default numerics (row-major operands, weights on the B side): the group-scaled kernels hold at
   // most one 16-row MFMA tile of activations, so the call is issued as ceil(m / 16) launches of up to 16 rows each on the caller's stream
@@ -516,39 +496,40 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
 #ifndef TG_ROW_BLOCKS_MAX_M
 #define TG_ROW_BLOCKS_MAX_M 64
 #endif
-  if (on_right && a->m > 16 && a->m <= TG_ROW_BLOCKS_MAX_M && (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA) && !p.x_tc && !p.y_tc &&
+  if (p.on_right && p.m > 16 && p.m <= TG_ROW_BLOCKS_MAX_M && (p.numerics == TG_NUM_FAST || p.numerics == TG_NUM_FAST_MFMA) && !p.x_tc && !p.y_tc &&
       !p.norm_w && !p.epilogue) {
+    // the rows [m0, m0 + mb) of the call as a call of their own
+    auto row_block = [&](int64_t m0, int mb) {
+      GemmParams q = p;
+      q.m = mb;
+      q.x = p.x + m0 * p.k * 2;
+      q.y = p.y + m0 * p.wrows * 2;
+      if (q.bias && q.bias_row_stride) q.bias = p.bias + m0 * q.bias_row_stride * 2;
+      return q;
+    };
     // decided on a dry pass over the two block shapes of the call (16 rows, the ragged last block): both on a group-scaled kernel, or the
     // whole call stays on the path below
     auto block_plan = [&](int mb) {
-      GemmParams q = p;
-      q.m = mb;
+      GemmParams q = row_block(0, mb);
       q.dry = true;
-      q.ws_need = 0;
-      return launch_w4(a->dtype, false, canon, a->qtype == TG_Q_MX4, q, 1, batch, st);
+      return launch_w4(q);
     };
     auto group_scaled = [](int rc) { return rc == TG_PLAN_PAIR || rc == TG_PLAN_PAIR_XR || rc == TG_PLAN_GEMV; };
-    const int last = (int)(a->m % 16 ? a->m % 16 : 16);
+    const int last = p.m % 16 ? p.m % 16 : 16;
     const int r16 = block_plan(16), rl = last == 16 ? r16 : block_plan(last);
     if (group_scaled(r16) && group_scaled(rl)) {
       int64_t need = 0;
-      for (int64_t m0 = 0; m0 < a->m; m0 += 16) {
-        GemmParams q = p;
-        q.m = (int32_t)(a->m - m0 < 16 ? a->m - m0 : 16);
-        q.x = p.x + m0 * a->k * 2;
-        q.y = p.y + m0 * a->wrows * 2;
-        if (q.bias && q.bias_row_stride) q.bias = p.bias + m0 * q.bias_row_stride * 2;
-        q.ws_need = 0;
-        const int rc = launch_w4(a->dtype, false, canon, a->qtype == TG_Q_MX4, q, 1, batch, st);
+      for (int m0 = 0; m0 < p.m; m0 += 16) {
+        GemmParams q = row_block(m0, p.m - m0 < 16 ? p.m - m0 : 16);
+        const int rc = launch_w4(q);
         if (rc < 0) return rc;
         if (rc == TG_PLAN_PAIR || rc == TG_PLAN_PAIR_XR) need = q.ws_need > need ? q.ws_need : need;
       }
       if (ws_need) *ws_need = need;
       return dry ? r16 : 0;
     }
-    p.ws_need = 0;
   }
-  const int rc = launch_w4(a->dtype, !on_right, canon, a->qtype == TG_Q_MX4, p, coltiles, batch, st);
+  const int rc = launch_w4(p);
   if (ws_need) *ws_need = (rc == TG_PLAN_PAIR || rc == TG_PLAN_PAIR_XR) ? p.ws_need : 0;
   return rc;
 }
@@ -571,11 +552,10 @@ static int gemm_dx_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
   int rc0 = take_args(caller, &full);
   if (rc0 == 0) rc0 = check_gemm(a, ENTRY_DX);
   if (rc0 != 0) return rc0;
-  const PackedLayout lay = gemm_layout(a);
-  GemmParams p = make_params(a, lay, dry);
+  GemmParams p = make_params(a, ENTRY_DX, stream, dry);
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
-  const int rc = tgx::gemm_dx(a->dtype, lay.I, a->qtype == TG_Q_MX4, p, (hipStream_t)stream);
+  const int rc = tgx::gemm_dx(p);
   if (ws_need) *ws_need = p.ws_need;
   return rc;
 }
@@ -625,37 +605,32 @@ static int gemm_w8_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
   int rc0 = take_args(caller, &full);
   if (rc0 == 0) rc0 = check_gemm(a, ENTRY_W8);
   if (rc0 != 0) return rc0;
-  const bool on_right = a->w_on_right != 0;   // (one packed format per side: w_format is not read)
-  const int I = a->inner_k_tiles, batch = a->batch > 1 ? a->batch : 1;
-  GemmParams p = make_params(a, {on_right, I}, dry);
+  GemmParams p = make_params(a, ENTRY_W8, stream, dry);
   // what the struct says for the 4-bit kernels only was not validated and does not reach an int8 kernel
   p.lut = nullptr; p.stride_lut = 0; p.numerics = TG_NUM_REFERENCE; p.dot2 = 0; p.norm_eps = 0.f; p.x_tc = p.y_tc = 0;
   DeviceScope ds(dry ? -1 : device);
   if (!dry && !ds.ok) return TG_E_DEVICE;
-  hipStream_t st = (hipStream_t)stream;
-  const int64_t coltiles = cdiv(a->m, 16);
 #ifdef TG_DEV_MIN
-  (void)coltiles; (void)st;
   return TG_E_SHAPE;
 #else
   // many activation rows: the LDS-tiled MFMA GEMM's int8 flavour (w4_gemm_tile.cuh; the same weights bit for bit), split-K with the caller's workspace
   {
-    const int trc = tgx::tile_w8(a->dtype, on_right, I, p, batch, st);
-    if (ws_need) *ws_need = trc == TG_PAIR_NA ? 0 : p.ws_need;
+    const int trc = offer(tgx::tile_w8, p);
+    if (ws_need) *ws_need = p.ws_need;
     if (trc != TG_PAIR_NA) return trc == TG_PLAN_TILE ? 0 : trc;
     if (dry) return 0;
   }
-#define TG_W8(DTT)                                                                                    \
-  do {                                                                                                \
-    if (on_right) {                                                                                   \
-      if (I == 1) return launch_w8<DTT, false, 1>(p, coltiles, batch, st);                           \
-      if (I == 2) return launch_w8<DTT, false, 2>(p, coltiles, batch, st);                           \
-      return launch_w8<DTT, false, 4>(p, coltiles, batch, st);                                       \
-    }                                                                                                 \
-    if (I == 1) return launch_w8<DTT, true, 1>(p, coltiles, batch, st);                              \
-    return launch_w8<DTT, true, 2>(p, coltiles, batch, st);                                          \
+#define TG_W8(DTT)                                                   \
+  do {                                                               \
+    if (p.on_right) {                                                \
+      if (p.inner == 1) return launch_w8<DTT, false, 1>(p);          \
+      if (p.inner == 2) return launch_w8<DTT, false, 2>(p);          \
+      return launch_w8<DTT, false, 4>(p);                            \
+    }                                                                \
+    if (p.inner == 1) return launch_w8<DTT, true, 1>(p);             \
+    return launch_w8<DTT, true, 2>(p);                               \
   } while (0)
-  if (a->dtype == TG_BF16) TG_W8(BF16);
+  if (p.dt == TG_BF16) TG_W8(BF16);
   TG_W8(F16);
 #undef TG_W8
 #endif

@@ -20,7 +20,7 @@
 //     and get scale = zero = 0, so they contribute exact zeros.
 #pragma once
 
-// (GemmParams and the CANON_* values live in tg_common.cuh: the launch paths of the kernel families are separate translation units)
+// (SplitKParams and the CANON_* values live in tg_common.cuh: the launch paths of the kernel families are separate translation units)
 
 
 // Word transpose between the four 16-lane rows of a wave so that every lane ends up with the
@@ -51,7 +51,7 @@ struct Slot {
 };
 
 template <typename DT, bool LAYOUT_A, int CANON, bool QMX, int WAVES, int DEPTH, int MINW>
-__global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const GemmParams p) {
+__global__ void __launch_bounds__(WAVES * 64, MINW) w4_gemm_kernel(const SplitKParams p) {
   constexpr int CHUNK = LAYOUT_A ? 16 : 32;  // k covered by one lane per step
   constexpr int KSTEP = 4 * CHUNK;           // k covered by one wave per step
   constexpr int NMMA = LAYOUT_A ? 2 : 4;     // MFMAs per step

@@ -20,7 +20,7 @@
 #define W8_RING 2   // steps in flight per wave (1 / 2 / 4 / 8 measured: 7.7 / 7.4 / 7.4 / 7.7 us at one row: VALU-bound at ~ 190 instructions per step, not latency-bound)
 #endif
 template <typename DT, bool LAYOUT_A, int I, int WAVES>
-__global__ void __launch_bounds__(WAVES * 64, WAVES <= 8 ? 2 : 1) w8_gemm_kernel(const GemmParams p) {
+__global__ void __launch_bounds__(WAVES * 64, WAVES <= 8 ? 2 : 1) w8_gemm_kernel(const SplitKParams p) {
   __shared__ f32x4 s_red[WAVES * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int i = lane & 15, Q = lane >> 4;

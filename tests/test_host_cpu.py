@@ -384,6 +384,44 @@ def test_xr_kernel_routing():
     assert ops.gemm_w4_plan(33, 4096, 4096, 128, q2["any4_rowwise"], True, 4, numerics="reference", detail=True) == "tile"
 
 
+def test_workspace_bytes_is_what_the_plan_takes():
+    """The invariant the ws_need protocol of the launch paths exists for (no GPU work): a workspace tg_gemm_w4_workspace_bytes asks for is
+    the workspace of the kernel that then runs.  For every valid call of the grid: an answer > 0, attached exactly, makes tg_gemm_w4_plan
+    answer one of the three families that take a workspace (pair, pair_xr, tile) -- a stale or forgotten ws_need of a family that
+    declined would show as bytes for a kernel that has no use for them; with 16 bytes less attached the call still has a valid plan."""
+    import itertools
+
+    from any4_amd import _lib
+
+    lib = _lib.load()
+    buf = ctypes.create_string_buffer(256)
+    pz = (ctypes.addressof(buf) + 63) & ~63   # (nothing is launched: nothing reads the operands)
+    a = _lib.W4Gemm(x=pz, w=pz, qinfo=pz, lut=pz, y=pz, dtype=_lib.TG_BF16, inner_k_tiles=4, stride_x=16, stride_w=16, stride_qinfo=16, stride_lut=16,
+                    stride_y=16)
+    ref = ctypes.byref(a)
+    takes_workspace = (_lib.TG_PLAN_PAIR, _lib.TG_PLAN_PAIR_XR, _lib.TG_PLAN_TILE)
+    cases = valid = with_ws = 0
+    for a.m, a.wrows, a.k, a.group, a.qtype, a.batch, a.numerics, a.w_on_right in itertools.product(
+            (1, 2, 4, 5, 8, 9, 16, 17, 33, 64, 65, 128), (256, 1024, 4096, 14336), (1024, 4096, 8192, 14336), (32, 64, 128),
+            (_lib.TG_Q_INT4, _lib.TG_Q_ANY4_ROWWISE, _lib.TG_Q_MX4), (1, 4, 512), (_lib.TG_NUM_FAST, _lib.TG_NUM_REFERENCE), (1, 0)):
+        cases += 1
+        a.workspace, a.workspace_bytes = None, 0
+        need = lib.tg_gemm_w4_workspace_bytes(ref)
+        if need < 0:   # (fails validation: not counted)
+            continue
+        valid += 1
+        case = (a.m, a.wrows, a.k, a.group, a.qtype, a.batch, a.numerics, a.w_on_right, need)
+        assert lib.tg_gemm_w4_plan(ref, -1) > 0, case
+        if need > 0:
+            with_ws += 1
+            a.workspace, a.workspace_bytes = pz, need
+            assert lib.tg_gemm_w4_plan(ref, -1) in takes_workspace, case
+            a.workspace_bytes = need - 16
+            assert lib.tg_gemm_w4_plan(ref, -1) > 0, case
+    print(f"{cases} calls, {valid} valid, {with_ws} with a workspace")
+    assert cases == 12 * 4 * 4 * 3 * 3 * 3 * 2 * 2 and valid > 0 and with_ws > 0
+
+
 def test_integration_md_binding_and_struct_bytes():
     """The reference-side binding shown in INTEGRATION.md is executed as written (its ctypes struct, against the built library): the
     struct matches the header's length, a call described by it plans a kernel; a binding written against an OLDER header (struct

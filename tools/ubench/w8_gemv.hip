@@ -14,7 +14,7 @@ namespace {
 #define WV_ 8
 #endif
 template <bool LA, int I>
-static void go(GemmParams& p, hipStream_t st) {
+static void go(SplitKParams& p, hipStream_t st) {
 #ifndef WV_
 #define WV_ 8
 #endif
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
   for (auto& v : h) { s = s * 1664525u + 1013904223u; v = s; }
   CK(hipMemcpy(dw, h.data(), wbytes * SETS, hipMemcpyHostToDevice));
   CK(hipMemset(dq, 0x3c, (size_t)(k / g) * n * 4)); CK(hipMemset(dx, 0x3c, (size_t)m * k * 2));
-  GemmParams p{};
+  SplitKParams p{};
   p.x = dx; p.w = dw; p.qinfo = dq; p.y = dy; p.m = m; p.wrows = n; p.k = k;
   const int I = side == 1 ? 4 : 2;
   p.ntiles = side == 0 ? n / 16 : n / 8; p.ksuper = k / (16 * I); p.gshift = 7; p.ngroups = k / g; p.qtype = TG_Q_INT8;
@@ -46,7 +46,7 @@ int main(int argc, char** argv) {
   while (sk < WV_ && (int64_t)p.rowtiles * ((m + 15) / 16) * sk < 256 * 16 && sk * 2 <= nsteps) sk *= 2;
   if (sk_arg) sk = sk_arg;
   p.splitk = sk; p.sk_shift = 0; while ((1 << p.sk_shift) < sk) ++p.sk_shift;
-  auto launch = [&](int i) { GemmParams q = p; q.w = dw + (size_t)(i % SETS) * wbytes; if (side == 0) go<true, 2>(q, 0); else if (side == 1) go<false, 4>(q, 0); else go<false, 2>(q, 0); };
+  auto launch = [&](int i) { SplitKParams q = p; q.w = dw + (size_t)(i % SETS) * wbytes; if (side == 0) go<true, 2>(q, 0); else if (side == 1) go<false, 4>(q, 0); else go<false, 2>(q, 0); };
   hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
   for (int rep = 0; rep < 3; ++rep) {
     for (int i = 0; i < 6; ++i) launch(i);
