@@ -25,7 +25,7 @@
 // nobody (every token only reads rows <= its own position) and leaves its output row unwritten; rows of a tile beyond the workgroup's
 // last valid position are zero-filled in LDS instead of being read, so NaN-filled or unallocated tails are never touched.
 #pragma once
-#include "rope_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
+#include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 
 struct PrefillParams {
   const uint16_t* qkv;

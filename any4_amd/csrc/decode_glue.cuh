@@ -5,17 +5,14 @@
 // there are 5 of them per layer instead of ~45 torch launches, not their individual bandwidth.  Rounding points
 // mirror the torch formulation in any4_amd/decode.py so the two paths can be compared in tests.
 #include "../../include/decode_glue_hip.h"
-#include "rope_math.cuh"
+#include "stage_math.cuh"
 
 namespace {
 
-// (tg_common.cuh, tgl: DPP rotations and row swaps instead of six trips through the LDS crossbar)
-__device__ __forceinline__ float wave_sum(float v) { return tgl::wave_sum(v); }
-__device__ __forceinline__ float wave_max(float v) { return tgl::wave_max(v); }
 // all threads of a 256-thread block get the reduction; `scratch` holds >= 4 floats and is reusable afterwards
 template <bool MAX>
 __device__ __forceinline__ float block_reduce(float v, float* scratch) {
-  v = MAX ? wave_max(v) : wave_sum(v);
+  v = MAX ? tgl::wave_max(v) : tgl::wave_sum(v);  // (DPP rotations and row swaps instead of six trips through the LDS crossbar)
   __syncthreads();
   if ((threadIdx.x & 63) == 0) scratch[threadIdx.x >> 6] = v;
   __syncthreads();
@@ -37,8 +34,6 @@ template <typename DT>
 __device__ __forceinline__ u32x4 pack8(const float (&f)[8]) {
   return u32x4{DT::pack2(f[0], f[1]), DT::pack2(f[2], f[3]), DT::pack2(f[4], f[5]), DT::pack2(f[6], f[7])};
 }
-template <typename DT>
-__device__ __forceinline__ float round16(float a) { return DT::to_f32(DT::from_f32(a)); }
 
 // ---- residual add + RMSNorm: one 256-thread block per row ------------------------------------------
 template <typename DT>
@@ -68,7 +63,7 @@ __global__ void __launch_bounds__(256) add_rmsnorm_kernel(const u32x4* h, const 
     unpack8<DT>(h_out[base + v], a);  // written by this same thread above (or the untouched input)
     unpack8<DT>(w[v], g);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) a[e] = round16<DT>(a[e] * r) * g[e];
+    for (int e = 0; e < 8; ++e) a[e] = rmsnorm_elem<DT>(a[e], r, g[e]);
     y[base + v] = pack8<DT>(a);
   }
 }
@@ -145,7 +140,7 @@ __global__ void rope_kv_kernel(const uint16_t* __restrict__ qkv, const float* __
   }
   const float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
   const float c1 = cos[pos * d + j], c2 = cos[pos * d + j + d2], s1 = sin[pos * d + j], s2 = sin[pos * d + j + d2];
-  // x * cos + rotate_half(x) * sin with each product and the sum rounded separately, as the torch ops do (rope_math.cuh: no FMA)
+  // x * cos + rotate_half(x) * sin with each product and the sum rounded separately, as the torch ops do (stage_math.cuh: no FMA)
   const float o1 = rope_mul_add(x1, c1, -x2, s1);
   const float o2 = rope_mul_add(x2, c2, x1, s2);
   uint16_t* dst = head < hl ? q_out + ((int64_t)b * hl + head) * d
@@ -429,14 +424,6 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
   if (t == 0) counters[bh] = 0;  // ready for the next launch / graph replay
 }
 
-template <typename DT>
-__device__ __forceinline__ float dot2_16(uint32_t a, uint32_t b, float acc) {
-  if constexpr (std::is_same<DT, BF16>::value)
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  else
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), acc, false);
-}
-
 // ---- RoPE + KV-cache write + decode attention, one launch, ONE barrier: block = one query head of one sequence, 8 waves ----
 // What a batch-1 decode step needs from this node is latency, not bandwidth (at a few hundred cached positions the K and V
 // rows of a head are < 100 KiB): rope_attn_kernel above walks five dependent phases with four barriers (11 us per layer in
@@ -467,13 +454,8 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const int NS = gridDim.y, cblk = blockIdx.y;
   // first row of the block's local iteration jl
   auto row0_of = [&](int jl) -> int { return (jl * NS + cblk) * RPI; };
-#if GEMV_TRACE
-  unsigned long long tr[8];
-#define DG_STAMP(n) tr[n] = __builtin_amdgcn_s_memrealtime()
-#else
-#define DG_STAMP(n)
-#endif
-  DG_STAMP(0);
+  TG_TRACE_BEGIN();
+  TG_STAMP(0);
   extern __shared__ float sm[];  // [8 waves][D + 2]: unnormalised accumulator, max, sum
   const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
   const int g = lane / LPR, i = lane % LPR, grp = wave * RPW + g;
@@ -508,7 +490,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const int64_t pos = *pos_p;
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check)
   const int S = (int)pos + 1;
-  DG_STAMP(1);
+  TG_STAMP(1);
   // ---- every load of the launch (positions past the end re-read position 0; the new token's row comes from qkv) ----
   const u32x4 qraw = reinterpret_cast<const u32x4*>(row + h * D)[i];
   const u32x4 kraw = reinterpret_cast<const u32x4*>(row + (hl + kv) * D)[i];
@@ -526,7 +508,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     }
   };
   request(0, NSPEC);
-  DG_STAMP(2);
+  TG_STAMP(2);
   // ---- rotary embedding of q and k (this lane's 8 elements; the partner elements j +- d/2 are LPR/2 lanes away) ----
   float cf[8], sf[8];
 #pragma unroll
@@ -550,7 +532,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     return pack8<DT>(o);
   };
   const u32x4 qp = rotate(qraw), kn = rotate(kraw);
-  DG_STAMP(3);
+  TG_STAMP(3);
   if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
     reinterpret_cast<u32x4*>(k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = kn;
     reinterpret_cast<u32x4*>(v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = vraw;
@@ -569,10 +551,10 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       const int r = row0_of(base / RPI + it) + grp;
       const u32x4 kr = r == S - 1 ? kn : kk[it];
       // (literal indices: with a loop variable hipcc (ROCm 7.2) fed dword 0 of both vectors to all four v_dot2)
-      float d2 = dot2_16<DT>(kr[0], qp[0], 0.f);
-      d2 = dot2_16<DT>(kr[1], qp[1], d2);
-      d2 = dot2_16<DT>(kr[2], qp[2], d2);
-      d2 = dot2_16<DT>(kr[3], qp[3], d2);
+      float d2 = dot2<DT>(kr[0], qp[0], 0.f);
+      d2 = dot2<DT>(kr[1], qp[1], d2);
+      d2 = dot2<DT>(kr[2], qp[2], d2);
+      d2 = dot2<DT>(kr[3], qp[3], d2);
       d2 = dpp_add(d2, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
       d2 = dpp_add(d2, std::integral_constant<int, 0x4E>{});    // quad_perm [2,3,0,1]
       d2 = dpp_add(d2, std::integral_constant<int, 0x141>{});   // row_half_mirror: the other quad of the 8 lanes
@@ -581,7 +563,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       cm = fmaxf(cm, x[it]);
     }
     const float mn = fmaxf(m, cm);
-    if (base == 0) { DG_STAMP(4); }
+    TG_STAMP_IF(base == 0, 4);
     if (mn > -INFINITY) {  // (uniform within the row group; a group without rows so far keeps its zeros)
       const float alpha = __expf(m - mn);  // exp(-inf) = 0 for the first chunk with rows
       l *= alpha;
@@ -601,7 +583,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       m = mn;
     }
   }
-  DG_STAMP(5);
+  TG_STAMP(5);
   // ---- the groups meet: out[e] = sum_g exp(m_g - M) acc_g[e] / sum_g exp(m_g - M) l_g.  First the RPW groups of a wave through
   // lane exchanges (no barrier), then the 8 waves once through LDS ----
   auto meet = [&](auto OO) {
@@ -629,7 +611,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     if (i == 0) { mine[D] = m; mine[D + 1] = l; }
   }
   __syncthreads();
-  DG_STAMP(6);
+  TG_STAMP(6);
   float Mb = -INFINITY, num = 0.f, den = 0.f;
   if (t < D) {
 #pragma unroll
@@ -681,14 +663,8 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       if (t == 0) __hip_atomic_store(&counters[bh], 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // ready for the next launch / graph replay
     }
   }
-#if GEMV_TRACE
-  DG_STAMP(7);
-  if (t == 0 && trace) {
-#pragma unroll
-    for (int n = 0; n < 8; ++n) trace[(size_t)blockIdx.x * 8 + n] = tr[n];
-  }
-#endif
-#undef DG_STAMP
+  TG_STAMP(7);
+  TG_TRACE_FLUSH(t == 0 && trace, trace, 8);
 }
 
 // ---- y[a][row] = RNE16(sum_k x[a][k] w[row][k]) for ROW-MAJOR 16-bit weights [n][k] and 1 ... 4 activation rows: the LM head of the
@@ -725,12 +701,12 @@ __global__ void __launch_bounds__(512) linear16_gemv_kernel(const uint16_t* __re
         acc[a] = 0.f;
 #pragma unroll
         for (int j = 0; j < KP; ++j) {
-          acc[a] = dot2_16<DT>(wr[i][j][0], xr[a][j][0], acc[a]);
-          acc[a] = dot2_16<DT>(wr[i][j][1], xr[a][j][1], acc[a]);
-          acc[a] = dot2_16<DT>(wr[i][j][2], xr[a][j][2], acc[a]);
-          acc[a] = dot2_16<DT>(wr[i][j][3], xr[a][j][3], acc[a]);
+          acc[a] = dot2<DT>(wr[i][j][0], xr[a][j][0], acc[a]);
+          acc[a] = dot2<DT>(wr[i][j][1], xr[a][j][1], acc[a]);
+          acc[a] = dot2<DT>(wr[i][j][2], xr[a][j][2], acc[a]);
+          acc[a] = dot2<DT>(wr[i][j][3], xr[a][j][3], acc[a]);
         }
-        acc[a] = wave_sum(acc[a]);
+        acc[a] = tgl::wave_sum(acc[a]);
       }
       if (lane == 0 && r + i < r1) {
 #pragma unroll
@@ -752,7 +728,7 @@ __global__ void __launch_bounds__(256) swiglu_kernel(const u32x4* __restrict__ g
     unpack8<DT>(gu[b * 2 * il8 + j], g);
     unpack8<DT>(gu[b * 2 * il8 + il8 + j], u);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) g[e] = round16<DT>(g[e] / (1.f + __expf(-g[e]))) * u[e];
+    for (int e = 0; e < 8; ++e) g[e] = swiglu_elem<DT>(g[e], u[e]);
     out[i] = pack8<DT>(g);
   }
 }
@@ -841,21 +817,18 @@ int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, con
   DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
   const unsigned lds = (unsigned)(8 * (d + 2) * sizeof(float));
-#define DG_ONLINE(DTT, LPR_)                                                                                                        \
-  hipLaunchKernelGGL((rope_attn_online_kernel<DTT, LPR_>), dim3((unsigned)(bs * hl)), dim3(512), lds, (hipStream_t)stream,          \
-                     (const uint16_t*)qkv, cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, trace, \
-                     (float*)nullptr, (int*)nullptr)
   unsigned long long* trace = nullptr;
 #if GEMV_TRACE
   trace = g_attn_trace;
 #endif
-  if (dtype == TG_BF16) {
-    if (d == 128) DG_ONLINE(BF16, 16); else DG_ONLINE(BF16, 8);
-  } else {
-    if (d == 128) DG_ONLINE(F16, 16); else DG_ONLINE(F16, 8);
-  }
-#undef DG_ONLINE
-  return launch_status();
+  return pick_dt(dtype, [&](auto DT_) {
+    return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
+      hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value>), dim3((unsigned)(bs * hl)), dim3(512), lds, (hipStream_t)stream,
+                         (const uint16_t*)qkv, cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, trace,
+                         (float*)nullptr, (int*)nullptr);
+      return launch_status();
+    });
+  });
 }
 
 int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
@@ -879,16 +852,13 @@ int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, cons
     // the one-barrier kernel, split over the sequence (same scratch layout: counters, then [head][chunk][max, sum, d outputs])
     const unsigned lds1 = (unsigned)(8 * (d + 2) * sizeof(float));
     const dim3 grid((unsigned)(bs * hl), (unsigned)nsplit);
-#define DG_ONLINE_SPLIT(DTT, LPR_)                                                                                                   \
-  hipLaunchKernelGGL((rope_attn_online_kernel<DTT, LPR_>), grid, dim3(512), lds1, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin, \
-                     pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, (unsigned long long*)nullptr, part, counters)
-    if (dtype == TG_BF16) {
-      if (d == 128) DG_ONLINE_SPLIT(BF16, 16); else DG_ONLINE_SPLIT(BF16, 8);
-    } else {
-      if (d == 128) DG_ONLINE_SPLIT(F16, 16); else DG_ONLINE_SPLIT(F16, 8);
-    }
-#undef DG_ONLINE_SPLIT
-    return launch_status();
+    return pick_dt(dtype, [&](auto DT_) {
+      return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value>), grid, dim3(512), lds1, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin,
+                           pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, (unsigned long long*)nullptr, part, counters);
+        return launch_status();
+      });
+    });
   }
   if (lds > 64u * 1024u) return TG_E_SHAPE;
   auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16> : rope_attn_split_kernel<F16>;
@@ -912,24 +882,20 @@ int dg_linear16(const void* x, const void* w, void* y, int64_t m, int64_t n, int
   const int64_t waves = 2 * 8 * (int64_t)cu_count();
   const int64_t rpw = (n + waves - 1) / waves;
   const unsigned blocks = (unsigned)((n + rpw * 8 - 1) / (rpw * 8));
-#define DG_L16(DTT, M_, KP_, NR_)                                                                                              \
-  hipLaunchKernelGGL((linear16_gemv_kernel<DTT, M_, KP_, NR_>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, (const uint16_t*)x, \
-                     (const uint16_t*)w, (uint16_t*)y, n, rpw)
-#define DG_L16_M(DTT, KP_, NR_)                                                          \
-  do {                                                                                   \
-    if (m == 1) DG_L16(DTT, 1, KP_, NR_); else if (m == 2) DG_L16(DTT, 2, KP_, NR_);      \
-    else if (m == 3) DG_L16(DTT, 3, KP_, NR_); else DG_L16(DTT, 4, KP_, NR_);             \
-  } while (0)
-#define DG_L16_K(DTT)                                                                    \
-  do {                                                                                   \
-    if (k == 2048) DG_L16_M(DTT, 4, 4); else if (k == 4096) DG_L16_M(DTT, 8, 2);           \
-    else if (m == 1) DG_L16(DTT, 1, 16, 1); else DG_L16(DTT, 2, 16, 1);  /* (k = 8192: one or two rows fit the registers) */ \
-  } while (0)
-  if (dtype == TG_BF16) DG_L16_K(BF16); else DG_L16_K(F16);
-#undef DG_L16_K
-#undef DG_L16_M
-#undef DG_L16
-  return launch_status();
+  return pick_dt(dtype, [&](auto DT_) {
+    return pick<4, 8, 16>((int)(k / 512), [&](auto KP_) {  // (k = 2048, 4096, 8192: pieces per lane)
+      return pick<1, 2, 3, 4>((int)m, [&](auto M_) {
+        constexpr int KP = decltype(KP_)::value, M = decltype(M_)::value, NR = KP == 4 ? 4 : KP == 8 ? 2 : 1;  // rows in flight per wave
+        if constexpr (KP == 16 && M > 2) {  // (k = 8192: one or two rows fit the registers)
+          return (int)TG_PAIR_NA;
+        } else {
+          hipLaunchKernelGGL((linear16_gemv_kernel<decltype(DT_), M, KP, NR>), dim3(blocks), dim3(512), 0, (hipStream_t)stream, (const uint16_t*)x,
+                             (const uint16_t*)w, (uint16_t*)y, n, rpw);
+          return launch_status();
+        }
+      });
+    });
+  });
 }
 
 int dg_swiglu(const void* gu, void* out, int64_t bs, int64_t il, int dtype, int device, tg_stream_t stream) {

@@ -15,12 +15,12 @@
 //   tg_tile.hip        w4_gemm_tile_kernel       (w4_gemm_tile.cuh)
 //   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
 //   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
+// Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
+// MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each);
+// tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once
-#ifndef GEMV_TRACE
-#define GEMV_TRACE 0  // developer builds (-DGEMV_TRACE=1): s_memrealtime stamps of kernel phases (dev/gemv_trace.py)
-#endif
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -30,6 +30,7 @@
 #include <utility>
 
 #include "../../include/tinygemm_hip.h"
+#include "tg_trace.cuh"
 
 // One validated call, complete: everything a launch path needs to plan and launch it (make_params fills it once).  Host-only -- every
 // kernel has an argument block of its own (copy_call).
@@ -232,6 +233,20 @@ struct F16 {
     return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
   }
 };
+
+// Kernel selection, the one idiom of the launch paths: a run-time value picks a template argument, the generic lambda `f` names the kernel.
+// pick<V0, V1, ...>(v, f) calls f(std::integral_constant<int, Vi>{}) for the Vi that equals v and answers TG_PAIR_NA when none does;
+// pick_dt(dt, f) calls f(BF16{}) or f(F16{}).  A combination that is not instantiated is an `if constexpr` in the lambda.
+template <int... VS, typename F>
+int pick(int v, F&& f) {
+  int rc = TG_PAIR_NA;
+  (void)((v == VS && ((rc = f(std::integral_constant<int, VS>{})), true)) || ...);
+  return rc;
+}
+template <typename F>
+int pick_dt(int dt, F&& f) {
+  return dt == TG_BF16 ? f(BF16{}) : f(F16{});
+}
 
 // fp4-e2m1 values in code order (reference FloatDefs.cuh:18-34)
 __device__ const float kMX4Values[16] = {0.0f,  0.5f,  1.0f,  1.5f,  2.0f,  3.0f,  4.0f,  6.0f,

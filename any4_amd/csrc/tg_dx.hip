@@ -50,6 +50,6 @@ int gemm_dx(GemmParams& p) {
   dp.sps = (nsteps + splits - 1) / splits;
   dp.part = splits > 1 ? reinterpret_cast<float*>(p.ws) : nullptr;
   if (p.qmx) return go_bm<BF16, true>(dp, bm, p.st);
-  return p.dt == TG_BF16 ? go_bm<BF16, false>(dp, bm, p.st) : go_bm<F16, false>(dp, bm, p.st);
+  return pick_dt(p.dt, [&](auto DT_) { return go_bm<decltype(DT_), false>(dp, bm, p.st); });
 }
 }  // namespace tgx

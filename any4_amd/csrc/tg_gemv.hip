@@ -2,7 +2,7 @@
 // and of Any4Linear.forward / Int4Linear.forward at batch 1); see tg_common.cuh and w4_gemv.cuh
 #include "tg_common.cuh"
 namespace {
-#include "w4_gemm_pair.cuh"   // shared device helpers (dot2, chunk_rmsnorm, swiglu16); its kernel is not instantiated here
+#include "w4_helpers.cuh"
 #include "w4_gemv.cuh"
 
 #ifndef TG_GEMV_MF_MIN_M
@@ -14,70 +14,11 @@ namespace {
 #ifndef TG_GEMV_MAX_TILES
 #define TG_GEMV_MAX_TILES 16384  // 8-row tiles per launch up to which this kernel takes single-problem launches (131072 rows)
 #endif
-
-template <typename DT, int M, int GPS, int D, bool NORM, bool MF = false>
-int go(const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  return launch_lds_kernel<w4_gemv_kernel<DT, M, GPS, D, NORM, MF>>(grid, dim3(512), lds, st, gp, true);  // (a part with less LDS: the older kernels take over)
-}
-template <typename DT, int M, int GPS, int D>
-int go_n(bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  return norm ? go<DT, M, GPS, D, true>(gp, grid, lds, st) : go<DT, M, GPS, D, false>(gp, grid, lds, st);
-}
-template <typename DT, int M, int GPS>
-int go_d(int d, bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  return d == 4 ? go_n<DT, M, GPS, 4>(norm, gp, grid, lds, st) : go_n<DT, M, GPS, 8>(norm, gp, grid, lds, st);
-}
-template <typename DT, int M>
-int go_g(int gps, int d, bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  return gps == 1 ? go_d<DT, M, 1>(d, norm, gp, grid, lds, st) : go_d<DT, M, 2>(d, norm, gp, grid, lds, st);
-}
-// the matrix-core contraction (w4_gemv.cuh, MF): 3 ... 8 rows, one group per step, ring of four (k <= 4096: four steps per pass)
-template <typename DT, int M>
-int go_mf(int d, bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  if (d == 8) {  // (k > 4096: slices of more than four steps; up to four rows -- the activation block has to fit next to the table)
-    if constexpr (M <= 4) return norm ? go<DT, M, 1, 8, true, true>(gp, grid, lds, st) : go<DT, M, 1, 8, false, true>(gp, grid, lds, st);
-    else return TG_PAIR_NA;
-  }
-  return norm ? go<DT, M, 1, 4, true, true>(gp, grid, lds, st) : go<DT, M, 1, 4, false, true>(gp, grid, lds, st);
-}
-template <typename DT>
-int go_mf_m(int m, int d, bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  switch (m) {
-#if TG_GEMV_MF_MIN_M <= 1
-    case 1: return go_mf<DT, 1>(d, norm, gp, grid, lds, st);
-#endif
-#if TG_GEMV_MF_MIN_M <= 2
-    case 2: return go_mf<DT, 2>(d, norm, gp, grid, lds, st);
-#endif
-    case 3: return go_mf<DT, 3>(d, norm, gp, grid, lds, st);
-    case 4: return go_mf<DT, 4>(d, norm, gp, grid, lds, st);
-    case 5: return go_mf<DT, 5>(d, norm, gp, grid, lds, st);
-    case 6: return go_mf<DT, 6>(d, norm, gp, grid, lds, st);
-    case 7: return go_mf<DT, 7>(d, norm, gp, grid, lds, st);
-    default: return go_mf<DT, 8>(d, norm, gp, grid, lds, st);
-  }
-}
-template <typename DT>
-int go_m(int m, int gps, int d, bool norm, const GemvParams& gp, dim3 grid, unsigned lds, hipStream_t st) {
-  switch (m) {
-    case 1: return go_g<DT, 1>(gps, d, norm, gp, grid, lds, st);
-    case 2: return go_g<DT, 2>(gps, d, norm, gp, grid, lds, st);
-    case 3: return go_g<DT, 3>(gps, d, norm, gp, grid, lds, st);
-    default: return go_g<DT, 4>(gps, d, norm, gp, grid, lds, st);
-  }
-}
-#if GEMV_TRACE
-unsigned long long* g_trace = nullptr;  // developer builds only (-DGEMV_TRACE=1): [slots][512 workgroups][8 stamps]
-int g_trace_slots = 0, g_trace_launch = 0;
-#endif
 }  // namespace
 
 #if GEMV_TRACE
-extern "C" TG_API void tg_dev_gemv_trace(unsigned long long* buf, int slots) {
-  g_trace = buf;
-  g_trace_slots = slots;
-  g_trace_launch = 0;
-}
+static TraceRing g_trace;
+extern "C" TG_API void tg_dev_gemv_trace(unsigned long long* buf, int slots) { g_trace.set(buf, slots); }
 #endif
 
 int tgx::gemv(const GemmParams& p) {
@@ -187,10 +128,29 @@ int tgx::gemv(const GemmParams& p) {
   if (p.dry) return TG_PLAN_GEMV;
   const dim3 grid((unsigned)wgs, (unsigned)p.batch);
 #if GEMV_TRACE
-  if (g_trace && g_trace_slots > 0) gp.trace = g_trace + (size_t)(g_trace_launch++ % g_trace_slots) * 512 * 8;
+  gp.trace = g_trace.next();
 #endif
-  if (mf) return p.dt == TG_BF16 ? go_mf_m<BF16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, p.st)
-                                 : go_mf_m<F16>(p.m, d, p.norm_w != nullptr, gp, grid, lds, p.st);
-  return p.dt == TG_BF16 ? go_m<BF16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, p.st)
-                         : go_m<F16>(p.m, gps, d, p.norm_w != nullptr, gp, grid, lds, p.st);
+  return pick_dt(p.dt, [&](auto DT_) {
+    using DT = decltype(DT_);
+    // (p.m: 1 ... 4, the matrix-core contraction 1 ... 8; gps: 1, 2; d: 4, 8 -- the tests and the plan above)
+    return pick<1, 2, 3, 4, 5, 6, 7, 8>(p.m, [&](auto M_) {
+      return pick<1, 2>(gps, [&](auto GPS_) {
+        return pick<4, 8>(d, [&](auto D_) {
+          return pick<0, 1>(p.norm_w != nullptr, [&](auto NORM_) {
+            return pick<0, 1>(mf, [&](auto MF_) {
+              constexpr int M = decltype(M_)::value, GPS = decltype(GPS_)::value, D = decltype(D_)::value;
+              constexpr bool NORM = decltype(NORM_)::value, MF = decltype(MF_)::value;
+              // the matrix-core contraction (w4_gemv.cuh, MF): 3 ... 8 rows, one group per step, ring of four (k <= 4096: four steps per pass)
+              // (k > 4096: slices of more than four steps; up to four rows -- the activation block has to fit next to the table)
+              if constexpr (MF ? (M < TG_GEMV_MF_MIN_M || GPS != 1 || (D == 8 && M > 4)) : M > 4) {
+                return (int)TG_PAIR_NA;
+              } else {
+                return launch_lds_kernel<w4_gemv_kernel<DT, M, GPS, D, NORM, MF>>(grid, dim3(512), lds, p.st, gp, true);  // (a part with less LDS: the older kernels take over)
+              }
+            });
+          });
+        });
+      });
+    });
+  });
 }

@@ -196,7 +196,6 @@ int launch_pair(GemmParams& p) {
     const int rc = launch_xprep<DT>(p, pp, ma);
     if (rc != 0) return rc;
   }
-#define TG_PAIR_M(GPS_, NSG_) launch_pair_m<DT, I, GPS_, QMX, NSG_>(p, pp, lds, xg, mregs)
   if (gps == 1) {
     // group boundaries at fixed places of the unrolled round when a group is one super-tile or one whole round
     // (the m = 1 specialisation too since its group update is spelled out instruction by instruction: before that, fixed
@@ -210,7 +209,7 @@ int launch_pair(GemmParams& p) {
       if (p.numerics == TG_NUM_FAST_MFMA && p.m == 1 && !xg && !p.norm_w && fixed && nsg == TG_PAIR_R)
         return launch_pair_k<DT, I, 1, 1, false, TG_PAIR_R, false, 0, false, true>(p, pp, lds);
     }
-    if (fixed && nsg == TG_PAIR_R) return TG_PAIR_M(1, TG_PAIR_R);
+    if (fixed && nsg == TG_PAIR_R) return launch_pair_m<DT, I, 1, QMX, TG_PAIR_R>(p, pp, lds, xg, mregs);
     // m = 1, a group of ONE super-tile (g = 64 at innerKTiles 4): fixed boundaries too since the dot2 contraction freed the registers
     // (with the MFMA this build spilled 27; 77 -> 81 %), and a group of FOUR super-tiles (g = 256) as one round of a ring of four
     // (76.7 -> 84.0 %; a ring of four at g = 128 / 64 measured 1-1.5 points below the ring of two).  Only the m = 1 kernels are
@@ -222,15 +221,14 @@ int launch_pair(GemmParams& p) {
           return xg ? launch_pair_k<DT, I, 1, 1, false, 4, true>(p, pp, lds) : launch_pair_k<DT, I, 1, 1, false, 4>(p, pp, lds);
       }
     }
-    return TG_PAIR_M(1, 0);
+    return launch_pair_m<DT, I, 1, QMX, 0>(p, pp, lds, xg, mregs);
   }
   if constexpr (I >= 4) {
-    if (gps == 2) return TG_PAIR_M(2, 0);
+    if (gps == 2) return launch_pair_m<DT, I, 2, QMX, 0>(p, pp, lds, xg, mregs);
   }
   if constexpr (I >= 8) {
-    if (gps == 4) return TG_PAIR_M(4, 0);
+    if (gps == 4) return launch_pair_m<DT, I, 4, QMX, 0>(p, pp, lds, xg, mregs);
   }
-#undef TG_PAIR_M
   return TG_PAIR_NA;
 }
 
@@ -286,22 +284,22 @@ int launch_pair_la(GemmParams& p) {
   }
 }
 
-template <typename DT, int I>
-int pair_q(GemmParams& p) {
-  return p.qmx ? launch_pair<DT, I, true>(p) : launch_pair<DT, I, false>(p);
-}
-template <typename DT, int I, int LA>
-int pair_la_q(GemmParams& p) {
-  return p.qmx ? launch_pair_la<DT, I, true, LA>(p) : launch_pair_la<DT, I, false, LA>(p);
-}
 }  // namespace
 namespace tgx {
-int TG_TU_SUF(pair)(GemmParams& p) { return p.inner == 2 ? pair_q<TG_TU_DT, 2>(p) : p.inner == 4 ? pair_q<TG_TU_DT, 4>(p) : pair_q<TG_TU_DT, 8>(p); }
-int TG_TU_SUF(pair_a)(GemmParams& p) {
-  return p.inner == 1 ? pair_la_q<TG_TU_DT, 1, 1>(p) : p.inner == 2 ? pair_la_q<TG_TU_DT, 2, 1>(p) : pair_la_q<TG_TU_DT, 4, 1>(p);
+int TG_TU_SUF(pair)(GemmParams& p) {  // (innerKTiles 2, 4, 8)
+  return pick<2, 4, 8>(p.inner, [&](auto I_) {
+    return pick<0, 1>(p.qmx, [&](auto QMX_) { return launch_pair<TG_TU_DT, decltype(I_)::value, (decltype(QMX_)::value != 0)>(p); });
+  });
+}
+int TG_TU_SUF(pair_a)(GemmParams& p) {  // (innerKTiles 1, 2, 4)
+  return pick<1, 2, 4>(p.inner, [&](auto I_) {
+    return pick<0, 1>(p.qmx, [&](auto QMX_) { return launch_pair_la<TG_TU_DT, decltype(I_)::value, (decltype(QMX_)::value != 0), 1>(p); });
+  });
 }
 int TG_TU_SUF(pair_b16)(GemmParams& p) {
   // (innerKTiles 8 on the 16x16x32 tiles compiled with > 100 bytes of scratch per lane: not instantiated)
-  return p.inner == 2 ? pair_la_q<TG_TU_DT, 2, 2>(p) : p.inner == 4 ? pair_la_q<TG_TU_DT, 4, 2>(p) : (int)TG_PAIR_NA;
+  return pick<2, 4>(p.inner, [&](auto I_) {
+    return pick<0, 1>(p.qmx, [&](auto QMX_) { return launch_pair_la<TG_TU_DT, decltype(I_)::value, (decltype(QMX_)::value != 0), 2>(p); });
+  });
 }
 }  // namespace tgx

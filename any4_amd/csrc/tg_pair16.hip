@@ -1,7 +1,11 @@
 // tg_pair16.hip -- launch path of w4_gemm_pair16_kernel (one layer per launch); see tg_common.cuh
 #include "tg_common.cuh"
+#if GEMV_TRACE
+static TraceRing g_p16_trace;
+extern "C" TG_API void tg_dev_p16_trace(unsigned long long* buf, int slots) { g_p16_trace.set(buf, slots); }
+#endif
 namespace {
-#include "w4_gemm_pair.cuh"   // shared device helpers (tc_a_index, dot2, chunk_rmsnorm, swiglu16, PairParams); its kernel is not instantiated here
+#include "w4_helpers.cuh"
 #include "w4_gemm_pair16.cuh"
 #include "w4_gemm_pair16_loop.cuh"
 #ifndef TG_P16_XREG_MIN_M
@@ -10,10 +14,6 @@ namespace {
 // Small launches of Bint4 weights (one layer per call): w4_gemm_pair16_kernel, 16 weight rows per workgroup, the whole k-slice
 // of a wave requested up front.  Taken when the launch is too small for the persistent kernel (or its LDS plan does not fit)
 // and the activations (m <= 16 rows) fit in LDS next to the table.
-#if GEMV_TRACE
-unsigned long long* g_p16_trace = nullptr;  // developer builds only (-DGEMV_TRACE=1): [slots][512 workgroups][8 stamps]
-int g_p16_slots = 0, g_p16_launch = 0;
-#endif
 template <typename DT, int I, bool QMX>
 int launch_pair16(const GemmParams& p) {
   const int64_t batch = p.batch;
@@ -42,7 +42,7 @@ int launch_pair16(const GemmParams& p) {
   int phases = 1;
   // XREG (w4_gemm_pair16.cuh): no LDS for activations, one pass whatever m x k is; one workgroup per CU (two rounds at most)
   bool xreg = p.m >= TG_P16_XREG_MIN_M && !p.norm_w && wgs <= 512 && p.ksuper % nsg == 0;
-  if (xreg && g == 32 && I == 4 && ((p.ksuper / nsg + 15) / 16) * nsg > 4) xreg = false;  // (see TG_P16: that instantiation spills)
+  if (xreg && g == 32 && I == 4 && ((p.ksuper / nsg + 15) / 16) * nsg > 4) xreg = false;  // (see the selection below: that instantiation spills)
   if (xreg) {
     pp.x_pitch = 0;
     pp.lds_xs = pp.lds_x;
@@ -65,31 +65,28 @@ int launch_pair16(const GemmParams& p) {
   if (p.dry) return TG_PLAN_PAIR;
   const dim3 grid((unsigned)((p.wrows + 15) / 16), (unsigned)batch);
 #if GEMV_TRACE
-  pp.trace = (g_p16_trace && g_p16_slots > 0 && grid.x <= 512) ? g_p16_trace + (size_t)(g_p16_launch++ % g_p16_slots) * 512 * 8 : nullptr;
+  pp.trace = grid.x <= 512 ? g_p16_trace.next() : nullptr;
 #endif
-#define TG_P16K(CPG_, NORM_, XREG_, CH_) do { if (XREG_ && p.x_tc) TG_P16KX(CPG_, NORM_, XREG_, CH_, XREG_); else TG_P16KX(CPG_, NORM_, XREG_, CH_, false); } while (0)
-#define TG_P16KX(CPG_, NORM_, XREG_, CH_, XTC_) \
-  return launch_lds_kernel<w4_gemm_pair16_kernel<DT, I, QMX, CPG_, 1, NORM_, XREG_, CH_, XTC_>>(grid, dim3(1024), lds, p.st, pp, false)
-#define TG_P16(CPG_)                                              \
-  do {                                                            \
-    if constexpr (!QMX) {                                         \
-      if (p.norm_w) TG_P16K(CPG_, true, false, 4);                \
-    }                                                             \
-    if (xreg && pp.spw <= 4) TG_P16K(CPG_, false, true, 4);  /* the whole slice in one block */ \
-    /* (groups of 32 at innerKTiles 4 with slices longer than a block: 84 ... 128 bytes of scratch -- not instantiated, the LDS path) */ \
-    if constexpr (!(CPG_ == 1 && I == 4)) {                       \
-      if (xreg) TG_P16K(CPG_, false, true, 2);                    \
-    }                                                             \
-    TG_P16K(CPG_, false, false, 4);                               \
-  } while (0)
-  if constexpr (QMX) TG_P16(1);  // mx4: group = 32
-  else if (g == 32) TG_P16(1);
-  else if (g == 64) TG_P16(2);
-  else if (g == 128) TG_P16(4);
-  else TG_P16(8);
-#undef TG_P16K
-#undef TG_P16KX
-#undef TG_P16
+  // the kernel: NORM (the fused norm), else XREG with the whole slice in one block (CH = 4) or in two register sets (CH = 2), else the LDS path
+  // (xreg excludes the norm: see above)
+  return pick<1, 2, 4, 8>(QMX ? 1 : g / 32, [&](auto CPG_) {  // (g = 32, 64, 128, 256; mx4: group = 32)
+    return pick<0, 1>(p.norm_w != nullptr, [&](auto NORM_) {
+      return pick<0, 1>(xreg, [&](auto XREG_) {
+        return pick<2, 4>(xreg && pp.spw > 4 ? 2 : 4, [&](auto CH_) {
+          return pick<0, 1>(xreg && p.x_tc, [&](auto XTC_) {
+            constexpr int CPG = decltype(CPG_)::value, CH = decltype(CH_)::value;
+            constexpr bool NORM = decltype(NORM_)::value, XREG = decltype(XREG_)::value, XTC = decltype(XTC_)::value;
+            // (groups of 32 at innerKTiles 4 with slices longer than a block: 84 ... 128 bytes of scratch -- not instantiated, the LDS path)
+            if constexpr ((QMX && (CPG != 1 || NORM)) || (NORM && XREG) || (!XREG && (CH != 4 || XTC)) || (XREG && CH == 2 && CPG == 1 && I == 4)) {
+              return (int)TG_PAIR_NA;
+            } else {
+              return launch_lds_kernel<w4_gemm_pair16_kernel<DT, I, QMX, CPG, 1, NORM, XREG, CH, XTC>>(grid, dim3(1024), lds, p.st, pp, false);
+            }
+          });
+        });
+      });
+    });
+  });
   }
 }
 
@@ -120,39 +117,30 @@ int launch_pair16_loop(const GemmParams& p) {
   const unsigned lds = (unsigned)pp.lds_nrm + 16u * 16u * 4u;
   if (p.dry) return TG_PLAN_PAIR;
   const int g = 1 << p.gshift;
-#define TG_P16L(CPG_, NORM_) return launch_lds_kernel<w4_gemm_pair16_loop_kernel<DT, CPG_, NORM_>>(dim3((unsigned)cus), dim3(1024), lds, p.st, pp, false)
-  if (p.norm_w) {
-    if (g == 64) TG_P16L(2, true);
-    if (g == 128) TG_P16L(4, true);
-    TG_P16L(8, true);
-  }
-  if (g == 32) TG_P16L(1, false);
-  if (g == 64) TG_P16L(2, false);
-  if (g == 128) TG_P16L(4, false);
-  TG_P16L(8, false);
-#undef TG_P16L
+  return pick<1, 2, 4, 8>(g / 32, [&](auto CPG_) {  // (g = 32, 64, 128, 256)
+    return pick<0, 1>(p.norm_w != nullptr, [&](auto NORM_) {
+      constexpr int CPG = decltype(CPG_)::value;
+      constexpr bool NORM = decltype(NORM_)::value;
+      if constexpr (NORM && CPG == 1) {  // (groups of 32 with the fused norm: not instantiated, see the kernel)
+        return (int)TG_PAIR_NA;
+      } else {
+        return launch_lds_kernel<w4_gemm_pair16_loop_kernel<DT, CPG, NORM>>(dim3((unsigned)cus), dim3(1024), lds, p.st, pp, false);
+      }
+    });
+  });
 }
 
-template <typename DT, int I>
-int p16_q(const GemmParams& p) {
-  return p.qmx ? launch_pair16<DT, I, true>(p) : launch_pair16<DT, I, false>(p);
-}
-template <typename DT>
-int p16_i(const GemmParams& p) {
-  // (innerKTiles 8: every instantiation compiled with 76 ... 308 bytes of scratch per lane at the 128-VGPR budget of a 1024-thread
-  //  workgroup -- not instantiated; those layers take the streaming kernels)
-  return p.inner == 2 ? p16_q<DT, 2>(p) : p.inner == 4 ? p16_q<DT, 4>(p) : (int)TG_PAIR_NA;
-}
 }  // namespace
-#if GEMV_TRACE
-extern "C" TG_API void tg_dev_p16_trace(unsigned long long* buf, int slots) {
-  g_p16_trace = buf;
-  g_p16_slots = slots;
-  g_p16_launch = 0;
-}
-#endif
 int tgx::pair16_loop(const GemmParams& p) {
   if (p.inner != 4 || p.qmx) return TG_PAIR_NA;
-  return p.dt == TG_BF16 ? launch_pair16_loop<BF16>(p) : launch_pair16_loop<F16>(p);
+  return pick_dt(p.dt, [&](auto DT_) { return launch_pair16_loop<decltype(DT_)>(p); });
 }
-int tgx::pair16(const GemmParams& p) { return p.dt == TG_BF16 ? p16_i<BF16>(p) : p16_i<F16>(p); }
+int tgx::pair16(const GemmParams& p) {
+  return pick_dt(p.dt, [&](auto DT_) {
+    // (innerKTiles 8: every instantiation compiled with 76 ... 308 bytes of scratch per lane at the 128-VGPR budget of a 1024-thread
+    //  workgroup -- not instantiated; those layers take the streaming kernels)
+    return pick<2, 4>(p.inner, [&](auto I_) {
+      return pick<0, 1>(p.qmx, [&](auto QMX_) { return launch_pair16<decltype(DT_), decltype(I_)::value, (decltype(QMX_)::value != 0)>(p); });
+    });
+  });
+}

@@ -45,6 +45,5 @@ extern "C" int dg_prefill_attn(const void* qkv, const float* cos, const float* s
   P.k_cache = (uint16_t*)k_cache; P.v_cache = (uint16_t*)v_cache; P.out = (uint16_t*)out;
   P.bs = (int32_t)bs; P.T = (int32_t)T; P.hl = hl; P.kvl = kvl; P.max_seq = (int32_t)max_seq; P.scale = scale;
   hipStream_t st = (hipStream_t)stream;
-  if (dtype == TG_BF16) return d == 128 ? go_rg<BF16, 128>(P, st) : go_rg<BF16, 64>(P, st);
-  return d == 128 ? go_rg<F16, 128>(P, st) : go_rg<F16, 64>(P, st);
+  return pick_dt(dtype, [&](auto DT_) { return d == 128 ? go_rg<decltype(DT_), 128>(P, st) : go_rg<decltype(DT_), 64>(P, st); });
 }

@@ -30,6 +30,7 @@ int go_c(const GemmParams& p, int waves, int splitk) {
 }
 }  // namespace
 int tgx::splitk(const GemmParams& p, int waves, int splitk) {
-  if (p.dt == TG_BF16) return !p.on_right ? go_c<BF16, true>(p, waves, splitk) : go_c<BF16, false>(p, waves, splitk);
-  return !p.on_right ? go_c<F16, true>(p, waves, splitk) : go_c<F16, false>(p, waves, splitk);
+  return pick_dt(p.dt, [&](auto DT_) {
+    return !p.on_right ? go_c<decltype(DT_), true>(p, waves, splitk) : go_c<decltype(DT_), false>(p, waves, splitk);
+  });
 }

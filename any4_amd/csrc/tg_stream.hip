@@ -57,27 +57,18 @@ int launch_stream_sw(const GemmParams& p, StreamParams& sp, int sk) {
     if (xl != 1) return TG_E_SHAPE;  // private slabs with split-K are only instantiated for one piece per lane (m = 1)
   }
   if (p.dry) return TG_PLAN_STREAM;
-#define TG_LAUNCH_STREAM_LK(XL, LK_) \
-  return launch_lds_kernel<w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, false, LK_>>(grid, dim3(SW * 64), lds, p.st, sp, false)
-#define TG_LAUNCH_STREAM(XL)                                                               \
-  do {                                                                                     \
-    if constexpr (!LAYOUT_A && !privx) {                                                   \
-      if (sp.m >= TG_STREAM_LK_MIN && sp.m <= 15) TG_LAUNCH_STREAM_LK(XL, 1);              \
-    }                                                                                      \
-    TG_LAUNCH_STREAM_LK(XL, 0);                                                            \
-  } while (0)
-  if constexpr (privx && SW > 1) {
-    TG_LAUNCH_STREAM(1);
-  } else if constexpr (SW == 1) {
-    if (xl == 1) TG_LAUNCH_STREAM(1);
-    else TG_LAUNCH_STREAM(2);
-  } else {
-    if (xl == 1) TG_LAUNCH_STREAM(1);
-    else if (xl == 2) TG_LAUNCH_STREAM(2);
-    else TG_LAUNCH_STREAM(4);
-  }
-#undef TG_LAUNCH_STREAM
-#undef TG_LAUNCH_STREAM_LK
+  const bool lk = !LAYOUT_A && !privx && sp.m >= TG_STREAM_LK_MIN && sp.m <= 15;
+  // (one wave, SW = 1: more than one piece per lane is XL = 2; private slabs with split-K: XL = 1, see above)
+  return pick<1, 2, 4>(SW == 1 && xl == 4 ? 2 : xl, [&](auto XL_) {
+    return pick<0, 1>(lk, [&](auto LK_) {
+      constexpr int XL = decltype(XL_)::value, LK = decltype(LK_)::value;
+      if constexpr ((privx && SW > 1 && XL != 1) || (SW == 1 && XL == 4) || (LK && (LAYOUT_A || privx))) {
+        return (int)TG_PAIR_NA;
+      } else {
+        return launch_lds_kernel<w4_gemm_stream_kernel<DT, LAYOUT_A, WPL, QMX, SW, STREAM_MINW, XL, privx, false, LK>>(grid, dim3(SW * 64), lds, p.st, sp, false);
+      }
+    });
+  });
 }
 
 // Resident-X launch: 16-wave workgroups, the whole [mrows][k] activation block staged once per workgroup.
@@ -115,14 +106,8 @@ int launch_stream(const GemmParams& p) {
   const int64_t want = mrows == 1 ? 256 * 16 : 2 * 256 * 16;
   while (sk < 8 && wave_tiles * sk < want && nunits >= 8 * sk * upg && mrows * sk * 2 <= 16) sk *= 2;
   // m == 1: every wave stages its own X slab (no barrier in the main loop); a workgroup is the sk waves of one tile
-  if (mrows == 1) {
-    switch (sk) {
-      case 1: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 1>(p, sp, 1);
-      case 2: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 2, true>(p, sp, 2);
-      case 4: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 4, true>(p, sp, 4);
-      default: return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8, true>(p, sp, 8);
-    }
-  }
+  if (mrows == 1)  // (sk = 1, 2, 4, 8)
+    return pick<1, 2, 4, 8>(sk, [&](auto SK_) { return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, decltype(SK_)::value, true>(p, sp, decltype(SK_)::value); });
   // m >= 2, one tile per wave: keep the whole activation block resident in LDS when it fits next to 16 lookup
   // tables (m = 8 at k = 4096 does: 66 KiB + 64 KiB) -- one barrier per workgroup instead of one per unit
   // (measured: wins for m >= 8 at k = 4096 and for m >= 2 at k = 8192; the 16-wave workgroup costs ~15 % in tile-granularity
@@ -145,22 +130,19 @@ int launch_stream(const GemmParams& p) {
   return launch_stream_sw<DT, LAYOUT_A, WPL, QMX, 8>(p, sp, sk);
 }
 
-template <typename DT, bool LAYOUT_A, int WPL>
-int stream_q(const GemmParams& p) {
-  if constexpr (!std::is_same<DT, BF16>::value) {
-    if (p.qmx) return TG_E_DTYPE;
-    return launch_stream<DT, LAYOUT_A, WPL, false>(p);
-  } else {
-    return p.qmx ? launch_stream<DT, LAYOUT_A, WPL, true>(p) : launch_stream<DT, LAYOUT_A, WPL, false>(p);
-  }
-}
-template <typename DT, bool LAYOUT_A>
-int stream_w(const GemmParams& p) {
-  switch (words_per_lane(p)) {
-    case 1: return stream_q<DT, LAYOUT_A, 1>(p);
-    case 2: return stream_q<DT, LAYOUT_A, 2>(p);
-    default: return stream_q<DT, LAYOUT_A, 4>(p);
-  }
-}
 }  // namespace
-int tgx::TG_TU_FN(const GemmParams& p) { return !p.on_right ? stream_w<TG_TU_DT, true>(p) : stream_w<TG_TU_DT, false>(p); }
+int tgx::TG_TU_FN(const GemmParams& p) {
+  using DT = TG_TU_DT;
+  return pick<1, 0>(!p.on_right, [&](auto LAYOUT_A_) {
+    return pick<1, 2, 4>(words_per_lane(p), [&](auto WPL_) {  // (innerKTiles 2, 4, 8 on the right; 1, 2, 4 on the left)
+      return pick<0, 1>(p.qmx, [&](auto QMX_) {
+        constexpr bool QMX = decltype(QMX_)::value != 0;
+        if constexpr (QMX && !std::is_same<DT, BF16>::value) {
+          return (int)TG_E_DTYPE;
+        } else {
+          return launch_stream<DT, (decltype(LAYOUT_A_)::value != 0), decltype(WPL_)::value, QMX>(p);
+        }
+      });
+    });
+  });
+}

@@ -79,8 +79,7 @@ int tile_w8(GemmParams& p) {
   if (p.dry) return TG_PLAN_TILE;
   const bool two = p.gshift >= 7 && (ksuper / splits) % 2 == 0;   // (two super-tiles per step: one group per step needs g >= 128)
   return tile_batch(p, ksuper, tiles_m, tiles_n, splits, [&](const TileParams& tp) {
-    if (p.dt == TG_BF16) return p.on_right ? go_w8<BF16, 1>(tp, two, p.st) : go_w8<BF16, 2>(tp, two, p.st);
-    return p.on_right ? go_w8<F16, 1>(tp, two, p.st) : go_w8<F16, 2>(tp, two, p.st);
+    return pick_dt(p.dt, [&](auto DT_) { return p.on_right ? go_w8<decltype(DT_), 1>(tp, two, p.st) : go_w8<decltype(DT_), 2>(tp, two, p.st); });
   });
 }
 
@@ -112,7 +111,8 @@ int tile(GemmParams& p) {
   if (p.dry) return TG_PLAN_TILE;
   const bool two = !wide && (p.ksuper / splits) % 2 == 0;
   return tile_batch(p, p.ksuper, tiles_m, tiles_n, splits, [&](const TileParams& tp) {
-    return qmx ? go_dt<BF16, true>(tp, wide, small, two, p.st) : p.dt == TG_BF16 ? go_dt<BF16>(tp, wide, small, two, p.st) : go_dt<F16>(tp, wide, small, two, p.st);
+    if (qmx) return go_dt<BF16, true>(tp, wide, small, two, p.st);
+    return pick_dt(p.dt, [&](auto DT_) { return go_dt<decltype(DT_)>(tp, wide, small, two, p.st); });
   });
 }
 }  // namespace tgx

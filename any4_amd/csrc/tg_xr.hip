@@ -1,7 +1,7 @@
 // tg_xr.hip -- launch path of w4_gemm_xr_kernel (stacked launches, activations resident in registers); see tg_common.cuh
 #include "tg_common.cuh"
 namespace {
-#include "w4_gemm_pair.cuh"   // shared device helpers; its kernel is not instantiated here
+#include "w4_helpers.cuh"
 #include "w4_gemm_xr.cuh"
 // Bint4 weights, stacked launches, TG_XR_MIN_M ... 16 activation rows, k = 4096: w4_gemm_xr_kernel (one 8-wave workgroup per CU, the
 // activations of a wave's k-slice resident in its registers, 64-row work items, two tables).  No workspace, no pre-pass.
@@ -84,22 +84,23 @@ int launch_pair_xr_n(const GemmParams& p, const XrWindow* win = nullptr) {
   if (single) wgs = items < (int64_t)wgs ? (unsigned)items : wgs;
   else if (items < TG_XR_MIN_ITEMS_PER_WG * (int64_t)wgs) return TG_PAIR_NA;
   // (a failed preparation -- a part with less LDS: the older kernels take over)
-#define TG_XR_LAUNCH(CPG_) \
-  return launch_lds_kernel<w4_gemm_xr_kernel<DT, I, NCH, CPG_, (((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R), false, PK>>(dim3(wgs), dim3(512), lds, p.st, xp, true)
   if constexpr (QMX) {
     return launch_lds_kernel<w4_gemm_xr_kernel<DT, I, NCH, 1, TG_XR_RMX, true>>(dim3(wgs), dim3(512), lds, p.st, xp, true);
   } else {
+    auto launch = [&](auto CPG_) {
+      constexpr int CPG = decltype(CPG_)::value, R = ((NCH > 24 && !PK) || NCH > 32) ? TG_XR_R8K : TG_XR_R;
+      if constexpr (CPG == 8 && NCH % 8 != 0) {  // (a wave's slice must hold whole groups)
+        return (int)TG_PAIR_NA;
+      } else {
+        return launch_lds_kernel<w4_gemm_xr_kernel<DT, I, NCH, CPG, R, false, PK>>(dim3(wgs), dim3(512), lds, p.st, xp, true);
+      }
+    };
 #ifdef TG_DEV_MIN
-  TG_XR_LAUNCH(4);
+    return pick<4>(cpg, launch);
 #else
-  if (cpg == 1) TG_XR_LAUNCH(1);
-  if (cpg == 2) TG_XR_LAUNCH(2);
-  if (cpg == 4) TG_XR_LAUNCH(4);
-  if constexpr (NCH % 8 == 0) TG_XR_LAUNCH(8);
-  return TG_PAIR_NA;  // (a wave's slice must hold whole groups)
+    return pick<1, 2, 4, 8>(cpg, launch);
 #endif
   }
-#undef TG_XR_LAUNCH
 #ifdef TG_DEV_MIN
   }
 #endif
@@ -220,10 +221,10 @@ int launch_pair_xr(GemmParams& p) {
   }
   return TG_PAIR_NA;
 }
-template <typename DT>
-int xr_i(GemmParams& p) {
-  if (p.inner != 4) return TG_PAIR_NA;
-  return p.qmx ? launch_pair_xr<DT, 4, true>(p) : launch_pair_xr<DT, 4, false>(p);
-}
 }  // namespace
-int tgx::pair_xr(GemmParams& p) { return p.dt == TG_BF16 ? xr_i<BF16>(p) : xr_i<F16>(p); }
+int tgx::pair_xr(GemmParams& p) {
+  if (p.inner != 4) return TG_PAIR_NA;
+  return pick_dt(p.dt, [&](auto DT_) {
+    return pick<0, 1>(p.qmx, [&](auto QMX_) { return launch_pair_xr<decltype(DT_), 4, (decltype(QMX_)::value != 0)>(p); });
+  });
+}

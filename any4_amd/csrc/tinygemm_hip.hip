@@ -172,10 +172,10 @@ int tg_convert_to_Bint4(const int32_t* in, int64_t n, int64_t k, int I, int32_t*
   const int64_t nTiles = cdiv(n, 8), ksuper = k / (I * 16);
   dim3 grid((unsigned)cdiv(k, 512), (unsigned)nTiles);
   hipStream_t st = (hipStream_t)stream;
-  if (I == 2) hipLaunchKernelGGL(pack_Bint4_kernel<2>, grid, dim3(256), 0, st, in, out, n, k, ksuper);
-  else if (I == 4) hipLaunchKernelGGL(pack_Bint4_kernel<4>, grid, dim3(256), 0, st, in, out, n, k, ksuper);
-  else hipLaunchKernelGGL(pack_Bint4_kernel<8>, grid, dim3(256), 0, st, in, out, n, k, ksuper);
-  return launch_status();
+  return pick<2, 4, 8>(I, [&](auto I_) {
+    hipLaunchKernelGGL(pack_Bint4_kernel<decltype(I_)::value>, grid, dim3(256), 0, st, in, out, n, k, ksuper);
+    return launch_status();
+  });
 }
 
 int tg_convert_to_Aint4(const int32_t* in, int64_t m, int64_t k, int I, int32_t* out, int device, tg_stream_t stream) {
@@ -188,10 +188,10 @@ int tg_convert_to_Aint4(const int32_t* in, int64_t m, int64_t k, int I, int32_t*
   const int64_t mTiles = cdiv(m, 16), ksuper = cdiv(k, I * 16);
   dim3 grid((unsigned)cdiv(ksuper * I * 16, 256), (unsigned)mTiles);
   hipStream_t st = (hipStream_t)stream;
-  if (I == 1) hipLaunchKernelGGL(pack_Aint4_kernel<1>, grid, dim3(256), 0, st, in, out, m, k, ksuper);
-  else if (I == 2) hipLaunchKernelGGL(pack_Aint4_kernel<2>, grid, dim3(256), 0, st, in, out, m, k, ksuper);
-  else hipLaunchKernelGGL(pack_Aint4_kernel<4>, grid, dim3(256), 0, st, in, out, m, k, ksuper);
-  return launch_status();
+  return pick<1, 2, 4>(I, [&](auto I_) {
+    hipLaunchKernelGGL(pack_Aint4_kernel<decltype(I_)::value>, grid, dim3(256), 0, st, in, out, m, k, ksuper);
+    return launch_status();
+  });
 }
 
 int tg_unpack_int4(const int32_t* packed, int layout_a, int64_t rows, int64_t k, int I, int32_t* codes, int device, tg_stream_t stream) {
@@ -232,15 +232,15 @@ int tg_dequant_w4_panel(const void* packed, const void* qinfo, const void* lut, 
   const int chk = k % 2048 == 0 ? 4 : 1;   // chunks of 512 k per wave
   const unsigned bs = k / 8 / chk < 256 ? (unsigned)(k / 8 / chk) : 256u;   // (a row's threads: a multiple of 64)
   const dim3 grid((unsigned)cdiv(k / 8 / chk, 256), (unsigned)(wrows < 65535 ? wrows : 65535), (unsigned)cdiv(wrows, 65535));
-#define TG_DQ2(DTT, I_, C_)                                                                                                                       \
-  hipLaunchKernelGGL((dequant_w4_kernel<DTT, I_, C_>), grid, dim3(bs), 0, (hipStream_t)stream, (const uint32_t*)packed, (const uint16_t*)qinfo, \
-                     (const uint16_t*)lut, (uint16_t*)out, wrows, wrows_q, k, ksuper, gshift, qtype)
-#define TG_DQ(DTT, I_) do { if (chk == 4) TG_DQ2(DTT, I_, 4); else TG_DQ2(DTT, I_, 1); } while (0)
-  if (dtype == TG_BF16) { if (I == 2) TG_DQ(BF16, 2); else if (I == 4) TG_DQ(BF16, 4); else TG_DQ(BF16, 8); }
-  else { if (I == 2) TG_DQ(F16, 2); else if (I == 4) TG_DQ(F16, 4); else TG_DQ(F16, 8); }
-#undef TG_DQ2
-#undef TG_DQ
-  return launch_status();
+  return pick_dt(dtype, [&](auto DT_) {
+    return pick<2, 4, 8>(I, [&](auto I_) {
+      return pick<4, 1>(chk, [&](auto CHK_) {
+        hipLaunchKernelGGL((dequant_w4_kernel<decltype(DT_), decltype(I_)::value, decltype(CHK_)::value>), grid, dim3(bs), 0, (hipStream_t)stream,
+                           (const uint32_t*)packed, (const uint16_t*)qinfo, (const uint16_t*)lut, (uint16_t*)out, wrows, wrows_q, k, ksuper, gshift, qtype);
+        return launch_status();
+      });
+    });
+  });
 }
 
 int tg_convert_to_A16(const void* rm, int64_t m, int64_t k, void* tc, int device, tg_stream_t stream) {
@@ -578,10 +578,10 @@ int tg_convert_to_Bint8(const int32_t* in, int64_t n, int64_t k, int I, int32_t*
   const int64_t ksuper = k / (I * 16), total = cdiv(n, 8) * ksuper * 32 * I;
   const unsigned blocks = (unsigned)(cdiv(total, 256) < 8192 ? cdiv(total, 256) : 8192);
   hipStream_t st = (hipStream_t)stream;
-  if (I == 1) hipLaunchKernelGGL(pack_Bint8_kernel<1>, dim3(blocks), dim3(256), 0, st, in, out, n, k, ksuper, total);
-  else if (I == 2) hipLaunchKernelGGL(pack_Bint8_kernel<2>, dim3(blocks), dim3(256), 0, st, in, out, n, k, ksuper, total);
-  else hipLaunchKernelGGL(pack_Bint8_kernel<4>, dim3(blocks), dim3(256), 0, st, in, out, n, k, ksuper, total);
-  return launch_status();
+  return pick<1, 2, 4>(I, [&](auto I_) {
+    hipLaunchKernelGGL(pack_Bint8_kernel<decltype(I_)::value>, dim3(blocks), dim3(256), 0, st, in, out, n, k, ksuper, total);
+    return launch_status();
+  });
 }
 
 int tg_convert_to_Aint8(const int32_t* in, int64_t m, int64_t k, int I, int32_t* out, int device, tg_stream_t stream) {
@@ -593,9 +593,10 @@ int tg_convert_to_Aint8(const int32_t* in, int64_t m, int64_t k, int I, int32_t*
   const int64_t kouter = cdiv(cdiv(k, 16), I), total = cdiv(m, 16) * kouter * 32 * I * 2;
   const unsigned blocks = (unsigned)(cdiv(total, 256) < 8192 ? cdiv(total, 256) : 8192);
   hipStream_t st = (hipStream_t)stream;
-  if (I == 1) hipLaunchKernelGGL(pack_Aint8_kernel<1>, dim3(blocks), dim3(256), 0, st, in, out, m, k, kouter, total);
-  else hipLaunchKernelGGL(pack_Aint8_kernel<2>, dim3(blocks), dim3(256), 0, st, in, out, m, k, kouter, total);
-  return launch_status();
+  return pick<1, 2>(I, [&](auto I_) {
+    hipLaunchKernelGGL(pack_Aint8_kernel<decltype(I_)::value>, dim3(blocks), dim3(256), 0, st, in, out, m, k, kouter, total);
+    return launch_status();
+  });
 }
 
 // dry: 0 launch, 2 report the workspace the fastest kernel wants (tg_gemm_w8_workspace_bytes)
@@ -620,19 +621,19 @@ static int gemm_w8_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
     if (trc != TG_PAIR_NA) return trc == TG_PLAN_TILE ? 0 : trc;
     if (dry) return 0;
   }
-#define TG_W8(DTT)                                                   \
-  do {                                                               \
-    if (p.on_right) {                                                \
-      if (p.inner == 1) return launch_w8<DTT, false, 1>(p);          \
-      if (p.inner == 2) return launch_w8<DTT, false, 2>(p);          \
-      return launch_w8<DTT, false, 4>(p);                            \
-    }                                                                \
-    if (p.inner == 1) return launch_w8<DTT, true, 1>(p);             \
-    return launch_w8<DTT, true, 2>(p);                               \
-  } while (0)
-  if (p.dt == TG_BF16) TG_W8(BF16);
-  TG_W8(F16);
-#undef TG_W8
+  return pick_dt(p.dt, [&](auto DT_) {
+    return pick<0, 1>(!p.on_right, [&](auto LAYOUT_A_) {
+      return pick<1, 2, 4>(p.inner, [&](auto I_) {  // (innerKTiles 1, 2, 4 on the right; 1, 2 on the left)
+        constexpr bool LAYOUT_A = decltype(LAYOUT_A_)::value != 0;
+        constexpr int I = decltype(I_)::value;
+        if constexpr (LAYOUT_A && I == 4) {
+          return (int)TG_PAIR_NA;
+        } else {
+          return launch_w8<decltype(DT_), LAYOUT_A, I>(p);
+        }
+      });
+    });
+  });
 #endif
 }
 
@@ -667,16 +668,19 @@ int tg_gemm_f16(const void* x, const void* w, void* y, int64_t m, int64_t wrows,
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)cdiv(wrows, 16), (unsigned)cdiv(m, 16));
   constexpr int WAVES = 8;
-  if (dtype == TG_BF16) {
-    if (w_on_right && I == 2) hipLaunchKernelGGL((f16_gemm_kernel<BF16, false, WAVES, 2>), grid, dim3(WAVES * 64), 0, st, p);
-    else if (w_on_right) hipLaunchKernelGGL((f16_gemm_kernel<BF16, false, WAVES, 1>), grid, dim3(WAVES * 64), 0, st, p);
-    else hipLaunchKernelGGL((f16_gemm_kernel<BF16, true, WAVES, 1>), grid, dim3(WAVES * 64), 0, st, p);
-  } else {
-    if (w_on_right && I == 2) hipLaunchKernelGGL((f16_gemm_kernel<F16, false, WAVES, 2>), grid, dim3(WAVES * 64), 0, st, p);
-    else if (w_on_right) hipLaunchKernelGGL((f16_gemm_kernel<F16, false, WAVES, 1>), grid, dim3(WAVES * 64), 0, st, p);
-    else hipLaunchKernelGGL((f16_gemm_kernel<F16, true, WAVES, 1>), grid, dim3(WAVES * 64), 0, st, p);
-  }
-  return launch_status();
+  return pick_dt(dtype, [&](auto DT_) {
+    return pick<0, 1>(!w_on_right, [&](auto LAYOUT_A_) {
+      return pick<1, 2>(I, [&](auto I_) {  // (innerKTiles 1, 2 on the right; 1 on the left)
+        constexpr bool LAYOUT_A = decltype(LAYOUT_A_)::value != 0;
+        if constexpr (LAYOUT_A && decltype(I_)::value == 2) {
+          return (int)TG_PAIR_NA;
+        } else {
+          hipLaunchKernelGGL((f16_gemm_kernel<decltype(DT_), LAYOUT_A, WAVES, decltype(I_)::value>), grid, dim3(WAVES * 64), 0, st, p);
+          return launch_status();
+        }
+      });
+    });
+  });
 }
 
 }  // extern "C"

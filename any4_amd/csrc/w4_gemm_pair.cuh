@@ -51,52 +51,7 @@
 //                runs across item boundaries, and the LUT rows of the next item are requested at the start of the current
 //                one, so the weight stream never drains while a table is rebuilt.  Two barriers per item.
 #pragma once
-
-// Element (r, c) of a matrix kept in the reference's m16n8k16 A-fragment order [ceil(rows/16)][ctiles = ceil(cols/16)][32][8]
-// (TinyGemmConvertA.cu:19-141: lane t = 4 (r & 7) + (c & 7) / 2 holds (r, c0) (r, c0+1) (r+8, c0) (r+8, c0+1) and the same at
-// c0 + 8): the "TC" activations / outputs of tinygemm_y_f16TC_x_f16TC_w_*TC with the weights on the right.
-__device__ __forceinline__ int64_t tc_a_index(int r, int c, int ctiles) {
-  const int t = (r & 7) * 4 + ((c & 7) >> 1);
-  const int j = (c & 1) + 2 * ((r >> 3) & 1) + 4 * ((c >> 3) & 1);
-  return (((int64_t)(r >> 4) * ctiles + (c >> 4)) * 32 + t) * 8 + j;
-}
-// the 32 k of chunk ch of row a (16 dwords in k order) from A-fragment-order activations
-__device__ __forceinline__ void tc_a_load_chunk(const char* xb, int a, int ch, int ktiles, uint32_t (&d)[16]) {
-#pragma unroll
-  for (int dw = 0; dw < 16; ++dw) d[dw] = *reinterpret_cast<const uint32_t*>(xb + tc_a_index(a, ch * 32 + 2 * dw, ktiles) * 2);
-}
-
-// mx4 on gfx950 without a table: v_cvt_scalef32_pk_bf16_fp4 converts the two fp4-e2m1 codes of one byte of a packed word into a pair
-// of bf16 values times an f32 scale -- the dequantised weights (fp4[code] * 2^(e - 127), exact) in ONE vector instruction per two
-// weights, no LDS lookup, and with the group's scale already inside the operand no per-group accumulator update either.  Checked
-// against the e2m1 table for every byte value, every byte position and scales from 2^-127 (denormal) to 2^127 and NaN (e = 255):
-// tools/ubench/mx4_cvt_probe.hip.
-__device__ __forceinline__ u32x4 mx4_cvt_word(uint32_t w, float scale) {
-  u32x4 r;
-  r[0] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-  r[1] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-  r[2] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-  r[3] = __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-  return r;
-}
-
-// ... one byte (sel = 0 ... 3, a constant after unrolling: the switch folds)
-__device__ __forceinline__ uint32_t mx4_cvt_byte(uint32_t w, float scale, int sel) {
-  switch (sel) {
-    case 0: return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 0));
-    case 1: return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 1));
-    case 2: return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 2));
-    default: return __builtin_bit_cast(uint32_t, __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(w, scale, 3));
-  }
-}
-
-template <typename DT>
-__device__ __forceinline__ float dot2_pair(uint32_t a, uint32_t b, float acc) {
-  if constexpr (std::is_same<DT, BF16>::value)
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, a), __builtin_bit_cast(bf16x2, b), acc, false);
-  else
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, a), __builtin_bit_cast(f16x2, b), acc, false);
-}
+#include "w4_helpers.cuh"
 
 struct PairParams {
   const char* x;
@@ -143,75 +98,6 @@ struct PairParams {
   int32_t y_tiles;
 };
 
-typedef __attribute__((ext_vector_type(16))) float f32x16;
-
-template <typename DT>
-__device__ __forceinline__ f32x16 mfma32(u32x4 a, u32x4 b, f32x16 c) {
-  if constexpr (std::is_same<DT, BF16>::value)
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-typedef __attribute__((ext_vector_type(4))) float f32x4_t;
-template <typename DT>
-__device__ __forceinline__ f32x4_t mfma16(u32x4 a, u32x4 b, f32x4_t c) {
-  if constexpr (std::is_same<DT, BF16>::value)
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-  else
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-
-__device__ __forceinline__ uint32_t bfi(uint32_t mask, uint32_t a, uint32_t b) {  // (mask & a) | (~mask & b)
-  uint32_t d;
-  asm("v_bfi_b32 %0, %1, %2, %3" : "=v"(d) : "s"(mask), "v"(a), "v"(b));
-  return d;
-}
-
-template <typename DT>
-__device__ __forceinline__ float dot2_ones(uint32_t pair, float acc) {
-  if constexpr (std::is_same<DT, BF16>::value)
-    return __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, pair), __builtin_bit_cast(bf16x2, 0x3f803f80u), acc, false);
-  else
-    return __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, pair), __builtin_bit_cast(f16x2, 0x3c003c00u), acc, false);
-}
-
-// sum of squares of the 32 values of a staged chunk (16 packed pairs), f32
-template <typename DT>
-__device__ __forceinline__ float chunk_sumsq(const uint32_t (&d)[16]) {
-  float s = 0.f;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if constexpr (std::is_same<DT, BF16>::value)
-      s = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, d[j]), __builtin_bit_cast(bf16x2, d[j]), s, false);
-    else
-      s = __builtin_amdgcn_fdot2(__builtin_bit_cast(f16x2, d[j]), __builtin_bit_cast(f16x2, d[j]), s, false);
-  }
-  return s;
-}
-// LlamaRMSNorm of a staged chunk: x' = RNE16(RNE16(x rs) g), g = the chunk's 32 norm weights (64 bytes at gsrc): the formula
-// and rounding points of dg_add_rmsnorm (decode_glue.cuh)
-template <typename DT>
-__device__ __forceinline__ void chunk_rmsnorm(uint32_t (&d)[16], float rs, const u32x4 (&gw)[4]) {
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const u32x4 g = gw[j];
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const uint32_t v = d[4 * j + e];
-      const float lo = DT::to_f32(DT::from_f32(DT::lo_f32(v) * rs)) * DT::lo_f32(g[e]);
-      const float hi = DT::to_f32(DT::from_f32(DT::hi_f32(v) * rs)) * DT::hi_f32(g[e]);
-      d[4 * j + e] = DT::pack2(lo, hi);
-    }
-  }
-}
-// SwiGLU of two 16-bit GEMM outputs (dg_swiglu's formula): RNE16(RNE16(silu(g)) u)
-template <typename DT>
-__device__ __forceinline__ uint16_t swiglu16(float gsum, float usum) {
-  const float g = DT::to_f32(DT::from_f32(gsum)), u = DT::to_f32(DT::from_f32(usum));
-  return DT::from_f32(DT::to_f32(DT::from_f32(g / (1.f + __expf(-g)))) * u);
-}
-
 // I     = innerKTiles of the Bint4 layout (2, 4, 8): k super-tile = 16 I, I words per lane and super-tile
 // GPS   = quantisation groups per super-tile (1 when group >= 16 I)
 // MR    = 1: m = 1 (one accumulator register per tile is finalised and exchanged); else the accumulator registers that can
@@ -248,7 +134,7 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
   constexpr int RW = T16 ? 32 : 32 * TILES;
   static_assert(!T16 || (XG && MR == 4 && (LB || I == 2 || I == 4)), "16x16x32 tiles: workspace activations, one pass of up to 16 rows");
   constexpr int NW = LB ? I / 2 : I;    // packed words per lane, word set and super-tile
-  using acc_t = typename std::conditional<T16, f32x4_t, f32x16>::type;
+  using acc_t = typename std::conditional<T16, f32x4, f32x16>::type;
   constexpr int CPS = I / 2;            // 32-k chunks per super-tile
   constexpr int CPG = CPS / GPS;        // chunks per group inside a super-tile (GPS > 1 only)
   constexpr int MREGS = MR == 1 ? 4 : MR;  // accumulator registers of a row set
@@ -908,8 +794,8 @@ __global__ void __launch_bounds__(512, 4) w4_gemm_pair_kernel(const PairParams p
         for (int t = 0; t < TILES; ++t) {
           if constexpr (DOT) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) dacc[t] = dot2_pair<DT>(bf[t][j], xf[j], dacc[t]);
-          } else if constexpr (T16) acc[t] = mfma16<DT>(xf, bf[t], (gfirst && !MXC) ? zero16 : acc[t]);
+            for (int j = 0; j < 4; ++j) dacc[t] = dot2<DT>(bf[t][j], xf[j], dacc[t]);
+          } else if constexpr (T16) acc[t] = DT::mfma(xf, bf[t], (gfirst && !MXC) ? zero16 : acc[t]);
           else if (!DIFF && gfirst && !MXC) acc[t] = mfma32<DT>(xf, bf[t], zero16);
           else acc[t] = mfma32<DT>(xf, bf[t], acc[t]);
         }

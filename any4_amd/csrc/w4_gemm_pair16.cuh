@@ -59,17 +59,12 @@ struct Pair16Params {
   const char* norm_w;       // fused RMSNorm of the activations (tg_w4_gemm.norm_weight; phases == 1 only), nullptr = off
   float norm_eps;
   int32_t epilogue;         // TG_EPI_SWIGLU: rows in blocks of 8 gate + 8 up, y is [m][wrows / 2]
-  int32_t x_tc, y_tc;  // 1: activations / output in A-fragment order (tc_a_index, w4_gemm_pair.cuh)
+  int32_t x_tc, y_tc;  // 1: activations / output in A-fragment order (tc_a_index, w4_helpers.cuh)
   int32_t y_tiles;     // ceil(wrows / 16)
 #if GEMV_TRACE
-  unsigned long long* trace;  // developer builds (-DGEMV_TRACE=1): [workgroup][8] s_memrealtime stamps
+  unsigned long long* trace;  // developer builds (tg_trace.cuh): [workgroup][8] s_memrealtime stamps
 #endif
 };
-#if GEMV_TRACE
-#define P16_STAMP(i) do { if (p.trace && tid == 0) tr[i] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define P16_STAMP(i) do { } while (0)
-#endif
 
 // I   = innerKTiles of the Bint4 layout (2, 4, 8): I / 2 words per lane and super-tile (one per 32-k chunk)
 // CPG = 32-k chunks per quantisation group (1, 2, 4, 8): a full block of CH super-tiles then has its group boundaries at fixed
@@ -95,10 +90,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
                  "s"(p.stride_x), "s"(p.stride_w), "s"(p.stride_qinfo), "s"(p.stride_lut), "s"(p.gshift), "s"(p.ngroups), "s"(p.qtype));
   }
   const int tid = threadIdx.x;
-#if GEMV_TRACE
-  unsigned long long tr[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-#endif
-  P16_STAMP(0);
+  TG_TRACE_BEGIN();
+  TG_STAMP_IF(p.trace && tid == 0, 0);
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int n = lane & 15, q = lane >> 4;
@@ -347,9 +340,9 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
         if ((idx & 15) >= p.m) *(lds_fptr)(lds_xs + (uint32_t)(idx * 4)) = 0.f;
     if (tid == 0) *(lds_u32x4ptr)(lds_x + (uint32_t)(p.m * p.x_pitch)) = u32x4{0, 0, 0, 0};  // zero piece for padding rows
   };
-  P16_STAMP(1);
+  TG_STAMP_IF(p.trace && tid == 0, 1);
   if constexpr (!XREG) x_stage(0, true);
-  // (mx4: no table -- the weights are converted in registers by v_cvt_scalef32_pk_bf16_fp4, w4_gemm_pair.cuh: mx4_cvt_word)
+  // (mx4: no table -- the weights are converted in registers by v_cvt_scalef32_pk_bf16_fp4, w4_helpers.cuh: mx4_cvt_word)
 #pragma unroll
   for (int t = 0; t < (QMX ? 0 : TPW); ++t) {
     // thread = (column tcol, high nibble (tid >> 5) & 15, half tid >> 9 of the low nibbles): entries (lut[lo], lut[hi])
@@ -374,11 +367,11 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
   // XREG: the fragment transposes (x_arrange) stay behind the barrier: in front of it no difference (7.71 vs 7.67 us) -- the stamps say the
   // LAST wave's activations land ~3.8 us after the requests whatever the order.  Every CU of an XCD pulls the same 128 KiB of x out of that
   // XCD's L2 -- 4 MiB per XCD and launch at ~2 TB/s: the launch is bound by that broadcast, not by the weights (profiles/r05_p16_trace_xfirst.txt)
-  P16_STAMP(2);
+  TG_STAMP_IF(p.trace && tid == 0, 2);
   // (`__syncthreads()` waits vmcnt(0) -- for every weight and activation request of the wave -- where only the table's LDS stores have to be
   //  done; a barrier spelled out without that wait measured 0.35 us SLOWER in either request order)
   __syncthreads();
-  P16_STAMP(3);
+  TG_STAMP_IF(p.trace && tid == 0, 3);
 
   // ---- main loop ----
   const bool a_on = n < p.m;  // (as the A operand's row index: lane (i = n, q))
@@ -391,8 +384,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
   // this lane's accumulator rows are activation rows 4 q + r
   const uint32_t xs_lane = lds_xs + (uint32_t)(4 * q * 4);
 
-  const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
-  f32x4_t acc[TPW];
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[TPW];
   float yacc[TPW][4];
   float gs[TPW], gz[TPW];
 #pragma unroll
@@ -403,7 +396,7 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
     for (int r = 0; r < 4; ++r) yacc[t][r] = 0.f;
   }
   f32x4 xsv = {0.f, 0.f, 0.f, 0.f};
-  f32x4_t xsacc = zero4;  // XREG: the group's activation sums, rows 4 q + r (an MFMA against ones)
+  f32x4 xsacc = zero4;  // XREG: the group's activation sums, rows 4 q + r (an MFMA against ones)
   const uint32_t one2 = DT::pack2(1.f, 1.f);
   const u32x4 ones = {one2, one2, one2, one2};
 
@@ -423,7 +416,7 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
           gs[t] = __builtin_fmaf(sc, 0.f, sc);                         // ... -> NaN
         }
         bf[t] = mx4_cvt_word(wreg[t][j][jc], gs[t]);
-        acc[t] = mfma16<DT>(xf, bf[t], acc[t]);
+        acc[t] = DT::mfma(xf, bf[t], acc[t]);
       }
       return;
     }
@@ -447,9 +440,9 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
       if constexpr (!QMX && !XREG) xsv = *(lds_cf32x4ptr)(xs_lane + (uint32_t)(((((chunk - chunk_ph) * 32) >> p.gshift) * 16) * 4));
     }
 #pragma unroll
-    for (int t = 0; t < TPW; ++t) acc[t] = mfma16<DT>(xf, bf[t], gfirst ? zero4 : acc[t]);
+    for (int t = 0; t < TPW; ++t) acc[t] = DT::mfma(xf, bf[t], gfirst ? zero4 : acc[t]);
     if constexpr (XREG && !QMX) {
-      xsacc = mfma16<DT>(xf, ones, gfirst ? zero4 : xsacc);
+      xsacc = DT::mfma(xf, ones, gfirst ? zero4 : xsacc);
       if (glast) xsv = f32x4{xsacc[0], xsacc[1], xsacc[2], xsacc[3]};
     }
     if (glast) {
@@ -503,10 +496,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
     chunk_ph = ph * p.ksuper_p * CPS;
     if (nl <= CH || (XREG && CH == 4)) {  // (wave-uniform) the whole slice was requested up front (XREG, CH = 4: always -- the host's choice)
       x_arrange(xfA);
-#if GEMV_TRACE
-      asm volatile("" ::"v"(xfA[0]), "v"(xfA[NXF - 1]));
-#endif
-      P16_STAMP(4);
+      TG_TRACE_KEEP("v"(xfA[0]), "v"(xfA[NXF - 1]));
+      TG_STAMP_IF(p.trace && tid == 0, 4);
       if (nl > 0) consume_block(wregA, qregA, xfA, 0);
       continue;
     }
@@ -538,23 +529,16 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_kernel(const Pair16Params
       for (int r = 0; r < 4; ++r) yacc[t][r] = acc[t][r];
   }
   // ---- split-K tail: partial sums of the 16 waves meet in the (now unused) table's LDS, added in wave order ----
-#if GEMV_TRACE
-  asm volatile("" ::"v"(yacc[0][0]), "v"(yacc[0][3]));
-#endif
-  P16_STAMP(5);
+  TG_TRACE_KEEP("v"(yacc[0][0]), "v"(yacc[0][3]));
+  TG_STAMP_IF(p.trace && tid == 0, 5);
   __syncthreads();
 #pragma unroll
   for (int t = 0; t < TPW; ++t)
 #pragma unroll
     for (int r = 0; r < 4; ++r) *(lds_fptr)((uint32_t)((((t * WAVES + wave) * 4 + r) * 64 + lane) * 4)) = yacc[t][r];
   __syncthreads();
-  P16_STAMP(6);
-#if GEMV_TRACE
-  if (p.trace && tid == 0) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) p.trace[(size_t)blockIdx.x * 8 + i] = tr[i];
-  }
-#endif
+  TG_STAMP_IF(p.trace && tid == 0, 6);
+  TG_TRACE_FLUSH(p.trace && tid == 0, p.trace, 7);
   if (tid < 256 * TPW) {
     const int t = tid >> 8, r = (tid >> 6) & 3, l = tid & 63;
     const int a = XQ ? 4 * r + (l >> 4) : 4 * (l >> 4) + r, row = row0 + 16 * t + (l & 15);  // (XQ: the A operand's rows are rotated)

@@ -189,14 +189,14 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_loop_kernel(const Pair16L
     }
   }
 
-  const f32x4_t zero4 = {0.f, 0.f, 0.f, 0.f};
+  const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
   const uint32_t one2 = DT::pack2(1.f, 1.f);
   const u32x4 ones = {one2, one2, one2, one2};
   uint32_t colreg = (uint32_t)((16 * (q & 1) + n) * 4);
 
   // one tile: 8 chunks x (4 lookups, the tile's MFMA, the activation sums' MFMA against ones), a scale / zero update per group
   auto consume = [&](const W& r, float (&yacc)[4]) {
-    f32x4_t acc = zero4, xs = zero4;
+    f32x4 acc = zero4, xs = zero4;
 #pragma unroll
     for (int u = 0; u < NCHK; ++u) {
       const uint32_t w = r.w[u / CPS][u % CPS];
@@ -204,8 +204,8 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_loop_kernel(const Pair16L
 #pragma unroll
       for (int e = 0; e < 4; ++e) bf[e] = *(lds_cu32ptr)(__builtin_amdgcn_perm(w, colreg, 0x0c0c0400u + ((uint32_t)e << 8)));
       const bool gfirst = u % CPG == 0, glast = u % CPG == CPG - 1;
-      acc = mfma16<DT>(xf[u], bf, gfirst ? zero4 : acc);
-      xs = mfma16<DT>(xf[u], ones, gfirst ? zero4 : xs);
+      acc = DT::mfma(xf[u], bf, gfirst ? zero4 : acc);
+      xs = DT::mfma(xf[u], ones, gfirst ? zero4 : xs);
       if (glast) {
         const uint32_t qv = r.qv[u / CPG];
         const float gs = DT::lo_f32(qv), gz = DT::hi_f32(qv);

@@ -67,7 +67,7 @@ struct XrParams {
 // NCH = 32-k chunks of a wave's k-slice (k = 256 NCH)
 // CPG = 32-k chunks per quantisation group, at most NCH (a group that spans several waves' slices: CPG = NCH)
 // R   = super-tiles a wave keeps in flight
-// QMX = mx4: the weights are converted in registers (v_cvt_scalef32_pk_bf16_fp4, w4_gemm_pair.cuh: mx4_cvt_word) with the group's
+// QMX = mx4: the weights are converted in registers (v_cvt_scalef32_pk_bf16_fp4, w4_helpers.cuh: mx4_cvt_word) with the group's
 //       scale 2^(e - 127) inside the conversion: no table, no lookups, no per-group accumulator updates; the word pair of a lane is
 //       swapped BEFORE the conversion (one v_permlane16_swap per stage); the e8m0 exponents of a lane's four rows over its k-slice
 //       are one 16-byte load per row and item, requested one item ahead.  CPG is 1 (a group is one 32-k chunk).

@@ -41,10 +41,6 @@
 //                front of the first requests, the residual / bias values requested up front, one inlined copy of the pass tail.
 #pragma once
 
-#ifndef GEMV_TRACE
-#define GEMV_TRACE 0  // developer builds: s_memrealtime stamps of workgroup phases into GemvParams.trace
-#endif
-
 struct GemvParams {
   const char* x;
   const char* w;
@@ -74,7 +70,7 @@ struct GemvParams {
   int32_t epilogue;
   int32_t xcd4;      // 1: four consecutive row ranges per XCD (no remainder ranges, workgroups a multiple of 32)
   int32_t cm;        // 1: chunk-mode staging (5 ... 8 activation rows on the matrix-core path, k = 2048 / 4096: w4_gemv_kernel, `cm`)
-  unsigned long long* trace;
+  unsigned long long* trace;  // developer builds (tg_trace.cuh): stamps of workgroup phases; else nullptr
 };
 
 // DT = BF16 / F16, M = activation rows (1 ... 4; MF: 3 ... 8), GPS = groups per super-tile half-step (1: g >= 64, 2: g = 32), D = ring depth,
@@ -101,12 +97,8 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
   const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   constexpr int b = 0;  // (ONE problem per launch, the host's condition: no stride arithmetic on the launch's critical path)
-#if GEMV_TRACE
-  unsigned long long tr[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) tr[i] = 0;
-  tr[0] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TG_TRACE_BEGIN();
+  TG_STAMP(0);
 
   // Every kernel argument into scalar registers NOW: left alone, hipcc loads them where they are first used -- four dependent
   // scalar-memory round trips (~0.3 us each from the cold argument segment) in front of the first weight request.
@@ -115,9 +107,7 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
   asm volatile("" ::"s"(p.m), "s"(p.wrows), "s"(p.k), "s"(p.ksuper), "s"(p.qtype), "s"(p.sg_shift), "s"(p.P), "s"(p.p_shift), "s"(p.unit),
                "s"(p.ubase), "s"(p.urem), "s"(p.spw), "s"(p.spp), "s"(p.rounds), "s"(p.x_pitch), "s"(p.xs_pitch), "s"(p.lds_lut),
                "s"(p.lds_x), "s"(p.lds_xs), "s"(p.lds_red), "s"(p.lds_nrm), "s"(p.norm_eps), "s"(p.epilogue), "s"(p.xcd4), "s"(p.cm), "s"(p.uextra), "s"(p.uh));
-#if GEMV_TRACE
-  tr[6] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TG_STAMP(6);
 
   // ---- this workgroup's tiles, this lane's place in a pass ----
   // Four CONSECUTIVE ranges go to the workgroups b, b + 8, b + 16, b + 24 -- one XCD (workgroup b runs on XCD b % 8: observed, used
@@ -293,9 +283,7 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
     issue(ring[j]);
   }
   __builtin_amdgcn_sched_barrier(0);
-#if GEMV_TRACE
-  tr[1] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TG_STAMP(1);
   // ---- stage the activations (byte order of w4_gemm_pair.cuh) and their sums ----
   const uint32_t lds_x = (uint32_t)p.lds_x, lds_xs = (uint32_t)p.lds_xs, lds_red = (uint32_t)p.lds_red;
   // one piece -> LDS (byte order); returns the sum of its 8 values
@@ -441,13 +429,9 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
     }
   };
   build_table(0);
-#if GEMV_TRACE
-  tr[2] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TG_STAMP(2);
   __syncthreads();
-#if GEMV_TRACE
-  tr[3] = __builtin_amdgcn_s_memrealtime();
-#endif
+  TG_STAMP(3);
 
   // ---- main loop ----
   uint32_t colreg = (uint32_t)((lane & 31) * 4);
@@ -539,7 +523,7 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
     const uint32_t xsa = xslane + (uint32_t)su * 16u;
     if constexpr (MF) {
       const uint32_t xr = xa + (uint32_t)(min(lane & 15, M - 1) * p.x_pitch);
-      f32x4_t acc = {0.f, 0.f, 0.f, 0.f};
+      f32x4 acc = {0.f, 0.f, 0.f, 0.f};
       u32x4 e4[4], xf4[4];
 #pragma unroll
       for (int u = 0; u < 4; ++u) {
@@ -549,19 +533,19 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
         for (int j = 0; j < 4; ++j) e4[u][j] = *(lds_cu32ptr)(__builtin_amdgcn_perm(w, colreg, 0x0c0c0400u + ((uint32_t)j << 8)));
         xf4[u] = *(lds_cu32x4ptr)(xr + (uint32_t)(jc * 64 + qq * 16));
       }
-      f32x4_t gs4 = {0.f, 0.f, 0.f, 0.f};
+      f32x4 gs4 = {0.f, 0.f, 0.f, 0.f};
       if constexpr (!MFS) {
         const f32x4 v = *(lds_cf32x4ptr)(lds_xs + (uint32_t)((su >> 1) * 64 + (lane >> 4) * 16));
-        gs4 = f32x4_t{v[0], v[1], v[2], v[3]};
+        gs4 = f32x4{v[0], v[1], v[2], v[3]};
       }
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-      for (int u = 0; u < 4; ++u) acc = mfma16<DT>(xf4[u], e4[u], acc);
+      for (int u = 0; u < 4; ++u) acc = DT::mfma(xf4[u], e4[u], acc);
       if constexpr (MFS) {
         const uint32_t one2 = DT::pack2(1.f, 1.f);
         const u32x4 ones = {one2, one2, one2, one2};
 #pragma unroll
-        for (int u = 0; u < 4; ++u) gs4 = mfma16<DT>(xf4[u], ones, gs4);
+        for (int u = 0; u < 4; ++u) gs4 = DT::mfma(xf4[u], ones, gs4);
       }
       const float sc = on ? DT::lo_f32(sl.q[0]) : 0.f;
       const float zz = on ? DT::hi_f32(sl.q[0]) : 0.f;
@@ -594,7 +578,7 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
 #pragma unroll
       for (int a = 0; a < M; ++a)
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dsum[a][GPS == 1 ? 0 : jc] = dot2_pair<DT>(e[u][j], xf[a][u][j], dsum[a][GPS == 1 ? 0 : jc]);
+        for (int j = 0; j < 4; ++j) dsum[a][GPS == 1 ? 0 : jc] = dot2<DT>(e[u][j], xf[a][u][j], dsum[a][GPS == 1 ? 0 : jc]);
     }
 #pragma unroll
     for (int g = 0; g < GPS; ++g) {
@@ -619,27 +603,18 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
       for (int j = 0; j < D; ++j) {
         if (r * D + j < spp) consume(ring[j], r * D + j);
         issue(ring[j]);
-#if GEMV_TRACE
-        if (cp == 0 && r == 0 && j == 0) tr[4] = __builtin_amdgcn_s_memrealtime();
-#endif
+        TG_STAMP_IF(cp == 0 && r == 0 && j == 0, 4);
       }
     }
     if (last) {
 #pragma unroll
       for (int j = 0; j < D; ++j) {
         if ((rounds - 1) * D + j < spp) consume(ring[j], (rounds - 1) * D + j);
-#if GEMV_TRACE
-        if (cp == 0 && rounds == 1 && j == 0) tr[4] = __builtin_amdgcn_s_memrealtime();
-#endif
+        TG_STAMP_IF(cp == 0 && rounds == 1 && j == 0, 4);
       }
     }
     pass_end(cp);
   }
-#if GEMV_TRACE
-  tr[5] = __builtin_amdgcn_s_memrealtime();
-  if (tid == 0 && p.trace) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) p.trace[(size_t)blockIdx.x * 8 + i] = tr[i];
-  }
-#endif
+  TG_STAMP(5);
+  TG_TRACE_FLUSH(tid == 0 && p.trace, p.trace, 7);
 }

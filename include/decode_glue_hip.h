@@ -39,7 +39,7 @@ TG_API int dg_add_rmsnorm(const void* h, const void* delta, const void* w, void*
  * (both halves filled, HF convention); *pos = sequence position (int64 on the device).
  * q_out [bs][hl][d] = rope(q); k_cache[b][kv][*pos][:] = rope(k); v_cache[b][kv][*pos][:] = v.
  * rope(x)[j] = to16(RN(x[j] cos[j]) + RN(rotate_half(x)[j] sin[j])) in f32: two rounded products, a rounded sum, never an FMA
- * (any4_amd/csrc/rope_math.cuh) -- the bits of the torch ops in decode._rope, and the same in every kernel below that ropes
+ * (any4_amd/csrc/stage_math.cuh) -- the bits of the torch ops in decode._rope, and the same in every kernel below that ropes
  * (dg_rope_attn, dg_rope_attn_online, dg_rope_attn_split, dg_prefill_attn; tests/test_gpu_glue_f64.py compares > 4e6 elements each).
  * caches are [bs][kvl][max_seq][d]; d even, d <= 256. */
 TG_API int dg_rope_kv(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* q_out,
