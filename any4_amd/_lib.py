@@ -113,6 +113,15 @@ SYMBOLS = {
     "dg_linear16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_prefill_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
                         ctypes.c_int, ctypes.c_int, _vp],
+    # ... with a position per sequence (`pos` int64[bs]); dg_prefill_attn_seq also takes a length and a cache slot per sequence
+    "dg_rope_attn_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
+                         ctypes.c_int, ctypes.c_int, _vp],
+    "dg_rope_attn_online_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
+                                ctypes.c_int, ctypes.c_int, _vp],
+    "dg_rope_attn_split_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
+                               ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
+    "dg_prefill_attn_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
+                            ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
 }
 
 _lib = None

@@ -24,6 +24,10 @@
 // Positions: *pos = p0 is read on the device.  A token whose position p0 + t is outside [0, max_seq) writes no cache row, is read by
 // nobody (every token only reads rows <= its own position) and leaves its output row unwritten; rows of a tile beyond the workgroup's
 // last valid position are zero-filled in LDS instead of being read, so NaN-filled or unallocated tails are never touched.
+//
+// SEQ (dg_prefill_attn_seq): position, length and cache slot are per sequence, read by every workgroup: p0 = pos[i], T_i = min(len[i], T)
+// decides which tokens exist (the padded T stays in the row addressing and sizes the grid), the cache base is slot[i]'s.  A sequence
+// with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
 #pragma once
 #include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 
@@ -41,11 +45,54 @@ struct PrefillParams {
   float scale;
 };
 
+// What only the SEQ kernels read: their LAST argument, and an empty one for SEQ = false, so that the scalar kernels keep the argument
+// offsets (and with them the code) they had before there was a SEQ flavour.
+struct PrefillSeq {
+  const int64_t* len;   // [bs] or null: every length is T
+  const int64_t* slot;  // [bs] or null: sequence i lives in cache slot i
+  int32_t cache_bs;
+};
+template <bool SEQ> struct PrefillSeqArg {};
+template <> struct PrefillSeqArg<true> : PrefillSeq {};
+
+// (developer builds: -D'DG_SEQ_INDEX(i)=0', -D'DG_SEQ_LEN(p)=nullptr', -D'DG_SEQ_SLOT(p)=nullptr' give three wrong-on-purpose
+// libraries -- every sequence at pos[0], len ignored, slot ignored -- to see tests/test_gpu_ragged.py fail; each still indexes only
+// what the right one may index)
+#ifndef DG_SEQ_INDEX
+#define DG_SEQ_INDEX(i) (i)
+#endif
+#ifndef DG_SEQ_LEN
+#define DG_SEQ_LEN(p) (p)
+#endif
+#ifndef DG_SEQ_SLOT
+#define DG_SEQ_SLOT(p) (p)
+#endif
+
+// (p0, T_i, slot) of sequence i; false: the sequence does nothing
+__device__ __forceinline__ bool pf_seq(const PrefillParams& P, const PrefillSeq& Q, int i, int64_t& p0, int& Ti, int& slot) {
+  p0 = P.pos[DG_SEQ_INDEX(i)];
+  const int64_t* lenp = DG_SEQ_LEN(Q.len);
+  const int64_t* slotp = DG_SEQ_SLOT(Q.slot);
+  const int64_t li = lenp ? lenp[i] : (int64_t)P.T, sl = slotp ? slotp[i] : (int64_t)i;
+  Ti = (int)(li < P.T ? li : P.T);
+  slot = (int)sl;
+  return li > 0 && sl >= 0 && sl < Q.cache_bs;
+}
+
 // ---- rope + cache append: block = one token of one sequence; a thread walks (kv head, rotation pair) items, k first, then v ----
-template <typename DT>
-__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d) {
+template <typename DT, bool SEQ = false>
+__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q) {
   const int t = blockIdx.x, b = blockIdx.y, d2 = d >> 1;
-  const int64_t pos = *P.pos + t;
+  int cb = b;  // the sequence's cache slot
+  int64_t pos;
+  if constexpr (SEQ) {
+    int64_t p0;
+    int Ti;
+    if (!pf_seq(P, Q, b, p0, Ti, cb) || t >= Ti || p0 < -(int64_t)P.T || p0 >= P.max_seq) return;
+    pos = p0 + t;
+  } else {
+    pos = *P.pos + t;
+  }
   if (pos < 0 || pos >= P.max_seq) return;  // never index the cache (or the tables) outside [0, max_seq)
   const uint16_t* row = P.qkv + ((int64_t)b * P.T + t) * (int64_t)(P.hl + 2 * P.kvl) * d;
   const int per = P.kvl * d2;
@@ -53,7 +100,7 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
     const bool isv = i >= per;
     const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
     const uint16_t* src = row + (int64_t)(P.hl + (isv ? P.kvl : 0) + kv) * d;
-    uint16_t* dst = (isv ? P.v_cache : P.k_cache) + (((int64_t)b * P.kvl + kv) * P.max_seq + pos) * d;
+    uint16_t* dst = (isv ? P.v_cache : P.k_cache) + (((int64_t)cb * P.kvl + kv) * P.max_seq + pos) * d;
     if (isv) {
       dst[j] = src[j];
       dst[j + d2] = src[j + d2];
@@ -76,8 +123,8 @@ __device__ __forceinline__ int pf_swz_v(int d, int chunk) { return chunk ^ (((d 
 
 constexpr int PF_NU = 2;  // 16-row units per wave: 2 x (O 4 D/16 + q D/8 + S 16) registers leave room for two workgroups per CU; 4 spill at D = 128
 
-template <typename DT, int D, int RG>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
+template <typename DT, int D, int RG, bool SEQ = false>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q) {
   constexpr int KD = D / 32;        // k-steps of the score product
   constexpr int DB = D / 16;        // 16-column blocks of the output
   constexpr int NU = PF_NU;         // 16-row units per wave
@@ -88,9 +135,11 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
 
   const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63, r = lane & 15, g = lane >> 4;
-  const int64_t p0l = *P.pos;
-  if (p0l <= -(int64_t)P.T || p0l >= P.max_seq) return;  // no token of the chunk is inside the cache
-  const int p0 = (int)p0l;
+  int64_t p0l;
+  if constexpr (!SEQ) {
+    p0l = *P.pos;
+    if (p0l <= -(int64_t)P.T || p0l >= P.max_seq) return;  // no token of the chunk is inside the cache
+  }
   int idx = blockIdx.x;
   const int per = P.bs * P.kvl * P.hgroups;
   const int qb = P.nqb - 1 - idx / per;  // longest blocks first
@@ -98,7 +147,12 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
   const int hgi = idx % P.hgroups, kv = (idx / P.hgroups) % P.kvl, b = idx / (P.hgroups * P.kvl);
   const int rep = P.hl / P.kvl;
   const int tq0 = qb * BQ;
-  const int tend = tq0 + BQ < P.T ? tq0 + BQ : P.T;             // (tq0 < T by construction of the grid)
+  int Tv = P.T, cb = b;  // tokens of this sequence that exist (T_i); its cache slot
+  if constexpr (SEQ) {
+    if (!pf_seq(P, Q, b, p0l, Tv, cb) || p0l <= -(int64_t)Tv || p0l >= P.max_seq || tq0 >= Tv) return;
+  }
+  const int p0 = (int)p0l;
+  const int tend = tq0 + BQ < Tv ? tq0 + BQ : Tv;               // (tq0 < T by construction of the grid)
   const int p_hi = p0 + tend - 1 < P.max_seq - 1 ? p0 + tend - 1 : P.max_seq - 1;  // last valid position any row of this block may see
   if (p_hi < 0 || p0 + tq0 >= P.max_seq) return;
   const int ntiles = p_hi / 64 + 1;
@@ -113,7 +167,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
     const int hu = hgi * RG + (NU * w + u) % RG, tb = (NU * w + u) / RG;
     tu0[u] = tq0 + 16 * tb;
     const int t = tu0[u] + r, p = p0 + t;
-    const bool ok = hu < rep && t < P.T && p >= 0 && p < P.max_seq;
+    const bool ok = hu < rep && t < Tv && p >= 0 && p < P.max_seq;
     pq[u] = ok ? p : INT32_MAX;
     const int head = kv * rep + hu;
     orow[u] = ((int64_t)b * P.T + t) * (int64_t)P.hl * D + (int64_t)head * D;
@@ -151,8 +205,8 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
     }
   }
 
-  const char* Kg = reinterpret_cast<const char*>(P.k_cache + ((int64_t)b * P.kvl + kv) * (int64_t)P.max_seq * D);
-  const char* Vg = reinterpret_cast<const char*>(P.v_cache + ((int64_t)b * P.kvl + kv) * (int64_t)P.max_seq * D);
+  const char* Kg = reinterpret_cast<const char*>(P.k_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
+  const char* Vg = reinterpret_cast<const char*>(P.v_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
 
   // ---- staging: K as 16-byte chunks (row, chunk); V as four consecutive positions 4 sg ... 4 sg + 3 of one 8-column chunk c
   u32x4 kreg[NCK], vreg[4];
@@ -215,7 +269,7 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P) {
     const int s0 = 64 * j;
     bool any = false;
 #pragma unroll
-    for (int u = 0; u < NU; ++u) any = any || (tu0[u] < P.T && s0 <= p0 + tu0[u] + 15);
+    for (int u = 0; u < NU; ++u) any = any || (tu0[u] < Tv && s0 <= p0 + tu0[u] + 15);
     // (wave-uniform) the tile is not entirely above the diagonal of every unit of this wave; a unit it is above masks all of it
     if (any) {
       // ---- S^T = K . Q^T and the online softmax (two units share the K fragments); the probabilities become the B fragments of the

@@ -201,7 +201,12 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
 // Every block rotates its own q head and the k head of its KV group, writes k / v of the new token into the caches
 // (the hl/kvl blocks of a group write identical bytes) and uses its LDS copy for position *pos, so nothing is read
 // back from global memory within the launch.  Same arithmetic, in the same order, as rope_kv_kernel + decode_attn_kernel.
-template <typename DT>
+// SEQ (here and in the two kernels below; the dg_*_seq entry points): `pos_p` is int64[bs] and sequence b sits at pos_p[b] -- the
+// same single read, at another address; a sequence whose position is outside the cache is the scalar kernels' "nothing happens".
+#ifndef DG_SEQ_INDEX  // (developer builds: -D'DG_SEQ_INDEX(b)=0' is a wrong-on-purpose library, every sequence at pos[0], to see tests/test_gpu_ragged.py fail)
+#define DG_SEQ_INDEX(b) (b)
+#endif
+template <typename DT, bool SEQ = false>
 __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                         const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                         uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
@@ -214,7 +219,7 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
   float* scratch = sm + 768;
   float* sc = sm + 772;
   const int b = blockIdx.x / hl, h = blockIdx.x % hl, kv = h / (hl / kvl), t = threadIdx.x;
-  const int64_t pos = *pos_p;
+  const int64_t pos = SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check): never index the cache outside [0, max_seq)
   const int S = (int)pos + 1, d8 = d >> 3, d2 = d >> 1;
   const uint16_t* row = qkv + (int64_t)b * (hl + 2 * kvl) * d;
@@ -321,7 +326,7 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
 // One block per head leaves 7/8 of the CUs idle and walks a long context at ~40 ns per position; this one fills the GPU.
 // Softmax statistics are combined flash-decoding style, so probabilities are normalised AFTER the value contraction
 // (the single-block kernels round normalised probabilities to 16 bit first): same result within 16-bit rounding.
-template <typename DT>
+template <typename DT, bool SEQ = false>
 __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                               const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                               uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
@@ -336,7 +341,7 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
   __shared__ int s_last;
   const int bh = blockIdx.x, c = blockIdx.y, NS = gridDim.y;
   const int b = bh / hl, h = bh % hl, kv = h / (hl / kvl), t = threadIdx.x;
-  const int64_t pos = *pos_p;
+  const int64_t pos = SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;  // (SEQ: all NS blocks of an inactive sequence's head return: its counter stays at zero)
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check): never index the cache outside [0, max_seq)
   const int S = (int)pos + 1, d8 = d >> 3, d2 = d >> 1;
   const int CS = (S + NS - 1) / NS;
@@ -440,7 +445,7 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 //                as dg_rope_attn_split: the same result within 16-bit rounding); the 32 (64) groups meet ONCE in LDS.
 //   RoPE         rotate_half pairs (j, j + d/2) sit d/16 lanes apart in the row: one lane exchange per value; the same products
 //                and roundings as rope_kv_kernel (the cache rows written are bit-identical to it).
-template <typename DT, int LPR>
+template <typename DT, int LPR, bool SEQ = false>
 __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                                const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                                uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
@@ -487,7 +492,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     kk[it] = piece(K, rc);
     vv[it] = piece(V, rc);
   }
-  const int64_t pos = *pos_p;
+  const int64_t pos = SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check)
   const int S = (int)pos + 1;
   TG_STAMP(1);
@@ -782,9 +787,15 @@ int dg_decode_attn(const void* q, const void* k_cache, const void* v_cache, cons
   return launch_status();
 }
 
-int dg_rope_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                 void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
-                 tg_stream_t stream) {
+}  // extern "C"
+
+namespace {
+
+// the three attention entry points the stack launches, each once for `pos` [1] (SEQ = false) and once for `pos` [bs] (dg_*_seq)
+template <bool SEQ>
+int rope_attn_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                     void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
+                     tg_stream_t stream) {
   if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out) return TG_E_NULL;
   if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
   if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
@@ -795,19 +806,16 @@ int dg_rope_attn(const void* qkv, const float* cos, const float* sin, const int6
   if (!ds.ok) return TG_E_DEVICE;
   const int64_t sc_floats = max_seq > (256 / (d / 8)) * (int64_t)d ? max_seq : (256 / (d / 8)) * (int64_t)d;
   const unsigned lds = (unsigned)((772 + sc_floats) * sizeof(float));
-  auto kern = dtype == TG_BF16 ? rope_attn_kernel<BF16> : rope_attn_kernel<F16>;
+  auto kern = dtype == TG_BF16 ? rope_attn_kernel<BF16, SEQ> : rope_attn_kernel<F16, SEQ>;
   hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl)), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin, pos,
                      (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, d, max_seq, scale);
   return launch_status();
 }
 
-#if GEMV_TRACE
-TG_API void tg_dev_attn_trace(unsigned long long* buf) { g_attn_trace = buf; }  // developer builds: [blocks][8] stamps of the last launch
-#endif
-
-int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                        void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
-                        tg_stream_t stream) {
+template <bool SEQ>
+int rope_attn_online_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                            void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
+                            tg_stream_t stream) {
   if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out) return TG_E_NULL;
   if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
   if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || !(d == 64 || d == 128) || max_seq <= 0 || bs * hl > INT32_MAX ||
@@ -823,7 +831,7 @@ int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, con
 #endif
   return pick_dt(dtype, [&](auto DT_) {
     return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
-      hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value>), dim3((unsigned)(bs * hl)), dim3(512), lds, (hipStream_t)stream,
+      hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, SEQ>), dim3((unsigned)(bs * hl)), dim3(512), lds, (hipStream_t)stream,
                          (const uint16_t*)qkv, cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, trace,
                          (float*)nullptr, (int*)nullptr);
       return launch_status();
@@ -831,9 +839,10 @@ int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, con
   });
 }
 
-int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                       void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                       float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+template <bool SEQ>
+int rope_attn_split_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                           void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                           float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
   if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out || !scratch) return TG_E_NULL;
   if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
   if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
@@ -854,18 +863,51 @@ int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, cons
     const dim3 grid((unsigned)(bs * hl), (unsigned)nsplit);
     return pick_dt(dtype, [&](auto DT_) {
       return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
-        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value>), grid, dim3(512), lds1, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin,
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, SEQ>), grid, dim3(512), lds1, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin,
                            pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, (unsigned long long*)nullptr, part, counters);
         return launch_status();
       });
     });
   }
   if (lds > 64u * 1024u) return TG_E_SHAPE;
-  auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16> : rope_attn_split_kernel<F16>;
+  auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16, SEQ> : rope_attn_split_kernel<F16, SEQ>;
   hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl), (unsigned)nsplit), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)qkv,
                      cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, part, counters, hl, kvl, d, max_seq, scale);
   return launch_status();
 }
+
+}  // namespace
+
+extern "C" {
+
+#if GEMV_TRACE
+TG_API void tg_dev_attn_trace(unsigned long long* buf) { g_attn_trace = buf; }  // developer builds: [blocks][8] stamps of the last launch
+#endif
+
+#define DG_ATTN_ARGS const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out
+int dg_rope_attn(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+}
+int dg_rope_attn_seq(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+}
+int dg_rope_attn_online(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_online_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+}
+int dg_rope_attn_online_seq(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_online_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+}
+int dg_rope_attn_split(DG_ATTN_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                       int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
+                                       dtype, device, stream);
+}
+int dg_rope_attn_split_seq(DG_ATTN_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                           int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
+                                      dtype, device, stream);
+}
+#undef DG_ATTN_ARGS
 
 int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) {
   return ((bs * hl * 4 + 15) / 16) * 16 + bs * hl * (int64_t)nsplit * (d + 2) * 4;

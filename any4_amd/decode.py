@@ -27,8 +27,10 @@ Launch structure, chosen for the hardware rather than copied from HF:
 from __future__ import annotations
 
 import math
+import operator
 import os
 from dataclasses import dataclass
+from functools import partial
 from typing import Callable, Optional
 
 import torch
@@ -206,6 +208,33 @@ def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl
     return ctx.view(bs, kvl, rep, T, d).permute(0, 3, 1, 2, 4).reshape(bs * T, hl * d)
 
 
+def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots, k_cache, v_cache, hl: int, kvl: int, d: int, T: int):
+    """prefill_attention_torch with a position, a length and a cache slot per sequence, all on the host (what dg_prefill_attn_seq is
+    tested against; also the CPU path).  qkv [n * T, (hl + 2 kvl) d], rows padded to the common T: sequence i has `lengths[i]` tokens
+    from position `positions[i]` on and lives in k_cache[slots[i]] / v_cache[slots[i]].  Every sequence gets its own rope rows, its
+    own cache rows and its own mask; a padding row writes nothing, is seen by nobody and its context row is zero.  A batch in which
+    nothing differs (equal positions, every length T, slot i for sequence i) IS prefill_attention_torch's batch and takes it."""
+    n = qkv.shape[0] // T
+    if n == k_cache.shape[0] and all(int(p) == int(positions[0]) for p in positions) and all(int(x) == T for x in lengths) and \
+            [int(x) for x in slots] == list(range(n)):
+        return prefill_attention_torch(qkv, cos_tab, sin_tab, int(positions[0]), k_cache, v_cache, hl, kvl, d, T)
+    ctx = qkv.new_zeros(n, T, hl * d)
+    rows = qkv.view(n, T, -1)
+    for i in range(n):
+        L, sl = int(lengths[i]), int(slots[i])
+        if L > 0:
+            ctx[i, :L] = prefill_attention_torch(rows[i, :L], cos_tab, sin_tab, int(positions[i]), k_cache[sl: sl + 1], v_cache[sl: sl + 1],
+                                                 hl, kvl, d, L)
+    return ctx.view(n * T, hl * d)
+
+
+def _scatter_rows(cache, pos, active, new):
+    """cache[b, :, pos[b], :] = new[b] for the active sequences b, with `pos` [bs] (clamped into the cache) and `active` [bs] on the
+    device: an inactive sequence gets its own row back, so nothing is read on the host and nothing of it changes."""
+    idx = pos.view(-1, 1, 1, 1).expand(-1, cache.shape[1], 1, cache.shape[3])
+    cache.scatter_(2, idx, torch.where(active.view(-1, 1, 1, 1), new.unsqueeze(2), cache.gather(2, idx)))
+
+
 class DecodeLayer(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int):
         super().__init__()
@@ -244,6 +273,34 @@ class DecodeLayer(torch.nn.Module):
         ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
+    def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather):
+        """`forward` with a position per sequence: `pos` int64 [bs] on the device.  Sequence b takes rope row pos[b], writes cache row
+        pos[b] and sees rows <= pos[b]; one whose position is outside [0, max_seq) is inactive: its caches keep their bits (its row of
+        the result is unspecified).  No value is read on the host."""
+        d, bs = self.cfg.head_dim, h.shape[0]
+        active = (pos >= 0) & (pos < self.cfg.max_seq)
+        pc = pos.clamp(0, self.cfg.max_seq - 1)
+        cos, sin = cos_tab.index_select(0, pc).view(bs, 1, d), sin_tab.index_select(0, pc).view(bs, 1, d)
+        qkv = self.qkv(self.norm1(h))
+        q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
+        k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
+        v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
+        _scatter_rows(self.k_cache, pc, active, k)
+        _scatter_rows(self.v_cache, pc, active, v)
+        rep = self.hl // self.kvl
+        qg = q.reshape(bs, self.kvl, rep, d)
+        att = torch.matmul(qg, self.k_cache.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
+        att = att.masked_fill(arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), float("-inf")).softmax(-1).to(h.dtype)
+        ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
+        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+
+    def forward_prefill_seq(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
+        """`forward_prefill` with a position, a length and a cache slot per sequence (host ints): `h` [n * T, hidden], rows padded to T."""
+        d = self.cfg.head_dim
+        ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
+                                          self.hl, self.kvl, d, T)
+        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+
     def forward_prefill(self, h, p0: int, T: int, cos_tab, sin_tab, gather):
         """Plain torch, a chunk of T tokens per sequence: `h` [bs * T, hidden] (row b * T + t), token 0 at position `p0` (on the
         host).  The T rows of k / v are appended to the caches and every token attends causally over cache + chunk."""
@@ -259,24 +316,28 @@ class DecodeLayer(torch.nn.Module):
         return h + gather(self.down(gather(act)))
 
     # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context
-    def decode_attention(self, qkv, pos, cos_tab, sin_tab):
-        """One token per sequence at `pos` [1]: split over the sequence when the stack gave this layer a scratch buffer, else the
-        latency kernel (head_dim 64 / 128), else the general one."""
+    def decode_attention(self, qkv, pos, cos_tab, sin_tab, per_sequence: bool = False):
+        """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
+        stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one."""
         from . import decode_ops as G
 
         d = self.cfg.head_dim
         args = (qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
         if self._attn_scratch is not None:
-            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split)
-        return (G.rope_attn_online if d in (64, 128) else G.rope_attn)(*args)
+            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence)
+        return (G.rope_attn_online if d in (64, 128) else G.rope_attn)(*args, per_sequence=per_sequence)
 
-    def prefill_attention(self, qkv, pos, cos_tab, sin_tab):
-        """A chunk of T = rows / bs tokens per sequence (row b * T + t), token 0 at `pos` [1]: T cache rows appended, causal."""
+    def prefill_attention(self, qkv, pos, cos_tab, sin_tab, T: Optional[int] = None, lengths=None, slots=None, per_sequence: bool = False):
+        """A chunk of T tokens per sequence (row b * T + t; default T = rows / the caches' batch), token 0 at `pos` [1]: T cache rows
+        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device (dg_prefill_attn_seq); the context rows of
+        tokens that do not exist are zero."""
         from . import decode_ops as G
 
         d = self.cfg.head_dim
-        return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d),
-                              qkv.shape[0] // self.k_cache.shape[0])
+        T = qkv.shape[0] // self.k_cache.shape[0] if T is None else T
+        out = qkv.new_zeros(qkv.shape[0], self.hl * d) if per_sequence else None
+        return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
+                              out=out, lengths=lengths, slots=slots, per_sequence=per_sequence)
 
     def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather):
         """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
@@ -374,8 +435,12 @@ class DecodeStack(torch.nn.Module):
 
     def __init__(self, cfg: DecodeConfig, linear_factory: Callable, device, dtype=torch.bfloat16, bs: int = 1,
                  rank: int = 0, world: int = 1, group=None, seed: int = 0, lm_head: bool = True,
-                 fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True):
-        """fused: run the non-GEMM parts on the HIP glue kernels (default on a GPU) or as plain torch ops
+                 fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
+                 ragged: bool = False):
+        """ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`
+        a position, a length and a cache slot per sequence, `generate` prompts of different lengths; the step (and its captured
+        graph) reads `pos_seq` [bs] in place of `pos`.  A stack built without it is what it was.
+        fused: run the non-GEMM parts on the HIP glue kernels (default on a GPU) or as plain torch ops
         (the formulation the glue kernels are tested against; also what runs in the CPU plumbing tests).
         emulate_gather: TIMING ONLY -- build rank `rank` of `world` in a single process and replace every all-gather
         by a local copy of the rank's shard into all `world` slots (the values are meaningless): the per-GPU compute
@@ -416,6 +481,10 @@ class DecodeStack(torch.nn.Module):
         self.register_buffer("pos", torch.zeros(1, dtype=torch.long, device=device), persistent=False)
         # prefill's own position (a captured decode graph reads `pos`; a prefill between two replays must not move it)
         self.register_buffer("prefill_pos", torch.zeros(1, dtype=torch.long, device=device), persistent=False)
+        self.ragged = bool(ragged)
+        if self.ragged:  # (a sequence per element; prefill uses the first n of its three)
+            for name in ("pos_seq", "prefill_pos_seq", "prefill_len", "prefill_slot"):
+                self.register_buffer(name, torch.zeros(bs, dtype=torch.long, device=device), persistent=False)
         self._graph = None
         self._out = None
         self._decodes = 0
@@ -464,8 +533,8 @@ class DecodeStack(torch.nn.Module):
 
     @torch.no_grad()
     def step(self) -> torch.Tensor:
-        """One decode step on the static inputs `self.tokens` [bs], `self.pos` [1]; returns logits (or the
-        final hidden state when built without LM head)."""
+        """One decode step on the static inputs `self.tokens` [bs], `self.pos` [1] (a ragged stack: `self.pos_seq` [bs]); returns
+        logits (or the final hidden state when built without LM head)."""
         if self._peer or (self.gather_mode == "peer" and self.world > 1 and not self.emulate_gather):
             before = {w: pg._calls for w, pg in self._peer.items()}
             out = self._step()
@@ -496,6 +565,8 @@ class DecodeStack(torch.nn.Module):
         return logits if logits is not None else self.lm_head(y)
 
     def _step(self) -> torch.Tensor:
+        if self.ragged:
+            return self._step_seq()
         pos = self.pos
         h, delta = self.embed(self.tokens), None
         if not self.fused:
@@ -510,6 +581,22 @@ class DecodeStack(torch.nn.Module):
         else:
             for layer in self.layers:
                 h, delta = layer.forward_fused(h, delta, layer.decode_attention, pos, self.cos, self.sin, self._gather)
+        return self._head(h, delta)
+
+    def _step_seq(self) -> torch.Tensor:
+        """_step with a position per sequence (`pos_seq`): the same schedules, the attention launches read pos_seq[b]."""
+        pos = self.pos_seq
+        h, delta = self.embed(self.tokens), None
+        if not self.fused:
+            for layer in self.layers:
+                h = layer.forward_seq(h, pos, self.cos, self.sin, self.arange, self._gather)
+        elif self._five_launch():
+            for layer in self.layers:
+                h = layer.forward_fused5(h, partial(layer.decode_attention, per_sequence=True), pos, self.cos, self.sin)
+        else:
+            for layer in self.layers:
+                h, delta = layer.forward_fused(h, delta, partial(layer.decode_attention, per_sequence=True), pos, self.cos, self.sin,
+                                               self._gather)
         return self._head(h, delta)
 
     @torch.no_grad()
@@ -531,12 +618,47 @@ class DecodeStack(torch.nn.Module):
             self.graph_nodes = sum(layer.launches() for layer in self.layers) + 2 + (1 if self.lm_head is not None else 0)
 
     @torch.no_grad()
-    def decode(self, tokens: torch.Tensor, position: int) -> torch.Tensor:
-        """Feed `tokens` [bs] at sequence position `position`; graph replay if captured, else eager."""
-        if not 0 <= int(position) < self.cfg.max_seq:
-            raise ValueError(f"position {position} outside the KV cache [0, {self.cfg.max_seq})")
+    def _set_positions(self, position) -> None:
+        """decode()'s `position` of a ragged stack into `pos_seq`: host values are checked here, a device tensor is copied as it is
+        (no sync; the kernels ignore a sequence whose position is outside the cache)."""
+        S = self.cfg.max_seq
+        if isinstance(position, torch.Tensor) and position.device.type != "cpu":
+            if position.dtype != torch.long or position.numel() != self.bs:
+                raise ValueError(f"a device position must be int64 [bs = {self.bs}], got {position.dtype} {tuple(position.shape)}")
+            self.pos_seq.copy_(position.view(-1))
+            return
+        if isinstance(position, torch.Tensor):
+            position = position.tolist()
+        vals = [operator.index(p) for p in position] if isinstance(position, (list, tuple)) else [operator.index(position)] * self.bs
+        if len(vals) != self.bs:
+            raise ValueError(f"{len(vals)} positions for bs = {self.bs} sequences")
+        if any(not (p == -1 or 0 <= p < S) for p in vals):
+            raise ValueError(f"positions {vals}: each must be -1 (inactive) or inside the KV cache [0, {S})")
+        if len(set(vals)) == 1:
+            self.pos_seq.fill_(vals[0])  # (a fill, as for `pos`: no copy from host memory in the way of the launches)
+        else:
+            self.pos_seq.copy_(torch.tensor(vals, dtype=torch.long))
+
+    @torch.no_grad()
+    def decode(self, tokens: torch.Tensor, position) -> torch.Tensor:
+        """Feed `tokens` [bs] at sequence position `position`; graph replay if captured, else eager.
+        A ragged stack also takes a position per sequence: a list / CPU tensor of `bs` ints, each -1 (the sequence is inactive: it
+        writes no cache row and its logits row is unspecified) or inside the cache, or an int64 device tensor [bs], which is copied
+        without a sync and without a host check (the kernels ignore positions outside the cache)."""
+        if self.ragged:
+            try:
+                self._set_positions(position)
+            except TypeError as e:
+                raise ValueError(f"position must be an int, {self.bs} ints or an int64 device tensor: {e}") from e
+        else:
+            try:
+                position = operator.index(position)
+            except TypeError as e:
+                raise ValueError("a position per sequence needs DecodeStack(..., ragged=True)") from e
+            if not 0 <= position < self.cfg.max_seq:
+                raise ValueError(f"position {position} outside the KV cache [0, {self.cfg.max_seq})")
+            self.pos.fill_(position)
         self.tokens.copy_(tokens)
-        self.pos.fill_(position)
         out = self._out if self._graph is not None else None
         if self._graph is not None:
             self._graph.replay()
@@ -570,8 +692,66 @@ class DecodeStack(torch.nn.Module):
         last = [None if t is None else t.view(self.bs, T, -1)[:, -1].contiguous() for t in (h, delta)]
         return self._head(*last)
 
+    def _prefill_chunk_seq(self, toks, positions, lengths, slots):
+        """A chunk [n, T] of a ragged prefill; `positions`, `lengths`, `slots`: n host ints each.  Returns the last layer's (h, delta),
+        [n * T, hidden] (delta: its not-yet-added MLP output on the fused path, else None)."""
+        n, T = toks.shape
+        h, delta = self.embed(toks.reshape(-1)), None
+        if self.fused:
+            dev = [buf[:n] for buf in (self.prefill_pos_seq, self.prefill_len, self.prefill_slot)]
+            for buf, vals in zip(dev, (positions, lengths, slots)):
+                buf.copy_(torch.tensor(vals, dtype=torch.long))
+        for layer in self.layers:
+            if self.fused:
+                attn = partial(layer.prefill_attention, T=T, lengths=dev[1], slots=dev[2], per_sequence=True)
+                h, delta = layer.forward_fused(h, delta, attn, dev[0], self.cos, self.sin, self._gather_rows)
+            else:
+                h = layer.forward_prefill_seq(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows)
+        return h, delta
+
+    def _prefill_seq(self, tokens, position, chunk, lengths, slots):
+        """prefill() of a ragged stack when anything is per sequence."""
+        S, n, T = self.cfg.max_seq, tokens.shape[0], tokens.shape[1]
+
+        def ints(x, what):
+            if isinstance(x, torch.Tensor):
+                x = x.tolist()
+            vals = [operator.index(v) for v in x] if isinstance(x, (list, tuple)) else [operator.index(x)] * n
+            if len(vals) != n:
+                raise ValueError(f"{what}: {len(vals)} values for {n} sequences")
+            return vals
+
+        try:
+            position, lengths = ints(position, "position"), ints(T if lengths is None else lengths, "lengths")
+            if slots is None and n != self.bs:
+                raise ValueError(f"{n} sequences in a stack of bs = {self.bs} need `slots`")
+            slots = ints(list(range(self.bs)) if slots is None else slots, "slots")
+        except TypeError as e:
+            raise ValueError(f"position / lengths / slots must be host ints: {e}") from e
+        if any(not 0 <= x <= T for x in lengths):
+            raise ValueError(f"lengths {lengths}: each must be in [0, T = {T}]")
+        if any(p < 0 or p + x > S for p, x in zip(position, lengths)):
+            raise ValueError(f"positions {position} + lengths {lengths} outside the KV cache [0, {S})")
+        if any(not 0 <= x < self.bs for x in slots) or len(set(slots)) != n:
+            raise ValueError(f"slots {slots}: {n} distinct values in [0, bs = {self.bs}) needed")
+        chunk = min(T, 2048) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError(f"chunk must be >= 1, got {chunk}")
+        # the last valid token of a sequence may lie in any chunk: its row of the last layer's output is picked on the device
+        last = torch.tensor([max(x - 1, 0) for x in lengths], dtype=torch.long).to(tokens.device)
+        keep = None
+        for c0 in range(0, T, chunk):
+            toks = tokens[:, c0: c0 + chunk]
+            Tc = toks.shape[1]
+            hd = self._prefill_chunk_seq(toks, [p + c0 for p in position], [min(max(x - c0, 0), Tc) for x in lengths], slots)
+            idx = (last - c0).clamp(0, Tc - 1).view(n, 1, 1)
+            here = ((last >= c0) & (last < c0 + Tc)).view(n, 1)
+            rows = [None if t is None else t.view(n, Tc, -1).gather(1, idx.expand(n, 1, t.shape[-1])).squeeze(1) for t in hd]
+            keep = rows if keep is None else [None if r is None else torch.where(here, r, k) for r, k in zip(rows, keep)]
+        return self._head(*[None if t is None else t.contiguous() for t in keep])
+
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, position: Optional[int] = 0, chunk: Optional[int] = None) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, position=0, chunk: Optional[int] = None, lengths=None, slots=None) -> torch.Tensor:
         """Feed a prompt: `tokens` [bs, T] at sequence positions position ... position + T - 1.  Every layer's KV cache receives the T
         rows a token-by-token `decode()` would have written (bit for bit on the fused path), and the logits [bs, vocab] of the LAST
         token are returned (the final hidden state when built without LM head) -- `decode()` continues at position + T.
@@ -581,7 +761,22 @@ class DecodeStack(torch.nn.Module):
         captured decode graph is not disturbed): pass position=None to leave that buffer as the caller set it (single chunk, fused
         path only; the kernel itself ignores tokens whose position is outside the cache).
         world > 1: attention stays local (heads are split across ranks); the four exchanges of a layer are all_gathers at bs * T
-        rows, also with gather="peer" (the peer-write buffers are sized for the `bs` rows of a decode step)."""
+        rows, also with gather="peer" (the peer-write buffers are sized for the `bs` rows of a decode step).
+        A ragged stack: `tokens` [n, T], rows padded on the right to the common T.  `position`: an int or n host ints; `lengths`: n host
+        ints in [0, T] (default T), sequence i has tokens[i, :lengths[i]] at positions position[i] ...; `slots`: n distinct host ints in
+        [0, bs), the cache slot (= row of a later `decode`) of each sequence (default: slot i, and n == bs).  Chunks advance every
+        sequence by `chunk` tokens.  Returns logits [n, vocab] of each sequence's LAST VALID token (unspecified for a length of 0);
+        cache slots not named are not touched."""
+        seq_args = lengths is not None or slots is not None or isinstance(position, (list, tuple)) or \
+            (isinstance(position, torch.Tensor) and position.dim() > 0)
+        if seq_args:
+            if not self.ragged:
+                raise ValueError("positions / lengths / slots per sequence need DecodeStack(..., ragged=True)")
+            if position is None:
+                raise ValueError("position=None (the caller owns prefill_pos) does not go with lengths / slots")
+            if tokens.dim() != 2 or tokens.shape[0] < 1 or tokens.shape[0] > self.bs or tokens.shape[1] < 1:
+                raise ValueError(f"tokens must be [1 <= n <= bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
+            return self._prefill_seq(tokens, position, chunk, lengths, slots)
         if tokens.dim() != 2 or tokens.shape[0] != self.bs or tokens.shape[1] < 1:
             raise ValueError(f"tokens must be [bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
         T = tokens.shape[1]
@@ -602,18 +797,50 @@ class DecodeStack(torch.nn.Module):
         return out
 
     @torch.no_grad()
-    def generate(self, prompt: torch.Tensor, new_tokens: int) -> torch.Tensor:
+    def generate(self, prompt, new_tokens: int, eos: Optional[int] = None) -> torch.Tensor:
         """Greedy continuation: `prefill(prompt)` [bs, T], then `decode` (graph replay if captured) from position T.
-        Returns the `new_tokens` generated token ids [bs, new_tokens]."""
+        Returns the `new_tokens` generated token ids [bs, new_tokens].
+        A ragged stack also takes a list of `bs` 1-D token tensors of different lengths, and `eos`: a sequence that has emitted `eos`,
+        or whose next position would be outside the cache, is inactive from the next step on (decided on the device, no sync per
+        step) and its remaining outputs are `eos` (-1 when eos is None)."""
         if self.lm_head is None:
             raise ValueError("generate needs the LM head")
         if new_tokens < 1:
             raise ValueError(f"new_tokens must be >= 1, got {new_tokens}")
+        if isinstance(prompt, (list, tuple)) or eos is not None:
+            if not self.ragged:
+                raise ValueError("prompts of different lengths / eos need DecodeStack(..., ragged=True)")
+            return self._generate_seq(list(prompt.unbind(0)) if isinstance(prompt, torch.Tensor) else list(prompt), new_tokens, eos)
         T = prompt.shape[1] if prompt.dim() == 2 else 0
         tok = self.prefill(prompt).argmax(-1)
         out = [tok.clone()]
         for i in range(new_tokens - 1):
             tok = self.decode(tok, T + i).argmax(-1)
+            out.append(tok.clone())
+        return torch.stack(out, dim=1)
+
+    @torch.no_grad()
+    def _generate_seq(self, prompts, new_tokens, eos):
+        """generate() on a ragged stack: right-padded prefill with lengths, then steps at positions len_b + i; who is still active is
+        kept on the device."""
+        if len(prompts) != self.bs or any(p.dim() != 1 or p.numel() < 1 for p in prompts):
+            raise ValueError(f"prompts must be bs = {self.bs} non-empty 1-D token tensors")
+        lens = [p.numel() for p in prompts]
+        dev = self.tokens.device
+        padded = torch.zeros(self.bs, max(lens), dtype=torch.long, device=dev)
+        for b, p in enumerate(prompts):
+            padded[b, : lens[b]] = p.to(dev)
+        tok = self.prefill(padded, position=0, lengths=lens).argmax(-1)
+        base = torch.tensor(lens, dtype=torch.long).to(dev)
+        alive = torch.ones(self.bs, dtype=torch.bool, device=dev)
+        fill = -1 if eos is None else int(eos)
+        out = [tok.clone()]
+        for i in range(new_tokens - 1):
+            if eos is not None:
+                alive = alive & (tok != eos)
+            alive = alive & (base + i < self.cfg.max_seq)
+            logits = self.decode(torch.where(alive, tok, 0), torch.where(alive, base + i, -1))
+            tok = torch.where(alive, logits.argmax(-1), fill)
             out.append(tok.clone())
         return torch.stack(out, dim=1)
 

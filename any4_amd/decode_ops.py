@@ -80,9 +80,20 @@ def decode_attn(q: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor, p
     return out
 
 
-def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale):
-    """rope_attn / rope_attn_online: two kernels behind one argument list."""
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d)
+def _per_sequence(pos, n, what):
+    """`pos` (already checked: int64, contiguous, on the device) holds one position per sequence."""
+    if pos.numel() != n:
+        raise RuntimeError(f"{what}: per_sequence needs {n} int64 positions (one per sequence), got {pos.numel()}")
+
+
+def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None):
+    """rope_attn / rope_attn_online: two kernels behind one argument list (per_sequence: their _seq entry points, `pos` [bs])."""
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, out=out)
+    if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"{entry}: out must be [{bs}, {hl * d}] {qkv.dtype}")
+    if per_sequence:
+        _per_sequence(pos, bs, entry)
+        entry += "_seq"
     _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
                                            v_cache.data_ptr(), out.data_ptr(), bs, hl, kvl, d, max_seq, float(scale), _dt(qkv),
                                            qkv.device.index, _stream(qkv)), entry)
@@ -90,16 +101,20 @@ def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale):
 
 
 def rope_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
-              v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float) -> torch.Tensor:
-    """rope_kv + decode_attn in one launch: qkv [bs, (hl + 2 kvl) d] -> context [bs, hl * d]; caches updated at `pos`."""
-    return _rope_attn("dg_rope_attn", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale)
+              v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, per_sequence: bool = False,
+              out: torch.Tensor = None) -> torch.Tensor:
+    """rope_kv + decode_attn in one launch: qkv [bs, (hl + 2 kvl) d] -> context [bs, hl * d]; caches updated at `pos`.
+    per_sequence: `pos` is int64 [bs], sequence b sits at pos[b]; a sequence whose position is outside [0, max_seq) writes nothing
+    and leaves its row of `out` (allocated here, uninitialised, unless given) as it was."""
+    return _rope_attn("dg_rope_attn", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
 
 
 def rope_attn_online(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
-                     v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float) -> torch.Tensor:
+                     v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, per_sequence: bool = False,
+                     out: torch.Tensor = None) -> torch.Tensor:
     """rope_attn built for latency (head_dim 64 / 128): one barrier, every load issued up front, softmax statistics combined
-    flash-decoding style -- the same caches bit for bit, the output within 16-bit rounding of rope_attn's."""
-    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale)
+    flash-decoding style -- the same caches bit for bit, the output within 16-bit rounding of rope_attn's.  per_sequence: as rope_attn."""
+    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
 
 
 def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> torch.Tensor:
@@ -109,28 +124,54 @@ def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> to
 
 
 def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
-                    v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int) -> torch.Tensor:
-    """rope_attn with the sequence split over `nsplit` blocks per head (fills the GPU at batch 1 / long contexts)."""
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch)
-    _lib.check(_lib.load().dg_rope_attn_split(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
+                    v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int,
+                    per_sequence: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """rope_attn with the sequence split over `nsplit` blocks per head (fills the GPU at batch 1 / long contexts).
+    per_sequence, out: as rope_attn."""
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, out=out)
+    if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"dg_rope_attn_split: out must be [{bs}, {hl * d}] {qkv.dtype}")
+    entry = "dg_rope_attn_split"
+    if per_sequence:
+        _per_sequence(pos, bs, entry)
+        entry += "_seq"
+    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
                                               v_cache.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, bs, hl,
                                               kvl, d, max_seq, float(scale), nsplit, _dt(qkv), qkv.device.index, _stream(qkv)),
-               "dg_rope_attn_split")
+               entry)
     return out
 
 
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
-                 v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None) -> torch.Tensor:
+                 v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None,
+                 lengths: torch.Tensor = None, slots: torch.Tensor = None, per_sequence: bool = False) -> torch.Tensor:
     """A chunk of T tokens per sequence: qkv [bs * T, (hl + 2 kvl) d] (row b * T + t) -> context [bs * T, hl * d]; the T roped k rows and
     the v rows are appended to the caches at positions pos ... pos + T - 1 (`pos` [1] int64 on the device = position of token 0), and
     token t attends causally over cache rows 0 ... pos + t.  A token whose position is outside the cache writes nothing and leaves its
-    row of `out` (allocated here unless given) as it was."""
-    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, out=out)
+    row of `out` (allocated here unless given) as it was.
+    per_sequence (also implied by `lengths` / `slots`): qkv is [n * T, ...], rows padded to the common T, and `pos` int64 [n] holds the
+    position of token 0 of each sequence.  `lengths` int64 [n] on the device: only tokens t < min(lengths[i], T) exist (default: all T);
+    `slots` int64 [n] on the device: sequence i lives in cache slot slots[i] (default: slot i, and n must be the caches' batch; with
+    slots n may be smaller).  A sequence of length <= 0 or with a slot outside the caches does nothing; slots must be distinct."""
+    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, out=out)
     T = int(T)
-    if T < 1 or qkv.dim() != 2 or rows % T or rows // T != k_cache.shape[0]:
+    per_sequence = per_sequence or lengths is not None or slots is not None
+    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != k_cache.shape[0] and slots is None):
         raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {k_cache.shape[0]} (the caches'), got {tuple(qkv.shape)}")
     if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"prefill_attn: out must be [{rows}, {hl * d}] {qkv.dtype}")
+    if per_sequence:
+        n = rows // T
+        _per_sequence(pos, n, "prefill_attn")
+        for name, t in (("lengths", lengths), ("slots", slots)):
+            if t is not None and (t.dtype != torch.int64 or t.numel() != n):
+                raise RuntimeError(f"prefill_attn: {name} must be int64 with {n} elements (one per sequence)")
+        _lib.check(_lib.load().dg_prefill_attn_seq(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
+                                                   None if lengths is None else lengths.data_ptr(),
+                                                   None if slots is None else slots.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                                                   out.data_ptr(), n, T, k_cache.shape[0], hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                                   qkv.device.index, _stream(qkv)), "dg_prefill_attn_seq")
+        return out
     _lib.check(_lib.load().dg_prefill_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
                                            v_cache.data_ptr(), out.data_ptr(), rows // T, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
                                            qkv.device.index, _stream(qkv)), "dg_prefill_attn")

@@ -103,6 +103,37 @@ TG_API int dg_prefill_attn(const void* qkv, const float* cos, const float* sin, 
                            void* out, int64_t bs, int64_t T, int hl, int kvl, int d, int64_t max_seq, float scale,
                            int dtype, int device, tg_stream_t stream);
 
+/* ---- a position per sequence (ragged batches) ----
+ * dg_rope_attn_seq / dg_rope_attn_online_seq / dg_rope_attn_split_seq: their namesakes' argument lists, arithmetic, rounding points,
+ * shape limits and scratch protocol, with `pos` an int64[bs] on the device: sequence b sits at pos[b] (one read per workgroup, as
+ * `*pos` is).  A sequence whose pos[b] is outside [0, max_seq) -- an inactive batch slot, by convention -1 -- writes no cache row
+ * and leaves its row of `out` unwritten, which is what the scalar entry points do for the whole batch.  For every other sequence
+ * the cache rows and the output row are, bit for bit, those of the namesake called for that sequence alone. */
+TG_API int dg_rope_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
+                            void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                            int dtype, int device, tg_stream_t stream);
+TG_API int dg_rope_attn_online_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
+                                   void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                                   int dtype, int device, tg_stream_t stream);
+TG_API int dg_rope_attn_split_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
+                                  void* v_cache, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                  int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+
+/* dg_prefill_attn with position, length and cache slot per sequence.  qkv [n * T][(hl + 2 kvl) * d]: row i * T + t = token t of
+ * chunk-sequence i, rows padded to the common T; out [n * T][hl * d] likewise.  All three arrays are int64 on the device:
+ *   pos  [n]           position of token 0 of sequence i
+ *   len  [n] or NULL   only tokens t < min(len[i], T) exist (NULL: all T); later rows write nothing, are seen by nobody and leave
+ *                      their output rows unwritten; len[i] <= 0 makes sequence i a no-op
+ *   slot [n] or NULL   sequence i lives in k_cache[slot[i]] / v_cache[slot[i]] of caches [cache_bs][kvl][max_seq][d] (NULL: slot i,
+ *                      and n == cache_bs is required); a slot outside [0, cache_bs) makes sequence i a no-op.  Slots must be
+ *                      distinct (the caller's obligation); whatever the three arrays hold, nothing outside the caches is indexed.
+ * Everything else is dg_prefill_attn's: two launches, no scratch, no atomics; rows above a token's own position are never read,
+ * tile rows beyond a workgroup's last valid position are zero-filled on chip; d = 64 / 128, max_seq <= 8192, n <= 65535.  For an
+ * existing token the cache rows and the output row are, bit for bit, dg_prefill_attn's for that sequence alone with T = len[i]. */
+TG_API int dg_prefill_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                               const int64_t* slot, void* k_cache, void* v_cache, void* out, int64_t n, int64_t T, int64_t cache_bs,
+                               int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

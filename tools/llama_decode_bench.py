@@ -8,6 +8,13 @@
 Random-initialised weights of the named architecture (no checkpoints here), random token ids, one new token per
 sequence per step over a static KV cache.  Prints one JSON line on rank 0: ms per token, tokens/s, and the rate at which
 the 4-bit weights stream (algorithmic bytes of the quantized linears / step time).
+
+    python tools/llama_decode_bench.py --config llama3_8b --ragged [--out profiles/ragged_bench.jsonl]
+
+--ragged (one GPU): what a position per sequence costs and buys, one JSON line per leg, appended to --out:
+  (a) the captured step of a ragged and a non-ragged stack at equal positions, bs = 1 / 4 / 8, alternating in one process;
+  (b) eight prompts of 16 ... 512 tokens through `generate(list)` on one ragged bs = 8 stack against the only route there is without
+      it, eight bs = 1 `generate` runs one after the other; tokens/s of the new tokens.
 """
 import argparse
 import json
@@ -38,6 +45,56 @@ def time_steps(stack, steps, warmup, start_pos):
     return (time.perf_counter() - t0) / steps
 
 
+def ragged_bench(a, cfg, device):
+    """The two legs of --ragged; returns the JSON-able results."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    def stack(bs, ragged):
+        st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                         fuse_gemm_stages=not a.no_fuse, ragged=ragged)
+        st.capture()
+        return st
+
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "data": "synthetic (random weights, random tokens)"}
+    legs = []
+    # (a) the same step, positions [p] * bs through pos_seq vs p through pos; rounds alternate so that drift hits both alike
+    leg = dict(base, leg="a: captured step at equal positions, ragged vs non-ragged, alternating", steps=a.steps, warmup=a.warmup,
+               start_pos=a.start_pos, rounds=a.rounds, ms_per_step={})
+    for bs in (1, 4, 8):
+        pair = {"plain": stack(bs, False), "ragged": stack(bs, True)}
+        series = {k: [] for k in pair}
+        for r in range(a.rounds):
+            for k in (("plain", "ragged") if r % 2 == 0 else ("ragged", "plain")):
+                series[k].append(round(time_steps(pair[k], a.steps, a.warmup, a.start_pos) * 1e3, 4))
+        leg["ms_per_step"][f"bs{bs}"] = {k: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "series": v}
+                                         for k, v in series.items()}
+        del pair
+        torch.cuda.empty_cache()
+    legs.append(leg)
+    # (b) a ragged batch of eight against eight runs at batch 1
+    lengths, new = [16, 32, 64, 96, 128, 256, 384, 512], a.new_tokens
+    gen = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, cfg.vocab, (n,), generator=gen).to(device) for n in lengths]
+
+    def timed(fn):
+        fn()  # (first call: allocator, workspaces)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    one, eight = stack(1, False), stack(8, True)
+    t_seq = timed(lambda: [one.generate(p.view(1, -1), new) for p in prompts])
+    t_rag = timed(lambda: eight.generate(prompts, new))
+    legs.append(dict(base, leg="b: eight prompts, generate(list) on a ragged bs = 8 stack vs eight bs = 1 runs in a row",
+                     prompt_lengths=lengths, new_tokens=new,
+                     sequential_bs1={"seconds": round(t_seq, 4), "tokens_per_s": round(8 * new / t_seq, 1)},
+                     ragged_bs8={"seconds": round(t_rag, 4), "tokens_per_s": round(8 * new / t_rag, 1)},
+                     speedup=round(t_seq / t_rag, 3)))
+    return legs
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "tiny"])
@@ -62,6 +119,10 @@ def main():
     ap.add_argument("--same-device", action="store_true",
                     help="functional check on a one-GPU box: every rank uses GPU 0 (needs --backend gloo --gather peer); the time "
                          "it prints is two processes sharing one GPU, not a TP measurement")
+    ap.add_argument("--ragged", action="store_true", help="the two legs of DESIGN.md section 13 (see the module docstring); one GPU")
+    ap.add_argument("--rounds", type=int, default=7, help="--ragged leg (a): alternations per batch size")
+    ap.add_argument("--new-tokens", type=int, default=64, help="--ragged leg (b): tokens generated per prompt")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_bench.jsonl"), help="--ragged: the file the JSON lines are appended to")
     a = ap.parse_args()
     if a.backend == "gloo" and a.gather != "peer":
         raise SystemExit("--backend gloo moves no CUDA tensors: use it with --gather peer")
@@ -88,6 +149,16 @@ def main():
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.ragged:
+        if world > 1:
+            raise SystemExit("--ragged runs on one GPU")
+        with open(a.out, "a") as f:
+            for leg in ragged_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     def run(factory_cls, label):
         torch.cuda.reset_peak_memory_stats(device)
