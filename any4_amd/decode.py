@@ -20,6 +20,13 @@ Launch structure, chosen for the hardware rather than copied from HF:
   * `DecodeLayer` states the layer once per schedule -- plain torch (`forward`, `forward_prefill`), eight launches (`forward_fused`),
     five launches (`forward_fused5`: the element-wise stages ride in the GEMMs) -- and the fused schedules take the attention launch as
     an argument: `decode_attention` (one token per sequence) or `prefill_attention` (a chunk; so far on the eight launches only);
+  * one position model: a stack whose sequences share a position is the ragged one (`ragged=True`: a position per sequence) with every
+    position equal, so `DecodeStack` has one step, one `decode` front, one prefill loop (positions, lengths and cache slots as host
+    lists; a call that names none per sequence still launches the scalar attention on `prefill_pos`) and one `generate`.  What differs
+    is which buffer the step reads (`pos` [1] or `pos_seq` [bs]) and which flavour of the attention launch it makes.  In plain torch the
+    token's arithmetic is written once (`DecodeLayer._token_torch`) behind two addressings that are kept apart on purpose: `forward`
+    (one rope row, `index_copy_`, one mask) and `forward_seq` (a row per sequence, gather / where / scatter, a mask per sequence) are
+    compared bit for bit by tests/test_ragged_cpu.py, which is a check only while they are written independently;
   * tensor parallelism = row-sharding of every linear (any4_amd/shard.py): heads are split across ranks so
     attention and the KV cache stay local; per layer 4 all-gathers of [bs, n/G] partial outputs (attention
     output, o_proj, SwiGLU activation, down_proj) over RCCL.  One process per GPU.
@@ -257,21 +264,31 @@ class DecodeLayer(torch.nn.Module):
         # decode_attention: the stack's split count and its scratch buffer (DecodeStack sets both once, when it is built)
         self._attn_scratch, self._attn_split = None, 1
 
-    def forward(self, h, pos, cos, sin, mask, gather):
-        """Plain torch, one token per sequence (the formulation the fused schedules are tested against)."""
+    def _token_torch(self, h, cos, sin, write, mask, gather):
+        """The plain-torch arithmetic of one token per sequence, behind either addressing (`forward`, `forward_seq`): `cos` / `sin` the
+        rope rows [1 | bs, 1, d], `write(cache, rows [bs, kvl, d])` puts the new k / v rows into a cache, `mask` [1 | bs, 1, 1, S] hides
+        the cache rows behind each position.  Rounding points: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit
+        P.V (the formulation the fused schedules are tested against)."""
         d, bs = self.cfg.head_dim, h.shape[0]
         qkv = self.qkv(self.norm1(h))
         q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
         k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
         v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
-        self.k_cache.index_copy_(2, pos, k.unsqueeze(2))
-        self.v_cache.index_copy_(2, pos, v.unsqueeze(2))
+        write(self.k_cache, k)
+        write(self.v_cache, v)
         rep = self.hl // self.kvl
         qg = q.reshape(bs, self.kvl, rep, d)
         att = torch.matmul(qg, self.k_cache.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
         att = att.masked_fill(mask, float("-inf")).softmax(-1).to(h.dtype)
         ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+
+    def forward(self, h, pos, cos_tab, sin_tab, arange, gather):
+        """Plain torch, one token per sequence, every sequence at `pos` [1] on the device: one rope row, one cache row and one mask
+        for the batch."""
+        cos, sin = cos_tab.index_select(0, pos).view(1, 1, -1), sin_tab.index_select(0, pos).view(1, 1, -1)
+        return self._token_torch(h, cos, sin, lambda cache, new: cache.index_copy_(2, pos, new.unsqueeze(2)),
+                                 (arange > pos).view(1, 1, 1, -1), gather)
 
     def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather):
         """`forward` with a position per sequence: `pos` int64 [bs] on the device.  Sequence b takes rope row pos[b], writes cache row
@@ -281,31 +298,17 @@ class DecodeLayer(torch.nn.Module):
         active = (pos >= 0) & (pos < self.cfg.max_seq)
         pc = pos.clamp(0, self.cfg.max_seq - 1)
         cos, sin = cos_tab.index_select(0, pc).view(bs, 1, d), sin_tab.index_select(0, pc).view(bs, 1, d)
-        qkv = self.qkv(self.norm1(h))
-        q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
-        k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
-        v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
-        _scatter_rows(self.k_cache, pc, active, k)
-        _scatter_rows(self.v_cache, pc, active, v)
-        rep = self.hl // self.kvl
-        qg = q.reshape(bs, self.kvl, rep, d)
-        att = torch.matmul(qg, self.k_cache.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
-        att = att.masked_fill(arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), float("-inf")).softmax(-1).to(h.dtype)
-        ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
-        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+        return self._token_torch(h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
+                                 arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
 
-    def forward_prefill_seq(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
-        """`forward_prefill` with a position, a length and a cache slot per sequence (host ints): `h` [n * T, hidden], rows padded to T."""
+    def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
+        """Plain torch, a chunk of tokens per sequence: `h` [n * T, hidden] (row i * T + t), rows padded to the common T.  Host ints
+        per sequence: token 0 of sequence i at `positions[i]`, `lengths[i]` tokens, cache slot `slots[i]`.  Each sequence's k / v rows
+        are appended to its caches and every token attends causally over cache + chunk (a batch in which nothing differs: in one
+        batched formulation, prefill_attention_torch)."""
         d = self.cfg.head_dim
         ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
                                           self.hl, self.kvl, d, T)
-        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
-
-    def forward_prefill(self, h, p0: int, T: int, cos_tab, sin_tab, gather):
-        """Plain torch, a chunk of T tokens per sequence: `h` [bs * T, hidden] (row b * T + t), token 0 at position `p0` (on the
-        host).  The T rows of k / v are appended to the caches and every token attends causally over cache + chunk."""
-        d = self.cfg.head_dim
-        ctx = prefill_attention_torch(self.qkv(self.norm1(h)), cos_tab, sin_tab, p0, self.k_cache, self.v_cache, self.hl, self.kvl, d, T)
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
     def _mlp_torch(self, h, gather):
@@ -565,38 +568,20 @@ class DecodeStack(torch.nn.Module):
         return logits if logits is not None else self.lm_head(y)
 
     def _step(self) -> torch.Tensor:
-        if self.ragged:
-            return self._step_seq()
-        pos = self.pos
+        """The three schedules.  A ragged stack reads `pos_seq` [bs] where the other reads `pos` [1]: its plain-torch layer addresses
+        per sequence (forward_seq), its attention launches are the _seq entry points."""
+        pos = self.pos_seq if self.ragged else self.pos
         h, delta = self.embed(self.tokens), None
-        if not self.fused:
-            cos = self.cos.index_select(0, pos).view(1, 1, -1)
-            sin = self.sin.index_select(0, pos).view(1, 1, -1)
-            mask = (self.arange > pos).view(1, 1, 1, -1)
-            for layer in self.layers:
-                h = layer(h, pos, cos, sin, mask, self._gather)
-        elif self._five_launch():
-            for layer in self.layers:
-                h = layer.forward_fused5(h, layer.decode_attention, pos, self.cos, self.sin)
-        else:
-            for layer in self.layers:
-                h, delta = layer.forward_fused(h, delta, layer.decode_attention, pos, self.cos, self.sin, self._gather)
-        return self._head(h, delta)
-
-    def _step_seq(self) -> torch.Tensor:
-        """_step with a position per sequence (`pos_seq`): the same schedules, the attention launches read pos_seq[b]."""
-        pos = self.pos_seq
-        h, delta = self.embed(self.tokens), None
-        if not self.fused:
-            for layer in self.layers:
-                h = layer.forward_seq(h, pos, self.cos, self.sin, self.arange, self._gather)
-        elif self._five_launch():
-            for layer in self.layers:
-                h = layer.forward_fused5(h, partial(layer.decode_attention, per_sequence=True), pos, self.cos, self.sin)
-        else:
-            for layer in self.layers:
-                h, delta = layer.forward_fused(h, delta, partial(layer.decode_attention, per_sequence=True), pos, self.cos, self.sin,
-                                               self._gather)
+        five = self._five_launch()
+        for layer in self.layers:
+            if not self.fused:
+                h = (layer.forward_seq if self.ragged else layer)(h, pos, self.cos, self.sin, self.arange, self._gather)
+                continue
+            attention = partial(layer.decode_attention, per_sequence=True) if self.ragged else layer.decode_attention
+            if five:
+                h = layer.forward_fused5(h, attention, pos, self.cos, self.sin)
+            else:
+                h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather)
         return self._head(h, delta)
 
     @torch.no_grad()
@@ -617,27 +602,37 @@ class DecodeStack(torch.nn.Module):
             # + embedding gather, final norm, LM head
             self.graph_nodes = sum(layer.launches() for layer in self.layers) + 2 + (1 if self.lm_head is not None else 0)
 
-    @torch.no_grad()
-    def _set_positions(self, position) -> None:
-        """decode()'s `position` of a ragged stack into `pos_seq`: host values are checked here, a device tensor is copied as it is
-        (no sync; the kernels ignore a sequence whose position is outside the cache)."""
-        S = self.cfg.max_seq
-        if isinstance(position, torch.Tensor) and position.device.type != "cpu":
+    def _set_position(self, position) -> None:
+        """decode()'s `position` into the step's position buffer (`pos_seq` of a ragged stack, else `pos`).  Host values are checked
+        here; a ragged stack's device tensor is copied as it is (no sync; the kernels ignore a sequence whose position is outside
+        the cache)."""
+        S, buf = self.cfg.max_seq, self.pos_seq if self.ragged else self.pos
+        if self.ragged and isinstance(position, torch.Tensor) and position.device.type != "cpu":
             if position.dtype != torch.long or position.numel() != self.bs:
                 raise ValueError(f"a device position must be int64 [bs = {self.bs}], got {position.dtype} {tuple(position.shape)}")
-            self.pos_seq.copy_(position.view(-1))
+            buf.copy_(position.view(-1))
             return
-        if isinstance(position, torch.Tensor):
-            position = position.tolist()
-        vals = [operator.index(p) for p in position] if isinstance(position, (list, tuple)) else [operator.index(position)] * self.bs
-        if len(vals) != self.bs:
+        try:
+            if self.ragged and isinstance(position, torch.Tensor):
+                position = position.tolist()
+            if self.ragged and isinstance(position, (list, tuple)):
+                vals = [operator.index(p) for p in position]
+            else:  # one position for every sequence; all a non-ragged stack takes
+                vals = [operator.index(position)] * buf.numel()
+        except TypeError as e:
+            if self.ragged:
+                raise ValueError(f"position must be an int, {self.bs} ints or an int64 device tensor: {e}") from e
+            raise ValueError("a position per sequence needs DecodeStack(..., ragged=True)") from e
+        if len(vals) != buf.numel():
             raise ValueError(f"{len(vals)} positions for bs = {self.bs} sequences")
+        if not self.ragged and not 0 <= vals[0] < S:
+            raise ValueError(f"position {vals[0]} outside the KV cache [0, {S})")
         if any(not (p == -1 or 0 <= p < S) for p in vals):
             raise ValueError(f"positions {vals}: each must be -1 (inactive) or inside the KV cache [0, {S})")
         if len(set(vals)) == 1:
-            self.pos_seq.fill_(vals[0])  # (a fill, as for `pos`: no copy from host memory in the way of the launches)
+            buf.fill_(vals[0])  # (a fill: no copy from host memory in the way of the launches)
         else:
-            self.pos_seq.copy_(torch.tensor(vals, dtype=torch.long))
+            buf.copy_(torch.tensor(vals, dtype=torch.long))
 
     @torch.no_grad()
     def decode(self, tokens: torch.Tensor, position) -> torch.Tensor:
@@ -645,19 +640,7 @@ class DecodeStack(torch.nn.Module):
         A ragged stack also takes a position per sequence: a list / CPU tensor of `bs` ints, each -1 (the sequence is inactive: it
         writes no cache row and its logits row is unspecified) or inside the cache, or an int64 device tensor [bs], which is copied
         without a sync and without a host check (the kernels ignore positions outside the cache)."""
-        if self.ragged:
-            try:
-                self._set_positions(position)
-            except TypeError as e:
-                raise ValueError(f"position must be an int, {self.bs} ints or an int64 device tensor: {e}") from e
-        else:
-            try:
-                position = operator.index(position)
-            except TypeError as e:
-                raise ValueError("a position per sequence needs DecodeStack(..., ragged=True)") from e
-            if not 0 <= position < self.cfg.max_seq:
-                raise ValueError(f"position {position} outside the KV cache [0, {self.cfg.max_seq})")
-            self.pos.fill_(position)
+        self._set_position(position)
         self.tokens.copy_(tokens)
         out = self._out if self._graph is not None else None
         if self._graph is not None:
@@ -677,41 +660,69 @@ class DecodeStack(torch.nn.Module):
         """_gather for bs * T rows: always the all_gather branch (the peer-write buffers are sized for `bs` rows)."""
         return self._gather(y, peer_ok=False)
 
-    def _prefill_chunk(self, toks, p0, want_logits):
-        T = toks.shape[1]
-        h = self.embed(toks.reshape(-1))  # [bs * T, hidden], row b * T + t
-        delta = None
-        for layer in self.layers:
-            if self.fused:  # the eight launches of a decode step at bs * T rows, with the chunk's attention
-                h, delta = layer.forward_fused(h, delta, layer.prefill_attention, self.prefill_pos, self.cos, self.sin, self._gather_rows)
-            else:           # plain torch needs the position on the host (prefill() refuses position=None on this path)
-                h = layer.forward_prefill(h, p0, T, self.cos, self.sin, self._gather_rows)
-        if not want_logits:
-            return None
-        # the LM head runs on the last token of every sequence only
-        last = [None if t is None else t.view(self.bs, T, -1)[:, -1].contiguous() for t in (h, delta)]
-        return self._head(*last)
-
-    def _prefill_chunk_seq(self, toks, positions, lengths, slots):
-        """A chunk [n, T] of a ragged prefill; `positions`, `lengths`, `slots`: n host ints each.  Returns the last layer's (h, delta),
-        [n * T, hidden] (delta: its not-yet-added MLP output on the fused path, else None)."""
+    def _prefill_chunk(self, toks, positions, lengths, slots, per_sequence):
+        """A chunk `toks` [n, T] through every layer; `positions`, `lengths`, `slots`: n host ints each.  Returns the last layer's
+        (h, delta), [n * T, hidden] (delta: its not-yet-added MLP output on the fused path, else None).  The fused attention launch is
+        the scalar entry point on `prefill_pos` (set to positions[0] here; positions None: left as the caller set it) or, per_sequence,
+        the _seq one on the first n of `prefill_pos_seq` / `prefill_len` / `prefill_slot`."""
         n, T = toks.shape
-        h, delta = self.embed(toks.reshape(-1)), None
-        if self.fused:
-            dev = [buf[:n] for buf in (self.prefill_pos_seq, self.prefill_len, self.prefill_slot)]
-            for buf, vals in zip(dev, (positions, lengths, slots)):
+        if not per_sequence and positions is not None:
+            self.prefill_pos.fill_(positions[0])
+        h, delta = self.embed(toks.reshape(-1)), None  # [n * T, hidden], row i * T + t
+        pos = self.prefill_pos
+        if per_sequence and self.fused:
+            pos, dev_len, dev_slot = [buf[:n] for buf in (self.prefill_pos_seq, self.prefill_len, self.prefill_slot)]
+            for buf, vals in zip((pos, dev_len, dev_slot), (positions, lengths, slots)):
                 buf.copy_(torch.tensor(vals, dtype=torch.long))
         for layer in self.layers:
-            if self.fused:
-                attn = partial(layer.prefill_attention, T=T, lengths=dev[1], slots=dev[2], per_sequence=True)
-                h, delta = layer.forward_fused(h, delta, attn, dev[0], self.cos, self.sin, self._gather_rows)
-            else:
-                h = layer.forward_prefill_seq(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows)
+            if not self.fused:  # plain torch needs the positions on the host (prefill() refuses position=None on this path)
+                h = layer.forward_prefill(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows)
+                continue
+            # the eight launches of a decode step at n * T rows, with the chunk's attention
+            attention = layer.prefill_attention
+            if per_sequence:
+                attention = partial(attention, T=T, lengths=dev_len, slots=dev_slot, per_sequence=True)
+            h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather_rows)
         return h, delta
 
-    def _prefill_seq(self, tokens, position, chunk, lengths, slots):
-        """prefill() of a ragged stack when anything is per sequence."""
-        S, n, T = self.cfg.max_seq, tokens.shape[0], tokens.shape[1]
+    @staticmethod
+    def _last_rows(hd, n):
+        """The last token's row of every sequence out of a chunk's (h, delta), [n * T, hidden] each."""
+        return [None if t is None else t.view(n, -1, t.shape[-1])[:, -1].contiguous() for t in hd]
+
+    @torch.no_grad()
+    def prefill(self, tokens: torch.Tensor, position=0, chunk: Optional[int] = None, lengths=None, slots=None) -> torch.Tensor:
+        """Feed a prompt: `tokens` [bs, T] at sequence positions position ... position + T - 1.  Every layer's KV cache receives the T
+        rows a token-by-token `decode()` would have written (bit for bit on the fused path), and the logits [bs, vocab] of the LAST
+        token are returned (the final hidden state when built without LM head) -- `decode()` continues at position + T.
+        chunk: tokens per pass (default: the whole prompt up to 2048 tokens, longer prompts in pieces of 2048); later pieces attend
+        over the cache rows of the earlier ones, which bounds activation memory at bs * chunk rows.
+        Eager.  It is also legal inside `torch.cuda.graph` for a fixed T; the position lives in `self.prefill_pos` (not `self.pos`, so a
+        captured decode graph is not disturbed): pass position=None to leave that buffer as the caller set it (single chunk, fused
+        path only; the kernel itself ignores tokens whose position is outside the cache).
+        world > 1: attention stays local (heads are split across ranks); the four exchanges of a layer are all_gathers at bs * T
+        rows, also with gather="peer" (the peer-write buffers are sized for the `bs` rows of a decode step).
+        A ragged stack: `tokens` [n, T], rows padded on the right to the common T.  `position`: an int or n host ints; `lengths`: n host
+        ints in [0, T] (default T), sequence i has tokens[i, :lengths[i]] at positions position[i] ...; `slots`: n distinct host ints in
+        [0, bs), the cache slot (= row of a later `decode`) of each sequence (default: slot i, and n == bs).  Chunks advance every
+        sequence by `chunk` tokens.  Returns logits [n, vocab] of each sequence's LAST VALID token (unspecified for a length of 0);
+        cache slots not named are not touched."""
+        per_sequence = lengths is not None or slots is not None or isinstance(position, (list, tuple)) or \
+            (isinstance(position, torch.Tensor) and position.dim() > 0)
+        if per_sequence and not self.ragged:
+            raise ValueError("positions / lengths / slots per sequence need DecodeStack(..., ragged=True)")
+        if per_sequence and position is None:
+            raise ValueError("position=None (the caller owns prefill_pos) does not go with lengths / slots")
+        if tokens.dim() != 2 or tokens.shape[1] < 1 or not (1 <= tokens.shape[0] <= self.bs if per_sequence else tokens.shape[0] == self.bs):
+            raise ValueError(f"tokens must be [{'1 <= n <= ' if per_sequence else ''}bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
+        S, (n, T) = self.cfg.max_seq, tokens.shape
+        if position is None:  # nothing is made on the host and copied here: a pageable copy is not legal inside a graph capture
+            if not self.fused or (chunk is not None and int(chunk) < T):
+                raise ValueError("position=None (the caller owns prefill_pos) needs the fused path and a single chunk")
+            return self._head(*self._last_rows(self._prefill_chunk(tokens, None, None, None, False), n))
+        # one model on the host: a position, a length and a slot per sequence (a call that names none: the same for everybody)
+        if not per_sequence:
+            position = int(position)
 
         def ints(x, what):
             if isinstance(x, torch.Tensor):
@@ -737,64 +748,22 @@ class DecodeStack(torch.nn.Module):
         chunk = min(T, 2048) if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
-        # the last valid token of a sequence may lie in any chunk: its row of the last layer's output is picked on the device
-        last = torch.tensor([max(x - 1, 0) for x in lengths], dtype=torch.long).to(tokens.device)
+        # the LM head runs on the last token of every sequence only.  Named per sequence, the last valid token may lie in any chunk: its
+        # row of the last layer's output is picked on the device; else it is the last row of the last chunk
+        last = torch.tensor([max(x - 1, 0) for x in lengths], dtype=torch.long).to(tokens.device) if per_sequence else None
         keep = None
         for c0 in range(0, T, chunk):
             toks = tokens[:, c0: c0 + chunk]
             Tc = toks.shape[1]
-            hd = self._prefill_chunk_seq(toks, [p + c0 for p in position], [min(max(x - c0, 0), Tc) for x in lengths], slots)
+            hd = self._prefill_chunk(toks, [p + c0 for p in position], [min(max(x - c0, 0), Tc) for x in lengths], slots, per_sequence)
+            if not per_sequence:
+                keep = self._last_rows(hd, n) if c0 + Tc >= T else None
+                continue
             idx = (last - c0).clamp(0, Tc - 1).view(n, 1, 1)
             here = ((last >= c0) & (last < c0 + Tc)).view(n, 1)
             rows = [None if t is None else t.view(n, Tc, -1).gather(1, idx.expand(n, 1, t.shape[-1])).squeeze(1) for t in hd]
             keep = rows if keep is None else [None if r is None else torch.where(here, r, k) for r, k in zip(rows, keep)]
         return self._head(*[None if t is None else t.contiguous() for t in keep])
-
-    @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, position=0, chunk: Optional[int] = None, lengths=None, slots=None) -> torch.Tensor:
-        """Feed a prompt: `tokens` [bs, T] at sequence positions position ... position + T - 1.  Every layer's KV cache receives the T
-        rows a token-by-token `decode()` would have written (bit for bit on the fused path), and the logits [bs, vocab] of the LAST
-        token are returned (the final hidden state when built without LM head) -- `decode()` continues at position + T.
-        chunk: tokens per pass (default: the whole prompt up to 2048 tokens, longer prompts in pieces of 2048); later pieces attend
-        over the cache rows of the earlier ones, which bounds activation memory at bs * chunk rows.
-        Eager.  It is also legal inside `torch.cuda.graph` for a fixed T; the position lives in `self.prefill_pos` (not `self.pos`, so a
-        captured decode graph is not disturbed): pass position=None to leave that buffer as the caller set it (single chunk, fused
-        path only; the kernel itself ignores tokens whose position is outside the cache).
-        world > 1: attention stays local (heads are split across ranks); the four exchanges of a layer are all_gathers at bs * T
-        rows, also with gather="peer" (the peer-write buffers are sized for the `bs` rows of a decode step).
-        A ragged stack: `tokens` [n, T], rows padded on the right to the common T.  `position`: an int or n host ints; `lengths`: n host
-        ints in [0, T] (default T), sequence i has tokens[i, :lengths[i]] at positions position[i] ...; `slots`: n distinct host ints in
-        [0, bs), the cache slot (= row of a later `decode`) of each sequence (default: slot i, and n == bs).  Chunks advance every
-        sequence by `chunk` tokens.  Returns logits [n, vocab] of each sequence's LAST VALID token (unspecified for a length of 0);
-        cache slots not named are not touched."""
-        seq_args = lengths is not None or slots is not None or isinstance(position, (list, tuple)) or \
-            (isinstance(position, torch.Tensor) and position.dim() > 0)
-        if seq_args:
-            if not self.ragged:
-                raise ValueError("positions / lengths / slots per sequence need DecodeStack(..., ragged=True)")
-            if position is None:
-                raise ValueError("position=None (the caller owns prefill_pos) does not go with lengths / slots")
-            if tokens.dim() != 2 or tokens.shape[0] < 1 or tokens.shape[0] > self.bs or tokens.shape[1] < 1:
-                raise ValueError(f"tokens must be [1 <= n <= bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
-            return self._prefill_seq(tokens, position, chunk, lengths, slots)
-        if tokens.dim() != 2 or tokens.shape[0] != self.bs or tokens.shape[1] < 1:
-            raise ValueError(f"tokens must be [bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
-        T = tokens.shape[1]
-        if position is None:
-            if not self.fused or (chunk is not None and int(chunk) < T):
-                raise ValueError("position=None (the caller owns prefill_pos) needs the fused path and a single chunk")
-            return self._prefill_chunk(tokens, None, True)
-        position = int(position)
-        if position < 0 or position + T > self.cfg.max_seq:
-            raise ValueError(f"positions [{position}, {position + T}) outside the KV cache [0, {self.cfg.max_seq})")
-        chunk = min(T, 2048) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError(f"chunk must be >= 1, got {chunk}")
-        out = None
-        for c0 in range(0, T, chunk):
-            self.prefill_pos.fill_(position + c0)
-            out = self._prefill_chunk(tokens[:, c0: c0 + chunk], position + c0, c0 + chunk >= T)
-        return out
 
     @torch.no_grad()
     def generate(self, prompt, new_tokens: int, eos: Optional[int] = None) -> torch.Tensor:
@@ -807,40 +776,35 @@ class DecodeStack(torch.nn.Module):
             raise ValueError("generate needs the LM head")
         if new_tokens < 1:
             raise ValueError(f"new_tokens must be >= 1, got {new_tokens}")
-        if isinstance(prompt, (list, tuple)) or eos is not None:
+        per_sequence = isinstance(prompt, (list, tuple)) or eos is not None
+        if not per_sequence:
+            base = prompt.shape[1] if prompt.dim() == 2 else 0  # a host int: decode() fills the position
+            tok = self.prefill(prompt).argmax(-1)
+        else:  # right-padded prefill with lengths; who is still active is kept on the device
             if not self.ragged:
                 raise ValueError("prompts of different lengths / eos need DecodeStack(..., ragged=True)")
-            return self._generate_seq(list(prompt.unbind(0)) if isinstance(prompt, torch.Tensor) else list(prompt), new_tokens, eos)
-        T = prompt.shape[1] if prompt.dim() == 2 else 0
-        tok = self.prefill(prompt).argmax(-1)
+            prompts = list(prompt.unbind(0)) if isinstance(prompt, torch.Tensor) else list(prompt)
+            if len(prompts) != self.bs or any(p.dim() != 1 or p.numel() < 1 for p in prompts):
+                raise ValueError(f"prompts must be bs = {self.bs} non-empty 1-D token tensors")
+            lens = [p.numel() for p in prompts]
+            dev = self.tokens.device
+            padded = torch.zeros(self.bs, max(lens), dtype=torch.long, device=dev)
+            for b, p in enumerate(prompts):
+                padded[b, : lens[b]] = p.to(dev)
+            tok = self.prefill(padded, position=0, lengths=lens).argmax(-1)
+            base = torch.tensor(lens, dtype=torch.long).to(dev)
+            alive = torch.ones(self.bs, dtype=torch.bool, device=dev)
+            fill = -1 if eos is None else int(eos)
         out = [tok.clone()]
-        for i in range(new_tokens - 1):
-            tok = self.decode(tok, T + i).argmax(-1)
-            out.append(tok.clone())
-        return torch.stack(out, dim=1)
-
-    @torch.no_grad()
-    def _generate_seq(self, prompts, new_tokens, eos):
-        """generate() on a ragged stack: right-padded prefill with lengths, then steps at positions len_b + i; who is still active is
-        kept on the device."""
-        if len(prompts) != self.bs or any(p.dim() != 1 or p.numel() < 1 for p in prompts):
-            raise ValueError(f"prompts must be bs = {self.bs} non-empty 1-D token tensors")
-        lens = [p.numel() for p in prompts]
-        dev = self.tokens.device
-        padded = torch.zeros(self.bs, max(lens), dtype=torch.long, device=dev)
-        for b, p in enumerate(prompts):
-            padded[b, : lens[b]] = p.to(dev)
-        tok = self.prefill(padded, position=0, lengths=lens).argmax(-1)
-        base = torch.tensor(lens, dtype=torch.long).to(dev)
-        alive = torch.ones(self.bs, dtype=torch.bool, device=dev)
-        fill = -1 if eos is None else int(eos)
-        out = [tok.clone()]
-        for i in range(new_tokens - 1):
-            if eos is not None:
-                alive = alive & (tok != eos)
-            alive = alive & (base + i < self.cfg.max_seq)
-            logits = self.decode(torch.where(alive, tok, 0), torch.where(alive, base + i, -1))
-            tok = torch.where(alive, logits.argmax(-1), fill)
+        for i in range(new_tokens - 1):  # the token emitted at step i is fed at position len_b + i
+            if not per_sequence:
+                tok = self.decode(tok, base + i).argmax(-1)
+            else:
+                if eos is not None:
+                    alive = alive & (tok != eos)
+                alive = alive & (base + i < self.cfg.max_seq)
+                logits = self.decode(torch.where(alive, tok, 0), torch.where(alive, base + i, -1))
+                tok = torch.where(alive, logits.argmax(-1), fill)
             out.append(tok.clone())
         return torch.stack(out, dim=1)
 

@@ -86,17 +86,21 @@ def _per_sequence(pos, n, what):
         raise RuntimeError(f"{what}: per_sequence needs {n} int64 positions (one per sequence), got {pos.numel()}")
 
 
-def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None):
-    """rope_attn / rope_attn_online: two kernels behind one argument list (per_sequence: their _seq entry points, `pos` [bs])."""
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, out=out)
+def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None):
+    """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
+    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split: its entry points take the scratch buffer (pointer, bytes) behind `out`
+    and nsplit behind the scale."""
+    scratch, nsplit = split if split is not None else (None, None)
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, out=out)
     if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"{entry}: out must be [{bs}, {hl * d}] {qkv.dtype}")
     if per_sequence:
         _per_sequence(pos, bs, entry)
         entry += "_seq"
+    mid, last = ((), ()) if split is None else ((scratch.data_ptr(), scratch.numel() * 4), (nsplit,))
     _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), out.data_ptr(), bs, hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                           qkv.device.index, _stream(qkv)), entry)
+                                           v_cache.data_ptr(), out.data_ptr(), *mid, bs, hl, kvl, d, max_seq, float(scale), *last,
+                                           _dt(qkv), qkv.device.index, _stream(qkv)), entry)
     return out
 
 
@@ -128,18 +132,7 @@ def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos
                     per_sequence: bool = False, out: torch.Tensor = None) -> torch.Tensor:
     """rope_attn with the sequence split over `nsplit` blocks per head (fills the GPU at batch 1 / long contexts).
     per_sequence, out: as rope_attn."""
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, out=out)
-    if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
-        raise RuntimeError(f"dg_rope_attn_split: out must be [{bs}, {hl * d}] {qkv.dtype}")
-    entry = "dg_rope_attn_split"
-    if per_sequence:
-        _per_sequence(pos, bs, entry)
-        entry += "_seq"
-    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                              v_cache.data_ptr(), out.data_ptr(), scratch.data_ptr(), scratch.numel() * 4, bs, hl,
-                                              kvl, d, max_seq, float(scale), nsplit, _dt(qkv), qkv.device.index, _stream(qkv)),
-               entry)
-    return out
+    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit))
 
 
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,

@@ -87,6 +87,12 @@ def test_equal_positions_reproduce_the_non_ragged_stack_exactly():
     assert torch.equal(a.decode(toks[:, 0], T + 2), b.decode(toks[:, 0], T + 2))  # an int: all sequences
     for la, lb in zip(a.layers, b.layers):
         assert torch.equal(la.k_cache, lb.k_cache) and torch.equal(la.v_cache, lb.v_cache)
+    # the chunk loop: positions and lengths named per sequence against the plain call, three chunks of 3 / 3 / 1 tokens from position 2
+    T = 7
+    a, b = _stack(cfg, bs), _stack(cfg, bs, ragged=False)
+    assert torch.equal(a.prefill(toks[:, :T], position=[2] * bs, lengths=[T] * bs, chunk=3), b.prefill(toks[:, :T], position=2, chunk=3))
+    for la, lb in zip(a.layers, b.layers):
+        assert torch.equal(la.k_cache, lb.k_cache) and torch.equal(la.v_cache, lb.v_cache)
 
 
 def test_inactive_sequence_writes_nothing_and_disturbs_nobody():
