@@ -84,6 +84,8 @@ SYMBOLS = {
     "tg_gemm_w4_workspace_bytes": [ctypes.POINTER(W4Gemm)],
     "tg_gemm_w4_dx": [ctypes.POINTER(W4Gemm), ctypes.c_int, _vp],
     "tg_gemm_w4_dx_workspace_bytes": [ctypes.POINTER(W4Gemm)],
+    "tg_gemm_w4_dq": [ctypes.POINTER(W4Gemm), _vp, _vp, _vp, ctypes.c_int, _vp],
+    "tg_gemm_w4_dq_workspace_bytes": [ctypes.POINTER(W4Gemm)],
     "tg_gemm_f16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
     "tg_convert_to_Bint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],
     "tg_convert_to_Aint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],
@@ -146,7 +148,7 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "tg_error_string" else
                       ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
-                                                                                          "tg_gemm_w4_dx_workspace_bytes") else ctypes.c_int)
+                                                                                          "tg_gemm_w4_dx_workspace_bytes", "tg_gemm_w4_dq_workspace_bytes") else ctypes.c_int)
     if lib.tg_abi_version() != TG_ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.tg_abi_version()} != {TG_ABI_VERSION}; rebuild")
     _lib = lib

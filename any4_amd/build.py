@@ -33,6 +33,7 @@ UNITS = [
     ("tg_gemv", "tg_gemv.hip", []),
     ("tg_tile", "tg_tile.hip", []),
     ("tg_dx", "tg_dx.hip", []),
+    ("tg_dq", "tg_dq.hip", []),
     ("tg_prefill", "tg_prefill.hip", []),
     ("tinygemm_hip", "tinygemm_hip.hip", []),
 ]

@@ -14,6 +14,7 @@
 //   tg_gemv.hip        w4_gemv_kernel            (w4_gemv.cuh)
 //   tg_tile.hip        w4_gemm_tile_kernel       (w4_gemm_tile.cuh)
 //   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
+//   tg_dq.hip          w4_gemm_dq_kernel         (w4_gemm_dq.cuh)          the gradients of scales, zeros and LUT (tg_gemm_w4_dq)
 //   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each);
@@ -174,6 +175,7 @@ int gemv(const GemmParams& p);
 int tile(GemmParams& p);     // w4_gemm_tile.cuh: many activation rows
 int tile_w8(GemmParams& p);  // ... int8 weights (tg_gemm_w8)
 int gemm_dx(GemmParams& p);  // w4_gemm_dx.cuh: dX = dY . W (tg_gemm_w4_dx)
+int gemm_dq(GemmParams& p, const char* dy, float* d_qinfo, float* d_lut);  // w4_gemm_dq.cuh: d(scales, zeros), dLUT (tg_gemm_w4_dq)
 inline int pair(GemmParams& p) { return p.dt == TG_BF16 ? pair_bf16(p) : pair_f16(p); }
 inline int pair_a(GemmParams& p) { return p.dt == TG_BF16 ? pair_a_bf16(p) : pair_a_f16(p); }
 inline int pair_b16(GemmParams& p) { return p.dt == TG_BF16 ? pair_b16_bf16(p) : pair_b16_f16(p); }

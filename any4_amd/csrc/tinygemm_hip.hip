@@ -317,12 +317,13 @@ static int take_args(const tg_w4_gemm* a, tg_w4_gemm* full) {
   return 0;
 }
 
-// ---- the preconditions of a tg_w4_gemm, for the three entry points that take one -----------------------------------------------
+// ---- the preconditions of a tg_w4_gemm, for the four entry points that take one -----------------------------------------------
 // `a` is the zero-extended struct (take_args).  Return codes AND their precedence are ABI: a struct that breaks several preconditions
 // gets the code of the first check below that fails.  Where an entry point's order differs from tg_gemm_w4's (dx says what it does not
 // do before it looks at the sizes; w8 looks at the sizes before the batch stride of the bias and the workspace), its checks sit at
-// that entry's own place.
-enum GemmEntry { ENTRY_W4, ENTRY_DX, ENTRY_W8 };
+// that entry's own place.  dq (tg_gemm_w4_dq) takes the FORWARD call's struct and checks it as dx does, except that `y` is not read
+// and mx4 -- no float parameters -- is refused.
+enum GemmEntry { ENTRY_W4, ENTRY_DX, ENTRY_W8, ENTRY_DQ };
 
 static bool misaligned(const void* p, unsigned bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) != 0; }
 
@@ -342,14 +343,15 @@ static bool too_large(const tg_w4_gemm* a, GemmEntry e) {
   const int64_t w_bytes = e == ENTRY_W8 ? a->wrows * a->k : a->wrows * a->k / 2;
   if (a->m * a->k * 2 >= lim || w_bytes >= lim || (a->k / a->group) * a->wrows * 4 >= lim) return true;
   // dx: its output is addressed that way as well, and its grid has no dimension of 16-row activation tiles
-  return e == ENTRY_DX ? a->m * a->wrows * 2 >= lim : cdiv(a->m, 16) > 65535;
+  return e == ENTRY_DX || e == ENTRY_DQ ? a->m * a->wrows * 2 >= lim : cdiv(a->m, 16) > 65535;
 }
 
 static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
-  const bool dx = e == ENTRY_DX, w8 = e == ENTRY_W8;
-  if (!a->x || !a->w || !a->qinfo || !a->y) return TG_E_NULL;
+  const bool dq = e == ENTRY_DQ, dx = e == ENTRY_DX || dq, w8 = e == ENTRY_W8;
+  if (!a->x || !a->w || !a->qinfo || (!dq && !a->y)) return TG_E_NULL;
   // w8: its own quantisation type -- no LUT, not mx4, so the LUT and mx4 checks below cannot fail for it
   if (w8 ? a->qtype != TG_Q_INT8 : (a->qtype < TG_Q_INT4 || a->qtype > TG_Q_MX4)) return TG_E_QTYPE;
+  if (dq && a->qtype == TG_Q_MX4) return TG_E_QTYPE;
   if ((a->qtype == TG_Q_ANY4_GLOBAL || a->qtype == TG_Q_ANY4_ROWWISE) && !a->lut) return TG_E_NULL;
   if (!(a->dtype == TG_BF16 || a->dtype == TG_F16)) return TG_E_DTYPE;
   if (a->qtype == TG_Q_MX4 && a->dtype != TG_BF16) return TG_E_DTYPE;  // TinyGemm_int4.cu:758,782
@@ -377,7 +379,7 @@ static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
   // x: 16-byte loads of the activation fragments (rows are k * 2 bytes with k % 32 == 0).  w: 16-byte loads of the 4-bit words, 4-byte
   // loads of the 8-bit ones.  y: dx stores 16 bytes per lane, w8 four rows (8 bytes), the 4-bit kernels' stores need the element's own
   // alignment only.  qinfo: (scale, zero) pairs.  LUT rows are read as two 16-byte vectors (w8 has none and ignores the pointer).
-  if (misaligned(a->x, 16) || misaligned(a->w, w8 ? 4 : 16) || misaligned(a->qinfo, 4) || misaligned(a->y, dx ? 16 : w8 ? 8 : 1)) return TG_E_ALIGN;
+  if (misaligned(a->x, 16) || misaligned(a->w, w8 ? 4 : 16) || misaligned(a->qinfo, 4) || misaligned(a->y, dq ? 1 : dx ? 16 : w8 ? 8 : 1)) return TG_E_ALIGN;
   if (w8 && a->batch > 1 && (a->stride_x & 15)) return TG_E_ALIGN;   // (w4 checks its batch strides further down, behind the fused stages)
   if (!w8 && a->lut && misaligned(a->lut, 16)) return TG_E_ALIGN;
   if (a->bias && misaligned(a->bias, 8)) return TG_E_ALIGN;          // (dx: no bias got this far)
@@ -400,6 +402,7 @@ static int check_gemm(const tg_w4_gemm* a, GemmEntry e) {
       return too_large(a, e) ? (int)TG_E_SIZE : 0;
     }
     case ENTRY_DX:
+    case ENTRY_DQ:
       if (bad_workspace(a)) return TG_E_ALIGN;
       return too_large(a, e) ? (int)TG_E_SIZE : 0;
     case ENTRY_W8:
@@ -565,6 +568,40 @@ int tg_gemm_w4_dx(const tg_w4_gemm* a, int device, tg_stream_t stream) { return 
 int64_t tg_gemm_w4_dx_workspace_bytes(const tg_w4_gemm* a) {
   int64_t need = 0;
   const int rc = gemm_dx_impl(a, -1, nullptr, 2, &need);
+  return rc < 0 ? rc : need;
+}
+
+// ---- gradients of scales, zeros and LUT (tg_gemm_w4_dq; the kernels and their launch path: w4_gemm_dq.cuh, tg_dq.hip) ----
+// query: report the workspace, look at nothing but the struct.  Every check runs before any HIP call.
+static int gemm_dq_impl(const tg_w4_gemm* caller, const void* dy, float* d_qinfo, float* d_lut, int device, tg_stream_t stream, bool query,
+                        int64_t* ws_need = nullptr) {
+  tg_w4_gemm full;
+  const tg_w4_gemm* a = &full;
+  int rc0 = take_args(caller, &full);
+  if (rc0 == 0) rc0 = check_gemm(a, ENTRY_DQ);
+  if (rc0 != 0) return rc0;
+  GemmParams plan = make_params(a, ENTRY_DQ, stream, 2);
+  tgx::gemm_dq(plan, nullptr, nullptr, nullptr);
+  if (ws_need) *ws_need = plan.ws_need;
+  if (query) return 0;
+  if (a->qtype == TG_Q_INT4) d_lut = nullptr;
+  if (!dy || (!d_qinfo && !d_lut)) return TG_E_NULL;
+  if (misaligned(dy, 16) || (d_qinfo && misaligned(d_qinfo, 16)) || (d_lut && misaligned(d_lut, 16))) return TG_E_ALIGN;
+  if (!a->workspace) return TG_E_NULL;
+  if (a->workspace_bytes < plan.ws_need) return TG_E_SHAPE;
+  GemmParams p = make_params(a, ENTRY_DQ, stream, 0);
+  DeviceScope ds(device);
+  if (!ds.ok) return TG_E_DEVICE;
+  return tgx::gemm_dq(p, (const char*)dy, d_qinfo, d_lut);
+}
+
+int tg_gemm_w4_dq(const tg_w4_gemm* a, const void* dy, float* d_qinfo, float* d_lut, int device, tg_stream_t stream) {
+  return gemm_dq_impl(a, dy, d_qinfo, d_lut, device, stream, false);
+}
+
+int64_t tg_gemm_w4_dq_workspace_bytes(const tg_w4_gemm* a) {
+  int64_t need = 0;
+  const int rc = gemm_dq_impl(a, nullptr, nullptr, nullptr, -1, nullptr, true, &need);
   return rc < 0 ? rc : need;
 }
 

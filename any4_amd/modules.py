@@ -40,6 +40,26 @@ class _Linear4Fn(torch.autograd.Function):
         return None, dx, db
 
 
+class _Linear4QFn(torch.autograd.Function):
+    """_Linear4Fn with the quantisation parameters as inputs of the node (any4_amd.quant_param_grad on): the same forward -- the same
+    launches and bits, the fused bias kept -- and a backward that adds the gradients of scales_and_zeros / lut through the module's dq op
+    (ops.QGRAD_OPS), cast once to the parameters' dtype.  A parameter with requires_grad False gets none."""
+
+    @staticmethod
+    def forward(ctx, mod, x2d, bias, qinfo, lut):
+        ctx.mod, ctx.has_bias, ctx.x = mod, bias is not None, x2d
+        return _Linear4Fn.forward(ctx, mod, x2d, bias)
+
+    @staticmethod
+    def backward(ctx, dy):
+        mod = ctx.mod
+        _, dx, db = _Linear4Fn.backward(ctx, dy)
+        lut = mod._luts()[0] if mod._luts() else None
+        dq, dl = _ops.w4_quant_param_grads(getattr(_T, mod._DQ_OP).default, ctx.x, dy, mod.weight, mod.group_size, mod._qinfo(), lut,
+                                           mod._DX_KERNELS[mod.kernel], ctx.needs_input_grad[3], lut is not None and ctx.needs_input_grad[4])
+        return None, dx, db, dq, dl
+
+
 class _PackedLinear(torch.nn.Module):
     """Shared machinery: parameter creation, one-off packing and the forward epilogue."""
 
@@ -168,6 +188,7 @@ class _PackedLinear(torch.nn.Module):
     # row-major 4-bit kernels with an input gradient (ops.AUTOGRAD_OPS) -> weightOnRight
     _DX_KERNELS: dict = {}
     _DX_OP = None
+    _DQ_OP = None   # ... and the op of the quantisation parameters' gradients (ops.QGRAD_OPS); None: the module has no float parameters
 
     def _input_grad(self, dy: torch.Tensor) -> torch.Tensor:
         """dX [rows][in_features] = dY . W on the packed weight (the op of ops.AUTOGRAD_OPS this module's kernel runs)."""
@@ -178,6 +199,16 @@ class _PackedLinear(torch.nn.Module):
 
     def _luts(self):
         return ()
+
+    def _wants_quant_param_grad(self) -> bool:
+        """scales_and_zeros or lut wants a gradient on a row-major kernel (the switch and grad mode: the caller's)."""
+        if self._DQ_OP is None or self.kernel not in self._DX_KERNELS or not self.weight_reshaped:
+            return False
+        if not (self._qinfo().requires_grad or any(t.requires_grad for t in self._luts())):
+            return False
+        if self.weight_format == "reference":
+            raise RuntimeError(_ops._RELAYOUT_HINT.replace("the input gradient needs", "the gradients of a 4-bit linear need"))
+        return True
 
     def forward(self, input: torch.Tensor) -> torch.Tensor:
         return self._forward(input)
@@ -195,7 +226,9 @@ class _PackedLinear(torch.nn.Module):
         d = self.__dict__
         plan = d.get("_plan")
         p = self._parameters
-        if plan is not None and p.get("bias") is None and not (input.requires_grad and torch.is_grad_enabled()):
+        # any4_amd.quant_param_grad: scales_and_zeros / lut get a gradient, so the call needs a graph even when the input wants none
+        qgrad = _ops.get_quant_param_grad() and torch.is_grad_enabled() and self._wants_quant_param_grad()
+        if plan is not None and p.get("bias") is None and not qgrad and not (input.requires_grad and torch.is_grad_enabled()):
             # (a bias assigned after the recording: the full path, which offers it to the kernel; an input that wants a gradient: below)
             # the validated launch of this (module, activation shape) re-issued with new pointers (ops.LaunchPlan.try_run): the eager hot path
             y = plan.try_run(input, p["weight"], p.get("scales_and_zeros") if "scales_and_zeros" in p else p.get("exponents"), p.get("lut"),
@@ -206,9 +239,12 @@ class _PackedLinear(torch.nn.Module):
             self._auto_relayout()    # (a checkpoint in the reference's Aint4 words that was loaded on the CPU: repacked once, see above)
         lead = input.shape[:-1]
         if (torch.is_grad_enabled() and self.kernel in self._DX_KERNELS and self.weight_reshaped and
-                (input.requires_grad or (self.bias is not None and self.bias.requires_grad))):
+                (input.requires_grad or (self.bias is not None and self.bias.requires_grad) or qgrad)):
             # training through the quantised layer: no recorded plan (its output has no graph); the same launches, with a grad_fn
-            y = _Linear4Fn.apply(self, input.reshape(-1, input.shape[-1]), self.bias)
+            if qgrad:
+                y = _Linear4QFn.apply(self, input.reshape(-1, input.shape[-1]), self.bias, self._qinfo(), *(self._luts() or (None,)))
+            else:
+                y = _Linear4Fn.apply(self, input.reshape(-1, input.shape[-1]), self.bias)
             return y.view(*lead, y.shape[-1])
         if input.is_cuda and self.bias is None and self.weight_reshaped and d.get("_no_plan") != (input.shape, _ops.get_numerics()):
             # a packed weight only: the plan points at the parameters themselves
@@ -249,6 +285,7 @@ class Int4Linear(_PackedLinear):
 
     _DX_KERNELS = {"linear_y_f16RM_x_f16RM_W_int4TC": True, "linear_y_f16RM_W_int4TC_x_f16RM": False}
     _DX_OP = "tinygemm_dx_f16RM_dy_f16RM_w_int4TC"
+    _DQ_OP = "tinygemm_dq_f16RM_x_f16RM_w_int4TC"
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
                  group_size: int = 128, kernel: str = "linear_y_f16RM_W_int4TC_x_f16RM", w_inner_k: int = 4) -> None:
@@ -292,6 +329,7 @@ class Any4Linear(_PackedLinear):
 
     _DX_KERNELS = {"linear_y_f16RM_x_f16RM_W_any4TC": True, "linear_y_f16RM_W_any4TC_x_f16RM": False}
     _DX_OP = "tinygemm_dx_f16RM_dy_f16RM_w_any4TC"
+    _DQ_OP = "tinygemm_dq_f16RM_x_f16RM_w_any4TC"
 
     def _luts(self):
         return (self.lut,)

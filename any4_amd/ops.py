@@ -50,6 +50,10 @@ SCHEMAS = {
     "tinygemm_dx_f16RM_dy_f16RM_w_int4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, bool weightOnRight) -> Tensor",
     "tinygemm_dx_f16RM_dy_f16RM_w_any4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, Tensor int4DequantValues, bool weightOnRight) -> Tensor",
     "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC": "(Tensor dY, Tensor W, int qGroupSize, Tensor mx4Exponents, bool weightOnRight) -> Tensor",
+    # the gradients of the quantisation parameters (tg_gemm_w4_dq): X and dY of the forward call, f32 outputs shaped like qScaleAndZeros
+    # (scale, zero) and int4DequantValues
+    "tinygemm_dq_f16RM_x_f16RM_w_int4TC": "(Tensor X, Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, bool weightOnRight) -> Tensor",
+    "tinygemm_dq_f16RM_x_f16RM_w_any4TC": "(Tensor X, Tensor dY, Tensor W, int qGroupSize, Tensor qScaleAndZeros, Tensor int4DequantValues, bool weightOnRight) -> (Tensor, Tensor)",
 }
 
 _F16_TYPES = (torch.bfloat16, torch.float16)
@@ -112,6 +116,38 @@ def set_numerics(name: str) -> None:
 def numerics(name: str):
     """Thread-local override: `with any4_amd.numerics("reference"): ...`"""
     return _numerics.override(name)
+
+
+# ---------------------------------------------------------------------------------------------
+# gradients for scales_and_zeros / lut (opt-in)
+# ---------------------------------------------------------------------------------------------
+_quant_param_grad = False
+
+
+def get_quant_param_grad() -> bool:
+    """Whether backward through a row-major int4 / any4 GEMM also fills the gradients of scales_and_zeros and lut (tg_gemm_w4_dq).  Off by
+    default: they are Parameters that require grad by default, and the kernel costs about a weight-gradient GEMM per layer."""
+    return getattr(_tls, "qgrad", _quant_param_grad)
+
+
+def set_quant_param_grad(on: bool) -> None:
+    """Process-wide default."""
+    global _quant_param_grad
+    _quant_param_grad = bool(on)
+
+
+@contextlib.contextmanager
+def quant_param_grad(enabled: bool = True):
+    """Thread-local override: `with any4_amd.quant_param_grad(): loss.backward()`.  The forward captures the switch."""
+    prev = getattr(_tls, "qgrad", None)
+    _tls.qgrad = bool(enabled)
+    try:
+        yield
+    finally:
+        if prev is None:
+            del _tls.qgrad
+        else:
+            _tls.qgrad = prev
 
 
 # ---------------------------------------------------------------------------------------------
@@ -847,13 +883,77 @@ def tinygemm_dx_f16RM_dy_f16RM_w_mx4TC(dY, W, qGroupSize, mx4Exponents, weightOn
     return _dx_rm(dY, W, qGroupSize, mx4Exponents, None, TG_Q_MX4, weightOnRight, "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC")
 
 
-# forward op -> its dx op.  Only the activations get a gradient: the packed weight, scales_and_zeros, LUT and exponents are constants
-# of the graph (None; learning them -- the reference's learn_anyq -- is not covered).
+def _dq_rm(X, dY, w, q_group, qinfo, lut, qtype, weight_on_right, opname):
+    """(d_qinfo, d_lut) in f32, shaped like qinfo / lut: the gradients of scales, zeros and LUT of _w4_rm's y = X . W^T for the output
+    gradient dY (straight through the weights' 16-bit rounding; include/tinygemm_hip.h, tg_gemm_w4_dq).  d_lut is None for int4."""
+    _check(X.device == w.device and dY.device == w.device, "X, dY and W must be on the same device")
+    _check(X.dim() == 2 and dY.dim() == 2, "X and dY must be 2-D matrices [activation rows][k] / [activation rows][weight rows]")
+    _check(X.dtype == dY.dtype, "X and dY must share a dtype")
+    m, k = X.shape
+    inner, wrows, w_format, qtype, qinfo, lut = _w4_operands(X, k, w, q_group, qinfo, lut, qtype, weight_on_right, aint4=False)
+    _check(dY.size(0) == m and dY.size(1) == wrows, "dY must be [activation rows][tile-padded weight rows]")
+    d_qinfo = torch.empty(qinfo.shape, dtype=torch.float32, device=X.device)
+    d_lut = None if lut is None else torch.empty(lut.shape, dtype=torch.float32, device=X.device)
+    if m == 0:
+        d_qinfo.zero_()
+        return d_qinfo, (None if d_lut is None else d_lut.zero_())
+    x, dy = X.contiguous(), dY.contiguous()   # (autograd hands in views and expanded tensors)
+    if x.data_ptr() % 16:
+        x = x.clone()
+    if dy.data_ptr() % 16:
+        dy = dy.clone()
+    args = W4Gemm(x=x.data_ptr(), w=w.data_ptr(), qinfo=qinfo.data_ptr(), lut=(lut.data_ptr() if lut is not None else None), y=None,
+                  m=m, wrows=wrows, k=k, group=q_group, qtype=qtype, dtype=_dt(x), w_on_right=1 if weight_on_right else 0,
+                  inner_k_tiles=inner, batch=1, w_format=w_format)
+    key = ("w4_dq", wrows, k, q_group, qtype, args.dtype, args.w_on_right, inner, args.w_format)   # (the bytes do not depend on m)
+    ws_bytes = _WS_BYTES.get(key)
+    if ws_bytes is None:
+        ws_bytes = _L.tg_gemm_w4_dq_workspace_bytes(ctypes.byref(args))
+        if ws_bytes < 0:
+            _lib.check(ws_bytes, opname)
+        if len(_WS_BYTES) < 4096:
+            _WS_BYTES[key] = ws_bytes
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=X.device)
+    args.workspace, args.workspace_bytes = ws.data_ptr(), ws_bytes
+    _lib.check(_L.tg_gemm_w4_dq(ctypes.byref(args), dy.data_ptr(), d_qinfo.data_ptr(), None if d_lut is None else d_lut.data_ptr(),
+                                _dev(x), _stream(x)), opname)
+    return d_qinfo, d_lut
+
+
+def tinygemm_dq_f16RM_x_f16RM_w_int4TC(X, dY, W, qGroupSize, qScaleAndZeros, weightOnRight):
+    return _dq_rm(X, dY, W, qGroupSize, qScaleAndZeros, None, TG_Q_INT4, weightOnRight, "tinygemm_dq_f16RM_x_f16RM_w_int4TC")[0]
+
+
+def tinygemm_dq_f16RM_x_f16RM_w_any4TC(X, dY, W, qGroupSize, qScaleAndZeros, int4DequantValues, weightOnRight):
+    return _dq_rm(X, dY, W, qGroupSize, qScaleAndZeros, int4DequantValues, TG_Q_ANY4_ROWWISE, weightOnRight, "tinygemm_dq_f16RM_x_f16RM_w_any4TC")
+
+
+# forward op -> its dx op.  The activations always get a gradient; the packed weight and the mx4 exponents are constants of the graph.
+# scales_and_zeros and the LUT get theirs -- the reference's learn_anyq trains them -- through QGRAD_OPS when the forward ran with
+# quant_param_grad on; otherwise (the default) they get None.
 AUTOGRAD_OPS = {
     "tinygemm_y_f16RM_x_f16RM_w_int4TC": "tinygemm_dx_f16RM_dy_f16RM_w_int4TC",
     "tinygemm_y_f16RM_x_f16RM_w_any4TC": "tinygemm_dx_f16RM_dy_f16RM_w_any4TC",
     "tinygemm_y_f16RM_x_f16RM_w_mx4TC": "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC",
 }
+
+
+# forward op -> the op of its quantisation parameters' gradients (no Autograd key of their own: they are leaves of a backward)
+QGRAD_OPS = {
+    "tinygemm_y_f16RM_x_f16RM_w_int4TC": "tinygemm_dq_f16RM_x_f16RM_w_int4TC",
+    "tinygemm_y_f16RM_x_f16RM_w_any4TC": "tinygemm_dq_f16RM_x_f16RM_w_any4TC",
+}
+
+
+def w4_quant_param_grads(dq_op, x, dY, w, q_group, qinfo, lut, weight_on_right, want_qinfo=True, want_lut=True):
+    """(d_qinfo, d_lut) of one row-major int4 / any4 GEMM call in the DTYPE of qinfo / lut (the f32 results cast once); None where not wanted."""
+    if not (want_qinfo or (want_lut and lut is not None)):
+        return None, None
+    if lut is None:
+        dq, dl = dq_op(x, dY, w, q_group, qinfo, weight_on_right), None
+    else:
+        dq, dl = dq_op(x, dY, w, q_group, qinfo, lut, weight_on_right)
+    return (dq.to(qinfo.dtype) if want_qinfo else None), (dl.to(lut.dtype) if want_lut and dl is not None else None)
 
 
 def w4_input_grad(dx_op, dY, args):
@@ -875,13 +975,25 @@ class _W4GemmFn(torch.autograd.Function):
     @staticmethod
     def setup_context(ctx, inputs, output):
         ctx.dx_op, ctx.args = inputs[1], inputs[2:]
+        # the switch as the forward saw it; the dq op of this forward op (mx4 has none)
+        name = QGRAD_OPS.get(inputs[0]._schema.name.split("::")[-1]) if get_quant_param_grad() else None
+        ctx.dq_op = None if name is None else getattr(torch.ops.tinygemm, name).default
 
     @staticmethod
     def backward(ctx, dy):
         args = ctx.args
         on_right = args[-1]
         dx = w4_input_grad(ctx.dx_op, dy, args) if ctx.needs_input_grad[2 if on_right else 3] else None
-        return (None, None) + ((dx, None) if on_right else (None, dx)) + (None,) * (len(args) - 2)
+        rest = [None] * (len(args) - 2)   # qGroupSize, qinfo[, lut], weightOnRight
+        if ctx.dq_op is not None:
+            lut = args[4] if len(args) == 6 else None
+            x, w = (args[0], args[1]) if on_right else (args[1], args[0])
+            dq, dl = w4_quant_param_grads(ctx.dq_op, x, dy, w, args[2], args[3], lut, on_right, ctx.needs_input_grad[5],
+                                          lut is not None and ctx.needs_input_grad[6])
+            rest[1] = dq
+            if lut is not None:
+                rest[2] = dl
+        return (None, None) + ((dx, None) if on_right else (None, dx)) + tuple(rest)
 
 
 _grad_on = torch.is_grad_enabled
@@ -1070,6 +1182,8 @@ _IMPLS = {
     "tinygemm_dx_f16RM_dy_f16RM_w_int4TC": tinygemm_dx_f16RM_dy_f16RM_w_int4TC,
     "tinygemm_dx_f16RM_dy_f16RM_w_any4TC": tinygemm_dx_f16RM_dy_f16RM_w_any4TC,
     "tinygemm_dx_f16RM_dy_f16RM_w_mx4TC": tinygemm_dx_f16RM_dy_f16RM_w_mx4TC,
+    "tinygemm_dq_f16RM_x_f16RM_w_int4TC": tinygemm_dq_f16RM_x_f16RM_w_int4TC,
+    "tinygemm_dq_f16RM_x_f16RM_w_any4TC": tinygemm_dq_f16RM_x_f16RM_w_any4TC,
 }
 
 _library = None

@@ -335,6 +335,50 @@ def anyq_layer(module: torch.nn.Module, name: str = "", n_bit: int = 4, group_si
     return q
 
 
+def tune_quant_params(module: torch.nn.Module, X: torch.Tensor, Y: torch.Tensor, steps: int = 100, lr: float = 1e-3,
+                      params=("lut", "scales_and_zeros")):
+    """The reference's learn_anyq (quantize.py:648-806) with objective `Y_mse`, run on the real kernels: Adam on the parameters named in
+    `params` of a packed Int4Linear / Any4Linear / NF4Linear against loss = mean((module(X) - Y)^2), the codes frozen.  The optimiser
+    works on f32 masters; each step rounds them into the module's 16-bit parameters, runs the module's forward and takes the f32
+    gradients of the dq op (torch.ops.tinygemm.tinygemm_dq_*) for dLoss/dY.  Returns (loss_before, loss_after) of the module as it was
+    handed in / as it is left."""
+    from . import ops as _ops
+
+    if getattr(module, "_DQ_OP", None) is None or module.kernel not in module._DX_KERNELS or not module.weight_reshaped:
+        raise ValueError("tune_quant_params needs a packed int4 / any4 module on a row-major kernel")
+    if module.weight_format == "reference":
+        raise RuntimeError(_ops._RELAYOUT_HINT)
+    names = tuple(params)
+    if not names or any(n not in ("lut", "scales_and_zeros") or getattr(module, n, None) is None for n in names):
+        raise ValueError(f"params must name parameters of the module out of ('lut', 'scales_and_zeros'), got {params!r}")
+    dq_op = getattr(torch.ops.tinygemm, module._DQ_OP).default
+    on_right = module._DX_KERNELS[module.kernel]
+    x2d, y2d = X.reshape(-1, X.shape[-1]), Y.reshape(-1, Y.shape[-1])
+    masters = {n: getattr(module, n).detach().float().clone().requires_grad_(True) for n in names}
+    opt = torch.optim.Adam(list(masters.values()), lr=lr)
+
+    def loss_and_dy():
+        with torch.no_grad():
+            diff = module(x2d).float() - y2d.float()
+            return float(diff.pow(2).mean()), (diff * (2.0 / diff.numel())).to(x2d.dtype)
+
+    loss_before, dy = loss_and_dy()
+    loss_after = loss_before
+    for _ in range(steps):
+        lut = module.lut if hasattr(module, "lut") else None
+        extra = () if lut is None else (lut,)
+        out = dq_op(x2d, dy, module.weight, module.group_size, module.scales_and_zeros, *extra, on_right)
+        grads = {"scales_and_zeros": out if lut is None else out[0], "lut": None if lut is None else out[1]}
+        for n in names:
+            masters[n].grad = grads[n]
+        opt.step()
+        with torch.no_grad():
+            for n in names:
+                getattr(module, n).copy_(masters[n])   # (one rounding to the parameter's 16-bit type; in place: a recorded plan stays valid)
+        loss_after, dy = loss_and_dy()
+    return loss_before, loss_after
+
+
 def intq_layer(module: torch.nn.Module, name: str = "", n_bit: int = 4, group_size: int = 128, pseudo: Optional[bool] = None,
                **kwargs) -> torch.nn.Module:
     """nn.Linear -> Int4Linear (uniform int4 on tinygemm's grid) or, pseudo=True, reconstructed weights in place."""

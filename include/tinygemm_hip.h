@@ -276,6 +276,22 @@ TG_API int tg_gemm_w4_dx(const tg_w4_gemm* args, int device, tg_stream_t stream)
 /* Bytes of workspace with which tg_gemm_w4_dx splits (0: it does not; negative: the TG_E_* code tg_gemm_w4_dx would return).  No GPU. */
 TG_API int64_t tg_gemm_w4_dx_workspace_bytes(const tg_w4_gemm* args);
 
+/* The gradients of the float quantisation parameters of the row-major 4-bit GEMM (int4 / any4), straight through the 16-bit rounding of
+ *   w[r][j] = RNE16(fma(lut[r][c(r,j)], s[g(j)][r], z[g(j)][r])).  With G[r][j] = sum_a dY[a][r] * x[a][j] (never written) and
+ *   H[g][r][c] = sum of G[r][j] over the columns j of group g whose code is c:
+ *     d_qinfo[g][r] = (ds, dz) = (sum_c lut[r][c] * H[g][r][c], sum_c H[g][r][c])        f32 [k / group][wrows][2]
+ *     d_lut[r][c]   = sum_g s[g][r] * H[g][r][c]   (global LUT: also summed over r)       f32 [wrows][16] / [16]
+ * `args` describes the FORWARD call (x [m][k], w, qinfo, lut, m, wrows, k, group, qtype, dtype, w_on_right, inner_k_tiles, w_format,
+ * workspace); y is ignored.  dy: [m][wrows] 16-bit, 16-byte aligned.  d_qinfo or d_lut may be NULL to skip that output (both, or the only
+ * one that applies: TG_E_NULL); d_lut is ignored for int4.  Products are summed in f32 in a fixed order, no atomics: the same bits call
+ * to call.  The workspace is REQUIRED: with none the call returns TG_E_NULL, with less than tg_gemm_w4_dq_workspace_bytes TG_E_SHAPE,
+ * before any HIP call.  Refusals as tg_gemm_w4_dx: mx4 (no float parameters) TG_E_QTYPE; the reference's Aint4 words and fragment-order
+ * layouts TG_E_LAYOUT; batch > 1 TG_E_SHAPE; bias / norm_weight / epilogue TG_E_FUSION.  Added without an ABI version bump: callers
+ * probe for the symbol. */
+TG_API int tg_gemm_w4_dq(const tg_w4_gemm* args, const void* dy, float* d_qinfo, float* d_lut, int device, tg_stream_t stream);
+/* Bytes of workspace tg_gemm_w4_dq needs (negative: the TG_E_* code it would return for `args`).  No GPU. */
+TG_API int64_t tg_gemm_w4_dq_workspace_bytes(const tg_w4_gemm* args);
+
 /* out[wrows][k] (16-bit, row-major) = the dequantised weights of a Bint4-packed tensor (also the native weights-on-the-left format,
  * which holds the same words): w = RNE16(fma(lut[row][code], scale[g][row], zero[g][row])), the reference's per-element formula
  * (MatrixLayoutB.cuh:1042-1046; int4: code - 8) -- what quantize.py:612-637 (anyq_dequantize_tensor) computes op by op on unpacked codes.  For MANY
