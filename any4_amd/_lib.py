@@ -124,6 +124,14 @@ SYMBOLS = {
                                ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
     "dg_prefill_attn_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
                             ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
+    # ... on an mx8 cache: their namesakes' lists with k_exp, v_exp behind v_cache
+    "dg_rope_attn_split_mx8": [_vp] * 10 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
+                                            ctypes.c_int, ctypes.c_int, _vp],
+    "dg_rope_attn_split_mx8_seq": [_vp] * 10 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
+                                                ctypes.c_int, ctypes.c_int, _vp],
+    "dg_prefill_attn_mx8": [_vp] * 9 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
+    "dg_prefill_attn_mx8_seq": [_vp] * 11 + [_i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
+                                             ctypes.c_int, _vp],
 }
 
 _lib = None

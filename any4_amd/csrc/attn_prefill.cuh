@@ -30,6 +30,7 @@
 // with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
 #pragma once
 #include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
+#include "kv8.cuh"         // the mx8 cache format (KV8 flavours)
 
 struct PrefillParams {
   const uint16_t* qkv;
@@ -80,8 +81,8 @@ __device__ __forceinline__ bool pf_seq(const PrefillParams& P, const PrefillSeq&
 }
 
 // ---- rope + cache append: block = one token of one sequence; a thread walks (kv head, rotation pair) items, k first, then v ----
-template <typename DT, bool SEQ = false>
-__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q) {
+template <typename DT, bool SEQ = false, bool KV8 = false>
+__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X) {
   const int t = blockIdx.x, b = blockIdx.y, d2 = d >> 1;
   int cb = b;  // the sequence's cache slot
   int64_t pos;
@@ -96,6 +97,36 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
   if (pos < 0 || pos >= P.max_seq) return;  // never index the cache (or the tables) outside [0, max_seq)
   const uint16_t* row = P.qkv + ((int64_t)b * P.T + t) * (int64_t)(P.hl + 2 * P.kvl) * d;
   const int per = P.kvl * d2;
+  if constexpr (KV8) {
+    // d / 2 is a multiple of 32 and 2 * per of 64: the waves of the loop are whole, and 32 aligned lanes hold the elements j of ONE 32-element
+    // block and their rotation partners j + d / 2 of another -- a block maximum is a reduction over those lanes
+    for (int i = threadIdx.x; i < 2 * per; i += 256) {
+      const bool isv = i >= per;
+      const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
+      const uint16_t* src = row + (int64_t)(P.hl + (isv ? P.kvl : 0) + kv) * d;
+      float x1 = DT::to_f32(src[j]), x2 = DT::to_f32(src[j + d2]);
+      if (!isv) {
+        const float c1 = P.cos[pos * d + j], c2 = P.cos[pos * d + j + d2], s1 = P.sin[pos * d + j], s2 = P.sin[pos * d + j + d2];
+        const float o1 = round16<DT>(rope_mul_add(x1, c1, -x2, s1)), o2 = round16<DT>(rope_mul_add(x2, c2, x1, s2));
+        x1 = o1;
+        x2 = o2;
+      }
+      uint32_t c1, e1, c2, e2;
+      mx8_encode_lane(x1, c1, e1);
+      mx8_encode_lane(x2, c2, e2);
+      const int64_t r = ((int64_t)cb * P.kvl + kv) * P.max_seq + pos;
+      uint8_t* dst = reinterpret_cast<uint8_t*>(isv ? P.v_cache : P.k_cache) + r * d;
+      dst[j] = (uint8_t)c1;
+      dst[j + d2] = (uint8_t)c2;
+      if ((j & 31) == 0) {
+        uint8_t* ed = (isv ? X.v_exp : X.k_exp) + r * (d >> 5);
+        ed[j >> 5] = (uint8_t)e1;
+        ed[(j + d2) >> 5] = (uint8_t)e2;
+      }
+    }
+    return;
+  }
+  // (16-bit caches from here on)
   for (int i = threadIdx.x; i < 2 * per; i += 256) {
     const bool isv = i >= per;
     const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
@@ -123,8 +154,8 @@ __device__ __forceinline__ int pf_swz_v(int d, int chunk) { return chunk ^ (((d 
 
 constexpr int PF_NU = 2;  // 16-row units per wave: 2 x (O 4 D/16 + q D/8 + S 16) registers leave room for two workgroups per CU; 4 spill at D = 128
 
-template <typename DT, int D, int RG, bool SEQ = false>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q) {
+template <typename DT, int D, int RG, bool SEQ = false, bool KV8 = false>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X) {
   constexpr int KD = D / 32;        // k-steps of the score product
   constexpr int DB = D / 16;        // 16-column blocks of the output
   constexpr int NU = PF_NU;         // 16-row units per wave
@@ -207,30 +238,70 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
 
   const char* Kg = reinterpret_cast<const char*>(P.k_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
   const char* Vg = reinterpret_cast<const char*>(P.v_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
+  const int64_t head0 = ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq;  // (KV8) first cache row of this (slot, kv head): D bytes of codes per row
 
   // ---- staging: K as 16-byte chunks (row, chunk); V as four consecutive positions 4 sg ... 4 sg + 3 of one 8-column chunk c
+  // (KV8: a chunk is 8 bytes of codes in the first two dwords of its register slot, and its block's exponent byte is byte i of kexp / vexp)
   u32x4 kreg[NCK], vreg[4];
+  u32x2 kreg8[NCK], vreg8[4];
+  uint32_t kexp = 0u, vexp = 0u;
   const int vc = tid % CPR, vsg = tid / CPR;  // (D = 64: the threads with vsg >= 16 stage no V)
   auto stage_load = [&](int j) {
     const int s0 = 64 * j;
+    if constexpr (KV8) {
+      const char* Kg8 = reinterpret_cast<const char*>(P.k_cache) + head0 * D;
+      const char* Vg8 = reinterpret_cast<const char*>(P.v_cache) + head0 * D;
+      const uint8_t* Ke = X.k_exp + head0 * (D / 32);
+      const uint8_t* Ve = X.v_exp + head0 * (D / 32);
+      kexp = vexp = 0u;  // (rows beyond p_hi: codes 0 with any exponent below 255 are the zero bits of the 16-bit flavour)
 #pragma unroll
-    for (int i = 0; i < NCK; ++i) {
-      const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
-      kreg[i] = u32x4{0u, 0u, 0u, 0u};
-      if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(Kg + (int64_t)(s0 + row) * (D * 2) + ch * 16);
-    }
-    if (vsg < 16) {
+      for (int i = 0; i < NCK; ++i) {
+        const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
+        kreg8[i] = u32x2{0u, 0u};
+        if (s0 + row <= p_hi) {
+          kreg8[i] = *reinterpret_cast<const u32x2*>(Kg8 + (int64_t)(s0 + row) * D + ch * 8);
+          kexp |= (uint32_t)Ke[(int64_t)(s0 + row) * (D / 32) + (ch >> 2)] << (8 * i);
+        }
+      }
+      if (vsg < 16) {
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int row = 4 * vsg + i;
-        vreg[i] = u32x4{0u, 0u, 0u, 0u};
-        if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(Vg + (int64_t)(s0 + row) * (D * 2) + vc * 16);
+        for (int i = 0; i < 4; ++i) {
+          const int row = 4 * vsg + i;
+          vreg8[i] = u32x2{0u, 0u};
+          if (s0 + row <= p_hi) {
+            vreg8[i] = *reinterpret_cast<const u32x2*>(Vg8 + (int64_t)(s0 + row) * D + vc * 8);
+            vexp |= (uint32_t)Ve[(int64_t)(s0 + row) * (D / 32) + (vc >> 2)] << (8 * i);
+          }
+        }
+      }
+    } else {
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) {
+        const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
+        kreg[i] = u32x4{0u, 0u, 0u, 0u};
+        if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(Kg + (int64_t)(s0 + row) * (D * 2) + ch * 16);
+      }
+      if (vsg < 16) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int row = 4 * vsg + i;
+          vreg[i] = u32x4{0u, 0u, 0u, 0u};
+          if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(Vg + (int64_t)(s0 + row) * (D * 2) + vc * 16);
+        }
       }
     }
   };
   auto stage_write = [&](int buf) {
     char* kb = smem + buf * BUF;
     char* vb = kb + KBYTES;
+    if constexpr (KV8) {  // the chunks become what the 16-bit flavour staged
+#pragma unroll
+      for (int i = 0; i < NCK; ++i) kreg[i] = mx8_to16<DT>(kreg8[i], (kexp >> (8 * i)) & 255u);
+      if (vsg < 16) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) vreg[i] = mx8_to16<DT>(vreg8[i], (vexp >> (8 * i)) & 255u);
+      }
+    }
 #pragma unroll
     for (int i = 0; i < NCK; ++i) {
       const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;

@@ -8,6 +8,7 @@
 #include "stage_math.cuh"
 
 namespace {
+#include "kv8.cuh"
 
 // all threads of a 256-thread block get the reduction; `scratch` holds >= 4 floats and is reusable afterwards
 template <bool MAX>
@@ -115,6 +116,81 @@ __device__ __forceinline__ void pv_accumulate(const u32x4* __restrict__ V, const
           for (int e = 0; e < 8; ++e) vf[e] = vnew[vc * 8 + e];
         } else {
           unpack8<DT>(vv[u], vf);
+        }
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
+      }
+    }
+  }
+}
+
+// ---- mx8 cache rows (any4_amd/kvcache.py is the definition): E4M3 codes [d] and one E8M0 exponent byte per 32 elements ----
+// The exponent bytes of one row, d / 32 = nb of them (1, 2, 4 or 8; the row's first byte at er, 16-byte aligned tensor): at d = 128 one dword.
+__device__ __forceinline__ u32x2 mx8_row_exps(const uint8_t* __restrict__ er, int nb) {
+  if (nb == 4) return u32x2{*reinterpret_cast<const uint32_t*>(er), 0u};
+  if (nb == 8) return *reinterpret_cast<const u32x2*>(er);
+  if (nb == 2) return u32x2{*reinterpret_cast<const uint16_t*>(er), 0u};
+  return u32x2{*er, 0u};
+}
+// exponent byte of the 8-element piece v of a row
+__device__ __forceinline__ uint32_t mx8_piece_exp(const u32x2& ew, int v) { return (ew[v >> 4] >> (((v >> 2) & 3) * 8)) & 255u; }
+
+// q . K[s] of an mx8 row (d / 16 pieces of 16 codes: a thread walks its own row, so a 16-byte load halves the cache lines a wave-load
+// touches against 8-byte ones), up to eight loads at a time, converted to the 16-bit type; then qk_dot's arithmetic in qk_dot's order
+template <typename DT>
+__device__ __forceinline__ float qk_dot8(const float* qf, const u32x4* __restrict__ Krow, const uint8_t* __restrict__ erow, int d8) {
+  const u32x2 ew = mx8_row_exps(erow, d8 >> 2);
+  const int d16 = d8 >> 1;
+  float acc = 0.f;
+  for (int v0 = 0; v0 < d16; v0 += 8) {
+    u32x4 kk[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (v0 + u < d16) kk[u] = Krow[v0 + u];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      if (v0 + u < d16) {
+        const uint32_t E = mx8_piece_exp(ew, 2 * (v0 + u));  // (both halves of a 16-element piece lie in one 32-element block)
+        float kf[8];
+        unpack8<DT>(mx8_to16<DT>(u32x2{kk[u][0], kk[u][1]}, E), kf);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = fmaf(qf[(v0 + u) * 16 + e], kf[e], acc);
+        unpack8<DT>(mx8_to16<DT>(u32x2{kk[u][2], kk[u][3]}, E), kf);
+#pragma unroll
+        for (int e = 0; e < 8; ++e) acc = fmaf(qf[(v0 + u) * 16 + 8 + e], kf[e], acc);
+      }
+    }
+  }
+  return acc;
+}
+
+// pv_accumulate over mx8 rows (V: codes, Vexp: exponent bytes, both at the chunk's first row): the same positions in the same order
+template <typename DT>
+__device__ __forceinline__ void pv_accumulate8(const u32x2* __restrict__ V, const uint8_t* __restrict__ Vexp, const float* vnew, const float* sc,
+                                               float inv, int S, int d8, int vc, int part, int nparts, float (&acc)[8]) {
+  const int nb = d8 >> 2;
+  for (int s0 = part; s0 < S; s0 += nparts * 8) {
+    u32x2 vv[8];
+    uint32_t ee[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int s = s0 + u * nparts;
+      if (s < S && !(vnew && s == S - 1)) {
+        vv[u] = V[(int64_t)s * d8 + vc];
+        ee[u] = Vexp[(int64_t)s * nb + (vc >> 2)];
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int s = s0 + u * nparts;
+      if (s < S) {
+        const float p = round16<DT>(sc[s] * inv);
+        float vf[8];
+        if (vnew && s == S - 1) {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) vf[e] = vnew[vc * 8 + e];
+        } else {
+          unpack8<DT>(mx8_to16<DT>(vv[u], ee[u]), vf);
         }
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(p, vf[e], acc[e]);
@@ -326,12 +402,15 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
 // One block per head leaves 7/8 of the CUs idle and walks a long context at ~40 ns per position; this one fills the GPU.
 // Softmax statistics are combined flash-decoding style, so probabilities are normalised AFTER the value contraction
 // (the single-block kernels round normalised probabilities to 16 bit first): same result within 16-bit rounding.
-template <typename DT, bool SEQ = false>
+// KV8 (the dg_rope_attn_split_mx8 entry points): the caches are mx8 -- `k_cache` / `v_cache` hold one byte per element, X the exponent
+// bytes.  The owner block encodes the roped k row and the raw v row per 32-element block, and the new token enters the scores and the
+// value sum as its DECODED row (what every later step will read); cached rows are converted on load, everything behind is shared.
+template <typename DT, bool SEQ = false, bool KV8 = false>
 __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                               const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                               uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                               uint16_t* __restrict__ out, float* part, int* counters, int hl,
-                                                              int kvl, int d, int64_t max_seq, float scale) {
+                                                              int kvl, int d, int64_t max_seq, float scale, Kv8Arg<KV8> X) {
   extern __shared__ float sm[];  // [256 q] [256 k_new] [256 v_new] [4 scratch] [scores / partial outputs]
   float* qf = sm;
   float* kn = sm + 256;
@@ -361,21 +440,46 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
     dstf[j + d2] = DT::to_f32(o2);
     const uint16_t vraw = row[(hl + kvl + kv) * d + t];
     vn[t] = DT::to_f32(vraw);
-    if (owner) {
-      uint16_t* kdst = k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
-      uint16_t* vdst = v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
-      if (isk) { kdst[j] = o1; kdst[j + d2] = o2; }
-      vdst[t] = vraw;
+    if constexpr (!KV8) {
+      if (owner) {
+        uint16_t* kdst = k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
+        uint16_t* vdst = v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
+        if (isk) { kdst[j] = o1; kdst[j + d2] = o2; }
+        vdst[t] = vraw;
+      }
     }
   }
   __syncthreads();
-  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + ((int64_t)b * kvl + kv) * max_seq * d);
-  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + ((int64_t)b * kvl + kv) * max_seq * d);
+  const int64_t head0 = ((int64_t)b * kvl + kv) * max_seq;  // first cache row of this (sequence, kv head)
+  if constexpr (KV8) {
+    if (owner) {  // (block-uniform) thread t encodes element t of both rows; a 32-element block is 32 aligned lanes
+      const bool in = t < d;
+      uint32_t kc, ke, vcode, ve;
+      const float kdec = mx8_encode_lane<DT>(in ? kn[t] : 0.f, kc, ke);
+      const float vdec = mx8_encode_lane<DT>(in ? vn[t] : 0.f, vcode, ve);
+      if (in) {
+        const int64_t r = head0 + pos;
+        reinterpret_cast<uint8_t*>(k_cache)[r * d + t] = (uint8_t)kc;
+        reinterpret_cast<uint8_t*>(v_cache)[r * d + t] = (uint8_t)vcode;
+        if ((t & 31) == 0) {
+          X.k_exp[r * (d >> 5) + (t >> 5)] = (uint8_t)ke;
+          X.v_exp[r * (d >> 5) + (t >> 5)] = (uint8_t)ve;
+        }
+        kn[t] = kdec;
+        vn[t] = vdec;
+      }
+    }
+    __syncthreads();
+  }
+  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + head0 * d);
+  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + head0 * d);
   float mx = -INFINITY;
   for (int s = c0 + t; s < c1; s += 256) {
     float acc = 0.f;
     if (s == S - 1) {
       for (int e = 0; e < d; ++e) acc = fmaf(qf[e], kn[e], acc);
+    } else if constexpr (KV8) {
+      acc = qk_dot8<DT>(qf, reinterpret_cast<const u32x4*>(reinterpret_cast<const uint8_t*>(k_cache) + (head0 + s) * d), X.k_exp + (head0 + s) * (d >> 5), d8);
     } else {
       acc = qk_dot<DT>(qf, K + (int64_t)s * d8, d8);
     }
@@ -395,7 +499,11 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
   const int vc = t % d8, prt = t / d8, nparts = 256 / d8;
   float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   // positions are chunk-relative inside pv_accumulate: shift the row pointer, the new token is the chunk's last row
-  pv_accumulate<DT>(V + (int64_t)c0 * d8, owner ? vn : nullptr, sc, 1.0f, c1 > c0 ? c1 - c0 : 0, d8, vc, prt, nparts, acc);
+  if constexpr (KV8)
+    pv_accumulate8<DT>(reinterpret_cast<const u32x2*>(reinterpret_cast<const uint8_t*>(v_cache) + (head0 + c0) * d), X.v_exp + (head0 + c0) * (d >> 5),
+                       owner ? vn : nullptr, sc, 1.0f, c1 > c0 ? c1 - c0 : 0, d8, vc, prt, nparts, acc);
+  else
+    pv_accumulate<DT>(V + (int64_t)c0 * d8, owner ? vn : nullptr, sc, 1.0f, c1 > c0 ? c1 - c0 : 0, d8, vc, prt, nparts, acc);
   __syncthreads();
 #pragma unroll
   for (int e = 0; e < 8; ++e) sc[prt * d + vc * 8 + e] = acc[e];
@@ -839,17 +947,18 @@ int rope_attn_online_launch(const void* qkv, const float* cos, const float* sin,
   });
 }
 
-template <bool SEQ>
+// (KV8: the dg_rope_attn_split_mx8 entry points -- mx8 caches with their exponent bytes; always rope_attn_split_kernel, any nsplit >= 1)
+template <bool SEQ, bool KV8 = false>
 int rope_attn_split_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
                            void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                           float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out || !scratch) return TG_E_NULL;
+                           float scale, int nsplit, int dtype, int device, tg_stream_t stream, void* k_exp = nullptr, void* v_exp = nullptr) {
+  if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out || !scratch || (KV8 && (!k_exp || !v_exp))) return TG_E_NULL;
   if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
   if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
-      max_seq <= 0 || max_seq > 65536 || bs * hl > INT32_MAX || nsplit < 1 || nsplit > 64)
+      max_seq <= 0 || max_seq > 65536 || bs * hl > INT32_MAX || nsplit < 1 || nsplit > 64 || (KV8 && d % 32 != 0))
     return TG_E_SHAPE;
   if (scratch_bytes < dg_rope_attn_split_scratch_bytes(bs, hl, d, nsplit)) return TG_E_SHAPE;
-  if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(scratch)) return TG_E_ALIGN;
+  if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(scratch) || !aligned16(k_exp) || !aligned16(v_exp)) return TG_E_ALIGN;
   DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
   const int64_t cs = (max_seq + nsplit - 1) / nsplit;
@@ -857,7 +966,7 @@ int rope_attn_split_launch(const void* qkv, const float* cos, const float* sin, 
   const unsigned lds = (unsigned)((772 + sc_floats) * sizeof(float));
   int* counters = reinterpret_cast<int*>(scratch);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + ((bs * hl * 4 + 15) / 16) * 16);
-  if ((d == 64 || d == 128) && max_seq * d * 2 < ((int64_t)1 << 32) && aligned16(qkv) && aligned16(cos) && aligned16(sin)) {
+  if (!KV8 && (d == 64 || d == 128) && max_seq * d * 2 < ((int64_t)1 << 32) && aligned16(qkv) && aligned16(cos) && aligned16(sin)) {
     // the one-barrier kernel, split over the sequence (same scratch layout: counters, then [head][chunk][max, sum, d outputs])
     const unsigned lds1 = (unsigned)(8 * (d + 2) * sizeof(float));
     const dim3 grid((unsigned)(bs * hl), (unsigned)nsplit);
@@ -870,9 +979,11 @@ int rope_attn_split_launch(const void* qkv, const float* cos, const float* sin, 
     });
   }
   if (lds > 64u * 1024u) return TG_E_SHAPE;
-  auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16, SEQ> : rope_attn_split_kernel<F16, SEQ>;
+  Kv8Arg<KV8> X;
+  if constexpr (KV8) { X.k_exp = (uint8_t*)k_exp; X.v_exp = (uint8_t*)v_exp; }
+  auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16, SEQ, KV8> : rope_attn_split_kernel<F16, SEQ, KV8>;
   hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl), (unsigned)nsplit), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)qkv,
-                     cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, part, counters, hl, kvl, d, max_seq, scale);
+                     cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, part, counters, hl, kvl, d, max_seq, scale, X);
   return launch_status();
 }
 
@@ -907,6 +1018,18 @@ int dg_rope_attn_split_seq(DG_ATTN_ARGS, void* scratch, int64_t scratch_bytes, i
   return rope_attn_split_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
                                       dtype, device, stream);
 }
+#define DG_ATTN8_ARGS const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp, void* v_exp, void* out
+int dg_rope_attn_split_mx8(DG_ATTN8_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                           int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch<false, true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
+                                             dtype, device, stream, k_exp, v_exp);
+}
+int dg_rope_attn_split_mx8_seq(DG_ATTN8_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
+                               int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch<true, true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
+                                            dtype, device, stream, k_exp, v_exp);
+}
+#undef DG_ATTN8_ARGS
 #undef DG_ATTN_ARGS
 
 int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) {

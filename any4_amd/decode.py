@@ -43,6 +43,8 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
+from .kvcache import F8, mx8_decode, mx8_encode
+
 
 @dataclass
 class DecodeConfig:
@@ -193,11 +195,21 @@ def _rope(x, cos, sin):
     return (x.float() * cos + rot.float() * sin).to(x.dtype)
 
 
-def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl: int, kvl: int, d: int, T: int):
+def _mx8_put(write, cache, exps, new):
+    """The plain-torch write side of an mx8 cache (any4_amd/kvcache.py): `new` rows are encoded, and `write(tensor, rows)` -- the
+    caller's addressing, the one it uses on a 16-bit cache -- puts the codes (as bytes) and the exponent bytes in place."""
+    codes, e = mx8_encode(new)
+    write(cache.view(torch.uint8), codes.view(torch.uint8))
+    write(exps, e)
+
+
+def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl: int, kvl: int, d: int, T: int, k_exp=None, v_exp=None):
     """Plain-torch formulation of a prefill chunk's attention (what dg_prefill_attn is tested against; also the CPU path).
     qkv [bs * T, (hl + 2 kvl) d], row b * T + t = token t of sequence b at position p0 + t.  Ropes q and k with the table rows
     [p0, p0 + T), writes the T k / v rows into the caches and attends over cache[:, :, :p0 + T] with the mask s > p0 + t; rounding
     points as in DecodeLayer.forward: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit P.V.
+    k_exp / v_exp: the caches are mx8 (float8_e4m3fn codes with these exponent bytes) -- the rows are encoded on the way in, and the
+    attention reads mx8_decode of the cache, the chunk's own rows included.
     Returns the context [bs * T, hl * d]."""
     bs, rep, S = qkv.shape[0] // T, hl // kvl, p0 + T
     rows = torch.arange(p0, S, device=qkv.device)
@@ -205,17 +217,24 @@ def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl
     q = _rope(qkv[:, : hl * d].reshape(bs, T, hl, d), cos, sin)
     k = _rope(qkv[:, hl * d: (hl + kvl) * d].reshape(bs, T, kvl, d), cos, sin)
     v = qkv[:, (hl + kvl) * d:].reshape(bs, T, kvl, d)
-    k_cache.index_copy_(2, rows, k.transpose(1, 2))
-    v_cache.index_copy_(2, rows, v.transpose(1, 2))
+    if k_exp is None:
+        k_cache.index_copy_(2, rows, k.transpose(1, 2))
+        v_cache.index_copy_(2, rows, v.transpose(1, 2))
+        K, V = k_cache[:, :, :S], v_cache[:, :, :S]
+    else:
+        _mx8_put(lambda c, new: c.index_copy_(2, rows, new), k_cache, k_exp, k.transpose(1, 2))
+        _mx8_put(lambda c, new: c.index_copy_(2, rows, new), v_cache, v_exp, v.transpose(1, 2))
+        K, V = mx8_decode(k_cache[:, :, :S], k_exp[:, :, :S], qkv.dtype), mx8_decode(v_cache[:, :, :S], v_exp[:, :, :S], qkv.dtype)
     qg = q.reshape(bs, T, kvl, rep, d).permute(0, 2, 3, 1, 4).reshape(bs, kvl, rep * T, d)
-    att = torch.matmul(qg, k_cache[:, :, :S].transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep * T, S]
+    att = torch.matmul(qg, K.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep * T, S]
     mask = torch.arange(S, device=qkv.device).view(1, S) > rows.view(T, 1)                    # [T, S]: s > p0 + t
     att = att.view(bs, kvl, rep, T, S).masked_fill(mask, float("-inf")).softmax(-1).to(qkv.dtype).view(bs, kvl, rep * T, S)
-    ctx = torch.matmul(att, v_cache[:, :, :S])                                                  # [bs, kvl, rep * T, d]
+    ctx = torch.matmul(att, V)                                                                  # [bs, kvl, rep * T, d]
     return ctx.view(bs, kvl, rep, T, d).permute(0, 3, 1, 2, 4).reshape(bs * T, hl * d)
 
 
-def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots, k_cache, v_cache, hl: int, kvl: int, d: int, T: int):
+def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots, k_cache, v_cache, hl: int, kvl: int, d: int, T: int,
+                                k_exp=None, v_exp=None):
     """prefill_attention_torch with a position, a length and a cache slot per sequence, all on the host (what dg_prefill_attn_seq is
     tested against; also the CPU path).  qkv [n * T, (hl + 2 kvl) d], rows padded to the common T: sequence i has `lengths[i]` tokens
     from position `positions[i]` on and lives in k_cache[slots[i]] / v_cache[slots[i]].  Every sequence gets its own rope rows, its
@@ -224,14 +243,15 @@ def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots
     n = qkv.shape[0] // T
     if n == k_cache.shape[0] and all(int(p) == int(positions[0]) for p in positions) and all(int(x) == T for x in lengths) and \
             [int(x) for x in slots] == list(range(n)):
-        return prefill_attention_torch(qkv, cos_tab, sin_tab, int(positions[0]), k_cache, v_cache, hl, kvl, d, T)
+        return prefill_attention_torch(qkv, cos_tab, sin_tab, int(positions[0]), k_cache, v_cache, hl, kvl, d, T, k_exp, v_exp)
     ctx = qkv.new_zeros(n, T, hl * d)
     rows = qkv.view(n, T, -1)
     for i in range(n):
         L, sl = int(lengths[i]), int(slots[i])
         if L > 0:
+            exps = () if k_exp is None else (k_exp[sl: sl + 1], v_exp[sl: sl + 1])
             ctx[i, :L] = prefill_attention_torch(rows[i, :L], cos_tab, sin_tab, int(positions[i]), k_cache[sl: sl + 1], v_cache[sl: sl + 1],
-                                                 hl, kvl, d, L)
+                                                 hl, kvl, d, L, *exps)
     return ctx.view(n * T, hl * d)
 
 
@@ -243,8 +263,15 @@ def _scatter_rows(cache, pos, active, new):
 
 
 class DecodeLayer(torch.nn.Module):
-    def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int):
+    def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int,
+                 kv_cache: Optional[str] = None):
+        """kv_cache: None = k / v rows in the layer's dtype; "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py): float8_e4m3fn codes
+        in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache)."""
         super().__init__()
+        if kv_cache not in (None, "mx8"):
+            raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
+        if kv_cache == "mx8" and cfg.head_dim % 32:
+            raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
         if cfg.heads % world or cfg.kv_heads % world or cfg.inter % (16 * world) or cfg.hidden % (16 * world):
             raise ValueError(f"heads={cfg.heads}, kv_heads={cfg.kv_heads}, inter={cfg.inter}, hidden={cfg.hidden} "
                              f"must split over world_size={world} in whole heads / 16-row tiles")
@@ -257,8 +284,16 @@ class DecodeLayer(torch.nn.Module):
         self.down = factory("down", idx, cfg.inter, cfg.hidden // world)
         self.norm1 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.norm2 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
-        self.register_buffer("k_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
-        self.register_buffer("v_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
+        if kv_cache == "mx8":
+            for name in ("k", "v"):
+                self.register_buffer(name + "_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=torch.uint8).view(F8),
+                                     persistent=False)
+                self.register_buffer(name + "_exp", torch.zeros(bs, self.kvl, cfg.max_seq, d // 32, device=device, dtype=torch.uint8),
+                                     persistent=False)
+        else:
+            self.register_buffer("k_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
+            self.register_buffer("v_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
+            self.k_exp = self.v_exp = None
         # forward_fused5: which stages the library fused (None: not tried yet; set by the first step)
         self._fuse = {"norm1": None, "norm2": None, "mlp": None}
         # decode_attention: the stack's split count and its scratch buffer (DecodeStack sets both once, when it is built)
@@ -268,19 +303,26 @@ class DecodeLayer(torch.nn.Module):
         """The plain-torch arithmetic of one token per sequence, behind either addressing (`forward`, `forward_seq`): `cos` / `sin` the
         rope rows [1 | bs, 1, d], `write(cache, rows [bs, kvl, d])` puts the new k / v rows into a cache, `mask` [1 | bs, 1, 1, S] hides
         the cache rows behind each position.  Rounding points: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit
-        P.V (the formulation the fused schedules are tested against)."""
+        P.V (the formulation the fused schedules are tested against).  An mx8 cache: the rows are encoded on the way in and the
+        attention reads mx8_decode of the cache, the new token's own rows included."""
         d, bs = self.cfg.head_dim, h.shape[0]
         qkv = self.qkv(self.norm1(h))
         q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
         k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
         v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
-        write(self.k_cache, k)
-        write(self.v_cache, v)
+        if self.k_exp is None:
+            write(self.k_cache, k)
+            write(self.v_cache, v)
+            K, V = self.k_cache, self.v_cache
+        else:
+            _mx8_put(write, self.k_cache, self.k_exp, k)
+            _mx8_put(write, self.v_cache, self.v_exp, v)
+            K, V = mx8_decode(self.k_cache, self.k_exp, h.dtype), mx8_decode(self.v_cache, self.v_exp, h.dtype)
         rep = self.hl // self.kvl
         qg = q.reshape(bs, self.kvl, rep, d)
-        att = torch.matmul(qg, self.k_cache.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
+        att = torch.matmul(qg, K.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
         att = att.masked_fill(mask, float("-inf")).softmax(-1).to(h.dtype)
-        ctx = torch.matmul(att, self.v_cache).reshape(bs, self.hl * d)
+        ctx = torch.matmul(att, V).reshape(bs, self.hl * d)
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
     def forward(self, h, pos, cos_tab, sin_tab, arange, gather):
@@ -308,7 +350,7 @@ class DecodeLayer(torch.nn.Module):
         batched formulation, prefill_attention_torch)."""
         d = self.cfg.head_dim
         ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
-                                          self.hl, self.kvl, d, T)
+                                          self.hl, self.kvl, d, T, self.k_exp, self.v_exp)
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
     def _mlp_torch(self, h, gather):
@@ -321,11 +363,16 @@ class DecodeLayer(torch.nn.Module):
     # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context
     def decode_attention(self, qkv, pos, cos_tab, sin_tab, per_sequence: bool = False):
         """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
-        stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one."""
+        stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one.  An mx8 cache
+        always takes the split entry point (also at a split count of 1: the other kernels have no 8-bit form)."""
         from . import decode_ops as G
 
         d = self.cfg.head_dim
         args = (qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+        if self.k_exp is not None:
+            if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
+                self._attn_scratch = G.rope_attn_split_scratch(self.k_cache.shape[0], self.hl, d, self._attn_split, qkv.device)
+            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp)
         if self._attn_scratch is not None:
             return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence)
         return (G.rope_attn_online if d in (64, 128) else G.rope_attn)(*args, per_sequence=per_sequence)
@@ -340,7 +387,7 @@ class DecodeLayer(torch.nn.Module):
         T = qkv.shape[0] // self.k_cache.shape[0] if T is None else T
         out = qkv.new_zeros(qkv.shape[0], self.hl * d) if per_sequence else None
         return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
-                              out=out, lengths=lengths, slots=slots, per_sequence=per_sequence)
+                              out=out, lengths=lengths, slots=slots, per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp)
 
     def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather):
         """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
@@ -439,8 +486,13 @@ class DecodeStack(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, linear_factory: Callable, device, dtype=torch.bfloat16, bs: int = 1,
                  rank: int = 0, world: int = 1, group=None, seed: int = 0, lm_head: bool = True,
                  fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
-                 ragged: bool = False):
-        """ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`
+                 ragged: bool = False, kv_cache: Optional[str] = None):
+        """kv_cache: None = a 16-bit KV cache in the stack's dtype (the default); "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py:
+        E4M3 codes and one exponent byte per 32 elements, (1 + 1/32) / 2 of the 16-bit cache's bytes; head_dim % 32 == 0).  The fused
+        attention launches then are the mx8 entry points (a decode step always the split one, so the stack always owns a split scratch);
+        capture, prefill, ragged decode and generate work unchanged on top, TP too (the caches are per rank).  In fp16, k / v values
+        beyond fp16's range are out of contract.
+        ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`
         a position, a length and a cache slot per sequence, `generate` prompts of different lengths; the step (and its captured
         graph) reads `pos_seq` [bs] in place of `pos`.  A stack built without it is what it was.
         fused: run the non-GEMM parts on the HIP glue kernels (default on a GPU) or as plain torch ops
@@ -456,6 +508,11 @@ class DecodeStack(torch.nn.Module):
         super().__init__()
         if gather not in ("rccl", "peer"):
             raise ValueError("gather must be 'rccl' or 'peer'")
+        if kv_cache not in (None, "mx8"):
+            raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
+        if kv_cache == "mx8" and cfg.head_dim % 32:
+            raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
+        self.kv_cache = kv_cache
         self.gather_mode = gather
         self._peer = {}  # output width per rank -> PeerWriteGather
         self.cfg, self.bs, self.rank, self.world, self.group = cfg, bs, rank, world, group
@@ -467,7 +524,7 @@ class DecodeStack(torch.nn.Module):
         self.embed.weight.data = torch.randn(cfg.vocab, cfg.hidden, device=device, generator=gen).to(dtype)
         self.embed.weight.requires_grad_(False)
         self.layers = torch.nn.ModuleList(
-            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs) for i in range(cfg.layers)])
+            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs, kv_cache=kv_cache) for i in range(cfg.layers)])
         self.norm = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.lm_head = None
         if lm_head:
@@ -506,10 +563,15 @@ class DecodeStack(torch.nn.Module):
             self._attn_split = max(1, min(want, 256 // max(1, bs * hl)))
             if os.environ.get("ANY4_ATTN_SPLIT"):  # developer override (A/B of the threshold above)
                 self._attn_split = max(1, int(os.environ["ANY4_ATTN_SPLIT"]))
-            if self._attn_split > 1:
+            if self._attn_split > 1 or kv_cache == "mx8":
                 self._attn_scratch = G.rope_attn_split_scratch(bs, hl, cfg.head_dim, self._attn_split, device)
             for layer in self.layers:
                 layer._attn_scratch, layer._attn_split = self._attn_scratch, self._attn_split
+
+    def kv_cache_bytes(self) -> int:
+        """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes)."""
+        return sum(t.numel() * t.element_size() for layer in self.layers
+                   for t in (layer.k_cache, layer.v_cache, layer.k_exp, layer.v_exp) if t is not None)
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
     def _gather(self, y, peer_ok=True):

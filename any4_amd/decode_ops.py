@@ -86,12 +86,34 @@ def _per_sequence(pos, n, what):
         raise RuntimeError(f"{what}: per_sequence needs {n} int64 positions (one per sequence), got {pos.numel()}")
 
 
-def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None):
+F8 = torch.float8_e4m3fn
+
+
+def _mx8_exps(what, k_cache, v_cache, k_exp, v_exp, d):
+    """The exponent tensors of an mx8 cache pair (any4_amd/kvcache.py), checked: () for 16-bit caches, which must bring none."""
+    mx8 = k_cache.dtype == F8 or v_cache.dtype == F8
+    if not mx8:
+        if k_exp is not None or v_exp is not None:
+            raise RuntimeError(f"{what}: k_exp / v_exp belong to float8_e4m3fn (mx8) caches, got {k_cache.dtype}")
+        return ()
+    if k_cache.dtype != F8 or v_cache.dtype != F8 or k_exp is None or v_exp is None:
+        raise RuntimeError(f"{what}: an mx8 cache is k_cache, v_cache (float8_e4m3fn) and k_exp, v_exp (uint8)")
+    if d % 32:
+        raise RuntimeError(f"{what}: an mx8 cache needs head_dim % 32 == 0, got {d}")
+    for c, e in ((k_cache, k_exp), (v_cache, v_exp)):
+        if e.dtype != torch.uint8 or tuple(e.shape) != tuple(c.shape[:-1]) + (d // 32,) or c.shape[-1] != d:
+            raise RuntimeError(f"{what}: exponents must be uint8 {tuple(c.shape[:-1]) + (d // 32,)} for codes {tuple(c.shape)}, got {e.dtype} {tuple(e.shape)}")
+    return (k_exp, v_exp)
+
+
+def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=()):
     """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
     `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split: its entry points take the scratch buffer (pointer, bytes) behind `out`
-    and nsplit behind the scale."""
+    and nsplit behind the scale.  exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points take them behind v_cache."""
     scratch, nsplit = split if split is not None else (None, None)
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, out=out)
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, *exps, out=out)
+    if exps:
+        entry += "_mx8"
     if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"{entry}: out must be [{bs}, {hl * d}] {qkv.dtype}")
     if per_sequence:
@@ -99,7 +121,8 @@ def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, p
         entry += "_seq"
     mid, last = ((), ()) if split is None else ((scratch.data_ptr(), scratch.numel() * 4), (nsplit,))
     _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), out.data_ptr(), *mid, bs, hl, kvl, d, max_seq, float(scale), *last,
+                                           v_cache.data_ptr(), *[e.data_ptr() for e in exps], out.data_ptr(), *mid, bs, hl, kvl, d, max_seq,
+                                           float(scale), *last,
                                            _dt(qkv), qkv.device.index, _stream(qkv)), entry)
     return out
 
@@ -129,15 +152,18 @@ def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> to
 
 def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                     v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int,
-                    per_sequence: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+                    per_sequence: bool = False, out: torch.Tensor = None, k_exp: torch.Tensor = None, v_exp: torch.Tensor = None) -> torch.Tensor:
     """rope_attn with the sequence split over `nsplit` blocks per head (fills the GPU at batch 1 / long contexts).
-    per_sequence, out: as rope_attn."""
-    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit))
+    per_sequence, out: as rope_attn.  float8_e4m3fn caches with `k_exp`, `v_exp` (uint8 [bs, kvl, max_seq, d / 32]) are an mx8 cache
+    (any4_amd/kvcache.py): the mx8 entry points, which also take nsplit = 1."""
+    exps = _mx8_exps("rope_attn_split", k_cache, v_cache, k_exp, v_exp, d)
+    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps)
 
 
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None,
-                 lengths: torch.Tensor = None, slots: torch.Tensor = None, per_sequence: bool = False) -> torch.Tensor:
+                 lengths: torch.Tensor = None, slots: torch.Tensor = None, per_sequence: bool = False, k_exp: torch.Tensor = None,
+                 v_exp: torch.Tensor = None) -> torch.Tensor:
     """A chunk of T tokens per sequence: qkv [bs * T, (hl + 2 kvl) d] (row b * T + t) -> context [bs * T, hl * d]; the T roped k rows and
     the v rows are appended to the caches at positions pos ... pos + T - 1 (`pos` [1] int64 on the device = position of token 0), and
     token t attends causally over cache rows 0 ... pos + t.  A token whose position is outside the cache writes nothing and leaves its
@@ -145,8 +171,11 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     per_sequence (also implied by `lengths` / `slots`): qkv is [n * T, ...], rows padded to the common T, and `pos` int64 [n] holds the
     position of token 0 of each sequence.  `lengths` int64 [n] on the device: only tokens t < min(lengths[i], T) exist (default: all T);
     `slots` int64 [n] on the device: sequence i lives in cache slot slots[i] (default: slot i, and n must be the caches' batch; with
-    slots n may be smaller).  A sequence of length <= 0 or with a slot outside the caches does nothing; slots must be distinct."""
-    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, out=out)
+    slots n may be smaller).  A sequence of length <= 0 or with a slot outside the caches does nothing; slots must be distinct.
+    float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split."""
+    exps = _mx8_exps("prefill_attn", k_cache, v_cache, k_exp, v_exp, d)
+    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, *exps, out=out)
+    mx8, eptr = "_mx8" if exps else "", [e.data_ptr() for e in exps]
     T = int(T)
     per_sequence = per_sequence or lengths is not None or slots is not None
     if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != k_cache.shape[0] and slots is None):
@@ -159,15 +188,17 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
         for name, t in (("lengths", lengths), ("slots", slots)):
             if t is not None and (t.dtype != torch.int64 or t.numel() != n):
                 raise RuntimeError(f"prefill_attn: {name} must be int64 with {n} elements (one per sequence)")
-        _lib.check(_lib.load().dg_prefill_attn_seq(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-                                                   None if lengths is None else lengths.data_ptr(),
-                                                   None if slots is None else slots.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-                                                   out.data_ptr(), n, T, k_cache.shape[0], hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                                   qkv.device.index, _stream(qkv)), "dg_prefill_attn_seq")
+        entry = f"dg_prefill_attn{mx8}_seq"
+        _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
+                                               None if lengths is None else lengths.data_ptr(),
+                                               None if slots is None else slots.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), *eptr,
+                                               out.data_ptr(), n, T, k_cache.shape[0], hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                               qkv.device.index, _stream(qkv)), entry)
         return out
-    _lib.check(_lib.load().dg_prefill_attn(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), out.data_ptr(), rows // T, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                           qkv.device.index, _stream(qkv)), "dg_prefill_attn")
+    entry = f"dg_prefill_attn{mx8}"
+    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
+                                           v_cache.data_ptr(), *eptr, out.data_ptr(), rows // T, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
+                                           qkv.device.index, _stream(qkv)), entry)
     return out
 
 

@@ -134,6 +134,33 @@ TG_API int dg_prefill_attn_seq(const void* qkv, const float* cos, const float* s
                                const int64_t* slot, void* k_cache, void* v_cache, void* out, int64_t n, int64_t T, int64_t cache_bs,
                                int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream);
 
+/* ---- mx8 KV cache: block-scaled 8-bit rows (OCP MXFP8; any4_amd/kvcache.py mx8_encode is the definition) ----
+ * k_cache / v_cache [bs][kvl][max_seq][d] hold one E4M3 code per element, k_exp / v_exp [bs][kvl][max_seq][d / 32] one E8M0 exponent byte
+ * per 32 consecutive elements of a row: value = code * 2^(E - 127); E = 255 marks a block with a non-finite element, which reads as NaN
+ * in all 32 places.  The four entry points take their namesakes' arguments plus the two exponent tensors (behind v_cache) and keep their
+ * namesakes' guards, scratch protocol and rounding points:
+ *   writers  the roped k row keeps dg_rope_kv's 16-bit bits; that row and the raw v row are encoded per block -- byte for byte
+ *            mx8_encode(rope(k)) / mx8_encode(v).  Rows that are not written keep their codes AND their exponent bytes.
+ *   readers  a cached row is converted to the 16-bit type (exact) and enters the namesake's arithmetic in the namesake's order.  In
+ *            dg_rope_attn_split_mx8 the new token's own k / v enter the scores and the value sum as their DECODED rows (what later
+ *            steps read), not as the unquantised ones.
+ * dg_rope_attn_split_mx8(_seq) always run the 256-thread split kernel (dg_rope_attn_split's for a d other than 64 / 128): nsplit = 1 is
+ * accepted, max_seq / nsplit <= ~15000; d % 32 == 0 (TG_E_SHAPE otherwise, nothing is touched).  dg_prefill_attn_mx8(_seq): d = 64 / 128.
+ * All four tensors 16-byte aligned.  fp16 stacks whose |k|, |v| exceed fp16's range after decoding are out of contract. */
+TG_API int dg_rope_attn_split_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                                  void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                  int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+TG_API int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                                      void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                      int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+TG_API int dg_prefill_attn_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                               void* k_exp, void* v_exp, void* out, int64_t bs, int64_t T, int hl, int kvl, int d, int64_t max_seq, float scale,
+                               int dtype, int device, tg_stream_t stream);
+TG_API int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                                   const int64_t* slot, void* k_cache, void* v_cache, void* k_exp, void* v_exp, void* out, int64_t n, int64_t T,
+                                   int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
+                                   tg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -15,6 +15,13 @@ the 4-bit weights stream (algorithmic bytes of the quantized linears / step time
   (a) the captured step of a ragged and a non-ragged stack at equal positions, bs = 1 / 4 / 8, alternating in one process;
   (b) eight prompts of 16 ... 512 tokens through `generate(list)` on one ragged bs = 8 stack against the only route there is without
       it, eight bs = 1 `generate` runs one after the other; tokens/s of the new tokens.
+
+    python tools/llama_decode_bench.py --config llama3_8b --kv-cache mx8 [--ragged] [--out profiles/kv8_bench.jsonl]
+
+--kv-cache mx8 (one GPU): the block-scaled 8-bit KV cache against the 16-bit one, one JSON line per leg, appended
+to --out: the caches' bytes, and the captured step of a 16-bit-cache stack and an mx8-cache stack, alternating in one process, at
+bs = 1 and 8 with the position near 512, 4096 and the end of an 8192-position cache.  With --ragged: leg (b) above on a 16-bit and on
+an mx8 ragged bs = 8 stack.
 """
 import argparse
 import json
@@ -95,6 +102,56 @@ def ragged_bench(a, cfg, device):
     return legs
 
 
+def kv8_bench(a, cfg, device):
+    """The legs of --kv-cache mx8; yields the JSON-able results."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    def stack(bs, kv_cache, ragged=False):
+        st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                         fuse_gemm_stages=not a.no_fuse, ragged=ragged, kv_cache=kv_cache)
+        st.capture()
+        return st
+
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "data": "synthetic (random weights, random tokens, zero caches)"}
+    if a.ragged:  # leg (b) of --ragged on either cache
+        lengths, new = [16, 32, 64, 96, 128, 256, 384, 512], a.new_tokens
+        gen = torch.Generator().manual_seed(0)
+        prompts = [torch.randint(0, cfg.vocab, (n,), generator=gen).to(device) for n in lengths]
+        res = {}
+        for name, kv in (("cache16", None), ("mx8", "mx8")):
+            st = stack(8, kv, ragged=True)
+            st.generate(prompts, new)  # (first call: allocator, workspaces)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            st.generate(prompts, new)
+            torch.cuda.synchronize()
+            t = time.perf_counter() - t0
+            res[name] = {"seconds": round(t, 4), "tokens_per_s": round(8 * new / t, 1), "kv_cache_bytes": st.kv_cache_bytes(), "attn_split": st._attn_split}
+            del st
+            torch.cuda.empty_cache()
+        yield dict(base, leg="kv8 b: eight prompts, generate(list) on a ragged bs = 8 stack, 16-bit cache vs mx8 cache", prompt_lengths=lengths,
+                   new_tokens=new, **res, mx8_over_cache16=round(res["mx8"]["seconds"] / res["cache16"]["seconds"], 4))
+        return
+    for bs in (1, 8):
+        pair = {"cache16": stack(bs, None), "mx8": stack(bs, "mx8")}
+        leg = dict(base, leg="kv8 a: captured step, 16-bit cache vs mx8 cache, alternating", bs=bs, steps=a.steps, warmup=a.warmup, rounds=a.rounds,
+                   kv_cache_bytes={k: st.kv_cache_bytes() for k, st in pair.items()}, attn_split={k: st._attn_split for k, st in pair.items()},
+                   ms_per_step={})
+        for want in (512, 4096, cfg.max_seq):
+            start = max(0, min(want, cfg.max_seq - a.warmup - a.steps))  # (the timed steps end inside the cache)
+            series = {k: [] for k in pair}
+            for r in range(a.rounds):
+                for k in (("cache16", "mx8") if r % 2 == 0 else ("mx8", "cache16")):
+                    series[k].append(round(time_steps(pair[k], a.steps, a.warmup, start) * 1e3, 4))
+            med = {k: sorted(v)[len(v) // 2] for k, v in series.items()}
+            leg["ms_per_step"][f"pos{start + a.warmup}"] = dict(
+                {k: {"median": med[k], "min": min(v), "max": max(v), "series": v} for k, v in series.items()},
+                mx8_over_cache16=round(med["mx8"] / med["cache16"], 4))
+        yield leg
+        del pair
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "tiny"])
@@ -122,8 +179,13 @@ def main():
     ap.add_argument("--ragged", action="store_true", help="the two legs of DESIGN.md section 13 (see the module docstring); one GPU")
     ap.add_argument("--rounds", type=int, default=7, help="--ragged leg (a): alternations per batch size")
     ap.add_argument("--new-tokens", type=int, default=64, help="--ragged leg (b): tokens generated per prompt")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "ragged_bench.jsonl"), help="--ragged: the file the JSON lines are appended to")
+    ap.add_argument("--kv-cache", default=None, choices=["mx8"],
+                    help="the legs of DESIGN.md section 15: the mx8 KV cache against the 16-bit one at an 8192-position cache (see the module docstring); one GPU")
+    ap.add_argument("--out", default=None, help="--ragged / --kv-cache: the file the JSON lines are appended to "
+                                                "(default profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl)")
     a = ap.parse_args()
+    if a.out is None:
+        a.out = os.path.join(ROOT, "profiles", "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
     if a.backend == "gloo" and a.gather != "peer":
         raise SystemExit("--backend gloo moves no CUDA tensors: use it with --gather peer")
 
@@ -149,6 +211,17 @@ def main():
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.kv_cache:
+        if world > 1:
+            raise SystemExit("--kv-cache runs on one GPU")
+        cfg.max_seq = 8192
+        with open(a.out, "a") as f:
+            for leg in kv8_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     if a.ragged:
         if world > 1:
