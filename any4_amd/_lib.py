@@ -3,6 +3,7 @@ import fails loudly (build it with `python -m any4_amd.build`)."""
 from __future__ import annotations
 
 import ctypes
+import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,6 +65,32 @@ class PeerGather(ctypes.Structure):
     ]
 
 
+# The twelve fused attention entry points of include/decode_glue_hip.h: four bases, each with a `_seq` flavour (a position per sequence), two of
+# them with `_mx8` ones (an mx8 KV cache).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
+# puts a call's values in the same order.
+_ci, _cf = ctypes.c_int, ctypes.c_float
+ATTN_BASES = {"dg_rope_attn": False, "dg_rope_attn_online": False, "dg_rope_attn_split": True, "dg_prefill_attn": True}  # base: has _mx8 flavours
+_ATTN_HEAD = [("qkv", _vp), ("cos", _vp), ("sin", _vp), ("pos", _vp)]
+_ATTN_LEN_SLOT = [("len", _vp), ("slot", _vp)]                      # dg_prefill_attn*_seq
+_ATTN_CACHES = [("k_cache", _vp), ("v_cache", _vp)]
+_ATTN_EXPS = [("k_exp", _vp), ("v_exp", _vp)]                       # *_mx8*
+_ATTN_SCRATCH = [("scratch", _vp), ("scratch_bytes", _i64)]         # dg_rope_attn_split*
+_ATTN_SHAPE = [("hl", _ci), ("kvl", _ci), ("d", _ci), ("max_seq", _i64), ("scale", _cf)]
+_ATTN_TAIL = [("dtype", _ci), ("device", _ci), ("stream", _vp)]
+
+
+@functools.lru_cache(maxsize=None)
+def attn_signature(base, seq=False, mx8=False):
+    """(entry point, ((argument name, ctype), ...)) of one flavour of an attention base"""
+    if base not in ATTN_BASES or (mx8 and not ATTN_BASES[base]):
+        raise KeyError(f"no attention entry point {base}{'_mx8' if mx8 else ''}")
+    prefill, split = base == "dg_prefill_attn", base == "dg_rope_attn_split"
+    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill and seq else []) + _ATTN_CACHES + (_ATTN_EXPS if mx8 else []) + [("out", _vp)]
+            + (_ATTN_SCRATCH if split else []) + [("bs", _i64)] + ([("T", _i64)] if prefill else []) + ([("cache_bs", _i64)] if prefill and seq else [])
+            + _ATTN_SHAPE + ([("nsplit", _ci)] if split else []) + _ATTN_TAIL)
+    return base + ("_mx8" if mx8 else "") + ("_seq" if seq else ""), tuple(args)
+
+
 # name -> argtypes, exactly the prototypes of include/tinygemm_hip.h
 SYMBOLS = {
     "tg_abi_version": [],
@@ -104,35 +131,15 @@ SYMBOLS = {
                    ctypes.c_int, ctypes.c_int, _vp],
     "dg_decode_attn": [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
                        ctypes.c_int, ctypes.c_int, _vp],
-    "dg_rope_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
-                     ctypes.c_int, ctypes.c_int, _vp],
-    "dg_rope_attn_online": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
-                     ctypes.c_int, ctypes.c_int, _vp],
     "dg_rope_attn_split_scratch_bytes": [_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int],
-    "dg_rope_attn_split": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
-                           ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
     "dg_swiglu": [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_linear16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
-    "dg_prefill_attn": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
-                        ctypes.c_int, ctypes.c_int, _vp],
-    # ... with a position per sequence (`pos` int64[bs]); dg_prefill_attn_seq also takes a length and a cache slot per sequence
-    "dg_rope_attn_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
-                         ctypes.c_int, ctypes.c_int, _vp],
-    "dg_rope_attn_online_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
-                                ctypes.c_int, ctypes.c_int, _vp],
-    "dg_rope_attn_split_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
-                               ctypes.c_float, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
-    "dg_prefill_attn_seq": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64,
-                            ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
-    # ... on an mx8 cache: their namesakes' lists with k_exp, v_exp behind v_cache
-    "dg_rope_attn_split_mx8": [_vp] * 10 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
-                                            ctypes.c_int, ctypes.c_int, _vp],
-    "dg_rope_attn_split_mx8_seq": [_vp] * 10 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
-                                                ctypes.c_int, ctypes.c_int, _vp],
-    "dg_prefill_attn_mx8": [_vp] * 9 + [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
-    "dg_prefill_attn_mx8_seq": [_vp] * 11 + [_i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float, ctypes.c_int,
-                                             ctypes.c_int, _vp],
 }
+for _base, _has_mx8 in ATTN_BASES.items():
+    for _seq in (False, True):
+        for _mx8 in (False, True) if _has_mx8 else (False,):
+            _name, _args = attn_signature(_base, _seq, _mx8)
+            SYMBOLS[_name] = [t for _, t in _args]
 
 _lib = None
 

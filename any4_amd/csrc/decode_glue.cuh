@@ -6,6 +6,7 @@
 // mirror the torch formulation in any4_amd/decode.py so the two paths can be compared in tests.
 #include "../../include/decode_glue_hip.h"
 #include "stage_math.cuh"
+#include "attn_call.cuh"
 
 namespace {
 #include "kv8.cuh"
@@ -846,6 +847,12 @@ __global__ void __launch_bounds__(256) swiglu_kernel(const u32x4* __restrict__ g
   }
 }
 
+// dynamic LDS of the 256-thread attention kernels: `fixed` floats, then a score per position -- reused as the [256 / (d / 8)][d] partial outputs
+inline unsigned attn_lds_bytes(int fixed, int64_t positions, int d) {
+  const int64_t partials = (256 / (d / 8)) * (int64_t)d;
+  return (unsigned)((fixed + (positions > partials ? positions : partials)) * sizeof(float));
+}
+
 }  // namespace
 
 extern "C" {
@@ -879,18 +886,13 @@ int dg_rope_kv(const void* qkv, const float* cos, const float* sin, const int64_
 
 int dg_decode_attn(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos, void* out, int64_t bs,
                    int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  if (!q || !k_cache || !v_cache || !pos || !out) return TG_E_NULL;
-  if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
-  if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
-      max_seq <= 0 || max_seq > 8192 || bs * hl > INT32_MAX)
-    return TG_E_SHAPE;
-  if (!aligned16(k_cache) || !aligned16(v_cache)) return TG_E_ALIGN;
+  const AttnCall c = attn_call(q, nullptr, nullptr, pos, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out, bs, hl, kvl, d, max_seq,
+                               scale, dtype, device, stream);
+  if (const int rc = check_attn(ATTN_UNFUSED, c)) return rc;
   DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
-  const int64_t sc_floats = max_seq > (256 / (d / 8)) * (int64_t)d ? max_seq : (256 / (d / 8)) * (int64_t)d;
-  const unsigned lds = (unsigned)((260 + sc_floats) * sizeof(float));
   auto kern = dtype == TG_BF16 ? decode_attn_kernel<BF16> : decode_attn_kernel<F16>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl)), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)q,
+  hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl)), dim3(256), attn_lds_bytes(260, max_seq, d), (hipStream_t)stream, (const uint16_t*)q,
                      (const uint16_t*)k_cache, (const uint16_t*)v_cache, pos, (uint16_t*)out, hl, kvl, d, max_seq, scale);
   return launch_status();
 }
@@ -899,92 +901,72 @@ int dg_decode_attn(const void* q, const void* k_cache, const void* v_cache, cons
 
 namespace {
 
-// the three attention entry points the stack launches, each once for `pos` [1] (SEQ = false) and once for `pos` [bs] (dg_*_seq)
-template <bool SEQ>
-int rope_attn_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                     void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
-                     tg_stream_t stream) {
-  if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out) return TG_E_NULL;
-  if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
-  if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
-      max_seq <= 0 || max_seq > 8192 || bs * hl > INT32_MAX)
-    return TG_E_SHAPE;
-  if (!aligned16(k_cache) || !aligned16(v_cache)) return TG_E_ALIGN;
-  DeviceScope ds(device);
+// The launchers of the three fused decode kernels: check_attn, then only what is a launcher's own.  c.seq / c.kv8 pick the kernel's flavour
+// (the dg_*_seq entry points: `pos` [bs]; the dg_*_mx8 ones: mx8 caches with their exponent bytes).
+int rope_attn_launch(const AttnCall& c) {
+  if (const int rc = check_attn(ATTN_GENERAL, c)) return rc;
+  DeviceScope ds(c.device);
   if (!ds.ok) return TG_E_DEVICE;
-  const int64_t sc_floats = max_seq > (256 / (d / 8)) * (int64_t)d ? max_seq : (256 / (d / 8)) * (int64_t)d;
-  const unsigned lds = (unsigned)((772 + sc_floats) * sizeof(float));
-  auto kern = dtype == TG_BF16 ? rope_attn_kernel<BF16, SEQ> : rope_attn_kernel<F16, SEQ>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl)), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin, pos,
-                     (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, d, max_seq, scale);
-  return launch_status();
-}
-
-template <bool SEQ>
-int rope_attn_online_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                            void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
-                            tg_stream_t stream) {
-  if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out) return TG_E_NULL;
-  if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
-  if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || !(d == 64 || d == 128) || max_seq <= 0 || bs * hl > INT32_MAX ||
-      max_seq * d * 2 >= ((int64_t)1 << 32))
-    return TG_E_SHAPE;
-  if (!aligned16(qkv) || !aligned16(cos) || !aligned16(sin) || !aligned16(k_cache) || !aligned16(v_cache)) return TG_E_ALIGN;
-  DeviceScope ds(device);
-  if (!ds.ok) return TG_E_DEVICE;
-  const unsigned lds = (unsigned)(8 * (d + 2) * sizeof(float));
-  unsigned long long* trace = nullptr;
-#if GEMV_TRACE
-  trace = g_attn_trace;
-#endif
-  return pick_dt(dtype, [&](auto DT_) {
-    return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
-      hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, SEQ>), dim3((unsigned)(bs * hl)), dim3(512), lds, (hipStream_t)stream,
-                         (const uint16_t*)qkv, cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, trace,
-                         (float*)nullptr, (int*)nullptr);
+  return pick_dt(c.dtype, [&](auto DT_) {
+    return pick<0, 1>(c.seq, [&](auto SEQ_) {
+      hipLaunchKernelGGL((rope_attn_kernel<decltype(DT_), (bool)decltype(SEQ_)::value>), dim3((unsigned)(c.bs * c.hl)), dim3(256),
+                         attn_lds_bytes(772, c.max_seq, c.d), (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache,
+                         (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.d, c.max_seq, c.scale);
       return launch_status();
     });
   });
 }
 
-// (KV8: the dg_rope_attn_split_mx8 entry points -- mx8 caches with their exponent bytes; always rope_attn_split_kernel, any nsplit >= 1)
-template <bool SEQ, bool KV8 = false>
-int rope_attn_split_launch(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                           void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                           float scale, int nsplit, int dtype, int device, tg_stream_t stream, void* k_exp = nullptr, void* v_exp = nullptr) {
-  if (!qkv || !cos || !sin || !pos || !k_cache || !v_cache || !out || !scratch || (KV8 && (!k_exp || !v_exp))) return TG_E_NULL;
-  if (!(dtype == TG_BF16 || dtype == TG_F16)) return TG_E_DTYPE;
-  if (bs <= 0 || hl <= 0 || kvl <= 0 || hl % kvl != 0 || d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0 ||
-      max_seq <= 0 || max_seq > 65536 || bs * hl > INT32_MAX || nsplit < 1 || nsplit > 64 || (KV8 && d % 32 != 0))
-    return TG_E_SHAPE;
-  if (scratch_bytes < dg_rope_attn_split_scratch_bytes(bs, hl, d, nsplit)) return TG_E_SHAPE;
-  if (!aligned16(k_cache) || !aligned16(v_cache) || !aligned16(scratch) || !aligned16(k_exp) || !aligned16(v_exp)) return TG_E_ALIGN;
-  DeviceScope ds(device);
-  if (!ds.ok) return TG_E_DEVICE;
-  const int64_t cs = (max_seq + nsplit - 1) / nsplit;
-  const int64_t sc_floats = cs > (256 / (d / 8)) * (int64_t)d ? cs : (256 / (d / 8)) * (int64_t)d;
-  const unsigned lds = (unsigned)((772 + sc_floats) * sizeof(float));
-  int* counters = reinterpret_cast<int*>(scratch);
-  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(scratch) + ((bs * hl * 4 + 15) / 16) * 16);
-  if (!KV8 && (d == 64 || d == 128) && max_seq * d * 2 < ((int64_t)1 << 32) && aligned16(qkv) && aligned16(cos) && aligned16(sin)) {
-    // the one-barrier kernel, split over the sequence (same scratch layout: counters, then [head][chunk][max, sum, d outputs])
-    const unsigned lds1 = (unsigned)(8 * (d + 2) * sizeof(float));
-    const dim3 grid((unsigned)(bs * hl), (unsigned)nsplit);
-    return pick_dt(dtype, [&](auto DT_) {
-      return pick<16, 8>(d / 8, [&](auto LPR_) {  // (d = 128, 64)
-        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, SEQ>), grid, dim3(512), lds1, (hipStream_t)stream, (const uint16_t*)qkv, cos, sin,
-                           pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, hl, kvl, max_seq, scale, (unsigned long long*)nullptr, part, counters);
+// The one-barrier kernel, for a call that check_attn(ATTN_ONLINE) accepts and inside the caller's DeviceScope: nsplit = 1 (no part, no
+// counters) is dg_rope_attn_online, more is the split entry's d = 64 / 128 path (block c of a head takes the 32-row iterations c, c + nsplit, ...)
+int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counters) {
+  const unsigned lds = (unsigned)(8 * (c.d + 2) * sizeof(float));
+  unsigned long long* trace = nullptr;
+#if GEMV_TRACE
+  if (!part) trace = g_attn_trace;
+#endif
+  return pick_dt(c.dtype, [&](auto DT_) {
+    return pick<16, 8>(c.d / 8, [&](auto LPR_) {  // (d = 128, 64)
+      return pick<0, 1>(c.seq, [&](auto SEQ_) {
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value>),
+                           dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
+                           c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters);
         return launch_status();
       });
     });
-  }
+  });
+}
+
+int rope_attn_online_launch(const AttnCall& c) {
+  if (const int rc = check_attn(ATTN_ONLINE, c)) return rc;
+  DeviceScope ds(c.device);
+  if (!ds.ok) return TG_E_DEVICE;
+  return online_kernel_launch(c, 1, nullptr, nullptr);
+}
+
+int rope_attn_split_launch(const AttnCall& c) {
+  if (const int rc = check_attn(ATTN_SPLIT, c)) return rc;
+  DeviceScope ds(c.device);
+  if (!ds.ok) return TG_E_DEVICE;
+  int* counters = reinterpret_cast<int*>(c.scratch);
+  float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.scratch) + split_scratch(c.bs, c.hl, c.d, c.nsplit).part_offset);
+  // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches never do
+  if (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0) return online_kernel_launch(c, c.nsplit, part, counters);
+  const unsigned lds = attn_lds_bytes(772, cdiv(c.max_seq, c.nsplit), c.d);  // the scores of one chunk
   if (lds > 64u * 1024u) return TG_E_SHAPE;
-  Kv8Arg<KV8> X;
-  if constexpr (KV8) { X.k_exp = (uint8_t*)k_exp; X.v_exp = (uint8_t*)v_exp; }
-  auto kern = dtype == TG_BF16 ? rope_attn_split_kernel<BF16, SEQ, KV8> : rope_attn_split_kernel<F16, SEQ, KV8>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)(bs * hl), (unsigned)nsplit), dim3(256), lds, (hipStream_t)stream, (const uint16_t*)qkv,
-                     cos, sin, pos, (uint16_t*)k_cache, (uint16_t*)v_cache, (uint16_t*)out, part, counters, hl, kvl, d, max_seq, scale, X);
-  return launch_status();
+  return pick_dt(c.dtype, [&](auto DT_) {
+    return pick<0, 1>(c.seq, [&](auto SEQ_) {
+      return pick<0, 1>(c.kv8, [&](auto KV8_) {
+        constexpr bool KV8 = decltype(KV8_)::value;
+        Kv8Arg<KV8> X;
+        if constexpr (KV8) { X.k_exp = (uint8_t*)c.k_exp; X.v_exp = (uint8_t*)c.v_exp; }
+        hipLaunchKernelGGL((rope_attn_split_kernel<decltype(DT_), (bool)decltype(SEQ_)::value, KV8>), dim3((unsigned)(c.bs * c.hl), (unsigned)c.nsplit),
+                           dim3(256), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache,
+                           (uint16_t*)c.out, part, counters, c.hl, c.kvl, c.d, c.max_seq, c.scale, X);
+        return launch_status();
+      });
+    });
+  });
 }
 
 }  // namespace
@@ -995,46 +977,48 @@ extern "C" {
 TG_API void tg_dev_attn_trace(unsigned long long* buf) { g_attn_trace = buf; }  // developer builds: [blocks][8] stamps of the last launch
 #endif
 
-#define DG_ATTN_ARGS const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out
-int dg_rope_attn(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+int dg_rope_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out, int64_t bs,
+                 int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream));
 }
-int dg_rope_attn_seq(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+int dg_rope_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out, int64_t bs,
+                     int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream).per_sequence());
 }
-int dg_rope_attn_online(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_online_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
+                        int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream));
 }
-int dg_rope_attn_online_seq(DG_ATTN_ARGS, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_online_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream);
+int dg_rope_attn_online_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
+                            int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream).per_sequence());
 }
-int dg_rope_attn_split(DG_ATTN_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                       int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch<false>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
-                                       dtype, device, stream);
+int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
+                       void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int nsplit,
+                       int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit));
 }
-int dg_rope_attn_split_seq(DG_ATTN_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                           int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch<true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
-                                      dtype, device, stream);
+int dg_rope_attn_split_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
+                           void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int nsplit,
+                           int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).per_sequence());
 }
-#define DG_ATTN8_ARGS const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp, void* v_exp, void* out
-int dg_rope_attn_split_mx8(DG_ATTN8_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                           int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch<false, true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
-                                             dtype, device, stream, k_exp, v_exp);
+int dg_rope_attn_split_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
+                           void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                           float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp));
 }
-int dg_rope_attn_split_mx8_seq(DG_ATTN8_ARGS, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                               int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch<true, true>(qkv, cos, sin, pos, k_cache, v_cache, out, scratch, scratch_bytes, bs, hl, kvl, d, max_seq, scale, nsplit,
-                                            dtype, device, stream, k_exp, v_exp);
+int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
+                               void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                               float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).per_sequence());
 }
-#undef DG_ATTN8_ARGS
-#undef DG_ATTN_ARGS
 
-int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) {
-  return ((bs * hl * 4 + 15) / 16) * 16 + bs * hl * (int64_t)nsplit * (d + 2) * 4;
-}
+int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) { return split_scratch(bs, hl, d, nsplit).bytes; }
 
 int dg_linear16(const void* x, const void* w, void* y, int64_t m, int64_t n, int64_t k, int dtype, int device, tg_stream_t stream) {
   if (!x || !w || !y) return TG_E_NULL;

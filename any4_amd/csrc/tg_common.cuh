@@ -19,6 +19,8 @@
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.
+// attn_call.cuh is the attention side's GemmParams: one attention call of the decode stack (AttnCall, host-only), its validation for all
+// five kinds of entry point (check_attn) and the split kernels' scratch layout (split_scratch); included by decode_glue.cuh and tg_prefill.hip.
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once

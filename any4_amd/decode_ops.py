@@ -106,24 +106,29 @@ def _mx8_exps(what, k_cache, v_cache, k_exp, v_exp, d):
     return (k_exp, v_exp)
 
 
-def _rope_attn(entry, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=()):
+def _attn_launch(base, seq, exps, qkv, **values):
+    """One launch of an attention entry point: _lib.attn_signature names the flavour of `base` (seq: `_seq`; exps = (k_exp, v_exp) of an
+    mx8 cache: `_mx8`) and the order of its arguments; `values` are given by argument name, tensors (or None) for pointers.  qkv also
+    supplies dtype, device and stream."""
+    entry, args = _lib.attn_signature(base, seq, bool(exps))
+    values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
+    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
+    _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
+
+
+def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=()):
     """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
-    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split: its entry points take the scratch buffer (pointer, bytes) behind `out`
-    and nsplit behind the scale.  exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points take them behind v_cache."""
+    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points."""
     scratch, nsplit = split if split is not None else (None, None)
     out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, *exps, out=out)
-    if exps:
-        entry += "_mx8"
+    what = base + ("_mx8" if exps else "")
     if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
-        raise RuntimeError(f"{entry}: out must be [{bs}, {hl * d}] {qkv.dtype}")
+        raise RuntimeError(f"{what}: out must be [{bs}, {hl * d}] {qkv.dtype}")
     if per_sequence:
-        _per_sequence(pos, bs, entry)
-        entry += "_seq"
-    mid, last = ((), ()) if split is None else ((scratch.data_ptr(), scratch.numel() * 4), (nsplit,))
-    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), *[e.data_ptr() for e in exps], out.data_ptr(), *mid, bs, hl, kvl, d, max_seq,
-                                           float(scale), *last,
-                                           _dt(qkv), qkv.device.index, _stream(qkv)), entry)
+        _per_sequence(pos, bs, what)
+    more = {} if split is None else dict(scratch=scratch, scratch_bytes=scratch.numel() * 4, nsplit=nsplit)
+    _attn_launch(base, per_sequence, exps, qkv, cos=cos, sin=sin, pos=pos, k_cache=k_cache, v_cache=v_cache, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
+                 max_seq=max_seq, scale=float(scale), **more)
     return out
 
 
@@ -175,30 +180,22 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split."""
     exps = _mx8_exps("prefill_attn", k_cache, v_cache, k_exp, v_exp, d)
     out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, *exps, out=out)
-    mx8, eptr = "_mx8" if exps else "", [e.data_ptr() for e in exps]
     T = int(T)
     per_sequence = per_sequence or lengths is not None or slots is not None
     if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != k_cache.shape[0] and slots is None):
         raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {k_cache.shape[0]} (the caches'), got {tuple(qkv.shape)}")
     if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"prefill_attn: out must be [{rows}, {hl * d}] {qkv.dtype}")
+    more = {}
     if per_sequence:
         n = rows // T
         _per_sequence(pos, n, "prefill_attn")
         for name, t in (("lengths", lengths), ("slots", slots)):
             if t is not None and (t.dtype != torch.int64 or t.numel() != n):
                 raise RuntimeError(f"prefill_attn: {name} must be int64 with {n} elements (one per sequence)")
-        entry = f"dg_prefill_attn{mx8}_seq"
-        _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(),
-                                               None if lengths is None else lengths.data_ptr(),
-                                               None if slots is None else slots.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(), *eptr,
-                                               out.data_ptr(), n, T, k_cache.shape[0], hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                               qkv.device.index, _stream(qkv)), entry)
-        return out
-    entry = f"dg_prefill_attn{mx8}"
-    _lib.check(getattr(_lib.load(), entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), k_cache.data_ptr(),
-                                           v_cache.data_ptr(), *eptr, out.data_ptr(), rows // T, T, hl, kvl, d, max_seq, float(scale), _dt(qkv),
-                                           qkv.device.index, _stream(qkv)), entry)
+        more = dict(len=lengths, slot=slots, cache_bs=k_cache.shape[0])
+    _attn_launch("dg_prefill_attn", per_sequence, exps, qkv, cos=cos, sin=sin, pos=pos, k_cache=k_cache, v_cache=v_cache, out=out, bs=rows // T, T=T,
+                 hl=hl, kvl=kvl, d=d, max_seq=max_seq, scale=float(scale), **more)
     return out
 
 

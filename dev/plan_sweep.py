@@ -1,6 +1,7 @@
 """What the C ABI answers over a grid of calls, as a digest (developer tool; needs no GPU: the planner and all validation run before any HIP call):
     python dev/plan_sweep.py [--lib PATH/libtinygemm_hip.so] [--quick]     the planner: workspace bytes and kernel family of every case
-    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...]           return codes of N broken structs per entry point
+    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...]           return codes of N broken structs per GEMM entry point, then of
+                                                                           N // 25 broken argument lists per attention entry point (dg_*)
 Prints the number of cases, a histogram of the answers and a sha256 over their sequence.  Two builds route / validate alike when they
 print the same digest for the same script; run it before and after a change of the host launch path (or with --lib on an older build).
 No digest is recorded anywhere: a performance change may move the routing on purpose.
@@ -147,7 +148,61 @@ def errors(n):
         report(name, out)
 
 
+# ---- the attention entry points of include/decode_glue_hip.h: start from a valid argument list, break none, one or two arguments ----
+# Every call names NO_DEVICE, so one that passes validation answers TG_E_DEVICE from DeviceScope (tg_common.cuh: hipGetDevice fails, or
+# hipSetDevice of an index no machine has) in front of everything that touches the GPU.  Any other non-negative answer ends the sweep.
+_I31 = (1 << 31) - 1
+ATTN_BREAKS = {
+    "dtype": (-1, 0, 1, 2),
+    "bs": (0, -1, 1, 2, 3, 65535, 65536, _I31 // 8, _I31 // 8 + 1),           # prefill: grid.y; the others: bs * hl (hl = 8) an int32
+    "T": (0, -1, 1, 16, _I31 // 4, _I31 // 4 + 1),                            # bs * T <= INT32_MAX / 2 at bs = 2
+    "cache_bs": (0, -1, 2, 3, _I31, _I31 + 1),
+    "hl": (0, -1, 1, 6, 7, 8), "kvl": (0, -1, 1, 2, 3, 8),
+    "d": (0, 4, 8, 12, 16, 24, 32, 48, 64, 96, 128, 136, 256, 264),
+    "max_seq": (0, -1, 1, 4096, 8192, 8193, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 25) - 1, 1 << 25),  # ... * d * 2 < 2^32 at d = 128 / 64
+    "nsplit": (0, -1, 1, 4, 64, 65),
+    "scratch_bytes": (0, -1, -4, 16),                                          # relative to what the (broken) sizes need
+}
+
+
+def attn_valid(names):
+    v = dict(bs=2, T=16, cache_bs=2, hl=8, kvl=2, d=128, max_seq=4096, scale=0.125, nsplit=4, dtype=0, device=NO_DEVICE, stream=None, scratch_bytes=0)
+    v.update((name, (i + 1) * BASE) for i, name in enumerate(n for n in names if n not in v))  # the pointers
+    return v
+
+
+def attn_errors(n):
+    decode_attn = ("dg_decode_attn", tuple((name, None) for name in ("qkv", "k_cache", "v_cache", "pos", "out", "bs", "hl", "kvl", "d", "max_seq", "scale",
+                                                                      "dtype", "device", "stream")))
+    entries = [decode_attn] + [L.attn_signature(base, seq, mx8) for base, has_mx8 in L.ATTN_BASES.items() for seq in (False, True)
+                               for mx8 in ((False, True) if has_mx8 else (False,))]
+    for e, (entry, args) in enumerate(entries):
+        names = [name for name, _ in args]
+        fn = getattr(lib, entry)
+        fn.argtypes = L.SYMBOLS[entry]
+        pointers = [name for name in attn_valid(names) if name not in ATTN_BREAKS and name not in ("scale", "device", "stream")]
+        fields = sorted(set(names) & set(ATTN_BREAKS)) + pointers
+        rng = random.Random(1000 * opt.seed + 100 + e)
+        out = array("q")
+        for _ in range(n):
+            v = attn_valid(names)
+            slack = 0
+            for f in rng.sample(fields, rng.choice((0, 1, 2))):
+                if f == "scratch_bytes":
+                    slack = rng.choice(ATTN_BREAKS[f])
+                else:
+                    v[f] = rng.choice(ATTN_BREAKS[f]) if f in ATTN_BREAKS else rng.choice((None, v[f] + 4, v[f] + 8, v[f]))
+            heads = v["bs"] * v["hl"]
+            v["scratch_bytes"] = max(-(1 << 62), min(1 << 62, (heads * 4 + 15) // 16 * 16 + heads * v["nsplit"] * (v["d"] + 2) * 4 + slack))
+            rc = fn(*[v[name] for name in names])
+            if rc >= 0:
+                sys.exit(f"{entry}: answer {rc} to {v}: a call of this sweep got past DeviceScope")
+            out.append(rc)
+        report(entry, out)
+
+
 if opt.errors:
     errors(opt.errors)
+    attn_errors(max(1, opt.errors // 25))
 else:
     planner()

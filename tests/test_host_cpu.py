@@ -33,6 +33,33 @@ def test_c_abi_exports_every_declared_symbol():
     assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 8
 
 
+def test_attention_signatures_are_the_headers_prototypes():
+    """_lib.attn_signature builds the twelve fused attention argument lists from named pieces, and decode_ops places a call's values by
+    those names: name for name and type for type they are the prototypes of include/decode_glue_hip.h."""
+    from any4_amd import _lib
+
+    header = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
+    ctype = {"int64_t": _lib._i64, "int": ctypes.c_int, "float": ctypes.c_float, "tg_stream_t": _lib._vp}
+    seen = set()
+    for base, has_mx8 in _lib.ATTN_BASES.items():
+        for seq in (False, True):
+            for mx8 in (False, True) if has_mx8 else (False,):
+                entry, args = _lib.attn_signature(base, seq, mx8)
+                m = re.search(r"TG_API int " + entry + r"\(([^;]*)\);", header)
+                assert m, entry
+                declared = []
+                for param in m.group(1).replace("\n", " ").split(","):
+                    kind, name = param.strip().rsplit(" ", 1)
+                    declared.append(("bs" if name == "n" else name, _lib._vp if kind.endswith("*") else ctype[kind]))
+                assert list(args) == declared, entry
+                assert _lib.SYMBOLS[entry] == [t for _, t in declared], entry
+                seen.add(entry)
+        if not has_mx8:
+            with pytest.raises(KeyError):
+                _lib.attn_signature(base, False, True)
+    assert len(seen) == 12 and seen == {s for s in _lib.SYMBOLS if s.startswith(("dg_rope_attn", "dg_prefill_attn")) and not s.endswith("_bytes")}
+
+
 def test_peer_gather_preconditions_fail_before_any_launch():
     """include/peer_gather_hip.h: argument validation of the one-shot gather returns TG_E_* without touching HIP."""
     from any4_amd import _lib
