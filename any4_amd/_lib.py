@@ -66,13 +66,17 @@ class PeerGather(ctypes.Structure):
 
 
 # The twelve fused attention entry points of include/decode_glue_hip.h: four bases, each with a `_seq` flavour (a position per sequence), two of
-# them with `_mx8` ones (an mx8 KV cache).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
+# them with `_mx8` ones (an mx8 KV cache) -- and, bound as a group of their own (PAGED_SYMBOLS; the header declares them DG_PAGED_API), the
+# `_paged` flavour of three bases (a page pool behind a block table; per sequence, 16-bit rows).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
 # puts a call's values in the same order.
 _ci, _cf = ctypes.c_int, ctypes.c_float
 ATTN_BASES = {"dg_rope_attn": False, "dg_rope_attn_online": False, "dg_rope_attn_split": True, "dg_prefill_attn": True}  # base: has _mx8 flavours
 _ATTN_HEAD = [("qkv", _vp), ("cos", _vp), ("sin", _vp), ("pos", _vp)]
 _ATTN_LEN_SLOT = [("len", _vp), ("slot", _vp)]                      # dg_prefill_attn*_seq
 _ATTN_CACHES = [("k_cache", _vp), ("v_cache", _vp)]
+_ATTN_POOLS = [("table", _vp), ("k_pool", _vp), ("v_pool", _vp)]   # *_paged
+_ATTN_PAGES = [("page_size", _i64), ("num_pages", _i64)]            # *_paged, behind max_seq
+ATTN_PAGED_BASES = ("dg_rope_attn_online", "dg_rope_attn_split", "dg_prefill_attn")
 _ATTN_EXPS = [("k_exp", _vp), ("v_exp", _vp)]                       # *_mx8*
 _ATTN_SCRATCH = [("scratch", _vp), ("scratch_bytes", _i64)]         # dg_rope_attn_split*
 _ATTN_SHAPE = [("hl", _ci), ("kvl", _ci), ("d", _ci), ("max_seq", _i64), ("scale", _cf)]
@@ -80,15 +84,17 @@ _ATTN_TAIL = [("dtype", _ci), ("device", _ci), ("stream", _vp)]
 
 
 @functools.lru_cache(maxsize=None)
-def attn_signature(base, seq=False, mx8=False):
-    """(entry point, ((argument name, ctype), ...)) of one flavour of an attention base"""
-    if base not in ATTN_BASES or (mx8 and not ATTN_BASES[base]):
-        raise KeyError(f"no attention entry point {base}{'_mx8' if mx8 else ''}")
+def attn_signature(base, seq=False, mx8=False, paged=False):
+    """(entry point, ((argument name, ctype), ...)) of one flavour of an attention base (paged: the `_paged` one, which is per sequence)"""
+    if base not in ATTN_BASES or (mx8 and not ATTN_BASES[base]) or (paged and (mx8 or base not in ATTN_PAGED_BASES)):
+        raise KeyError(f"no attention entry point {base}{'_mx8' if mx8 else ''}{'_paged' if paged else ''}")
+    seq = seq or paged
     prefill, split = base == "dg_prefill_attn", base == "dg_rope_attn_split"
-    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill and seq else []) + _ATTN_CACHES + (_ATTN_EXPS if mx8 else []) + [("out", _vp)]
-            + (_ATTN_SCRATCH if split else []) + [("bs", _i64)] + ([("T", _i64)] if prefill else []) + ([("cache_bs", _i64)] if prefill and seq else [])
-            + _ATTN_SHAPE + ([("nsplit", _ci)] if split else []) + _ATTN_TAIL)
-    return base + ("_mx8" if mx8 else "") + ("_seq" if seq else ""), tuple(args)
+    shape = _ATTN_SHAPE[:4] + _ATTN_PAGES + _ATTN_SHAPE[4:] if paged else _ATTN_SHAPE
+    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill and seq else []) + (_ATTN_POOLS if paged else _ATTN_CACHES) + (_ATTN_EXPS if mx8 else [])
+            + [("out", _vp)] + (_ATTN_SCRATCH if split else []) + [("bs", _i64)] + ([("T", _i64)] if prefill else [])
+            + ([("cache_bs", _i64)] if prefill and seq else []) + shape + ([("nsplit", _ci)] if split else []) + _ATTN_TAIL)
+    return base + ("_paged" if paged else ("_mx8" if mx8 else "") + ("_seq" if seq else "")), tuple(args)
 
 
 # name -> argtypes, exactly the prototypes of include/tinygemm_hip.h
@@ -140,6 +146,11 @@ for _base, _has_mx8 in ATTN_BASES.items():
         for _mx8 in (False, True) if _has_mx8 else (False,):
             _name, _args = attn_signature(_base, _seq, _mx8)
             SYMBOLS[_name] = [t for _, t in _args]
+# name -> argtypes of the paged attention entry points (the DG_PAGED_API prototypes of include/decode_glue_hip.h); load() binds them too
+PAGED_SYMBOLS = {}
+for _base in ATTN_PAGED_BASES:
+    _name, _args = attn_signature(_base, paged=True)
+    PAGED_SYMBOLS[_name] = [t for _, t in _args]
 
 _lib = None
 
@@ -155,7 +166,7 @@ def load() -> ctypes.CDLL:
             "There is no CPU/PyTorch fallback for the tinygemm ops."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in SYMBOLS.items():
+    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # a stale build: the header declares a symbol the .so does not export

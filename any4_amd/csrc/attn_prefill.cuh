@@ -28,9 +28,15 @@
 // SEQ (dg_prefill_attn_seq): position, length and cache slot are per sequence, read by every workgroup: p0 = pos[i], T_i = min(len[i], T)
 // decides which tokens exist (the padded T stays in the row addressing and sizes the grid), the cache base is slot[i]'s.  A sequence
 // with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
+//
+// PAGED (dg_prefill_attn_paged; implies SEQ, 16-bit rows): the caches are pools [num_pages][kvl][page_size][D] behind a block table
+// (kv_paged.cuh) whose row is slot[i]'s.  A 64-position tile lies in one page (page_size >= 64), so the staging pass takes the tile's base
+// from its page -- one scalar table read per tile, made when the tile's loads are issued, i.e. one tile ahead of its use -- and the rows
+// stay tile-relative; the append drops a row whose own table entry is outside the pool.  Everything else is the SEQ flavour's.
 #pragma once
 #include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 #include "kv8.cuh"         // the mx8 cache format (KV8 flavours)
+#include "kv_paged.cuh"    // the paged cache (PAGED flavours)
 
 struct PrefillParams {
   const uint16_t* qkv;
@@ -81,8 +87,9 @@ __device__ __forceinline__ bool pf_seq(const PrefillParams& P, const PrefillSeq&
 }
 
 // ---- rope + cache append: block = one token of one sequence; a thread walks (kv head, rotation pair) items, k first, then v ----
-template <typename DT, bool SEQ = false, bool KV8 = false>
-__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X) {
+template <typename DT, bool SEQ = false, bool KV8 = false, bool PAGED = false>
+__global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X, PagedArg<PAGED> G) {
+  static_assert(!PAGED || (SEQ && !KV8), "a paged cache has a position per sequence and 16-bit rows");
   const int t = blockIdx.x, b = blockIdx.y, d2 = d >> 1;
   int cb = b;  // the sequence's cache slot
   int64_t pos;
@@ -127,11 +134,18 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
     return;
   }
   // (16-bit caches from here on)
+  [[maybe_unused]] int page = 0;
+  if constexpr (PAGED) {  // (block-uniform) the row's own page; an entry outside the pool: nothing is written
+    page = kv_page_write(G, cb, (int)pos);
+    if (page < 0) return;
+  }
   for (int i = threadIdx.x; i < 2 * per; i += 256) {
     const bool isv = i >= per;
     const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
     const uint16_t* src = row + (int64_t)(P.hl + (isv ? P.kvl : 0) + kv) * d;
-    uint16_t* dst = (isv ? P.v_cache : P.k_cache) + (((int64_t)cb * P.kvl + kv) * P.max_seq + pos) * d;
+    uint16_t* dst;
+    if constexpr (PAGED) dst = (isv ? P.v_cache : P.k_cache) + kv_page_base(G, page, P.kvl, kv, d) + (pos & ((1 << G.page_shift) - 1)) * d;
+    else dst = (isv ? P.v_cache : P.k_cache) + (((int64_t)cb * P.kvl + kv) * P.max_seq + pos) * d;
     if (isv) {
       dst[j] = src[j];
       dst[j + d2] = src[j + d2];
@@ -154,8 +168,9 @@ __device__ __forceinline__ int pf_swz_v(int d, int chunk) { return chunk ^ (((d 
 
 constexpr int PF_NU = 2;  // 16-row units per wave: 2 x (O 4 D/16 + q D/8 + S 16) registers leave room for two workgroups per CU; 4 spill at D = 128
 
-template <typename DT, int D, int RG, bool SEQ = false, bool KV8 = false>
-__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X) {
+template <typename DT, int D, int RG, bool SEQ = false, bool KV8 = false, bool PAGED = false>
+__global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X, PagedArg<PAGED> G) {
+  static_assert(!PAGED || (SEQ && !KV8), "a paged cache has a position per sequence and 16-bit rows");
   constexpr int KD = D / 32;        // k-steps of the score product
   constexpr int DB = D / 16;        // 16-column blocks of the output
   constexpr int NU = PF_NU;         // 16-row units per wave
@@ -236,8 +251,9 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
     }
   }
 
-  const char* Kg = reinterpret_cast<const char*>(P.k_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
-  const char* Vg = reinterpret_cast<const char*>(P.v_cache + ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D);
+  // (PAGED: the pools' first byte; stage_load adds the tile's page)
+  const char* Kg = reinterpret_cast<const char*>(P.k_cache + (PAGED ? (int64_t)0 : ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D));
+  const char* Vg = reinterpret_cast<const char*>(P.v_cache + (PAGED ? (int64_t)0 : ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D));
   const int64_t head0 = ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq;  // (KV8) first cache row of this (slot, kv head): D bytes of codes per row
 
   // ---- staging: K as 16-byte chunks (row, chunk); V as four consecutive positions 4 sg ... 4 sg + 3 of one 8-column chunk c
@@ -275,18 +291,22 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
         }
       }
     } else {
+      // first byte of the tile's row 0 behind Kg / Vg (PAGED: in the tile's page, s0 <= p_hi < max_seq; workgroup-uniform)
+      [[maybe_unused]] int64_t t0 = 0;
+      if constexpr (PAGED)
+        t0 = (kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, cb, s0)), P.kvl, kv, D) + (int64_t)(s0 & ((1 << G.page_shift) - 1)) * D) * 2;
 #pragma unroll
       for (int i = 0; i < NCK; ++i) {
         const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
         kreg[i] = u32x4{0u, 0u, 0u, 0u};
-        if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(Kg + (int64_t)(s0 + row) * (D * 2) + ch * 16);
+        if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(PAGED ? Kg + t0 + row * (D * 2) + ch * 16 : Kg + (int64_t)(s0 + row) * (D * 2) + ch * 16);
       }
       if (vsg < 16) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int row = 4 * vsg + i;
           vreg[i] = u32x4{0u, 0u, 0u, 0u};
-          if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(Vg + (int64_t)(s0 + row) * (D * 2) + vc * 16);
+          if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(PAGED ? Vg + t0 + row * (D * 2) + vc * 16 : Vg + (int64_t)(s0 + row) * (D * 2) + vc * 16);
         }
       }
     }

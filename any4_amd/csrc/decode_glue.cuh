@@ -10,6 +10,7 @@
 
 namespace {
 #include "kv8.cuh"
+#include "kv_paged.cuh"
 
 // all threads of a 256-thread block get the reduction; `scratch` holds >= 4 floats and is reusable afterwards
 template <bool MAX>
@@ -554,12 +555,23 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 //                as dg_rope_attn_split: the same result within 16-bit rounding); the 32 (64) groups meet ONCE in LDS.
 //   RoPE         rotate_half pairs (j, j + d/2) sit d/16 lanes apart in the row: one lane exchange per value; the same products
 //                and roundings as rope_kv_kernel (the cache rows written are bit-identical to it).
-template <typename DT, int LPR, bool SEQ = false>
+// PAGED (the dg_rope_attn_*_paged entry points; implies SEQ): k_cache / v_cache are pools [num_pages][kvl][page_size][D] behind the block
+// table G (kv_paged.cuh).  An RPI-row iteration lies in one page (page_size >= 64 >= RPI), so only its base changes: the page id is a
+// scalar read, the rows are page-relative.  The table entries of the speculative iterations do not depend on the position: they are
+// requested beside pos[b], in front of the speculative K / V requests.  Rows past the end re-read the iteration's own first row (the
+// contiguous flavours re-read position 0, which may sit in another page); they are masked either way, so every sum is the SEQ flavour's.
+// The paging argument is the kernel's last parameter and exists only for PAGED (PG = KvPages): this kernel reads gridDim from the implicit
+// arguments BEHIND the explicit ones, and even an empty trailing struct moves those by eight bytes -- the contiguous flavours would keep
+// their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
+template <typename DT, int LPR, bool SEQ = false, bool PAGED = false, typename... PG>
 __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                                const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                                uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                                uint16_t* __restrict__ out, int hl, int kvl, int64_t max_seq, float scale,
-                                                               unsigned long long* trace, float* part, int* counters) {
+                                                               unsigned long long* trace, float* part, int* counters, PG... pages) {
+  static_assert(sizeof...(PG) == (PAGED ? 1 : 0) && (!PAGED || SEQ), "PAGED: one KvPages argument, a position per sequence");
+  [[maybe_unused]] KvPages G{};
+  if constexpr (PAGED) G = kv_pages_arg(pages...);
   // gridDim.y = NS > 1: split over the sequence.  Block (head, c) takes the 32-row iterations c, c + NS, c + 2 NS, ... of the context
   // (a partition that does not depend on the position: the speculative requests below stay possible), writes its (max, sum,
   // unnormalised output) to `part`, and the last block of a head to arrive (self-resetting counter: replayable in a graph) combines
@@ -582,8 +594,20 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const int kv = h / rep;
   const uint16_t* row = qkv + (int64_t)b * (hl + 2 * kvl) * D;
   // (row r, piece i) of this head's K / V at byte ((r * LPR + i) << 4): a 32-bit offset on a scalar base (host: max_seq * d * 2 < 4 GiB)
-  const char* K = reinterpret_cast<const char*>(k_cache + ((int64_t)b * kvl + kv) * max_seq * D);
-  const char* V = reinterpret_cast<const char*>(v_cache + ((int64_t)b * kvl + kv) * max_seq * D);
+  // (PAGED: the pools' first byte; an iteration adds its page's base, page_bytes)
+  const char* K = reinterpret_cast<const char*>(k_cache + (PAGED ? (int64_t)0 : ((int64_t)b * kvl + kv) * max_seq * D));
+  const char* V = reinterpret_cast<const char*>(v_cache + (PAGED ? (int64_t)0 : ((int64_t)b * kvl + kv) * max_seq * D));
+  [[maybe_unused]] int64_t pos_early = 0;
+  [[maybe_unused]] int in_page = 0;  // PAGED: page_size - 1
+  if constexpr (PAGED) {
+    pos_early = pos_p[DG_SEQ_INDEX(b)];
+    in_page = (1 << G.page_shift) - 1;
+  }
+  // PAGED: byte offset of (the page of logical row r0 < max_seq, this kv head) in a pool -- wave-uniform
+  [[maybe_unused]] auto page_bytes = [&](int r0) -> int64_t {
+    if constexpr (PAGED) return kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, b, r0)), kvl, kv, D) * 2;
+    else return 0;
+  };
   auto piece = [&](const char* base, int r) -> u32x4 { return *reinterpret_cast<const u32x4*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 4)); };
   // the first NSPEC iterations' rows are requested BEFORE the position is known (rows past it are valid memory and masked later):
   // the read of `pos` is a dependent round trip the K / V requests of a short context need not wait for
@@ -597,11 +621,18 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   u32x4 kk[NI], vv[NI];
 #pragma unroll
   for (int it = 0; it < NSPEC; ++it) {
-    const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
-    kk[it] = piece(K, rc);
-    vv[it] = piece(V, rc);
+    if constexpr (PAGED) {  // (an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
+      const int r0 = min(row0_of(it), (int)max_seq - RPI);
+      const int64_t pb = page_bytes(r0);
+      kk[it] = piece(K + pb, (r0 & in_page) + grp);
+      vv[it] = piece(V + pb, (r0 & in_page) + grp);
+    } else {
+      const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
+      kk[it] = piece(K, rc);
+      vv[it] = piece(V, rc);
+    }
   }
-  const int64_t pos = SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;
+  const int64_t pos = PAGED ? pos_early : SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check)
   const int S = (int)pos + 1;
   TG_STAMP(1);
@@ -616,9 +647,17 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     for (int it = 0; it < NI; ++it) {
       if (it < first || row0_of(base / RPI + it) >= S) continue;  // (wave-uniform) iterations past the last position request nothing
       const int r = row0_of(base / RPI + it) + grp;
-      const int rc = r < S - 1 ? r : 0;
-      kk[it] = piece(K, rc);
-      vv[it] = piece(V, rc);
+      if constexpr (PAGED) {  // (row0 < S <= max_seq)
+        const int r0 = row0_of(base / RPI + it);
+        const int64_t pb = page_bytes(r0);
+        const int rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
+        kk[it] = piece(K + pb, rc);
+        vv[it] = piece(V + pb, rc);
+      } else {
+        const int rc = r < S - 1 ? r : 0;
+        kk[it] = piece(K, rc);
+        vv[it] = piece(V, rc);
+      }
     }
   };
   request(0, NSPEC);
@@ -648,8 +687,17 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const u32x4 qp = rotate(qraw), kn = rotate(kraw);
   TG_STAMP(3);
   if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
-    reinterpret_cast<u32x4*>(k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = kn;
-    reinterpret_cast<u32x4*>(v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = vraw;
+    if constexpr (PAGED) {  // (a position whose own table entry is outside the pool writes nothing)
+      const int pg = kv_page_write(G, b, (int)pos);
+      if (pg >= 0) {
+        const int64_t e = kv_page_base(G, pg, kvl, kv, D) + (int64_t)((int)pos & in_page) * D;
+        reinterpret_cast<u32x4*>(k_cache + e)[i] = kn;
+        reinterpret_cast<u32x4*>(v_cache + e)[i] = vraw;
+      }
+    } else {
+      reinterpret_cast<u32x4*>(k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = kn;
+      reinterpret_cast<u32x4*>(v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = vraw;
+    }
   }
   auto dpp_add = [](float v, auto ctrl) -> float {
     return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), decltype(ctrl)::value, 0xf, 0xf, true));
@@ -927,6 +975,13 @@ int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counte
 #endif
   return pick_dt(c.dtype, [&](auto DT_) {
     return pick<16, 8>(c.d / 8, [&](auto LPR_) {  // (d = 128, 64)
+      if (c.paging) {  // (pools behind a block table: always a position per sequence)
+        const KvPages G = kv_pages(c);
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, true, true, KvPages>), dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit),
+                           dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache,
+                           (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, G);
+        return launch_status();
+      }
       return pick<0, 1>(c.seq, [&](auto SEQ_) {
         hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value>),
                            dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
@@ -951,7 +1006,9 @@ int rope_attn_split_launch(const AttnCall& c) {
   int* counters = reinterpret_cast<int*>(c.scratch);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.scratch) + split_scratch(c.bs, c.hl, c.d, c.nsplit).part_offset);
   // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches never do
+  // (a paged call always: check_attn holds it to that kernel's d and alignment, there is no paged 256-thread kernel)
   if (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0) return online_kernel_launch(c, c.nsplit, part, counters);
+  if (c.paging) return TG_E_SHAPE;
   const unsigned lds = attn_lds_bytes(772, cdiv(c.max_seq, c.nsplit), c.d);  // the scores of one chunk
   if (lds > 64u * 1024u) return TG_E_SHAPE;
   return pick_dt(c.dtype, [&](auto DT_) {
@@ -1016,6 +1073,19 @@ int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* s
                                float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
   return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
                                     .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).per_sequence());
+}
+
+int dg_rope_attn_online_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
+                              void* v_pool, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages,
+                              float scale, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                     .paged(table, page_size, num_pages));
+}
+int dg_rope_attn_split_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
+                             void* v_pool, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                             int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).paged(table, page_size, num_pages));
 }
 
 int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) { return split_scratch(bs, hl, d, nsplit).bytes; }

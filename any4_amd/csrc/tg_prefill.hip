@@ -4,9 +4,9 @@
 namespace {
 #include "attn_prefill.cuh"
 
-template <typename DT, int D, int RG, bool SEQ, bool KV8>
-int go(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, hipStream_t st) {
-  constexpr auto kern = prefill_attn_kernel<DT, D, RG, SEQ, KV8>;
+template <typename DT, int D, int RG, bool SEQ, bool KV8, bool PAGED = false>
+int go(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, const KvPages& pages, hipStream_t st) {
+  constexpr auto kern = prefill_attn_kernel<DT, D, RG, SEQ, KV8, PAGED>;
   const int prc = prepare_lds_kernel<kern>();
   if (prc != 0) return prc;
   constexpr int BQ = 16 * 4 * PF_NU / RG;
@@ -19,20 +19,22 @@ int go(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, hipStream_t st) 
   if constexpr (SEQ) static_cast<PrefillSeq&>(Q) = S;
   Kv8Arg<KV8> X;
   if constexpr (KV8) static_cast<Kv8Exps&>(X) = E;
-  hipLaunchKernelGGL((prefill_rope_kv_kernel<DT, SEQ, KV8>), dim3((unsigned)P.T, (unsigned)P.bs), dim3(256), 0, st, P, D, Q, X);
-  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 2 * (64 * D * 2 + D * 128), st, P, Q, X);
+  PagedArg<PAGED> G;
+  if constexpr (PAGED) static_cast<KvPages&>(G) = pages;
+  hipLaunchKernelGGL((prefill_rope_kv_kernel<DT, SEQ, KV8, PAGED>), dim3((unsigned)P.T, (unsigned)P.bs), dim3(256), 0, st, P, D, Q, X, G);
+  hipLaunchKernelGGL(kern, dim3((unsigned)blocks), dim3(256), 2 * (64 * D * 2 + D * 128), st, P, Q, X, G);
   return launch_status();
 }
-template <typename DT, int D, bool SEQ, bool KV8>
-int go_rg(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, hipStream_t st) {
+template <typename DT, int D, bool SEQ, bool KV8, bool PAGED = false>
+int go_rg(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, const KvPages& pages, hipStream_t st) {
   const int rep = P.hl / P.kvl;  // query heads per kv head: 4 of them share a workgroup's K / V tiles (2 / 1 when there are no more)
-  if (rep == 1) return go<DT, D, 1, SEQ, KV8>(P, S, E, st);
-  if (rep == 2) return go<DT, D, 2, SEQ, KV8>(P, S, E, st);
-  return go<DT, D, 4, SEQ, KV8>(P, S, E, st);
+  if (rep == 1) return go<DT, D, 1, SEQ, KV8, PAGED>(P, S, E, pages, st);
+  if (rep == 2) return go<DT, D, 2, SEQ, KV8, PAGED>(P, S, E, pages, st);
+  return go<DT, D, 4, SEQ, KV8, PAGED>(P, S, E, pages, st);
 }
 
-// The four entry points behind one validation (check_attn).  c.seq: `len` / `slot` / cache_bs per sequence (otherwise null, null, bs);
-// c.kv8: mx8 caches, `k_exp` / `v_exp` their exponent bytes.
+// The five entry points behind one validation (check_attn).  c.seq: `len` / `slot` / cache_bs per sequence (otherwise null, null, bs);
+// c.kv8: mx8 caches, `k_exp` / `v_exp` their exponent bytes; c.paging: pools behind a block table (per sequence, 16-bit rows).
 int prefill_launch(const AttnCall& c) {
   if (const int rc = check_attn(ATTN_PREFILL, c)) return rc;
   DeviceScope ds(c.device);
@@ -43,12 +45,14 @@ int prefill_launch(const AttnCall& c) {
   P.bs = (int32_t)c.bs; P.T = (int32_t)c.T; P.hl = c.hl; P.kvl = c.kvl; P.max_seq = (int32_t)c.max_seq; P.scale = c.scale;
   const PrefillSeq S{c.len, c.slot, (int32_t)c.cache_bs};
   const Kv8Exps E{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
+  const KvPages pages = c.paging ? kv_pages(c) : KvPages{};
   hipStream_t st = (hipStream_t)c.stream;
   return pick_dt(c.dtype, [&](auto DT_) {
     return pick<128, 64>(c.d, [&](auto D_) {
+      if (c.paging) return go_rg<decltype(DT_), decltype(D_)::value, true, false, true>(P, S, E, pages, st);
       return pick<0, 1>(c.seq, [&](auto SEQ_) {
         return pick<0, 1>(c.kv8, [&](auto KV8_) {
-          return go_rg<decltype(DT_), decltype(D_)::value, (bool)decltype(SEQ_)::value, (bool)decltype(KV8_)::value>(P, S, E, st);
+          return go_rg<decltype(DT_), decltype(D_)::value, (bool)decltype(SEQ_)::value, (bool)decltype(KV8_)::value>(P, S, E, pages, st);
         });
       });
     });
@@ -83,4 +87,12 @@ extern "C" int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const 
                                        tg_stream_t stream) {
   return prefill_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, n, hl, kvl, d, max_seq, scale, dtype, device, stream)
                             .chunk(T).slots(len, slot, cache_bs).mx8(k_exp, v_exp));
+}
+
+extern "C" int dg_prefill_attn_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                                     const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* out, int64_t n, int64_t T,
+                                     int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale,
+                                     int dtype, int device, tg_stream_t stream) {
+  return prefill_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, n, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                            .chunk(T).slots(len, slot, cache_bs).paged(table, page_size, num_pages));
 }

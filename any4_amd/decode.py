@@ -33,6 +33,7 @@ Launch structure, chosen for the hardware rather than copied from HF:
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import operator
 import os
@@ -43,7 +44,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from .kvcache import F8, mx8_decode, mx8_encode
+from .kvcache import F8, PagePool, mx8_decode, mx8_encode
 
 
 @dataclass
@@ -255,6 +256,19 @@ def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots
     return ctx.view(n * T, hl * d)
 
 
+def check_page_size(cfg: DecodeConfig, kv_pages, page_size, kv_cache=None) -> None:
+    """The rule of a paged cache (include/decode_glue_hip.h): a page is a power of two of at least 64 positions, max_seq whole pages."""
+    if kv_pages is None:
+        return
+    if kv_cache == "mx8":
+        raise ValueError("kv_pages with kv_cache='mx8': paged mx8 pools are not built yet")
+    ps = operator.index(page_size)
+    if operator.index(kv_pages) < 1:
+        raise ValueError(f"kv_pages must be at least 1, got {kv_pages}")
+    if ps < 64 or ps & (ps - 1) or ps > cfg.max_seq or cfg.max_seq % ps:
+        raise ValueError(f"page_size must be a power of two with 64 <= page_size <= max_seq = {cfg.max_seq} and max_seq % page_size == 0, got {ps}")
+
+
 def _scatter_rows(cache, pos, active, new):
     """cache[b, :, pos[b], :] = new[b] for the active sequences b, with `pos` [bs] (clamped into the cache) and `active` [bs] on the
     device: an inactive sequence gets its own row back, so nothing is read on the host and nothing of it changes."""
@@ -264,10 +278,13 @@ def _scatter_rows(cache, pos, active, new):
 
 class DecodeLayer(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int,
-                 kv_cache: Optional[str] = None):
+                 kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64):
         """kv_cache: None = k / v rows in the layer's dtype; "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py): float8_e4m3fn codes
-        in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache)."""
+        in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache).
+        kv_pages: a paged cache -- `k_pool` / `v_pool` [kv_pages, kvl, page_size, d] in place of the caches (which are None), addressed
+        through `block_table` int32 [bs, max_seq / page_size], the stack's (it is shared by all layers and set by the stack)."""
         super().__init__()
+        check_page_size(cfg, kv_pages, page_size, kv_cache)
         if kv_cache not in (None, "mx8"):
             raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
         if kv_cache == "mx8" and cfg.head_dim % 32:
@@ -284,7 +301,12 @@ class DecodeLayer(torch.nn.Module):
         self.down = factory("down", idx, cfg.inter, cfg.hidden // world)
         self.norm1 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.norm2 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
-        if kv_cache == "mx8":
+        self.block_table = None
+        if kv_pages is not None:
+            for name in ("k", "v"):
+                self.register_buffer(name + "_pool", torch.zeros(kv_pages, self.kvl, page_size, d, device=device, dtype=dtype), persistent=False)
+            self.k_cache = self.v_cache = self.k_exp = self.v_exp = None
+        elif kv_cache == "mx8":
             for name in ("k", "v"):
                 self.register_buffer(name + "_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=torch.uint8).view(F8),
                                      persistent=False)
@@ -335,13 +357,49 @@ class DecodeLayer(torch.nn.Module):
     def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather):
         """`forward` with a position per sequence: `pos` int64 [bs] on the device.  Sequence b takes rope row pos[b], writes cache row
         pos[b] and sees rows <= pos[b]; one whose position is outside [0, max_seq) is inactive: its caches keep their bits (its row of
-        the result is unspecified).  No value is read on the host."""
+        the result is unspecified).  No value is read on the host.
+        A paged layer runs the same formulation on a contiguous view gathered through the block table and puts the written rows back
+        into the pools (`_paged_view`; that path does read a mask on the host)."""
         d, bs = self.cfg.head_dim, h.shape[0]
         active = (pos >= 0) & (pos < self.cfg.max_seq)
         pc = pos.clamp(0, self.cfg.max_seq - 1)
         cos, sin = cos_tab.index_select(0, pc).view(bs, 1, d), sin_tab.index_select(0, pc).view(bs, 1, d)
-        return self._token_torch(h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
-                                 arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
+        with self._paged_view() as put:
+            out = self._token_torch(h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
+                                    arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
+            if self.block_table is not None:
+                put(torch.arange(bs, device=pos.device)[active], pc[active])
+        return out
+
+    @contextlib.contextmanager
+    def _paged_view(self):
+        """The plain-torch twin of a paged layer (what the paged kernels are tested against, not a product): inside the block `k_cache`
+        / `v_cache` are [bs, kvl, max_seq, d] copies gathered through the table, with entries outside the pool clamped to page 0 as the
+        kernels clamp them, so that the contiguous formulation runs unchanged; `put(slots, positions)` (two int64 tensors of one length)
+        copies those rows of the view back into the pools, dropping a row whose own table entry is outside the pool.  A layer without
+        pools: nothing happens."""
+        if self.block_table is None:
+            yield lambda slots, positions: None
+            return
+        n, _, ps, d = self.k_pool.shape
+        tab = self.block_table.long()
+        valid = (tab >= 0) & (tab < n)
+        idx = torch.where(valid, tab, torch.zeros_like(tab))
+        bs = tab.shape[0]
+        for name, pool in (("k_cache", self.k_pool), ("v_cache", self.v_pool)):
+            setattr(self, name, pool[idx].permute(0, 2, 1, 3, 4).reshape(bs, self.kvl, self.cfg.max_seq, d))
+
+        def put(slots, positions):
+            ok = valid[slots, positions // ps]
+            slots, positions = slots[ok], positions[ok]
+            pages = tab[slots, positions // ps]
+            for view, pool in ((self.k_cache, self.k_pool), (self.v_cache, self.v_pool)):
+                pool[pages, :, positions % ps] = view[slots, :, positions]
+
+        try:
+            yield put
+        finally:
+            self.k_cache = self.v_cache = None
 
     def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
         """Plain torch, a chunk of tokens per sequence: `h` [n * T, hidden] (row i * T + t), rows padded to the common T.  Host ints
@@ -349,8 +407,12 @@ class DecodeLayer(torch.nn.Module):
         are appended to its caches and every token attends causally over cache + chunk (a batch in which nothing differs: in one
         batched formulation, prefill_attention_torch)."""
         d = self.cfg.head_dim
-        ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
-                                          self.hl, self.kvl, d, T, self.k_exp, self.v_exp)
+        with self._paged_view() as put:
+            ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
+                                              self.hl, self.kvl, d, T, self.k_exp, self.v_exp)
+            if self.block_table is not None:
+                rows = [(sl, p + t) for p, n, sl in zip(positions, lengths, slots) for t in range(n)]
+                put(*[torch.tensor([r[i] for r in rows], dtype=torch.long, device=h.device) for i in (0, 1)])
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
     def _mlp_torch(self, h, gather):
@@ -368,6 +430,13 @@ class DecodeLayer(torch.nn.Module):
         from . import decode_ops as G
 
         d = self.cfg.head_dim
+        if self.block_table is not None:  # pools behind the block table: the _paged entry points (a position per sequence, d = 64 / 128)
+            if not per_sequence:
+                raise RuntimeError("a paged KV cache has a position per sequence")
+            args = (qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+            if self._attn_scratch is not None:
+                return G.rope_attn_split_paged(*args, self._attn_scratch, self._attn_split)
+            return G.rope_attn_online_paged(*args)
         args = (qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
         if self.k_exp is not None:
             if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
@@ -384,6 +453,11 @@ class DecodeLayer(torch.nn.Module):
         from . import decode_ops as G
 
         d = self.cfg.head_dim
+        if self.block_table is not None:
+            if not per_sequence or T is None:
+                raise RuntimeError("a paged KV cache has a position per sequence")
+            return G.prefill_attn_paged(qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d,
+                                        1.0 / math.sqrt(d), T, out=qkv.new_zeros(qkv.shape[0], self.hl * d), lengths=lengths, slots=slots)
         T = qkv.shape[0] // self.k_cache.shape[0] if T is None else T
         out = qkv.new_zeros(qkv.shape[0], self.hl * d) if per_sequence else None
         return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
@@ -486,8 +560,17 @@ class DecodeStack(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, linear_factory: Callable, device, dtype=torch.bfloat16, bs: int = 1,
                  rank: int = 0, world: int = 1, group=None, seed: int = 0, lm_head: bool = True,
                  fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
-                 ragged: bool = False, kv_cache: Optional[str] = None):
-        """kv_cache: None = a 16-bit KV cache in the stack's dtype (the default); "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py:
+                 ragged: bool = False, kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64):
+        """kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks, 16-bit rows) --
+        every layer holds pools [kv_pages, kvl, page_size, d] and one `block_table` int32 [bs, max_seq / page_size] (a static device
+        buffer, -1 = unmapped, mirrored on the host) maps position p of slot b to row p % page_size of page block_table[b, p // page_size];
+        a `PagePool` (any4_amd/kvcache.py) hands the pages out.  page_size: a power of two, 64 <= page_size <= max_seq, max_seq % page_size
+        == 0.  `decode` / `prefill` with host positions and `generate` map what they are about to write (RuntimeError "KV page pool
+        exhausted" before anything is launched or mapped) and refuse a write into a page that two slots share; with a device position
+        `reserve` is the caller's.  `reserve` / `release` / `fork` manage slots by hand.  The table is updated by in-place copies, so a
+        captured step sees pages mapped between two replays.  Under tensor parallelism table and pool decisions are the same on every
+        rank and the pools are per rank.  The fused path needs head_dim 64 / 128.
+        kv_cache: None = a 16-bit KV cache in the stack's dtype (the default); "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py:
         E4M3 codes and one exponent byte per 32 elements, (1 + 1/32) / 2 of the 16-bit cache's bytes; head_dim % 32 == 0).  The fused
         attention launches then are the mx8 entry points (a decode step always the split one, so the stack always owns a split scratch);
         capture, prefill, ragged decode and generate work unchanged on top, TP too (the caches are per rank).  In fp16, k / v values
@@ -508,6 +591,10 @@ class DecodeStack(torch.nn.Module):
         super().__init__()
         if gather not in ("rccl", "peer"):
             raise ValueError("gather must be 'rccl' or 'peer'")
+        self.paged = kv_pages is not None
+        if self.paged and not ragged:
+            raise ValueError("kv_pages (a paged KV cache) needs DecodeStack(..., ragged=True)")
+        check_page_size(cfg, kv_pages, page_size, kv_cache)
         if kv_cache not in (None, "mx8"):
             raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
         if kv_cache == "mx8" and cfg.head_dim % 32:
@@ -518,13 +605,23 @@ class DecodeStack(torch.nn.Module):
         self.cfg, self.bs, self.rank, self.world, self.group = cfg, bs, rank, world, group
         self.emulate_gather = emulate_gather
         self.fused = torch.device(device).type == "cuda" if fused is None else fused
+        if self.paged and self.fused and cfg.head_dim not in (64, 128):
+            raise ValueError(f"a fused stack with kv_pages needs head_dim 64 or 128 (the paged kernels), got {cfg.head_dim}")
         self.fuse_gemm_stages = fuse_gemm_stages
         gen = torch.Generator(device=device).manual_seed(seed)
         self.embed = torch.nn.Embedding(cfg.vocab, cfg.hidden, device=device, dtype=dtype)
         self.embed.weight.data = torch.randn(cfg.vocab, cfg.hidden, device=device, generator=gen).to(dtype)
         self.embed.weight.requires_grad_(False)
         self.layers = torch.nn.ModuleList(
-            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs, kv_cache=kv_cache) for i in range(cfg.layers)])
+            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs, kv_cache=kv_cache, kv_pages=kv_pages, page_size=page_size)
+             for i in range(cfg.layers)])
+        if self.paged:
+            self.page_size, self.page_pool = operator.index(page_size), PagePool(kv_pages)
+            self._table = [[-1] * (cfg.max_seq // self.page_size) for _ in range(bs)]  # the host mirror of block_table
+            self.register_buffer("block_table", torch.full((bs, cfg.max_seq // self.page_size), -1, dtype=torch.int32, device=device),
+                                 persistent=False)
+            for layer in self.layers:
+                layer.block_table = self.block_table
         self.norm = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.lm_head = None
         if lm_head:
@@ -569,9 +666,87 @@ class DecodeStack(torch.nn.Module):
                 layer._attn_scratch, layer._attn_split = self._attn_scratch, self._attn_split
 
     def kv_cache_bytes(self) -> int:
-        """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes)."""
+        """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes; a paged one: the pools)."""
+        if self.paged:
+            return sum(t.numel() * t.element_size() for layer in self.layers for t in (layer.k_pool, layer.v_pool))
         return sum(t.numel() * t.element_size() for layer in self.layers
                    for t in (layer.k_cache, layer.v_cache, layer.k_exp, layer.v_exp) if t is not None)
+
+    # ---- the paged cache: which pages a slot holds (host mirror `_table`, device `block_table`, counts in `page_pool`) ----
+    def _need_paged(self, slot=None):
+        if not self.paged:
+            raise ValueError("this stack has no paged KV cache (DecodeStack(..., kv_pages=N))")
+        if slot is not None and not 0 <= operator.index(slot) < self.bs:
+            raise ValueError(f"slot {slot} outside [0, bs = {self.bs})")
+
+    def _mapped(self, slot) -> int:
+        """Pages slot `slot` holds (they are its first table entries)."""
+        row = self._table[slot]
+        return row.index(-1) if -1 in row else len(row)
+
+    def _sync_row(self, slot) -> None:
+        self.block_table[slot].copy_(torch.tensor(self._table[slot], dtype=torch.int32))  # (in place: a captured step reads this buffer)
+
+    def _reserve_all(self, wants) -> None:
+        """`wants`: (slot, tokens) pairs.  Maps pages so that positions < tokens of each slot exist -- all of them or, when the pool
+        has too few (RuntimeError), none."""
+        ps, short = self.page_size, []
+        for slot, tokens in wants:
+            if not 0 <= tokens <= self.cfg.max_seq:
+                raise ValueError(f"{tokens} tokens in slot {slot}: outside the KV cache [0, {self.cfg.max_seq}]")
+            have = self._mapped(slot)
+            if -(-tokens // ps) > have:
+                short.append((slot, have, -(-tokens // ps) - have))
+        new = self.page_pool.alloc(sum(n for _, _, n in short))
+        for slot, have, n in short:
+            self._table[slot][have: have + n] = [new.pop() for _ in range(n)]
+            self._sync_row(slot)
+
+    def _refuse_shared(self, writes) -> None:
+        """`writes`: (slot, first position, one past the last) -- a row a call is about to write must not lie in a page that another
+        slot holds as well (the cache is append-only; there is no copy-on-write)."""
+        for slot, p0, p1 in writes:
+            for e in range(p0 // self.page_size, -(-p1 // self.page_size)):
+                page = self._table[slot][e]
+                if page >= 0 and self.page_pool.refs[page] > 1:
+                    raise ValueError(f"slot {slot}: positions [{p0}, {p1}) would be written into page {page}, which {self.page_pool.refs[page]} "
+                                     "slots share (fork() shares whole pages of a prefix; they are never written again)")
+
+    def reserve(self, slot: int, tokens: int) -> None:
+        """Map pages so that positions < `tokens` of `slot` exist (idempotent; pages are never unmapped here)."""
+        self._need_paged(slot)
+        self._reserve_all([(operator.index(slot), operator.index(tokens))])
+
+    def release(self, slot: int) -> None:
+        """Unmap `slot`: its pages lose a holder, and those nobody else holds return to the pool."""
+        self._need_paged(slot)
+        n = self._mapped(slot)
+        if n:
+            self.page_pool.release(self._table[slot][:n])
+            self._table[slot][:n] = [-1] * n
+            self._sync_row(slot)
+
+    @torch.no_grad()
+    def fork(self, src: int, dst: int, tokens: int) -> None:
+        """Prefix sharing: `dst` (released first) starts as the first `tokens` positions of `src`.  Its first tokens // page_size table
+        entries point at src's pages, which gain a holder -- whole shared pages are never written again, since the cache is append-only
+        -- and the tokens % page_size rows of a partial last page are copied into a fresh page, in every layer."""
+        self._need_paged(src)
+        self._need_paged(dst)
+        src, dst, tokens, ps = operator.index(src), operator.index(dst), operator.index(tokens), self.page_size
+        if src == dst or not 0 <= tokens <= self._mapped(src) * ps:
+            raise ValueError(f"fork({src}, {dst}, {tokens}): two slots and a prefix inside what slot {src} has mapped "
+                             f"({self._mapped(src) * ps} positions) needed")
+        self.release(dst)
+        full, part = divmod(tokens, ps)
+        fresh = self.page_pool.alloc(1 if part else 0)
+        self.page_pool.retain(self._table[src][:full])
+        self._table[dst][: full + len(fresh)] = self._table[src][:full] + fresh
+        self._sync_row(dst)
+        if part:
+            for layer in self.layers:
+                for pool in (layer.k_pool, layer.v_pool):
+                    pool[fresh[0], :, :part] = pool[self._table[src][full], :, :part]
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
     def _gather(self, y, peer_ok=True):
@@ -691,6 +866,9 @@ class DecodeStack(torch.nn.Module):
             raise ValueError(f"position {vals[0]} outside the KV cache [0, {S})")
         if any(not (p == -1 or 0 <= p < S) for p in vals):
             raise ValueError(f"positions {vals}: each must be -1 (inactive) or inside the KV cache [0, {S})")
+        if self.paged:  # the rows this step writes exist and are this slot's alone, or nothing is launched
+            self._refuse_shared([(b, p, p + 1) for b, p in enumerate(vals) if p >= 0])
+            self._reserve_all([(b, p + 1) for b, p in enumerate(vals) if p >= 0])
         if len(set(vals)) == 1:
             buf.fill_(vals[0])  # (a fill: no copy from host memory in the way of the launches)
         else:
@@ -770,7 +948,7 @@ class DecodeStack(torch.nn.Module):
         sequence by `chunk` tokens.  Returns logits [n, vocab] of each sequence's LAST VALID token (unspecified for a length of 0);
         cache slots not named are not touched."""
         per_sequence = lengths is not None or slots is not None or isinstance(position, (list, tuple)) or \
-            (isinstance(position, torch.Tensor) and position.dim() > 0)
+            (isinstance(position, torch.Tensor) and position.dim() > 0) or self.paged  # (there is no scalar-position paged kernel)
         if per_sequence and not self.ragged:
             raise ValueError("positions / lengths / slots per sequence need DecodeStack(..., ragged=True)")
         if per_sequence and position is None:
@@ -810,6 +988,9 @@ class DecodeStack(torch.nn.Module):
         chunk = min(T, 2048) if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if self.paged:
+            self._refuse_shared([(sl, p, p + x) for p, x, sl in zip(position, lengths, slots) if x > 0])
+            self._reserve_all([(sl, p + x) for p, x, sl in zip(position, lengths, slots) if x > 0])
         # the LM head runs on the last token of every sequence only.  Named per sequence, the last valid token may lie in any chunk: its
         # row of the last layer's output is picked on the device; else it is the last row of the last chunk
         last = torch.tensor([max(x - 1, 0) for x in lengths], dtype=torch.long).to(tokens.device) if per_sequence else None
@@ -839,6 +1020,10 @@ class DecodeStack(torch.nn.Module):
         if new_tokens < 1:
             raise ValueError(f"new_tokens must be >= 1, got {new_tokens}")
         per_sequence = isinstance(prompt, (list, tuple)) or eos is not None
+        if self.paged:  # every slot's whole run, up front (the per-sequence steps below pass device positions); nothing is released here
+            lens = [p.numel() for p in prompt] if isinstance(prompt, (list, tuple)) else [prompt.shape[-1]] * self.bs
+            if len(lens) == self.bs:
+                self._reserve_all([(b, min(n + new_tokens, self.cfg.max_seq)) for b, n in enumerate(lens)])
         if not per_sequence:
             base = prompt.shape[1] if prompt.dim() == 2 else 0  # a host int: decode() fills the position
             tok = self.prefill(prompt).argmax(-1)

@@ -106,29 +106,49 @@ def _mx8_exps(what, k_cache, v_cache, k_exp, v_exp, d):
     return (k_exp, v_exp)
 
 
-def _attn_launch(base, seq, exps, qkv, **values):
+def _paged(what, table, k_pool, v_pool, kvl, d):
+    """The paging arguments of a `_paged` launch, checked: `table` int32 [cache_bs, max_seq / page_size] on the pools' device, the pools
+    [num_pages, kvl, page_size, d] in a 16-bit type.  Returns them by argument name, with max_seq."""
+    if table.dtype != torch.int32 or table.dim() != 2 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape or k_pool.dtype != v_pool.dtype or \
+            tuple(k_pool.shape[1::2]) != (kvl, d):
+        raise RuntimeError(f"{what}: table must be int32 [cache_bs, max_seq / page_size] and the pools [num_pages, {kvl}, page_size, {d}], got "
+                           f"{table.dtype} {tuple(table.shape)}, {tuple(k_pool.shape)}, {tuple(v_pool.shape)}")
+    if k_pool.dtype not in (torch.bfloat16, torch.float16):
+        raise RuntimeError(f"{what}: a paged cache holds 16-bit rows, got {k_pool.dtype}")
+    num_pages, _, page_size, _ = k_pool.shape
+    return dict(table=table, k_pool=k_pool, v_pool=v_pool, page_size=page_size, num_pages=num_pages, max_seq=table.shape[1] * page_size)
+
+
+def _attn_launch(base, seq, exps, qkv, paged=False, **values):
     """One launch of an attention entry point: _lib.attn_signature names the flavour of `base` (seq: `_seq`; exps = (k_exp, v_exp) of an
-    mx8 cache: `_mx8`) and the order of its arguments; `values` are given by argument name, tensors (or None) for pointers.  qkv also
-    supplies dtype, device and stream."""
-    entry, args = _lib.attn_signature(base, seq, bool(exps))
+    mx8 cache: `_mx8`; paged: `_paged`) and the order of its arguments; `values` are given by argument name, tensors (or None) for
+    pointers.  qkv also supplies dtype, device and stream."""
+    entry, args = _lib.attn_signature(base, seq, bool(exps), paged)
     values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
     ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
     _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
 
 
-def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=()):
+def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=(), table=None):
     """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
-    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points."""
+    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points; table: the
+    caches are page pools behind this block table: the _paged entry points (per sequence)."""
     scratch, nsplit = split if split is not None else (None, None)
-    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, *exps, out=out)
-    what = base + ("_mx8" if exps else "")
+    out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, table, *exps, out=out)
+    what = base + ("_mx8" if exps else "") + ("_paged" if table is not None else "")
     if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"{what}: out must be [{bs}, {hl * d}] {qkv.dtype}")
     if per_sequence:
         _per_sequence(pos, bs, what)
     more = {} if split is None else dict(scratch=scratch, scratch_bytes=scratch.numel() * 4, nsplit=nsplit)
-    _attn_launch(base, per_sequence, exps, qkv, cos=cos, sin=sin, pos=pos, k_cache=k_cache, v_cache=v_cache, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
-                 max_seq=max_seq, scale=float(scale), **more)
+    if table is not None:
+        if table.shape[0] != bs:
+            raise RuntimeError(f"{what}: the table needs a row per sequence ({bs}), got {tuple(table.shape)}")
+        more.update(_paged(what, table, k_cache, v_cache, kvl, d))
+    else:
+        more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
+    _attn_launch(base, per_sequence, exps, qkv, table is not None, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
+                 scale=float(scale), **more)
     return out
 
 
@@ -165,10 +185,33 @@ def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos
     return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps)
 
 
+def rope_attn_online_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,
+                           k_pool: torch.Tensor, v_pool: torch.Tensor, hl: int, kvl: int, d: int, scale: float, out: torch.Tensor = None) -> torch.Tensor:
+    """rope_attn_online(per_sequence=True) on a paged cache: pools [num_pages, kvl, page_size, d] behind `table` int32 [bs, max_seq /
+    page_size] on the device -- position p of sequence b is row p % page_size of page table[b, p // page_size] (-1: unmapped).  An entry
+    outside the pool is read as page 0 and never written through."""
+    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, table=table)
+
+
+def rope_attn_split_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
+                          v_pool: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int,
+                          out: torch.Tensor = None) -> torch.Tensor:
+    """rope_attn_split(per_sequence=True) on a paged cache (rope_attn_online_paged): the one-barrier kernel with nsplit blocks per head."""
+    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), table=table)
+
+
+def prefill_attn_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
+                       v_pool: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None,
+                       lengths: torch.Tensor = None, slots: torch.Tensor = None) -> torch.Tensor:
+    """prefill_attn(per_sequence=True) on a paged cache (rope_attn_online_paged): `slots` names the table ROW of each sequence (default:
+    row i, and n must be the table's rows)."""
+    return prefill_attn(qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, T, out, lengths, slots, True, table=table)
+
+
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None,
                  lengths: torch.Tensor = None, slots: torch.Tensor = None, per_sequence: bool = False, k_exp: torch.Tensor = None,
-                 v_exp: torch.Tensor = None) -> torch.Tensor:
+                 v_exp: torch.Tensor = None, table: torch.Tensor = None) -> torch.Tensor:
     """A chunk of T tokens per sequence: qkv [bs * T, (hl + 2 kvl) d] (row b * T + t) -> context [bs * T, hl * d]; the T roped k rows and
     the v rows are appended to the caches at positions pos ... pos + T - 1 (`pos` [1] int64 on the device = position of token 0), and
     token t attends causally over cache rows 0 ... pos + t.  A token whose position is outside the cache writes nothing and leaves its
@@ -177,13 +220,14 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     position of token 0 of each sequence.  `lengths` int64 [n] on the device: only tokens t < min(lengths[i], T) exist (default: all T);
     `slots` int64 [n] on the device: sequence i lives in cache slot slots[i] (default: slot i, and n must be the caches' batch; with
     slots n may be smaller).  A sequence of length <= 0 or with a slot outside the caches does nothing; slots must be distinct.
-    float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split."""
+    float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split.  table: prefill_attn_paged."""
     exps = _mx8_exps("prefill_attn", k_cache, v_cache, k_exp, v_exp, d)
-    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, *exps, out=out)
+    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, table, *exps, out=out)
     T = int(T)
     per_sequence = per_sequence or lengths is not None or slots is not None
-    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != k_cache.shape[0] and slots is None):
-        raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {k_cache.shape[0]} (the caches'), got {tuple(qkv.shape)}")
+    cache_bs = k_cache.shape[0] if table is None else table.shape[0]
+    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != cache_bs and slots is None):
+        raise RuntimeError(f"prefill_attn: qkv must be [bs * T, ...] with T = {T} and bs = {cache_bs} (the caches'), got {tuple(qkv.shape)}")
     if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"prefill_attn: out must be [{rows}, {hl * d}] {qkv.dtype}")
     more = {}
@@ -193,9 +237,13 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
         for name, t in (("lengths", lengths), ("slots", slots)):
             if t is not None and (t.dtype != torch.int64 or t.numel() != n):
                 raise RuntimeError(f"prefill_attn: {name} must be int64 with {n} elements (one per sequence)")
-        more = dict(len=lengths, slot=slots, cache_bs=k_cache.shape[0])
-    _attn_launch("dg_prefill_attn", per_sequence, exps, qkv, cos=cos, sin=sin, pos=pos, k_cache=k_cache, v_cache=v_cache, out=out, bs=rows // T, T=T,
-                 hl=hl, kvl=kvl, d=d, max_seq=max_seq, scale=float(scale), **more)
+        more = dict(len=lengths, slot=slots, cache_bs=cache_bs)
+    if table is not None:
+        more.update(_paged("prefill_attn_paged", table, k_cache, v_cache, kvl, d))
+    else:
+        more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
+    _attn_launch("dg_prefill_attn", per_sequence, exps, qkv, table is not None, cos=cos, sin=sin, pos=pos, out=out, bs=rows // T, T=T,
+                 hl=hl, kvl=kvl, d=d, scale=float(scale), **more)
     return out
 
 

@@ -1,4 +1,7 @@
-"""The `mx8` KV-cache format of the decode stack: block-scaled 8-bit rows (OCP MXFP8: E4M3 elements, one E8M0 exponent byte per 32
+"""KV-cache formats and bookkeeping of the decode stack.  `PagePool` (at the end) is the host side of the paged cache: which pages of a
+layer's pools are free and how many block-table entries point at each.
+
+The `mx8` KV-cache format of the decode stack: block-scaled 8-bit rows (OCP MXFP8: E4M3 elements, one E8M0 exponent byte per 32
 consecutive elements of a row).  Plain torch, CPU and GPU; `mx8_encode` IS the definition of the format -- the HIP writers
 (dg_rope_attn_split_mx8, dg_prefill_attn_mx8 and their _seq forms) reproduce its bytes, the readers compute `mx8_decode`.
 
@@ -59,3 +62,51 @@ def mx8_decode(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype) -> t
     vals = codes.float().reshape(*codes.shape[:-1], nb, BLOCK) * mx8_scale(exps).unsqueeze(-1)
     vals = torch.where((exps == 255).unsqueeze(-1), torch.full_like(vals, float("nan")), vals)
     return vals.reshape(codes.shape).to(dtype)
+
+
+class PagePool:
+    """The pages of a paged KV cache (DecodeStack(kv_pages=...)): a free list and a reference count per page.  Plain Python, no tensors --
+    one pool serves every layer and, under tensor parallelism, every rank makes the same decisions.  A page is handed out with count 1;
+    `retain` adds a holder (prefix sharing), `release` removes one, and a page nobody holds returns to the free list."""
+
+    def __init__(self, num_pages: int):
+        if int(num_pages) < 1:
+            raise ValueError(f"a page pool needs at least one page, got {num_pages}")
+        self.num_pages = int(num_pages)
+        self.refs = [0] * self.num_pages
+        self._free = list(range(self.num_pages - 1, -1, -1))  # (handed out from the end: page 0 first)
+
+    @property
+    def free_pages(self) -> int:
+        return len(self._free)
+
+    def alloc(self, n: int) -> list:
+        """`n` free pages, each now held once.  More than the free list has: RuntimeError, and nothing changes."""
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"alloc of {n} pages")
+        if n > len(self._free):
+            raise RuntimeError(f"KV page pool exhausted: {n} pages wanted, {len(self._free)} of {self.num_pages} free")
+        ids = [self._free.pop() for _ in range(n)]
+        for i in ids:
+            self.refs[i] = 1
+        return ids
+
+    def _held(self, ids, what):
+        ids = [int(i) for i in ids]
+        for i in set(ids):
+            if not 0 <= i < self.num_pages or self.refs[i] < max(1, ids.count(i) if what == "release" else 1):
+                raise ValueError(f"{what} of page {i}, which is not held{' that often' if 0 <= i < self.num_pages and self.refs[i] else ''}")
+        return ids
+
+    def retain(self, ids) -> None:
+        """One more holder for each of `ids` (pages that are held already)."""
+        for i in self._held(ids, "retain"):
+            self.refs[i] += 1
+
+    def release(self, ids) -> None:
+        """One holder fewer for each of `ids`; a page whose count drops to zero is free again."""
+        for i in self._held(ids, "release"):
+            self.refs[i] -= 1
+            if self.refs[i] == 0:
+                self._free.append(i)

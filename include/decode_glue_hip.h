@@ -161,6 +161,38 @@ TG_API int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const floa
                                    int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
                                    tg_stream_t stream);
 
+/* ---- paged KV cache: a pool of fixed-size pages behind a block table ----
+ * Per layer k_pool / v_pool are [num_pages][kvl][page_size][d] in the 16-bit type; one table, int32 [cache_bs][max_seq / page_size] on the
+ * device, serves every layer: logical position p of the sequence in cache slot s is row p % page_size of page table[s][p / page_size]
+ * (-1: unmapped, by convention).  page_size is a power of two, 64 <= page_size <= max_seq, max_seq % page_size == 0, num_pages > 0
+ * (TG_E_SHAPE otherwise); d = 64 / 128 in all three; max_seq <= 65536 for the decode entry points, <= 8192 for prefill; the table 16-byte
+ * aligned like the other tensors (TG_E_ALIGN), not null (TG_E_NULL); in every such case nothing is touched.  The contiguous caches
+ * [bs][kvl][max_seq][d] ARE the pool with page_size = max_seq and the identity table.
+ *   dg_rope_attn_online_paged   dg_rope_attn_online_seq's arguments, `table` in front of the pools, page_size / num_pages behind max_seq
+ *   dg_rope_attn_split_paged    the same on dg_rope_attn_split_seq; always the one-barrier kernel with nsplit blocks per head
+ *   dg_prefill_attn_paged       the same on dg_prefill_attn_seq; slot[i] picks the table ROW, cache_bs is the number of table rows
+ * A position per sequence always (there is no scalar-position paged flavour); the position, length and slot guards are the _seq ones.
+ * Whatever the table holds, nothing outside the pools is indexed: an entry outside [0, num_pages) is read as page 0 (that sequence's
+ * output is then unspecified), and a row whose OWN entry is outside [0, num_pages) is not written -- neither pool changes.  Pages of
+ * different sequences that are written by one call must be distinct (the caller's obligation, as distinct slots are).
+ * The kernels walk the context in units that a page holds whole (32- / 64-row iterations, 64-position tiles); paging changes where a
+ * unit's base comes from (one scalar table read) and nothing else: partition of work, order of every sum, masks and rounding points are
+ * the _seq namesakes', so for tables that map the same rows the cache rows written and the output rows are, bit for bit, theirs.
+ * The three are exported like every other symbol; they are declared with a macro of their own because they are bound as a group of
+ * their own (any4_amd/_lib.py: PAGED_SYMBOLS, next to SYMBOLS, which stays the list of the twelve unpaged attention entry points). */
+#define DG_PAGED_API TG_API /* (exported) */
+DG_PAGED_API int dg_rope_attn_online_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
+                                           void* k_pool, void* v_pool, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                                           int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream);
+DG_PAGED_API int dg_rope_attn_split_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
+                                          void* k_pool, void* v_pool, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                          int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype,
+                                          int device, tg_stream_t stream);
+DG_PAGED_API int dg_prefill_attn_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                                       const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* out, int64_t n, int64_t T,
+                                       int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale,
+                                       int dtype, int device, tg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,6 +22,15 @@ the 4-bit weights stream (algorithmic bytes of the quantized linears / step time
 to --out: the caches' bytes, and the captured step of a 16-bit-cache stack and an mx8-cache stack, alternating in one process, at
 bs = 1 and 8 with the position near 512, 4096 and the end of an 8192-position cache.  With --ragged: leg (b) above on a 16-bit and on
 an mx8 ragged bs = 8 stack.
+
+    python tools/llama_decode_bench.py --config llama3_8b --paged [--out profiles/paged_bench.jsonl]
+
+--paged (one GPU): the paged KV cache against the contiguous one, one JSON line per leg, appended to --out:
+  (a) the captured step of a paged ragged stack (64-position pages, every page mapped up front, in reverse physical order) and of the
+      contiguous ragged stack, alternating in one process, at bs = 1 and 8 with the position near 512, 4096 and the end of an
+      8192-position cache;
+  (b) `kv_cache_bytes()` of a pool sized for the eight prompts of --ragged leg (b) plus their new tokens against the contiguous bs = 8
+      stack's, and the seconds of `generate(list)` on either.
 """
 import argparse
 import json
@@ -152,6 +161,64 @@ def kv8_bench(a, cfg, device):
         torch.cuda.empty_cache()
 
 
+def paged_bench(a, cfg, device):
+    """The legs of --paged; yields the JSON-able results."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    ps = 64
+
+    def stack(bs, kv_pages, capture=True):
+        st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                         fuse_gemm_stages=not a.no_fuse, ragged=True, kv_pages=kv_pages, page_size=ps)
+        if kv_pages is not None and capture:  # every position exists before the timed steps; physical order is not logical order
+            st.page_pool._free.reverse()
+            for b in range(bs):
+                st.reserve(b, cfg.max_seq)
+        if capture:
+            st.capture()
+        return st
+
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "page_size": ps,
+            "data": "synthetic (random weights, random tokens, zero caches)"}
+    for bs in (1, 8):
+        pair = {"contiguous": stack(bs, None), "paged": stack(bs, bs * cfg.max_seq // ps)}
+        leg = dict(base, leg="paged a: captured ragged step, contiguous cache vs page pool, alternating", bs=bs, steps=a.steps, warmup=a.warmup,
+                   rounds=a.rounds, kv_cache_bytes={k: st.kv_cache_bytes() for k, st in pair.items()},
+                   attn_split={k: st._attn_split for k, st in pair.items()}, ms_per_step={})
+        for want in (512, 4096, cfg.max_seq):
+            start = max(0, min(want, cfg.max_seq - a.warmup - a.steps))  # (the timed steps end inside the cache)
+            series = {k: [] for k in pair}
+            for r in range(a.rounds):
+                for k in (("contiguous", "paged") if r % 2 == 0 else ("paged", "contiguous")):
+                    series[k].append(round(time_steps(pair[k], a.steps, a.warmup, start) * 1e3, 4))
+            med = {k: sorted(v)[len(v) // 2] for k, v in series.items()}
+            leg["ms_per_step"][f"pos{start + a.warmup}"] = dict(
+                {k: {"median": med[k], "min": min(v), "max": max(v), "series": v} for k, v in series.items()},
+                paged_over_contiguous=round(med["paged"] / med["contiguous"], 4))
+        yield leg
+        del pair
+        torch.cuda.empty_cache()
+    # (b) the pool the eight prompts need against eight slots of max_seq rows
+    lengths, new = [16, 32, 64, 96, 128, 256, 384, 512], a.new_tokens
+    gen = torch.Generator().manual_seed(0)
+    prompts = [torch.randint(0, cfg.vocab, (n,), generator=gen).to(device) for n in lengths]
+    pages = sum(-(-(n + new) // ps) for n in lengths)
+    res = {}
+    for name, kv_pages in (("contiguous", None), ("paged", pages)):
+        st = stack(8, kv_pages, capture=False)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        st.generate(prompts, new)
+        torch.cuda.synchronize()
+        res[name] = {"kv_cache_bytes": st.kv_cache_bytes(), "generate_seconds_eager_first_call": round(time.perf_counter() - t0, 4)}
+        if kv_pages is not None:
+            res[name].update(kv_pages=pages, free_pages_after=st.page_pool.free_pages)
+        del st
+        torch.cuda.empty_cache()
+    yield dict(base, leg="paged b: KV bytes of a pool sized for eight prompts + new tokens vs the contiguous bs = 8 stack", prompt_lengths=lengths,
+               new_tokens=new, **res, paged_over_contiguous_bytes=round(res["paged"]["kv_cache_bytes"] / res["contiguous"]["kv_cache_bytes"], 4))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "tiny"])
@@ -181,11 +248,13 @@ def main():
     ap.add_argument("--new-tokens", type=int, default=64, help="--ragged leg (b): tokens generated per prompt")
     ap.add_argument("--kv-cache", default=None, choices=["mx8"],
                     help="the legs of DESIGN.md section 15: the mx8 KV cache against the 16-bit one at an 8192-position cache (see the module docstring); one GPU")
-    ap.add_argument("--out", default=None, help="--ragged / --kv-cache: the file the JSON lines are appended to "
-                                                "(default profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl)")
+    ap.add_argument("--paged", action="store_true",
+                    help="the legs of DESIGN.md section 16: the paged KV cache against the contiguous one at an 8192-position cache (see the module docstring); one GPU")
+    ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
+                                                "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl)")
     a = ap.parse_args()
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "paged_bench.jsonl" if a.paged else "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
     if a.backend == "gloo" and a.gather != "peer":
         raise SystemExit("--backend gloo moves no CUDA tensors: use it with --gather peer")
 
@@ -211,6 +280,17 @@ def main():
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.paged:
+        if world > 1:
+            raise SystemExit("--paged runs on one GPU")
+        cfg.max_seq = 8192
+        with open(a.out, "a") as f:
+            for leg in paged_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     if a.kv_cache:
         if world > 1:
