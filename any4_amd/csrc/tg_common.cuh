@@ -59,6 +59,7 @@ struct GemmParams {
   int32_t numerics;  // TG_NUM_* (dispatch)
   int32_t dot2;      // TG_NUM_FAST_DOT2 was asked for (never promote a stacked m = 1 launch to the matrix-core contraction)
   int32_t dry;       // report the kernel family instead of launching (tg_gemm_w4_plan)
+  int32_t dry_detail;  // ... and, within the pair-table family, the lean m = 1 kernel as TG_PLAN_PAIR_M1_LEAN (tg_gemm_w4_plan_detail)
   int64_t stride_x, stride_w, stride_qinfo, stride_lut, stride_y;
   const char* bias;   // optional [wrows] 16-bit, added after the first rounding (see store_rows4)
   int64_t stride_bias;
@@ -386,7 +387,8 @@ inline int plan_cu_count(const GemmParams& p) { return p.dry ? 256 : cu_count();
 #if !defined(TG_DEV) && !defined(TG_DEV_MIN)
 #if defined(TG_PAIR_R) || defined(TG_PAIR_MR1) || defined(TG_PAIR_NSG2) || defined(TG_PAIR_MR1_GPS) || defined(TG_PAIR_RA) ||   \
     defined(TG_PAIR_RA1) || defined(TG_PAIR_RB16) || defined(TG_B16_CHUNK) || defined(TG_PAIR_MIN_ITEMS) || defined(TG_XG_CHUNK) || defined(TG_PAIR_WGS) || \
-    defined(TG_PAIR_NSG2_M1) || defined(TG_XR_MIN_M) || defined(TG_XR_R) || defined(TG_XR_R8K) || defined(TG_XR_RMX)
+    defined(TG_PAIR_NSG2_M1) || defined(TG_XR_MIN_M) || defined(TG_XR_R) || defined(TG_XR_R8K) || defined(TG_XR_RMX) || defined(TG_PAIR_M1_LEAN) || \
+    defined(TG_PAIR_M1_AHEAD)
 #error "the TG_PAIR_* / TG_XG_* / TG_B16_* tuning constants can only be overridden in developer builds (-DTG_DEV or -DTG_DEV_MIN)"
 #endif
 #endif
@@ -451,6 +453,12 @@ inline int plan_cu_count(const GemmParams& p) { return p.dry ? 256 : cu_count();
 #endif
 #ifndef TG_XR_R
 #define TG_XR_R 4              // super-tiles a wave of that kernel keeps in flight
+#endif
+#ifndef TG_PAIR_M1_LEAN
+#define TG_PAIR_M1_LEAN 1      // plain stacked m = 1 calls (g = 128, innerKTiles 4, int4 / any4) run w4_pair_m1_lean_kernel; 0: the general template
+#endif
+#ifndef TG_PAIR_M1_AHEAD
+#define TG_PAIR_M1_AHEAD 1     // ... whose lookups run one step ahead of the products (+ 0.9 % over lookups in step, profiles/m1_lean_ab.txt)
 #endif
 #ifndef TG_PAIR_WGS
 #define TG_PAIR_WGS 512        // persistent workgroups: two per CU (768 / 1024: +4 % / +1 % time)

@@ -43,6 +43,31 @@ int launch_pair_k(const GemmParams& p, PairParams& pp, unsigned lds) {
 #endif
 }
 
+// The lean m = 1 kernel (w4_pair_m1_lean_kernel): a plain stacked call of one activation row -- staged activations, row-major operands,
+// no bias / epilogue / fused norm, whole 64-row blocks, partial sums beside the table -- at innerKTiles 4 with a group of one ring round
+// (g = 128), int4 / any4.  Every other call keeps the general template.
+inline bool pair_lean_call(const GemmParams& p, const PairParams& pp, bool xg) {
+  return TG_PAIR_M1_LEAN && TG_PAIR_MR1 == 1 && TG_PAIR_R == 2 && p.m == 1 && !xg && !p.norm_w && !p.bias && !p.epilogue && !p.x_tc && !p.y_tc &&
+         p.wrows % 64 == 0 && p.ntiles * 8 == p.wrows && !pp.red_alias && pp.cblocks == 1 && pp.spw % 2 == 0 && p.ksuper % 2 == 0 &&
+         p.numerics != TG_NUM_FAST_MFMA;
+}
+template <typename DT>
+int launch_pair_lean(const GemmParams& p, const PairParams& pp, unsigned lds) {
+#ifdef TG_DEV_MIN
+  if constexpr (!(std::is_same<DT, BF16>::value && TG_DEV_MIN == 2)) return TG_PAIR_NA;
+  else {
+#endif
+  if (p.dry) return p.dry_detail ? (int)TG_PLAN_PAIR_M1_LEAN : (int)TG_PLAN_PAIR;
+  PairLeanParams lp;
+  copy_call(lp, p);
+  lp.spw = pp.spw; lp.lds_x = pp.lds_x; lp.lds_xs = pp.lds_xs; lp.lds_red = pp.lds_red; lp.rblocks = pp.rblocks; lp.items = pp.items;
+  const unsigned wgs = (unsigned)(pp.items < TG_PAIR_WGS ? pp.items : TG_PAIR_WGS);
+  return launch_lds_kernel<w4_pair_m1_lean_kernel<DT, TG_PAIR_M1_AHEAD != 0>>(dim3(wgs), dim3(512), lds, p.st, lp, false);
+#ifdef TG_DEV_MIN
+  }
+#endif
+}
+
 // The activation block of one pass does not fit next to the table (m = 8 at k = 4096, m = 1 at k >= 8192): the XG variant
 // takes the activations pre-arranged from a caller-provided workspace (w4_xprep_kernel, one small launch in front).
 // Workspace = [batch][m k 2 bytes] arranged activations, then [batch][passes][groups][xs_rows] f32 sums.
@@ -208,6 +233,9 @@ int launch_pair(GemmParams& p) {
     if constexpr (I == 4 && !QMX) {
       if (p.numerics == TG_NUM_FAST_MFMA && p.m == 1 && !xg && !p.norm_w && fixed && nsg == TG_PAIR_R)
         return launch_pair_k<DT, I, 1, 1, false, TG_PAIR_R, false, 0, false, true>(p, pp, lds);
+    }
+    if constexpr (I == 4 && !QMX) {
+      if (fixed && nsg == TG_PAIR_R && pair_lean_call(p, pp, xg)) return launch_pair_lean<DT>(p, pp, lds);
     }
     if (fixed && nsg == TG_PAIR_R) return launch_pair_m<DT, I, 1, QMX, TG_PAIR_R>(p, pp, lds, xg, mregs);
     // m = 1, a group of ONE super-tile (g = 64 at innerKTiles 4): fixed boundaries too since the dot2 contraction freed the registers

@@ -449,6 +449,7 @@ static GemmParams make_params(const tg_w4_gemm* a, GemmEntry e, tg_stream_t stre
   p.numerics = a->numerics == TG_NUM_FAST_DOT2 ? (int)TG_NUM_FAST : a->numerics;
   p.dot2 = a->numerics == TG_NUM_FAST_DOT2;
   p.dry = dry != 0;
+  p.dry_detail = dry == 3;
   p.stride_x = batched ? a->stride_x : 0;
   p.stride_w = batched ? a->stride_w : 0;
   p.stride_qinfo = batched ? a->stride_qinfo : 0;
@@ -468,7 +469,8 @@ static GemmParams make_params(const tg_w4_gemm* a, GemmEntry e, tg_stream_t stre
   return p;
 }
 
-// dry: 0 launch, 1 report the kernel family (tg_gemm_w4_plan), 2 report the workspace the fastest kernel wants
+// dry: 0 launch, 1 report the kernel family (tg_gemm_w4_plan), 2 report the workspace the fastest kernel wants, 3 as 1 but naming the
+// lean m = 1 pair kernel (tg_gemm_w4_plan_detail)
 static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream, int dry, int64_t* ws_need = nullptr) {
   tg_w4_gemm full;
   int rc0 = take_args(caller, &full);
@@ -540,6 +542,8 @@ static int gemm_w4_impl(const tg_w4_gemm* caller, int device, tg_stream_t stream
 int tg_gemm_w4(const tg_w4_gemm* a, int device, tg_stream_t stream) { return gemm_w4_impl(a, device, stream, 0); }
 
 int tg_gemm_w4_plan(const tg_w4_gemm* a, int device) { return gemm_w4_impl(a, device, nullptr, 1); }
+
+int tg_gemm_w4_plan_detail(const tg_w4_gemm* a, int device) { return gemm_w4_impl(a, device, nullptr, 3); }
 
 int64_t tg_gemm_w4_workspace_bytes(const tg_w4_gemm* a) {
   int64_t need = 0;

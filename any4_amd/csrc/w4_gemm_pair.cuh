@@ -52,6 +52,7 @@
 //                one, so the weight stream never drains while a table is rebuilt.  Two barriers per item.
 #pragma once
 #include "w4_helpers.cuh"
+#include "pair_walk.h"
 
 struct PairParams {
   const char* x;
@@ -960,4 +961,315 @@ __global__ void __launch_bounds__(256) w4_xprep_kernel(const XPrepParams p) {
   for (int o = 1; o <= p.gch_mask; o <<= 1) sum += __shfl_xor(sum, o);
   if (on && (ch & p.gch_mask) == 0)
     reinterpret_cast<float*>(p.xsum + (int64_t)b * p.stride_xsum)[((int64_t)ct * p.ngroups + (ch >> (p.gshift - 5))) * p.xs_rows + ar] = sum;
+}
+
+// ---- the lean m = 1 kernel: the DOT path of w4_gemm_pair_kernel<DT, 4, 1, 1, false, 2, 2> for a plain stacked call ----------------
+// One activation row, innerKTiles 4, g = 128 (a group = one round of the ring of two), int4 / any4, row-major operands, no bias, no
+// epilogue, no fused norm, wrows % 64 == 0, staged activations, partial sums beside the table: what the headline launch of bench.py
+// is.  Same LDS plan, same table, same lookups, same products in the same order as the general kernel -- the outputs are the same
+// bits -- but everything such a call fixes is a compile-time constant and the parameter block holds only what is read.  The general
+// template at this instantiation keeps 88 scalars in spilled lanes of a VGPR and reloads them with ~93 v_readlane per item and wave
+// (an item is only four rounds of the main loop per wave); here they fit the SGPR file.
+//   item walk   pair_walk.h: per-lane offsets are computed once per launch, the wave-uniform bases of an item come from its
+//               coordinates (problem, row block), which advance without a division
+//   AHEAD       the lookups of step u + 1 (8 v_perm, 8 ds_read_b32, the step's activation piece) are issued before the 8 v_dot2 of
+//               step u, across slot and round boundaries of an item: a wave's own LDS round trip overlaps its own products.  One
+//               scheduling fence per step keeps the compiler from running further ahead (registers).  Nothing is in flight across the
+//               end of an item.
+struct PairLeanParams {
+  const char* x;
+  const char* w;
+  const char* qinfo;
+  const char* lut;
+  char* y;
+  int32_t wrows, k, ksuper, qtype;
+  int32_t spw;      // k super-tiles per wave (even: a wave's slice never cuts a group)
+  int32_t lds_x, lds_xs, lds_red;  // as in PairParams
+  int32_t rblocks, items;
+  int64_t stride_x, stride_w, stride_qinfo, stride_lut, stride_y;
+};
+
+template <typename DT, bool AHEAD>
+__global__ void __launch_bounds__(512, 4) w4_pair_m1_lean_kernel(const PairLeanParams p) {
+  constexpr int R = 2, CPS = 2, TILES = 2, WAVES = 8;
+  const int tid = threadIdx.x;
+  const int lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int c = lane & 31;
+  const int h = lane >> 5;
+  const uint32_t lds_x = (uint32_t)p.lds_x, lds_xs = (uint32_t)p.lds_xs, lds_red = (uint32_t)p.lds_red;
+
+  int it_begin, it_end;
+  pair_walk_range((int)blockIdx.x, (int)gridDim.x, p.items, it_begin, it_end);
+  if (it_begin >= it_end) return;
+  const int s_begin = wave * p.spw;
+  const int nl = max(min(p.spw, p.ksuper - s_begin), 0);  // even
+
+  PairWalkGeom geo;
+  geo.rblocks = p.rblocks;
+  geo.step[PW_W] = (int64_t)p.ksuper * 2048;  // 8 row tiles x ksuper x 256 bytes
+  geo.step[PW_Q] = 256;
+  geo.step[PW_LUT] = p.qtype == TG_Q_ANY4_ROWWISE ? 2048 : 0;
+  geo.stride[PW_W] = p.stride_w; geo.stride[PW_Q] = p.stride_qinfo; geo.stride[PW_LUT] = p.stride_lut;
+
+  // per-lane byte offsets inside a 64-row block: the same for every item
+  uint32_t wlane = (uint32_t)(((c >> 3) * p.ksuper * 32 + 4 * (c & 7) + 2 * h) * 8);  // tile 1: + ksuper * 1024 (wave-uniform)
+  uint32_t qlane = (uint32_t)(c * 4);                                                  // tile 1: + 128
+  const uint32_t llane = p.qtype == TG_Q_ANY4_ROWWISE ? (uint32_t)((tid & 63) * 32) : 0u;
+  const int tcol = tid & 63;
+  auto pin = [](uint32_t& v) -> uint32_t { asm volatile("" : "+v"(v)); return v; };
+  auto uni = [](uint32_t v) -> uint32_t { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+
+  uint32_t lp[8];
+  const bool lut_loaded = p.qtype != TG_Q_INT4;
+  auto lut_request = [&](const PairWalk& e) {
+    const char* lsrc = p.lut + e.off[PW_LUT] + llane;
+    const u32x4 l0 = reinterpret_cast<const u32x4*>(lsrc)[0];
+    const u32x4 l1 = reinterpret_cast<const u32x4*>(lsrc)[1];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { lp[j] = l0[j]; lp[4 + j] = l1[j]; }
+  };
+
+  struct Slot {
+    uint32_t w[TILES][4];
+    uint32_t q[TILES];
+  };
+  Slot ring[R];
+  // super-tile s of the rows of `e` (an invalid request takes super-tile 0: see w4_gemm_pair_kernel's issue)
+  auto issue = [&](const PairWalk& e, int s, Slot& sl, bool valid, bool needq) {
+    const uint32_t sv = valid ? (uint32_t)s : 0u;
+    const char* wb = p.w + e.off[PW_W];
+    const char* qb = p.qinfo + e.off[PW_Q];
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {
+      const char* src = wb + uni(sv * 256u + (uint32_t)(t * p.ksuper * 1024)) + pin(wlane);
+      const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(src));
+#pragma unroll
+      for (int j = 0; j < 4; ++j) sl.w[t][j] = v[j];
+      if (needq) sl.q[t] = *reinterpret_cast<const uint32_t*>(qb + uni((sv >> 1) * (uint32_t)p.wrows * 4u) + pin(qlane) + t * 128);
+    }
+  };
+
+  // ---- activation staging (one row): chunk of 32 k -> LDS in byte order, and the per-group sums, formed as the general kernel forms them.
+  // (Its zero piece and the sums of rows 1 ... 3 are never read at m = 1 on the v_dot2 path: not written.)
+  const int nch = p.k >> 5;
+  auto x_load = [&](const char* xb, int ch, uint32_t (&d)[16]) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(xb + (int64_t)ch * 64);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const u32x4 v = src[j];
+      d[4 * j] = v[0]; d[4 * j + 1] = v[1]; d[4 * j + 2] = v[2]; d[4 * j + 3] = v[3];
+    }
+  };
+  auto x_store = [&](int ch, bool on, const uint32_t (&d)[16]) {  // d holds zeros when !on
+    if (on) {
+      const uint32_t dst = lds_x + (uint32_t)(ch * 64);
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        u32x4 o;
+        o[0] = __builtin_amdgcn_perm(d[q + 4], d[q], 0x05040100u);
+        o[1] = __builtin_amdgcn_perm(d[q + 12], d[q + 8], 0x05040100u);
+        o[2] = __builtin_amdgcn_perm(d[q + 4], d[q], 0x07060302u);
+        o[3] = __builtin_amdgcn_perm(d[q + 12], d[q + 8], 0x07060302u);
+        *(lds_u32x4ptr)(dst + (uint32_t)(q * 16)) = o;
+      }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) sum = dot2_ones<DT>(d[j], sum);
+    sum += __shfl_xor(sum, 1);  // the four chunks of a group sit in adjacent lanes
+    sum += __shfl_xor(sum, 2);
+    if (on && (ch & 3) == 0) *(lds_fptr)(lds_xs + (uint32_t)((ch >> 2) * 16)) = sum;
+  };
+  auto x_stage = [&](const char* xb, bool pre, uint32_t (&xd)[16]) {
+    for (int it0 = 0; it0 < nch; it0 += 512) {
+      const int ch = it0 + tid;
+      const bool on = ch < nch;
+      if (!(pre && it0 == 0)) {
+#pragma unroll
+        for (int j = 0; j < 16; ++j) xd[j] = 0u;
+        if (on) x_load(xb, ch, xd);
+      }
+      x_store(on ? ch : 0, on, xd);
+    }
+  };
+
+  // ---- requests before the first item, in the order the prologue consumes them ----
+  PairWalk cur = pair_walk_first(geo, it_begin);
+  if (lut_loaded) lut_request(cur);
+  else {
+#pragma unroll
+    for (int e = 0; e < 16; e += 2) lp[e >> 1] = DT::pack2((float)(e - 8), (float)(e - 7));
+  }
+  int staged_b = cur.b;
+  uint32_t xd0[16];
+#pragma unroll
+  for (int j = 0; j < 16; ++j) xd0[j] = 0u;
+  if (tid < nch) x_load(p.x + (int64_t)cur.b * p.stride_x, tid, xd0);
+#pragma unroll
+  for (int j = 0; j < R; ++j) {
+    __builtin_amdgcn_sched_barrier(0);
+    issue(cur, s_begin + j, ring[j], j < nl, j == 0);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  x_stage(p.x + (int64_t)cur.b * p.stride_x, true, xd0);
+
+  uint32_t colreg[TILES];
+#pragma unroll
+  for (int t = 0; t < TILES; ++t) colreg[t] = (uint32_t)((t * 32 + c) * 4);
+  const uint32_t xrow = lds_x + (uint32_t)(32 * h);  // this lane's k-quads 2 h, 2 h + 1 of every 32-k chunk
+
+  int table_b = -1;
+  for (int it = it_begin; it < it_end; ++it) {
+    const bool has_next = it + 1 < it_end;
+    PairWalk next = cur;  // (the last item asks for its own rows again)
+    if (has_next) pair_walk_next(geo, next);
+
+    // ---- pair table (see w4_gemm_pair_kernel): only a per-row LUT changes from item to item, a global LUT from problem to problem ----
+    if (it == it_begin || p.qtype == TG_Q_ANY4_ROWWISE || (p.qtype == TG_Q_ANY4_GLOBAL && cur.b != table_b)) {
+      table_b = cur.b;
+      // (the wave number made opaque per item: otherwise the seven comparisons below are hoisted out of the item loop as seven
+      //  live 64-bit lane masks, which alone push the kernel's scalars into spilled lanes)
+      int wv = wave;
+      asm volatile("" : "+s"(wv));
+      uint32_t hw = lp[0];
+#pragma unroll
+      for (int j = 1; j < 8; ++j) hw = (wv == j) ? lp[j] : hw;
+      const lds_u32ptr tb = (lds_u32ptr)(uint32_t)(wave * 2 * 16 * 256 + tcol * 4);
+#pragma unroll
+      for (int a = 0; a < 16; ++a) {
+        tb[a * 64] = __builtin_amdgcn_perm(hw, lp[a >> 1], (a & 1) ? 0x05040302u : 0x05040100u);
+        tb[(16 + a) * 64] = __builtin_amdgcn_perm(hw, lp[a >> 1], (a & 1) ? 0x07060302u : 0x07060100u);
+      }
+    }
+    if (cur.b != staged_b) {
+      staged_b = cur.b;
+      uint32_t xd[16];
+      x_stage(p.x + (int64_t)cur.b * p.stride_x, false, xd);
+    }
+    if (lut_loaded) lut_request(next);
+    __syncthreads();  // table and activations visible (and every thread is done with the previous item's partial sums)
+
+    // ---- main loop of the item ----
+    float dacc[TILES] = {0.f, 0.f}, prev[TILES] = {0.f, 0.f}, yacc[TILES] = {0.f, 0.f};
+    float gs[TILES] = {0.f, 0.f}, gz[TILES] = {0.f, 0.f}, xsv = 0.f;
+    // a group starts: the finished group's y += scale * (sum since its start) + zero * sum(x), then the new group's scale | zero
+    // (both lane halves of a row accumulate, the zero-point term only once) and activation sum
+    auto group_start = [&](const Slot& sl, uint32_t xs_addr) {
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) {
+        const float d = dacc[t] - prev[t];
+        prev[t] = dacc[t];
+        yacc[t] = __builtin_fmaf(gz[t], xsv, __builtin_fmaf(gs[t], d, yacc[t]));
+      }
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) {
+        gs[t] = DT::lo_f32(sl.q[t]);
+        gz[t] = h ? 0.f : DT::hi_f32(sl.q[t]);
+      }
+      xsv = *(lds_cfptr)(xs_addr);
+    };
+    // one step = half a 32-k chunk: the activation piece of this lane's k-quad and 8 table lookups ...
+    struct Look {
+      u32x4 xf;
+      uint32_t bf[TILES][4];
+    };
+    auto look = [&](const Slot& sl, uint32_t xst, int u, Look& o) {
+      const int jc = u >> 1, qq = u & 1;
+      o.xf = *(lds_cu32x4ptr)(xst + (uint32_t)(jc * 64 + 16 * qq));
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) {
+        const uint32_t w = sl.w[t][qq * CPS + jc];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o.bf[t][j] = *(lds_cu32ptr)(__builtin_amdgcn_perm(w, colreg[t], 0x0c0c0400u + ((uint32_t)j << 8)));
+      }
+    };
+    // ... and its 8 products
+    auto products = [&](const Look& o) {
+#pragma unroll
+      for (int t = 0; t < TILES; ++t)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) dacc[t] = dot2<DT>(o.bf[t][j], o.xf[j], dacc[t]);
+    };
+
+    const int rounds = __builtin_amdgcn_readfirstlane(max(nl / R, 1));
+    uint32_t xst = xrow + (uint32_t)(s_begin * CPS * 64);  // this lane's pieces of the round's first super-tile
+    uint32_t xs_addr = lds_xs + (uint32_t)(s_begin * 8);   // the round's group: (s / 2) * 16 bytes
+    // One round = R super-tiles = one group; `last`: the peeled round, which refills the ring with the NEXT item's first super-tiles
+    // (always issued, also by waves with an empty slice: the weight stream never drains and the count of loads in flight is the same
+    // on every path).
+    if constexpr (!AHEAD) {
+      auto round = [&](int l0, bool last) {
+#pragma unroll
+        for (int j = 0; j < R; ++j) {
+          if (l0 + j < nl) {
+#pragma unroll
+            for (int u = 0; u < 2 * CPS; ++u) {
+              Look o;
+              look(ring[j], xst + (uint32_t)(j * CPS * 64), u, o);
+              __builtin_amdgcn_sched_barrier(0);
+              if (j == 0 && u == 0) group_start(ring[0], xs_addr);
+              products(o);
+              __builtin_amdgcn_sched_barrier(0);
+            }
+          }
+          if (last) issue(next, s_begin + j, ring[j], has_next && j < nl, j == 0);
+          else issue(cur, s_begin + l0 + j + R, ring[j], l0 + j + R < nl, j == 0);
+        }
+      };
+      int l0 = 0;
+      for (int rd = 0; rd < rounds - 1; ++rd, l0 += R, xst += R * CPS * 64, xs_addr += 16) round(l0, false);
+      round(l0, true);
+    } else {
+      // step v of a round (slot v / 4, step v % 4 of it) multiplies what was looked up one step earlier, behind the lookups of step
+      // v + 1; a slot is refilled right behind its last lookups.  Look-ahead registers alternate: 8 steps per round, so a round starts
+      // and ends on la[0].
+      Look la[2];
+      auto round = [&](int l0, bool last) {
+#pragma unroll
+        for (int v = 0; v < 4 * R; ++v) {
+          if (v == 0) group_start(ring[0], xs_addr);  // (its LDS read goes out in front of the next step's)
+          if (v + 1 < 4 * R) look(ring[(v + 1) >> 2], xst + (uint32_t)(((v + 1) >> 2) * CPS * 64), (v + 1) & 3, la[(v + 1) & 1]);
+          else if (!last) look(ring[0], xst + (uint32_t)(R * CPS * 64), 0, la[0]);
+          if ((v & 3) == 2) {
+            const int j = v >> 2;
+            if (last) issue(next, s_begin + j, ring[j], has_next, j == 0);
+            else issue(cur, s_begin + l0 + j + R, ring[j], true, j == 0);
+          }
+          products(la[v & 1]);
+          __builtin_amdgcn_sched_barrier(0);
+        }
+      };
+      if (nl > 0) {
+        look(ring[0], xst, 0, la[0]);
+        __builtin_amdgcn_sched_barrier(0);
+        int l0 = 0;
+        for (int rd = 0; rd < rounds - 1; ++rd, l0 += R, xst += R * CPS * 64, xs_addr += 16) round(l0, false);
+        round(l0, true);
+      } else {
+#pragma unroll
+        for (int j = 0; j < R; ++j) issue(next, s_begin + j, ring[j], false, j == 0);
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < TILES; ++t) {  // the last group of the slice
+      const float d = dacc[t] - prev[t];
+      yacc[t] = __builtin_fmaf(gz[t], xsv, __builtin_fmaf(gs[t], d, yacc[t]));
+      yacc[t] += __shfl_xor(yacc[t], 32);  // the two k-slots of a row live in lanes c and c + 32
+    }
+
+    // ---- split-K tail: the partial sums of the 8 waves meet in LDS and are added in wave order ----
+    if (lane < 32) {
+#pragma unroll
+      for (int t = 0; t < TILES; ++t) *(lds_fptr)(lds_red + (uint32_t)(((wave * TILES + t) * 32 + lane) * 4)) = yacc[t];
+    }
+    __syncthreads();  // partial sums visible; every wave is done with this item's table
+    if (tid < 64) {   // thread = row of the block (tile tid / 32, lane tid % 32)
+      float sum = 0.f;
+#pragma unroll
+      for (int w = 0; w < WAVES; ++w) sum += *(lds_fptr)(lds_red + (uint32_t)((w * 64 + tid) * 4));
+      *reinterpret_cast<uint16_t*>(p.y + (int64_t)cur.b * p.stride_y + (cur.rb * 64 + tid) * 2) = DT::from_f32(sum);
+    }
+    cur = next;
+  }
 }

@@ -211,16 +211,17 @@ def aside_format(w: torch.Tensor, k: int) -> str:
 
 
 _PLANS = {_lib.TG_PLAN_SPLITK: "splitk", _lib.TG_PLAN_STREAM: "stream", _lib.TG_PLAN_PAIR: "pair", _lib.TG_PLAN_PAIR_XR: "pair_xr", _lib.TG_PLAN_GEMV: "gemv",
-          _lib.TG_PLAN_TILE: "tile"}
+          _lib.TG_PLAN_TILE: "tile", _lib.TG_PLAN_PAIR_M1_LEAN: "pair_m1_lean"}
 
 
 def gemm_w4_plan(m: int, wrows: int, k: int, group: int, qtype: int, weight_on_right: bool = True, inner_k_tiles: int = 4,
                  dtype=torch.bfloat16, batch: int = 1, numerics: str | None = None, workspace: bool = True, detail: bool = False,
-                 weight_format: str | None = None) -> str:
+                 weight_format: str | None = None, lean: bool = False) -> str:
     """Which kernel family tg_gemm_w4 launches for this problem (tg_gemm_w4_plan; nothing is launched, no GPU needed):
     'pair' = pair-table kernels, group-scaled numerics; 'stream' / 'splitk' = reference-numerics kernels.
     `workspace`: the caller provides the scratch tg_gemm_w4_workspace_bytes asks for (the ops of this module do).
-    `detail`: name the member of the pair-table family too ('pair_xr' = w4_gemm_xr_kernel, activations resident in registers)."""
+    `detail`: name the member of the pair-table family too ('pair_xr' = w4_gemm_xr_kernel, activations resident in registers); with
+    `lean` also 'pair_m1_lean' = w4_pair_m1_lean_kernel, the plain stacked launch of one activation row (tg_gemm_w4_plan_detail)."""
     buf = ctypes.create_string_buffer(256)
     p = (ctypes.addressof(buf) + 63) & ~63  # a non-NULL, aligned dummy: the planner never dereferences data pointers
     args = W4Gemm(x=p, w=p, qinfo=p, lut=p, y=p, m=m, wrows=wrows, k=k, group=group, qtype=qtype,
@@ -233,7 +234,7 @@ def gemm_w4_plan(m: int, wrows: int, k: int, group: int, qtype: int, weight_on_r
         _lib.check(need if need < 0 else 0, "tg_gemm_w4_workspace_bytes")
         if need > 0:
             args.workspace, args.workspace_bytes = p, need
-    rc = _L.tg_gemm_w4_plan(ctypes.byref(args), 0)
+    rc = (_L.tg_gemm_w4_plan_detail if detail and lean else _L.tg_gemm_w4_plan)(ctypes.byref(args), 0)
     _lib.check(rc if rc < 0 else 0, "tg_gemm_w4_plan")
     plan = _PLANS[rc]
     return plan if detail else plan.split("_")[0]

@@ -256,6 +256,12 @@ enum { TG_PLAN_SPLITK = 1, TG_PLAN_STREAM = 2, TG_PLAN_PAIR = 3, TG_PLAN_PAIR_XR
 enum { TG_LAYOUT_RM = 0, TG_LAYOUT_TC_A = 1 };
 TG_API int tg_gemm_w4_plan(const tg_w4_gemm* args, int device);
 
+/* tg_gemm_w4_plan, one level finer: a call that the pair-table family runs on its lean kernel for ONE activation row
+ * (w4_pair_m1_lean_kernel: plain stacked launches, innerKTiles 4, g = 128, int4 / any4, whole 64-row blocks, no fused stage) answers
+ * TG_PLAN_PAIR_M1_LEAN instead of TG_PLAN_PAIR; every other answer is tg_gemm_w4_plan's. */
+enum { TG_PLAN_PAIR_M1_LEAN = 7 };
+TG_API int tg_gemm_w4_plan_detail(const tg_w4_gemm* args, int device);
+
 /* Bytes of `workspace` with which tg_gemm_w4 takes its fastest kernel for these arguments (0: none needed; negative: the
  * TG_E_* code tg_gemm_w4 would return).  Today: TG_NUM_FAST, Bint4 weights, stacked launches whose activation block of one
  * pass does not fit next to the pair table in LDS (m > 4 at k = 4096, any m at k >= 8192): the activations are re-arranged
