@@ -1,7 +1,9 @@
 """Input builders and float64 references for the non-GEMM kernels of the decode stack (include/decode_glue_hip.h).
 
 A plain helper module (not a conftest): it runs on any device and never touches the HIP library.  tests/test_glue_ref_cpu.py checks
-the builders and the references themselves on the CPU; tests/test_gpu_glue_f64.py uses them against the kernels.
+the builders and the references themselves on the CPU; tests/test_gpu_glue_f64.py uses them against the kernels, and
+tests/test_gpu_ragged_f64.py against the per-sequence and paged ones (`ragged_case`: several cases with positions of their own in one
+launch; `page_layout` / `to_pools` / `from_pools`: the same caches as page pools behind a scrambled block table).
 
 Attention cases are built on the CPU from a seeded generator (the same bits whichever device runs the test) and moved with `.to()`.
 A case describes ONE call of an attention entry point: a chunk of T tokens per sequence at positions p0 ... p0 + T - 1 (T = 1: a
@@ -59,7 +61,7 @@ def _target_candidates(pos, p0, rnd):
     return torch.minimum(c.clamp_min(0), pos[:, None])
 
 
-def attn_case(kind, dtype, bs, hl, kvl, d, S, T, p0, seed=0, beta_min=4):
+def attn_case(kind, dtype, bs, hl, kvl, d, S, T, p0, seed=0, beta_min=4, prefix_from=None):
     """One call of an attention entry point (see the module docstring).  Fields of the returned namespace (CPU tensors; `.to(device)`):
       qkv [bs * T, (hl + 2 kvl) d]   the call's input (row b * T + t), cos / sin [S, d] float32
       kc0 / vc0 [bs, kvl, S, d]      the caches before the call: rows [0, p0) hold the prefix, everything else NaN (decoy: the one
@@ -70,7 +72,9 @@ def attn_case(kind, dtype, bs, hl, kvl, d, S, T, p0, seed=0, beta_min=4):
       target [bs, T, hl]             lookup: the position whose V row is the expected output; decoy: the hidden position pointed at
                                      (-1 where there is none and the row is a lookup of its own position)
       want [bs * T, hl * d]          lookup only: the expected output, bit for bit
-      beta, margin                   lookup / decoy: the query scale used and the smallest score margin it gives (>= MARGIN)"""
+      beta, margin                   lookup / decoy: the query scale used and the smallest score margin it gives (>= MARGIN)
+    prefix_from: a case of the same kind, type and geometry whose first min(p0, its p0) cache rows this case takes over (two sequences
+    that share a prefix, as forked sequences of a paged cache do); everything else is drawn as without it."""
     assert kind in ("lookup", "decoy", "peaked", "normal") and hl % kvl == 0 and 0 <= p0 and p0 + T <= S and T >= 1
     rep, scale = hl // kvl, 1.0 / math.sqrt(d)
     gen = torch.Generator().manual_seed(seed * 7919 + 13)
@@ -85,6 +89,9 @@ def attn_case(kind, dtype, bs, hl, kvl, d, S, T, p0, seed=0, beta_min=4):
         assert d >= 64, "+-1 key codes collide at small head dimensions"
         keys = (torch.randint(0, 2, (bs, kvl, P, d), generator=gen) * 2 - 1).float()
         vals = (torch.randint(-32, 32, (bs, kvl, P, d), generator=gen) * 2 + 1).float() / 16.0
+        if prefix_from is not None:  # (lookup / decoy prefixes are un-roped +-1 codes: k_all holds them exactly)
+            n = min(p0, prefix_from.p0)
+            keys[:, :, :n], vals[:, :, :n] = prefix_from.k_all[:, :, :n].float(), prefix_from.v_all[:, :, :n].float()
         if kind == "lookup":
             rnd = (torch.rand(T, generator=gen) * (pos + 1)).long()
             cand = _target_candidates(pos, p0, torch.minimum(rnd, pos))
@@ -130,6 +137,9 @@ def attn_case(kind, dtype, bs, hl, kvl, d, S, T, p0, seed=0, beta_min=4):
         k_all = torch.randn(bs, kvl, P, d, generator=gen).to(dtype)
         v_all = torch.randn(bs, kvl, P, d, generator=gen).to(dtype)
         q = (torch.randn(bs, T, hl, d, generator=gen) * (4.0 if kind == "peaked" else 1.0)).to(dtype)
+        if prefix_from is not None:
+            n = min(p0, prefix_from.p0)
+            k_all[:, :, :n], v_all[:, :, :n] = prefix_from.k_all[:, :, :n], prefix_from.v_all[:, :, :n]
     kraw = k_all[:, :, p0:p0 + T].transpose(1, 2)                                               # [bs, T, kvl, d]: the chunk's un-roped k
     vraw = v_all[:, :, p0:p0 + T].transpose(1, 2)
     case.qkv = torch.cat([q.reshape(bs * T, hl * d), kraw.reshape(bs * T, kvl * d), vraw.reshape(bs * T, kvl * d)], dim=1).contiguous()
@@ -366,3 +376,209 @@ def swiglu_input(dtype, bs, il, device, seed=0):
         gu[:, col] = gates[i % 7].to(dtype)
         gu[:, il + col] = ups[(torch.arange(bs) + i) % 8].to(dtype)
     return gu.to(device)
+
+
+# ---- ragged launches: several scalar cases in one call of a per-sequence (_seq) or paged entry point ----
+
+def ragged_case(cases, T=None, slots=None, cache_bs=None, caches=True):
+    """One launch made of `attn_case` results built with bs = 1 that share kind, type, geometry and S and may differ in p0 and T; None
+    is an inactive sequence.  A launch whose common T is 1 is a decode step (inactive: pos = -1, the sequence keeps its own slot);
+    otherwise a prefill chunk (inactive: len = 0, slot = -1, pos = 0).  Fields (CPU tensors; `.to(device)` moves them):
+      qkv [n * T, (hl + 2 kvl) d]   row i * T + t; rows t >= T_i (and every row of an inactive sequence) hold finite random filler
+      pos / lengths / slots [n]     int64
+      kc0 / vc0 [cache_bs, kvl, S, d]   before the call: slot slots[i] is case i's cache; a slot nobody uses holds a finite random prefix
+                                    of its own (rows[slot] rows) under NaN, so that a read of the wrong slot returns wrong finite data
+      kc1 / vc1                     after the call, bit for bit
+      rows [cache_bs]               finite rows per slot after the call (what a live block table has to map)
+      seqs [n]                      the scalar cases (None: inactive), each with `ref64` [1, T_i, hl, d] added: want, q16, k_all, v_all,
+                                    visible, target are theirs
+    caches = False leaves out kc0 / vc0 / kc1 / vc1 (launches whose caches are too large to build on the host)."""
+    live = [c for c in cases if c is not None]
+    f = live[0]
+    for c in live:
+        assert c.bs == 1 and (c.kind, c.dtype, c.hl, c.kvl, c.d, c.S) == (f.kind, f.dtype, f.hl, f.kvl, f.d, f.S)
+    n = len(cases)
+    T = max(c.T for c in live) if T is None else T
+    assert all(c.T <= T for c in live)
+    decode = T == 1
+    if slots is None:
+        slots = [i if (c is not None or decode) else -1 for i, c in enumerate(cases)]
+    assert len(slots) == n and all((c is None and not decode) == (s < 0) for c, s in zip(cases, slots))
+    used = [s for s in slots if s >= 0]
+    assert len(set(used)) == len(used)
+    cache_bs = max(n if decode else 0, max(used) + 1) if cache_bs is None else cache_bs
+    assert cache_bs > max(used) and (not decode or (cache_bs == n and slots == list(range(n))))
+    width = (f.hl + 2 * f.kvl) * f.d
+    gen = torch.Generator().manual_seed(977 + sum(c.seed for c in live))
+    qkv = torch.randn(n, T, width, generator=gen).to(f.dtype)
+    for i, c in enumerate(cases):
+        if c is not None:
+            qkv[i, :c.T] = c.qkv
+            c.ref64 = case_ref64(c)
+    rc = SimpleNamespace(kind=f.kind, dtype=f.dtype, hl=f.hl, kvl=f.kvl, d=f.d, S=f.S, rep=f.rep, scale=f.scale, cos=f.cos, sin=f.sin,
+                         n=n, T=T, decode=decode, cache_bs=cache_bs, seqs=list(cases), qkv=qkv.view(n * T, width).contiguous(),
+                         pos=torch.tensor([-1 if c is None and decode else 0 if c is None else c.p0 for c in cases]),
+                         lengths=torch.tensor([0 if c is None else c.T for c in cases]), slots=torch.tensor(slots))
+    rows = [0] * cache_bs
+    for c, s in zip(cases, slots):
+        if c is not None:
+            rows[s] = c.k_all.shape[2]
+    if caches:
+        kc0 = torch.full((cache_bs, f.kvl, f.S, f.d), float("nan"), dtype=f.dtype)
+        vc0 = kc0.clone()
+        for s in range(cache_bs):
+            if s not in used or cases[slots.index(s)] is None:  # nobody's slot (decode: an inactive sequence's)
+                rows[s] = min(f.S, 40 + 37 * s)
+                kc0[s, :, :rows[s]] = torch.randn(f.kvl, rows[s], f.d, generator=gen).to(f.dtype)
+                vc0[s, :, :rows[s]] = torch.randn(f.kvl, rows[s], f.d, generator=gen).to(f.dtype)
+        kc1, vc1 = kc0.clone(), vc0.clone()
+        for c, s in zip(cases, slots):
+            if c is not None:
+                kc0[s], vc0[s] = c.kc0[0], c.vc0[0]
+                kc1[s], vc1[s] = (x[0] for x in expected_caches(c))
+        rc.kc0, rc.vc0, rc.kc1, rc.vc1 = kc0, vc0, kc1, vc1
+    rc.rows = rows
+
+    def to(device):
+        moved = SimpleNamespace(**vars(rc))
+        for name, val in vars(rc).items():
+            if torch.is_tensor(val):
+                setattr(moved, name, val.to(device))
+        moved.seqs = [None if c is None else c.to(device) for c in rc.seqs]
+        return moved
+
+    rc.to = to
+    return rc
+
+
+def page_layout(cache_bs, S, page_size, seed, spare=2, shared=()):
+    """(table int32 [cache_bs, S / page_size], num_pages): physical ids are a seeded permutation of range(num_pages), `spare` of them
+    referenced by nobody; each (a, b, n) of `shared` gives the first n entries of row b the pages of row a (the caller guarantees that
+    both slots hold the same rows there)."""
+    assert S % page_size == 0
+    entries = S // page_size
+    assert all(n <= entries and a != b for a, b, n in shared)
+    num_pages = cache_bs * entries - sum(n for _, _, n in shared) + spare
+    perm = torch.randperm(num_pages, generator=torch.Generator().manual_seed(4241 + seed)).tolist()
+    table = torch.full((cache_bs, entries), -1, dtype=torch.int32)
+    take = {b: (a, n) for a, b, n in shared}
+    for b in sorted(range(cache_bs), key=lambda r: r in take):  # (sharing rows after the rows they share with)
+        first = 0
+        if b in take:
+            a, first = take[b]
+            table[b, :first] = table[a, :first]
+        for e in range(first, entries):
+            table[b, e] = perm.pop()
+    assert len(perm) == spare
+    return table, num_pages
+
+
+def trim(table, mapped_rows, page_size):
+    """A copy of `table` with the entries above each slot's last needed page (mapped_rows[slot] rows are needed) at -1: the normal
+    state of a live table."""
+    t = table.clone()
+    for s, r in enumerate(mapped_rows):
+        t[s, -(-int(r) // page_size):] = -1
+    return t
+
+
+def cache_pages(cache, page_size):
+    """[cache_bs, kvl, S, d] -> its pages [cache_bs * S / page_size, kvl, page_size, d], in the order of a flattened table."""
+    cb, kvl, S, d = cache.shape
+    return cache.view(cb, kvl, S // page_size, page_size, d).permute(0, 2, 1, 3, 4).reshape(-1, kvl, page_size, d)
+
+
+def to_pools(cache, table, page_size, num_pages, fill):
+    """[cache_bs, kvl, S, d] -> the pool [num_pages, kvl, page_size, d] behind `table`; pages nobody references hold `fill`."""
+    kvl, d = cache.shape[1], cache.shape[3]
+    pool = torch.full((num_pages, kvl, page_size, d), fill, dtype=cache.dtype, device=cache.device)
+    pages = cache_pages(cache, page_size)
+    idx = table.to(cache.device).long().flatten()
+    pool[idx[idx >= 0]] = pages[idx >= 0]
+    return pool
+
+
+def from_pools(pool, table, page_size):
+    """The contiguous view [cache_bs, kvl, S, d] of a pool behind `table`; unmapped pages read as NaN."""
+    _, kvl, ps, d = pool.shape
+    assert ps == page_size
+    cb, entries = table.shape
+    idx = table.to(pool.device).long().flatten()
+    pages = torch.full((cb * entries, kvl, ps, d), float("nan"), dtype=pool.dtype, device=pool.device)
+    pages[idx >= 0] = pool[idx[idx >= 0]]
+    return pages.view(cb, entries, kvl, ps, d).permute(0, 2, 1, 3, 4).reshape(cb, kvl, entries * ps, d)
+
+
+def high_page_table(cache_bs, entries, num_pages, seed):
+    """A table whose rows are a seeded permutation of the HIGHEST cache_bs * entries page ids of a pool (pools above 4 GiB)."""
+    n = cache_bs * entries
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(977 + seed)) + (num_pages - n)
+    return perm.to(torch.int32).view(cache_bs, entries)
+
+
+# the shapes of tests/test_gpu_ragged_f64.py: several positions per launch.  (positions of one launch, max_seq); None: inactive
+RAGGED_GEOMS = [(4, 2, 64), (6, 2, 64), (3, 1, 128), (32, 8, 128), (8, 8, 128)]   # + GENERIC_PROBE_GEOM on the non-paged general / split kernels
+RAGGED_DECODE = [([0, 31, 32, 700], 1024), ([255, 256, 257, 1023], 1024), ([5, None, 64, 33], 1024), ([8191, 4096, 0, 8190], 8192)]
+RAGGED_SPLIT_LONG = ([32767, 257], 32768)   # split kernels only (nsplit 8), on RAGGED_SPLIT_LONG_GEOMS
+RAGGED_SPLIT_LONG_GEOMS = [(4, 2, 128), (6, 2, 64)]   # (4, 2, 128) is not in RAGGED_GEOMS: it runs this launch alone (ragged_decode_geoms)
+RAGGED_SPLITS = SPLITS
+# prefill: ((T, p0) per sequence, slots, cache_bs, max_seq); the second set has every p0 on a page edge
+RAGGED_PREFILL = [([(129, 257), (17, 1007), (64, 0), (1, 63), None, (33, 64)], [4, 0, 5, 2, -1, 1], 6, 1024),
+                  ([(65, 128), (128, 256), (15, 0)], [3, 5, 0], 6, 1024)]
+RAGGED_PREFILL_LONG = ([(300, 7892), (64, 4090)], [1, 0], 2, 8192)   # on PREFILL_LONG_GEOMS
+PAGE_SIZES = (64, 128, 256, None)   # None: max_seq itself, one page per sequence
+# addresses above 4 GiB: pools of 32 KiB pages that end just above the line, caches of 16 MiB slots whose slot 256 starts on it
+BIG_POOL_PAGES, BIG_POOL_GEOM, BIG_POOL_PAGE, BIG_POOL_S = 131072 + 32, (4, 2, 128), 64, 1024
+BIG_CACHE_BS, BIG_CACHE_GEOM, BIG_CACHE_S = 260, (8, 8, 128), 8192
+BIG_DECODE_POSITIONS = [8191, 4096]
+# ragged seeds whose lookup / decoy case misses the margin at beta <= 16 (found by tests/test_glue_ref_cpu.py): (T, p0, i) -> seed
+RAGGED_RESEED = {}
+
+
+def page_sizes(S):
+    """256 and max_seq itself (one page per sequence) run for the 1024 cases only."""
+    return [S if ps is None else ps for ps in PAGE_SIZES] if S == 1024 else [64, 128]
+
+
+def ragged_seed(T, p0, i):
+    return RAGGED_RESEED.get((T, p0, i), case_seed(T, p0) + 1009 * (i + 1))
+
+
+def ragged_decode_geoms(paged):
+    """The geometries of the ragged decode tests: RAGGED_GEOMS (+ GENERIC_PROBE_GEOM on the non-paged general / split kernels), and the
+    geometries of RAGGED_SPLIT_LONG_GEOMS that are not among them, which run the 32768-position launch alone."""
+    geoms = RAGGED_GEOMS + ([] if paged else [GENERIC_PROBE_GEOM])
+    return geoms + [g for g in RAGGED_SPLIT_LONG_GEOMS if g not in geoms]
+
+
+def ragged_decode_sets(geom):
+    """(positions, max_seq, split_only) of the decode launches of a geometry: RAGGED_DECODE on RAGGED_GEOMS and GENERIC_PROBE_GEOM, and
+    RAGGED_SPLIT_LONG on every geometry of RAGGED_SPLIT_LONG_GEOMS."""
+    sets = [(p, S, False) for p, S in RAGGED_DECODE] if geom in RAGGED_GEOMS + [GENERIC_PROBE_GEOM] else []
+    return sets + ([RAGGED_SPLIT_LONG + (True,)] if geom in RAGGED_SPLIT_LONG_GEOMS else [])
+
+
+def ragged_prefill_sets(geom):
+    return RAGGED_PREFILL + ([RAGGED_PREFILL_LONG] if geom in PREFILL_LONG_GEOMS else [])
+
+
+def ragged_decode_case(kind, dtype, geom, positions, S, caches=True):
+    hl, kvl, d = geom
+    return ragged_case([None if p is None else attn_case(kind, dtype, 1, hl, kvl, d, S, 1, p, ragged_seed(1, p, i))
+                        for i, p in enumerate(positions)], caches=caches)
+
+
+def ragged_prefill_case(kind, dtype, geom, seqs, slots, cache_bs, S, caches=True):
+    hl, kvl, d = geom
+    return ragged_case([None if tp is None else attn_case(kind, dtype, 1, hl, kvl, d, S, tp[0], tp[1], ragged_seed(tp[0], tp[1], i))
+                        for i, tp in enumerate(seqs)], slots=slots, cache_bs=cache_bs, caches=caches)
+
+
+def shared_pair_case(kind, dtype, geom, S, T, p0, positions=None):
+    """Three sequences in slots 0, 1, 2 of which 0 and 2 share the cache rows [0, p0) and differ in everything they append: a decode step
+    (T = 1) or a prefill chunk at p0 (a multiple of the page size)."""
+    hl, kvl, d = geom
+    a = attn_case(kind, dtype, 1, hl, kvl, d, S, T, p0, ragged_seed(T, p0, 0))
+    b = attn_case(kind, dtype, 1, hl, kvl, d, S, max(1, T // 2), p0 + 70, ragged_seed(T, p0 + 70, 1))
+    c = attn_case(kind, dtype, 1, hl, kvl, d, S, max(1, T - 3), p0, ragged_seed(T, p0, 2), prefix_from=a)
+    return ragged_case([a, b, c], slots=None if T == 1 else [0, 1, 2], cache_bs=3)
