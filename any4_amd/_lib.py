@@ -68,7 +68,8 @@ class PeerGather(ctypes.Structure):
 
 # The twelve fused attention entry points of include/decode_glue_hip.h: four bases, each with a `_seq` flavour (a position per sequence), two of
 # them with `_mx8` ones (an mx8 KV cache) -- and, bound as a group of their own (PAGED_SYMBOLS; the header declares them DG_PAGED_API), the
-# `_paged` flavour of three bases (a page pool behind a block table; per sequence, 16-bit rows).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
+# `_paged` flavour of three bases (a page pool behind a block table; per sequence, 16-bit rows) -- and, a group of their own too (KV8_ONLINE_SYMBOLS;
+# DG_KV8_API), dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache (kv8_online_signature).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
 # puts a call's values in the same order.
 _ci, _cf = ctypes.c_int, ctypes.c_float
 ATTN_BASES = {"dg_rope_attn": False, "dg_rope_attn_online": False, "dg_rope_attn_split": True, "dg_prefill_attn": True}  # base: has _mx8 flavours
@@ -96,6 +97,15 @@ def attn_signature(base, seq=False, mx8=False, paged=False):
             + [("out", _vp)] + (_ATTN_SCRATCH if split else []) + [("bs", _i64)] + ([("T", _i64)] if prefill else [])
             + ([("cache_bs", _i64)] if prefill and seq else []) + shape + ([("nsplit", _ci)] if split else []) + _ATTN_TAIL)
     return base + ("_paged" if paged else ("_mx8" if mx8 else "") + ("_seq" if seq else "")), tuple(args)
+
+
+def kv8_online_signature(seq=False):
+    """(entry point, ((argument name, ctype), ...)) of dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache, which takes
+    the argument list of dg_rope_attn_split_mx8(_seq).  A function of its own: attn_signature("dg_rope_attn_online", mx8=True) stays a
+    KeyError, as that base has no `_mx8` flavour among the twelve."""
+    args = (_ATTN_HEAD + _ATTN_CACHES + _ATTN_EXPS + [("out", _vp)] + _ATTN_SCRATCH + [("bs", _i64)] + _ATTN_SHAPE + [("nsplit", _ci)]
+            + _ATTN_TAIL)
+    return "dg_rope_attn_online_mx8" + ("_seq" if seq else ""), tuple(args)
 
 
 # name -> argtypes, exactly the prototypes of include/tinygemm_hip.h
@@ -154,6 +164,12 @@ for _base in ATTN_PAGED_BASES:
     _name, _args = attn_signature(_base, paged=True)
     PAGED_SYMBOLS[_name] = [t for _, t in _args]
 
+# name -> argtypes of the one-barrier kernel's mx8 entry points (the DG_KV8_API prototypes of include/decode_glue_hip.h); load() binds them too
+KV8_ONLINE_SYMBOLS = {}
+for _seq in (False, True):
+    _name, _args = kv8_online_signature(_seq)
+    KV8_ONLINE_SYMBOLS[_name] = [t for _, t in _args]
+
 _lib = None
 
 
@@ -168,7 +184,7 @@ def load() -> ctypes.CDLL:
             "There is no CPU/PyTorch fallback for the tinygemm ops."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS}.items():
+    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS, **KV8_ONLINE_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # a stale build: the header declares a symbol the .so does not export

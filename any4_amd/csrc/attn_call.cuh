@@ -1,5 +1,5 @@
 // attn_call.cuh -- one attention call of the decode stack, described once (include/decode_glue_hip.h: dg_decode_attn, dg_rope_attn*,
-// dg_prefill_attn*, the _paged ones among them).  Host-only, as GemmParams is: no kernel receives an AttnCall, every kernel keeps its own argument list.  Included by
+// dg_prefill_attn*, the _paged and the _online_mx8 ones among them).  Host-only, as GemmParams is: no kernel receives an AttnCall, every kernel keeps its own argument list.  Included by
 // decode_glue.cuh (tinygemm_hip.hip) and tg_prefill.hip; an entry point builds the call (attn_call), sets what only it takes and hands it
 // to its kind's launcher, which validates it with check_attn and keeps only DeviceScope, LDS size, grid and the choice of kernel.
 #pragma once
@@ -13,7 +13,7 @@ enum AttnKind {
   ATTN_UNFUSED,  // dg_decode_attn: q is already roped (AttnCall::qkv holds it), no tables
   ATTN_GENERAL,  // dg_rope_attn(_seq): one 256-thread block per head, any d % 8 == 0
   ATTN_ONLINE,   // dg_rope_attn_online(_seq, _paged): the one-barrier kernel, d = 64 / 128
-  ATTN_SPLIT,    // dg_rope_attn_split(_seq, _mx8, _mx8_seq, _paged): nsplit blocks per head and a scratch buffer
+  ATTN_SPLIT,    // dg_rope_attn_split(_seq, _mx8, _mx8_seq, _paged), dg_rope_attn_online_mx8(_seq): nsplit blocks per head and a scratch buffer
   ATTN_PREFILL,  // dg_prefill_attn(_seq, _mx8, _mx8_seq, _paged): T tokens per sequence
 };
 
@@ -35,6 +35,7 @@ struct AttnCall {
   tg_stream_t stream;
   bool seq = false;  // `pos` holds a position per sequence (the _seq entry points)
   bool kv8 = false;  // mx8 caches (the _mx8 entry points)
+  bool one_barrier = false;  // a split call that must run the one-barrier kernel (dg_rope_attn_online_mx8): that kernel's d and alignment
   // paged: k_cache / v_cache are pools [num_pages][kvl][page_size][d] behind `table` int32 [cache_bs][max_seq / page_size] (the _paged entry points)
   bool paging = false;
   const int32_t* table = nullptr;
@@ -43,6 +44,7 @@ struct AttnCall {
   // what an entry point takes on top of the sixteen common arguments (attn_call)
   AttnCall& per_sequence() { seq = true; return *this; }
   AttnCall& mx8(void* ke, void* ve) { kv8 = true; k_exp = ke; v_exp = ve; return *this; }
+  AttnCall& online() { one_barrier = true; return *this; }
   AttnCall& split(void* s, int64_t bytes, int n) { scratch = s; scratch_bytes = bytes; nsplit = n; return *this; }
   AttnCall& chunk(int64_t tokens) { T = tokens; return *this; }
   AttnCall& slots(const int64_t* l, const int64_t* s, int64_t n) { len = l; slot = s; cache_bs = n; return per_sequence(); }
@@ -87,9 +89,9 @@ inline int check_attn(AttnKind kind, const AttnCall& c) {
     return TG_E_NULL;
   if (!(c.dtype == TG_BF16 || c.dtype == TG_F16)) return TG_E_DTYPE;
   if (bs <= 0 || c.hl <= 0 || c.kvl <= 0 || c.hl % c.kvl != 0 || max_seq <= 0) return TG_E_SHAPE;
-  // d: the one-barrier and the prefill kernel are instantiated for 64 / 128 (every paged call runs one of the two); a 256-thread block of
-  // the others works in d / 8 columns
-  if (online || prefill || c.paging ? !(d == 64 || d == 128) : (d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0)) return TG_E_SHAPE;
+  // d: the one-barrier and the prefill kernel are instantiated for 64 / 128 (every paged call runs one of the two, and so does a split
+  // call held to the one-barrier kernel); a 256-thread block of the others works in d / 8 columns
+  if (online || prefill || c.paging || c.one_barrier ? !(d == 64 || d == 128) : (d < 8 || d % 8 != 0 || d > 256 || (256 % (d / 8)) != 0)) return TG_E_SHAPE;
   // max_seq: LDS holds a score per cache position (8192; prefill fills those caches) or per position of a chunk (split: 65536, the launcher
   // refuses what does not fit); the one-barrier kernel keeps no scores: its bound is the 32-bit byte offset of a row within a head
   // (paged: that offset is taken within a page; the decode entry points keep the split kind's 65536)
@@ -112,7 +114,7 @@ inline int check_attn(AttnKind kind, const AttnCall& c) {
   // single entries and aligned by contract
   if (!aligned16(c.k_cache) || !aligned16(c.v_cache) || !aligned16(c.k_exp) || !aligned16(c.v_exp) || !aligned16(c.scratch)) return TG_E_ALIGN;
   if (!aligned16(c.table)) return TG_E_ALIGN;
-  if ((online || prefill || c.paging) && (!aligned16(c.qkv) || !aligned16(c.cos) || !aligned16(c.sin))) return TG_E_ALIGN;
+  if ((online || prefill || c.paging || c.one_barrier) && (!aligned16(c.qkv) || !aligned16(c.cos) || !aligned16(c.sin))) return TG_E_ALIGN;
   if (prefill && !aligned16(c.out)) return TG_E_ALIGN;
   return 0;
 }

@@ -563,15 +563,24 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 // The paging argument is the kernel's last parameter and exists only for PAGED (PG = KvPages): this kernel reads gridDim from the implicit
 // arguments BEHIND the explicit ones, and even an empty trailing struct moves those by eight bytes -- the contiguous flavours would keep
 // their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
+// KV8 (the dg_rope_attn_online_mx8 entry points; PG = Kv8Exps, the same optional last parameter; never with PAGED): the caches are mx8
+// (kv8.cuh).  Same lanes, same partition of work: a lane's K / V piece is 8 code bytes and one exponent byte, requested where the
+// 16-byte pieces are (the speculative ones in front of `pos`), clamped and masked alike, and converted to the 16-bit type on use --
+// behind the conversion every sum and rounding point is the 16-bit flavour's.  The new token's roped k row and raw v row are encoded
+// from the registers they are in (mx8_encode_piece: the host encoder's bytes) and enter the scores and the value sum DECODED.
 template <typename DT, int LPR, bool SEQ = false, bool PAGED = false, typename... PG>
 __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                                const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
                                                                uint16_t* __restrict__ k_cache, uint16_t* __restrict__ v_cache,
                                                                uint16_t* __restrict__ out, int hl, int kvl, int64_t max_seq, float scale,
                                                                unsigned long long* trace, float* part, int* counters, PG... pages) {
-  static_assert(sizeof...(PG) == (PAGED ? 1 : 0) && (!PAGED || SEQ), "PAGED: one KvPages argument, a position per sequence");
+  constexpr bool KV8 = Kv8Pack<PG...>::value;  // (the flavour is the pack's type: no template parameter that would rename the others)
+  static_assert(sizeof...(PG) == (PAGED || KV8 ? 1 : 0) && (!PAGED || SEQ), "PAGED: one KvPages argument, a position per sequence");
+  static_assert(!(PAGED && KV8), "there is no paged mx8 flavour");
   [[maybe_unused]] KvPages G{};
   if constexpr (PAGED) G = kv_pages_arg(pages...);
+  [[maybe_unused]] Kv8Exps X{};
+  if constexpr (KV8) X = kv8_exps_arg(pages...);
   // gridDim.y = NS > 1: split over the sequence.  Block (head, c) takes the 32-row iterations c, c + NS, c + 2 NS, ... of the context
   // (a partition that does not depend on the position: the speculative requests below stay possible), writes its (max, sum,
   // unnormalised output) to `part`, and the last block of a head to arrive (self-resetting counter: replayable in a graph) combines
@@ -609,6 +618,15 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     else return 0;
   };
   auto piece = [&](const char* base, int r) -> u32x4 { return *reinterpret_cast<const u32x4*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 4)); };
+  // KV8: the head's rows are D code bytes and D / 32 exponent bytes each -- (row r, piece i) is the 8 bytes at ((r * LPR + i) << 3) and
+  // byte r * (D / 32) + (i >> 2) of the exponents (a wave's exponent bytes of one iteration: 16 contiguous bytes)
+  [[maybe_unused]] const int64_t head0 = ((int64_t)b * kvl + kv) * max_seq;  // first cache row of this (sequence, kv head)
+  [[maybe_unused]] const char* K8 = reinterpret_cast<const char*>(k_cache) + head0 * D;
+  [[maybe_unused]] const char* V8 = reinterpret_cast<const char*>(v_cache) + head0 * D;
+  [[maybe_unused]] const uint8_t* KE = KV8 ? X.k_exp + head0 * (D / 32) : nullptr;
+  [[maybe_unused]] const uint8_t* VE = KV8 ? X.v_exp + head0 * (D / 32) : nullptr;
+  [[maybe_unused]] auto piece8 = [&](const char* base, int r) -> u32x2 { return *reinterpret_cast<const u32x2*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 3)); };
+  [[maybe_unused]] auto pexp = [&](const uint8_t* base, int r) -> uint32_t { return base[(uint32_t)r * (D / 32) + ((uint32_t)i >> 2)]; };
   // the first NSPEC iterations' rows are requested BEFORE the position is known (rows past it are valid memory and masked later):
   // the read of `pos` is a dependent round trip the K / V requests of a short context need not wait for
   // (all of the first chunk: same box, Llama-3-8B decode, 2 -> 8 iterations: 620 -> 620 tokens/s at position 136, 544 -> 553 at 900,
@@ -618,7 +636,8 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
 #define DG_ATTN_NSPEC 8
 #endif
   constexpr int NSPEC = NI < DG_ATTN_NSPEC ? NI : DG_ATTN_NSPEC;
-  u32x4 kk[NI], vv[NI];
+  std::conditional_t<KV8, u32x2, u32x4> kk[NI], vv[NI];
+  [[maybe_unused]] uint32_t ke[KV8 ? NI : 1], ve[KV8 ? NI : 1];  // KV8: the exponent byte of each piece
 #pragma unroll
   for (int it = 0; it < NSPEC; ++it) {
     if constexpr (PAGED) {  // (an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
@@ -626,6 +645,12 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       const int64_t pb = page_bytes(r0);
       kk[it] = piece(K + pb, (r0 & in_page) + grp);
       vv[it] = piece(V + pb, (r0 & in_page) + grp);
+    } else if constexpr (KV8) {
+      const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
+      kk[it] = piece8(K8, rc);
+      vv[it] = piece8(V8, rc);
+      ke[it] = pexp(KE, rc);
+      ve[it] = pexp(VE, rc);
     } else {
       const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
       kk[it] = piece(K, rc);
@@ -653,6 +678,12 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
         const int rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
         kk[it] = piece(K + pb, rc);
         vv[it] = piece(V + pb, rc);
+      } else if constexpr (KV8) {
+        const int rc = r < S - 1 ? r : 0;
+        kk[it] = piece8(K8, rc);
+        vv[it] = piece8(V8, rc);
+        ke[it] = pexp(KE, rc);
+        ve[it] = pexp(VE, rc);
       } else {
         const int rc = r < S - 1 ? r : 0;
         kk[it] = piece(K, rc);
@@ -684,9 +715,26 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     }
     return pack8<DT>(o);
   };
-  const u32x4 qp = rotate(qraw), kn = rotate(kraw);
+  const u32x4 qp = rotate(qraw);
+  u32x4 kn = rotate(kraw), vn = vraw;  // the new token's rows as the scores and the value sum take them
   TG_STAMP(3);
-  if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
+  if constexpr (KV8) {
+    // every row group holds the same row and every lane encodes it (a block is an aligned quad of lanes); from here on the new token
+    // is its DECODED row -- what every later step reads -- and only the block that writes the 16-bit rows stores the bytes
+    u32x2 kc, vc;
+    uint32_t kE, vE;
+    kn = mx8_encode_piece<DT>(kn, kc, kE);
+    vn = mx8_encode_piece<DT>(vraw, vc, vE);
+    if (h % rep == 0 && grp == 0 && cblk == 0) {
+      const int64_t r = head0 + pos;
+      *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + r * D + i * 8) = kc;
+      *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + r * D + i * 8) = vc;
+      if ((i & 3) == 0) {
+        X.k_exp[r * (D / 32) + (i >> 2)] = (uint8_t)kE;
+        X.v_exp[r * (D / 32) + (i >> 2)] = (uint8_t)vE;
+      }
+    }
+  } else if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
     if constexpr (PAGED) {  // (a position whose own table entry is outside the pool writes nothing)
       const int pg = kv_page_write(G, b, (int)pos);
       if (pg >= 0) {
@@ -704,6 +752,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   };
   // ---- this group's rows: running max m, sum l, unnormalised accumulator acc[8] (the lane's 8 elements of the value row) ----
   float m = -INFINITY, l = 0.f, acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  [[maybe_unused]] bool poisoned = false;  // KV8: a score of this row group is NaN
   for (int base = 0; row0_of(base / RPI) < S; base += NI * RPI) {  // (base counts the block's own rows: local iteration base / RPI)
     if (base > 0) request(base, 0);
     float x[NI];
@@ -711,7 +760,9 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
       const int r = row0_of(base / RPI + it) + grp;
-      const u32x4 kr = r == S - 1 ? kn : kk[it];
+      u32x4 kr;
+      if constexpr (KV8) kr = r == S - 1 ? kn : mx8_to16<DT>(kk[it], ke[it]);  // (converted on use; E = 255: NaN in the block's places)
+      else kr = r == S - 1 ? kn : kk[it];
       // (literal indices: with a loop variable hipcc (ROCm 7.2) fed dword 0 of both vectors to all four v_dot2)
       float d2 = dot2<DT>(kr[0], qp[0], 0.f);
       d2 = dot2<DT>(kr[1], qp[1], d2);
@@ -722,6 +773,7 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
       d2 = dpp_add(d2, std::integral_constant<int, 0x141>{});   // row_half_mirror: the other quad of the 8 lanes
       if constexpr (LPR == 16) d2 = dpp_add(d2, std::integral_constant<int, 0x140>{});  // row_mirror: the other half of the 16 lanes
       x[it] = r < S ? round16<DT>(d2) * scale : -INFINITY;
+      if constexpr (KV8) poisoned |= x[it] != x[it];
       cm = fmaxf(cm, x[it]);
     }
     const float mn = fmaxf(m, cm);
@@ -738,11 +790,22 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
         l += pr;
         float vf[8];
         // (rows past the end re-read position 0, which at S = 1 is the row this launch is writing: never let its bytes in)
-        unpack8<DT>(r == S - 1 ? vraw : r < S ? vv[it] : u32x4{0u, 0u, 0u, 0u}, vf);
+        if constexpr (KV8) unpack8<DT>(r == S - 1 ? vn : r < S ? mx8_to16<DT>(vv[it], ve[it]) : u32x4{0u, 0u, 0u, 0u}, vf);
+        else unpack8<DT>(r == S - 1 ? vn : r < S ? vv[it] : u32x4{0u, 0u, 0u, 0u}, vf);
 #pragma unroll
         for (int e = 0; e < 8; ++e) acc[e] = fmaf(pr, vf[e], acc[e]);
       }
       m = mn;
+    }
+  }
+  if constexpr (KV8) {
+    // A key block with exponent 255 reads as NaN and so does its row's score.  fmaxf drops a NaN: where such a row is the ONLY row its
+    // group has seen (a short context, or many blocks per head) the chunk is skipped as empty and the row would vanish from the sums.
+    // The group is marked instead, as the NaN probability marks it everywhere else: every output of the head is NaN.
+    if (poisoned) {
+      l = NAN;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) acc[e] = NAN;
     }
   }
   TG_STAMP(5);
@@ -784,6 +847,12 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
         const float wt = __expf(sm[w * (D + 2) + D] - Mb);
         num = fmaf(wt, sm[w * (D + 2) + t], num);
         den = fmaf(wt, sm[w * (D + 2) + D + 1], den);
+      }
+    } else if constexpr (KV8) {  // (no finite score in the block: zeros, or the NaN mark, which the weight 0 of the combine keeps)
+#pragma unroll
+      for (int w = 0; w < NWV; ++w) {
+        num += sm[w * (D + 2) + t];
+        den += sm[w * (D + 2) + D + 1];
       }
     }
     if (NS == 1) out[((int64_t)b * hl + h) * D + t] = DT::from_f32(num / den);
@@ -982,6 +1051,15 @@ int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counte
                            (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, G);
         return launch_status();
       }
+      if (c.kv8) {  // (mx8 caches: the exponent pointers are the flavour's last argument)
+        const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
+        return pick<0, 1>(c.seq, [&](auto SEQ_) {
+          hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value, false, Kv8Exps>),
+                             dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
+                             c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, X);
+          return launch_status();
+        });
+      }
       return pick<0, 1>(c.seq, [&](auto SEQ_) {
         hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value>),
                            dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
@@ -1005,9 +1083,11 @@ int rope_attn_split_launch(const AttnCall& c) {
   if (!ds.ok) return TG_E_DEVICE;
   int* counters = reinterpret_cast<int*>(c.scratch);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.scratch) + split_scratch(c.bs, c.hl, c.d, c.nsplit).part_offset);
-  // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches never do
+  // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches only
+  // through dg_rope_attn_online_mx8 (c.one_barrier: check_attn held the call to that kernel's d and alignment; with nsplit = 1 the kernel
+  // touches neither part nor counters) -- dg_rope_attn_split_mx8 stays the 256-thread kernel
   // (a paged call always: check_attn holds it to that kernel's d and alignment, there is no paged 256-thread kernel)
-  if (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0) return online_kernel_launch(c, c.nsplit, part, counters);
+  if (c.one_barrier || (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0)) return online_kernel_launch(c, c.nsplit, part, counters);
   if (c.paging) return TG_E_SHAPE;
   const unsigned lds = attn_lds_bytes(772, cdiv(c.max_seq, c.nsplit), c.d);  // the scores of one chunk
   if (lds > 64u * 1024u) return TG_E_SHAPE;
@@ -1073,6 +1153,19 @@ int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* s
                                float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
   return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
                                     .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).per_sequence());
+}
+
+int dg_rope_attn_online_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
+                            void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                            float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online());
+}
+int dg_rope_attn_online_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
+                                void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
+                                float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online().per_sequence());
 }
 
 int dg_rope_attn_online_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,

@@ -73,3 +73,42 @@ __device__ __forceinline__ float mx8_encode_lane(float x, uint32_t& code, uint32
   mx8_encode_lane(x, code, E);
   return DT::lo_f32(mx8_to16<DT>(u32x2{code, 0u}, E)[0]);
 }
+
+// (a kernel that takes the exponent pointers as an optional last parameter, `PG... pack`: the one element of the pack, and whether the pack is that)
+__device__ __forceinline__ const Kv8Exps& kv8_exps_arg(const Kv8Exps& x) { return x; }
+template <typename... PG> struct Kv8Pack : std::false_type {};
+template <> struct Kv8Pack<Kv8Exps> : std::true_type {};
+
+// EIGHT elements per lane (a row lies across d / 8 lanes, as in rope_attn_online_kernel), a 32-element block = an ALIGNED QUAD of lanes;
+// every lane of the quad must be here.  `v`: the lane's eight 16-bit values.  The block maximum is the lane's own maximum and two
+// quad_perm exchanges; exponent rule, clamp, RNE and the non-finite block are mx8_encode_lane's, so the bytes are the host encoder's.
+// Returns the lane's eight codes (element order), the block's exponent byte, and the eight values the cache row now holds.
+template <typename DT>
+__device__ __forceinline__ u32x4 mx8_encode_piece(const u32x4& v, u32x2& codes, uint32_t& E) {
+  float x[8];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    x[2 * q] = DT::lo_f32(v[q]);
+    x[2 * q + 1] = DT::hi_f32(v[q]);
+  }
+  float m = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    float a = fabsf(x[e]);
+    a = a < INFINITY ? a : INFINITY;  // (a NaN too: the block is marked, fmaxf would drop it)
+    m = fmaxf(m, a);
+  }
+  m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xB1, 0xf, 0xf, true)));  // quad_perm [1,0,3,2]
+  m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x4E, 0xf, 0xf, true)));  // quad_perm [2,3,0,1]
+  const uint32_t u = f2u(m);
+  int e = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+  e = e < 0 ? 0 : e;
+  const bool bad = u >= 0x7f800000u;
+  const float s = u2f((uint32_t)(254 - e) << 23);
+  uint32_t c[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) c[j] = bad ? 0x7fu : mx8_e4m3_rne(fminf(fmaxf(x[j] * s, -448.f), 448.f));
+  codes = u32x2{c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24)};
+  E = bad ? 255u : (uint32_t)e;
+  return mx8_to16<DT>(codes, E);
+}

@@ -269,6 +269,14 @@ def check_page_size(cfg: DecodeConfig, kv_pages, page_size, kv_cache=None) -> No
         raise ValueError(f"page_size must be a power of two with 64 <= page_size <= max_seq = {cfg.max_seq} and max_seq % page_size == 0, got {ps}")
 
 
+def check_mx8_attention(mx8_attention, kv_cache) -> None:
+    """mx8_attention names the decode attention kernel of an mx8 cache: "split" (the default) or "online", which only such a cache takes."""
+    if mx8_attention not in ("split", "online"):
+        raise ValueError(f"mx8_attention must be 'split' or 'online', got {mx8_attention!r}")
+    if mx8_attention == "online" and kv_cache != "mx8":
+        raise ValueError("mx8_attention='online' needs kv_cache='mx8' (a 16-bit cache takes the one-barrier kernel by itself)")
+
+
 def _scatter_rows(cache, pos, active, new):
     """cache[b, :, pos[b], :] = new[b] for the active sequences b, with `pos` [bs] (clamped into the cache) and `active` [bs] on the
     device: an inactive sequence gets its own row back, so nothing is read on the host and nothing of it changes."""
@@ -278,9 +286,11 @@ def _scatter_rows(cache, pos, active, new):
 
 class DecodeLayer(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int,
-                 kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64):
+                 kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64, mx8_attention: str = "split"):
         """kv_cache: None = k / v rows in the layer's dtype; "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py): float8_e4m3fn codes
         in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache).
+        mx8_attention: the fused decode attention of an mx8 cache -- "split" (the 256-thread split kernel) or "online" (the one-barrier
+        kernel, head_dim 64 / 128); the plain-torch path is the same for both.
         kv_pages: a paged cache -- `k_pool` / `v_pool` [kv_pages, kvl, page_size, d] in place of the caches (which are None), addressed
         through `block_table` int32 [bs, max_seq / page_size], the stack's (it is shared by all layers and set by the stack)."""
         super().__init__()
@@ -289,6 +299,8 @@ class DecodeLayer(torch.nn.Module):
             raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
         if kv_cache == "mx8" and cfg.head_dim % 32:
             raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
+        check_mx8_attention(mx8_attention, kv_cache)
+        self.mx8_attention = mx8_attention
         if cfg.heads % world or cfg.kv_heads % world or cfg.inter % (16 * world) or cfg.hidden % (16 * world):
             raise ValueError(f"heads={cfg.heads}, kv_heads={cfg.kv_heads}, inter={cfg.inter}, hidden={cfg.hidden} "
                              f"must split over world_size={world} in whole heads / 16-row tiles")
@@ -426,7 +438,8 @@ class DecodeLayer(torch.nn.Module):
     def decode_attention(self, qkv, pos, cos_tab, sin_tab, per_sequence: bool = False):
         """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
         stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one.  An mx8 cache
-        always takes the split entry point (also at a split count of 1: the other kernels have no 8-bit form)."""
+        always takes an entry point with a scratch buffer (also at a split count of 1): the 256-thread split kernel's, or with
+        mx8_attention="online" the one-barrier kernel's."""
         from . import decode_ops as G
 
         d = self.cfg.head_dim
@@ -441,6 +454,9 @@ class DecodeLayer(torch.nn.Module):
         if self.k_exp is not None:
             if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
                 self._attn_scratch = G.rope_attn_split_scratch(self.k_cache.shape[0], self.hl, d, self._attn_split, qkv.device)
+            if self.mx8_attention == "online":
+                return G.rope_attn_online_mx8(*args[:6], self.k_exp, self.v_exp, *args[6:], self._attn_scratch, self._attn_split,
+                                              per_sequence=per_sequence)
             return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp)
         if self._attn_scratch is not None:
             return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence)
@@ -560,7 +576,8 @@ class DecodeStack(torch.nn.Module):
     def __init__(self, cfg: DecodeConfig, linear_factory: Callable, device, dtype=torch.bfloat16, bs: int = 1,
                  rank: int = 0, world: int = 1, group=None, seed: int = 0, lm_head: bool = True,
                  fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
-                 ragged: bool = False, kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64):
+                 ragged: bool = False, kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64,
+                 mx8_attention: str = "split"):
         """kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks, 16-bit rows) --
         every layer holds pools [kv_pages, kvl, page_size, d] and one `block_table` int32 [bs, max_seq / page_size] (a static device
         buffer, -1 = unmapped, mirrored on the host) maps position p of slot b to row p % page_size of page block_table[b, p // page_size];
@@ -575,6 +592,10 @@ class DecodeStack(torch.nn.Module):
         attention launches then are the mx8 entry points (a decode step always the split one, so the stack always owns a split scratch);
         capture, prefill, ragged decode and generate work unchanged on top, TP too (the caches are per rank).  In fp16, k / v values
         beyond fp16's range are out of contract.
+        mx8_attention (kv_cache="mx8"): which kernel a fused decode step launches -- "split" (the default): the 256-thread split kernel,
+        a thread per key row; "online": the one-barrier kernel's 8-bit flavour (dg_rope_attn_online_mx8: rows across lanes, the first
+        chunk requested before the position is known; a fused stack needs head_dim 64 / 128), with the same split count and scratch.
+        Prefill and the plain-torch path are the same for both.
         ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`
         a position, a length and a cache slot per sequence, `generate` prompts of different lengths; the step (and its captured
         graph) reads `pos_seq` [bs] in place of `pos`.  A stack built without it is what it was.
@@ -599,7 +620,8 @@ class DecodeStack(torch.nn.Module):
             raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
         if kv_cache == "mx8" and cfg.head_dim % 32:
             raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
-        self.kv_cache = kv_cache
+        check_mx8_attention(mx8_attention, kv_cache)
+        self.kv_cache, self.mx8_attention = kv_cache, mx8_attention
         self.gather_mode = gather
         self._peer = {}  # output width per rank -> PeerWriteGather
         self.cfg, self.bs, self.rank, self.world, self.group = cfg, bs, rank, world, group
@@ -607,13 +629,16 @@ class DecodeStack(torch.nn.Module):
         self.fused = torch.device(device).type == "cuda" if fused is None else fused
         if self.paged and self.fused and cfg.head_dim not in (64, 128):
             raise ValueError(f"a fused stack with kv_pages needs head_dim 64 or 128 (the paged kernels), got {cfg.head_dim}")
+        if mx8_attention == "online" and self.fused and cfg.head_dim not in (64, 128):
+            raise ValueError(f"a fused stack with mx8_attention='online' needs head_dim 64 or 128 (the one-barrier kernel), got {cfg.head_dim}")
         self.fuse_gemm_stages = fuse_gemm_stages
         gen = torch.Generator(device=device).manual_seed(seed)
         self.embed = torch.nn.Embedding(cfg.vocab, cfg.hidden, device=device, dtype=dtype)
         self.embed.weight.data = torch.randn(cfg.vocab, cfg.hidden, device=device, generator=gen).to(dtype)
         self.embed.weight.requires_grad_(False)
         self.layers = torch.nn.ModuleList(
-            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs, kv_cache=kv_cache, kv_pages=kv_pages, page_size=page_size)
+            [DecodeLayer(cfg, i, linear_factory, rank, world, device, dtype, bs, kv_cache=kv_cache, kv_pages=kv_pages, page_size=page_size,
+                         mx8_attention=mx8_attention)
              for i in range(cfg.layers)])
         if self.paged:
             self.page_size, self.page_pool = operator.index(page_size), PagePool(kv_pages)

@@ -119,20 +119,22 @@ def _paged(what, table, k_pool, v_pool, kvl, d):
     return dict(table=table, k_pool=k_pool, v_pool=v_pool, page_size=page_size, num_pages=num_pages, max_seq=table.shape[1] * page_size)
 
 
-def _attn_launch(base, seq, exps, qkv, paged=False, **values):
+def _attn_launch(base, seq, exps, qkv, paged=False, kv8_online=False, **values):
     """One launch of an attention entry point: _lib.attn_signature names the flavour of `base` (seq: `_seq`; exps = (k_exp, v_exp) of an
     mx8 cache: `_mx8`; paged: `_paged`) and the order of its arguments; `values` are given by argument name, tensors (or None) for
-    pointers.  qkv also supplies dtype, device and stream."""
-    entry, args = _lib.attn_signature(base, seq, bool(exps), paged)
+    pointers.  qkv also supplies dtype, device and stream.  kv8_online: dg_rope_attn_online_mx8(_seq), _lib.kv8_online_signature."""
+    entry, args = _lib.kv8_online_signature(seq) if kv8_online else _lib.attn_signature(base, seq, bool(exps), paged)
     values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
     ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
     _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
 
 
-def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=(), table=None):
+def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=(), table=None,
+               kv8_online=False):
     """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
     `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points; table: the
-    caches are page pools behind this block table: the _paged entry points (per sequence)."""
+    caches are page pools behind this block table: the _paged entry points (per sequence); kv8_online: rope_attn_online_mx8 (split and
+    exps given, base dg_rope_attn_online)."""
     scratch, nsplit = split if split is not None else (None, None)
     out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, table, *exps, out=out)
     what = base + ("_mx8" if exps else "") + ("_paged" if table is not None else "")
@@ -147,7 +149,7 @@ def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, pe
         more.update(_paged(what, table, k_cache, v_cache, kvl, d))
     else:
         more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
-    _attn_launch(base, per_sequence, exps, qkv, table is not None, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
+    _attn_launch(base, per_sequence, exps, qkv, table is not None, kv8_online, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
                  scale=float(scale), **more)
     return out
 
@@ -183,6 +185,20 @@ def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos
     (any4_amd/kvcache.py): the mx8 entry points, which also take nsplit = 1."""
     exps = _mx8_exps("rope_attn_split", k_cache, v_cache, k_exp, v_exp, d)
     return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps)
+
+
+def rope_attn_online_mx8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                         k_exp: torch.Tensor, v_exp: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int,
+                         per_sequence: bool = False, out: torch.Tensor = None) -> torch.Tensor:
+    """rope_attn_online's one-barrier kernel on an mx8 cache (head_dim 64 / 128), `nsplit` blocks per head (1 ... 64; `scratch` as for
+    rope_attn_split): a row's 8-byte pieces lie across lanes as the 16-bit rows do and are converted on use, the new token is encoded
+    byte for byte as mx8_encode does and enters the scores and the value sum as its decoded row.  The arithmetic behind the conversion
+    is rope_attn_online's (nsplit = 1) / rope_attn_split's (more) on a 16-bit cache holding the decoded values, bit for bit."""
+    exps = _mx8_exps("rope_attn_online_mx8", k_cache, v_cache, k_exp, v_exp, d)
+    if not exps:
+        raise RuntimeError(f"rope_attn_online_mx8: the caches must be float8_e4m3fn (mx8), got {k_cache.dtype}; 16-bit caches: rope_attn_online / rope_attn_split")
+    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps,
+                      kv8_online=True)
 
 
 def rope_attn_online_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,

@@ -161,6 +161,28 @@ TG_API int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const floa
                                    int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
                                    tg_stream_t stream);
 
+/* ---- mx8 KV cache on the one-barrier kernel ----
+ * dg_rope_attn_online_mx8(_seq): the argument list of dg_rope_attn_split_mx8(_seq), and always dg_rope_attn_online's one-barrier kernel
+ * in its 8-bit flavour with `nsplit` blocks per head (nsplit = 1: neither partials nor counters are used; the scratch layout and protocol
+ * are dg_rope_attn_split's).  A row lies across d / 8 lanes as the 16-bit rows do: a lane's piece is 8 code bytes and the exponent byte
+ * of its block, every wave-load is contiguous, the first 256 rows are requested before `pos` is known; pieces are converted to the
+ * 16-bit type on use, and behind the conversion every sum and rounding point is the 16-bit kernel's -- on a 16-bit cache that holds the
+ * decoded values dg_rope_attn_online(_seq) (nsplit = 1) / dg_rope_attn_split(_seq) give the same output bit for bit.  Writer and new
+ * token as in dg_rope_attn_split_mx8: byte for byte mx8_encode(rope(k)) / mx8_encode(v), entering the sums as the DECODED rows; rows that
+ * are not written keep their codes and exponent bytes, and whatever `pos` holds nothing outside [0, max_seq) of the four tensors is
+ * indexed.  In this order: a null pointer (k_exp, v_exp, scratch included) is TG_E_NULL; d other than 64 / 128, nsplit outside 1 ... 64,
+ * max_seq > 65536 or a scratch that is too small TG_E_SHAPE; caches, exponents, scratch, qkv, cos or sin off a 16-byte boundary
+ * TG_E_ALIGN; nothing is touched in any of these cases.  There is no paged mx8 flavour.
+ * Exported like every other symbol; declared with a macro of their own because they are bound as a group of their own
+ * (any4_amd/_lib.py: KV8_ONLINE_SYMBOLS). */
+#define DG_KV8_API TG_API /* (exported) */
+DG_KV8_API int dg_rope_attn_online_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                                       void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                       int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+DG_KV8_API int dg_rope_attn_online_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
+                                           void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
+                                           int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+
 /* ---- paged KV cache: a pool of fixed-size pages behind a block table ----
  * Per layer k_pool / v_pool are [num_pages][kvl][page_size][d] in the 16-bit type; one table, int32 [cache_bs][max_seq / page_size] on the
  * device, serves every layer: logical position p of the sequence in cache slot s is row p % page_size of page table[s][p / page_size]

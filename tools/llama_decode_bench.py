@@ -23,6 +23,13 @@ to --out: the caches' bytes, and the captured step of a 16-bit-cache stack and a
 bs = 1 and 8 with the position near 512, 4096 and the end of an 8192-position cache.  With --ragged: leg (b) above on a 16-bit and on
 an mx8 ragged bs = 8 stack.
 
+    python tools/llama_decode_bench.py --config llama3_8b --kv-cache mx8 --mx8-attention online [--out profiles/kv8_online_bench.jsonl]
+
+--mx8-attention online (with --kv-cache mx8; one GPU): the one-barrier kernel's 8-bit flavour ("the one-barrier
+kernel on mx8 rows"): THREE captured steps in one process -- 16-bit cache, mx8 cache with mx8_attention="split", mx8 cache with
+mx8_attention="online" -- alternating five times (the order rotates), 30 steps after 10 warm-up steps each, at bs = 1 and 8 with the
+position near 512, 4096 and the end of an 8192-position cache; one JSON line per (bs, position) cell, appended to --out.
+
     python tools/llama_decode_bench.py --config llama3_8b --paged [--out profiles/paged_bench.jsonl]
 
 --paged (one GPU): the paged KV cache against the contiguous one, one JSON line per leg, appended to --out:
@@ -161,6 +168,38 @@ def kv8_bench(a, cfg, device):
         torch.cuda.empty_cache()
 
 
+def kv8_online_bench(a, cfg, device):
+    """The cells of --kv-cache mx8 --mx8-attention online; yields the JSON-able results, one per (bs, position)."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    def stack(bs, **kw):
+        st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                         fuse_gemm_stages=not a.no_fuse, **kw)
+        st.capture()
+        return st
+
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "data": "synthetic (random weights, random tokens, zero caches)"}
+    names = ("cache16", "mx8_split", "mx8_online")
+    for bs in (1, 8):
+        trio = {"cache16": stack(bs), "mx8_split": stack(bs, kv_cache="mx8", mx8_attention="split"),
+                "mx8_online": stack(bs, kv_cache="mx8", mx8_attention="online")}
+        for want in (512, 4096, cfg.max_seq):
+            start = max(0, min(want, cfg.max_seq - a.warmup - a.steps))  # (the timed steps end inside the cache)
+            series = {k: [] for k in names}
+            for r in range(a.rounds):
+                for k in names[r % 3:] + names[:r % 3]:
+                    series[k].append(round(time_steps(trio[k], a.steps, a.warmup, start) * 1e3, 4))
+            med = {k: sorted(v)[len(v) // 2] for k, v in series.items()}
+            yield dict(base, leg="kv8 online: captured step, 16-bit cache vs mx8 split vs mx8 online, alternating", bs=bs, pos=start + a.warmup,
+                       steps=a.steps, warmup=a.warmup, rounds=a.rounds, attn_split={k: st._attn_split for k, st in trio.items()},
+                       ms_per_step={k: {"median": med[k], "min": min(v), "max": max(v), "series": v} for k, v in series.items()},
+                       online_over_split=round(med["mx8_online"] / med["mx8_split"], 4),
+                       online_over_cache16=round(med["mx8_online"] / med["cache16"], 4),
+                       split_over_cache16=round(med["mx8_split"] / med["cache16"], 4))
+        del trio
+        torch.cuda.empty_cache()
+
+
 def paged_bench(a, cfg, device):
     """The legs of --paged; yields the JSON-able results."""
     from any4_amd.decode import Any4Factory, DecodeStack
@@ -224,8 +263,8 @@ def main():
     ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "tiny"])
     ap.add_argument("--layers", type=int, default=None, help="override the number of decoder layers")
     ap.add_argument("--bs", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=100)
-    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; with --mx8-attention online 30)")
+    ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 20; with --mx8-attention online 10)")
     ap.add_argument("--max-seq", type=int, default=1024)
     ap.add_argument("--start-pos", type=int, default=128, help="sequence position of the first timed token")
     ap.add_argument("--no-graph", action="store_true")
@@ -244,17 +283,26 @@ def main():
                     help="functional check on a one-GPU box: every rank uses GPU 0 (needs --backend gloo --gather peer); the time "
                          "it prints is two processes sharing one GPU, not a TP measurement")
     ap.add_argument("--ragged", action="store_true", help="the two legs of DESIGN.md section 13 (see the module docstring); one GPU")
-    ap.add_argument("--rounds", type=int, default=7, help="--ragged leg (a): alternations per batch size")
+    ap.add_argument("--rounds", type=int, default=None, help="--ragged leg (a): alternations per batch size (default 7; with --mx8-attention online 5)")
     ap.add_argument("--new-tokens", type=int, default=64, help="--ragged leg (b): tokens generated per prompt")
     ap.add_argument("--kv-cache", default=None, choices=["mx8"],
                     help="the legs of DESIGN.md section 15: the mx8 KV cache against the 16-bit one at an 8192-position cache (see the module docstring); one GPU")
+    ap.add_argument("--mx8-attention", default=None, choices=["online"],
+                    help="with --kv-cache mx8: the three-way comparison of DESIGN.md section 15 (16-bit, mx8 split, mx8 online; see the module docstring); one GPU")
     ap.add_argument("--paged", action="store_true",
                     help="the legs of DESIGN.md section 16: the paged KV cache against the contiguous one at an 8192-position cache (see the module docstring); one GPU")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
                                                 "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl)")
     a = ap.parse_args()
+    if a.mx8_attention and not a.kv_cache:
+        raise SystemExit("--mx8-attention goes with --kv-cache mx8")
+    three_way = a.mx8_attention == "online"
+    a.steps = a.steps if a.steps is not None else 30 if three_way else 100
+    a.warmup = a.warmup if a.warmup is not None else 10 if three_way else 20
+    a.rounds = a.rounds if a.rounds is not None else 5 if three_way else 7
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "paged_bench.jsonl" if a.paged else "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
+        a.out = os.path.join(ROOT, "profiles", "paged_bench.jsonl" if a.paged else "kv8_online_bench.jsonl" if three_way else
+                             "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
     if a.backend == "gloo" and a.gather != "peer":
         raise SystemExit("--backend gloo moves no CUDA tensors: use it with --gather peer")
 
@@ -297,7 +345,7 @@ def main():
             raise SystemExit("--kv-cache runs on one GPU")
         cfg.max_seq = 8192
         with open(a.out, "a") as f:
-            for leg in kv8_bench(a, cfg, device):
+            for leg in (kv8_online_bench if three_way else kv8_bench)(a, cfg, device):
                 line = json.dumps(leg)
                 print(line, flush=True)
                 f.write(line + "\n")
