@@ -69,7 +69,8 @@ class PeerGather(ctypes.Structure):
 # The twelve fused attention entry points of include/decode_glue_hip.h: four bases, each with a `_seq` flavour (a position per sequence), two of
 # them with `_mx8` ones (an mx8 KV cache) -- and, bound as a group of their own (PAGED_SYMBOLS; the header declares them DG_PAGED_API), the
 # `_paged` flavour of three bases (a page pool behind a block table; per sequence, 16-bit rows) -- and, a group of their own too (KV8_ONLINE_SYMBOLS;
-# DG_KV8_API), dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache (kv8_online_signature).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
+# DG_KV8_API), dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache (kv8_online_signature) -- and, again a group of their own
+# (PAGED_MX8_SYMBOLS; DG_PAGED_KV8_API), dg_rope_attn_online_mx8_paged / dg_prefill_attn_mx8_paged: mx8 page pools (paged_mx8_signature).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
 # puts a call's values in the same order.
 _ci, _cf = ctypes.c_int, ctypes.c_float
 ATTN_BASES = {"dg_rope_attn": False, "dg_rope_attn_online": False, "dg_rope_attn_split": True, "dg_prefill_attn": True}  # base: has _mx8 flavours
@@ -106,6 +107,22 @@ def kv8_online_signature(seq=False):
     args = (_ATTN_HEAD + _ATTN_CACHES + _ATTN_EXPS + [("out", _vp)] + _ATTN_SCRATCH + [("bs", _i64)] + _ATTN_SHAPE + [("nsplit", _ci)]
             + _ATTN_TAIL)
     return "dg_rope_attn_online_mx8" + ("_seq" if seq else ""), tuple(args)
+
+
+ATTN_PAGED_MX8_BASES = ("dg_rope_attn_online", "dg_prefill_attn")
+
+
+def paged_mx8_signature(base):
+    """(entry point, ((argument name, ctype), ...)) of dg_rope_attn_online_mx8_paged / dg_prefill_attn_mx8_paged: mx8 page pools behind the
+    block table -- the `_paged` list of dg_rope_attn_split / dg_prefill_attn with the exponent pools behind the code pools.  A function of
+    its own: attn_signature(base, mx8=True, paged=True) stays a KeyError, the twelve and the three paged ones are what they were."""
+    if base not in ATTN_PAGED_MX8_BASES:
+        raise KeyError(f"no attention entry point {base}_mx8_paged")
+    prefill = base == "dg_prefill_attn"
+    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill else []) + _ATTN_POOLS + _ATTN_EXPS + [("out", _vp)] + ([] if prefill else _ATTN_SCRATCH)
+            + [("bs", _i64)] + ([("T", _i64), ("cache_bs", _i64)] if prefill else []) + _ATTN_SHAPE[:4] + _ATTN_PAGES + _ATTN_SHAPE[4:]
+            + ([] if prefill else [("nsplit", _ci)]) + _ATTN_TAIL)
+    return base + "_mx8_paged", tuple(args)
 
 
 # name -> argtypes, exactly the prototypes of include/tinygemm_hip.h
@@ -170,6 +187,12 @@ for _seq in (False, True):
     _name, _args = kv8_online_signature(_seq)
     KV8_ONLINE_SYMBOLS[_name] = [t for _, t in _args]
 
+# name -> argtypes of the paged mx8 entry points (the DG_PAGED_KV8_API prototypes of include/decode_glue_hip.h); load() binds them too
+PAGED_MX8_SYMBOLS = {}
+for _base in ATTN_PAGED_MX8_BASES:
+    _name, _args = paged_mx8_signature(_base)
+    PAGED_MX8_SYMBOLS[_name] = [t for _, t in _args]
+
 _lib = None
 
 
@@ -184,7 +207,7 @@ def load() -> ctypes.CDLL:
             "There is no CPU/PyTorch fallback for the tinygemm ops."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS, **KV8_ONLINE_SYMBOLS}.items():
+    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS, **KV8_ONLINE_SYMBOLS, **PAGED_MX8_SYMBOLS}.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # a stale build: the header declares a symbol the .so does not export

@@ -1,5 +1,5 @@
 // attn_call.cuh -- one attention call of the decode stack, described once (include/decode_glue_hip.h: dg_decode_attn, dg_rope_attn*,
-// dg_prefill_attn*, the _paged and the _online_mx8 ones among them).  Host-only, as GemmParams is: no kernel receives an AttnCall, every kernel keeps its own argument list.  Included by
+// dg_prefill_attn*, the _paged, the _online_mx8 and the _mx8_paged ones among them).  Host-only, as GemmParams is: no kernel receives an AttnCall, every kernel keeps its own argument list.  Included by
 // decode_glue.cuh (tinygemm_hip.hip) and tg_prefill.hip; an entry point builds the call (attn_call), sets what only it takes and hands it
 // to its kind's launcher, which validates it with check_attn and keeps only DeviceScope, LDS size, grid and the choice of kernel.
 #pragma once
@@ -13,8 +13,8 @@ enum AttnKind {
   ATTN_UNFUSED,  // dg_decode_attn: q is already roped (AttnCall::qkv holds it), no tables
   ATTN_GENERAL,  // dg_rope_attn(_seq): one 256-thread block per head, any d % 8 == 0
   ATTN_ONLINE,   // dg_rope_attn_online(_seq, _paged): the one-barrier kernel, d = 64 / 128
-  ATTN_SPLIT,    // dg_rope_attn_split(_seq, _mx8, _mx8_seq, _paged), dg_rope_attn_online_mx8(_seq): nsplit blocks per head and a scratch buffer
-  ATTN_PREFILL,  // dg_prefill_attn(_seq, _mx8, _mx8_seq, _paged): T tokens per sequence
+  ATTN_SPLIT,    // dg_rope_attn_split(_seq, _mx8, _mx8_seq, _paged), dg_rope_attn_online_mx8(_seq, _paged): nsplit blocks per head and a scratch buffer
+  ATTN_PREFILL,  // dg_prefill_attn(_seq, _mx8, _mx8_seq, _paged, _mx8_paged): T tokens per sequence
 };
 
 struct AttnCall {
@@ -36,7 +36,8 @@ struct AttnCall {
   bool seq = false;  // `pos` holds a position per sequence (the _seq entry points)
   bool kv8 = false;  // mx8 caches (the _mx8 entry points)
   bool one_barrier = false;  // a split call that must run the one-barrier kernel (dg_rope_attn_online_mx8): that kernel's d and alignment
-  // paged: k_cache / v_cache are pools [num_pages][kvl][page_size][d] behind `table` int32 [cache_bs][max_seq / page_size] (the _paged entry points)
+  // paged: k_cache / v_cache are pools [num_pages][kvl][page_size][d] behind `table` int32 [cache_bs][max_seq / page_size] (the _paged entry points;
+  // with kv8, the _mx8_paged ones: k_exp / v_exp are pools [num_pages][kvl][page_size][d / 32] behind the same table, and both rule sets hold)
   bool paging = false;
   const int32_t* table = nullptr;
   int64_t page_size = 0, num_pages = 0;

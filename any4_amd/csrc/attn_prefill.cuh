@@ -29,10 +29,12 @@
 // decides which tokens exist (the padded T stays in the row addressing and sizes the grid), the cache base is slot[i]'s.  A sequence
 // with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
 //
-// PAGED (dg_prefill_attn_paged; implies SEQ, 16-bit rows): the caches are pools [num_pages][kvl][page_size][D] behind a block table
+// PAGED (dg_prefill_attn_paged, dg_prefill_attn_mx8_paged; implies SEQ): the caches are pools [num_pages][kvl][page_size][D] behind a block table
 // (kv_paged.cuh) whose row is slot[i]'s.  A 64-position tile lies in one page (page_size >= 64), so the staging pass takes the tile's base
 // from its page -- one scalar table read per tile, made when the tile's loads are issued, i.e. one tile ahead of its use -- and the rows
 // stay tile-relative; the append drops a row whose own table entry is outside the pool.  Everything else is the SEQ flavour's.
+// With KV8 the four pools (codes [num_pages][kvl][page_size][D] bytes, exponents [...][D / 32] bytes) sit behind the one table: the same
+// page, the code base kv_page_base(..., D) and the exponent base kv_page_base(..., D / 32), both in bytes.
 #pragma once
 #include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 #include "kv8.cuh"         // the mx8 cache format (KV8 flavours)
@@ -89,7 +91,7 @@ __device__ __forceinline__ bool pf_seq(const PrefillParams& P, const PrefillSeq&
 // ---- rope + cache append: block = one token of one sequence; a thread walks (kv head, rotation pair) items, k first, then v ----
 template <typename DT, bool SEQ = false, bool KV8 = false, bool PAGED = false>
 __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, int d, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X, PagedArg<PAGED> G) {
-  static_assert(!PAGED || (SEQ && !KV8), "a paged cache has a position per sequence and 16-bit rows");
+  static_assert(!PAGED || SEQ, "a paged cache has a position per sequence");
   const int t = blockIdx.x, b = blockIdx.y, d2 = d >> 1;
   int cb = b;  // the sequence's cache slot
   int64_t pos;
@@ -107,6 +109,11 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
   if constexpr (KV8) {
     // d / 2 is a multiple of 32 and 2 * per of 64: the waves of the loop are whole, and 32 aligned lanes hold the elements j of ONE 32-element
     // block and their rotation partners j + d / 2 of another -- a block maximum is a reduction over those lanes
+    [[maybe_unused]] int page8 = 0;
+    if constexpr (PAGED) {  // (block-uniform) the row's own page, looked up once; an entry outside the pool: neither codes nor exponents are written
+      page8 = kv_page_write(G, cb, (int)pos);
+      if (page8 < 0) return;
+    }
     for (int i = threadIdx.x; i < 2 * per; i += 256) {
       const bool isv = i >= per;
       const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
@@ -121,7 +128,9 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
       uint32_t c1, e1, c2, e2;
       mx8_encode_lane(x1, c1, e1);
       mx8_encode_lane(x2, c2, e2);
-      const int64_t r = ((int64_t)cb * P.kvl + kv) * P.max_seq + pos;
+      int64_t r;  // the row among the rows of the cache (PAGED: of the pool)
+      if constexpr (PAGED) r = kv_page_base(G, page8, P.kvl, kv, 1) + (pos & ((1 << G.page_shift) - 1));
+      else r = ((int64_t)cb * P.kvl + kv) * P.max_seq + pos;
       uint8_t* dst = reinterpret_cast<uint8_t*>(isv ? P.v_cache : P.k_cache) + r * d;
       dst[j] = (uint8_t)c1;
       dst[j + d2] = (uint8_t)c2;
@@ -170,7 +179,7 @@ constexpr int PF_NU = 2;  // 16-row units per wave: 2 x (O 4 D/16 + q D/8 + S 16
 
 template <typename DT, int D, int RG, bool SEQ = false, bool KV8 = false, bool PAGED = false>
 __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, PrefillSeqArg<SEQ> Q, Kv8Arg<KV8> X, PagedArg<PAGED> G) {
-  static_assert(!PAGED || (SEQ && !KV8), "a paged cache has a position per sequence and 16-bit rows");
+  static_assert(!PAGED || SEQ, "a paged cache has a position per sequence");
   constexpr int KD = D / 32;        // k-steps of the score product
   constexpr int DB = D / 16;        // 16-column blocks of the output
   constexpr int NU = PF_NU;         // 16-row units per wave
@@ -270,13 +279,24 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
       const uint8_t* Ke = X.k_exp + head0 * (D / 32);
       const uint8_t* Ve = X.v_exp + head0 * (D / 32);
       kexp = vexp = 0u;  // (rows beyond p_hi: codes 0 with any exponent below 255 are the zero bits of the 16-bit flavour)
+      // PAGED: first row of the tile among the rows of (the tile's page, this kv head) of a pool -- s0 <= p_hi < max_seq; workgroup-uniform,
+      // one table read per tile, made one tile ahead of its use.  A page holds at least 64 rows, so the code base (row * D bytes) and the
+      // exponent base (row * D / 32 bytes) of a (page, kv head) are multiples of 16 bytes for D = 64 and 128.
+      [[maybe_unused]] int64_t t0 = 0;
+      if constexpr (PAGED)
+        t0 = kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, cb, s0)), P.kvl, kv, 1) + (s0 & ((1 << G.page_shift) - 1));
 #pragma unroll
       for (int i = 0; i < NCK; ++i) {
         const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
         kreg8[i] = u32x2{0u, 0u};
         if (s0 + row <= p_hi) {
-          kreg8[i] = *reinterpret_cast<const u32x2*>(Kg8 + (int64_t)(s0 + row) * D + ch * 8);
-          kexp |= (uint32_t)Ke[(int64_t)(s0 + row) * (D / 32) + (ch >> 2)] << (8 * i);
+          if constexpr (PAGED) {
+            kreg8[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(P.k_cache) + t0 * D + row * D + ch * 8);
+            kexp |= (uint32_t)X.k_exp[t0 * (D / 32) + row * (D / 32) + (ch >> 2)] << (8 * i);
+          } else {
+            kreg8[i] = *reinterpret_cast<const u32x2*>(Kg8 + (int64_t)(s0 + row) * D + ch * 8);
+            kexp |= (uint32_t)Ke[(int64_t)(s0 + row) * (D / 32) + (ch >> 2)] << (8 * i);
+          }
         }
       }
       if (vsg < 16) {
@@ -285,8 +305,13 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
           const int row = 4 * vsg + i;
           vreg8[i] = u32x2{0u, 0u};
           if (s0 + row <= p_hi) {
-            vreg8[i] = *reinterpret_cast<const u32x2*>(Vg8 + (int64_t)(s0 + row) * D + vc * 8);
-            vexp |= (uint32_t)Ve[(int64_t)(s0 + row) * (D / 32) + (vc >> 2)] << (8 * i);
+            if constexpr (PAGED) {
+              vreg8[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(P.v_cache) + t0 * D + row * D + vc * 8);
+              vexp |= (uint32_t)X.v_exp[t0 * (D / 32) + row * (D / 32) + (vc >> 2)] << (8 * i);
+            } else {
+              vreg8[i] = *reinterpret_cast<const u32x2*>(Vg8 + (int64_t)(s0 + row) * D + vc * 8);
+              vexp |= (uint32_t)Ve[(int64_t)(s0 + row) * (D / 32) + (vc >> 2)] << (8 * i);
+            }
           }
         }
       }

@@ -563,11 +563,16 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 // The paging argument is the kernel's last parameter and exists only for PAGED (PG = KvPages): this kernel reads gridDim from the implicit
 // arguments BEHIND the explicit ones, and even an empty trailing struct moves those by eight bytes -- the contiguous flavours would keep
 // their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
-// KV8 (the dg_rope_attn_online_mx8 entry points; PG = Kv8Exps, the same optional last parameter; never with PAGED): the caches are mx8
+// KV8 (the dg_rope_attn_online_mx8 entry points; PG = Kv8Exps, the same optional last parameter): the caches are mx8
 // (kv8.cuh).  Same lanes, same partition of work: a lane's K / V piece is 8 code bytes and one exponent byte, requested where the
 // 16-byte pieces are (the speculative ones in front of `pos`), clamped and masked alike, and converted to the 16-bit type on use --
 // behind the conversion every sum and rounding point is the 16-bit flavour's.  The new token's roped k row and raw v row are encoded
 // from the registers they are in (mx8_encode_piece: the host encoder's bytes) and enter the scores and the value sum DECODED.
+// PAGED with KV8 (dg_rope_attn_online_mx8_paged; PG = KvPages, Kv8Exps): four pools behind the one table -- codes [num_pages][kvl][page_size][D]
+// bytes, exponents [...][D / 32] bytes.  The page lookup is PAGED's (one scalar table read per iteration, page-relative rows, rows past the
+// end re-read the iteration's own first row, the speculative iterations' entries beside pos[b]); the piece, its conversion on use, the
+// NaN mark and the combine are KV8's; the new token's codes and exponent bytes are written only where its own table entry is in the pool.
+// Partition of work, order of every sum, masks and rounding points are the contiguous <SEQ, Kv8Exps> flavour's.
 template <typename DT, int LPR, bool SEQ = false, bool PAGED = false, typename... PG>
 __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                                const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
@@ -575,8 +580,8 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
                                                                uint16_t* __restrict__ out, int hl, int kvl, int64_t max_seq, float scale,
                                                                unsigned long long* trace, float* part, int* counters, PG... pages) {
   constexpr bool KV8 = Kv8Pack<PG...>::value;  // (the flavour is the pack's type: no template parameter that would rename the others)
-  static_assert(sizeof...(PG) == (PAGED || KV8 ? 1 : 0) && (!PAGED || SEQ), "PAGED: one KvPages argument, a position per sequence");
-  static_assert(!(PAGED && KV8), "there is no paged mx8 flavour");
+  static_assert(!PAGED || SEQ, "PAGED: a position per sequence");
+  static_assert(sizeof...(PG) == (PAGED ? 1 : 0) + (KV8 ? 1 : 0), "the pack is empty, KvPages (PAGED), Kv8Exps (mx8), or KvPages, Kv8Exps");
   [[maybe_unused]] KvPages G{};
   if constexpr (PAGED) G = kv_pages_arg(pages...);
   [[maybe_unused]] Kv8Exps X{};
@@ -623,8 +628,16 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   [[maybe_unused]] const int64_t head0 = ((int64_t)b * kvl + kv) * max_seq;  // first cache row of this (sequence, kv head)
   [[maybe_unused]] const char* K8 = reinterpret_cast<const char*>(k_cache) + head0 * D;
   [[maybe_unused]] const char* V8 = reinterpret_cast<const char*>(v_cache) + head0 * D;
-  [[maybe_unused]] const uint8_t* KE = KV8 ? X.k_exp + head0 * (D / 32) : nullptr;
-  [[maybe_unused]] const uint8_t* VE = KV8 ? X.v_exp + head0 * (D / 32) : nullptr;
+  // (PAGED: the exponent pools' first byte; an iteration adds its page's base)
+  [[maybe_unused]] const uint8_t* KE = KV8 ? X.k_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
+  [[maybe_unused]] const uint8_t* VE = KV8 ? X.v_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
+  // PAGED with KV8: the page of logical row r0 < max_seq (wave-uniform).  A code row is D bytes and an exponent row D / 32 bytes, so the
+  // byte bases of (page, this kv head) are kv_page_base(..., D) in K / V and kv_page_base(..., D / 32) in KE / VE; a page holds at least
+  // 64 rows, so both are multiples of 16 bytes for D = 64 and 128 and the 8-byte pieces stay aligned.
+  [[maybe_unused]] auto page_of = [&](int r0) -> int {
+    if constexpr (PAGED) return __builtin_amdgcn_readfirstlane(kv_page_read(G, b, r0));
+    else return 0;
+  };
   [[maybe_unused]] auto piece8 = [&](const char* base, int r) -> u32x2 { return *reinterpret_cast<const u32x2*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 3)); };
   [[maybe_unused]] auto pexp = [&](const uint8_t* base, int r) -> uint32_t { return base[(uint32_t)r * (D / 32) + ((uint32_t)i >> 2)]; };
   // the first NSPEC iterations' rows are requested BEFORE the position is known (rows past it are valid memory and masked later):
@@ -640,7 +653,14 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   [[maybe_unused]] uint32_t ke[KV8 ? NI : 1], ve[KV8 ? NI : 1];  // KV8: the exponent byte of each piece
 #pragma unroll
   for (int it = 0; it < NSPEC; ++it) {
-    if constexpr (PAGED) {  // (an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
+    if constexpr (PAGED && KV8) {  // (PAGED's rows, KV8's pieces)
+      const int r0 = min(row0_of(it), (int)max_seq - RPI);
+      const int pg = page_of(r0), rc = (r0 & in_page) + grp;
+      kk[it] = piece8(K + kv_page_base(G, pg, kvl, kv, D), rc);
+      vv[it] = piece8(V + kv_page_base(G, pg, kvl, kv, D), rc);
+      ke[it] = pexp(KE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
+      ve[it] = pexp(VE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
+    } else if constexpr (PAGED) {  // (an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
       const int r0 = min(row0_of(it), (int)max_seq - RPI);
       const int64_t pb = page_bytes(r0);
       kk[it] = piece(K + pb, (r0 & in_page) + grp);
@@ -672,7 +692,14 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     for (int it = 0; it < NI; ++it) {
       if (it < first || row0_of(base / RPI + it) >= S) continue;  // (wave-uniform) iterations past the last position request nothing
       const int r = row0_of(base / RPI + it) + grp;
-      if constexpr (PAGED) {  // (row0 < S <= max_seq)
+      if constexpr (PAGED && KV8) {  // (row0 < S <= max_seq)
+        const int r0 = row0_of(base / RPI + it);
+        const int pg = page_of(r0), rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
+        kk[it] = piece8(K + kv_page_base(G, pg, kvl, kv, D), rc);
+        vv[it] = piece8(V + kv_page_base(G, pg, kvl, kv, D), rc);
+        ke[it] = pexp(KE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
+        ve[it] = pexp(VE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
+      } else if constexpr (PAGED) {  // (row0 < S <= max_seq)
         const int r0 = row0_of(base / RPI + it);
         const int64_t pb = page_bytes(r0);
         const int rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
@@ -726,12 +753,26 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
     kn = mx8_encode_piece<DT>(kn, kc, kE);
     vn = mx8_encode_piece<DT>(vraw, vc, vE);
     if (h % rep == 0 && grp == 0 && cblk == 0) {
-      const int64_t r = head0 + pos;
-      *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + r * D + i * 8) = kc;
-      *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + r * D + i * 8) = vc;
-      if ((i & 3) == 0) {
-        X.k_exp[r * (D / 32) + (i >> 2)] = (uint8_t)kE;
-        X.v_exp[r * (D / 32) + (i >> 2)] = (uint8_t)vE;
+      if constexpr (PAGED) {  // (a position whose own table entry is outside the pool writes neither codes nor exponents)
+        const int pg = kv_page_write(G, b, (int)pos);
+        if (pg >= 0) {
+          const int64_t cb8 = kv_page_base(G, pg, kvl, kv, D) + (int64_t)((int)pos & in_page) * D;
+          const int64_t eb8 = kv_page_base(G, pg, kvl, kv, D / 32) + (int64_t)((int)pos & in_page) * (D / 32);
+          *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + cb8 + i * 8) = kc;
+          *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + cb8 + i * 8) = vc;
+          if ((i & 3) == 0) {
+            X.k_exp[eb8 + (i >> 2)] = (uint8_t)kE;
+            X.v_exp[eb8 + (i >> 2)] = (uint8_t)vE;
+          }
+        }
+      } else {
+        const int64_t r = head0 + pos;
+        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + r * D + i * 8) = kc;
+        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + r * D + i * 8) = vc;
+        if ((i & 3) == 0) {
+          X.k_exp[r * (D / 32) + (i >> 2)] = (uint8_t)kE;
+          X.v_exp[r * (D / 32) + (i >> 2)] = (uint8_t)vE;
+        }
       }
     }
   } else if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
@@ -1044,6 +1085,14 @@ int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counte
 #endif
   return pick_dt(c.dtype, [&](auto DT_) {
     return pick<16, 8>(c.d / 8, [&](auto LPR_) {  // (d = 128, 64)
+      if (c.paging && c.kv8) {  // (mx8 pools behind a block table: the paging argument, then the exponent pools)
+        const KvPages G = kv_pages(c);
+        const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, true, true, KvPages, Kv8Exps>),
+                           dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
+                           c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, G, X);
+        return launch_status();
+      }
       if (c.paging) {  // (pools behind a block table: always a position per sequence)
         const KvPages G = kv_pages(c);
         hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, true, true, KvPages>), dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit),
@@ -1086,7 +1135,8 @@ int rope_attn_split_launch(const AttnCall& c) {
   // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches only
   // through dg_rope_attn_online_mx8 (c.one_barrier: check_attn held the call to that kernel's d and alignment; with nsplit = 1 the kernel
   // touches neither part nor counters) -- dg_rope_attn_split_mx8 stays the 256-thread kernel
-  // (a paged call always: check_attn holds it to that kernel's d and alignment, there is no paged 256-thread kernel)
+  // (a paged call always: check_attn holds it to that kernel's d and alignment, there is no paged 256-thread kernel -- a paged mx8 call
+  //  comes from dg_rope_attn_online_mx8_paged with c.one_barrier set, and one without it is refused below, never sent to that kernel)
   if (c.one_barrier || (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0)) return online_kernel_launch(c, c.nsplit, part, counters);
   if (c.paging) return TG_E_SHAPE;
   const unsigned lds = attn_lds_bytes(772, cdiv(c.max_seq, c.nsplit), c.d);  // the scores of one chunk
@@ -1179,6 +1229,14 @@ int dg_rope_attn_split_paged(const void* qkv, const float* cos, const float* sin
                              int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
   return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
                                     .split(scratch, scratch_bytes, nsplit).paged(table, page_size, num_pages));
+}
+
+int dg_rope_attn_online_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
+                                  void* v_pool, void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl,
+                                  int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype,
+                                  int device, tg_stream_t stream) {
+  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online().paged(table, page_size, num_pages));
 }
 
 int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) { return split_scratch(bs, hl, d, nsplit).bytes; }

@@ -78,6 +78,9 @@ __device__ __forceinline__ float mx8_encode_lane(float x, uint32_t& code, uint32
 __device__ __forceinline__ const Kv8Exps& kv8_exps_arg(const Kv8Exps& x) { return x; }
 template <typename... PG> struct Kv8Pack : std::false_type {};
 template <> struct Kv8Pack<Kv8Exps> : std::true_type {};
+// (the paged mx8 flavour: the pack is `KvPages, Kv8Exps`, in that order -- kv_paged.cuh; the exponent pointers are then those of the pools)
+template <typename PAGES> __device__ __forceinline__ const Kv8Exps& kv8_exps_arg(const PAGES&, const Kv8Exps& x) { return x; }
+template <typename PAGES> struct Kv8Pack<PAGES, Kv8Exps> : std::true_type {};
 
 // EIGHT elements per lane (a row lies across d / 8 lanes, as in rope_attn_online_kernel), a 32-element block = an ALIGNED QUAD of lanes;
 // every lane of the quad must be here.  `v`: the lane's eight 16-bit values.  The block maximum is the lane's own maximum and two

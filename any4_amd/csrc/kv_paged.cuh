@@ -3,6 +3,9 @@
 // logical position p of the sequence in slot s to row p % page_size of page table[s][p / page_size].  The kernels walk the context in
 // units that a page holds whole (page_size >= 64 and a power of two), so paging only changes where a unit's base address comes from:
 // the page id is wave-uniform (a scalar read), the base a 64-bit scalar, the offset within the page the 32-bit one it was.
+// mx8 pools (the dg_*_mx8_paged entry points; kv8.cuh): four pools behind the one table -- codes [num_pages][kvl][page_size][d] BYTES and
+// exponents [num_pages][kvl][page_size][d / 32] bytes.  kv_page_base counts elements: the byte base of the codes of (page, kv head) is
+// kv_page_base(G, page, kvl, kv, d), that of the exponents kv_page_base(G, page, kvl, kv, d / 32).
 #pragma once
 
 // What only the PAGED kernels read: their LAST argument.  The prefill kernels take PagedArg<PAGED>, an empty one for the contiguous
@@ -18,6 +21,8 @@ template <bool PAGED> struct PagedArg {};
 template <> struct PagedArg<true> : KvPages {};
 // (a kernel that takes the argument as an optional last parameter, `PG... pages`: the one element of the pack)
 __device__ __forceinline__ const KvPages& kv_pages_arg(const KvPages& g) { return g; }
+// (... `KvPages, Kv8Exps`, the paged mx8 flavour: the first of the two)
+template <typename REST> __device__ __forceinline__ const KvPages& kv_pages_arg(const KvPages& g, const REST&) { return g; }
 
 // Page of logical row `r` (inside [0, max_seq)) of the sequence in slot `s`, for a READ: an entry outside [0, num_pages) -- unmapped is
 // -1 by convention -- reads page 0, so nothing outside the pools is indexed (that sequence's output is then unspecified).

@@ -33,8 +33,8 @@ int go_rg(PrefillParams& P, const PrefillSeq& S, const Kv8Exps& E, const KvPages
   return go<DT, D, 4, SEQ, KV8, PAGED>(P, S, E, pages, st);
 }
 
-// The five entry points behind one validation (check_attn).  c.seq: `len` / `slot` / cache_bs per sequence (otherwise null, null, bs);
-// c.kv8: mx8 caches, `k_exp` / `v_exp` their exponent bytes; c.paging: pools behind a block table (per sequence, 16-bit rows).
+// The six entry points behind one validation (check_attn).  c.seq: `len` / `slot` / cache_bs per sequence (otherwise null, null, bs);
+// c.kv8: mx8 caches, `k_exp` / `v_exp` their exponent bytes; c.paging: pools behind a block table (per sequence; with c.kv8 four pools, codes and exponents).
 int prefill_launch(const AttnCall& c) {
   if (const int rc = check_attn(ATTN_PREFILL, c)) return rc;
   DeviceScope ds(c.device);
@@ -49,6 +49,7 @@ int prefill_launch(const AttnCall& c) {
   hipStream_t st = (hipStream_t)c.stream;
   return pick_dt(c.dtype, [&](auto DT_) {
     return pick<128, 64>(c.d, [&](auto D_) {
+      if (c.paging && c.kv8) return go_rg<decltype(DT_), decltype(D_)::value, true, true, true>(P, S, E, pages, st);
       if (c.paging) return go_rg<decltype(DT_), decltype(D_)::value, true, false, true>(P, S, E, pages, st);
       return pick<0, 1>(c.seq, [&](auto SEQ_) {
         return pick<0, 1>(c.kv8, [&](auto KV8_) {
@@ -95,4 +96,12 @@ extern "C" int dg_prefill_attn_paged(const void* qkv, const float* cos, const fl
                                      int dtype, int device, tg_stream_t stream) {
   return prefill_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, n, hl, kvl, d, max_seq, scale, dtype, device, stream)
                             .chunk(T).slots(len, slot, cache_bs).paged(table, page_size, num_pages));
+}
+
+extern "C" int dg_prefill_attn_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                                         const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* k_exp, void* v_exp,
+                                         void* out, int64_t n, int64_t T, int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq,
+                                         int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream) {
+  return prefill_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, n, hl, kvl, d, max_seq, scale, dtype, device, stream)
+                            .chunk(T).slots(len, slot, cache_bs).mx8(k_exp, v_exp).paged(table, page_size, num_pages));
 }

@@ -260,8 +260,8 @@ def check_page_size(cfg: DecodeConfig, kv_pages, page_size, kv_cache=None) -> No
     """The rule of a paged cache (include/decode_glue_hip.h): a page is a power of two of at least 64 positions, max_seq whole pages."""
     if kv_pages is None:
         return
-    if kv_cache == "mx8":
-        raise ValueError("kv_pages with kv_cache='mx8': paged mx8 pools are not built yet")
+    if kv_cache == "mx8" and cfg.head_dim not in (64, 128):  # (fused or not: the only head sizes for which a kernel reads such pools)
+        raise ValueError(f"kv_pages with kv_cache='mx8': paged mx8 pools are not built yet for head_dim {cfg.head_dim} (64 and 128 are)")
     ps = operator.index(page_size)
     if operator.index(kv_pages) < 1:
         raise ValueError(f"kv_pages must be at least 1, got {kv_pages}")
@@ -290,9 +290,12 @@ class DecodeLayer(torch.nn.Module):
         """kv_cache: None = k / v rows in the layer's dtype; "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py): float8_e4m3fn codes
         in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache).
         mx8_attention: the fused decode attention of an mx8 cache -- "split" (the 256-thread split kernel) or "online" (the one-barrier
-        kernel, head_dim 64 / 128); the plain-torch path is the same for both.
+        kernel, head_dim 64 / 128); the plain-torch path is the same for both.  A paged mx8 layer (kv_pages) accepts either value and
+        always runs the one-barrier kernel.
         kv_pages: a paged cache -- `k_pool` / `v_pool` [kv_pages, kvl, page_size, d] in place of the caches (which are None), addressed
-        through `block_table` int32 [bs, max_seq / page_size], the stack's (it is shared by all layers and set by the stack)."""
+        through `block_table` int32 [bs, max_seq / page_size], the stack's (it is shared by all layers and set by the stack).  With
+        kv_cache="mx8" (head_dim 64 / 128) four pools behind that table: `k_pool` / `v_pool` hold the float8_e4m3fn codes, `k_exp_pool` /
+        `v_exp_pool` uint8 [kv_pages, kvl, page_size, d / 32] the exponent bytes."""
         super().__init__()
         check_page_size(cfg, kv_pages, page_size, kv_cache)
         if kv_cache not in (None, "mx8"):
@@ -315,8 +318,13 @@ class DecodeLayer(torch.nn.Module):
         self.norm2 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.block_table = None
         if kv_pages is not None:
+            code_dtype = torch.uint8 if kv_cache == "mx8" else dtype
             for name in ("k", "v"):
-                self.register_buffer(name + "_pool", torch.zeros(kv_pages, self.kvl, page_size, d, device=device, dtype=dtype), persistent=False)
+                pool = torch.zeros(kv_pages, self.kvl, page_size, d, device=device, dtype=code_dtype)
+                self.register_buffer(name + "_pool", pool.view(F8) if kv_cache == "mx8" else pool, persistent=False)
+                if kv_cache == "mx8":
+                    self.register_buffer(name + "_exp_pool", torch.zeros(kv_pages, self.kvl, page_size, d // 32, device=device, dtype=torch.uint8),
+                                         persistent=False)
             self.k_cache = self.v_cache = self.k_exp = self.v_exp = None
         elif kv_cache == "mx8":
             for name in ("k", "v"):
@@ -328,6 +336,8 @@ class DecodeLayer(torch.nn.Module):
             self.register_buffer("k_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
             self.register_buffer("v_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
             self.k_exp = self.v_exp = None
+        if kv_pages is None or kv_cache != "mx8":
+            self.k_exp_pool = self.v_exp_pool = None  # (only a paged mx8 layer has exponent pools)
         # forward_fused5: which stages the library fused (None: not tried yet; set by the first step)
         self._fuse = {"norm1": None, "norm2": None, "mlp": None}
         # decode_attention: the stack's split count and its scratch buffer (DecodeStack sets both once, when it is built)
@@ -388,8 +398,9 @@ class DecodeLayer(torch.nn.Module):
         """The plain-torch twin of a paged layer (what the paged kernels are tested against, not a product): inside the block `k_cache`
         / `v_cache` are [bs, kvl, max_seq, d] copies gathered through the table, with entries outside the pool clamped to page 0 as the
         kernels clamp them, so that the contiguous formulation runs unchanged; `put(slots, positions)` (two int64 tensors of one length)
-        copies those rows of the view back into the pools, dropping a row whose own table entry is outside the pool.  A layer without
-        pools: nothing happens."""
+        copies those rows of the view back into the pools, dropping a row whose own table entry is outside the pool.  mx8 pools: codes
+        AND exponent bytes are gathered (`k_exp` / `v_exp` too) and put back, so that the contiguous mx8 formulation runs unchanged.
+        A layer without pools: nothing happens."""
         if self.block_table is None:
             yield lambda slots, positions: None
             return
@@ -398,20 +409,29 @@ class DecodeLayer(torch.nn.Module):
         valid = (tab >= 0) & (tab < n)
         idx = torch.where(valid, tab, torch.zeros_like(tab))
         bs = tab.shape[0]
-        for name, pool in (("k_cache", self.k_pool), ("v_cache", self.v_pool)):
-            setattr(self, name, pool[idx].permute(0, 2, 1, 3, 4).reshape(bs, self.kvl, self.cfg.max_seq, d))
+        views = {"k_cache": self.k_pool, "v_cache": self.v_pool}
+        if self.k_exp_pool is not None:
+            views.update(k_exp=self.k_exp_pool, v_exp=self.v_exp_pool)
+        for name, pool in views.items():
+            # (float8 codes travel as their bytes: indexing is not implemented for that dtype everywhere)
+            raw = pool.view(torch.uint8) if pool.dtype == F8 else pool
+            view = raw[idx].permute(0, 2, 1, 3, 4).reshape(bs, self.kvl, self.cfg.max_seq, pool.shape[3])
+            setattr(self, name, view.view(pool.dtype))
 
         def put(slots, positions):
             ok = valid[slots, positions // ps]
             slots, positions = slots[ok], positions[ok]
             pages = tab[slots, positions // ps]
-            for view, pool in ((self.k_cache, self.k_pool), (self.v_cache, self.v_pool)):
+            for name, pool in views.items():
+                view = getattr(self, name)
+                if pool.dtype == F8:
+                    view, pool = view.view(torch.uint8), pool.view(torch.uint8)
                 pool[pages, :, positions % ps] = view[slots, :, positions]
 
         try:
             yield put
         finally:
-            self.k_cache = self.v_cache = None
+            self.k_cache = self.v_cache = self.k_exp = self.v_exp = None
 
     def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
         """Plain torch, a chunk of tokens per sequence: `h` [n * T, hidden] (row i * T + t), rows padded to the common T.  Host ints
@@ -439,7 +459,8 @@ class DecodeLayer(torch.nn.Module):
         """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
         stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one.  An mx8 cache
         always takes an entry point with a scratch buffer (also at a split count of 1): the 256-thread split kernel's, or with
-        mx8_attention="online" the one-barrier kernel's."""
+        mx8_attention="online" the one-barrier kernel's.  Pools behind the block table take the _paged entry points; mx8 pools the one
+        _mx8_paged entry point (the one-barrier kernel, with the stack's split count and scratch)."""
         from . import decode_ops as G
 
         d = self.cfg.head_dim
@@ -447,6 +468,10 @@ class DecodeLayer(torch.nn.Module):
             if not per_sequence:
                 raise RuntimeError("a paged KV cache has a position per sequence")
             args = (qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
+            if self.k_exp_pool is not None:  # mx8 pools: always the one-barrier kernel, whatever mx8_attention names
+                if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
+                    self._attn_scratch = G.rope_attn_split_scratch(self.block_table.shape[0], self.hl, d, self._attn_split, qkv.device)
+                return G.rope_attn_online_mx8_paged(*args[:7], self.k_exp_pool, self.v_exp_pool, *args[7:], self._attn_scratch, self._attn_split)
             if self._attn_scratch is not None:
                 return G.rope_attn_split_paged(*args, self._attn_scratch, self._attn_split)
             return G.rope_attn_online_paged(*args)
@@ -472,6 +497,10 @@ class DecodeLayer(torch.nn.Module):
         if self.block_table is not None:
             if not per_sequence or T is None:
                 raise RuntimeError("a paged KV cache has a position per sequence")
+            if self.k_exp_pool is not None:
+                return G.prefill_attn_mx8_paged(qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.k_exp_pool,
+                                                self.v_exp_pool, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
+                                                out=qkv.new_zeros(qkv.shape[0], self.hl * d), lengths=lengths, slots=slots)
             return G.prefill_attn_paged(qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d,
                                         1.0 / math.sqrt(d), T, out=qkv.new_zeros(qkv.shape[0], self.hl * d), lengths=lengths, slots=slots)
         T = qkv.shape[0] // self.k_cache.shape[0] if T is None else T
@@ -578,7 +607,7 @@ class DecodeStack(torch.nn.Module):
                  fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
                  ragged: bool = False, kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64,
                  mx8_attention: str = "split"):
-        """kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks, 16-bit rows) --
+        """kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks) --
         every layer holds pools [kv_pages, kvl, page_size, d] and one `block_table` int32 [bs, max_seq / page_size] (a static device
         buffer, -1 = unmapped, mirrored on the host) maps position p of slot b to row p % page_size of page block_table[b, p // page_size];
         a `PagePool` (any4_amd/kvcache.py) hands the pages out.  page_size: a power of two, 64 <= page_size <= max_seq, max_seq % page_size
@@ -586,7 +615,8 @@ class DecodeStack(torch.nn.Module):
         exhausted" before anything is launched or mapped) and refuse a write into a page that two slots share; with a device position
         `reserve` is the caller's.  `reserve` / `release` / `fork` manage slots by hand.  The table is updated by in-place copies, so a
         captured step sees pages mapped between two replays.  Under tensor parallelism table and pool decisions are the same on every
-        rank and the pools are per rank.  The fused path needs head_dim 64 / 128.
+        rank and the pools are per rank.  The fused path needs head_dim 64 / 128.  With kv_cache="mx8" the pools are mx8 (head_dim 64 / 128
+        only, fused or not: every layer holds four pools, codes and exponent bytes, behind the one table) and everything above holds unchanged.
         kv_cache: None = a 16-bit KV cache in the stack's dtype (the default); "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py:
         E4M3 codes and one exponent byte per 32 elements, (1 + 1/32) / 2 of the 16-bit cache's bytes; head_dim % 32 == 0).  The fused
         attention launches then are the mx8 entry points (a decode step always the split one, so the stack always owns a split scratch);
@@ -595,6 +625,8 @@ class DecodeStack(torch.nn.Module):
         mx8_attention (kv_cache="mx8"): which kernel a fused decode step launches -- "split" (the default): the 256-thread split kernel,
         a thread per key row; "online": the one-barrier kernel's 8-bit flavour (dg_rope_attn_online_mx8: rows across lanes, the first
         chunk requested before the position is known; a fused stack needs head_dim 64 / 128), with the same split count and scratch.
+        A paged mx8 stack (kv_pages) accepts either value and always runs the one-barrier kernel (dg_rope_attn_online_mx8_paged): it is
+        the only decode attention kernel with a paged flavour.
         Prefill and the plain-torch path are the same for both.
         ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`
         a position, a length and a cache slot per sequence, `generate` prompts of different lengths; the step (and its captured
@@ -691,9 +723,10 @@ class DecodeStack(torch.nn.Module):
                 layer._attn_scratch, layer._attn_split = self._attn_scratch, self._attn_split
 
     def kv_cache_bytes(self) -> int:
-        """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes; a paged one: the pools)."""
+        """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes; a paged one: the pools, all four of an mx8 one)."""
         if self.paged:
-            return sum(t.numel() * t.element_size() for layer in self.layers for t in (layer.k_pool, layer.v_pool))
+            return sum(t.numel() * t.element_size() for layer in self.layers
+                       for t in (layer.k_pool, layer.v_pool, layer.k_exp_pool, layer.v_exp_pool) if t is not None)
         return sum(t.numel() * t.element_size() for layer in self.layers
                    for t in (layer.k_cache, layer.v_cache, layer.k_exp, layer.v_exp) if t is not None)
 
@@ -755,7 +788,8 @@ class DecodeStack(torch.nn.Module):
     def fork(self, src: int, dst: int, tokens: int) -> None:
         """Prefix sharing: `dst` (released first) starts as the first `tokens` positions of `src`.  Its first tokens // page_size table
         entries point at src's pages, which gain a holder -- whole shared pages are never written again, since the cache is append-only
-        -- and the tokens % page_size rows of a partial last page are copied into a fresh page, in every layer."""
+        -- and the tokens % page_size rows of a partial last page are copied into a fresh page, in every layer (mx8 pools: codes and
+        exponent bytes)."""
         self._need_paged(src)
         self._need_paged(dst)
         src, dst, tokens, ps = operator.index(src), operator.index(dst), operator.index(tokens), self.page_size
@@ -770,8 +804,10 @@ class DecodeStack(torch.nn.Module):
         self._sync_row(dst)
         if part:
             for layer in self.layers:
-                for pool in (layer.k_pool, layer.v_pool):
-                    pool[fresh[0], :, :part] = pool[self._table[src][full], :, :part]
+                for pool in (layer.k_pool, layer.v_pool, layer.k_exp_pool, layer.v_exp_pool):
+                    if pool is not None:
+                        raw = pool.view(torch.uint8) if pool.dtype == F8 else pool
+                        raw[fresh[0], :, :part] = raw[self._table[src][full], :, :part]
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
     def _gather(self, y, peer_ok=True):

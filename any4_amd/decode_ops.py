@@ -224,6 +224,70 @@ def prefill_attn_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, 
     return prefill_attn(qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, T, out, lengths, slots, True, table=table)
 
 
+def _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d):
+    """The pool arguments of a `_mx8_paged` launch, checked on the host: code pools float8_e4m3fn [num_pages, kvl, page_size, d], exponent
+    pools uint8 [num_pages, kvl, page_size, d / 32], `table` int32 [cache_bs, max_seq / page_size].  By argument name, with max_seq."""
+    if not _mx8_exps(what, k_pool, v_pool, k_exp, v_exp, d):
+        raise RuntimeError(f"{what}: the pools must be float8_e4m3fn (mx8), got {k_pool.dtype}; 16-bit pools: the _paged entry points")
+    if table.dtype != torch.int32 or table.dim() != 2 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape or tuple(k_pool.shape[1::2]) != (kvl, d):
+        raise RuntimeError(f"{what}: table must be int32 [cache_bs, max_seq / page_size] and the pools [num_pages, {kvl}, page_size, {d}], got "
+                           f"{table.dtype} {tuple(table.shape)}, {tuple(k_pool.shape)}, {tuple(v_pool.shape)}")
+    num_pages, _, page_size, _ = k_pool.shape
+    return dict(table=table, k_pool=k_pool, v_pool=v_pool, k_exp=k_exp, v_exp=v_exp, page_size=page_size, num_pages=num_pages,
+                max_seq=table.shape[1] * page_size)
+
+
+def _paged_mx8_launch(base, qkv, **values):
+    """One launch of a `_mx8_paged` entry point (_lib.paged_mx8_signature: the order of its arguments), values by argument name."""
+    entry, args = _lib.paged_mx8_signature(base)
+    values.update(qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
+    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
+    _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
+
+
+def rope_attn_online_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,
+                               k_pool: torch.Tensor, v_pool: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor, hl: int, kvl: int, d: int,
+                               scale: float, scratch: torch.Tensor, nsplit: int, out: torch.Tensor = None) -> torch.Tensor:
+    """rope_attn_online_mx8(per_sequence=True) on paged mx8 pools: codes float8_e4m3fn [num_pages, kvl, page_size, d] and exponents uint8
+    [num_pages, kvl, page_size, d / 32] behind the one `table` (rope_attn_online_paged).  Always the one-barrier kernel, `nsplit` blocks per
+    head (1 ... 64; `scratch` as for rope_attn_split); bytes written and output are rope_attn_online_mx8's on caches holding the same rows."""
+    what = "rope_attn_online_mx8_paged"
+    pools = _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d)
+    out, bs, _ = _rope_front(qkv, cos, sin, pos, k_pool, v_pool, hl, d, scratch, table, k_exp, v_exp, out=out)
+    if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"{what}: out must be [{bs}, {hl * d}] {qkv.dtype}")
+    _per_sequence(pos, bs, what)
+    if table.shape[0] != bs:
+        raise RuntimeError(f"{what}: the table needs a row per sequence ({bs}), got {tuple(table.shape)}")
+    _paged_mx8_launch("dg_rope_attn_online", qkv, cos=cos, sin=sin, pos=pos, out=out, scratch=scratch, scratch_bytes=scratch.numel() * 4, bs=bs,
+                      hl=hl, kvl=kvl, d=d, scale=float(scale), nsplit=nsplit, **pools)
+    return out
+
+
+def prefill_attn_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
+                           v_pool: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int,
+                           out: torch.Tensor = None, lengths: torch.Tensor = None, slots: torch.Tensor = None) -> torch.Tensor:
+    """prefill_attn(per_sequence=True) on paged mx8 pools (rope_attn_online_mx8_paged): `slots` names the table ROW of each sequence
+    (default: row i, and n must be the table's rows)."""
+    what = "prefill_attn_mx8_paged"
+    pools = _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d)
+    out, rows, _ = _rope_front(qkv, cos, sin, pos, k_pool, v_pool, hl, d, lengths, slots, table, k_exp, v_exp, out=out)
+    T = int(T)
+    cache_bs = table.shape[0]
+    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != cache_bs and slots is None):
+        raise RuntimeError(f"{what}: qkv must be [n * T, ...] with T = {T} and n = {cache_bs} (the table's rows), got {tuple(qkv.shape)}")
+    if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"{what}: out must be [{rows}, {hl * d}] {qkv.dtype}")
+    n = rows // T
+    _per_sequence(pos, n, what)
+    for name, t in (("lengths", lengths), ("slots", slots)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != n):
+            raise RuntimeError(f"{what}: {name} must be int64 with {n} elements (one per sequence)")
+    _paged_mx8_launch("dg_prefill_attn", qkv, cos=cos, sin=sin, pos=pos, len=lengths, slot=slots, out=out, bs=n, T=T, cache_bs=cache_bs,
+                      hl=hl, kvl=kvl, d=d, scale=float(scale), **pools)
+    return out
+
+
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
                  v_cache: torch.Tensor, hl: int, kvl: int, d: int, scale: float, T: int, out: torch.Tensor = None,
                  lengths: torch.Tensor = None, slots: torch.Tensor = None, per_sequence: bool = False, k_exp: torch.Tensor = None,

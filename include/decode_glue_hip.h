@@ -172,7 +172,7 @@ TG_API int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const floa
  * are not written keep their codes and exponent bytes, and whatever `pos` holds nothing outside [0, max_seq) of the four tensors is
  * indexed.  In this order: a null pointer (k_exp, v_exp, scratch included) is TG_E_NULL; d other than 64 / 128, nsplit outside 1 ... 64,
  * max_seq > 65536 or a scratch that is too small TG_E_SHAPE; caches, exponents, scratch, qkv, cos or sin off a 16-byte boundary
- * TG_E_ALIGN; nothing is touched in any of these cases.  There is no paged mx8 flavour.
+ * TG_E_ALIGN; nothing is touched in any of these cases.  (Paged mx8 pools: dg_rope_attn_online_mx8_paged, at the end of this header.)
  * Exported like every other symbol; declared with a macro of their own because they are bound as a group of their own
  * (any4_amd/_lib.py: KV8_ONLINE_SYMBOLS). */
 #define DG_KV8_API TG_API /* (exported) */
@@ -214,6 +214,33 @@ DG_PAGED_API int dg_prefill_attn_paged(const void* qkv, const float* cos, const 
                                        const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* out, int64_t n, int64_t T,
                                        int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale,
                                        int dtype, int device, tg_stream_t stream);
+
+/* ---- paged mx8 KV cache: 8-bit page pools behind the block table ----
+ * Per layer FOUR pools behind the one table: k_pool / v_pool [num_pages][kvl][page_size][d] hold one E4M3 code BYTE per element, k_exp /
+ * v_exp [num_pages][kvl][page_size][d / 32] one E8M0 exponent byte per 32 consecutive elements of a row (the mx8 format above); logical
+ * position p of the sequence in slot s is row p % page_size of page table[s][p / page_size] in all four.  A page holds at least 64 rows,
+ * so the codes and the exponents of a (page, kv head) begin on 16-byte boundaries when the pools do.
+ *   dg_rope_attn_online_mx8_paged   dg_rope_attn_split_paged's arguments with k_exp / v_exp behind the pools: always the one-barrier kernel
+ *                                   with nsplit blocks per head (nsplit = 1: neither partials nor counters are used), the one decode entry point
+ *   dg_prefill_attn_mx8_paged       dg_prefill_attn_paged's arguments with k_exp / v_exp behind the pools
+ * Both obey the paged AND the mx8 rules, in the order null, dtype, shape, alignment: a null pointer (table, k_exp, v_exp, scratch included)
+ * is TG_E_NULL; d other than 64 / 128, a page_size that is no power of two in [64, max_seq] or does not divide max_seq, num_pages <= 0,
+ * nsplit outside 1 ... 64 or a scratch that is too small TG_E_SHAPE; pools, exponents, table, scratch, qkv, cos or sin off a 16-byte boundary
+ * TG_E_ALIGN; nothing is touched in any of these cases.  The page lookup is the paged entry points' (an entry outside [0, num_pages) reads
+ * page 0; a row whose OWN entry is outside the pool writes neither codes nor exponent bytes), the rows' bytes and the arithmetic are the
+ * contiguous mx8 entry points': for tables that map the same rows, the bytes written and the output rows are, bit for bit, those of
+ * dg_rope_attn_online_mx8_seq (same nsplit) / dg_prefill_attn_mx8_seq.
+ * Exported like every other symbol; declared with a macro of their own because they are bound as a group of their own
+ * (any4_amd/_lib.py: PAGED_MX8_SYMBOLS). */
+#define DG_PAGED_KV8_API TG_API /* (exported) */
+DG_PAGED_KV8_API int dg_rope_attn_online_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
+                                                   void* k_pool, void* v_pool, void* k_exp, void* v_exp, void* out, void* scratch,
+                                                   int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size,
+                                                   int64_t num_pages, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+DG_PAGED_KV8_API int dg_prefill_attn_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
+                                               const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* k_exp, void* v_exp,
+                                               void* out, int64_t n, int64_t T, int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq,
+                                               int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream);
 
 #ifdef __cplusplus
 }

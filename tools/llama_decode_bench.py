@@ -38,6 +38,12 @@ position near 512, 4096 and the end of an 8192-position cache; one JSON line per
       8192-position cache;
   (b) `kv_cache_bytes()` of a pool sized for the eight prompts of --ragged leg (b) plus their new tokens against the contiguous bs = 8
       stack's, and the seconds of `generate(list)` on either.
+
+    python tools/llama_decode_bench.py --config llama3_8b --paged --kv-cache mx8 [--out profiles/paged_mx8_bench.jsonl]
+
+--paged --kv-cache mx8 (one GPU): the same two legs with mx8 stacks -- leg (a) alternates the contiguous mx8 stack
+with mx8_attention="online" (dg_rope_attn_online_mx8_seq) against the paged mx8 stack (dg_rope_attn_online_mx8_paged), the same kernel
+with and without the page lookup; leg (b) reports the bytes of the four mx8 pools for the eight prompts.
 """
 import argparse
 import json
@@ -201,14 +207,16 @@ def kv8_online_bench(a, cfg, device):
 
 
 def paged_bench(a, cfg, device):
-    """The legs of --paged; yields the JSON-able results."""
+    """The legs of --paged (with --kv-cache mx8: on mx8 stacks, the contiguous one on the one-barrier kernel); yields the JSON-able results."""
     from any4_amd.decode import Any4Factory, DecodeStack
 
     ps = 64
+    mx8 = a.kv_cache == "mx8"
 
     def stack(bs, kv_pages, capture=True):
         st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
-                         fuse_gemm_stages=not a.no_fuse, ragged=True, kv_pages=kv_pages, page_size=ps)
+                         fuse_gemm_stages=not a.no_fuse, ragged=True, kv_pages=kv_pages, page_size=ps,
+                         **(dict(kv_cache="mx8", mx8_attention="online") if mx8 else {}))
         if kv_pages is not None and capture:  # every position exists before the timed steps; physical order is not logical order
             st.page_pool._free.reverse()
             for b in range(bs):
@@ -217,7 +225,7 @@ def paged_bench(a, cfg, device):
             st.capture()
         return st
 
-    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "page_size": ps,
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "page_size": ps, **({"kv_cache": "mx8"} if mx8 else {}),
             "data": "synthetic (random weights, random tokens, zero caches)"}
     for bs in (1, 8):
         pair = {"contiguous": stack(bs, None), "paged": stack(bs, bs * cfg.max_seq // ps)}
@@ -292,7 +300,7 @@ def main():
     ap.add_argument("--paged", action="store_true",
                     help="the legs of DESIGN.md section 16: the paged KV cache against the contiguous one at an 8192-position cache (see the module docstring); one GPU")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
-                                                "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl)")
+                                                "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl, with both profiles/paged_mx8_bench.jsonl)")
     a = ap.parse_args()
     if a.mx8_attention and not a.kv_cache:
         raise SystemExit("--mx8-attention goes with --kv-cache mx8")
@@ -301,7 +309,7 @@ def main():
     a.warmup = a.warmup if a.warmup is not None else 10 if three_way else 20
     a.rounds = a.rounds if a.rounds is not None else 5 if three_way else 7
     if a.out is None:
-        a.out = os.path.join(ROOT, "profiles", "paged_bench.jsonl" if a.paged else "kv8_online_bench.jsonl" if three_way else
+        a.out = os.path.join(ROOT, "profiles", "paged_mx8_bench.jsonl" if a.paged and a.kv_cache else "paged_bench.jsonl" if a.paged else "kv8_online_bench.jsonl" if three_way else
                              "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
     if a.backend == "gloo" and a.gather != "peer":
         raise SystemExit("--backend gloo moves no CUDA tensors: use it with --gather peer")
