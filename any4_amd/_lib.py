@@ -169,6 +169,10 @@ SYMBOLS = {
     "dg_rope_attn_split_scratch_bytes": [_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int],
     "dg_swiglu": [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_linear16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
+    # the sampler: logits, ctr, temperature, top_k, top_p, seed, u_in, token_out, u_out, scratch, scratch_bytes, bs, vocab, ld,
+    # per_sequence, ctr_add, dtype, device, stream
+    "dg_sample": [_vp] * 10 + [_i64, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp],
+    "dg_sample_scratch_bytes": [_i64, _i64],
 }
 for _base, _has_mx8 in ATTN_BASES.items():
     for _seq in (False, True):
@@ -214,7 +218,7 @@ def load() -> ctypes.CDLL:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild with `python -m any4_amd.build`") from e
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "tg_error_string" else
-                      ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
+                      ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "dg_sample_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
                                                                                           "tg_gemm_w4_dx_workspace_bytes", "tg_gemm_w4_dq_workspace_bytes") else ctypes.c_int)
     if lib.tg_abi_version() != TG_ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.tg_abi_version()} != {TG_ABI_VERSION}; rebuild")

@@ -16,6 +16,7 @@
 //   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
 //   tg_dq.hip          w4_gemm_dq_kernel         (w4_gemm_dq.cuh)          the gradients of scales, zeros and LUT (tg_gemm_w4_dq)
 //   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
+//   tg_sample.hip      sample_kernel             (sample.cuh)              temperature / top-k / top-p sampling of the logits (dg_sample)
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.

@@ -700,6 +700,7 @@ class DecodeStack(torch.nn.Module):
             for name in ("pos_seq", "prefill_pos_seq", "prefill_len", "prefill_slot"):
                 self.register_buffer(name, torch.zeros(bs, dtype=torch.long, device=device), persistent=False)
         self._graph = None
+        self._graph_samples = False  # the captured step ends with the sampler (capture(sample=True))
         self._out = None
         self._decodes = 0
         self.peer_poll_every = 16  # decode() calls between two non-blocking reads of the peer-gather status words
@@ -882,23 +883,104 @@ class DecodeStack(torch.nn.Module):
                 h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather)
         return self._head(h, delta)
 
+    # ---- sampling (any4_amd/sampling.py is the definition; fused: dg_sample, one launch) ----
+    def _sampling_buffers(self) -> None:
+        """The sampler's static buffers, registered on first use (a stack that never samples has none of them): a temperature, a top-k, a
+        top-p and a seed per sequence, read by the kernel -- so a captured step sees values set between two replays -- and `sampled`
+        int64 [bs], the tokens of the last `sample`.  The defaults are greedy."""
+        if "sampled" in self._buffers:
+            return
+        dev = self.tokens.device
+        for name, dtype, fill in (("sample_temperature", torch.float32, 0), ("sample_top_k", torch.int32, 0), ("sample_top_p", torch.float32, 1),
+                                  ("sample_seed", torch.long, 0), ("sampled", torch.long, 0)):
+            self.register_buffer(name, torch.full((self.bs,), fill, dtype=dtype, device=dev), persistent=False)
+
+    def set_sampling(self, temperature, top_k=0, top_p=1.0, seed=0) -> None:
+        """Sampling parameters of the `bs` sequences, each a scalar or `bs` host values: temperature >= 0 (0: greedy), top_k (<= 0 or >=
+        vocab: off), top_p > 0 (>= 1: off), seed (int64).  Checked on the host (ValueError) before anything is written."""
+        if self.lm_head is None:
+            raise ValueError("sampling needs the LM head")
+
+        def per_sequence(x, what, conv):
+            if isinstance(x, torch.Tensor):
+                x = x.tolist()
+            try:
+                vals = [conv(v) for v in x] if isinstance(x, (list, tuple)) else [conv(x)] * self.bs
+            except TypeError as e:
+                raise ValueError(f"{what} must be a number or {self.bs} host numbers: {e}") from e
+            if len(vals) != self.bs:
+                raise ValueError(f"{what}: {len(vals)} values for bs = {self.bs} sequences")
+            return vals
+
+        temperature = per_sequence(temperature, "temperature", float)
+        top_k = per_sequence(top_k, "top_k", operator.index)
+        top_p = per_sequence(top_p, "top_p", float)
+        seed = per_sequence(seed, "seed", operator.index)
+        if any(not t >= 0 or math.isinf(t) for t in temperature):
+            raise ValueError(f"temperature {temperature}: each must be a finite number >= 0 (0: greedy)")
+        if any(not p > 0 for p in top_p):
+            raise ValueError(f"top_p {top_p}: each must be > 0 (>= 1: off)")
+        if any(not -2 ** 63 <= s < 2 ** 63 for s in seed):
+            raise ValueError(f"seed {seed}: each must fit int64")
+        self._sampling_buffers()
+        top_k = [min(max(k, 0), 2 ** 31 - 1) for k in top_k]
+        for buf, vals in ((self.sample_temperature, temperature), (self.sample_top_k, top_k), (self.sample_top_p, top_p), (self.sample_seed, seed)):
+            buf.copy_(torch.tensor(vals, dtype=buf.dtype))  # (in place: a captured step reads these buffers)
+
     @torch.no_grad()
-    def capture(self, warmup: int = 3) -> None:
-        """Capture `step()` in a hipGraph (torch.cuda.graph).  All ranks must call it together when world > 1."""
+    def sample(self, logits: torch.Tensor, ctr, ctr_add: int = 1) -> torch.Tensor:
+        """Sample a token per sequence from `logits` [bs, vocab] under `set_sampling`'s parameters into `self.sampled` (int64 [bs], returned).
+        `ctr` (int64 tensor [bs] or [1], or a host int) + ctr_add is the index the new token will have in its sequence: a decode step passes
+        its position buffer and 1, a prefill position + length and 0.  Sequence b draws sampling.uniform(seed[b], ctr + ctr_add) -- nothing
+        else enters, not the batch slot and not the number of replays.  A negative `ctr` value marks an inactive sequence: token -1.
+        Fused: one dg_sample launch on the buffers (graph-capturable); else sampling.sample_ref."""
+        self._sampling_buffers()
+        if not isinstance(ctr, torch.Tensor):
+            ctr = torch.full((1,), operator.index(ctr), dtype=torch.long, device=logits.device)
+        if self.fused:
+            from . import decode_ops as G
+
+            return G.sample(logits, ctr, self.sample_temperature, self.sample_top_k, self.sample_top_p, self.sample_seed, ctr_add,
+                            token_out=self.sampled)
+        from . import sampling
+
+        c = ctr.reshape(-1).expand(logits.shape[0])
+        u = sampling.uniform(self.sample_seed, c + ctr_add)
+        tok = sampling.sample_ref(logits, self.sample_temperature, self.sample_top_k, self.sample_top_p, u)
+        self.sampled.copy_(torch.where(c >= 0, tok, -1))
+        return self.sampled
+
+    @torch.no_grad()
+    def capture(self, warmup: int = 3, sample: bool = False) -> None:
+        """Capture `step()` in a hipGraph (torch.cuda.graph).  All ranks must call it together when world > 1.
+        sample: the captured step ends with the sampler (`sample` on the step's logits and position buffer): `decode()` returns the logits
+        as before and the tokens are in `self.sampled`, under whatever `set_sampling` set last."""
+        if sample:
+            if self.lm_head is None:
+                raise ValueError("capture(sample=True) needs the LM head")
+            self._sampling_buffers()
+
+        def step():
+            out = self.step()
+            if sample:
+                self.sample(out, self.pos_seq if self.ragged else self.pos, 1)
+            return out
+
         s = torch.cuda.Stream()
         s.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(s):
             for _ in range(warmup):
-                self.step()
+                step()
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
         with torch.cuda.graph(g):
-            self._out = self.step()
+            self._out = step()
         self._graph = g
+        self._graph_samples = bool(sample)
         if self._five_launch():
             self.kernels_per_layer = self.layers[0].launches()
-            # + embedding gather, final norm, LM head
-            self.graph_nodes = sum(layer.launches() for layer in self.layers) + 2 + (1 if self.lm_head is not None else 0)
+            # + embedding gather, final norm, LM head (+ the sampler)
+            self.graph_nodes = sum(layer.launches() for layer in self.layers) + 2 + (1 if self.lm_head is not None else 0) + (1 if sample else 0)
 
     def _set_position(self, position) -> None:
         """decode()'s `position` into the step's position buffer (`pos_seq` of a ragged stack, else `pos`).  Host values are checked
@@ -1069,10 +1151,22 @@ class DecodeStack(torch.nn.Module):
             keep = rows if keep is None else [None if r is None else torch.where(here, r, k) for r, k in zip(rows, keep)]
         return self._head(*[None if t is None else t.contiguous() for t in keep])
 
+    def _picked(self, logits):
+        """The sampled tokens of the decode step that returned `logits`: the captured sampler has written them, else one launch does."""
+        if self._graph is not None and self._graph_samples:
+            return self.sampled
+        return self.sample(logits, self.pos_seq if self.ragged else self.pos, 1)
+
     @torch.no_grad()
-    def generate(self, prompt, new_tokens: int, eos: Optional[int] = None) -> torch.Tensor:
+    def generate(self, prompt, new_tokens: int, eos: Optional[int] = None, *, temperature=None, top_k=0, top_p=1.0, seed=0) -> torch.Tensor:
         """Greedy continuation: `prefill(prompt)` [bs, T], then `decode` (graph replay if captured) from position T.
         Returns the `new_tokens` generated token ids [bs, new_tokens].
+        temperature (None: greedy, the argmax of every step): a SAMPLED continuation -- every token, the first one after the prefill
+        included, comes from `sample` under `set_sampling(temperature, top_k, top_p, seed)` (each a scalar or `bs` host values, checked
+        before anything is launched).  The token with index i of a sequence is drawn with sampling.uniform(seed, i), so a sequence's
+        continuation does not depend on its slot or on the rest of the batch beyond what the logits do.  A step captured with
+        `capture(sample=True)` samples inside the graph and the tokens go back in without a host round trip; otherwise the sampler is
+        one launch behind each step.
         A ragged stack also takes a list of `bs` 1-D token tensors of different lengths, and `eos`: a sequence that has emitted `eos`,
         or whose next position would be outside the cache, is inactive from the next step on (decided on the device, no sync per
         step) and its remaining outputs are `eos` (-1 when eos is None)."""
@@ -1081,13 +1175,17 @@ class DecodeStack(torch.nn.Module):
         if new_tokens < 1:
             raise ValueError(f"new_tokens must be >= 1, got {new_tokens}")
         per_sequence = isinstance(prompt, (list, tuple)) or eos is not None
+        sampled = temperature is not None
+        if sampled:
+            self.set_sampling(temperature, top_k, top_p, seed)
         if self.paged:  # every slot's whole run, up front (the per-sequence steps below pass device positions); nothing is released here
             lens = [p.numel() for p in prompt] if isinstance(prompt, (list, tuple)) else [prompt.shape[-1]] * self.bs
             if len(lens) == self.bs:
                 self._reserve_all([(b, min(n + new_tokens, self.cfg.max_seq)) for b, n in enumerate(lens)])
         if not per_sequence:
             base = prompt.shape[1] if prompt.dim() == 2 else 0  # a host int: decode() fills the position
-            tok = self.prefill(prompt).argmax(-1)
+            logits = self.prefill(prompt)
+            tok = self.sample(logits, base, 0) if sampled else logits.argmax(-1)
         else:  # right-padded prefill with lengths; who is still active is kept on the device
             if not self.ragged:
                 raise ValueError("prompts of different lengths / eos need DecodeStack(..., ragged=True)")
@@ -1099,20 +1197,22 @@ class DecodeStack(torch.nn.Module):
             padded = torch.zeros(self.bs, max(lens), dtype=torch.long, device=dev)
             for b, p in enumerate(prompts):
                 padded[b, : lens[b]] = p.to(dev)
-            tok = self.prefill(padded, position=0, lengths=lens).argmax(-1)
+            logits = self.prefill(padded, position=0, lengths=lens)
             base = torch.tensor(lens, dtype=torch.long).to(dev)
+            tok = self.sample(logits, base, 0) if sampled else logits.argmax(-1)
             alive = torch.ones(self.bs, dtype=torch.bool, device=dev)
             fill = -1 if eos is None else int(eos)
         out = [tok.clone()]
         for i in range(new_tokens - 1):  # the token emitted at step i is fed at position len_b + i
             if not per_sequence:
-                tok = self.decode(tok, base + i).argmax(-1)
+                logits = self.decode(tok, base + i)
+                tok = self._picked(logits) if sampled else logits.argmax(-1)
             else:
                 if eos is not None:
                     alive = alive & (tok != eos)
                 alive = alive & (base + i < self.cfg.max_seq)
                 logits = self.decode(torch.where(alive, tok, 0), torch.where(alive, base + i, -1))
-                tok = torch.where(alive, logits.argmax(-1), fill)
+                tok = torch.where(alive, self._picked(logits) if sampled else logits.argmax(-1), fill)
             out.append(tok.clone())
         return torch.stack(out, dim=1)
 

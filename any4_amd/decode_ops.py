@@ -327,6 +327,42 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     return out
 
 
+def sample(logits: torch.Tensor, ctr: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
+           seed: torch.Tensor = None, ctr_add: int = 1, u: torch.Tensor = None, token_out: torch.Tensor = None, u_out: torch.Tensor = None,
+           scratch: torch.Tensor = None, vocab: int = None) -> torch.Tensor:
+    """Temperature / top-k / top-p sampling of logits [bs, ld] (16-bit; the first `vocab` columns, default all; the last dimension must be
+    contiguous, rows may be `ld` apart) in one launch -- any4_amd/sampling.py: sample_ref is the definition.  Returns token_out int64 [bs]
+    (allocated unless given).  temperature, top_p float32 [bs], top_k int32 [bs], seed int64 [bs], all on the device.  ctr int64 on the
+    device, [bs] or [1] (one value for every sequence): sequence b draws sampling.uniform(seed[b], ctr + ctr_add), and a NEGATIVE value
+    read from ctr makes it inactive (token -1).  u float32 [bs]: replaces that draw (seed may then be None).  u_out float32 [bs]: receives
+    the u used."""
+    if logits.dim() != 2 or logits.stride(1) != 1 or not logits.is_cuda:
+        raise RuntimeError("sample: logits must be [bs, vocab] on a ROCm device with a contiguous last dimension (there is no CPU fallback)")
+    bs, width = logits.shape
+    ld = logits.stride(0) if bs > 1 else max(logits.stride(0), width)
+    vocab = width if vocab is None else int(vocab)
+    if token_out is None:
+        token_out = torch.empty(bs, dtype=torch.int64, device=logits.device)
+    _gpu(ctr, temperature, top_k, top_p, seed, u, token_out, u_out, scratch)
+    for name, t, dt in (("temperature", temperature, torch.float32), ("top_k", top_k, torch.int32), ("top_p", top_p, torch.float32),
+                        ("seed", seed, torch.int64), ("u", u, torch.float32), ("token_out", token_out, torch.int64), ("u_out", u_out, torch.float32)):
+        if t is not None and (t.dtype != dt or t.numel() != bs):
+            raise RuntimeError(f"sample: {name} must be {dt} with {bs} elements (one per sequence), got {t.dtype} {tuple(t.shape)}")
+    if ctr.dtype != torch.int64 or ctr.numel() not in (1, bs):
+        raise RuntimeError(f"sample: ctr must be int64 with 1 or {bs} elements, got {ctr.dtype} {tuple(ctr.shape)}")
+    if seed is None and u is None:
+        raise RuntimeError("sample: a seed per sequence is needed unless u is given")
+    if not 1 <= vocab <= width or ld < vocab:
+        raise RuntimeError(f"sample: vocab {vocab} outside the logits' {width} columns (row stride {ld})")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    # (per_sequence: ctr has an element per sequence; with bs == 1 both readings are the same element)
+    _lib.check(_lib.load().dg_sample(logits.data_ptr(), ctr.data_ptr(), temperature.data_ptr(), top_k.data_ptr(), top_p.data_ptr(), ptr(seed),
+                                     ptr(u), token_out.data_ptr(), ptr(u_out), ptr(scratch), 0 if scratch is None else scratch.numel() * 4,
+                                     bs, vocab, ld, int(ctr.numel() == bs), int(ctr_add), _dt(logits), logits.device.index, _stream(logits)),
+               "dg_sample")
+    return token_out
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """gu [bs, 2 il] = [gate | up] -> silu(gate) * up [bs, il]."""
     _gpu(gu)

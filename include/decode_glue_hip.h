@@ -242,6 +242,34 @@ DG_PAGED_KV8_API int dg_prefill_attn_mx8_paged(const void* qkv, const float* cos
                                                void* out, int64_t n, int64_t T, int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq,
                                                int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream);
 
+/* ---- sampling: temperature, top-k, top-p (nucleus) and a counter-based draw, one launch per step ----
+ * The definition is any4_amd/sampling.py (sample_ref, uniform, philox4x32_10), in float64; this is its kernel.  Per row b of
+ * logits [bs][ld] (16-bit, ld >= vocab; rows need no alignment beyond 2 bytes):
+ *   rank      tokens ordered by (logit descending, index ascending)
+ *   weights   w_i = exp((l_i - l_max) / temperature[b]); temperature[b] == 0: the answer is rank 0 (argmax, lowest index among ties)
+ *   top-k     the first top_k[b] ranks are kept (top_k <= 0 or >= vocab: all), Z_k their mass
+ *   top-p     of those, the shortest rank prefix whose mass is >= top_p[b] * Z_k (top_p >= 1: all; at least one token), Z its mass
+ *   draw      the first kept rank whose inclusive cumulative mass exceeds u * Z (the last kept rank if there is none)
+ * u: u_in[b] when u_in is given, else (w >> 8) * 2^-24 with w the first word of Philox4x32-10 at counter (lo32(c), hi32(c), 0, 0) under
+ * key (lo32(seed[b]), hi32(seed[b])), c = ctr[per_sequence ? b : 0] + ctr_add -- the index the new token will have in its sequence (a decode
+ * step passes its position buffer and ctr_add = 1), so a draw depends on the seed and the place only.  When the value READ from ctr is
+ * negative the sequence is inactive: token_out[b] = -1, u_out[b] = 0, its logits are not read.
+ * token_out int64 [bs]; u_out float [bs] or NULL: the u used.  temperature / top_p float [bs], top_k int32 [bs], seed int64 [bs] (may be
+ * NULL when u_in is given) are read on the device, so a captured graph sees values changed between replays.
+ * Arithmetic: the kernel sorts nothing and keeps no [vocab] temporary; it counts tokens per 16-bit value, and a value's mass is
+ * count x floor(expf((l - l_max) / temperature) x 2^s) as a 64-bit integer, s = 62 - bit_length(vocab); the argument is formed in float64
+ * and rounded to float32 once.  Integer sums have no order, so the same inputs give the same token on every launch and every device.
+ * A row whose values occupy more than 512 of the 1024 bins of 64 consecutive 16-bit values (both signs over most binades) is walked in
+ * two windows, with extra passes over the row.  Against the float64 definition the normalised cumulative
+ * masses differ by at most 2^-22 (3 + ln vocab) + 2^-27, 3.5e-6 at vocab 128256.  Out of contract: NaN or +inf logits, a row that is all -inf, temperature < 0.
+ * scratch: dg_sample_scratch_bytes(bs, vocab) bytes, caller-owned; the answer is 0 today and scratch may then be NULL.
+ * TG_E_NULL: a required pointer is NULL; TG_E_DTYPE; TG_E_SHAPE: bs < 1, vocab < 1 or ld < vocab; TG_E_SIZE: vocab > 2^30 or bs >= 2^31;
+ * TG_E_ALIGN: a pointer off its element's alignment.  Nothing is touched in any of these cases. */
+TG_API int dg_sample(const void* logits, const int64_t* ctr, const float* temperature, const int32_t* top_k, const float* top_p,
+                     const int64_t* seed, const float* u_in, int64_t* token_out, float* u_out, void* scratch, int64_t scratch_bytes,
+                     int64_t bs, int64_t vocab, int64_t ld, int per_sequence, int64_t ctr_add, int dtype, int device, tg_stream_t stream);
+TG_API int64_t dg_sample_scratch_bytes(int64_t bs, int64_t vocab);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,13 @@ position near 512, 4096 and the end of an 8192-position cache; one JSON line per
 --paged --kv-cache mx8 (one GPU): the same two legs with mx8 stacks -- leg (a) alternates the contiguous mx8 stack
 with mx8_attention="online" (dg_rope_attn_online_mx8_seq) against the paged mx8 stack (dg_rope_attn_online_mx8_paged), the same kernel
 with and without the page lookup; leg (b) reports the bytes of the four mx8 pools for the eight prompts.
+
+    python tools/llama_decode_bench.py --config llama3_8b --sample [--out profiles/sample_bench.jsonl]
+
+--sample (one GPU): what sampling costs, one JSON line per batch size (1 and 8), appended to --out: the captured step
+alone, with the fused sampler (dg_sample) as its last node, followed by the same sampler as an eager launch, and followed by the torch
+formulation (sort, softmax, cumsum, masked softmax, multinomial) -- alternating in one process, the order rotating -- and the sampler
+launched back to back on its own.  temperature 0.8, top_k 50, top_p 0.95.
 """
 import argparse
 import json
@@ -58,20 +65,83 @@ import torch  # noqa: E402
 import torch.distributed as dist  # noqa: E402
 
 
-def time_steps(stack, steps, warmup, start_pos):
+def time_steps(stack, steps, warmup, start_pos, after=None):
+    """Seconds per decode step; after(logits): what follows every step (--sample: a sampler behind the replay)."""
     tok = torch.randint(0, stack.cfg.vocab, (stack.bs,), device=stack.tokens.device)
     for i in range(warmup):
-        stack.decode(tok, start_pos + i)
+        out = stack.decode(tok, start_pos + i)
+        if after is not None:
+            after(out)
     if dist.is_initialized():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        stack.decode(tok, start_pos + warmup + i)
+        out = stack.decode(tok, start_pos + warmup + i)
+        if after is not None:
+            after(out)
     if dist.is_initialized():
         dist.barrier()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / steps
+
+
+def torch_sample(logits, temperature, top_k, top_p):
+    """Temperature / top-k / top-p the way it is written in torch: a full sort of the row, softmax, cumsum, a masked softmax, multinomial."""
+    vals, idx = torch.sort(logits.float() / temperature, dim=-1, descending=True)
+    vals[:, top_k:] = float("-inf")
+    probs = torch.softmax(vals, dim=-1)
+    before = torch.cumsum(probs, dim=-1) - probs
+    probs = torch.softmax(vals.masked_fill(before >= top_p, float("-inf")), dim=-1)
+    return idx.gather(1, torch.multinomial(probs, 1)).squeeze(1)
+
+
+def sample_bench(a, cfg, device):
+    """--sample: the captured step without the sampler, with the sampler as its last node, and followed by the torch formulation;
+    and the sampler launch on its own."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    T, K, P = 0.8, 50, 0.95
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "vocab": cfg.vocab, "data": "synthetic (random weights, random tokens)",
+            "temperature": T, "top_k": K, "top_p": P, "steps": a.steps, "warmup": a.warmup, "start_pos": a.start_pos, "rounds": a.rounds}
+    legs = []
+    for bs in (1, 8):
+        def stack(sample):
+            st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                             fuse_gemm_stages=not a.no_fuse)
+            st.set_sampling(T, K, P, seed=list(range(bs)))
+            st.capture(sample=sample)
+            return st
+
+        plain, fused = stack(False), stack(True)
+        runs = {"step": (plain, None), "step_with_sampler_node": (fused, None),
+                "step_then_torch_sampler": (plain, lambda logits: torch_sample(logits, T, K, P)),
+                "step_then_eager_sampler": (plain, lambda logits: plain.sample(logits, plain.pos, 1))}
+        series = {k: [] for k in runs}
+        order = list(runs)
+        for r in range(a.rounds):
+            for k in order[r % len(order):] + order[: r % len(order)]:
+                st, after = runs[k]
+                series[k].append(round(time_steps(st, a.steps, a.warmup, a.start_pos, after) * 1e3, 4))
+        ms = {k: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "series": v} for k, v in series.items()}
+        # the sampler alone, back to back on the logits of the last step: kernel time (an empty launch is ~8 us of the ~70)
+        logits = plain._out
+        for _ in range(20):
+            plain.sample(logits, plain.pos, 1)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        ev[0].record()
+        for _ in range(200):
+            plain.sample(logits, plain.pos, 1)
+        ev[1].record()
+        torch.cuda.synchronize()
+        legs.append(dict(base, leg="captured step: plain / sampler as last node / followed by the torch formulation / by the eager sampler",
+                         bs=bs, graph_nodes={"step": getattr(plain, "graph_nodes", None), "step_with_sampler_node": getattr(fused, "graph_nodes", None)},
+                         ms_per_step=ms, sampler_node_us=round((ms["step_with_sampler_node"]["median"] - ms["step"]["median"]) * 1e3, 2),
+                         torch_sampler_us=round((ms["step_then_torch_sampler"]["median"] - ms["step"]["median"]) * 1e3, 2),
+                         sampler_back_to_back_us=round(ev[0].elapsed_time(ev[1]) / 200 * 1e3, 2)))
+        del plain, fused, runs
+        torch.cuda.empty_cache()
+    return legs
 
 
 def ragged_bench(a, cfg, device):
@@ -299,6 +369,8 @@ def main():
                     help="with --kv-cache mx8: the three-way comparison of DESIGN.md section 15 (16-bit, mx8 split, mx8 online; see the module docstring); one GPU")
     ap.add_argument("--paged", action="store_true",
                     help="the legs of DESIGN.md section 16: the paged KV cache against the contiguous one at an 8192-position cache (see the module docstring); one GPU")
+    ap.add_argument("--sample", action="store_true",
+                    help="the leg of DESIGN.md section 18: the captured step with and without the sampler node, and followed by the torch formulation (see the module docstring); one GPU")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
                                                 "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl, with both profiles/paged_mx8_bench.jsonl)")
     a = ap.parse_args()
@@ -308,6 +380,8 @@ def main():
     a.steps = a.steps if a.steps is not None else 30 if three_way else 100
     a.warmup = a.warmup if a.warmup is not None else 10 if three_way else 20
     a.rounds = a.rounds if a.rounds is not None else 5 if three_way else 7
+    if a.out is None and a.sample:
+        a.out = os.path.join(ROOT, "profiles", "sample_bench.jsonl")
     if a.out is None:
         a.out = os.path.join(ROOT, "profiles", "paged_mx8_bench.jsonl" if a.paged and a.kv_cache else "paged_bench.jsonl" if a.paged else "kv8_online_bench.jsonl" if three_way else
                              "kv8_bench.jsonl" if a.kv_cache else "ragged_bench.jsonl")
@@ -336,6 +410,16 @@ def main():
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.sample:
+        if world > 1:
+            raise SystemExit("--sample runs on one GPU")
+        with open(a.out, "a") as f:
+            for leg in sample_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     if a.paged:
         if world > 1:
