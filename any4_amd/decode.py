@@ -20,6 +20,10 @@ Launch structure, chosen for the hardware rather than copied from HF:
   * `DecodeLayer` states the layer once per schedule -- plain torch (`forward`, `forward_prefill`), eight launches (`forward_fused`),
     five launches (`forward_fused5`: the element-wise stages ride in the GEMMs) -- and the fused schedules take the attention launch as
     an argument: `decode_attention` (one token per sequence) or `prefill_attention` (a chunk; so far on the eight launches only);
+  * a layer's KV cache is one object, `DecodeLayer.kv` (any4_amd/kvcache.py: KVCache): it owns the tensors -- 16-bit or mx8 rows,
+    contiguous or page pools --, reads and writes them for the plain-torch formulations, gathers a paged cache's contiguous twin, and
+    picks the fused attention entry point from what it holds; the two attention fronts of the layer only hand over to it.  The stack
+    owns what the layers share: the block table and the page pool, the split count and its scratch buffer;
   * one position model: a stack whose sequences share a position is the ragged one (`ragged=True`: a position per sequence) with every
     position equal, so `DecodeStack` has one step, one `decode` front, one prefill loop (positions, lengths and cache slots as host
     lists; a call that names none per sequence still launches the scalar attention on `prefill_pos`) and one `generate`.  What differs
@@ -33,7 +37,6 @@ Launch structure, chosen for the hardware rather than copied from HF:
 """
 from __future__ import annotations
 
-import contextlib
 import math
 import operator
 import os
@@ -44,7 +47,7 @@ from typing import Callable, Optional
 import torch
 import torch.distributed as dist
 
-from .kvcache import F8, PagePool, mx8_decode, mx8_encode
+from .kvcache import KVCache, PagePool, check_cache_config
 
 
 @dataclass
@@ -196,14 +199,6 @@ def _rope(x, cos, sin):
     return (x.float() * cos + rot.float() * sin).to(x.dtype)
 
 
-def _mx8_put(write, cache, exps, new):
-    """The plain-torch write side of an mx8 cache (any4_amd/kvcache.py): `new` rows are encoded, and `write(tensor, rows)` -- the
-    caller's addressing, the one it uses on a 16-bit cache -- puts the codes (as bytes) and the exponent bytes in place."""
-    codes, e = mx8_encode(new)
-    write(cache.view(torch.uint8), codes.view(torch.uint8))
-    write(exps, e)
-
-
 def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl: int, kvl: int, d: int, T: int, k_exp=None, v_exp=None):
     """Plain-torch formulation of a prefill chunk's attention (what dg_prefill_attn is tested against; also the CPU path).
     qkv [bs * T, (hl + 2 kvl) d], row b * T + t = token t of sequence b at position p0 + t.  Ropes q and k with the table rows
@@ -218,14 +213,9 @@ def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl
     q = _rope(qkv[:, : hl * d].reshape(bs, T, hl, d), cos, sin)
     k = _rope(qkv[:, hl * d: (hl + kvl) * d].reshape(bs, T, kvl, d), cos, sin)
     v = qkv[:, (hl + kvl) * d:].reshape(bs, T, kvl, d)
-    if k_exp is None:
-        k_cache.index_copy_(2, rows, k.transpose(1, 2))
-        v_cache.index_copy_(2, rows, v.transpose(1, 2))
-        K, V = k_cache[:, :, :S], v_cache[:, :, :S]
-    else:
-        _mx8_put(lambda c, new: c.index_copy_(2, rows, new), k_cache, k_exp, k.transpose(1, 2))
-        _mx8_put(lambda c, new: c.index_copy_(2, rows, new), v_cache, v_exp, v.transpose(1, 2))
-        K, V = mx8_decode(k_cache[:, :, :S], k_exp[:, :, :S], qkv.dtype), mx8_decode(v_cache[:, :, :S], v_exp[:, :, :S], qkv.dtype)
+    kv = KVCache.over(k_cache, v_cache, k_exp, v_exp)
+    kv.write(lambda cache, new: cache.index_copy_(2, rows, new), k.transpose(1, 2), v.transpose(1, 2))
+    K, V = kv.read(qkv.dtype, S)
     qg = q.reshape(bs, T, kvl, rep, d).permute(0, 2, 3, 1, 4).reshape(bs, kvl, rep * T, d)
     att = torch.matmul(qg, K.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep * T, S]
     mask = torch.arange(S, device=qkv.device).view(1, S) > rows.view(T, 1)                    # [T, S]: s > p0 + t
@@ -256,27 +246,6 @@ def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots
     return ctx.view(n * T, hl * d)
 
 
-def check_page_size(cfg: DecodeConfig, kv_pages, page_size, kv_cache=None) -> None:
-    """The rule of a paged cache (include/decode_glue_hip.h): a page is a power of two of at least 64 positions, max_seq whole pages."""
-    if kv_pages is None:
-        return
-    if kv_cache == "mx8" and cfg.head_dim not in (64, 128):  # (fused or not: the only head sizes for which a kernel reads such pools)
-        raise ValueError(f"kv_pages with kv_cache='mx8': paged mx8 pools are not built yet for head_dim {cfg.head_dim} (64 and 128 are)")
-    ps = operator.index(page_size)
-    if operator.index(kv_pages) < 1:
-        raise ValueError(f"kv_pages must be at least 1, got {kv_pages}")
-    if ps < 64 or ps & (ps - 1) or ps > cfg.max_seq or cfg.max_seq % ps:
-        raise ValueError(f"page_size must be a power of two with 64 <= page_size <= max_seq = {cfg.max_seq} and max_seq % page_size == 0, got {ps}")
-
-
-def check_mx8_attention(mx8_attention, kv_cache) -> None:
-    """mx8_attention names the decode attention kernel of an mx8 cache: "split" (the default) or "online", which only such a cache takes."""
-    if mx8_attention not in ("split", "online"):
-        raise ValueError(f"mx8_attention must be 'split' or 'online', got {mx8_attention!r}")
-    if mx8_attention == "online" and kv_cache != "mx8":
-        raise ValueError("mx8_attention='online' needs kv_cache='mx8' (a 16-bit cache takes the one-barrier kernel by itself)")
-
-
 def _scatter_rows(cache, pos, active, new):
     """cache[b, :, pos[b], :] = new[b] for the active sequences b, with `pos` [bs] (clamped into the cache) and `active` [bs] on the
     device: an inactive sequence gets its own row back, so nothing is read on the host and nothing of it changes."""
@@ -285,25 +254,28 @@ def _scatter_rows(cache, pos, active, new):
 
 
 class DecodeLayer(torch.nn.Module):
+    """One decoder layer: four fused linears, two norms and `kv`, its KV cache (any4_amd/kvcache.py: KVCache, the one place that knows
+    what the cache looks like and which attention kernel goes with it).
+    `k_cache`, `v_cache`, `k_exp`, `v_exp` (a contiguous cache's tensors) and `k_pool`, `v_pool`, `k_exp_pool`, `v_exp_pool` (a paged
+    one's) are read-only views of `kv` for the test suites and the dev tools, each None where the layer has no such tensor; nothing in
+    the package reads them.  A later change may move the suites to `layer.kv` and drop them."""
+
+    k_cache, v_cache, k_exp, v_exp = (property(lambda self, n=n: None if self.kv.paged else getattr(self.kv, n)) for n in ("k", "v", "k_exp", "v_exp"))
+    k_pool, v_pool, k_exp_pool, v_exp_pool = (property(lambda self, n=n: getattr(self.kv, n) if self.kv.paged else None)
+                                              for n in ("k", "v", "k_exp", "v_exp"))
+
     def __init__(self, cfg: DecodeConfig, idx: int, factory: Callable, rank: int, world: int, device, dtype, bs: int,
                  kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64, mx8_attention: str = "split"):
         """kv_cache: None = k / v rows in the layer's dtype; "mx8" = block-scaled 8-bit rows (any4_amd/kvcache.py): float8_e4m3fn codes
-        in `k_cache` / `v_cache` and one exponent byte per 32 elements in `k_exp` / `v_exp` (both None for a 16-bit cache).
+        in `kv.k` / `kv.v` and one exponent byte per 32 elements in `kv.k_exp` / `kv.v_exp` (both None for a 16-bit cache).
         mx8_attention: the fused decode attention of an mx8 cache -- "split" (the 256-thread split kernel) or "online" (the one-barrier
         kernel, head_dim 64 / 128); the plain-torch path is the same for both.  A paged mx8 layer (kv_pages) accepts either value and
         always runs the one-barrier kernel.
-        kv_pages: a paged cache -- `k_pool` / `v_pool` [kv_pages, kvl, page_size, d] in place of the caches (which are None), addressed
-        through `block_table` int32 [bs, max_seq / page_size], the stack's (it is shared by all layers and set by the stack).  With
-        kv_cache="mx8" (head_dim 64 / 128) four pools behind that table: `k_pool` / `v_pool` hold the float8_e4m3fn codes, `k_exp_pool` /
-        `v_exp_pool` uint8 [kv_pages, kvl, page_size, d / 32] the exponent bytes."""
+        kv_pages: a paged cache -- `kv.k` / `kv.v` are pools [kv_pages, kvl, page_size, d], addressed through `kv.table` int32 [bs,
+        max_seq / page_size], the stack's (it is shared by all layers and set by the stack).  With kv_cache="mx8" (head_dim 64 / 128) four
+        pools behind that table: the float8_e4m3fn codes and, in `kv.k_exp` / `kv.v_exp` uint8 [kv_pages, kvl, page_size, d / 32], the
+        exponent bytes."""
         super().__init__()
-        check_page_size(cfg, kv_pages, page_size, kv_cache)
-        if kv_cache not in (None, "mx8"):
-            raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
-        if kv_cache == "mx8" and cfg.head_dim % 32:
-            raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
-        check_mx8_attention(mx8_attention, kv_cache)
-        self.mx8_attention = mx8_attention
         if cfg.heads % world or cfg.kv_heads % world or cfg.inter % (16 * world) or cfg.hidden % (16 * world):
             raise ValueError(f"heads={cfg.heads}, kv_heads={cfg.kv_heads}, inter={cfg.inter}, hidden={cfg.hidden} "
                              f"must split over world_size={world} in whole heads / 16-row tiles")
@@ -316,52 +288,24 @@ class DecodeLayer(torch.nn.Module):
         self.down = factory("down", idx, cfg.inter, cfg.hidden // world)
         self.norm1 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.norm2 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
-        self.block_table = None
-        if kv_pages is not None:
-            code_dtype = torch.uint8 if kv_cache == "mx8" else dtype
-            for name in ("k", "v"):
-                pool = torch.zeros(kv_pages, self.kvl, page_size, d, device=device, dtype=code_dtype)
-                self.register_buffer(name + "_pool", pool.view(F8) if kv_cache == "mx8" else pool, persistent=False)
-                if kv_cache == "mx8":
-                    self.register_buffer(name + "_exp_pool", torch.zeros(kv_pages, self.kvl, page_size, d // 32, device=device, dtype=torch.uint8),
-                                         persistent=False)
-            self.k_cache = self.v_cache = self.k_exp = self.v_exp = None
-        elif kv_cache == "mx8":
-            for name in ("k", "v"):
-                self.register_buffer(name + "_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=torch.uint8).view(F8),
-                                     persistent=False)
-                self.register_buffer(name + "_exp", torch.zeros(bs, self.kvl, cfg.max_seq, d // 32, device=device, dtype=torch.uint8),
-                                     persistent=False)
-        else:
-            self.register_buffer("k_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
-            self.register_buffer("v_cache", torch.zeros(bs, self.kvl, cfg.max_seq, d, device=device, dtype=dtype), persistent=False)
-            self.k_exp = self.v_exp = None
-        if kv_pages is None or kv_cache != "mx8":
-            self.k_exp_pool = self.v_exp_pool = None  # (only a paged mx8 layer has exponent pools)
+        self.kv = KVCache(cfg, self.kvl, bs, device, dtype, kv_cache, kv_pages, page_size, mx8_attention)  # (refuses what check_cache_config refuses)
+        self.mx8_attention = mx8_attention
         # forward_fused5: which stages the library fused (None: not tried yet; set by the first step)
         self._fuse = {"norm1": None, "norm2": None, "mlp": None}
-        # decode_attention: the stack's split count and its scratch buffer (DecodeStack sets both once, when it is built)
-        self._attn_scratch, self._attn_split = None, 1
 
-    def _token_torch(self, h, cos, sin, write, mask, gather):
-        """The plain-torch arithmetic of one token per sequence, behind either addressing (`forward`, `forward_seq`): `cos` / `sin` the
-        rope rows [1 | bs, 1, d], `write(cache, rows [bs, kvl, d])` puts the new k / v rows into a cache, `mask` [1 | bs, 1, 1, S] hides
-        the cache rows behind each position.  Rounding points: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit
-        P.V (the formulation the fused schedules are tested against).  An mx8 cache: the rows are encoded on the way in and the
-        attention reads mx8_decode of the cache, the new token's own rows included."""
+    def _token_torch(self, kv, h, cos, sin, write, mask, gather):
+        """The plain-torch arithmetic of one token per sequence, behind either addressing (`forward`, `forward_seq`): `kv` the cache
+        (a paged one's gathered twin), `cos` / `sin` the rope rows [1 | bs, 1, d], `write(cache, rows [bs, kvl, d])` puts the new k / v
+        rows into a cache, `mask` [1 | bs, 1, 1, S] hides the cache rows behind each position.  Rounding points: 16-bit score matmul,
+        f32 scale + softmax, 16-bit probabilities, 16-bit P.V (the formulation the fused schedules are tested against).  An mx8 cache:
+        the rows are encoded on the way in and the attention reads mx8_decode of the cache, the new token's own rows included."""
         d, bs = self.cfg.head_dim, h.shape[0]
         qkv = self.qkv(self.norm1(h))
         q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
         k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
         v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
-        if self.k_exp is None:
-            write(self.k_cache, k)
-            write(self.v_cache, v)
-            K, V = self.k_cache, self.v_cache
-        else:
-            _mx8_put(write, self.k_cache, self.k_exp, k)
-            _mx8_put(write, self.v_cache, self.v_exp, v)
-            K, V = mx8_decode(self.k_cache, self.k_exp, h.dtype), mx8_decode(self.v_cache, self.v_exp, h.dtype)
+        kv.write(write, k, v)
+        K, V = kv.read(h.dtype)
         rep = self.hl // self.kvl
         qg = q.reshape(bs, self.kvl, rep, d)
         att = torch.matmul(qg, K.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
@@ -373,78 +317,37 @@ class DecodeLayer(torch.nn.Module):
         """Plain torch, one token per sequence, every sequence at `pos` [1] on the device: one rope row, one cache row and one mask
         for the batch."""
         cos, sin = cos_tab.index_select(0, pos).view(1, 1, -1), sin_tab.index_select(0, pos).view(1, 1, -1)
-        return self._token_torch(h, cos, sin, lambda cache, new: cache.index_copy_(2, pos, new.unsqueeze(2)),
+        return self._token_torch(self.kv, h, cos, sin, lambda cache, new: cache.index_copy_(2, pos, new.unsqueeze(2)),
                                  (arange > pos).view(1, 1, 1, -1), gather)
 
     def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather):
         """`forward` with a position per sequence: `pos` int64 [bs] on the device.  Sequence b takes rope row pos[b], writes cache row
         pos[b] and sees rows <= pos[b]; one whose position is outside [0, max_seq) is inactive: its caches keep their bits (its row of
         the result is unspecified).  No value is read on the host.
-        A paged layer runs the same formulation on a contiguous view gathered through the block table and puts the written rows back
-        into the pools (`_paged_view`; that path does read a mask on the host)."""
+        A paged layer runs the same formulation on a contiguous cache gathered through the block table and puts the written rows back
+        into the pools (`KVCache.gathered`; that path does read a mask on the host)."""
         d, bs = self.cfg.head_dim, h.shape[0]
         active = (pos >= 0) & (pos < self.cfg.max_seq)
         pc = pos.clamp(0, self.cfg.max_seq - 1)
         cos, sin = cos_tab.index_select(0, pc).view(bs, 1, d), sin_tab.index_select(0, pc).view(bs, 1, d)
-        with self._paged_view() as put:
-            out = self._token_torch(h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
-                                    arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
-            if self.block_table is not None:
-                put(torch.arange(bs, device=pos.device)[active], pc[active])
+        kv, put = self.kv.gathered()
+        out = self._token_torch(kv, h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
+                                arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
+        if put is not None:
+            put(torch.arange(bs, device=pos.device)[active], pc[active])
         return out
-
-    @contextlib.contextmanager
-    def _paged_view(self):
-        """The plain-torch twin of a paged layer (what the paged kernels are tested against, not a product): inside the block `k_cache`
-        / `v_cache` are [bs, kvl, max_seq, d] copies gathered through the table, with entries outside the pool clamped to page 0 as the
-        kernels clamp them, so that the contiguous formulation runs unchanged; `put(slots, positions)` (two int64 tensors of one length)
-        copies those rows of the view back into the pools, dropping a row whose own table entry is outside the pool.  mx8 pools: codes
-        AND exponent bytes are gathered (`k_exp` / `v_exp` too) and put back, so that the contiguous mx8 formulation runs unchanged.
-        A layer without pools: nothing happens."""
-        if self.block_table is None:
-            yield lambda slots, positions: None
-            return
-        n, _, ps, d = self.k_pool.shape
-        tab = self.block_table.long()
-        valid = (tab >= 0) & (tab < n)
-        idx = torch.where(valid, tab, torch.zeros_like(tab))
-        bs = tab.shape[0]
-        views = {"k_cache": self.k_pool, "v_cache": self.v_pool}
-        if self.k_exp_pool is not None:
-            views.update(k_exp=self.k_exp_pool, v_exp=self.v_exp_pool)
-        for name, pool in views.items():
-            # (float8 codes travel as their bytes: indexing is not implemented for that dtype everywhere)
-            raw = pool.view(torch.uint8) if pool.dtype == F8 else pool
-            view = raw[idx].permute(0, 2, 1, 3, 4).reshape(bs, self.kvl, self.cfg.max_seq, pool.shape[3])
-            setattr(self, name, view.view(pool.dtype))
-
-        def put(slots, positions):
-            ok = valid[slots, positions // ps]
-            slots, positions = slots[ok], positions[ok]
-            pages = tab[slots, positions // ps]
-            for name, pool in views.items():
-                view = getattr(self, name)
-                if pool.dtype == F8:
-                    view, pool = view.view(torch.uint8), pool.view(torch.uint8)
-                pool[pages, :, positions % ps] = view[slots, :, positions]
-
-        try:
-            yield put
-        finally:
-            self.k_cache = self.v_cache = self.k_exp = self.v_exp = None
 
     def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
         """Plain torch, a chunk of tokens per sequence: `h` [n * T, hidden] (row i * T + t), rows padded to the common T.  Host ints
         per sequence: token 0 of sequence i at `positions[i]`, `lengths[i]` tokens, cache slot `slots[i]`.  Each sequence's k / v rows
         are appended to its caches and every token attends causally over cache + chunk (a batch in which nothing differs: in one
-        batched formulation, prefill_attention_torch)."""
-        d = self.cfg.head_dim
-        with self._paged_view() as put:
-            ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, self.k_cache, self.v_cache,
-                                              self.hl, self.kvl, d, T, self.k_exp, self.v_exp)
-            if self.block_table is not None:
-                rows = [(sl, p + t) for p, n, sl in zip(positions, lengths, slots) for t in range(n)]
-                put(*[torch.tensor([r[i] for r in rows], dtype=torch.long, device=h.device) for i in (0, 1)])
+        batched formulation, prefill_attention_torch).  A paged layer: on its gathered twin, as forward_seq."""
+        kv, put = self.kv.gathered()
+        ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, kv.k, kv.v,
+                                          self.hl, self.kvl, self.cfg.head_dim, T, kv.k_exp, kv.v_exp)
+        if put is not None:
+            rows = [(sl, p + t) for p, n, sl in zip(positions, lengths, slots) for t in range(n)]
+            put(*[torch.tensor([r[i] for r in rows], dtype=torch.long, device=h.device) for i in (0, 1)])
         return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
 
     def _mlp_torch(self, h, gather):
@@ -454,59 +357,16 @@ class DecodeLayer(torch.nn.Module):
         act = torch.nn.functional.silu(gu[:, :il]) * gu[:, il:]
         return h + gather(self.down(gather(act)))
 
-    # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context
+    # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context.
+    # Which entry point that is follows from what the cache is: KVCache.decode_attention / prefill_attention
     def decode_attention(self, qkv, pos, cos_tab, sin_tab, per_sequence: bool = False):
-        """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
-        stack gave this layer a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one.  An mx8 cache
-        always takes an entry point with a scratch buffer (also at a split count of 1): the 256-thread split kernel's, or with
-        mx8_attention="online" the one-barrier kernel's.  Pools behind the block table take the _paged entry points; mx8 pools the one
-        _mx8_paged entry point (the one-barrier kernel, with the stack's split count and scratch)."""
-        from . import decode_ops as G
-
-        d = self.cfg.head_dim
-        if self.block_table is not None:  # pools behind the block table: the _paged entry points (a position per sequence, d = 64 / 128)
-            if not per_sequence:
-                raise RuntimeError("a paged KV cache has a position per sequence")
-            args = (qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
-            if self.k_exp_pool is not None:  # mx8 pools: always the one-barrier kernel, whatever mx8_attention names
-                if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
-                    self._attn_scratch = G.rope_attn_split_scratch(self.block_table.shape[0], self.hl, d, self._attn_split, qkv.device)
-                return G.rope_attn_online_mx8_paged(*args[:7], self.k_exp_pool, self.v_exp_pool, *args[7:], self._attn_scratch, self._attn_split)
-            if self._attn_scratch is not None:
-                return G.rope_attn_split_paged(*args, self._attn_scratch, self._attn_split)
-            return G.rope_attn_online_paged(*args)
-        args = (qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d))
-        if self.k_exp is not None:
-            if self._attn_scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
-                self._attn_scratch = G.rope_attn_split_scratch(self.k_cache.shape[0], self.hl, d, self._attn_split, qkv.device)
-            if self.mx8_attention == "online":
-                return G.rope_attn_online_mx8(*args[:6], self.k_exp, self.v_exp, *args[6:], self._attn_scratch, self._attn_split,
-                                              per_sequence=per_sequence)
-            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp)
-        if self._attn_scratch is not None:
-            return G.rope_attn_split(*args, self._attn_scratch, self._attn_split, per_sequence=per_sequence)
-        return (G.rope_attn_online if d in (64, 128) else G.rope_attn)(*args, per_sequence=per_sequence)
+        """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points)."""
+        return self.kv.decode_attention(qkv, pos, cos_tab, sin_tab, self.hl, per_sequence)
 
     def prefill_attention(self, qkv, pos, cos_tab, sin_tab, T: Optional[int] = None, lengths=None, slots=None, per_sequence: bool = False):
-        """A chunk of T tokens per sequence (row b * T + t; default T = rows / the caches' batch), token 0 at `pos` [1]: T cache rows
-        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device (dg_prefill_attn_seq); the context rows of
-        tokens that do not exist are zero."""
-        from . import decode_ops as G
-
-        d = self.cfg.head_dim
-        if self.block_table is not None:
-            if not per_sequence or T is None:
-                raise RuntimeError("a paged KV cache has a position per sequence")
-            if self.k_exp_pool is not None:
-                return G.prefill_attn_mx8_paged(qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.k_exp_pool,
-                                                self.v_exp_pool, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
-                                                out=qkv.new_zeros(qkv.shape[0], self.hl * d), lengths=lengths, slots=slots)
-            return G.prefill_attn_paged(qkv, cos_tab, sin_tab, pos, self.block_table, self.k_pool, self.v_pool, self.hl, self.kvl, d,
-                                        1.0 / math.sqrt(d), T, out=qkv.new_zeros(qkv.shape[0], self.hl * d), lengths=lengths, slots=slots)
-        T = qkv.shape[0] // self.k_cache.shape[0] if T is None else T
-        out = qkv.new_zeros(qkv.shape[0], self.hl * d) if per_sequence else None
-        return G.prefill_attn(qkv, cos_tab, sin_tab, pos, self.k_cache, self.v_cache, self.hl, self.kvl, d, 1.0 / math.sqrt(d), T,
-                              out=out, lengths=lengths, slots=slots, per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp)
+        """A chunk of T tokens per sequence (row b * T + t; default T = rows / the cache's batch), token 0 at `pos` [1]: T cache rows
+        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device."""
+        return self.kv.prefill_attention(qkv, pos, cos_tab, sin_tab, self.hl, T, lengths, slots, per_sequence)
 
     def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather):
         """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
@@ -647,12 +507,7 @@ class DecodeStack(torch.nn.Module):
         self.paged = kv_pages is not None
         if self.paged and not ragged:
             raise ValueError("kv_pages (a paged KV cache) needs DecodeStack(..., ragged=True)")
-        check_page_size(cfg, kv_pages, page_size, kv_cache)
-        if kv_cache not in (None, "mx8"):
-            raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
-        if kv_cache == "mx8" and cfg.head_dim % 32:
-            raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
-        check_mx8_attention(mx8_attention, kv_cache)
+        check_cache_config(cfg, kv_cache, kv_pages, page_size, mx8_attention)
         self.kv_cache, self.mx8_attention = kv_cache, mx8_attention
         self.gather_mode = gather
         self._peer = {}  # output width per rank -> PeerWriteGather
@@ -677,8 +532,6 @@ class DecodeStack(torch.nn.Module):
             self._table = [[-1] * (cfg.max_seq // self.page_size) for _ in range(bs)]  # the host mirror of block_table
             self.register_buffer("block_table", torch.full((bs, cfg.max_seq // self.page_size), -1, dtype=torch.int32, device=device),
                                  persistent=False)
-            for layer in self.layers:
-                layer.block_table = self.block_table
         self.norm = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.lm_head = None
         if lm_head:
@@ -720,16 +573,12 @@ class DecodeStack(torch.nn.Module):
                 self._attn_split = max(1, int(os.environ["ANY4_ATTN_SPLIT"]))
             if self._attn_split > 1 or kv_cache == "mx8":
                 self._attn_scratch = G.rope_attn_split_scratch(bs, hl, cfg.head_dim, self._attn_split, device)
-            for layer in self.layers:
-                layer._attn_scratch, layer._attn_split = self._attn_scratch, self._attn_split
+        for layer in self.layers:  # what the stack owns of every layer's cache (as built: no table, no scratch, one block per head)
+            layer.kv.table, layer.kv.scratch, layer.kv.nsplit = self.block_table if self.paged else None, self._attn_scratch, self._attn_split
 
     def kv_cache_bytes(self) -> int:
         """Bytes of this rank's KV cache over all layers (an mx8 cache: codes and exponent bytes; a paged one: the pools, all four of an mx8 one)."""
-        if self.paged:
-            return sum(t.numel() * t.element_size() for layer in self.layers
-                       for t in (layer.k_pool, layer.v_pool, layer.k_exp_pool, layer.v_exp_pool) if t is not None)
-        return sum(t.numel() * t.element_size() for layer in self.layers
-                   for t in (layer.k_cache, layer.v_cache, layer.k_exp, layer.v_exp) if t is not None)
+        return sum(t.numel() * t.element_size() for layer in self.layers for t in layer.kv.tensors())
 
     # ---- the paged cache: which pages a slot holds (host mirror `_table`, device `block_table`, counts in `page_pool`) ----
     def _need_paged(self, slot=None):
@@ -805,10 +654,8 @@ class DecodeStack(torch.nn.Module):
         self._sync_row(dst)
         if part:
             for layer in self.layers:
-                for pool in (layer.k_pool, layer.v_pool, layer.k_exp_pool, layer.v_exp_pool):
-                    if pool is not None:
-                        raw = pool.view(torch.uint8) if pool.dtype == F8 else pool
-                        raw[fresh[0], :, :part] = raw[self._table[src][full], :, :part]
+                for pool in layer.kv.tensors():
+                    pool[fresh[0], :, :part] = pool[self._table[src][full], :, :part]
 
     # [bs, n/G] on every rank -> [bs, n], rank-major feature order (== row order of the unsharded weight)
     def _gather(self, y, peer_ok=True):

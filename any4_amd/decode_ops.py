@@ -106,24 +106,38 @@ def _mx8_exps(what, k_cache, v_cache, k_exp, v_exp, d):
     return (k_exp, v_exp)
 
 
-def _paged(what, table, k_pool, v_pool, kvl, d):
+def _paged(what, table, k_pool, v_pool, kvl, d, exps=()):
     """The paging arguments of a `_paged` launch, checked: `table` int32 [cache_bs, max_seq / page_size] on the pools' device, the pools
-    [num_pages, kvl, page_size, d] in a 16-bit type.  Returns them by argument name, with max_seq."""
+    [num_pages, kvl, page_size, d] in a 16-bit type -- or, with exps = (k_exp, v_exp) (checked already: _mx8_pools), float8_e4m3fn codes of
+    an `_mx8_paged` launch.  Returns them by argument name, with max_seq (the exponents go in with every mx8 call: _attn_launch)."""
     if table.dtype != torch.int32 or table.dim() != 2 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape or k_pool.dtype != v_pool.dtype or \
             tuple(k_pool.shape[1::2]) != (kvl, d):
         raise RuntimeError(f"{what}: table must be int32 [cache_bs, max_seq / page_size] and the pools [num_pages, {kvl}, page_size, {d}], got "
                            f"{table.dtype} {tuple(table.shape)}, {tuple(k_pool.shape)}, {tuple(v_pool.shape)}")
-    if k_pool.dtype not in (torch.bfloat16, torch.float16):
+    if not exps and k_pool.dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError(f"{what}: a paged cache holds 16-bit rows, got {k_pool.dtype}")
     num_pages, _, page_size, _ = k_pool.shape
     return dict(table=table, k_pool=k_pool, v_pool=v_pool, page_size=page_size, num_pages=num_pages, max_seq=table.shape[1] * page_size)
 
 
+def _mx8_pools(what, k_pool, v_pool, k_exp, v_exp, d):
+    """(k_exp, v_exp) of mx8 page pools, checked on the host (in front of the device check): code pools float8_e4m3fn [num_pages, kvl,
+    page_size, d], exponent pools uint8 [num_pages, kvl, page_size, d / 32].  16-bit pools do not belong to the entry points that ask."""
+    exps = _mx8_exps(what, k_pool, v_pool, k_exp, v_exp, d)
+    if not exps:
+        raise RuntimeError(f"{what}: the pools must be float8_e4m3fn (mx8), got {k_pool.dtype}; 16-bit pools: the _paged entry points")
+    return exps
+
+
 def _attn_launch(base, seq, exps, qkv, paged=False, kv8_online=False, **values):
     """One launch of an attention entry point: _lib.attn_signature names the flavour of `base` (seq: `_seq`; exps = (k_exp, v_exp) of an
     mx8 cache: `_mx8`; paged: `_paged`) and the order of its arguments; `values` are given by argument name, tensors (or None) for
-    pointers.  qkv also supplies dtype, device and stream.  kv8_online: dg_rope_attn_online_mx8(_seq), _lib.kv8_online_signature."""
-    entry, args = _lib.kv8_online_signature(seq) if kv8_online else _lib.attn_signature(base, seq, bool(exps), paged)
+    pointers.  qkv also supplies dtype, device and stream.  kv8_online: dg_rope_attn_online_mx8(_seq), _lib.kv8_online_signature; exps
+    and paged: the `_mx8_paged` entry point of `base`, _lib.paged_mx8_signature."""
+    if exps and paged:
+        entry, args = _lib.paged_mx8_signature(base)
+    else:
+        entry, args = _lib.kv8_online_signature(seq) if kv8_online else _lib.attn_signature(base, seq, bool(exps), paged)
     values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
     ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
     _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
@@ -134,7 +148,7 @@ def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, pe
     """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
     `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points; table: the
     caches are page pools behind this block table: the _paged entry points (per sequence); kv8_online: rope_attn_online_mx8 (split and
-    exps given, base dg_rope_attn_online)."""
+    exps given, base dg_rope_attn_online); exps and table: rope_attn_online_mx8_paged (split given, base dg_rope_attn_online)."""
     scratch, nsplit = split if split is not None else (None, None)
     out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, table, *exps, out=out)
     what = base + ("_mx8" if exps else "") + ("_paged" if table is not None else "")
@@ -146,7 +160,7 @@ def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, pe
     if table is not None:
         if table.shape[0] != bs:
             raise RuntimeError(f"{what}: the table needs a row per sequence ({bs}), got {tuple(table.shape)}")
-        more.update(_paged(what, table, k_cache, v_cache, kvl, d))
+        more.update(_paged(what, table, k_cache, v_cache, kvl, d, exps))
     else:
         more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
     _attn_launch(base, per_sequence, exps, qkv, table is not None, kv8_online, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
@@ -224,44 +238,14 @@ def prefill_attn_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, 
     return prefill_attn(qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, T, out, lengths, slots, True, table=table)
 
 
-def _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d):
-    """The pool arguments of a `_mx8_paged` launch, checked on the host: code pools float8_e4m3fn [num_pages, kvl, page_size, d], exponent
-    pools uint8 [num_pages, kvl, page_size, d / 32], `table` int32 [cache_bs, max_seq / page_size].  By argument name, with max_seq."""
-    if not _mx8_exps(what, k_pool, v_pool, k_exp, v_exp, d):
-        raise RuntimeError(f"{what}: the pools must be float8_e4m3fn (mx8), got {k_pool.dtype}; 16-bit pools: the _paged entry points")
-    if table.dtype != torch.int32 or table.dim() != 2 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape or tuple(k_pool.shape[1::2]) != (kvl, d):
-        raise RuntimeError(f"{what}: table must be int32 [cache_bs, max_seq / page_size] and the pools [num_pages, {kvl}, page_size, {d}], got "
-                           f"{table.dtype} {tuple(table.shape)}, {tuple(k_pool.shape)}, {tuple(v_pool.shape)}")
-    num_pages, _, page_size, _ = k_pool.shape
-    return dict(table=table, k_pool=k_pool, v_pool=v_pool, k_exp=k_exp, v_exp=v_exp, page_size=page_size, num_pages=num_pages,
-                max_seq=table.shape[1] * page_size)
-
-
-def _paged_mx8_launch(base, qkv, **values):
-    """One launch of a `_mx8_paged` entry point (_lib.paged_mx8_signature: the order of its arguments), values by argument name."""
-    entry, args = _lib.paged_mx8_signature(base)
-    values.update(qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
-    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
-    _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
-
-
 def rope_attn_online_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,
                                k_pool: torch.Tensor, v_pool: torch.Tensor, k_exp: torch.Tensor, v_exp: torch.Tensor, hl: int, kvl: int, d: int,
                                scale: float, scratch: torch.Tensor, nsplit: int, out: torch.Tensor = None) -> torch.Tensor:
     """rope_attn_online_mx8(per_sequence=True) on paged mx8 pools: codes float8_e4m3fn [num_pages, kvl, page_size, d] and exponents uint8
     [num_pages, kvl, page_size, d / 32] behind the one `table` (rope_attn_online_paged).  Always the one-barrier kernel, `nsplit` blocks per
     head (1 ... 64; `scratch` as for rope_attn_split); bytes written and output are rope_attn_online_mx8's on caches holding the same rows."""
-    what = "rope_attn_online_mx8_paged"
-    pools = _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d)
-    out, bs, _ = _rope_front(qkv, cos, sin, pos, k_pool, v_pool, hl, d, scratch, table, k_exp, v_exp, out=out)
-    if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
-        raise RuntimeError(f"{what}: out must be [{bs}, {hl * d}] {qkv.dtype}")
-    _per_sequence(pos, bs, what)
-    if table.shape[0] != bs:
-        raise RuntimeError(f"{what}: the table needs a row per sequence ({bs}), got {tuple(table.shape)}")
-    _paged_mx8_launch("dg_rope_attn_online", qkv, cos=cos, sin=sin, pos=pos, out=out, scratch=scratch, scratch_bytes=scratch.numel() * 4, bs=bs,
-                      hl=hl, kvl=kvl, d=d, scale=float(scale), nsplit=nsplit, **pools)
-    return out
+    exps = _mx8_pools("rope_attn_online_mx8_paged", k_pool, v_pool, k_exp, v_exp, d)
+    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), exps, table)
 
 
 def prefill_attn_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
@@ -269,23 +253,8 @@ def prefill_attn_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
                            out: torch.Tensor = None, lengths: torch.Tensor = None, slots: torch.Tensor = None) -> torch.Tensor:
     """prefill_attn(per_sequence=True) on paged mx8 pools (rope_attn_online_mx8_paged): `slots` names the table ROW of each sequence
     (default: row i, and n must be the table's rows)."""
-    what = "prefill_attn_mx8_paged"
-    pools = _paged_mx8(what, table, k_pool, v_pool, k_exp, v_exp, kvl, d)
-    out, rows, _ = _rope_front(qkv, cos, sin, pos, k_pool, v_pool, hl, d, lengths, slots, table, k_exp, v_exp, out=out)
-    T = int(T)
-    cache_bs = table.shape[0]
-    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != cache_bs and slots is None):
-        raise RuntimeError(f"{what}: qkv must be [n * T, ...] with T = {T} and n = {cache_bs} (the table's rows), got {tuple(qkv.shape)}")
-    if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
-        raise RuntimeError(f"{what}: out must be [{rows}, {hl * d}] {qkv.dtype}")
-    n = rows // T
-    _per_sequence(pos, n, what)
-    for name, t in (("lengths", lengths), ("slots", slots)):
-        if t is not None and (t.dtype != torch.int64 or t.numel() != n):
-            raise RuntimeError(f"{what}: {name} must be int64 with {n} elements (one per sequence)")
-    _paged_mx8_launch("dg_prefill_attn", qkv, cos=cos, sin=sin, pos=pos, len=lengths, slot=slots, out=out, bs=n, T=T, cache_bs=cache_bs,
-                      hl=hl, kvl=kvl, d=d, scale=float(scale), **pools)
-    return out
+    _mx8_pools("prefill_attn_mx8_paged", k_pool, v_pool, k_exp, v_exp, d)
+    return prefill_attn(qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, T, out, lengths, slots, True, k_exp, v_exp, table)
 
 
 def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
@@ -300,7 +269,8 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     position of token 0 of each sequence.  `lengths` int64 [n] on the device: only tokens t < min(lengths[i], T) exist (default: all T);
     `slots` int64 [n] on the device: sequence i lives in cache slot slots[i] (default: slot i, and n must be the caches' batch; with
     slots n may be smaller).  A sequence of length <= 0 or with a slot outside the caches does nothing; slots must be distinct.
-    float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split.  table: prefill_attn_paged."""
+    float8_e4m3fn caches with `k_exp`, `v_exp`: an mx8 cache, as in rope_attn_split.  table: prefill_attn_paged (with mx8 pools:
+    prefill_attn_mx8_paged)."""
     exps = _mx8_exps("prefill_attn", k_cache, v_cache, k_exp, v_exp, d)
     out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, table, *exps, out=out)
     T = int(T)
@@ -319,7 +289,7 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
                 raise RuntimeError(f"prefill_attn: {name} must be int64 with {n} elements (one per sequence)")
         more = dict(len=lengths, slot=slots, cache_bs=cache_bs)
     if table is not None:
-        more.update(_paged("prefill_attn_paged", table, k_cache, v_cache, kvl, d))
+        more.update(_paged("prefill_attn_mx8_paged" if exps else "prefill_attn_paged", table, k_cache, v_cache, kvl, d, exps))
     else:
         more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
     _attn_launch("dg_prefill_attn", per_sequence, exps, qkv, table is not None, cos=cos, sin=sin, pos=pos, out=out, bs=rows // T, T=T,

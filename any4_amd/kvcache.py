@@ -1,5 +1,7 @@
-"""KV-cache formats and bookkeeping of the decode stack.  `PagePool` (at the end) is the host side of the paged cache: which pages of a
-layer's pools are free and how many block-table entries point at each.
+"""KV-cache formats and bookkeeping of the decode stack.  `KVCache` is a layer's cache: the one place that knows its storage (16-bit or
+mx8 rows, contiguous or page pools) and which attention kernel goes with it; `check_cache_config` is the one copy of its rules.
+`PagePool` (at the end) is the host side of the paged cache: which pages of a layer's pools are free and how many block-table entries
+point at each.
 
 The `mx8` KV-cache format of the decode stack: block-scaled 8-bit rows (OCP MXFP8: E4M3 elements, one E8M0 exponent byte per 32
 consecutive elements of a row).  Plain torch, CPU and GPU; `mx8_encode` IS the definition of the format -- the HIP writers
@@ -19,7 +21,12 @@ same values.
 """
 from __future__ import annotations
 
+import math
+import operator
+
 import torch
+
+from . import decode_ops as G  # (binds nothing of the library until a kernel is launched)
 
 BLOCK = 32
 F8 = torch.float8_e4m3fn
@@ -62,6 +69,146 @@ def mx8_decode(codes: torch.Tensor, exps: torch.Tensor, dtype: torch.dtype) -> t
     vals = codes.float().reshape(*codes.shape[:-1], nb, BLOCK) * mx8_scale(exps).unsqueeze(-1)
     vals = torch.where((exps == 255).unsqueeze(-1), torch.full_like(vals, float("nan")), vals)
     return vals.reshape(codes.shape).to(dtype)
+
+
+def check_cache_config(cfg, kv_cache=None, kv_pages=None, page_size=64, mx8_attention="split") -> None:
+    """The rules of a layer's KV cache (`cfg`: head_dim and max_seq), in the order they are refused.  A paged cache (include/
+    decode_glue_hip.h): a page is a power of two of at least 64 positions, max_seq whole pages.  kv_cache: None or "mx8", which needs
+    head_dim % 32 == 0.  mx8_attention names the decode attention kernel of an mx8 cache: "split" (the default) or "online", which only
+    such a cache takes."""
+    if kv_pages is not None:
+        if kv_cache == "mx8" and cfg.head_dim not in (64, 128):  # (fused or not: the only head sizes for which a kernel reads such pools)
+            raise ValueError(f"kv_pages with kv_cache='mx8': paged mx8 pools are not built yet for head_dim {cfg.head_dim} (64 and 128 are)")
+        ps = operator.index(page_size)
+        if operator.index(kv_pages) < 1:
+            raise ValueError(f"kv_pages must be at least 1, got {kv_pages}")
+        if ps < 64 or ps & (ps - 1) or ps > cfg.max_seq or cfg.max_seq % ps:
+            raise ValueError(f"page_size must be a power of two with 64 <= page_size <= max_seq = {cfg.max_seq} and max_seq % page_size == 0, got {ps}")
+    if kv_cache not in (None, "mx8"):
+        raise ValueError(f"kv_cache must be None (the stack's dtype) or 'mx8', got {kv_cache!r}")
+    if kv_cache == "mx8" and cfg.head_dim % 32:
+        raise ValueError(f"kv_cache='mx8' needs head_dim % 32 == 0, got {cfg.head_dim}")
+    if mx8_attention not in ("split", "online"):
+        raise ValueError(f"mx8_attention must be 'split' or 'online', got {mx8_attention!r}")
+    if mx8_attention == "online" and kv_cache != "mx8":
+        raise ValueError("mx8_attention='online' needs kv_cache='mx8' (a 16-bit cache takes the one-barrier kernel by itself)")
+
+
+class KVCache(torch.nn.Module):
+    """The KV cache of one decoder layer.  `k` / `v` hold the rows: [bs, kvl, max_seq, d], or with kv_pages the pools [kv_pages, kvl,
+    page_size, d] that `table` (int32 [bs, max_seq / page_size], the stack's, shared by all layers) addresses.  kv_cache="mx8": they hold
+    float8_e4m3fn codes and `k_exp` / `v_exp` (else None) one exponent byte per 32 elements, [..., d / 32].  `mx8`, `paged`: what it is.
+    `table`, `scratch` and `nsplit` are the stack's to set (the split count of the fused decode attention and its scratch buffer); as
+    built they are what a layer outside a stack has."""
+
+    def __init__(self, cfg, kvl: int, bs: int, device, dtype, kv_cache=None, kv_pages=None, page_size: int = 64, mx8_attention: str = "split"):
+        super().__init__()
+        check_cache_config(cfg, kv_cache, kv_pages, page_size, mx8_attention)
+        self.mx8, self.paged, self.mx8_attention = kv_cache == "mx8", kv_pages is not None, mx8_attention
+        lead = (kv_pages, kvl, page_size) if self.paged else (bs, kvl, cfg.max_seq)
+        for name in ("k", "v"):
+            rows = torch.zeros(*lead, cfg.head_dim, device=device, dtype=torch.uint8 if self.mx8 else dtype)
+            self.register_buffer(name, rows.view(F8) if self.mx8 else rows, persistent=False)
+            exps = torch.zeros(*lead, cfg.head_dim // BLOCK, device=device, dtype=torch.uint8) if self.mx8 else None
+            self.register_buffer(name + "_exp", exps, persistent=False)
+        self.table, self.scratch, self.nsplit = None, None, 1
+
+    @classmethod
+    def over(cls, k, v, k_exp=None, v_exp=None) -> "KVCache":
+        """A contiguous cache over tensors that exist: the arguments of decode.prefill_attention_torch, a paged cache's gathered twin."""
+        kv = cls.__new__(cls)
+        torch.nn.Module.__init__(kv)
+        kv.mx8, kv.paged, kv.mx8_attention = k_exp is not None, False, "split"
+        kv.k, kv.v, kv.k_exp, kv.v_exp = k, v, k_exp, v_exp
+        kv.table, kv.scratch, kv.nsplit = None, None, 1
+        return kv
+
+    def tensors(self) -> list:
+        """The two or four tensors it holds, float8 codes as their bytes (indexing and copies are not implemented for that dtype everywhere)."""
+        return [t.view(torch.uint8) if t.dtype == F8 else t for t in (self.k, self.v, self.k_exp, self.v_exp) if t is not None]
+
+    # ---- plain torch (the formulation the kernels are tested against; also the CPU path) ----
+    def write(self, put, k_rows, v_rows) -> None:
+        """New rows into a contiguous cache: `put(tensor, rows)` is the caller's addressing.  An mx8 cache: the rows are encoded, and `put`
+        places the codes (as bytes) and the exponent bytes."""
+        if not self.mx8:
+            put(self.k, k_rows)
+            put(self.v, v_rows)
+            return
+        for cache, exps, rows in ((self.k, self.k_exp, k_rows), (self.v, self.v_exp, v_rows)):
+            codes, e = mx8_encode(rows)
+            put(cache.view(torch.uint8), codes.view(torch.uint8))
+            put(exps, e)
+
+    def read(self, dtype, S=None):
+        """(K, V) [bs, kvl, S, d] (default: every position) of a contiguous cache in `dtype`: mx8_decode of an mx8 cache."""
+        if not self.mx8:
+            return self.k[:, :, :S], self.v[:, :, :S]
+        return mx8_decode(self.k[:, :, :S], self.k_exp[:, :, :S], dtype), mx8_decode(self.v[:, :, :S], self.v_exp[:, :, :S], dtype)
+
+    def gathered(self):
+        """The plain-torch twin of a paged cache (what the paged kernels are tested against, not a product): (cache, put) -- `cache` a
+        contiguous KVCache [bs, kvl, max_seq, d] over copies gathered through the table, with entries outside the pool clamped to page 0
+        as the kernels clamp them, so that the contiguous formulation runs unchanged (mx8 pools: codes AND exponent bytes);
+        `put(slots, positions)` (two int64 tensors of one length) copies those rows of `cache` back into the pools, dropping a row whose
+        own table entry is outside the pool.  A contiguous cache: (itself, None)."""
+        if not self.paged:
+            return self, None
+        n, kvl, ps, _ = self.k.shape
+        tab = self.table.long()
+        valid = (tab >= 0) & (tab < n)
+        idx = torch.where(valid, tab, torch.zeros_like(tab))
+        held = [t for t in (self.k, self.v, self.k_exp, self.v_exp) if t is not None]
+        pools = self.tensors()
+        views = [pool[idx].permute(0, 2, 1, 3, 4).reshape(tab.shape[0], kvl, tab.shape[1] * ps, pool.shape[3]) for pool in pools]
+
+        def put(slots, positions):
+            ok = valid[slots, positions // ps]
+            slots, positions = slots[ok], positions[ok]
+            pages = tab[slots, positions // ps]
+            for pool, view in zip(pools, views):
+                pool[pages, :, positions % ps] = view[slots, :, positions]
+
+        return KVCache.over(*[view.view(t.dtype) for view, t in zip(views, held)]), put
+
+    # ---- fused: the one attention launch that goes with this cache (any4_amd/decode_ops.py) ----
+    def decode_attention(self, qkv, pos, cos_tab, sin_tab, hl: int, per_sequence: bool = False):
+        """One token per sequence at `pos` [1] (per_sequence: `pos` [bs], the _seq entry points): split over the sequence when the
+        stack gave a scratch buffer, else the latency kernel (head_dim 64 / 128), else the general one.  An mx8 cache always takes an
+        entry point with a scratch buffer (also at a split count of 1): the 256-thread split kernel's, or with mx8_attention="online"
+        the one-barrier kernel's.  Pools behind the block table take the _paged entry points; mx8 pools the one _mx8_paged entry point
+        (the one-barrier kernel, whatever mx8_attention names, with the stack's split count and scratch)."""
+        k, v = self.k, self.v
+        _, kvl, _, d = k.shape
+        if self.paged and not per_sequence:
+            raise RuntimeError("a paged KV cache has a position per sequence")
+        if self.mx8 and self.scratch is None:  # (a layer built outside a stack; a stack sets the buffer when it is built)
+            self.scratch = G.rope_attn_split_scratch((self.table if self.paged else k).shape[0], hl, d, self.nsplit, qkv.device)
+        split = None if self.scratch is None else (self.scratch, self.nsplit)
+        exps = (self.k_exp, self.v_exp) if self.mx8 else ()
+        if self.mx8 and not self.paged and self.mx8_attention == "online":
+            # (by its public name, the only launch made that way: tests/test_gpu_kv8_online.py counts the steps that go through it)
+            return G.rope_attn_online_mx8(qkv, cos_tab, sin_tab, pos, k, v, *exps, hl, kvl, d, 1.0 / math.sqrt(d), *split,
+                                          per_sequence=per_sequence)
+        if (self.mx8 and self.paged) or (split is None and d in (64, 128)):
+            base = "dg_rope_attn_online"
+        else:
+            base = "dg_rope_attn" if split is None else "dg_rope_attn_split"
+        return G._rope_attn(base, qkv, cos_tab, sin_tab, pos, k, v, hl, kvl, d, 1.0 / math.sqrt(d), per_sequence, split=split, exps=exps,
+                            table=self.table)
+
+    def prefill_attention(self, qkv, pos, cos_tab, sin_tab, hl: int, T=None, lengths=None, slots=None, per_sequence: bool = False):
+        """A chunk of T tokens per sequence (row b * T + t; default T = rows / the cache's batch), token 0 at `pos` [1]: T cache rows
+        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device (dg_prefill_attn_seq); the context rows of tokens
+        that do not exist are zero."""
+        k, v = self.k, self.v
+        _, kvl, _, d = k.shape
+        if self.paged and (not per_sequence or T is None):
+            raise RuntimeError("a paged KV cache has a position per sequence")
+        T = qkv.shape[0] // k.shape[0] if T is None else T
+        out = qkv.new_zeros(qkv.shape[0], hl * d) if per_sequence else None
+        return G.prefill_attn(qkv, cos_tab, sin_tab, pos, k, v, hl, kvl, d, 1.0 / math.sqrt(d), T, out=out, lengths=lengths, slots=slots,
+                              per_sequence=per_sequence, k_exp=self.k_exp, v_exp=self.v_exp, table=self.table)
 
 
 class PagePool:
