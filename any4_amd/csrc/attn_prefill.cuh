@@ -30,11 +30,11 @@
 // with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
 //
 // PAGED (dg_prefill_attn_paged, dg_prefill_attn_mx8_paged; implies SEQ): the caches are pools [num_pages][kvl][page_size][D] behind a block table
-// (kv_paged.cuh) whose row is slot[i]'s.  A 64-position tile lies in one page (page_size >= 64), so the staging pass takes the tile's base
-// from its page -- one scalar table read per tile, made when the tile's loads are issued, i.e. one tile ahead of its use -- and the rows
-// stay tile-relative; the append drops a row whose own table entry is outside the pool.  Everything else is the SEQ flavour's.
-// With KV8 the four pools (codes [num_pages][kvl][page_size][D] bytes, exponents [...][D / 32] bytes) sit behind the one table: the same
-// page, the code base kv_page_base(..., D) and the exponent base kv_page_base(..., D / 32), both in bytes.
+// (kv_paged.cuh) whose row is slot[i]'s.  A 64-position tile lies in one page (page_size >= 64), so the staging pass takes the tile's
+// first row from its page (kv_unit_row) -- one scalar table read per tile, made when the tile's loads are issued, i.e. one tile ahead of
+// its use -- and the rows stay tile-relative; the append drops a row whose own table entry is outside the pool.  Everything else is the
+// SEQ flavour's.  With KV8 the four pools (codes [num_pages][kvl][page_size][D] bytes, exponents [...][D / 32] bytes) sit behind the one
+// table: the same row, times D for the codes and times D / 32 for the exponents.
 #pragma once
 #include "stage_math.cuh"  // rope_mul_add: two rounded products, a rounded sum (contraction off)
 #include "kv8.cuh"         // the mx8 cache format (KV8 flavours)
@@ -106,14 +106,20 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
   if (pos < 0 || pos >= P.max_seq) return;  // never index the cache (or the tables) outside [0, max_seq)
   const uint16_t* row = P.qkv + ((int64_t)b * P.T + t) * (int64_t)(P.hl + 2 * P.kvl) * d;
   const int per = P.kvl * d2;
+  // The destination row of kv head `kv` among the rows of the cache (PAGED: of the pool).  PAGED: (block-uniform) the row's own page is
+  // looked up once; an entry outside the pool: nothing is written, neither rows, nor codes, nor exponents
+  [[maybe_unused]] int page = 0;
+  if constexpr (PAGED) {
+    page = kv_page_write(G, cb, (int)pos);
+    if (page < 0) return;
+  }
+  auto dst_row = [&](int kv) -> int64_t {
+    if constexpr (PAGED) return kv_page_row(G, page, P.kvl, kv, (int)pos);
+    else return kv_head_row(cb, P.kvl, kv, P.max_seq) + pos;
+  };
   if constexpr (KV8) {
     // d / 2 is a multiple of 32 and 2 * per of 64: the waves of the loop are whole, and 32 aligned lanes hold the elements j of ONE 32-element
     // block and their rotation partners j + d / 2 of another -- a block maximum is a reduction over those lanes
-    [[maybe_unused]] int page8 = 0;
-    if constexpr (PAGED) {  // (block-uniform) the row's own page, looked up once; an entry outside the pool: neither codes nor exponents are written
-      page8 = kv_page_write(G, cb, (int)pos);
-      if (page8 < 0) return;
-    }
     for (int i = threadIdx.x; i < 2 * per; i += 256) {
       const bool isv = i >= per;
       const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
@@ -128,9 +134,7 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
       uint32_t c1, e1, c2, e2;
       mx8_encode_lane(x1, c1, e1);
       mx8_encode_lane(x2, c2, e2);
-      int64_t r;  // the row among the rows of the cache (PAGED: of the pool)
-      if constexpr (PAGED) r = kv_page_base(G, page8, P.kvl, kv, 1) + (pos & ((1 << G.page_shift) - 1));
-      else r = ((int64_t)cb * P.kvl + kv) * P.max_seq + pos;
+      const int64_t r = dst_row(kv);
       uint8_t* dst = reinterpret_cast<uint8_t*>(isv ? P.v_cache : P.k_cache) + r * d;
       dst[j] = (uint8_t)c1;
       dst[j + d2] = (uint8_t)c2;
@@ -143,18 +147,11 @@ __global__ void __launch_bounds__(256) prefill_rope_kv_kernel(PrefillParams P, i
     return;
   }
   // (16-bit caches from here on)
-  [[maybe_unused]] int page = 0;
-  if constexpr (PAGED) {  // (block-uniform) the row's own page; an entry outside the pool: nothing is written
-    page = kv_page_write(G, cb, (int)pos);
-    if (page < 0) return;
-  }
   for (int i = threadIdx.x; i < 2 * per; i += 256) {
     const bool isv = i >= per;
     const int kv = (isv ? i - per : i) / d2, j = (isv ? i - per : i) % d2;
     const uint16_t* src = row + (int64_t)(P.hl + (isv ? P.kvl : 0) + kv) * d;
-    uint16_t* dst;
-    if constexpr (PAGED) dst = (isv ? P.v_cache : P.k_cache) + kv_page_base(G, page, P.kvl, kv, d) + (pos & ((1 << G.page_shift) - 1)) * d;
-    else dst = (isv ? P.v_cache : P.k_cache) + (((int64_t)cb * P.kvl + kv) * P.max_seq + pos) * d;
+    uint16_t* dst = (isv ? P.v_cache : P.k_cache) + dst_row(kv) * d;
     if (isv) {
       dst[j] = src[j];
       dst[j + d2] = src[j + d2];
@@ -260,10 +257,11 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
     }
   }
 
-  // (PAGED: the pools' first byte; stage_load adds the tile's page)
-  const char* Kg = reinterpret_cast<const char*>(P.k_cache + (PAGED ? (int64_t)0 : ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D));
-  const char* Vg = reinterpret_cast<const char*>(P.v_cache + (PAGED ? (int64_t)0 : ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq * D));
-  const int64_t head0 = ((int64_t)cb * P.kvl + kv) * (int64_t)P.max_seq;  // (KV8) first cache row of this (slot, kv head): D bytes of codes per row
+  // one base per cache or pool: the first byte of this (slot, kv head)'s rows; PAGED: the pool's, and stage_load adds the tile's
+  constexpr int RB = KV8 ? D : D * 2;  // bytes of a row
+  const int64_t head0 = PAGED ? (int64_t)0 : kv_head_row(cb, P.kvl, kv, P.max_seq);
+  const char* Kg = reinterpret_cast<const char*>(P.k_cache) + head0 * RB;
+  const char* Vg = reinterpret_cast<const char*>(P.v_cache) + head0 * RB;
 
   // ---- staging: K as 16-byte chunks (row, chunk); V as four consecutive positions 4 sg ... 4 sg + 3 of one 8-column chunk c
   // (KV8: a chunk is 8 bytes of codes in the first two dwords of its register slot, and its block's exponent byte is byte i of kexp / vexp)
@@ -273,30 +271,27 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
   const int vc = tid % CPR, vsg = tid / CPR;  // (D = 64: the threads with vsg >= 16 stage no V)
   auto stage_load = [&](int j) {
     const int s0 = 64 * j;
+    // The tile's rows are rows r0, r0 + 1, ... of a unit of rows whose first row is row u behind the bases: the head's rows from s0 on;
+    // PAGED: the tile itself, u its first row among the rows of the pool (s0 <= p_hi < max_seq; workgroup-uniform, one table read per
+    // tile, made one tile ahead of its use) -- a 64-bit scalar, so that the rows stay 32-bit offsets
+    int64_t u = 0;
+    int r0 = s0;
+    if constexpr (PAGED) {
+      u = kv_unit_row(G, cb, P.kvl, kv, s0);
+      r0 = 0;
+    }
+    const int64_t ub = u * RB;  // (added LAST: what stands in front of it does not change from tile to tile)
+    using Off = std::conditional_t<PAGED, int, int64_t>;  // (the head's rows need 64-bit offsets, a tile's own rows do not)
     if constexpr (KV8) {
-      const char* Kg8 = reinterpret_cast<const char*>(P.k_cache) + head0 * D;
-      const char* Vg8 = reinterpret_cast<const char*>(P.v_cache) + head0 * D;
-      const uint8_t* Ke = X.k_exp + head0 * (D / 32);
-      const uint8_t* Ve = X.v_exp + head0 * (D / 32);
+      const uint8_t *Ke = X.k_exp + (head0 + u) * (D / 32), *Ve = X.v_exp + (head0 + u) * (D / 32);
       kexp = vexp = 0u;  // (rows beyond p_hi: codes 0 with any exponent below 255 are the zero bits of the 16-bit flavour)
-      // PAGED: first row of the tile among the rows of (the tile's page, this kv head) of a pool -- s0 <= p_hi < max_seq; workgroup-uniform,
-      // one table read per tile, made one tile ahead of its use.  A page holds at least 64 rows, so the code base (row * D bytes) and the
-      // exponent base (row * D / 32 bytes) of a (page, kv head) are multiples of 16 bytes for D = 64 and 128.
-      [[maybe_unused]] int64_t t0 = 0;
-      if constexpr (PAGED)
-        t0 = kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, cb, s0)), P.kvl, kv, 1) + (s0 & ((1 << G.page_shift) - 1));
 #pragma unroll
       for (int i = 0; i < NCK; ++i) {
         const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
         kreg8[i] = u32x2{0u, 0u};
         if (s0 + row <= p_hi) {
-          if constexpr (PAGED) {
-            kreg8[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(P.k_cache) + t0 * D + row * D + ch * 8);
-            kexp |= (uint32_t)X.k_exp[t0 * (D / 32) + row * (D / 32) + (ch >> 2)] << (8 * i);
-          } else {
-            kreg8[i] = *reinterpret_cast<const u32x2*>(Kg8 + (int64_t)(s0 + row) * D + ch * 8);
-            kexp |= (uint32_t)Ke[(int64_t)(s0 + row) * (D / 32) + (ch >> 2)] << (8 * i);
-          }
+          kreg8[i] = *reinterpret_cast<const u32x2*>(Kg + (Off)(r0 + row) * D + ch * 8 + ub);
+          kexp |= (uint32_t)Ke[(Off)(r0 + row) * (D / 32) + (ch >> 2)] << (8 * i);
         }
       }
       if (vsg < 16) {
@@ -305,33 +300,24 @@ __global__ void __launch_bounds__(256) prefill_attn_kernel(PrefillParams P, Pref
           const int row = 4 * vsg + i;
           vreg8[i] = u32x2{0u, 0u};
           if (s0 + row <= p_hi) {
-            if constexpr (PAGED) {
-              vreg8[i] = *reinterpret_cast<const u32x2*>(reinterpret_cast<const char*>(P.v_cache) + t0 * D + row * D + vc * 8);
-              vexp |= (uint32_t)X.v_exp[t0 * (D / 32) + row * (D / 32) + (vc >> 2)] << (8 * i);
-            } else {
-              vreg8[i] = *reinterpret_cast<const u32x2*>(Vg8 + (int64_t)(s0 + row) * D + vc * 8);
-              vexp |= (uint32_t)Ve[(int64_t)(s0 + row) * (D / 32) + (vc >> 2)] << (8 * i);
-            }
+            vreg8[i] = *reinterpret_cast<const u32x2*>(Vg + (Off)(r0 + row) * D + vc * 8 + ub);
+            vexp |= (uint32_t)Ve[(Off)(r0 + row) * (D / 32) + (vc >> 2)] << (8 * i);
           }
         }
       }
     } else {
-      // first byte of the tile's row 0 behind Kg / Vg (PAGED: in the tile's page, s0 <= p_hi < max_seq; workgroup-uniform)
-      [[maybe_unused]] int64_t t0 = 0;
-      if constexpr (PAGED)
-        t0 = (kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, cb, s0)), P.kvl, kv, D) + (int64_t)(s0 & ((1 << G.page_shift) - 1)) * D) * 2;
 #pragma unroll
       for (int i = 0; i < NCK; ++i) {
         const int q = tid + 256 * i, row = q / CPR, ch = q % CPR;
         kreg[i] = u32x4{0u, 0u, 0u, 0u};
-        if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(PAGED ? Kg + t0 + row * (D * 2) + ch * 16 : Kg + (int64_t)(s0 + row) * (D * 2) + ch * 16);
+        if (s0 + row <= p_hi) kreg[i] = *reinterpret_cast<const u32x4*>(Kg + (Off)(r0 + row) * (D * 2) + ch * 16 + ub);
       }
       if (vsg < 16) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int row = 4 * vsg + i;
           vreg[i] = u32x4{0u, 0u, 0u, 0u};
-          if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(PAGED ? Vg + t0 + row * (D * 2) + vc * 16 : Vg + (int64_t)(s0 + row) * (D * 2) + vc * 16);
+          if (s0 + row <= p_hi) vreg[i] = *reinterpret_cast<const u32x4*>(Vg + (Off)(r0 + row) * (D * 2) + vc * 16 + ub);
         }
       }
     }

@@ -211,7 +211,7 @@ __global__ void rope_kv_kernel(const uint16_t* __restrict__ qkv, const float* __
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check): never index the cache outside [0, max_seq)
   const uint16_t* src = qkv + ((int64_t)b * (hl + 2 * kvl) + head) * d;
   if (head >= hl + kvl) {  // v: plain copy into the cache
-    uint16_t* dst = v_cache + (((int64_t)b * kvl + (head - hl - kvl)) * max_seq + pos) * d;
+    uint16_t* dst = v_cache + (kv_head_row(b, kvl, head - hl - kvl, max_seq) + pos) * d;
     dst[j] = src[j];
     dst[j + d2] = src[j + d2];
     return;
@@ -222,7 +222,7 @@ __global__ void rope_kv_kernel(const uint16_t* __restrict__ qkv, const float* __
   const float o1 = rope_mul_add(x1, c1, -x2, s1);
   const float o2 = rope_mul_add(x2, c2, x1, s2);
   uint16_t* dst = head < hl ? q_out + ((int64_t)b * hl + head) * d
-                            : k_cache + (((int64_t)b * kvl + (head - hl)) * max_seq + pos) * d;
+                            : k_cache + (kv_head_row(b, kvl, head - hl, max_seq) + pos) * d;
   dst[j] = DT::from_f32(o1);
   dst[j + d2] = DT::from_f32(o2);
 }
@@ -242,8 +242,8 @@ __global__ void __launch_bounds__(256) decode_attn_kernel(const uint16_t* __rest
   const int S = (int)(*pos_p) + 1, d8 = d >> 3;
   if (t < d) qf[t] = DT::to_f32(q[((int64_t)b * hl + h) * d + t]);
   __syncthreads();
-  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + ((int64_t)b * kvl + kv) * max_seq * d);
-  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + ((int64_t)b * kvl + kv) * max_seq * d);
+  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + kv_head_row(b, kvl, kv, max_seq) * d);
+  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + kv_head_row(b, kvl, kv, max_seq) * d);
   float mx = -INFINITY;
   for (int s = t; s < S; s += 256) {
     const float acc = qk_dot<DT>(qf, K + (int64_t)s * d8, d8);
@@ -301,13 +301,13 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check): never index the cache outside [0, max_seq)
   const int S = (int)pos + 1, d8 = d >> 3, d2 = d >> 1;
   const uint16_t* row = qkv + (int64_t)b * (hl + 2 * kvl) * d;
-  uint16_t* kdst = k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
-  uint16_t* vdst = v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
+  uint16_t* kdst = k_cache + (kv_head_row(b, kvl, kv, max_seq) + pos) * d;
+  uint16_t* vdst = v_cache + (kv_head_row(b, kvl, kv, max_seq) + pos) * d;
   // Issue every cache read this thread will need first -- its key row and the first eight value vectors of its
   // partition -- so that the HBM round trips of qkv / K / V overlap instead of following each other (the KV cache of a
   // layer is cold: ~4 GB of weights have streamed through the caches since the previous token).
-  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + ((int64_t)b * kvl + kv) * max_seq * d);
-  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + ((int64_t)b * kvl + kv) * max_seq * d);
+  const u32x4* K = reinterpret_cast<const u32x4*>(k_cache + kv_head_row(b, kvl, kv, max_seq) * d);
+  const u32x4* V = reinterpret_cast<const u32x4*>(v_cache + kv_head_row(b, kvl, kv, max_seq) * d);
   const int vc = t % d8, part = t / d8, nparts = 256 / d8;
   const bool kpre = d8 <= 16 && t < S - 1;
   u32x4 kreg[16], vpre[8];
@@ -444,15 +444,15 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
     vn[t] = DT::to_f32(vraw);
     if constexpr (!KV8) {
       if (owner) {
-        uint16_t* kdst = k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
-        uint16_t* vdst = v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * d;
+        uint16_t* kdst = k_cache + (kv_head_row(b, kvl, kv, max_seq) + pos) * d;
+        uint16_t* vdst = v_cache + (kv_head_row(b, kvl, kv, max_seq) + pos) * d;
         if (isk) { kdst[j] = o1; kdst[j + d2] = o2; }
         vdst[t] = vraw;
       }
     }
   }
   __syncthreads();
-  const int64_t head0 = ((int64_t)b * kvl + kv) * max_seq;  // first cache row of this (sequence, kv head)
+  const int64_t head0 = kv_head_row(b, kvl, kv, max_seq);  // first cache row of this (sequence, kv head)
   if constexpr (KV8) {
     if (owner) {  // (block-uniform) thread t encodes element t of both rows; a 32-element block is 32 aligned lanes
       const bool in = t < d;
@@ -555,24 +555,20 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 //                as dg_rope_attn_split: the same result within 16-bit rounding); the 32 (64) groups meet ONCE in LDS.
 //   RoPE         rotate_half pairs (j, j + d/2) sit d/16 lanes apart in the row: one lane exchange per value; the same products
 //                and roundings as rope_kv_kernel (the cache rows written are bit-identical to it).
-// PAGED (the dg_rope_attn_*_paged entry points; implies SEQ): k_cache / v_cache are pools [num_pages][kvl][page_size][D] behind the block
-// table G (kv_paged.cuh).  An RPI-row iteration lies in one page (page_size >= 64 >= RPI), so only its base changes: the page id is a
-// scalar read, the rows are page-relative.  The table entries of the speculative iterations do not depend on the position: they are
-// requested beside pos[b], in front of the speculative K / V requests.  Rows past the end re-read the iteration's own first row (the
-// contiguous flavours re-read position 0, which may sit in another page); they are masked either way, so every sum is the SEQ flavour's.
-// The paging argument is the kernel's last parameter and exists only for PAGED (PG = KvPages): this kernel reads gridDim from the implicit
-// arguments BEHIND the explicit ones, and even an empty trailing struct moves those by eight bytes -- the contiguous flavours would keep
-// their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
-// KV8 (the dg_rope_attn_online_mx8 entry points; PG = Kv8Exps, the same optional last parameter): the caches are mx8
-// (kv8.cuh).  Same lanes, same partition of work: a lane's K / V piece is 8 code bytes and one exponent byte, requested where the
-// 16-byte pieces are (the speculative ones in front of `pos`), clamped and masked alike, and converted to the 16-bit type on use --
-// behind the conversion every sum and rounding point is the 16-bit flavour's.  The new token's roped k row and raw v row are encoded
-// from the registers they are in (mx8_encode_piece: the host encoder's bytes) and enter the scores and the value sum DECODED.
-// PAGED with KV8 (dg_rope_attn_online_mx8_paged; PG = KvPages, Kv8Exps): four pools behind the one table -- codes [num_pages][kvl][page_size][D]
-// bytes, exponents [...][D / 32] bytes.  The page lookup is PAGED's (one scalar table read per iteration, page-relative rows, rows past the
-// end re-read the iteration's own first row, the speculative iterations' entries beside pos[b]); the piece, its conversion on use, the
-// NaN mark and the combine are KV8's; the new token's codes and exponent bytes are written only where its own table entry is in the pool.
-// Partition of work, order of every sum, masks and rounding points are the contiguous <SEQ, Kv8Exps> flavour's.
+// The cache is addressed in one place, `fetch`: a lane asks for its piece of row rc of a unit of rows (kv_paged.cuh), and two switches say
+// what those are.  Both are read off the kernel's optional LAST parameters, the pack PG (empty, KvPages, Kv8Exps, or KvPages, Kv8Exps):
+// this kernel reads gridDim from the implicit arguments BEHIND the explicit ones, and even an empty trailing struct moves those by
+// eight bytes -- the contiguous flavours would keep their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
+// PAGED (the dg_rope_attn_*_paged entry points; implies SEQ) -- where the unit starts: k_cache / v_cache (and the exponents) are pools
+// behind the block table G instead of the head's max_seq rows.  An RPI-row iteration lies in one page (page_size >= 64 >= RPI), so the
+// unit is the iteration's page: one scalar table read, the rows relative to the iteration's first.  The table entries of the speculative iterations do not depend
+// on the position: they are requested beside pos[b], in front of the speculative K / V requests.  Rows past the end re-read the
+// iteration's own first row (the contiguous flavours re-read position 0, which may sit in another page); they are masked either way, so
+// every sum is the SEQ flavour's.  The new token's row is written only where its own table entry is in the pool.
+// KV8 (the dg_rope_attn_online_mx8* entry points) -- what a piece is: the caches are mx8 (kv8.cuh), a lane's K / V piece 8 code bytes and
+// one exponent byte instead of 16 bytes, requested where the 16-byte pieces are, clamped and masked alike, and converted to the 16-bit
+// type on use -- behind the conversion every sum and rounding point is the 16-bit flavour's.  The new token's roped k row and raw v row
+// are encoded from the registers they are in (mx8_encode_piece: the host encoder's bytes) and enter the scores and the value sum DECODED.
 template <typename DT, int LPR, bool SEQ = false, bool PAGED = false, typename... PG>
 __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* __restrict__ qkv, const float* __restrict__ cos,
                                                                const float* __restrict__ sin, const int64_t* __restrict__ pos_p,
@@ -607,39 +603,42 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const int h = (kvl == 8 && hl == 8 * rep) ? rep * (hb & 7) + (hb >> 3) : hb;
   const int kv = h / rep;
   const uint16_t* row = qkv + (int64_t)b * (hl + 2 * kvl) * D;
-  // (row r, piece i) of this head's K / V at byte ((r * LPR + i) << 4): a 32-bit offset on a scalar base (host: max_seq * d * 2 < 4 GiB)
-  // (PAGED: the pools' first byte; an iteration adds its page's base, page_bytes)
-  const char* K = reinterpret_cast<const char*>(k_cache + (PAGED ? (int64_t)0 : ((int64_t)b * kvl + kv) * max_seq * D));
-  const char* V = reinterpret_cast<const char*>(v_cache + (PAGED ? (int64_t)0 : ((int64_t)b * kvl + kv) * max_seq * D));
+  // A lane's part of a cache row: 16 bytes, or (KV8) 8 code bytes and the exponent byte of their 32-element block.  Of row rc of a unit
+  // of rows (kv_paged.cuh) it is the piece at byte ((rc * LPR + i) << 4, KV8: 3) and the exponent byte rc * (D / 32) + (i >> 2) (a wave's
+  // exponent bytes of one iteration: 16 contiguous bytes): 32-bit offsets on a scalar base (host: max_seq * d * 2 < 4 GiB).
+  using Piece = std::conditional_t<KV8, u32x2, u32x4>;
+  constexpr int RB = KV8 ? D : D * 2;  // bytes of a row
+  const int64_t head0 = kv_head_row(b, kvl, kv, max_seq);  // contiguous: first cache row of this (sequence, kv head)
+  // one base per cache or pool: the head's first byte (the unit is the head's rows); PAGED: the pool's, and `fetch` adds the unit's
+  const char* Kp = reinterpret_cast<const char*>(k_cache) + (PAGED ? (int64_t)0 : head0 * RB);
+  const char* Vp = reinterpret_cast<const char*>(v_cache) + (PAGED ? (int64_t)0 : head0 * RB);
   [[maybe_unused]] int64_t pos_early = 0;
   [[maybe_unused]] int in_page = 0;  // PAGED: page_size - 1
   if constexpr (PAGED) {
     pos_early = pos_p[DG_SEQ_INDEX(b)];
     in_page = (1 << G.page_shift) - 1;
   }
-  // PAGED: byte offset of (the page of logical row r0 < max_seq, this kv head) in a pool -- wave-uniform
-  [[maybe_unused]] auto page_bytes = [&](int r0) -> int64_t {
-    if constexpr (PAGED) return kv_page_base(G, __builtin_amdgcn_readfirstlane(kv_page_read(G, b, r0)), kvl, kv, D) * 2;
-    else return 0;
+  [[maybe_unused]] const uint8_t* Ke = KV8 ? X.k_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
+  [[maybe_unused]] const uint8_t* Ve = KV8 ? X.v_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
+  Piece kk[NI], vv[NI];
+  [[maybe_unused]] uint32_t ke[KV8 ? NI : 1], ve[KV8 ? NI : 1];  // KV8: the exponent byte of each piece
+  // Request iteration `it`'s pieces: row rc of the head's rows.  PAGED: row rc of the iteration's own rows, which start at logical row
+  // r0 < max_seq; the unit is r0's page (one wave-uniform table read; a page holds whole iterations, page_size >= 64 >= RPI), so that
+  // only the page's first row is 64-bit arithmetic and the row within it stays in the 32-bit offset (in the 64-bit base it cost the
+  // d = 64 flavour 8 VGPRs and a wave of occupancy).  The offset stands in front of the table read, so that it is computed under it.
+  auto fetch = [&](int it, [[maybe_unused]] int r0, int rc) {
+    if constexpr (PAGED) rc += r0 & in_page;
+    const uint32_t o = ((uint32_t)rc * LPR + (uint32_t)i) << (KV8 ? 3 : 4);
+    int64_t u = 0;  // the unit's first row behind the bases
+    if constexpr (PAGED) u = kv_unit_page_row(G, b, kvl, kv, r0);
+    kk[it] = *reinterpret_cast<const Piece*>(Kp + u * RB + o);
+    vv[it] = *reinterpret_cast<const Piece*>(Vp + u * RB + o);
+    if constexpr (KV8) {
+      const uint32_t eo = (uint32_t)rc * (D / 32) + ((uint32_t)i >> 2);
+      ke[it] = (Ke + u * (D / 32))[eo];
+      ve[it] = (Ve + u * (D / 32))[eo];
+    }
   };
-  auto piece = [&](const char* base, int r) -> u32x4 { return *reinterpret_cast<const u32x4*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 4)); };
-  // KV8: the head's rows are D code bytes and D / 32 exponent bytes each -- (row r, piece i) is the 8 bytes at ((r * LPR + i) << 3) and
-  // byte r * (D / 32) + (i >> 2) of the exponents (a wave's exponent bytes of one iteration: 16 contiguous bytes)
-  [[maybe_unused]] const int64_t head0 = ((int64_t)b * kvl + kv) * max_seq;  // first cache row of this (sequence, kv head)
-  [[maybe_unused]] const char* K8 = reinterpret_cast<const char*>(k_cache) + head0 * D;
-  [[maybe_unused]] const char* V8 = reinterpret_cast<const char*>(v_cache) + head0 * D;
-  // (PAGED: the exponent pools' first byte; an iteration adds its page's base)
-  [[maybe_unused]] const uint8_t* KE = KV8 ? X.k_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
-  [[maybe_unused]] const uint8_t* VE = KV8 ? X.v_exp + (PAGED ? (int64_t)0 : head0 * (D / 32)) : nullptr;
-  // PAGED with KV8: the page of logical row r0 < max_seq (wave-uniform).  A code row is D bytes and an exponent row D / 32 bytes, so the
-  // byte bases of (page, this kv head) are kv_page_base(..., D) in K / V and kv_page_base(..., D / 32) in KE / VE; a page holds at least
-  // 64 rows, so both are multiples of 16 bytes for D = 64 and 128 and the 8-byte pieces stay aligned.
-  [[maybe_unused]] auto page_of = [&](int r0) -> int {
-    if constexpr (PAGED) return __builtin_amdgcn_readfirstlane(kv_page_read(G, b, r0));
-    else return 0;
-  };
-  [[maybe_unused]] auto piece8 = [&](const char* base, int r) -> u32x2 { return *reinterpret_cast<const u32x2*>(base + (((uint32_t)r * LPR + (uint32_t)i) << 3)); };
-  [[maybe_unused]] auto pexp = [&](const uint8_t* base, int r) -> uint32_t { return base[(uint32_t)r * (D / 32) + ((uint32_t)i >> 2)]; };
   // the first NSPEC iterations' rows are requested BEFORE the position is known (rows past it are valid memory and masked later):
   // the read of `pos` is a dependent round trip the K / V requests of a short context need not wait for
   // (all of the first chunk: same box, Llama-3-8B decode, 2 -> 8 iterations: 620 -> 620 tokens/s at position 136, 544 -> 553 at 900,
@@ -649,33 +648,10 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
 #define DG_ATTN_NSPEC 8
 #endif
   constexpr int NSPEC = NI < DG_ATTN_NSPEC ? NI : DG_ATTN_NSPEC;
-  std::conditional_t<KV8, u32x2, u32x4> kk[NI], vv[NI];
-  [[maybe_unused]] uint32_t ke[KV8 ? NI : 1], ve[KV8 ? NI : 1];  // KV8: the exponent byte of each piece
 #pragma unroll
-  for (int it = 0; it < NSPEC; ++it) {
-    if constexpr (PAGED && KV8) {  // (PAGED's rows, KV8's pieces)
-      const int r0 = min(row0_of(it), (int)max_seq - RPI);
-      const int pg = page_of(r0), rc = (r0 & in_page) + grp;
-      kk[it] = piece8(K + kv_page_base(G, pg, kvl, kv, D), rc);
-      vv[it] = piece8(V + kv_page_base(G, pg, kvl, kv, D), rc);
-      ke[it] = pexp(KE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
-      ve[it] = pexp(VE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
-    } else if constexpr (PAGED) {  // (an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
-      const int r0 = min(row0_of(it), (int)max_seq - RPI);
-      const int64_t pb = page_bytes(r0);
-      kk[it] = piece(K + pb, (r0 & in_page) + grp);
-      vv[it] = piece(V + pb, (r0 & in_page) + grp);
-    } else if constexpr (KV8) {
-      const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
-      kk[it] = piece8(K8, rc);
-      vv[it] = piece8(V8, rc);
-      ke[it] = pexp(KE, rc);
-      ve[it] = pexp(VE, rc);
-    } else {
-      const int rc = min(row0_of(it) + grp, (int)max_seq - 1);
-      kk[it] = piece(K, rc);
-      vv[it] = piece(V, rc);
-    }
+  for (int it = 0; it < NSPEC; ++it) {  // (PAGED: an iteration past the cache re-reads the last one: max_seq is whole pages, a page whole iterations)
+    const int r0 = min(row0_of(it), (int)max_seq - RPI);
+    fetch(it, r0, PAGED ? grp : min(row0_of(it) + grp, (int)max_seq - 1));
   }
   const int64_t pos = PAGED ? pos_early : SEQ ? pos_p[DG_SEQ_INDEX(b)] : *pos_p;
   if (pos < 0 || pos >= max_seq) return;  // the position lives on the device (graph replays bypass the host check)
@@ -691,31 +667,8 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
 #pragma unroll
     for (int it = 0; it < NI; ++it) {
       if (it < first || row0_of(base / RPI + it) >= S) continue;  // (wave-uniform) iterations past the last position request nothing
-      const int r = row0_of(base / RPI + it) + grp;
-      if constexpr (PAGED && KV8) {  // (row0 < S <= max_seq)
-        const int r0 = row0_of(base / RPI + it);
-        const int pg = page_of(r0), rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
-        kk[it] = piece8(K + kv_page_base(G, pg, kvl, kv, D), rc);
-        vv[it] = piece8(V + kv_page_base(G, pg, kvl, kv, D), rc);
-        ke[it] = pexp(KE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
-        ve[it] = pexp(VE + kv_page_base(G, pg, kvl, kv, D / 32), rc);
-      } else if constexpr (PAGED) {  // (row0 < S <= max_seq)
-        const int r0 = row0_of(base / RPI + it);
-        const int64_t pb = page_bytes(r0);
-        const int rc = (r0 & in_page) + (r < S - 1 ? grp : 0);
-        kk[it] = piece(K + pb, rc);
-        vv[it] = piece(V + pb, rc);
-      } else if constexpr (KV8) {
-        const int rc = r < S - 1 ? r : 0;
-        kk[it] = piece8(K8, rc);
-        vv[it] = piece8(V8, rc);
-        ke[it] = pexp(KE, rc);
-        ve[it] = pexp(VE, rc);
-      } else {
-        const int rc = r < S - 1 ? r : 0;
-        kk[it] = piece(K, rc);
-        vv[it] = piece(V, rc);
-      }
+      const int r0 = row0_of(base / RPI + it), r = r0 + grp;  // (r0 < S <= max_seq)
+      fetch(it, r0, r < S - 1 ? (PAGED ? grp : r) : 0);  // (the new token's row and the rows past it: the unit's row 0 again)
     }
   };
   request(0, NSPEC);
@@ -745,47 +698,29 @@ __global__ void __launch_bounds__(512) rope_attn_online_kernel(const uint16_t* _
   const u32x4 qp = rotate(qraw);
   u32x4 kn = rotate(kraw), vn = vraw;  // the new token's rows as the scores and the value sum take them
   TG_STAMP(3);
+  [[maybe_unused]] u32x2 kc, vc;
+  [[maybe_unused]] uint32_t kE, vE;
   if constexpr (KV8) {
     // every row group holds the same row and every lane encodes it (a block is an aligned quad of lanes); from here on the new token
-    // is its DECODED row -- what every later step reads -- and only the block that writes the 16-bit rows stores the bytes
-    u32x2 kc, vc;
-    uint32_t kE, vE;
+    // is its DECODED row -- what every later step reads -- and only the row group that writes stores the bytes
     kn = mx8_encode_piece<DT>(kn, kc, kE);
     vn = mx8_encode_piece<DT>(vraw, vc, vE);
-    if (h % rep == 0 && grp == 0 && cblk == 0) {
-      if constexpr (PAGED) {  // (a position whose own table entry is outside the pool writes neither codes nor exponents)
-        const int pg = kv_page_write(G, b, (int)pos);
-        if (pg >= 0) {
-          const int64_t cb8 = kv_page_base(G, pg, kvl, kv, D) + (int64_t)((int)pos & in_page) * D;
-          const int64_t eb8 = kv_page_base(G, pg, kvl, kv, D / 32) + (int64_t)((int)pos & in_page) * (D / 32);
-          *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + cb8 + i * 8) = kc;
-          *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + cb8 + i * 8) = vc;
-          if ((i & 3) == 0) {
-            X.k_exp[eb8 + (i >> 2)] = (uint8_t)kE;
-            X.v_exp[eb8 + (i >> 2)] = (uint8_t)vE;
-          }
+  }
+  if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
+    int64_t wr = head0 + pos;  // the row among the rows of the cache; PAGED: of the pool, -1 where the position's own table entry is outside it
+    if constexpr (PAGED) wr = kv_write_row(G, b, kvl, kv, (int)pos);
+    if (!PAGED || wr >= 0) {  // (a dropped write stores nothing: neither rows, nor codes, nor exponents)
+      if constexpr (KV8) {
+        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + wr * D + i * 8) = kc;
+        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + wr * D + i * 8) = vc;
+        if ((i & 3) == 0) {
+          X.k_exp[wr * (D / 32) + (i >> 2)] = (uint8_t)kE;
+          X.v_exp[wr * (D / 32) + (i >> 2)] = (uint8_t)vE;
         }
       } else {
-        const int64_t r = head0 + pos;
-        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(k_cache) + r * D + i * 8) = kc;
-        *reinterpret_cast<u32x2*>(reinterpret_cast<char*>(v_cache) + r * D + i * 8) = vc;
-        if ((i & 3) == 0) {
-          X.k_exp[r * (D / 32) + (i >> 2)] = (uint8_t)kE;
-          X.v_exp[r * (D / 32) + (i >> 2)] = (uint8_t)vE;
-        }
+        reinterpret_cast<u32x4*>(k_cache + wr * D)[i] = kn;
+        reinterpret_cast<u32x4*>(v_cache + wr * D)[i] = vraw;
       }
-    }
-  } else if (h % rep == 0 && grp == 0 && cblk == 0) {  // one row group of the KV group's first head writes the new token's cache rows
-    if constexpr (PAGED) {  // (a position whose own table entry is outside the pool writes nothing)
-      const int pg = kv_page_write(G, b, (int)pos);
-      if (pg >= 0) {
-        const int64_t e = kv_page_base(G, pg, kvl, kv, D) + (int64_t)((int)pos & in_page) * D;
-        reinterpret_cast<u32x4*>(k_cache + e)[i] = kn;
-        reinterpret_cast<u32x4*>(v_cache + e)[i] = vraw;
-      }
-    } else {
-      reinterpret_cast<u32x4*>(k_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = kn;
-      reinterpret_cast<u32x4*>(v_cache + (((int64_t)b * kvl + kv) * max_seq + pos) * D)[i] = vraw;
     }
   }
   auto dpp_add = [](float v, auto ctrl) -> float {
@@ -1085,36 +1020,17 @@ int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counte
 #endif
   return pick_dt(c.dtype, [&](auto DT_) {
     return pick<16, 8>(c.d / 8, [&](auto LPR_) {  // (d = 128, 64)
-      if (c.paging && c.kv8) {  // (mx8 pools behind a block table: the paging argument, then the exponent pools)
-        const KvPages G = kv_pages(c);
-        const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
-        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, true, true, KvPages, Kv8Exps>),
+      // the one launch: `tail` is the flavour's optional last arguments -- none, KvPages (pools behind a block table: always a position per
+      // sequence), Kv8Exps (mx8 caches), or both in that order -- and names the kernel's pack
+      auto launch = [&](auto SEQ_, auto PAGED_, auto... tail) {
+        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value, (bool)decltype(PAGED_)::value, decltype(tail)...>),
                            dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
-                           c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, G, X);
+                           c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, tail...);
         return launch_status();
-      }
-      if (c.paging) {  // (pools behind a block table: always a position per sequence)
-        const KvPages G = kv_pages(c);
-        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, true, true, KvPages>), dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit),
-                           dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache,
-                           (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, G);
-        return launch_status();
-      }
-      if (c.kv8) {  // (mx8 caches: the exponent pointers are the flavour's last argument)
-        const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
-        return pick<0, 1>(c.seq, [&](auto SEQ_) {
-          hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value, false, Kv8Exps>),
-                             dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
-                             c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, X);
-          return launch_status();
-        });
-      }
-      return pick<0, 1>(c.seq, [&](auto SEQ_) {
-        hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value>),
-                           dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
-                           c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters);
-        return launch_status();
-      });
+      };
+      const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
+      if (c.paging) return c.kv8 ? launch(std::true_type{}, std::true_type{}, kv_pages(c), X) : launch(std::true_type{}, std::true_type{}, kv_pages(c));
+      return pick<0, 1>(c.seq, [&](auto SEQ_) { return c.kv8 ? launch(SEQ_, std::false_type{}, X) : launch(SEQ_, std::false_type{}); });
     });
   });
 }
