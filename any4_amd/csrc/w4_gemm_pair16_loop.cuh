@@ -271,6 +271,9 @@ __global__ void __launch_bounds__(1024) w4_gemm_pair16_loop_kernel(const Pair16L
 #pragma unroll
             for (int w16 = 0; w16 < 16; ++w16) up += *(lds_fptr)((uint32_t)p.lds_red + (uint32_t)(par * 16384 + ((w16 * 4 + rr) * 64 + l + 8) * 4));
             up *= rsn;
+            // (the f32 product of the plain store, then its rounding: left to hipcc, fp16 folds product and conversion into v_fma_mixlo_f16 --
+            //  one rounding instead of two -- and an up row comes out one step off the plain launch's at a near-tie)
+            if constexpr (NORM && !std::is_same<DT, BF16>::value) asm volatile("" : "+v"(up));
             *reinterpret_cast<uint16_t*>(p.y + ((int64_t)a * (p.wrows >> 1) + tile * 8 + (l & 7)) * 2) = swiglu16<DT>(sum, up);
           }
         } else {

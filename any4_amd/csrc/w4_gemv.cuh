@@ -499,6 +499,9 @@ __global__ void __launch_bounds__(512, 2) w4_gemv_kernel(const GemvParams p) {
 #pragma unroll
             for (int w8 = 0; w8 < NW; ++w8) up += *(lds_fptr)(lds_red + (uint32_t)((((par * NW + w8) * M + a) * 32 + r + 8) * 4));
             up *= rsn;
+            // (the f32 product of the plain store, then its rounding: left to hipcc, fp16 folds product and conversion into v_fma_mixlo_f16 --
+            //  one rounding instead of two -- and an up row comes out one step off the plain launch's at a near-tie)
+            if constexpr (NORM && !std::is_same<DT, BF16>::value) asm volatile("" : "+v"(up));
             *reinterpret_cast<uint16_t*>(p.y + (int64_t)b * p.stride_y + ((int64_t)a * (p.wrows >> 1) + ((row >> 4) << 3) + (row & 7)) * 2) = swiglu16<DT>(sum, up);
           }
         } else {

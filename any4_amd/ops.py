@@ -740,6 +740,8 @@ def w4_linear_fused(x, w, q_group, qinfo, lut=None, *, residual=None, norm_weigh
     reference's op surface; the decode harness (any4_amd/decode.py) calls it instead of Linear + glue kernel:
 
       norm_weight [k]        the activations pass through LlamaRMSNorm in the kernel's staging: x' = rmsnorm(x, eps) * norm_weight
+                             (w4_gemv_kernel -- up to 4 rows, up to 8 on the matrix core -- and the 16-row loop kernel multiply the f32
+                             sum of RNE16(x * norm_weight) by 1 / rms instead: include/tinygemm_hip.h, tg_w4_gemm.norm_weight)
       residual    [m][n]     y = RNE16(RNE16(acc) + residual)   (the residual stream; may be `out` itself: updated in place)
       swiglu                 the weight rows come in blocks of 8 gate + 8 up rows and y is [m][n / 2] = silu(gate) * up
       out                    where to write y (default: a new tensor)

@@ -211,9 +211,14 @@ typedef struct tg_w4_gemm {
                            /* x'[a][j] = RNE16(RNE16(x[a][j] * rsqrt(mean_j(x[a][j]^2) + norm_eps)) * norm_weight[j])               */
                            /* (dg_add_rmsnorm's formula).  TG_NUM_FAST pair-table kernels, row-major x, k % 2048 == 0, the          */
                            /* activation block staged whole on chip; otherwise TG_E_FUSION.  Launches that w4_gemv_kernel takes    */
-                           /* (m <= 4, one problem; tg_gemm_w4_plan = TG_PLAN_GEMV) apply the row's factor to the f32 sum instead:  */
+                           /* (one problem, m <= 4, or m <= 8 where it contracts on the matrix core: groups of 128 / 256, k <= 4096; */
+                           /* tg_gemm_w4_plan = TG_PLAN_GEMV) and those of w4_gemm_pair16_loop_kernel (one problem, 5 ... 16 rows,   */
+                           /* k = 4096, more 16-row tiles than CUs; reported as TG_PLAN_PAIR) apply the row's factor to the f32 sum: */
                            /* y[a][row] = RNE16(rsqrt(mean_j(x[a][j]^2) + norm_eps) * sum_j RNE16(x[a][j] * norm_weight[j]) w[row][j]) */
                            /* -- one rounding of the activation where the separate kernel has two; within 2^-8 sum|x' w| of it.     */
+                           /* Refused (TG_E_FUSION) besides the above: mx4; more than m k = 32768 activations on                    */
+                           /* w4_gemm_pair16_kernel (e.g. 9 ... 16 rows of k = 4096 with at most as many 16-row tiles as CUs);       */
+                           /* innerKTiles 8; groups of 32 on the loop kernel.  tests/fused_ref.py holds the table of carriers.       */
   float norm_eps;
   int32_t epilogue;        /* TG_EPI_NONE or TG_EPI_SWIGLU: the weight rows come in blocks of 16 = 8 "gate" rows followed by the 8  */
                            /* matching "up" rows, and y is [m][wrows / 2]:                                                         */
@@ -244,7 +249,7 @@ TG_API int tg_gemm_w4(const tg_w4_gemm* args, int device, tg_stream_t stream);
  *                                          registers by v_cvt_scalef32_pk_bf16_fp4, exact -- in both numerics)
  *   TG_PLAN_PAIR_XR w4_gemm_xr_kernel      the same tables and numerics, activations resident in registers (Bint4 weights,
  *                                          2 ... 16 activation rows, k = 4096, stacked launches)
- *   TG_PLAN_GEMV    w4_gemv_kernel         the same tables and numerics for ONE layer per launch with 1 ... 4 activation rows (a
+ *   TG_PLAN_GEMV    w4_gemv_kernel         the same tables and numerics for ONE layer per launch with 1 ... 4 (matrix core: 8) activation rows (a
  *                                          decode step's GEMMs): one workgroup per CU over a contiguous range of weight rows,
  *                                          v_dot2 contraction, fused norm / residual / SwiGLU stages
  *   TG_PLAN_TILE    w4_gemm_tile_kernel    more than 64 activation rows (Bint4 innerKTiles 4, int4 / any4): an LDS-tiled MFMA GEMM
