@@ -344,20 +344,20 @@ def test_tc_variants_match_rm(T, oracle, m):
 
 @pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
 def test_f16_weight_gemm(T, dtype):
-    """16-bit weights (reference tests/tinygemm/test_tinygemm_f16.py): identity exact, random assert_close(0.01, 0.1)."""
+    """16-bit weights (reference tests/tinygemm/test_tinygemm_f16.py): identity exact, random data within the GEMM tolerance of this file
+    (the reference's own test takes assert_close(0.01, 0.1); every loop regime of the kernel: test_gpu_w16_f64.py)."""
     import tinygemm_lib.functional as F
 
     gen = torch.Generator().manual_seed(0)
     for m, n, k in ((5, 64, 256), (16, 48, 1024), (33, 16, 64)):
         x = (torch.randn(m, k, generator=gen) * 0.1).to(dtype).to(DEV)
         w = (torch.randn(n, k, generator=gen) * 0.1).to(dtype).to(DEV)
-        y_ref = (x.double() @ w.double().t())
         outs = [F.linear_y_f16RM_x_f16RM_W_f16TC(x, w, 1), F.linear_y_f16RM_x_f16RM_W_f16TC(x, w, 2),
                 F.linear_y_f16RM_W_f16TC_x_f16RM(x, w, 1), F.linear_y_f16TC_x_f16TC_W_f16TC(x, w, 2),
                 F.linear_y_f16TC_W_f16TC_x_f16TC(x, w, 1)]
         for y in outs:
             assert y.shape == (m, n)
-            torch.testing.assert_close(y.double(), y_ref, atol=0.01, rtol=0.1)
+            assert_gemm_close(y, x, bits16(w), dtype)
     x = torch.randn(19, 256, generator=gen).to(dtype).to(DEV)
     eye = torch.eye(256, dtype=dtype, device=DEV)
     assert torch.equal(F.linear_y_f16RM_x_f16RM_W_f16TC(x, eye, 2), x)
