@@ -173,6 +173,10 @@ SYMBOLS = {
     # per_sequence, ctr_add, dtype, device, stream
     "dg_sample": [_vp] * 10 + [_i64, _i64, _i64, _i64, ctypes.c_int, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_sample_scratch_bytes": [_i64, _i64],
+    # per-sequence LoRA adapters: x, norm_weight, A, idx, t, m, k, r, n_adapters, rows_per_id, eps, dtype, device, stream
+    "dg_lora_shrink": [_vp] * 5 + [_i64] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
+    # t, B, scale, idx, y, m, n, r, ldy, n_adapters, rows_per_id, dtype, device, stream
+    "dg_lora_expand": [_vp] * 5 + [_i64] * 6 + [ctypes.c_int, ctypes.c_int, _vp],
 }
 for _base, _has_mx8 in ATTN_BASES.items():
     for _seq in (False, True):

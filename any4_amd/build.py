@@ -36,6 +36,7 @@ UNITS = [
     ("tg_dq", "tg_dq.hip", []),
     ("tg_prefill", "tg_prefill.hip", []),
     ("tg_sample", "tg_sample.hip", []),
+    ("tg_lora", "tg_lora.hip", []),
     ("tinygemm_hip", "tinygemm_hip.hip", []),
 ]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-comment", "-Wno-int-to-pointer-cast"]

@@ -17,6 +17,7 @@
 //   tg_dq.hip          w4_gemm_dq_kernel         (w4_gemm_dq.cuh)          the gradients of scales, zeros and LUT (tg_gemm_w4_dq)
 //   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
 //   tg_sample.hip      sample_kernel             (sample.cuh)              temperature / top-k / top-p sampling of the logits (dg_sample)
+//   tg_lora.hip        lora_shrink_kernel, lora_expand_kernel (lora.cuh)   per-sequence LoRA adapters on a linear's output (dg_lora_shrink / dg_lora_expand)
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.

@@ -31,6 +31,10 @@ Launch structure, chosen for the hardware rather than copied from HF:
     token's arithmetic is written once (`DecodeLayer._token_torch`) behind two addressings that are kept apart on purpose: `forward`
     (one rope row, `index_copy_`, one mask) and `forward_seq` (a row per sequence, gather / where / scatter, a mask per sequence) are
     compared bit for bit by tests/test_ragged_cpu.py, which is a check only while they are written independently;
+  * LoRA adapters, one per sequence (`DecodeStack(..., adapters=AdapterSet)`, any4_amd/lora.py): every adapted linear is followed by a
+    shrink and an expand launch that add the sequence's delta to the linear's output in place, in every schedule; which adapter a
+    sequence takes is `adapter_ids`, a static buffer the kernels read, so a captured step serves another mix at every replay.  A stack
+    built without `adapters=` has none of it;
   * tensor parallelism = row-sharding of every linear (any4_amd/shard.py): heads are split across ranks so
     attention and the KV cache stay local; per layer 4 all-gathers of [bs, n/G] partial outputs (attention
     output, o_proj, SwiGLU activation, down_proj) over RCCL.  One process per GPU.
@@ -279,7 +283,8 @@ class DecodeLayer(torch.nn.Module):
         if cfg.heads % world or cfg.kv_heads % world or cfg.inter % (16 * world) or cfg.hidden % (16 * world):
             raise ValueError(f"heads={cfg.heads}, kv_heads={cfg.kv_heads}, inter={cfg.inter}, hidden={cfg.hidden} "
                              f"must split over world_size={world} in whole heads / 16-row tiles")
-        self.cfg, self.world = cfg, world
+        self.cfg, self.world, self.idx = cfg, world, idx
+        self.adapters = None  # the stack's AdapterSet (any4_amd/lora.py), set by the stack; None: no adapted linear, nothing changes
         self.hl, self.kvl = cfg.heads // world, cfg.kv_heads // world
         d = cfg.head_dim
         self.qkv = factory("qkv", idx, cfg.hidden, (self.hl + 2 * self.kvl) * d)
@@ -293,14 +298,20 @@ class DecodeLayer(torch.nn.Module):
         # forward_fused5: which stages the library fused (None: not tried yet; set by the first step)
         self._fuse = {"norm1": None, "norm2": None, "mlp": None}
 
-    def _token_torch(self, kv, h, cos, sin, write, mask, gather):
+    def _adapted(self, lora, target, x, y, norm=None):
+        """`y` = linear `target`'s output for the input `x`, plus the rows' adapter deltas (in place) when the call has adapters (`lora`: an
+        any4_amd.lora.AdapterCall); norm: the RMSNorm the GEMM fused, when x is the un-normalised residual stream."""
+        return y if lora is None else lora.apply(self.idx, target, x, y, norm)
+
+    def _token_torch(self, kv, h, cos, sin, write, mask, gather, lora=None):
         """The plain-torch arithmetic of one token per sequence, behind either addressing (`forward`, `forward_seq`): `kv` the cache
         (a paged one's gathered twin), `cos` / `sin` the rope rows [1 | bs, 1, d], `write(cache, rows [bs, kvl, d])` puts the new k / v
         rows into a cache, `mask` [1 | bs, 1, 1, S] hides the cache rows behind each position.  Rounding points: 16-bit score matmul,
         f32 scale + softmax, 16-bit probabilities, 16-bit P.V (the formulation the fused schedules are tested against).  An mx8 cache:
         the rows are encoded on the way in and the attention reads mx8_decode of the cache, the new token's own rows included."""
         d, bs = self.cfg.head_dim, h.shape[0]
-        qkv = self.qkv(self.norm1(h))
+        xn = self.norm1(h)
+        qkv = self._adapted(lora, "qkv", xn, self.qkv(xn))
         q = _rope(qkv[:, : self.hl * d].reshape(bs, self.hl, d), cos, sin)
         k = _rope(qkv[:, self.hl * d: (self.hl + self.kvl) * d].reshape(bs, self.kvl, d), cos, sin)
         v = qkv[:, (self.hl + self.kvl) * d:].reshape(bs, self.kvl, d)
@@ -310,17 +321,17 @@ class DecodeLayer(torch.nn.Module):
         qg = q.reshape(bs, self.kvl, rep, d)
         att = torch.matmul(qg, K.transpose(2, 3)).float() * (1.0 / math.sqrt(d))  # [bs, kvl, rep, S]
         att = att.masked_fill(mask, float("-inf")).softmax(-1).to(h.dtype)
-        ctx = torch.matmul(att, V).reshape(bs, self.hl * d)
-        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+        ctx = gather(torch.matmul(att, V).reshape(bs, self.hl * d))
+        return self._mlp_torch(h + gather(self._adapted(lora, "o", ctx, self.o(ctx))), gather, lora)
 
-    def forward(self, h, pos, cos_tab, sin_tab, arange, gather):
+    def forward(self, h, pos, cos_tab, sin_tab, arange, gather, lora=None):
         """Plain torch, one token per sequence, every sequence at `pos` [1] on the device: one rope row, one cache row and one mask
         for the batch."""
         cos, sin = cos_tab.index_select(0, pos).view(1, 1, -1), sin_tab.index_select(0, pos).view(1, 1, -1)
         return self._token_torch(self.kv, h, cos, sin, lambda cache, new: cache.index_copy_(2, pos, new.unsqueeze(2)),
-                                 (arange > pos).view(1, 1, 1, -1), gather)
+                                 (arange > pos).view(1, 1, 1, -1), gather, lora)
 
-    def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather):
+    def forward_seq(self, h, pos, cos_tab, sin_tab, arange, gather, lora=None):
         """`forward` with a position per sequence: `pos` int64 [bs] on the device.  Sequence b takes rope row pos[b], writes cache row
         pos[b] and sees rows <= pos[b]; one whose position is outside [0, max_seq) is inactive: its caches keep their bits (its row of
         the result is unspecified).  No value is read on the host.
@@ -332,30 +343,33 @@ class DecodeLayer(torch.nn.Module):
         cos, sin = cos_tab.index_select(0, pc).view(bs, 1, d), sin_tab.index_select(0, pc).view(bs, 1, d)
         kv, put = self.kv.gathered()
         out = self._token_torch(kv, h, cos, sin, lambda cache, new: _scatter_rows(cache, pc, active, new),
-                                arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather)
+                                arange.view(1, 1, 1, -1) > pc.view(bs, 1, 1, 1), gather, lora)
         if put is not None:
             put(torch.arange(bs, device=pos.device)[active], pc[active])
         return out
 
-    def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather):
+    def forward_prefill(self, h, positions, lengths, slots, T: int, cos_tab, sin_tab, gather, lora=None):
         """Plain torch, a chunk of tokens per sequence: `h` [n * T, hidden] (row i * T + t), rows padded to the common T.  Host ints
         per sequence: token 0 of sequence i at `positions[i]`, `lengths[i]` tokens, cache slot `slots[i]`.  Each sequence's k / v rows
         are appended to its caches and every token attends causally over cache + chunk (a batch in which nothing differs: in one
         batched formulation, prefill_attention_torch).  A paged layer: on its gathered twin, as forward_seq."""
         kv, put = self.kv.gathered()
-        ctx = prefill_attention_torch_seq(self.qkv(self.norm1(h)), cos_tab, sin_tab, positions, lengths, slots, kv.k, kv.v,
+        xn = self.norm1(h)
+        ctx = prefill_attention_torch_seq(self._adapted(lora, "qkv", xn, self.qkv(xn)), cos_tab, sin_tab, positions, lengths, slots, kv.k, kv.v,
                                           self.hl, self.kvl, self.cfg.head_dim, T, kv.k_exp, kv.v_exp)
         if put is not None:
             rows = [(sl, p + t) for p, n, sl in zip(positions, lengths, slots) for t in range(n)]
             put(*[torch.tensor([r[i] for r in rows], dtype=torch.long, device=h.device) for i in (0, 1)])
-        return self._mlp_torch(h + gather(self.o(gather(ctx))), gather)
+        ctx = gather(ctx)
+        return self._mlp_torch(h + gather(self._adapted(lora, "o", ctx, self.o(ctx))), gather, lora)
 
-    def _mlp_torch(self, h, gather):
+    def _mlp_torch(self, h, gather, lora=None):
         """The plain-torch MLP block behind either attention: h + down(silu(gate) * up) of norm2(h)."""
-        gu = self._split_gate_up(self.gate_up(self.norm2(h)))
+        xn = self.norm2(h)
+        gu = self._split_gate_up(self._adapted(lora, "gate_up", xn, self.gate_up(xn)))
         il = self.cfg.inter // self.world
-        act = torch.nn.functional.silu(gu[:, :il]) * gu[:, il:]
-        return h + gather(self.down(gather(act)))
+        act = gather(torch.nn.functional.silu(gu[:, :il]) * gu[:, il:])
+        return h + gather(self._adapted(lora, "down", act, self.down(act)))
 
     # ---- the attention launch handed to forward_fused / forward_fused5: RoPE, KV write, attention over the cache; qkv -> context.
     # Which entry point that is follows from what the cache is: KVCache.decode_attention / prefill_attention
@@ -368,16 +382,17 @@ class DecodeLayer(torch.nn.Module):
         appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device."""
         return self.kv.prefill_attention(qkv, pos, cos_tab, sin_tab, self.hl, T, lengths, slots, per_sequence)
 
-    def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather):
+    def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather, lora=None):
         """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
         (the linears are called as modules, so the library routes them by row count).  `h` is the residual stream (updated in
         place), `delta` the previous layer's not-yet-added MLP output; returns (h, this layer's delta)."""
         from . import decode_ops as G
 
         h, y = G.add_rmsnorm(h, delta, self.norm1.weight, self.norm1.eps)
-        ctx = attention(self.qkv(y), pos, cos_tab, sin_tab)
-        h, y = G.add_rmsnorm(h, gather(self.o(gather(ctx))), self.norm2.weight, self.norm2.eps)
-        return h, gather(self.down(gather(G.swiglu(self._split_gate_up(self.gate_up(y)).contiguous()))))
+        ctx = gather(attention(self._adapted(lora, "qkv", y, self.qkv(y)), pos, cos_tab, sin_tab))
+        h, y = G.add_rmsnorm(h, gather(self._adapted(lora, "o", ctx, self.o(ctx))), self.norm2.weight, self.norm2.eps)
+        act = gather(G.swiglu(self._split_gate_up(self._adapted(lora, "gate_up", y, self.gate_up(y))).contiguous()))
+        return h, gather(self._adapted(lora, "down", act, self.down(act)))
 
     # ---- five launches per layer: every element-wise stage rides in a GEMM launch (tg_w4_gemm ABI 5) ----
     def _w4(self, lin, x, **kw):
@@ -407,6 +422,8 @@ class DecodeLayer(torch.nn.Module):
         if not f.get("mlp"):
             n += 0 if f.get("norm2") else 1                  # RMSNorm in front of gate_up
             n += 0 if f.get("swiglu") else 1                 # SwiGLU behind it
+        if self.adapters is not None:
+            n += 2 * len(self.adapters.targets)              # shrink + expand behind every adapted linear
         return n
 
     def fusable(self) -> bool:
@@ -422,39 +439,52 @@ class DecodeLayer(torch.nn.Module):
             return gu
         return gu.view(gu.shape[0], -1, 2, b).transpose(1, 2).reshape(gu.shape[0], -1)
 
-    def forward_fused5(self, h, attention, pos, cos_tab, sin_tab):
+    def forward_fused5(self, h, attention, pos, cos_tab, sin_tab, lora=None):
         """TP = 1.  qkv GEMM (RMSNorm in its activation staging) -> `attention` -> o GEMM (residual add in its store) -> gate_up
         GEMM (RMSNorm in its staging, SwiGLU in its store) -> down GEMM (residual add in its store): 5 launches instead of 8.
         `h` [bs, hidden] is the residual stream, updated in place.  A stage the library cannot fuse for this problem
-        (w4_linear_fused returns None) runs as its own launch, as in forward_fused."""
+        (w4_linear_fused returns None) runs as its own launch, as in forward_fused.
+        lora (the call has adapters): shrink + expand behind every adapted linear.  Where the GEMM fused the norm no normalised
+        activations exist, so the shrink takes the norm weight and reads `h`; the o / down GEMMs keep their residual store and the
+        expand adds into `h`; an adapted gate_up gives up the SwiGLU store (the delta must land in front of the activation): norm fused,
+        expand, then dg_swiglu."""
         from . import decode_ops as G
 
         n1, n2 = self.norm1, self.norm2
         qkv = self._try_fused("norm1", self.qkv, h, norm_weight=n1.weight, norm_eps=n1.eps)
         if qkv is None:
-            qkv = self.qkv(G.add_rmsnorm(h, None, n1.weight, n1.eps)[1])
+            y = G.add_rmsnorm(h, None, n1.weight, n1.eps)[1]
+            qkv = self._adapted(lora, "qkv", y, self.qkv(y))
+        else:
+            self._adapted(lora, "qkv", h, qkv, n1)
         ctx = attention(qkv, pos, cos_tab, sin_tab)
         if self._w4(self.o, ctx, residual=h, out=h) is None:       # (a residual add is available in every 4-bit kernel)
-            G.add_rmsnorm(h, self.o(ctx), n2.weight, n2.eps, want_norm=False)
+            G.add_rmsnorm(h, self._adapted(lora, "o", ctx, self.o(ctx)), n2.weight, n2.eps, want_norm=False)
+        else:
+            self._adapted(lora, "o", ctx, h)
         # MLP block: norm2 + SwiGLU inside the gate_up launch ("mlp"; the store needs the 8 + 8 row order); else whichever of the two
         # the library can fuse (a block too large to stage on chip has no fused norm, "norm2", but still the SwiGLU store, "swiglu")
-        il8 = self.cfg.gate_up_interleave == 8
+        il8 = self.cfg.gate_up_interleave == 8 and not (lora is not None and lora.has("gate_up"))
         act = gu = None
         if il8:
             act = self._try_fused("mlp", self.gate_up, h, norm_weight=n2.weight, norm_eps=n2.eps, swiglu=True)
         else:
             self._fuse["mlp"] = False
             gu = self._try_fused("norm2", self.gate_up, h, norm_weight=n2.weight, norm_eps=n2.eps)
+            if gu is not None:
+                self._adapted(lora, "gate_up", h, gu, n2)
         if act is None and gu is None:
             y = G.add_rmsnorm(h, None, n2.weight, n2.eps)[1]
             if il8:
                 act = self._try_fused("swiglu", self.gate_up, y, swiglu=True)
             if act is None:
-                gu = self.gate_up(y)
+                gu = self._adapted(lora, "gate_up", y, self.gate_up(y))
         if act is None:
             act = G.swiglu(self._split_gate_up(gu).contiguous())
         if self._w4(self.down, act, residual=h, out=h) is None:
-            G.add_rmsnorm(h, self.down(act), n2.weight, n2.eps, want_norm=False)
+            G.add_rmsnorm(h, self._adapted(lora, "down", act, self.down(act)), n2.weight, n2.eps, want_norm=False)
+        else:
+            self._adapted(lora, "down", act, h)
         return h
 
 
@@ -466,8 +496,13 @@ class DecodeStack(torch.nn.Module):
                  rank: int = 0, world: int = 1, group=None, seed: int = 0, lm_head: bool = True,
                  fused: Optional[bool] = None, emulate_gather: bool = False, gather: str = "rccl", fuse_gemm_stages: bool = True,
                  ragged: bool = False, kv_cache: Optional[str] = None, kv_pages: Optional[int] = None, page_size: int = 64,
-                 mx8_attention: str = "split"):
-        """kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks) --
+                 mx8_attention: str = "split", adapters=None):
+        """adapters: an `any4_amd.lora.AdapterSet` -- LoRA adapters on the fused linears, one per sequence: `adapter_ids` int32 [bs] (a
+        static buffer the step reads, so a captured graph sees ids changed between two replays; -1: none) names every sequence's slot of
+        the set, `prefill_adapter_ids` those of a prefill's sequences; `decode`, `prefill` and `generate` take a host list (`adapters=`).
+        Every adapted linear becomes linear -> lora_shrink -> lora_expand in all schedules (plain torch: lora.lora_ref); TP = 1 only.
+        With None (the default) nothing of this exists and the stack is what it was.
+        kv_pages: None = every batch slot owns max_seq cache rows (the default).  A number: a PAGED cache (ragged stacks) --
         every layer holds pools [kv_pages, kvl, page_size, d] and one `block_table` int32 [bs, max_seq / page_size] (a static device
         buffer, -1 = unmapped, mirrored on the host) maps position p of slot b to row p % page_size of page block_table[b, p // page_size];
         a `PagePool` (any4_amd/kvcache.py) hands the pages out.  page_size: a power of two, 64 <= page_size <= max_seq, max_seq % page_size
@@ -509,6 +544,17 @@ class DecodeStack(torch.nn.Module):
             raise ValueError("kv_pages (a paged KV cache) needs DecodeStack(..., ragged=True)")
         check_cache_config(cfg, kv_cache, kv_pages, page_size, mx8_attention)
         self.kv_cache, self.mx8_attention = kv_cache, mx8_attention
+        if adapters is not None:
+            if world > 1:
+                raise ValueError("adapters need world == 1 (row-sharding an adapter's B across ranks is not implemented)")
+            want = {name: (n, k) for name, n, k in cfg.linear_shapes() if name in adapters.targets}
+            if adapters.cfg.layers != cfg.layers or adapters.shapes != want or adapters.dtype != dtype or \
+                    adapters.cfg.gate_up_interleave != cfg.gate_up_interleave:
+                raise ValueError("the AdapterSet was built for another configuration or dtype than this stack")
+            sd, ad = torch.device(device), adapters.device
+            if sd.type != ad.type or (sd.index is not None and ad.index is not None and sd.index != ad.index):
+                raise ValueError(f"the AdapterSet lives on {ad}, this stack on {sd}")
+        self.adapters = adapters
         self.gather_mode = gather
         self._peer = {}  # output width per rank -> PeerWriteGather
         self.cfg, self.bs, self.rank, self.world, self.group = cfg, bs, rank, world, group
@@ -552,6 +598,15 @@ class DecodeStack(torch.nn.Module):
         if self.ragged:  # (a sequence per element; prefill uses the first n of its three)
             for name in ("pos_seq", "prefill_pos_seq", "prefill_len", "prefill_slot"):
                 self.register_buffer(name, torch.zeros(bs, dtype=torch.long, device=device), persistent=False)
+        if adapters is not None:
+            for layer in self.layers:
+                layer.adapters = adapters
+            self._adapter_ids = [-1] * bs  # the host mirror of adapter_ids
+            # False: a fused stack adds the deltas with lora.lora_ref (index_select + bmm) instead of the two kernels -- the torch
+            # formulation behind the same step, what tools/llama_decode_bench.py --lora measures the kernels against
+            self.lora_kernels = True
+            for name in ("adapter_ids", "prefill_adapter_ids"):
+                self.register_buffer(name, torch.full((bs,), -1, dtype=torch.int32, device=device), persistent=False)
         self._graph = None
         self._graph_samples = False  # the captured step ends with the sampler (capture(sample=True))
         self._out = None
@@ -680,6 +735,42 @@ class DecodeStack(torch.nn.Module):
             return parts.view(1, -1)
         return parts.movedim(0, 1).reshape(y.shape[0], -1)
 
+    # ---- adapters: which slot of the AdapterSet every sequence takes (host mirror `_adapter_ids`, device `adapter_ids`) ----
+    def _adapter_list(self, ids, n) -> list:
+        """`ids` (a call's `adapters=`: n host ints, negative = none) checked against the set."""
+        if self.adapters is None:
+            raise ValueError("this stack has no adapters (DecodeStack(..., adapters=AdapterSet))")
+        if isinstance(ids, torch.Tensor):
+            ids = ids.tolist()
+        try:
+            vals = [operator.index(v) for v in ids]
+        except TypeError as e:
+            raise ValueError(f"adapters must be {n} host ints (-1: none): {e}") from e
+        if len(vals) != n:
+            raise ValueError(f"adapters: {len(vals)} ids for {n} sequences")
+        if any(v >= self.adapters.n_adapters for v in vals):
+            raise ValueError(f"adapters {vals}: each must be -1 (none) or a slot in [0, n_adapters = {self.adapters.n_adapters})")
+        return [max(v, -1) for v in vals]
+
+    def _set_adapters(self, slots, vals) -> None:
+        """adapter_ids[slot] = id for the named cache slots, in place (a captured step reads this buffer)."""
+        for sl, v in zip(slots, vals):
+            self._adapter_ids[sl] = v
+        self.adapter_ids.copy_(torch.tensor(self._adapter_ids, dtype=torch.int32))
+
+    def set_adapters(self, ids) -> None:
+        """The adapter slot of every sequence from the next step on: `bs` host ints (-1: none; an id >= n_adapters raises).  What
+        `decode(..., adapters=ids)` does in front of its step; a captured step sees it at the next replay."""
+        self._set_adapters(range(self.bs), self._adapter_list(ids, self.bs))
+
+    def _lora(self, idx, rows_per_id):
+        """The adapters of one call as the layers take them (None: a stack without)."""
+        if self.adapters is None:
+            return None
+        from .lora import AdapterCall
+
+        return AdapterCall(self.adapters, idx, rows_per_id, self.fused and self.lora_kernels)
+
     @torch.no_grad()
     def step(self) -> torch.Tensor:
         """One decode step on the static inputs `self.tokens` [bs], `self.pos` [1] (a ragged stack: `self.pos_seq` [bs]); returns
@@ -719,15 +810,16 @@ class DecodeStack(torch.nn.Module):
         pos = self.pos_seq if self.ragged else self.pos
         h, delta = self.embed(self.tokens), None
         five = self._five_launch()
+        lora = self._lora(self.adapter_ids, 1) if self.adapters is not None else None
         for layer in self.layers:
             if not self.fused:
-                h = (layer.forward_seq if self.ragged else layer)(h, pos, self.cos, self.sin, self.arange, self._gather)
+                h = (layer.forward_seq if self.ragged else layer)(h, pos, self.cos, self.sin, self.arange, self._gather, lora=lora)
                 continue
             attention = partial(layer.decode_attention, per_sequence=True) if self.ragged else layer.decode_attention
             if five:
-                h = layer.forward_fused5(h, attention, pos, self.cos, self.sin)
+                h = layer.forward_fused5(h, attention, pos, self.cos, self.sin, lora=lora)
             else:
-                h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather)
+                h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather, lora=lora)
         return self._head(h, delta)
 
     # ---- sampling (any4_amd/sampling.py is the definition; fused: dg_sample, one launch) ----
@@ -865,12 +957,17 @@ class DecodeStack(torch.nn.Module):
             buf.copy_(torch.tensor(vals, dtype=torch.long))
 
     @torch.no_grad()
-    def decode(self, tokens: torch.Tensor, position) -> torch.Tensor:
+    def decode(self, tokens: torch.Tensor, position, adapters=None) -> torch.Tensor:
         """Feed `tokens` [bs] at sequence position `position`; graph replay if captured, else eager.
         A ragged stack also takes a position per sequence: a list / CPU tensor of `bs` ints, each -1 (the sequence is inactive: it
         writes no cache row and its logits row is unspecified) or inside the cache, or an int64 device tensor [bs], which is copied
-        without a sync and without a host check (the kernels ignore positions outside the cache)."""
+        without a sync and without a host check (the kernels ignore positions outside the cache).
+        adapters (a stack with an AdapterSet): `bs` host ints, the adapter slot of every sequence from this step on (-1: none; an id >=
+        n_adapters raises); None: as they are."""
+        ids = None if adapters is None else self._adapter_list(adapters, self.bs)
         self._set_position(position)
+        if ids is not None:  # (after every check: a refused call writes nothing)
+            self._set_adapters(range(self.bs), ids)
         self.tokens.copy_(tokens)
         out = self._out if self._graph is not None else None
         if self._graph is not None:
@@ -899,6 +996,7 @@ class DecodeStack(torch.nn.Module):
         if not per_sequence and positions is not None:
             self.prefill_pos.fill_(positions[0])
         h, delta = self.embed(toks.reshape(-1)), None  # [n * T, hidden], row i * T + t
+        lora = self._lora(self.prefill_adapter_ids[:n], T) if self.adapters is not None else None  # (row i * T + t: sequence i's adapter)
         pos = self.prefill_pos
         if per_sequence and self.fused:
             pos, dev_len, dev_slot = [buf[:n] for buf in (self.prefill_pos_seq, self.prefill_len, self.prefill_slot)]
@@ -906,13 +1004,13 @@ class DecodeStack(torch.nn.Module):
                 buf.copy_(torch.tensor(vals, dtype=torch.long))
         for layer in self.layers:
             if not self.fused:  # plain torch needs the positions on the host (prefill() refuses position=None on this path)
-                h = layer.forward_prefill(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows)
+                h = layer.forward_prefill(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows, lora=lora)
                 continue
             # the eight launches of a decode step at n * T rows, with the chunk's attention
             attention = layer.prefill_attention
             if per_sequence:
                 attention = partial(attention, T=T, lengths=dev_len, slots=dev_slot, per_sequence=True)
-            h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather_rows)
+            h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather_rows, lora=lora)
         return h, delta
 
     @staticmethod
@@ -921,7 +1019,7 @@ class DecodeStack(torch.nn.Module):
         return [None if t is None else t.view(n, -1, t.shape[-1])[:, -1].contiguous() for t in hd]
 
     @torch.no_grad()
-    def prefill(self, tokens: torch.Tensor, position=0, chunk: Optional[int] = None, lengths=None, slots=None) -> torch.Tensor:
+    def prefill(self, tokens: torch.Tensor, position=0, chunk: Optional[int] = None, lengths=None, slots=None, adapters=None) -> torch.Tensor:
         """Feed a prompt: `tokens` [bs, T] at sequence positions position ... position + T - 1.  Every layer's KV cache receives the T
         rows a token-by-token `decode()` would have written (bit for bit on the fused path), and the logits [bs, vocab] of the LAST
         token are returned (the final hidden state when built without LM head) -- `decode()` continues at position + T.
@@ -936,7 +1034,10 @@ class DecodeStack(torch.nn.Module):
         ints in [0, T] (default T), sequence i has tokens[i, :lengths[i]] at positions position[i] ...; `slots`: n distinct host ints in
         [0, bs), the cache slot (= row of a later `decode`) of each sequence (default: slot i, and n == bs).  Chunks advance every
         sequence by `chunk` tokens.  Returns logits [n, vocab] of each sequence's LAST VALID token (unspecified for a length of 0);
-        cache slots not named are not touched."""
+        cache slots not named are not touched.
+        adapters (a stack with an AdapterSet): n host ints, the adapter slot of each sequence (-1: none).  They are written to
+        `adapter_ids[slot]` too, so the decode steps that follow use the same adapter; None: each sequence takes what `adapter_ids` holds
+        for its cache slot.  (position=None: the caller owns `prefill_adapter_ids` as well.)"""
         per_sequence = lengths is not None or slots is not None or isinstance(position, (list, tuple)) or \
             (isinstance(position, torch.Tensor) and position.dim() > 0) or self.paged  # (there is no scalar-position paged kernel)
         if per_sequence and not self.ragged:
@@ -947,6 +1048,8 @@ class DecodeStack(torch.nn.Module):
             raise ValueError(f"tokens must be [{'1 <= n <= ' if per_sequence else ''}bs = {self.bs}, T >= 1], got {tuple(tokens.shape)}")
         S, (n, T) = self.cfg.max_seq, tokens.shape
         if position is None:  # nothing is made on the host and copied here: a pageable copy is not legal inside a graph capture
+            if adapters is not None:
+                raise ValueError("position=None (the caller owns the prefill buffers) does not go with adapters=")
             if not self.fused or (chunk is not None and int(chunk) < T):
                 raise ValueError("position=None (the caller owns prefill_pos) needs the fused path and a single chunk")
             return self._head(*self._last_rows(self._prefill_chunk(tokens, None, None, None, False), n))
@@ -978,12 +1081,18 @@ class DecodeStack(torch.nn.Module):
         chunk = min(T, 2048) if chunk is None else int(chunk)
         if chunk < 1:
             raise ValueError(f"chunk must be >= 1, got {chunk}")
+        if adapters is not None:
+            adapters = self._adapter_list(adapters, n)
         if self.paged:
             self._refuse_shared([(sl, p, p + x) for p, x, sl in zip(position, lengths, slots) if x > 0])
             self._reserve_all([(sl, p + x) for p, x, sl in zip(position, lengths, slots) if x > 0])
         # the LM head runs on the last token of every sequence only.  Named per sequence, the last valid token may lie in any chunk: its
         # row of the last layer's output is picked on the device; else it is the last row of the last chunk
         last = torch.tensor([max(x - 1, 0) for x in lengths], dtype=torch.long).to(tokens.device) if per_sequence else None
+        if self.adapters is not None:  # (after every check: nothing is written by a call that raises)
+            if adapters is not None:
+                self._set_adapters(slots, adapters)
+            self.prefill_adapter_ids[:n].copy_(torch.tensor([self._adapter_ids[sl] for sl in slots], dtype=torch.int32))
         keep = None
         for c0 in range(0, T, chunk):
             toks = tokens[:, c0: c0 + chunk]
@@ -1005,7 +1114,8 @@ class DecodeStack(torch.nn.Module):
         return self.sample(logits, self.pos_seq if self.ragged else self.pos, 1)
 
     @torch.no_grad()
-    def generate(self, prompt, new_tokens: int, eos: Optional[int] = None, *, temperature=None, top_k=0, top_p=1.0, seed=0) -> torch.Tensor:
+    def generate(self, prompt, new_tokens: int, eos: Optional[int] = None, *, temperature=None, top_k=0, top_p=1.0, seed=0,
+                 adapters=None) -> torch.Tensor:
         """Greedy continuation: `prefill(prompt)` [bs, T], then `decode` (graph replay if captured) from position T.
         Returns the `new_tokens` generated token ids [bs, new_tokens].
         temperature (None: greedy, the argmax of every step): a SAMPLED continuation -- every token, the first one after the prefill
@@ -1016,7 +1126,11 @@ class DecodeStack(torch.nn.Module):
         one launch behind each step.
         A ragged stack also takes a list of `bs` 1-D token tensors of different lengths, and `eos`: a sequence that has emitted `eos`,
         or whose next position would be outside the cache, is inactive from the next step on (decided on the device, no sync per
-        step) and its remaining outputs are `eos` (-1 when eos is None)."""
+        step) and its remaining outputs are `eos` (-1 when eos is None).
+        adapters (a stack with an AdapterSet): `bs` host ints, the adapter slot of every sequence for the prefill and every step (they
+        stay in `adapter_ids`); None: as they are."""
+        if adapters is not None:
+            adapters = self._adapter_list(adapters, self.bs)
         if self.lm_head is None:
             raise ValueError("generate needs the LM head")
         if new_tokens < 1:
@@ -1031,7 +1145,7 @@ class DecodeStack(torch.nn.Module):
                 self._reserve_all([(b, min(n + new_tokens, self.cfg.max_seq)) for b, n in enumerate(lens)])
         if not per_sequence:
             base = prompt.shape[1] if prompt.dim() == 2 else 0  # a host int: decode() fills the position
-            logits = self.prefill(prompt)
+            logits = self.prefill(prompt, adapters=adapters)
             tok = self.sample(logits, base, 0) if sampled else logits.argmax(-1)
         else:  # right-padded prefill with lengths; who is still active is kept on the device
             if not self.ragged:
@@ -1044,7 +1158,7 @@ class DecodeStack(torch.nn.Module):
             padded = torch.zeros(self.bs, max(lens), dtype=torch.long, device=dev)
             for b, p in enumerate(prompts):
                 padded[b, : lens[b]] = p.to(dev)
-            logits = self.prefill(padded, position=0, lengths=lens)
+            logits = self.prefill(padded, position=0, lengths=lens, adapters=adapters)
             base = torch.tensor(lens, dtype=torch.long).to(dev)
             tok = self.sample(logits, base, 0) if sampled else logits.argmax(-1)
             alive = torch.ones(self.bs, dtype=torch.bool, device=dev)

@@ -333,6 +333,65 @@ def sample(logits: torch.Tensor, ctr: torch.Tensor, temperature: torch.Tensor, t
     return token_out
 
 
+def _lora_ids(what, idx, rows, rows_per_id, n_adapters_of):
+    rows_per_id = int(rows_per_id)
+    if rows_per_id < 1:
+        raise RuntimeError(f"{what}: rows_per_id must be >= 1, got {rows_per_id}")
+    if idx.dtype != torch.int32 or idx.dim() != 1 or idx.numel() < -(-rows // rows_per_id):
+        raise RuntimeError(f"{what}: idx must be int32 with at least ceil({rows} / {rows_per_id}) elements (one per sequence), got {idx.dtype} "
+                           f"{tuple(idx.shape)}")
+    if n_adapters_of.dim() != 3:
+        raise RuntimeError(f"{what}: adapter weights must be [n_adapters, rows, columns], got {tuple(n_adapters_of.shape)}")
+    return rows_per_id
+
+
+def lora_shrink(x: torch.Tensor, A: torch.Tensor, idx: torch.Tensor, rows_per_id: int = 1, norm_weight: torch.Tensor = None,
+                eps: float = 0.0, out: torch.Tensor = None) -> torch.Tensor:
+    """t [m, r] float32 = A[idx[i // rows_per_id]] @ x[i] per activation row i (any4_amd/lora.py: lora_ref is the definition).  x [m, k]
+    16-bit, A [n_adapters, r, k] of x's dtype, idx int32 on the device (an id outside [0, n_adapters): no adapter, t = 0).  norm_weight
+    [k]: the RMSNorm of the activations in the "sum" convention, t = rs * A @ RNE16(x * norm_weight).  out: the float32 buffer to fill."""
+    _gpu(x, A, idx, norm_weight, out)
+    if x.dim() != 2:
+        raise RuntimeError(f"lora_shrink: x must be [m, k], got {tuple(x.shape)}")
+    m, k = x.shape
+    rows_per_id = _lora_ids("lora_shrink", idx, m, rows_per_id, A)
+    na, r = A.shape[0], A.shape[1]
+    if A.dtype != x.dtype or A.shape[2] != k:
+        raise RuntimeError(f"lora_shrink: A must be [n_adapters, r, k = {k}] {x.dtype}, got {tuple(A.shape)} {A.dtype}")
+    if norm_weight is not None and (norm_weight.dtype != x.dtype or norm_weight.numel() != k):
+        raise RuntimeError(f"lora_shrink: norm_weight must be [k = {k}] {x.dtype}, got {tuple(norm_weight.shape)} {norm_weight.dtype}")
+    if out is None:
+        out = torch.empty((m, r), dtype=torch.float32, device=x.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != (m, r):
+        raise RuntimeError(f"lora_shrink: out must be float32 [{m}, {r}], got {out.dtype} {tuple(out.shape)}")
+    _lib.check(_lib.load().dg_lora_shrink(x.data_ptr(), None if norm_weight is None else norm_weight.data_ptr(), A.data_ptr(), idx.data_ptr(),
+                                          out.data_ptr(), m, k, r, na, rows_per_id, float(eps), _dt(x), x.device.index, _stream(x)),
+               "dg_lora_shrink")
+    return out
+
+
+def lora_expand(t: torch.Tensor, B: torch.Tensor, scale: torch.Tensor, idx: torch.Tensor, y: torch.Tensor, rows_per_id: int = 1) -> torch.Tensor:
+    """y [m, n] += scale[a] * t[i] @ B[a].T IN PLACE, a = idx[i // rows_per_id]; rows without an adapter are not rewritten.  t [m, r] float32
+    (lora_shrink's), B [n_adapters, n, r] of y's dtype, scale float32 [n_adapters]; y 16-bit with a contiguous last dimension (its rows may
+    be further apart: a view into a wider tensor)."""
+    _gpu(t, B, scale, idx)
+    if y.dim() != 2 or y.stride(1) != 1 or not y.is_cuda:
+        raise RuntimeError("lora_expand: y must be [m, n] on a ROCm device with a contiguous last dimension (there is no CPU fallback)")
+    m, n = y.shape
+    rows_per_id = _lora_ids("lora_expand", idx, m, rows_per_id, B)
+    na, r = B.shape[0], B.shape[2]
+    ldy = y.stride(0) if m > 1 else max(y.stride(0), n)
+    if B.dtype != y.dtype or B.shape[1] != n:
+        raise RuntimeError(f"lora_expand: B must be [n_adapters, n = {n}, r] {y.dtype}, got {tuple(B.shape)} {B.dtype}")
+    if t.dtype != torch.float32 or tuple(t.shape) != (m, r):
+        raise RuntimeError(f"lora_expand: t must be float32 [{m}, {r}], got {t.dtype} {tuple(t.shape)}")
+    if scale.dtype != torch.float32 or scale.numel() != na:
+        raise RuntimeError(f"lora_expand: scale must be float32 [{na}], got {scale.dtype} {tuple(scale.shape)}")
+    _lib.check(_lib.load().dg_lora_expand(t.data_ptr(), B.data_ptr(), scale.data_ptr(), idx.data_ptr(), y.data_ptr(), m, n, r, ldy, na,
+                                          rows_per_id, _dt(y), y.device.index, _stream(y)), "dg_lora_expand")
+    return y
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """gu [bs, 2 il] = [gate | up] -> silu(gate) * up [bs, il]."""
     _gpu(gu)

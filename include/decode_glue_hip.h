@@ -270,6 +270,27 @@ TG_API int dg_sample(const void* logits, const int64_t* ctr, const float* temper
                      int64_t bs, int64_t vocab, int64_t ld, int per_sequence, int64_t ctr_add, int dtype, int device, tg_stream_t stream);
 TG_API int64_t dg_sample_scratch_bytes(int64_t bs, int64_t vocab);
 
+/* ---- per-sequence LoRA adapters on a linear's output: shrink (t = A x) and expand (y += scale B t), the "BGMV" pair ----
+ * The definition is any4_amd/lora.py: lora_ref.  Adapter weights of ONE linear [n][k]: A [n_adapters][r][k] and B [n_adapters][n][r], 16-bit
+ * row-major, scale float [n_adapters] (alpha / rank); an adapter of lower rank is zero-padded to r.  The adapter of activation row i is
+ * idx[i / rows_per_id] (int32 on the device, ceil(m / rows_per_id) entries: 1 for a decode step, the chunk length for a prefill), read by
+ * the kernels, so a captured graph sees ids changed between replays.  A value outside [0, n_adapters) means "no adapter": no address
+ * is formed from it.
+ *   dg_lora_shrink   t[i][j] = sum_c A[a][j][c] x~[i][c], f32.  x [m][k] 16-bit.  norm_weight NULL: x~ = x.  norm_weight g [k]: x~ =
+ *                    RNE16(x g) and the sum is multiplied by rs = rsqrt(mean(x^2) + eps) in f32 -- the "sum" convention of the GEMV's
+ *                    fused RMSNorm (tg_w4_gemm.norm_weight), so the adapter contracts the 16-bit activations the base GEMM contracts.
+ *                    Rows without an adapter: t = 0.
+ *   dg_lora_expand   y[i][c] = RNE16(fma(scale[a], sum_j B[a][c][j] t[i][j], f32(y[i][c]))), j ascending in f32, IN PLACE on y [m][ldy]
+ *                    (16-bit, the first n columns of every row).  Rows without an adapter keep their bits: they are not rewritten.
+ * Sums run in a fixed order without atomics: the same inputs give the same bits on every launch.  Any m >= 1.
+ * TG_E_NULL: a required pointer is NULL; TG_E_DTYPE; TG_E_SHAPE: m, n_adapters or rows_per_id < 1, r outside {8, 16, ..., 64}, k < 8,
+ * n < 8, n % 8, ldy < n, ldy % 8; TG_E_K_DIV: k % 8; TG_E_SIZE: m >= 2^31, k > 2^17, n > 65535 x 512; TG_E_ALIGN: x, norm_weight, A,
+ * B, t or y off a 16-byte boundary, idx or scale off 4.  Nothing is launched in any of these cases.  No allocation, no synchronisation. */
+TG_API int dg_lora_shrink(const void* x, const void* norm_weight, const void* A, const int32_t* idx, float* t, int64_t m, int64_t k,
+                          int64_t r, int64_t n_adapters, int64_t rows_per_id, float eps, int dtype, int device, tg_stream_t stream);
+TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, const int32_t* idx, void* y, int64_t m, int64_t n, int64_t r,
+                          int64_t ldy, int64_t n_adapters, int64_t rows_per_id, int dtype, int device, tg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,14 @@ with and without the page lookup; leg (b) reports the bytes of the four mx8 pool
 alone, with the fused sampler (dg_sample) as its last node, followed by the same sampler as an eager launch, and followed by the torch
 formulation (sort, softmax, cumsum, masked softmax, multinomial) -- alternating in one process, the order rotating -- and the sampler
 launched back to back on its own.  temperature 0.8, top_k 50, top_p 0.95.
+
+    python tools/llama_decode_bench.py --config llama3_8b --interleave --lora 16 [--adapters 8] [--out profiles/lora_bench.jsonl]
+
+--lora RANK (one GPU): per-sequence LoRA adapters on the four fused linears, one JSON line per batch size (1 and 8),
+appended to --out: the captured step near position 512 (a) without adapters, (b) with an AdapterSet attached and every id -1 -- the price
+of the eight added launches per layer --, (c) every sequence on adapter 0, (d) a different adapter per sequence (bs = 8), (e) the torch
+formulation of the deltas (index_select + bmm) behind the same fused step.  The legs alternate in one process, three runs each, the order
+rotating; (b), (c) and (d) replay one captured graph and differ only in `adapter_ids`.
 """
 import argparse
 import json
@@ -140,6 +148,61 @@ def sample_bench(a, cfg, device):
                          torch_sampler_us=round((ms["step_then_torch_sampler"]["median"] - ms["step"]["median"]) * 1e3, 2),
                          sampler_back_to_back_us=round(ev[0].elapsed_time(ev[1]) / 200 * 1e3, 2)))
         del plain, fused, runs
+        torch.cuda.empty_cache()
+    return legs
+
+
+def lora_bench(a, cfg, device):
+    """--lora RANK: the captured step without adapters (a), with adapters attached and every id -1 (b), every sequence on adapter 0 (c), a
+    different adapter per sequence (d, bs = 8), and the torch formulation of the deltas (lora_ref: index_select + bmm) behind the same
+    fused step with every sequence on adapter 0 (e).  (b), (c) and (d) are ONE captured graph: only `adapter_ids` changes."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+    from any4_amd.lora import AdapterSet
+
+    base = {"config": a.config, "layers": cfg.layers, "max_seq": cfg.max_seq, "data": "synthetic (random weights, random tokens, random adapters)",
+            "rank": a.lora, "n_adapters": a.adapters, "steps": a.steps, "warmup": a.warmup, "start_pos": a.start_pos, "rounds": a.rounds,
+            "interleave": cfg.gate_up_interleave}
+    legs = []
+    for bs in (1, 8):
+        def stack(adapters, kernels=True):
+            aset = None
+            if adapters:
+                aset = AdapterSet(cfg, a.adapters, a.lora, device, torch.bfloat16)
+                gen = torch.Generator(device=device).manual_seed(5)
+                for slot in range(a.adapters):  # random adapters of full rank on all four linears of every layer, scale 2
+                    aset.load(slot, {(layer, name): ((torch.randn(a.lora, k, device=device, generator=gen) / k ** 0.5).bfloat16(),
+                                                     (torch.randn(n, a.lora, device=device, generator=gen) * 0.05).bfloat16())
+                                     for layer in range(cfg.layers) for name, n, k in cfg.linear_shapes()}, alpha=2.0 * a.lora)
+            st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                             fuse_gemm_stages=not a.no_fuse, adapters=aset)
+            if adapters:
+                st.lora_kernels = kernels
+                st.decode(torch.zeros(bs, dtype=torch.long, device=device), 0, adapters=[0] * bs)  # (captured with live adapters)
+            st.capture()
+            return st
+
+        plain, kern, ref = stack(False), stack(True), stack(True, kernels=False)
+        runs = {"a_no_adapters": (plain, None), "b_attached_all_off": (kern, [-1] * bs), "c_all_on_adapter_0": (kern, [0] * bs),
+                "e_torch_all_on_adapter_0": (ref, [0] * bs)}
+        if bs > 1:
+            runs["d_adapter_per_sequence"] = (kern, [i % a.adapters for i in range(bs)])
+        series = {k: [] for k in runs}
+        order = list(runs)
+        for r in range(a.rounds):
+            for k in order[r % len(order):] + order[: r % len(order)]:
+                st, ids = runs[k]
+                if ids is not None:
+                    st.set_adapters(ids)
+                series[k].append(round(time_steps(st, a.steps, a.warmup, a.start_pos) * 1e3, 4))
+        ms = {k: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "series": v} for k, v in series.items()}
+        med = lambda k: ms[k]["median"]
+        legs.append(dict(base, leg="captured step: no adapters / attached, all off / all on adapter 0 / one per sequence / torch formulation",
+                         bs=bs, kernels_per_layer={"a": getattr(plain, "kernels_per_layer", None), "b_c_d": getattr(kern, "kernels_per_layer", None)},
+                         ms_per_step=ms,
+                         added_launches_us_per_layer=round((med("b_attached_all_off") - med("a_no_adapters")) * 1e3 / cfg.layers, 2),
+                         adapter_work_us_per_layer=round((med("c_all_on_adapter_0") - med("b_attached_all_off")) * 1e3 / cfg.layers, 2),
+                         kernels_vs_torch=round(med("c_all_on_adapter_0") / med("e_torch_all_on_adapter_0"), 4)))
+        del plain, kern, ref, runs
         torch.cuda.empty_cache()
     return legs
 
@@ -344,7 +407,7 @@ def main():
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; with --mx8-attention online 30)")
     ap.add_argument("--warmup", type=int, default=None, help="warm-up steps (default 20; with --mx8-attention online 10)")
     ap.add_argument("--max-seq", type=int, default=1024)
-    ap.add_argument("--start-pos", type=int, default=128, help="sequence position of the first timed token")
+    ap.add_argument("--start-pos", type=int, default=None, help="sequence position of the first timed token (default 128; with --lora 512)")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--interleave", action="store_true", help="gate_up rows in blocks of 8 gate + 8 up (lets the GEMM fuse SwiGLU)")
     ap.add_argument("--no-fuse", action="store_true", help="separate glue kernels around the GEMMs (8 launches per layer instead of 5)")
@@ -371,6 +434,9 @@ def main():
                     help="the legs of DESIGN.md section 16: the paged KV cache against the contiguous one at an 8192-position cache (see the module docstring); one GPU")
     ap.add_argument("--sample", action="store_true",
                     help="the leg of DESIGN.md section 18: the captured step with and without the sampler node, and followed by the torch formulation (see the module docstring); one GPU")
+    ap.add_argument("--lora", type=int, default=0, metavar="RANK",
+                    help="per-sequence LoRA adapters of this rank on the four fused linears (DESIGN.md section 20; see the module docstring); one GPU")
+    ap.add_argument("--adapters", type=int, default=8, help="--lora: adapters resident in the set")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
                                                 "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl, with both profiles/paged_mx8_bench.jsonl)")
     a = ap.parse_args()
@@ -379,7 +445,10 @@ def main():
     three_way = a.mx8_attention == "online"
     a.steps = a.steps if a.steps is not None else 30 if three_way else 100
     a.warmup = a.warmup if a.warmup is not None else 10 if three_way else 20
-    a.rounds = a.rounds if a.rounds is not None else 5 if three_way else 7
+    a.rounds = a.rounds if a.rounds is not None else 3 if a.lora else 5 if three_way else 7  # (--lora: three runs per leg)
+    a.start_pos = a.start_pos if a.start_pos is not None else 512 if a.lora else 128
+    if a.lora:
+        a.out = a.out or os.path.join(ROOT, "profiles", "lora_bench.jsonl")
     if a.out is None and a.sample:
         a.out = os.path.join(ROOT, "profiles", "sample_bench.jsonl")
     if a.out is None:
@@ -410,6 +479,16 @@ def main():
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.lora:
+        if world > 1:
+            raise SystemExit("--lora runs on one GPU")
+        with open(a.out, "a") as f:
+            for leg in lora_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     if a.sample:
         if world > 1:
