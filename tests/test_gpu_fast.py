@@ -1102,6 +1102,9 @@ def test_module_more_than_16_rows(T, oracle, kernel, cls):
     # (round 6: ONE layer from 17 rows with the op's workspace = the split-K tile launch; without a workspace: 16-row blocks -- both checked here)
     assert ops.gemm_w4_plan(2 * m, n, k, g, QT[qtype], on_right, 4, weight_format="native") == "tile"
     assert ops.gemm_w4_plan(2 * m, n, k, g, QT[qtype], on_right, 4, weight_format="native", workspace=False) in ("pair", "pair_xr", "gemv")
+    from tests.test_gpu_parity import assert_tile_regime
+    assert_tile_regime((64, 64, 2, 8, 4), 2 * m, n, k, g, qtype)            # 4 tiles x 8 splits of 8 super-tiles
+    assert_tile_regime(None, 2 * m, n, k, g, qtype, workspace=False)
     x = x2.view(2, m, k).to(DEV)
     y = mod(x)
     bias = mod.bias

@@ -690,6 +690,28 @@ def test_gemm_int8_vs_oracle(T, oracle, on_right, inner, g, m, n, k, dtype):
     assert (y[:, n:] == 0).all()  # padded rows: zero codes... with scale = zero = 0 they dequantise to 0
 
 
+# The tile GEMM's launch for the shapes of the many-rows tests below on 256 CUs, as tests/tile_ref.py restates tg_tile.hip: (BM, BN, KS,
+# splits, steps per workgroup).  A change to tile_splits or to a threshold moves a shape to another kernel flavour: the tests then say so.
+TILE_REGIMES = {(65, 200, 512): (128, 64, 2, 1, 4), (128, 64, 64): (128, 64, 1, 1, 1), (130, 1008, 1024): (128, 64, 2, 2, 4), (512, 528, 2048): (128, 64, 2, 4, 4),
+                (33, 200, 2048): (64, 64, 2, 4, 4), (64, 528, 2048): (64, 64, 2, 4, 4), (48, 1008, 4096): (64, 64, 2, 8, 4), (130, 1008, 4096): (128, 64, 2, 8, 4),
+                (256, 2056, 2048): (128, 64, 2, 2, 8), (17, 72, 2048): (64, 64, 2, 4, 4), (20, 4096, 2048): (64, 64, 2, 4, 4), (40, 264, 2048): (64, 64, 2, 4, 4),
+                (100, 4096, 4096): (128, 64, 2, 4, 8)}
+# int8: (splits, steps at g = 64 (KS = 1), steps at g >= 128 (KS = 2)) on 128 x 64 tiles
+TILE_REGIMES_W8 = {(17, 200, 512): (1, 8, 4), (33, 264, 2048): (4, 8, 4), (64, 4096, 2048): (4, 8, 4), (130, 1008, 4096): (8, 8, 4), (512, 528, 1024): (2, 8, 4),
+                   (100, 48, 192): (1, 3, None)}
+
+
+def assert_tile_regime(want, m, wrows, k, g, qtype, dtype=torch.bfloat16, **kw):
+    """The restated launch plan of this call is a tile launch -- and, on 256 CUs, the one `want` names (None: the tile GEMM declines)."""
+    from tests import tile_ref
+
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    plan = tile_ref.tile_plan(m, wrows, k, g, qtype, cus, dtype=dtype, **kw)
+    assert (plan is None) == (want is None), (plan, want)
+    if want is not None and cus == 256:
+        assert plan[:5] == want, (plan, want)
+
+
 @pytest.mark.parametrize("on_right", [True, False])
 @pytest.mark.parametrize("g", [64, 128, 256])
 @pytest.mark.parametrize("m,n,k,dtype", [(17, 200, 512, torch.bfloat16), (7, 200, 512, torch.bfloat16), (33, 264, 2048, torch.bfloat16), (64, 4096, 2048, torch.float16), (130, 1008, 4096, torch.bfloat16),
@@ -712,6 +734,8 @@ def test_gemm_int8_many_rows_on_the_tile_gemm(T, oracle, on_right, g, m, n, k, d
         n_pad = w2.size(0) * 16
     szp = torch.zeros(k // g, n_pad, 2, dtype=dtype)
     szp[:, :n] = sz
+    w8 = TILE_REGIMES_W8.get((m, n, k))      # (7 rows: the 16-row kernel)
+    assert_tile_regime(w8 and (128, 64, 1 if g == 64 else 2, w8[0], w8[1] if g == 64 else w8[2]), m, n_pad, k, g, "int8", dtype, int8=True, on_right=on_right)
     run = lambda: T.tinygemm_y_f16RM_x_f16RM_w_int8TC(d(x), w2, g, d(szp), True) if on_right else T.tinygemm_y_f16RM_x_f16RM_w_int8TC(w2, d(x), g, d(szp), False)
     y = run()
     assert y.shape == (m, n_pad)
@@ -819,6 +843,7 @@ def test_tile_gemm_many_rows_against_oracle(T, oracle, dtype, qtype, g, m, n, k)
     codes, x, qinfo, lut = rand_problem(n, k, g, m, qtype, dtype=dtype, seed=m + n + g)
     want = oracle_weights(oracle, codes, g, qtype, qinfo, lut, dtype)
     assert ops.gemm_w4_plan(m, -(-n // 8) * 8, k, g, QT[qtype], True, 4, dtype=dtype) == "tile"
+    assert_tile_regime(TILE_REGIMES[(m, n, k)], m, -(-n // 8) * 8, k, g, qtype, dtype)
     for num in ("fast", "reference"):
         with any4_amd.numerics(num):
             y = run_rm(T, codes, x, qinfo, lut, g, qtype, True, 4)
@@ -847,6 +872,7 @@ def test_tile_gemm_many_rows_mx4(T, oracle, m, n, k):
     codes, x, qinfo, lut = rand_problem(n, k, 32, m, "mx4", seed=m + n)
     want = oracle_weights(oracle, codes, 32, "mx4", qinfo, None, torch.bfloat16)
     assert ops.gemm_w4_plan(m, -(-n // 8) * 8, k, 32, 3, True, 4) == "tile"
+    assert_tile_regime(TILE_REGIMES[(m, n, k)], m, -(-n // 8) * 8, k, 32, "mx4")
     y = run_rm(T, codes, x, qinfo, None, 32, "mx4", True, 4)
     assert y.shape[0] == m and torch.isfinite(y.float()).all()
     assert_gemm_close(y[:, :n], x, want, torch.bfloat16)
@@ -872,6 +898,9 @@ def test_tile_gemm_without_a_workspace(T, oracle, monkeypatch):
     m, n, k, g = 128, 1008, 4096, 128
     codes, x, qinfo, lut = rand_problem(n, k, g, m, "any4_rowwise", seed=77)
     want = oracle_weights(oracle, codes, g, "any4_rowwise", qinfo, lut, torch.bfloat16)
+    assert_tile_regime((128, 64, 2, 8, 4), m, n, k, g, "any4_rowwise")                       # split 8 with the op's workspace,
+    assert_tile_regime((128, 64, 2, 1, 32), m, n, k, g, "any4_rowwise", workspace=False)    # 32 steps without; 48 rows without: not this kernel
+    assert_tile_regime(None, 48, n, k, g, "any4_rowwise", workspace=False)
     y_split = run_rm(T, codes, x, qinfo, lut, g, "any4_rowwise", True, 4)
     assert torch.equal(y_split, run_rm(T, codes, x, qinfo, lut, g, "any4_rowwise", True, 4))
     saved = dict(ops._WS_BYTES)
