@@ -3,7 +3,6 @@ import fails loudly (build it with `python -m any4_amd.build`)."""
 from __future__ import annotations
 
 import ctypes
-import functools
 import os
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -12,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtinygemm_hip.so")
 TG_BF16, TG_F16 = 0, 1
 TG_Q_INT4, TG_Q_ANY4_GLOBAL, TG_Q_ANY4_ROWWISE, TG_Q_MX4, TG_Q_INT8 = 0, 1, 2, 3, 4
 TG_NUM_FAST, TG_NUM_REFERENCE, TG_NUM_FAST_MFMA, TG_NUM_FAST_DOT2 = 0, 1, 2, 3
-TG_ABI_VERSION = 8
+TG_ABI_VERSION = 9
 TG_PLAN_SPLITK, TG_PLAN_STREAM, TG_PLAN_PAIR, TG_PLAN_PAIR_XR, TG_PLAN_GEMV, TG_PLAN_TILE = 1, 2, 3, 4, 5, 6
 TG_PLAN_PAIR_M1_LEAN = 7  # tg_gemm_w4_plan_detail only
 TG_LAYOUT_RM, TG_LAYOUT_TC_A = 0, 1
@@ -66,63 +65,53 @@ class PeerGather(ctypes.Structure):
     ]
 
 
-# The twelve fused attention entry points of include/decode_glue_hip.h: four bases, each with a `_seq` flavour (a position per sequence), two of
-# them with `_mx8` ones (an mx8 KV cache) -- and, bound as a group of their own (PAGED_SYMBOLS; the header declares them DG_PAGED_API), the
-# `_paged` flavour of three bases (a page pool behind a block table; per sequence, 16-bit rows) -- and, a group of their own too (KV8_ONLINE_SYMBOLS;
-# DG_KV8_API), dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache (kv8_online_signature) -- and, again a group of their own
-# (PAGED_MX8_SYMBOLS; DG_PAGED_KV8_API), dg_rope_attn_online_mx8_paged / dg_prefill_attn_mx8_paged: mx8 page pools (paged_mx8_signature).  Their argument lists are these pieces, by name: SYMBOLS takes the types, decode_ops.attn_args
-# puts a call's values in the same order.
-_ci, _cf = ctypes.c_int, ctypes.c_float
-ATTN_BASES = {"dg_rope_attn": False, "dg_rope_attn_online": False, "dg_rope_attn_split": True, "dg_prefill_attn": True}  # base: has _mx8 flavours
-_ATTN_HEAD = [("qkv", _vp), ("cos", _vp), ("sin", _vp), ("pos", _vp)]
-_ATTN_LEN_SLOT = [("len", _vp), ("slot", _vp)]                      # dg_prefill_attn*_seq
-_ATTN_CACHES = [("k_cache", _vp), ("v_cache", _vp)]
-_ATTN_POOLS = [("table", _vp), ("k_pool", _vp), ("v_pool", _vp)]   # *_paged
-_ATTN_PAGES = [("page_size", _i64), ("num_pages", _i64)]            # *_paged, behind max_seq
-ATTN_PAGED_BASES = ("dg_rope_attn_online", "dg_rope_attn_split", "dg_prefill_attn")
-_ATTN_EXPS = [("k_exp", _vp), ("v_exp", _vp)]                       # *_mx8*
-_ATTN_SCRATCH = [("scratch", _vp), ("scratch_bytes", _i64)]         # dg_rope_attn_split*
-_ATTN_SHAPE = [("hl", _ci), ("kvl", _ci), ("d", _ci), ("max_seq", _i64), ("scale", _cf)]
-_ATTN_TAIL = [("dtype", _ci), ("device", _ci), ("stream", _vp)]
+# The fused attention call of include/decode_glue_hip.h: four kernels, four flag bits, one struct
+DG_ATTN_GENERAL, DG_ATTN_ONLINE, DG_ATTN_SPLIT, DG_ATTN_PREFILL = 0, 1, 2, 3
+DG_ATTN_SEQ, DG_ATTN_MX8, DG_ATTN_PAGED, DG_ATTN_ONE_BARRIER = 1, 2, 4, 8
+_u32, _f32 = ctypes.c_uint32, ctypes.c_float
 
 
-@functools.lru_cache(maxsize=None)
-def attn_signature(base, seq=False, mx8=False, paged=False):
-    """(entry point, ((argument name, ctype), ...)) of one flavour of an attention base (paged: the `_paged` one, which is per sequence)"""
-    if base not in ATTN_BASES or (mx8 and not ATTN_BASES[base]) or (paged and (mx8 or base not in ATTN_PAGED_BASES)):
-        raise KeyError(f"no attention entry point {base}{'_mx8' if mx8 else ''}{'_paged' if paged else ''}")
-    seq = seq or paged
-    prefill, split = base == "dg_prefill_attn", base == "dg_rope_attn_split"
-    shape = _ATTN_SHAPE[:4] + _ATTN_PAGES + _ATTN_SHAPE[4:] if paged else _ATTN_SHAPE
-    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill and seq else []) + (_ATTN_POOLS if paged else _ATTN_CACHES) + (_ATTN_EXPS if mx8 else [])
-            + [("out", _vp)] + (_ATTN_SCRATCH if split else []) + [("bs", _i64)] + ([("T", _i64)] if prefill else [])
-            + ([("cache_bs", _i64)] if prefill and seq else []) + shape + ([("nsplit", _ci)] if split else []) + _ATTN_TAIL)
-    return base + ("_paged" if paged else ("_mx8" if mx8 else "") + ("_seq" if seq else "")), tuple(args)
+class Attn(ctypes.Structure):
+    """struct dg_attn (include/decode_glue_hip.h)"""
+
+    _fields_ = [
+        ("struct_bytes", _u32), ("kernel", _i32),
+        ("qkv", _vp), ("cos", _vp), ("sin", _vp), ("pos", _vp), ("k_cache", _vp), ("v_cache", _vp), ("out", _vp),
+        ("k_exp", _vp), ("v_exp", _vp), ("len", _vp), ("slot", _vp), ("table", _vp), ("scratch", _vp),
+        ("scratch_bytes", _i64), ("bs", _i64), ("T", _i64), ("cache_bs", _i64), ("max_seq", _i64), ("page_size", _i64), ("num_pages", _i64),
+        ("flags", _u32), ("hl", _i32), ("kvl", _i32), ("d", _i32), ("nsplit", _i32), ("dtype", _i32), ("scale", _f32), ("reserved", _u32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = ctypes.sizeof(Attn)
 
 
-def kv8_online_signature(seq=False):
-    """(entry point, ((argument name, ctype), ...)) of dg_rope_attn_online_mx8(_seq): the one-barrier kernel on an mx8 cache, which takes
-    the argument list of dg_rope_attn_split_mx8(_seq).  A function of its own: attn_signature("dg_rope_attn_online", mx8=True) stays a
-    KeyError, as that base has no `_mx8` flavour among the twelve."""
-    args = (_ATTN_HEAD + _ATTN_CACHES + _ATTN_EXPS + [("out", _vp)] + _ATTN_SCRATCH + [("bs", _i64)] + _ATTN_SHAPE + [("nsplit", _ci)]
-            + _ATTN_TAIL)
-    return "dg_rope_attn_online_mx8" + ("_seq" if seq else ""), tuple(args)
-
-
-ATTN_PAGED_MX8_BASES = ("dg_rope_attn_online", "dg_prefill_attn")
-
-
-def paged_mx8_signature(base):
-    """(entry point, ((argument name, ctype), ...)) of dg_rope_attn_online_mx8_paged / dg_prefill_attn_mx8_paged: mx8 page pools behind the
-    block table -- the `_paged` list of dg_rope_attn_split / dg_prefill_attn with the exponent pools behind the code pools.  A function of
-    its own: attn_signature(base, mx8=True, paged=True) stays a KeyError, the twelve and the three paged ones are what they were."""
-    if base not in ATTN_PAGED_MX8_BASES:
-        raise KeyError(f"no attention entry point {base}_mx8_paged")
-    prefill = base == "dg_prefill_attn"
-    args = (_ATTN_HEAD + (_ATTN_LEN_SLOT if prefill else []) + _ATTN_POOLS + _ATTN_EXPS + [("out", _vp)] + ([] if prefill else _ATTN_SCRATCH)
-            + [("bs", _i64)] + ([("T", _i64), ("cache_bs", _i64)] if prefill else []) + _ATTN_SHAPE[:4] + _ATTN_PAGES + _ATTN_SHAPE[4:]
-            + ([] if prefill else [("nsplit", _ci)]) + _ATTN_TAIL)
-    return base + "_mx8_paged", tuple(args)
+# (kernel, flags) -> the name the call had as an entry point of its own up to ABI 8: DG_ATTN_FLAVOURS of the header, which is what
+# dg_attn_launch accepts; error messages keep these names.  A copy written by hand (the header is not read at run time): a new flavour
+# gets its row here as well as there, and tests/test_host_cpu.py fails until the two agree.
+ATTN_FLAVOURS = {
+    (DG_ATTN_GENERAL, 0): "dg_rope_attn",
+    (DG_ATTN_GENERAL, DG_ATTN_SEQ): "dg_rope_attn_seq",
+    (DG_ATTN_ONLINE, 0): "dg_rope_attn_online",
+    (DG_ATTN_ONLINE, DG_ATTN_SEQ): "dg_rope_attn_online_seq",
+    (DG_ATTN_ONLINE, DG_ATTN_SEQ | DG_ATTN_PAGED): "dg_rope_attn_online_paged",
+    (DG_ATTN_SPLIT, 0): "dg_rope_attn_split",
+    (DG_ATTN_SPLIT, DG_ATTN_SEQ): "dg_rope_attn_split_seq",
+    (DG_ATTN_SPLIT, DG_ATTN_MX8): "dg_rope_attn_split_mx8",
+    (DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_SEQ): "dg_rope_attn_split_mx8_seq",
+    (DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER): "dg_rope_attn_online_mx8",
+    (DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER | DG_ATTN_SEQ): "dg_rope_attn_online_mx8_seq",
+    (DG_ATTN_SPLIT, DG_ATTN_SEQ | DG_ATTN_PAGED): "dg_rope_attn_split_paged",
+    (DG_ATTN_SPLIT, DG_ATTN_SEQ | DG_ATTN_PAGED | DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER): "dg_rope_attn_online_mx8_paged",
+    (DG_ATTN_PREFILL, 0): "dg_prefill_attn",
+    (DG_ATTN_PREFILL, DG_ATTN_SEQ): "dg_prefill_attn_seq",
+    (DG_ATTN_PREFILL, DG_ATTN_MX8): "dg_prefill_attn_mx8",
+    (DG_ATTN_PREFILL, DG_ATTN_MX8 | DG_ATTN_SEQ): "dg_prefill_attn_mx8_seq",
+    (DG_ATTN_PREFILL, DG_ATTN_SEQ | DG_ATTN_PAGED): "dg_prefill_attn_paged",
+    (DG_ATTN_PREFILL, DG_ATTN_SEQ | DG_ATTN_PAGED | DG_ATTN_MX8): "dg_prefill_attn_mx8_paged",
+}
 
 
 # name -> argtypes, exactly the prototypes of include/tinygemm_hip.h
@@ -166,6 +155,7 @@ SYMBOLS = {
                    ctypes.c_int, ctypes.c_int, _vp],
     "dg_decode_attn": [_vp, _vp, _vp, _vp, _vp, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _i64, ctypes.c_float,
                        ctypes.c_int, ctypes.c_int, _vp],
+    "dg_attn_launch": [ctypes.POINTER(Attn), ctypes.c_int, _vp],
     "dg_rope_attn_split_scratch_bytes": [_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int],
     "dg_swiglu": [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_linear16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
@@ -178,28 +168,10 @@ SYMBOLS = {
     # t, B, scale, idx, y, m, n, r, ldy, n_adapters, rows_per_id, dtype, device, stream
     "dg_lora_expand": [_vp] * 5 + [_i64] * 6 + [ctypes.c_int, ctypes.c_int, _vp],
 }
-for _base, _has_mx8 in ATTN_BASES.items():
-    for _seq in (False, True):
-        for _mx8 in (False, True) if _has_mx8 else (False,):
-            _name, _args = attn_signature(_base, _seq, _mx8)
-            SYMBOLS[_name] = [t for _, t in _args]
-# name -> argtypes of the paged attention entry points (the DG_PAGED_API prototypes of include/decode_glue_hip.h); load() binds them too
-PAGED_SYMBOLS = {}
-for _base in ATTN_PAGED_BASES:
-    _name, _args = attn_signature(_base, paged=True)
-    PAGED_SYMBOLS[_name] = [t for _, t in _args]
-
-# name -> argtypes of the one-barrier kernel's mx8 entry points (the DG_KV8_API prototypes of include/decode_glue_hip.h); load() binds them too
-KV8_ONLINE_SYMBOLS = {}
-for _seq in (False, True):
-    _name, _args = kv8_online_signature(_seq)
-    KV8_ONLINE_SYMBOLS[_name] = [t for _, t in _args]
-
-# name -> argtypes of the paged mx8 entry points (the DG_PAGED_KV8_API prototypes of include/decode_glue_hip.h); load() binds them too
-PAGED_MX8_SYMBOLS = {}
-for _base in ATTN_PAGED_MX8_BASES:
-    _name, _args = paged_mx8_signature(_base)
-    PAGED_MX8_SYMBOLS[_name] = [t for _, t in _args]
+# Up to ABI 8 three groups of attention entry points were bound from tables of their own.  Nothing is any more, and nothing in this
+# tree reads these; the names stay, empty, so that a module written against that binding, which merges the four tables when it is
+# imported (`{**SYMBOLS, **PAGED_SYMBOLS, ...}`), still imports and fails where it makes its call, not where it is loaded.
+PAGED_SYMBOLS, KV8_ONLINE_SYMBOLS, PAGED_MX8_SYMBOLS = {}, {}, {}
 
 _lib = None
 
@@ -215,7 +187,7 @@ def load() -> ctypes.CDLL:
             "There is no CPU/PyTorch fallback for the tinygemm ops."
         )
     lib = ctypes.CDLL(LIB_PATH)
-    for name, argtypes in {**SYMBOLS, **PAGED_SYMBOLS, **KV8_ONLINE_SYMBOLS, **PAGED_MX8_SYMBOLS}.items():
+    for name, argtypes in SYMBOLS.items():
         try:
             fn = getattr(lib, name)
         except AttributeError as e:  # a stale build: the header declares a symbol the .so does not export

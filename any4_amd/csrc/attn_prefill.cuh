@@ -1,4 +1,4 @@
-// attn_prefill.cuh -- prompt prefill for the decode stack (include/decode_glue_hip.h, dg_prefill_attn): a chunk of T new tokens per
+// attn_prefill.cuh -- prompt prefill for the decode stack (include/decode_glue_hip.h, DG_ATTN_PREFILL): a chunk of T new tokens per
 // sequence is roped, appended to the static KV cache [bs][kvl][max_seq][D] and attended causally over cache + chunk.
 //
 // Two launches:
@@ -25,11 +25,11 @@
 // nobody (every token only reads rows <= its own position) and leaves its output row unwritten; rows of a tile beyond the workgroup's
 // last valid position are zero-filled in LDS instead of being read, so NaN-filled or unallocated tails are never touched.
 //
-// SEQ (dg_prefill_attn_seq): position, length and cache slot are per sequence, read by every workgroup: p0 = pos[i], T_i = min(len[i], T)
+// SEQ (DG_ATTN_SEQ): position, length and cache slot are per sequence, read by every workgroup: p0 = pos[i], T_i = min(len[i], T)
 // decides which tokens exist (the padded T stays in the row addressing and sizes the grid), the cache base is slot[i]'s.  A sequence
 // with T_i <= 0 or a slot outside [0, cache_bs) does nothing.  The SEQ = false instantiations read none of the three.
 //
-// PAGED (dg_prefill_attn_paged, dg_prefill_attn_mx8_paged; implies SEQ): the caches are pools [num_pages][kvl][page_size][D] behind a block table
+// PAGED (DG_ATTN_PAGED, with or without DG_ATTN_MX8; goes with SEQ): the caches are pools [num_pages][kvl][page_size][D] behind a block table
 // (kv_paged.cuh) whose row is slot[i]'s.  A 64-position tile lies in one page (page_size >= 64), so the staging pass takes the tile's
 // first row from its page (kv_unit_row) -- one scalar table read per tile, made when the tile's loads are issued, i.e. one tile ahead of
 // its use -- and the rows stay tile-relative; the append drops a row whose own table entry is outside the pool.  Everything else is the

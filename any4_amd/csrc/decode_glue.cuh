@@ -404,7 +404,7 @@ __global__ void __launch_bounds__(256) rope_attn_kernel(const uint16_t* __restri
 // One block per head leaves 7/8 of the CUs idle and walks a long context at ~40 ns per position; this one fills the GPU.
 // Softmax statistics are combined flash-decoding style, so probabilities are normalised AFTER the value contraction
 // (the single-block kernels round normalised probabilities to 16 bit first): same result within 16-bit rounding.
-// KV8 (the dg_rope_attn_split_mx8 entry points): the caches are mx8 -- `k_cache` / `v_cache` hold one byte per element, X the exponent
+// KV8 (the dg_rope_attn_split_mx8 flavours of dg_attn_launch): the caches are mx8 -- `k_cache` / `v_cache` hold one byte per element, X the exponent
 // bytes.  The owner block encodes the roped k row and the raw v row per 32-element block, and the new token enters the scores and the
 // value sum as its DECODED row (what every later step will read); cached rows are converted on load, everything behind is shared.
 template <typename DT, bool SEQ = false, bool KV8 = false>
@@ -559,13 +559,13 @@ __global__ void __launch_bounds__(256) rope_attn_split_kernel(const uint16_t* __
 // what those are.  Both are read off the kernel's optional LAST parameters, the pack PG (empty, KvPages, Kv8Exps, or KvPages, Kv8Exps):
 // this kernel reads gridDim from the implicit arguments BEHIND the explicit ones, and even an empty trailing struct moves those by
 // eight bytes -- the contiguous flavours would keep their size and lose their bytes (measured; profiles/paged_kernel_bytes.txt).
-// PAGED (the dg_rope_attn_*_paged entry points; implies SEQ) -- where the unit starts: k_cache / v_cache (and the exponents) are pools
+// PAGED (the dg_rope_attn_*_paged flavours; implies SEQ) -- where the unit starts: k_cache / v_cache (and the exponents) are pools
 // behind the block table G instead of the head's max_seq rows.  An RPI-row iteration lies in one page (page_size >= 64 >= RPI), so the
 // unit is the iteration's page: one scalar table read, the rows relative to the iteration's first.  The table entries of the speculative iterations do not depend
 // on the position: they are requested beside pos[b], in front of the speculative K / V requests.  Rows past the end re-read the
 // iteration's own first row (the contiguous flavours re-read position 0, which may sit in another page); they are masked either way, so
 // every sum is the SEQ flavour's.  The new token's row is written only where its own table entry is in the pool.
-// KV8 (the dg_rope_attn_online_mx8* entry points) -- what a piece is: the caches are mx8 (kv8.cuh), a lane's K / V piece 8 code bytes and
+// KV8 (the dg_rope_attn_online_mx8* flavours) -- what a piece is: the caches are mx8 (kv8.cuh), a lane's K / V piece 8 code bytes and
 // one exponent byte instead of 16 bytes, requested where the 16-byte pieces are, clamped and masked alike, and converted to the 16-bit
 // type on use -- behind the conversion every sum and rounding point is the 16-bit flavour's.  The new token's roped k row and raw v row
 // are encoded from the registers they are in (mx8_encode_piece: the host encoder's bytes) and enter the scores and the value sum DECODED.
@@ -979,8 +979,9 @@ int dg_rope_kv(const void* qkv, const float* cos, const float* sin, const int64_
 
 int dg_decode_attn(const void* q, const void* k_cache, const void* v_cache, const int64_t* pos, void* out, int64_t bs,
                    int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  const AttnCall c = attn_call(q, nullptr, nullptr, pos, const_cast<void*>(k_cache), const_cast<void*>(v_cache), out, bs, hl, kvl, d, max_seq,
-                               scale, dtype, device, stream);
+  dg_attn c = {};  // (no cos / sin, no flags: check_attn's ATTN_UNFUSED kind)
+  c.qkv = q; c.pos = pos; c.k_cache = const_cast<void*>(k_cache); c.v_cache = const_cast<void*>(v_cache); c.out = out;
+  c.bs = c.cache_bs = bs; c.T = 1; c.hl = hl; c.kvl = kvl; c.d = d; c.max_seq = max_seq; c.scale = scale; c.nsplit = 1; c.dtype = dtype;
   if (const int rc = check_attn(ATTN_UNFUSED, c)) return rc;
   DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
@@ -994,25 +995,27 @@ int dg_decode_attn(const void* q, const void* k_cache, const void* v_cache, cons
 
 namespace {
 
-// The launchers of the three fused decode kernels: check_attn, then only what is a launcher's own.  c.seq / c.kv8 pick the kernel's flavour
+// The launchers of the three fused decode kernels: check_attn, then only what is a launcher's own.  f.seq / f.kv8 pick the kernel's flavour
 // (the dg_*_seq entry points: `pos` [bs]; the dg_*_mx8 ones: mx8 caches with their exponent bytes).
-int rope_attn_launch(const AttnCall& c) {
-  if (const int rc = check_attn(ATTN_GENERAL, c)) return rc;
-  DeviceScope ds(c.device);
+int rope_attn_launch(const dg_attn& c, int device, tg_stream_t stream) {
+  if (const int rc = check_attn(DG_ATTN_GENERAL, c)) return rc;
+  const AttnFlags f(c);
+  DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
   return pick_dt(c.dtype, [&](auto DT_) {
-    return pick<0, 1>(c.seq, [&](auto SEQ_) {
+    return pick<0, 1>(f.seq, [&](auto SEQ_) {
       hipLaunchKernelGGL((rope_attn_kernel<decltype(DT_), (bool)decltype(SEQ_)::value>), dim3((unsigned)(c.bs * c.hl)), dim3(256),
-                         attn_lds_bytes(772, c.max_seq, c.d), (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache,
+                         attn_lds_bytes(772, c.max_seq, c.d), (hipStream_t)stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache,
                          (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.d, c.max_seq, c.scale);
       return launch_status();
     });
   });
 }
 
-// The one-barrier kernel, for a call that check_attn(ATTN_ONLINE) accepts and inside the caller's DeviceScope: nsplit = 1 (no part, no
-// counters) is dg_rope_attn_online, more is the split entry's d = 64 / 128 path (block c of a head takes the 32-row iterations c, c + nsplit, ...)
-int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counters) {
+// The one-barrier kernel, for a call that check_attn(DG_ATTN_ONLINE) accepts and inside the caller's DeviceScope: nsplit = 1 (no part, no
+// counters) is DG_ATTN_ONLINE, more is DG_ATTN_SPLIT's d = 64 / 128 path (block c of a head takes the 32-row iterations c, c + nsplit, ...)
+int online_kernel_launch(const dg_attn& c, tg_stream_t stream, int nsplit, float* part, int* counters) {
+  const AttnFlags f(c);
   const unsigned lds = (unsigned)(8 * (c.d + 2) * sizeof(float));
   unsigned long long* trace = nullptr;
 #if GEMV_TRACE
@@ -1024,47 +1027,48 @@ int online_kernel_launch(const AttnCall& c, int nsplit, float* part, int* counte
       // sequence), Kv8Exps (mx8 caches), or both in that order -- and names the kernel's pack
       auto launch = [&](auto SEQ_, auto PAGED_, auto... tail) {
         hipLaunchKernelGGL((rope_attn_online_kernel<decltype(DT_), decltype(LPR_)::value, (bool)decltype(SEQ_)::value, (bool)decltype(PAGED_)::value, decltype(tail)...>),
-                           dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin,
+                           dim3((unsigned)(c.bs * c.hl), (unsigned)nsplit), dim3(512), lds, (hipStream_t)stream, (const uint16_t*)c.qkv, c.cos, c.sin,
                            c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache, (uint16_t*)c.out, c.hl, c.kvl, c.max_seq, c.scale, trace, part, counters, tail...);
         return launch_status();
       };
       const Kv8Exps X{(uint8_t*)c.k_exp, (uint8_t*)c.v_exp};
-      if (c.paging) return c.kv8 ? launch(std::true_type{}, std::true_type{}, kv_pages(c), X) : launch(std::true_type{}, std::true_type{}, kv_pages(c));
-      return pick<0, 1>(c.seq, [&](auto SEQ_) { return c.kv8 ? launch(SEQ_, std::false_type{}, X) : launch(SEQ_, std::false_type{}); });
+      if (f.paging) return f.kv8 ? launch(std::true_type{}, std::true_type{}, kv_pages(c), X) : launch(std::true_type{}, std::true_type{}, kv_pages(c));
+      return pick<0, 1>(f.seq, [&](auto SEQ_) { return f.kv8 ? launch(SEQ_, std::false_type{}, X) : launch(SEQ_, std::false_type{}); });
     });
   });
 }
 
-int rope_attn_online_launch(const AttnCall& c) {
-  if (const int rc = check_attn(ATTN_ONLINE, c)) return rc;
-  DeviceScope ds(c.device);
+int rope_attn_online_launch(const dg_attn& c, int device, tg_stream_t stream) {
+  if (const int rc = check_attn(DG_ATTN_ONLINE, c)) return rc;
+  DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
-  return online_kernel_launch(c, 1, nullptr, nullptr);
+  return online_kernel_launch(c, stream, 1, nullptr, nullptr);
 }
 
-int rope_attn_split_launch(const AttnCall& c) {
-  if (const int rc = check_attn(ATTN_SPLIT, c)) return rc;
-  DeviceScope ds(c.device);
+int rope_attn_split_launch(const dg_attn& c, int device, tg_stream_t stream) {
+  if (const int rc = check_attn(DG_ATTN_SPLIT, c)) return rc;
+  const AttnFlags f(c);
+  DeviceScope ds(device);
   if (!ds.ok) return TG_E_DEVICE;
   int* counters = reinterpret_cast<int*>(c.scratch);
   float* part = reinterpret_cast<float*>(reinterpret_cast<char*>(c.scratch) + split_scratch(c.bs, c.hl, c.d, c.nsplit).part_offset);
   // a 16-bit call the one-barrier kernel would take runs that kernel, split over the sequence (same scratch layout); mx8 caches only
-  // through dg_rope_attn_online_mx8 (c.one_barrier: check_attn held the call to that kernel's d and alignment; with nsplit = 1 the kernel
-  // touches neither part nor counters) -- dg_rope_attn_split_mx8 stays the 256-thread kernel
+  // with DG_ATTN_ONE_BARRIER (check_attn held the call to that kernel's d and alignment; with nsplit = 1 the kernel touches neither part
+  // nor counters) -- an mx8 call without it stays the 256-thread kernel
   // (a paged call always: check_attn holds it to that kernel's d and alignment, there is no paged 256-thread kernel -- a paged mx8 call
-  //  comes from dg_rope_attn_online_mx8_paged with c.one_barrier set, and one without it is refused below, never sent to that kernel)
-  if (c.one_barrier || (!c.kv8 && check_attn(ATTN_ONLINE, c) == 0)) return online_kernel_launch(c, c.nsplit, part, counters);
-  if (c.paging) return TG_E_SHAPE;
+  //  carries DG_ATTN_ONE_BARRIER, attn_flavour has no pair without it, and one that came without it is refused below, never sent to that kernel)
+  if (f.one_barrier || (!f.kv8 && check_attn(DG_ATTN_ONLINE, c) == 0)) return online_kernel_launch(c, stream, c.nsplit, part, counters);
+  if (f.paging) return TG_E_SHAPE;
   const unsigned lds = attn_lds_bytes(772, cdiv(c.max_seq, c.nsplit), c.d);  // the scores of one chunk
   if (lds > 64u * 1024u) return TG_E_SHAPE;
   return pick_dt(c.dtype, [&](auto DT_) {
-    return pick<0, 1>(c.seq, [&](auto SEQ_) {
-      return pick<0, 1>(c.kv8, [&](auto KV8_) {
+    return pick<0, 1>(f.seq, [&](auto SEQ_) {
+      return pick<0, 1>(f.kv8, [&](auto KV8_) {
         constexpr bool KV8 = decltype(KV8_)::value;
         Kv8Arg<KV8> X;
         if constexpr (KV8) { X.k_exp = (uint8_t*)c.k_exp; X.v_exp = (uint8_t*)c.v_exp; }
         hipLaunchKernelGGL((rope_attn_split_kernel<decltype(DT_), (bool)decltype(SEQ_)::value, KV8>), dim3((unsigned)(c.bs * c.hl), (unsigned)c.nsplit),
-                           dim3(256), lds, (hipStream_t)c.stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache,
+                           dim3(256), lds, (hipStream_t)stream, (const uint16_t*)c.qkv, c.cos, c.sin, c.pos, (uint16_t*)c.k_cache, (uint16_t*)c.v_cache,
                            (uint16_t*)c.out, part, counters, c.hl, c.kvl, c.d, c.max_seq, c.scale, X);
         return launch_status();
       });
@@ -1080,79 +1084,17 @@ extern "C" {
 TG_API void tg_dev_attn_trace(unsigned long long* buf) { g_attn_trace = buf; }  // developer builds: [blocks][8] stamps of the last launch
 #endif
 
-int dg_rope_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out, int64_t bs,
-                 int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream));
-}
-int dg_rope_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out, int64_t bs,
-                     int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream).per_sequence());
-}
-int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
-                        int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream));
-}
-int dg_rope_attn_online_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
-                            int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream).per_sequence());
-}
-int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
-                       void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int nsplit,
-                       int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit));
-}
-int dg_rope_attn_split_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* out,
-                           void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int nsplit,
-                           int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).per_sequence());
-}
-int dg_rope_attn_split_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
-                           void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                           float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp));
-}
-int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
-                               void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                               float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).per_sequence());
-}
-
-int dg_rope_attn_online_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
-                            void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                            float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online());
-}
-int dg_rope_attn_online_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache, void* k_exp,
-                                void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                                float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_cache, v_cache, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online().per_sequence());
-}
-
-int dg_rope_attn_online_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
-                              void* v_pool, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages,
-                              float scale, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_online_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                     .paged(table, page_size, num_pages));
-}
-int dg_rope_attn_split_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
-                             void* v_pool, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                             int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype, int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).paged(table, page_size, num_pages));
-}
-
-int dg_rope_attn_online_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table, void* k_pool,
-                                  void* v_pool, void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl,
-                                  int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype,
-                                  int device, tg_stream_t stream) {
-  return rope_attn_split_launch(attn_call(qkv, cos, sin, pos, k_pool, v_pool, out, bs, hl, kvl, d, max_seq, scale, dtype, device, stream)
-                                    .split(scratch, scratch_bytes, nsplit).mx8(k_exp, v_exp).online().paged(table, page_size, num_pages));
+int dg_attn_launch(const dg_attn* call, int device, tg_stream_t stream) {
+  if (!call) return TG_E_NULL;
+  if (call->struct_bytes != sizeof(dg_attn)) return TG_E_STRUCT;
+  if (!attn_flavour(call->kernel, call->flags)) return TG_E_LAYOUT;
+  const dg_attn c = attn_used_fields(*call);
+  switch (c.kernel) {
+    case DG_ATTN_GENERAL: return rope_attn_launch(c, device, stream);
+    case DG_ATTN_ONLINE: return rope_attn_online_launch(c, device, stream);
+    case DG_ATTN_SPLIT: return rope_attn_split_launch(c, device, stream);
+    default: return prefill_launch(c, device, stream);
+  }
 }
 
 int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit) { return split_scratch(bs, hl, d, nsplit).bytes; }

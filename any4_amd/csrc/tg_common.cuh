@@ -15,14 +15,14 @@
 //   tg_tile.hip        w4_gemm_tile_kernel       (w4_gemm_tile.cuh)
 //   tg_dx.hip          w4_gemm_dx_kernel         (w4_gemm_dx.cuh)          the input gradient dX = dY . W (tg_gemm_w4_dx)
 //   tg_dq.hip          w4_gemm_dq_kernel         (w4_gemm_dq.cuh)          the gradients of scales, zeros and LUT (tg_gemm_w4_dq)
-//   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (dg_prefill_attn)
+//   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (DG_ATTN_PREFILL)
 //   tg_sample.hip      sample_kernel             (sample.cuh)              temperature / top-k / top-p sampling of the logits (dg_sample)
 //   tg_lora.hip        lora_shrink_kernel, lora_expand_kernel (lora.cuh)   per-sequence LoRA adapters on a linear's output (dg_lora_shrink / dg_lora_expand)
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.
-// attn_call.cuh is the attention side's GemmParams: one attention call of the decode stack (AttnCall, host-only), its validation for all
-// five kinds of entry point (check_attn) and the split kernels' scratch layout (split_scratch); included by decode_glue.cuh and tg_prefill.hip.
+// attn_call.cuh is the attention side's GemmParams: what the library does with one attention call of the decode stack (dg_attn, the public struct): the accepted
+// (kernel, flags) pairs, its validation for all five kinds of kernel (check_attn) and the split kernels' scratch layout (split_scratch); included by decode_glue.cuh and tg_prefill.hip.
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once

@@ -154,9 +154,9 @@ const char* tg_error_string(int code) {
     case TG_E_DEVICE: return "could not select the requested device";
     case TG_E_SIZE: return "an operand is too large for the kernels' 32-bit byte offsets (activations, packed weights or quantisation info of one problem must stay below 2 GiB; at most 65535 16-row activation tiles)";
     case TG_E_INTERNAL: return "internal error: a kernel that addresses LDS from offset 0 was built with static LDS";
-    case TG_E_STRUCT: return "tg_w4_gemm.struct_bytes must be sizeof(struct tg_w4_gemm) of the header the caller was built with (at least the ABI-1 prefix, at most this library's struct)";
+    case TG_E_STRUCT: return "tg_w4_gemm.struct_bytes must be sizeof(struct tg_w4_gemm) of the header the caller was built with (at least the ABI-1 prefix, at most this library's struct); dg_attn.struct_bytes must be this library's sizeof(struct dg_attn)";
     case TG_E_FUSION: return "no kernel with the requested fused stage (norm_weight / epilogue) for this problem: run that stage as its own launch (include/decode_glue_hip.h)";
-    case TG_E_LAYOUT: return "fragment-order activations / outputs (x_layout, y_layout) are not available for this problem: convert with tg_convert_{from,to}_A16 around a row-major call";
+    case TG_E_LAYOUT: return "no kernel for this layout / cache layout: fragment-order activations / outputs (x_layout, y_layout) are not available for this problem (convert with tg_convert_{from,to}_A16 around a row-major call), or dg_attn names a (kernel, flags) pair that DG_ATTN_FLAVOURS does not list";
     default: return code > 0 ? hipGetErrorString((hipError_t)code) : "unknown tinygemm error";
   }
 }

@@ -204,7 +204,7 @@ def _rope(x, cos, sin):
 
 
 def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl: int, kvl: int, d: int, T: int, k_exp=None, v_exp=None):
-    """Plain-torch formulation of a prefill chunk's attention (what dg_prefill_attn is tested against; also the CPU path).
+    """Plain-torch formulation of a prefill chunk's attention (what the prefill kernel, DG_ATTN_PREFILL of dg_attn_launch, is tested against; also the CPU path).
     qkv [bs * T, (hl + 2 kvl) d], row b * T + t = token t of sequence b at position p0 + t.  Ropes q and k with the table rows
     [p0, p0 + T), writes the T k / v rows into the caches and attends over cache[:, :, :p0 + T] with the mask s > p0 + t; rounding
     points as in DecodeLayer.forward: 16-bit score matmul, f32 scale + softmax, 16-bit probabilities, 16-bit P.V.
@@ -230,7 +230,7 @@ def prefill_attention_torch(qkv, cos_tab, sin_tab, p0: int, k_cache, v_cache, hl
 
 def prefill_attention_torch_seq(qkv, cos_tab, sin_tab, positions, lengths, slots, k_cache, v_cache, hl: int, kvl: int, d: int, T: int,
                                 k_exp=None, v_exp=None):
-    """prefill_attention_torch with a position, a length and a cache slot per sequence, all on the host (what dg_prefill_attn_seq is
+    """prefill_attention_torch with a position, a length and a cache slot per sequence, all on the host (what its DG_ATTN_SEQ flavour is
     tested against; also the CPU path).  qkv [n * T, (hl + 2 kvl) d], rows padded to the common T: sequence i has `lengths[i]` tokens
     from position `positions[i]` on and lives in k_cache[slots[i]] / v_cache[slots[i]].  Every sequence gets its own rope rows, its
     own cache rows and its own mask; a padding row writes nothing, is seen by nobody and its context row is zero.  A batch in which
@@ -518,9 +518,9 @@ class DecodeStack(torch.nn.Module):
         capture, prefill, ragged decode and generate work unchanged on top, TP too (the caches are per rank).  In fp16, k / v values
         beyond fp16's range are out of contract.
         mx8_attention (kv_cache="mx8"): which kernel a fused decode step launches -- "split" (the default): the 256-thread split kernel,
-        a thread per key row; "online": the one-barrier kernel's 8-bit flavour (dg_rope_attn_online_mx8: rows across lanes, the first
+        a thread per key row; "online": the one-barrier kernel's 8-bit flavour (DG_ATTN_ONE_BARRIER: rows across lanes, the first
         chunk requested before the position is known; a fused stack needs head_dim 64 / 128), with the same split count and scratch.
-        A paged mx8 stack (kv_pages) accepts either value and always runs the one-barrier kernel (dg_rope_attn_online_mx8_paged): it is
+        A paged mx8 stack (kv_pages) accepts either value and always runs the one-barrier kernel (the same flag on paged pools): it is
         the only decode attention kernel with a paged flavour.
         Prefill and the plain-torch path are the same for both.
         ragged: a position per sequence.  `decode` takes `bs` positions (-1: the sequence is inactive and writes nothing), `prefill`

@@ -7,6 +7,8 @@ allocator, current stream) and launches on `torch.cuda.current_stream()`; they a
 """
 from __future__ import annotations
 
+import ctypes
+
 import torch
 
 from . import _lib
@@ -107,9 +109,9 @@ def _mx8_exps(what, k_cache, v_cache, k_exp, v_exp, d):
 
 
 def _paged(what, table, k_pool, v_pool, kvl, d, exps=()):
-    """The paging arguments of a `_paged` launch, checked: `table` int32 [cache_bs, max_seq / page_size] on the pools' device, the pools
+    """The paging fields of a DG_ATTN_PAGED launch, checked: `table` int32 [cache_bs, max_seq / page_size] on the pools' device, the pools
     [num_pages, kvl, page_size, d] in a 16-bit type -- or, with exps = (k_exp, v_exp) (checked already: _mx8_pools), float8_e4m3fn codes of
-    an `_mx8_paged` launch.  Returns them by argument name, with max_seq (the exponents go in with every mx8 call: _attn_launch)."""
+    a paged mx8 launch.  Returns them by field name (the pools are the call's k_cache / v_cache), with max_seq (the exponents go in with every mx8 call: _attn_launch)."""
     if table.dtype != torch.int32 or table.dim() != 2 or k_pool.dim() != 4 or k_pool.shape != v_pool.shape or k_pool.dtype != v_pool.dtype or \
             tuple(k_pool.shape[1::2]) != (kvl, d):
         raise RuntimeError(f"{what}: table must be int32 [cache_bs, max_seq / page_size] and the pools [num_pages, {kvl}, page_size, {d}], got "
@@ -117,7 +119,7 @@ def _paged(what, table, k_pool, v_pool, kvl, d, exps=()):
     if not exps and k_pool.dtype not in (torch.bfloat16, torch.float16):
         raise RuntimeError(f"{what}: a paged cache holds 16-bit rows, got {k_pool.dtype}")
     num_pages, _, page_size, _ = k_pool.shape
-    return dict(table=table, k_pool=k_pool, v_pool=v_pool, page_size=page_size, num_pages=num_pages, max_seq=table.shape[1] * page_size)
+    return dict(table=table, k_cache=k_pool, v_cache=v_pool, page_size=page_size, num_pages=num_pages, max_seq=table.shape[1] * page_size)
 
 
 def _mx8_pools(what, k_pool, v_pool, k_exp, v_exp, d):
@@ -129,29 +131,40 @@ def _mx8_pools(what, k_pool, v_pool, k_exp, v_exp, d):
     return exps
 
 
-def _attn_launch(base, seq, exps, qkv, paged=False, kv8_online=False, **values):
-    """One launch of an attention entry point: _lib.attn_signature names the flavour of `base` (seq: `_seq`; exps = (k_exp, v_exp) of an
-    mx8 cache: `_mx8`; paged: `_paged`) and the order of its arguments; `values` are given by argument name, tensors (or None) for
-    pointers.  qkv also supplies dtype, device and stream.  kv8_online: dg_rope_attn_online_mx8(_seq), _lib.kv8_online_signature; exps
-    and paged: the `_mx8_paged` entry point of `base`, _lib.paged_mx8_signature."""
-    if exps and paged:
-        entry, args = _lib.paged_mx8_signature(base)
-    else:
-        entry, args = _lib.kv8_online_signature(seq) if kv8_online else _lib.attn_signature(base, seq, bool(exps), paged)
-    values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv, dtype=_dt(qkv), device=qkv.device.index, stream=_stream(qkv))
-    ptr = lambda v: v.data_ptr() if isinstance(v, torch.Tensor) else v
-    _lib.check(getattr(_lib.load(), entry)(*[ptr(values[name]) for name, _ in args]), entry)
+def _attn_flags(per_sequence, exps, table, one_barrier=False):
+    """The flag word of a call: what its caches are and how `pos` is read, said explicitly (the library infers nothing)"""
+    return ((_lib.DG_ATTN_SEQ if per_sequence else 0) | (_lib.DG_ATTN_MX8 if exps else 0) | (_lib.DG_ATTN_PAGED if table is not None else 0)
+            | (_lib.DG_ATTN_ONE_BARRIER if one_barrier else 0))
 
 
-def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=(), table=None,
-               kv8_online=False):
-    """rope_attn / rope_attn_online / rope_attn_split: three kernels behind one argument list (per_sequence: their _seq entry points,
-    `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache: the _mx8 entry points; table: the
-    caches are page pools behind this block table: the _paged entry points (per sequence); kv8_online: rope_attn_online_mx8 (split and
-    exps given, base dg_rope_attn_online); exps and table: rope_attn_online_mx8_paged (split given, base dg_rope_attn_online)."""
+def _attn_name(kernel, flags):
+    """The call's name in messages: the one it has in the header's table of accepted calls"""
+    return _lib.ATTN_FLAVOURS.get((kernel, flags), "dg_attn_launch")
+
+
+def _attn_launch(kernel, flags, exps, qkv, **values):
+    """One dg_attn_launch: `values` are fields of _lib.Attn by name, tensors (or None) for pointers; exps = (k_exp, v_exp) of an mx8 cache,
+    or ().  qkv also supplies dtype, device and stream."""
+    values.update(zip(("k_exp", "v_exp"), exps), qkv=qkv)
+    call = _lib.Attn(kernel=kernel, flags=flags, dtype=_dt(qkv),
+                     **{name: v.data_ptr() if isinstance(v, torch.Tensor) else v for name, v in values.items()})
+    rc = _lib.load().dg_attn_launch(ctypes.byref(call), qkv.device.index, _stream(qkv))
+    if rc != 0:
+        _lib.check(rc, _attn_name(kernel, flags))
+
+
+def _rope_attn(kernel, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence=False, out=None, split=None, exps=(), table=None,
+               one_barrier=False):
+    """rope_attn / rope_attn_online / rope_attn_split: three kernels (_lib.DG_ATTN_GENERAL / ONLINE / SPLIT) behind one argument list
+    (per_sequence: DG_ATTN_SEQ, `pos` [bs]).  split = (scratch, nsplit) of rope_attn_split; exps = (k_exp, v_exp) of an mx8 cache:
+    DG_ATTN_MX8; table: the caches are page pools behind this block table: DG_ATTN_PAGED (per sequence); one_barrier: DG_ATTN_ONE_BARRIER,
+    rope_attn_online_mx8 and rope_attn_online_mx8_paged (split and exps given, kernel DG_ATTN_SPLIT)."""
     scratch, nsplit = split if split is not None else (None, None)
     out, bs, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, scratch, table, *exps, out=out)
-    what = base + ("_mx8" if exps else "") + ("_paged" if table is not None else "")
+    flags = _attn_flags(per_sequence, exps, table, one_barrier)
+    # the prefix of the messages below is the flavour's name without `_seq`, as it always was (a paged flavour has no such suffix: it
+    # is per sequence by definition).  Every public function above gives a pair of the table; _attn_name's fallback is for none of them.
+    what = _attn_name(kernel, flags & ~_lib.DG_ATTN_SEQ if table is None else flags)
     if out.shape != (bs, hl * d) or out.dtype != qkv.dtype:
         raise RuntimeError(f"{what}: out must be [{bs}, {hl * d}] {qkv.dtype}")
     if per_sequence:
@@ -163,8 +176,7 @@ def _rope_attn(base, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, pe
         more.update(_paged(what, table, k_cache, v_cache, kvl, d, exps))
     else:
         more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
-    _attn_launch(base, per_sequence, exps, qkv, table is not None, kv8_online, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d,
-                 scale=float(scale), **more)
+    _attn_launch(kernel, flags, exps, qkv, cos=cos, sin=sin, pos=pos, out=out, bs=bs, hl=hl, kvl=kvl, d=d, scale=float(scale), **more)
     return out
 
 
@@ -174,7 +186,7 @@ def rope_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torc
     """rope_kv + decode_attn in one launch: qkv [bs, (hl + 2 kvl) d] -> context [bs, hl * d]; caches updated at `pos`.
     per_sequence: `pos` is int64 [bs], sequence b sits at pos[b]; a sequence whose position is outside [0, max_seq) writes nothing
     and leaves its row of `out` (allocated here, uninitialised, unless given) as it was."""
-    return _rope_attn("dg_rope_attn", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
+    return _rope_attn(_lib.DG_ATTN_GENERAL, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
 
 
 def rope_attn_online(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor,
@@ -182,7 +194,7 @@ def rope_attn_online(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, po
                      out: torch.Tensor = None) -> torch.Tensor:
     """rope_attn built for latency (head_dim 64 / 128): one barrier, every load issued up front, softmax statistics combined
     flash-decoding style -- the same caches bit for bit, the output within 16-bit rounding of rope_attn's.  per_sequence: as rope_attn."""
-    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
+    return _rope_attn(_lib.DG_ATTN_ONLINE, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out)
 
 
 def rope_attn_split_scratch(bs: int, hl: int, d: int, nsplit: int, device) -> torch.Tensor:
@@ -198,7 +210,7 @@ def rope_attn_split(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos
     per_sequence, out: as rope_attn.  float8_e4m3fn caches with `k_exp`, `v_exp` (uint8 [bs, kvl, max_seq, d / 32]) are an mx8 cache
     (any4_amd/kvcache.py): the mx8 entry points, which also take nsplit = 1."""
     exps = _mx8_exps("rope_attn_split", k_cache, v_cache, k_exp, v_exp, d)
-    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps)
+    return _rope_attn(_lib.DG_ATTN_SPLIT, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps)
 
 
 def rope_attn_online_mx8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
@@ -211,8 +223,8 @@ def rope_attn_online_mx8(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor
     exps = _mx8_exps("rope_attn_online_mx8", k_cache, v_cache, k_exp, v_exp, d)
     if not exps:
         raise RuntimeError(f"rope_attn_online_mx8: the caches must be float8_e4m3fn (mx8), got {k_cache.dtype}; 16-bit caches: rope_attn_online / rope_attn_split")
-    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps,
-                      kv8_online=True)
+    return _rope_attn(_lib.DG_ATTN_SPLIT, qkv, cos, sin, pos, k_cache, v_cache, hl, kvl, d, scale, per_sequence, out, (scratch, nsplit), exps,
+                      one_barrier=True)
 
 
 def rope_attn_online_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor,
@@ -220,14 +232,14 @@ def rope_attn_online_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tens
     """rope_attn_online(per_sequence=True) on a paged cache: pools [num_pages, kvl, page_size, d] behind `table` int32 [bs, max_seq /
     page_size] on the device -- position p of sequence b is row p % page_size of page table[b, p // page_size] (-1: unmapped).  An entry
     outside the pool is read as page 0 and never written through."""
-    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, table=table)
+    return _rope_attn(_lib.DG_ATTN_ONLINE, qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, table=table)
 
 
 def rope_attn_split_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
                           v_pool: torch.Tensor, hl: int, kvl: int, d: int, scale: float, scratch: torch.Tensor, nsplit: int,
                           out: torch.Tensor = None) -> torch.Tensor:
     """rope_attn_split(per_sequence=True) on a paged cache (rope_attn_online_paged): the one-barrier kernel with nsplit blocks per head."""
-    return _rope_attn("dg_rope_attn_split", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), table=table)
+    return _rope_attn(_lib.DG_ATTN_SPLIT, qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), table=table)
 
 
 def prefill_attn_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
@@ -245,7 +257,8 @@ def rope_attn_online_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.
     [num_pages, kvl, page_size, d / 32] behind the one `table` (rope_attn_online_paged).  Always the one-barrier kernel, `nsplit` blocks per
     head (1 ... 64; `scratch` as for rope_attn_split); bytes written and output are rope_attn_online_mx8's on caches holding the same rows."""
     exps = _mx8_pools("rope_attn_online_mx8_paged", k_pool, v_pool, k_exp, v_exp, d)
-    return _rope_attn("dg_rope_attn_online", qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), exps, table)
+    return _rope_attn(_lib.DG_ATTN_SPLIT, qkv, cos, sin, pos, k_pool, v_pool, hl, kvl, d, scale, True, out, (scratch, nsplit), exps, table,
+                      one_barrier=True)
 
 
 def prefill_attn_mx8_paged(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, table: torch.Tensor, k_pool: torch.Tensor,
@@ -292,7 +305,7 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
         more.update(_paged("prefill_attn_mx8_paged" if exps else "prefill_attn_paged", table, k_cache, v_cache, kvl, d, exps))
     else:
         more.update(k_cache=k_cache, v_cache=v_cache, max_seq=max_seq)
-    _attn_launch("dg_prefill_attn", per_sequence, exps, qkv, table is not None, cos=cos, sin=sin, pos=pos, out=out, bs=rows // T, T=T,
+    _attn_launch(_lib.DG_ATTN_PREFILL, _attn_flags(per_sequence, exps, table), exps, qkv, cos=cos, sin=sin, pos=pos, out=out, bs=rows // T, T=T,
                  hl=hl, kvl=kvl, d=d, scale=float(scale), **more)
     return out
 

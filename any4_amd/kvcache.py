@@ -5,7 +5,7 @@ point at each.
 
 The `mx8` KV-cache format of the decode stack: block-scaled 8-bit rows (OCP MXFP8: E4M3 elements, one E8M0 exponent byte per 32
 consecutive elements of a row).  Plain torch, CPU and GPU; `mx8_encode` IS the definition of the format -- the HIP writers
-(dg_rope_attn_split_mx8, dg_prefill_attn_mx8 and their _seq forms) reproduce its bytes, the readers compute `mx8_decode`.
+(the DG_ATTN_MX8 flavours of dg_attn_launch) reproduce its bytes, the readers compute `mx8_decode`.
 
 Per block of 32 elements (values taken as f32):
     amax = max|x| = m * 2^ex, m in [0.5, 1)                          (torch.frexp)
@@ -26,7 +26,7 @@ import operator
 
 import torch
 
-from . import decode_ops as G  # (binds nothing of the library until a kernel is launched)
+from . import _lib, decode_ops as G  # (binds nothing of the library until a kernel is launched)
 
 BLOCK = 32
 F8 = torch.float8_e4m3fn
@@ -190,16 +190,17 @@ class KVCache(torch.nn.Module):
             # (by its public name, the only launch made that way: tests/test_gpu_kv8_online.py counts the steps that go through it)
             return G.rope_attn_online_mx8(qkv, cos_tab, sin_tab, pos, k, v, *exps, hl, kvl, d, 1.0 / math.sqrt(d), *split,
                                           per_sequence=per_sequence)
-        if (self.mx8 and self.paged) or (split is None and d in (64, 128)):
-            base = "dg_rope_attn_online"
+        if split is None:
+            kernel = _lib.DG_ATTN_ONLINE if d in (64, 128) else _lib.DG_ATTN_GENERAL
         else:
-            base = "dg_rope_attn" if split is None else "dg_rope_attn_split"
-        return G._rope_attn(base, qkv, cos_tab, sin_tab, pos, k, v, hl, kvl, d, 1.0 / math.sqrt(d), per_sequence, split=split, exps=exps,
-                            table=self.table)
+            kernel = _lib.DG_ATTN_SPLIT
+        # (paged mx8 pools: the one-barrier kernel is the only decode kernel with that flavour)
+        return G._rope_attn(kernel, qkv, cos_tab, sin_tab, pos, k, v, hl, kvl, d, 1.0 / math.sqrt(d), per_sequence, split=split, exps=exps,
+                            table=self.table, one_barrier=self.mx8 and self.paged)
 
     def prefill_attention(self, qkv, pos, cos_tab, sin_tab, hl: int, T=None, lengths=None, slots=None, per_sequence: bool = False):
         """A chunk of T tokens per sequence (row b * T + t; default T = rows / the cache's batch), token 0 at `pos` [1]: T cache rows
-        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device (dg_prefill_attn_seq); the context rows of tokens
+        appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device (DG_ATTN_SEQ); the context rows of tokens
         that do not exist are zero."""
         k, v = self.k, self.v
         _, kvl, _, d = k.shape

@@ -1,7 +1,8 @@
 """What the C ABI answers over a grid of calls, as a digest (developer tool; needs no GPU: the planner and all validation run before any HIP call):
     python dev/plan_sweep.py [--lib PATH/libtinygemm_hip.so] [--quick]     the planner: workspace bytes and kernel family of every case
-    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...]           return codes of N broken structs per GEMM entry point, then of
-                                                                           N // 25 broken argument lists per attention entry point (dg_*)
+    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...] [--abi8]  return codes of N broken structs per GEMM entry point, then of
+                                                                           N // 25 broken calls of dg_decode_attn and of each of the
+                                                                           nineteen accepted calls of dg_attn_launch
 Prints the number of cases, a histogram of the answers and a sha256 over their sequence.  Two builds route / validate alike when they
 print the same digest for the same script; run it before and after a change of the host launch path (or with --lib on an older build).
 No digest is recorded anywhere: a performance change may move the routing on purpose.
@@ -24,6 +25,7 @@ ap.add_argument("--lib", default=L.LIB_PATH)
 ap.add_argument("--quick", action="store_true", help="a 1/96 sub-grid of the planner sweep")
 ap.add_argument("--errors", nargs="?", type=int, const=100000, default=0, metavar="N")
 ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--abi8", action="store_true", help="--errors: --lib is a build up to ABI 8; make the attention calls through its positional entry points")
 opt = ap.parse_args()
 lib = ctypes.CDLL(opt.lib)
 P = ctypes.POINTER(L.W4Gemm)
@@ -148,7 +150,7 @@ def errors(n):
         report(name, out)
 
 
-# ---- the attention entry points of include/decode_glue_hip.h: start from a valid argument list, break none, one or two arguments ----
+# ---- the attention calls of include/decode_glue_hip.h: start from a valid call, break none, one or two fields ----
 # Every call names NO_DEVICE, so one that passes validation answers TG_E_DEVICE from DeviceScope (tg_common.cuh: hipGetDevice fails, or
 # hipSetDevice of an index no machine has) in front of everything that touches the GPU.  Any other non-negative answer ends the sweep.
 _I31 = (1 << 31) - 1
@@ -162,24 +164,51 @@ ATTN_BREAKS = {
     "max_seq": (0, -1, 1, 4096, 8192, 8193, 65536, 65537, (1 << 24) - 1, 1 << 24, (1 << 25) - 1, 1 << 25),  # ... * d * 2 < 2^32 at d = 128 / 64
     "nsplit": (0, -1, 1, 4, 64, 65),
     "scratch_bytes": (0, -1, -4, 16),                                          # relative to what the (broken) sizes need
+    "page_size": (0, -64, 32, 48, 64, 96, 128, 4096, 8192), "num_pages": (0, -1, 1, 5, _I31, _I31 + 1),
 }
 
 
 def attn_valid(names):
-    v = dict(bs=2, T=16, cache_bs=2, hl=8, kvl=2, d=128, max_seq=4096, scale=0.125, nsplit=4, dtype=0, device=NO_DEVICE, stream=None, scratch_bytes=0)
+    v = dict(bs=2, T=16, cache_bs=2, hl=8, kvl=2, d=128, max_seq=4096, scale=0.125, nsplit=4, dtype=0, device=NO_DEVICE, stream=None, scratch_bytes=0,
+             page_size=64, num_pages=5)
     v.update((name, (i + 1) * BASE) for i, name in enumerate(n for n in names if n not in v))  # the pointers
     return v
 
 
+DECODE_ATTN = ("qkv", "k_cache", "v_cache", "pos", "out", "bs", "hl", "kvl", "d", "max_seq", "scale", "dtype", "device", "stream")
+INT64 = ("scratch_bytes", "bs", "T", "cache_bs", "max_seq", "page_size", "num_pages")
+
+
+def draw_order(kernel, flags):
+    """The argument order this call had as a positional entry point up to ABI 8.  The sweep hands out pointers and draws what to break in
+    this order, so its digests are those recorded for that ABI (profiles/attn_call_refactor_checks.txt), and --abi8 can still make the call."""
+    prefill, split, seq, mx8, paged = kernel == L.DG_ATTN_PREFILL, kernel == L.DG_ATTN_SPLIT, flags & L.DG_ATTN_SEQ, flags & L.DG_ATTN_MX8, flags & L.DG_ATTN_PAGED
+    return (["qkv", "cos", "sin", "pos"] + (["len", "slot"] if prefill and seq else []) + (["table"] if paged else []) + ["k_cache", "v_cache"]
+            + (["k_exp", "v_exp"] if mx8 else []) + ["out"] + (["scratch", "scratch_bytes"] if split else []) + ["bs"] + (["T"] if prefill else [])
+            + (["cache_bs"] if prefill and seq else []) + ["hl", "kvl", "d", "max_seq"] + (["page_size", "num_pages"] if paged else []) + ["scale"]
+            + (["nsplit"] if split else []) + ["dtype", "device", "stream"])
+
+
 def attn_errors(n):
-    decode_attn = ("dg_decode_attn", tuple((name, None) for name in ("qkv", "k_cache", "v_cache", "pos", "out", "bs", "hl", "kvl", "d", "max_seq", "scale",
-                                                                      "dtype", "device", "stream")))
-    entries = [decode_attn] + [L.attn_signature(base, seq, mx8) for base, has_mx8 in L.ATTN_BASES.items() for seq in (False, True)
-                               for mx8 in ((False, True) if has_mx8 else (False,))]
-    for e, (entry, args) in enumerate(entries):
-        names = [name for name, _ in args]
-        fn = getattr(lib, entry)
-        fn.argtypes = L.SYMBOLS[entry]
+    """dg_decode_attn, then the nineteen accepted calls of dg_attn_launch: first the twelve that were swept as positional entry points (base
+    by base, scalar / per sequence, 16-bit / mx8), then the paged, the one-barrier mx8 and the paged mx8 ones.  --abi8: the same argument
+    lists through the positional symbols of a build up to ABI 8 (--lib), which is how two such builds are compared."""
+    twelve = [(k, (L.DG_ATTN_SEQ if seq else 0) | (L.DG_ATTN_MX8 if mx8 else 0))
+              for k, has_mx8 in ((L.DG_ATTN_GENERAL, False), (L.DG_ATTN_ONLINE, False), (L.DG_ATTN_SPLIT, True), (L.DG_ATTN_PREFILL, True))
+              for seq in (False, True) for mx8 in ((False, True) if has_mx8 else (False,))]
+    pairs = twelve + [p for p in L.ATTN_FLAVOURS if p[1] & L.DG_ATTN_PAGED and not p[1] & L.DG_ATTN_MX8] + \
+        [p for p in L.ATTN_FLAVOURS if p[1] & L.DG_ATTN_ONE_BARRIER and not p[1] & L.DG_ATTN_PAGED] + \
+        [p for p in L.ATTN_FLAVOURS if p[1] & L.DG_ATTN_PAGED and p[1] & L.DG_ATTN_MX8]
+    assert len(pairs) == len(set(pairs)) == 19
+    if not opt.abi8:
+        lib.dg_attn_launch.argtypes = [ctypes.POINTER(L.Attn), ctypes.c_int, ctypes.c_void_p]
+    for e, pair in enumerate([None] + pairs):
+        entry = "dg_decode_attn" if pair is None else L.ATTN_FLAVOURS[pair]
+        names = list(DECODE_ATTN) if pair is None else draw_order(*pair)
+        if pair is None or opt.abi8:
+            fn = getattr(lib, entry)
+            fn.argtypes = [ctypes.c_int64 if a in INT64 else ctypes.c_float if a == "scale" else ctypes.c_int if a in ATTN_BREAKS or a == "device"
+                           else ctypes.c_void_p for a in names]
         pointers = [name for name in attn_valid(names) if name not in ATTN_BREAKS and name not in ("scale", "device", "stream")]
         fields = sorted(set(names) & set(ATTN_BREAKS)) + pointers
         rng = random.Random(1000 * opt.seed + 100 + e)
@@ -194,7 +223,11 @@ def attn_errors(n):
                     v[f] = rng.choice(ATTN_BREAKS[f]) if f in ATTN_BREAKS else rng.choice((None, v[f] + 4, v[f] + 8, v[f]))
             heads = v["bs"] * v["hl"]
             v["scratch_bytes"] = max(-(1 << 62), min(1 << 62, (heads * 4 + 15) // 16 * 16 + heads * v["nsplit"] * (v["d"] + 2) * 4 + slack))
-            rc = fn(*[v[name] for name in names])
+            if pair is None or opt.abi8:
+                rc = fn(*[v[name] for name in names])
+            else:
+                call = L.Attn(kernel=pair[0], flags=pair[1], **{name: v[name] for name in names if name not in ("device", "stream")})
+                rc = lib.dg_attn_launch(ctypes.byref(call), v["device"], v["stream"])
             if rc >= 0:
                 sys.exit(f"{entry}: answer {rc} to {v}: a call of this sweep got past DeviceScope")
             out.append(rc)

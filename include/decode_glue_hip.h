@@ -1,5 +1,5 @@
 /* decode_glue_hip.h -- C ABI of the non-GEMM kernels of the decode stack: one decode step (one new token per sequence,
- * SURVEY.md 8f row N2) and the prompt prefill in front of it (dg_prefill_attn: a chunk of tokens per sequence).
+ * SURVEY.md 8f row N2) and the prompt prefill in front of it (DG_ATTN_PREFILL: a chunk of tokens per sequence).
  *
  * Not part of the tinygemm drop-in boundary (include/tinygemm_hip.h).  The reference times model-level
  * decode through HuggingFace `transformers` (benchmark.py:113-215 -> LlamaDecoderLayer, an external
@@ -10,9 +10,9 @@
  *   dg_add_rmsnorm   h' = h + delta;  y = rmsnorm(h') * w          (residual add + LlamaRMSNorm)
  *   dg_rope_kv       rotary embedding of q and k, k/v written into the static KV cache at *pos
  *   dg_decode_attn   grouped-query attention of one new token against cache[0 .. *pos]
- *   dg_rope_attn     the two above fused (what the decode harness launches)
+ *   dg_attn_launch   the two above fused (what the decode harness launches), and a chunk of T tokens: rotary embedding, T cache rows
+ *                    appended, causal flash attention over cache + chunk -- one call struct for every kernel and cache layout
  *   dg_swiglu        silu(gate) * up
- *   dg_prefill_attn  a chunk of T tokens: rotary embedding, T cache rows appended, causal flash attention over cache + chunk
  *
  * Conventions are those of include/tinygemm_hip.h: raw device pointers, caller-owned outputs, explicit
  * stream, no allocation, no host sync, graph-capturable (`pos` is read on the device, so a captured graph
@@ -53,33 +53,6 @@ TG_API int dg_decode_attn(const void* q, const void* k_cache, const void* v_cach
                           int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
                           tg_stream_t stream);
 
-/* dg_rope_kv followed by dg_decode_attn in ONE launch (a hipGraph of dependent kernels advances at ~5 us per node on
- * MI355X): same arguments, same arithmetic in the same order, bit-identical results; q is not
- * materialised.  d % 8 == 0, d <= 256, max_seq <= 8192. */
-TG_API int dg_rope_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                        void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                        int dtype, int device, tg_stream_t stream);
-
-/* dg_rope_attn for latency (what the decode harness launches at d = 64 / 128): every load of the launch is issued behind the read
- * of `pos`, scores are reduced with DPP, the softmax statistics are kept per row group and combined once (flash-decoding style,
- * ONE barrier), so probabilities are normalised after the value contraction: the cache rows written are bit-identical to
- * dg_rope_kv's, the output agrees with dg_rope_attn within 16-bit rounding.  qkv and the rotary tables 16-byte aligned. */
-TG_API int dg_rope_attn_online(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                               void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                               int dtype, int device, tg_stream_t stream);
-
-/* dg_rope_attn with the sequence split over `nsplit` blocks per head (flash-decoding style combine by the last block to
- * arrive): fills the GPU at batch 1 and long contexts.  With d = 64 / 128 (and 16-byte aligned qkv / tables) it is
- * dg_rope_attn_online's one-barrier kernel with gridDim.y = nsplit: block c of a head takes the 32-row iterations c, c + nsplit,
- * ... of the context; what crosses blocks goes through agent-scope atomics, not through a device-scope fence.  `scratch`: dg_rope_attn_split_scratch_bytes(...) bytes, 16-byte
- * aligned, ZEROED ONCE by the caller before the first launch (the kernel leaves its counters at zero again); launches
- * sharing a scratch buffer must be stream-ordered.  Probabilities are normalised after the value contraction, so results
- * agree with dg_rope_attn within 16-bit rounding, not bit for bit.  max_seq / nsplit <= ~15000. */
-TG_API int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit);
-TG_API int dg_rope_attn_split(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                              void* v_cache, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                              int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-
 /* out[b][j] = to16(silu(gu[b][j])) * gu[b][il + j], j < il; gu [bs][2 il]; il % 8 == 0. */
 TG_API int dg_swiglu(const void* gu, void* out, int64_t bs, int64_t il, int dtype, int device, tg_stream_t stream);
 
@@ -88,159 +61,196 @@ TG_API int dg_swiglu(const void* gu, void* out, int64_t bs, int64_t il, int dtyp
  * keeps its GEMM); x and w 16-byte aligned. */
 TG_API int dg_linear16(const void* x, const void* w, void* y, int64_t m, int64_t n, int64_t k, int dtype, int device, tg_stream_t stream);
 
-/* A chunk of T new tokens per sequence.  qkv [bs * T][(hl + 2 kvl) * d], row b * T + t = token t of sequence b (q heads, k heads,
- * v heads, as in dg_rope_kv); *pos = p0 = sequence position of token 0 (int64 on the device, read by the kernel).
- *   k_cache[b][kv][p0 + t][:] = rope(k, p0 + t);  v_cache[b][kv][p0 + t][:] = v          -- the bits dg_rope_kv writes
- *   out[b * T + t][h * d ...] = softmax_{s <= p0 + t}( (rope(q) . k_cache[b][h / (hl/kvl)][s]) * scale ) applied to v_cache
- * i.e. token t sees the cache rows [0, p0) that earlier calls wrote and rows [p0, p0 + t] of its own chunk.  q is roped and rounded
- * to 16 bit like k; scores and softmax statistics in f32 (online softmax over 64-position tiles), probabilities rounded to 16 bit
- * for the value product, f32 accumulation, normalised once, one rounding of the output (dg_rope_attn_online's recipe).  Two
- * launches (cache append, then attention), no scratch memory, no atomics: a call repeated gives the same bits.
- * A token whose position p0 + t is outside [0, max_seq) writes no cache row, is seen by nobody and leaves its output row unwritten;
- * cache rows outside [p0, p0 + T) are not written, rows above a token's own position are not read.
- * d = 64 / 128, hl % kvl == 0, max_seq <= 8192, bs <= 65535 (TG_E_SHAPE otherwise); qkv, the tables, the caches and out 16-byte aligned. */
-TG_API int dg_prefill_attn(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                           void* out, int64_t bs, int64_t T, int hl, int kvl, int d, int64_t max_seq, float scale,
-                           int dtype, int device, tg_stream_t stream);
+/* ---- fused attention: one call struct (dg_attn), one entry point (dg_attn_launch) ----
+ * A call names its kernel (`kernel`, one of DG_ATTN_GENERAL / ONLINE / SPLIT / PREFILL) and says what its caches are and how `pos` is
+ * read (`flags`, DG_ATTN_SEQ | MX8 | PAGED | ONE_BARRIER).  Nothing is inferred from null pointers.  DG_ATTN_FLAVOURS below lists the
+ * nineteen accepted (kernel, flags) pairs under the names they had as functions of their own up to ABI 8 (any4_amd/decode_ops.py keeps
+ * those names for its functions, and the text below uses them for "the call with that pair").
+ *
+ * The four kernels, for 16-bit caches [bs][kvl][max_seq][d] and a scalar position (flags = 0):
+ *
+ * DG_ATTN_GENERAL (dg_rope_attn): dg_rope_kv followed by dg_decode_attn in ONE launch (a hipGraph of dependent kernels advances at ~5 us
+ *   per node on MI355X): same arithmetic in the same order, bit-identical results; q is not materialised.  d % 8 == 0,
+ *   d <= 256, max_seq <= 8192.
+ *
+ * DG_ATTN_ONLINE (dg_rope_attn_online): dg_rope_attn for latency (what the decode harness launches at d = 64 / 128): every load of the
+ *   launch is issued behind the read of `pos`, scores are reduced with DPP, the softmax statistics are kept per row group and combined
+ *   once (flash-decoding style, ONE barrier), so probabilities are normalised after the value contraction: the cache rows written are
+ *   bit-identical to dg_rope_kv's, the output agrees with dg_rope_attn within 16-bit rounding.  qkv and the rotary tables 16-byte aligned.
+ *
+ * DG_ATTN_SPLIT (dg_rope_attn_split): dg_rope_attn with the sequence split over `nsplit` blocks per head (flash-decoding style combine by
+ *   the last block to arrive): fills the GPU at batch 1 and long contexts.  With d = 64 / 128 (and 16-byte aligned qkv / tables) it is
+ *   dg_rope_attn_online's one-barrier kernel with gridDim.y = nsplit: block c of a head takes the 32-row iterations c, c + nsplit, ... of
+ *   the context; what crosses blocks goes through agent-scope atomics, not through a device-scope fence.  `scratch`:
+ *   dg_rope_attn_split_scratch_bytes bytes, 16-byte aligned, ZEROED ONCE by the caller before the first launch (the kernel leaves its
+ *   counters at zero again); launches sharing a scratch buffer must be stream-ordered.  Probabilities are normalised after the value
+ *   contraction, so results agree with dg_rope_attn within 16-bit rounding, not bit for bit.  max_seq / nsplit <= ~15000.
+ *
+ * DG_ATTN_PREFILL (dg_prefill_attn): a chunk of T new tokens per sequence.  qkv [bs * T][(hl + 2 kvl) * d], row b * T + t = token t of
+ *   sequence b (q heads, k heads, v heads, as in dg_rope_kv); *pos = p0 = sequence position of token 0 (int64 on the device, read by the
+ *   kernel).
+ *     k_cache[b][kv][p0 + t][:] = rope(k, p0 + t);  v_cache[b][kv][p0 + t][:] = v          -- the bits dg_rope_kv writes
+ *     out[b * T + t][h * d ...] = softmax_{s <= p0 + t}( (rope(q) . k_cache[b][h / (hl/kvl)][s]) * scale ) applied to v_cache
+ *   i.e. token t sees the cache rows [0, p0) that earlier calls wrote and rows [p0, p0 + t] of its own chunk.  q is roped and rounded to
+ *   16 bit like k; scores and softmax statistics in f32 (online softmax over 64-position tiles), probabilities rounded to 16 bit for the
+ *   value product, f32 accumulation, normalised once, one rounding of the output (dg_rope_attn_online's recipe).  Two launches (cache
+ *   append, then attention), no scratch memory, no atomics: a call repeated gives the same bits.  A token whose position p0 + t is
+ *   outside [0, max_seq) writes no cache row, is seen by nobody and leaves its output row unwritten; cache rows outside [p0, p0 + T) are
+ *   not written, rows above a token's own position are not read.  d = 64 / 128, hl % kvl == 0, max_seq <= 8192, bs <= 65535 (TG_E_SHAPE
+ *   otherwise); qkv, the tables, the caches and out 16-byte aligned. */
+enum {
+  DG_ATTN_GENERAL = 0,
+  DG_ATTN_ONLINE = 1,
+  DG_ATTN_SPLIT = 2,
+  DG_ATTN_PREFILL = 3
+};
 
-/* ---- a position per sequence (ragged batches) ----
- * dg_rope_attn_seq / dg_rope_attn_online_seq / dg_rope_attn_split_seq: their namesakes' argument lists, arithmetic, rounding points,
- * shape limits and scratch protocol, with `pos` an int64[bs] on the device: sequence b sits at pos[b] (one read per workgroup, as
- * `*pos` is).  A sequence whose pos[b] is outside [0, max_seq) -- an inactive batch slot, by convention -1 -- writes no cache row
- * and leaves its row of `out` unwritten, which is what the scalar entry points do for the whole batch.  For every other sequence
- * the cache rows and the output row are, bit for bit, those of the namesake called for that sequence alone. */
-TG_API int dg_rope_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                            void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                            int dtype, int device, tg_stream_t stream);
-TG_API int dg_rope_attn_online_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                                   void* v_cache, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq, float scale,
-                                   int dtype, int device, tg_stream_t stream);
-TG_API int dg_rope_attn_split_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache,
-                                  void* v_cache, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                  int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
+/* DG_ATTN_SEQ -- a position per sequence (ragged batches).  The decode kernels (the _seq flavours): their namesakes' arithmetic, rounding
+ *   points, shape limits and scratch protocol, with `pos` an int64[bs] on the device: sequence b sits at pos[b] (one read per workgroup,
+ *   as `*pos` is).  A sequence whose pos[b] is outside [0, max_seq) -- an inactive batch slot, by convention -1 -- writes no cache row and
+ *   leaves its row of `out` unwritten, which is what a scalar-position call does for the whole batch.  For every other sequence the cache
+ *   rows and the output row are, bit for bit, those of the namesake called for that sequence alone.
+ *   DG_ATTN_PREFILL (dg_prefill_attn_seq): position, length and cache slot per sequence.  qkv [bs * T][(hl + 2 kvl) * d]: row i * T + t =
+ *   token t of chunk-sequence i, rows padded to the common T; out [bs * T][hl * d] likewise.  All three arrays are int64 on the device:
+ *     pos  [bs]           position of token 0 of sequence i
+ *     len  [bs] or NULL   only tokens t < min(len[i], T) exist (NULL: all T); later rows write nothing, are seen by nobody and leave
+ *                         their output rows unwritten; len[i] <= 0 makes sequence i a no-op
+ *     slot [bs] or NULL   sequence i lives in k_cache[slot[i]] / v_cache[slot[i]] of caches [cache_bs][kvl][max_seq][d] (NULL: slot i,
+ *                         and bs == cache_bs is required); a slot outside [0, cache_bs) makes sequence i a no-op.  Slots must be
+ *                         distinct (the caller's obligation); whatever the three arrays hold, nothing outside the caches is indexed.
+ *   Everything else is dg_prefill_attn's: two launches, no scratch, no atomics; rows above a token's own position are never read, tile
+ *   rows beyond a workgroup's last valid position are zero-filled on chip; d = 64 / 128, max_seq <= 8192, bs <= 65535.  For an existing
+ *   token the cache rows and the output row are, bit for bit, dg_prefill_attn's for that sequence alone with T = len[i].
+ *
+ * DG_ATTN_MX8 -- mx8 KV cache: block-scaled 8-bit rows (OCP MXFP8; any4_amd/kvcache.py mx8_encode is the definition).  k_cache / v_cache
+ *   [bs][kvl][max_seq][d] hold one E4M3 code per element, k_exp / v_exp [bs][kvl][max_seq][d / 32] one E8M0 exponent byte per 32
+ *   consecutive elements of a row: value = code * 2^(E - 127); E = 255 marks a block with a non-finite element, which reads as NaN in all
+ *   32 places.  The _mx8 flavours keep their namesakes' guards, scratch protocol and rounding points:
+ *     writers  the roped k row keeps dg_rope_kv's 16-bit bits; that row and the raw v row are encoded per block -- byte for byte
+ *              mx8_encode(rope(k)) / mx8_encode(v).  Rows that are not written keep their codes AND their exponent bytes.
+ *     readers  a cached row is converted to the 16-bit type (exact) and enters the namesake's arithmetic in the namesake's order.  In
+ *              dg_rope_attn_split_mx8 the new token's own k / v enter the scores and the value sum as their DECODED rows (what later
+ *              steps read), not as the unquantised ones.
+ *   dg_rope_attn_split_mx8 and its _seq flavour always run the 256-thread split kernel (dg_rope_attn_split's for a d other than 64 / 128):
+ *   nsplit = 1 is accepted, max_seq / nsplit <= ~15000; d % 32 == 0 (TG_E_SHAPE otherwise, nothing is touched).  dg_prefill_attn_mx8 and
+ *   its _seq flavour: d = 64 / 128.  All four tensors 16-byte aligned; a null k_exp or v_exp is TG_E_NULL.  fp16 stacks whose |k|, |v|
+ *   exceed fp16's range after decoding are out of contract.
+ *
+ * DG_ATTN_ONE_BARRIER -- a DG_ATTN_SPLIT | DG_ATTN_MX8 call held to the one-barrier kernel (dg_rope_attn_online_mx8 and its _seq flavour):
+ *   always dg_rope_attn_online's one-barrier kernel in its 8-bit flavour with `nsplit` blocks per head (nsplit = 1: neither partials nor
+ *   counters are used; the scratch layout and protocol are dg_rope_attn_split's).  A row lies across d / 8 lanes as the 16-bit rows do: a
+ *   lane's piece is 8 code bytes and the exponent byte of its block, every wave-load is contiguous, the first 256 rows are requested
+ *   before `pos` is known; pieces are converted to the 16-bit type on use, and behind the conversion every sum and rounding point is the
+ *   16-bit kernel's -- on a 16-bit cache that holds the decoded values dg_rope_attn_online / _online_seq (nsplit = 1) and
+ *   dg_rope_attn_split / _split_seq give the same output bit for bit.  Writer and new token as in dg_rope_attn_split_mx8: byte for byte
+ *   mx8_encode(rope(k)) / mx8_encode(v), entering the sums as the DECODED rows; rows that are not written keep their codes and exponent
+ *   bytes, and whatever `pos` holds nothing outside [0, max_seq) of the four tensors is indexed.  In this order: a null pointer (k_exp,
+ *   v_exp, scratch included) is TG_E_NULL; d other than 64 / 128, nsplit outside 1 ... 64, max_seq > 65536 or a scratch that is too small
+ *   TG_E_SHAPE; caches, exponents, scratch, qkv, cos or sin off a 16-byte boundary TG_E_ALIGN; nothing is touched in any of these cases.
+ *
+ * DG_ATTN_PAGED -- paged KV cache: a pool of fixed-size pages behind a block table.  Per layer k_cache / v_cache are the POOLS
+ *   [num_pages][kvl][page_size][d] in the 16-bit type; one table, int32 [cache_bs][max_seq / page_size] on the device, serves every layer:
+ *   logical position p of the sequence in cache slot s is row p % page_size of page table[s][p / page_size] (-1: unmapped, by convention).
+ *   page_size is a power of two, 64 <= page_size <= max_seq, max_seq % page_size == 0, num_pages > 0 (TG_E_SHAPE otherwise); d = 64 / 128
+ *   in all three; max_seq <= 65536 for the decode kernels, <= 8192 for prefill; the table 16-byte aligned like the other tensors
+ *   (TG_E_ALIGN), not null (TG_E_NULL); in every such case nothing is touched.  The contiguous caches [bs][kvl][max_seq][d] ARE the pool
+ *   with page_size = max_seq and the identity table.
+ *     dg_rope_attn_online_paged   dg_rope_attn_online_seq behind the table
+ *     dg_rope_attn_split_paged    the same on dg_rope_attn_split_seq; always the one-barrier kernel with nsplit blocks per head
+ *     dg_prefill_attn_paged       the same on dg_prefill_attn_seq; slot[i] picks the table ROW, cache_bs is the number of table rows
+ *   A position per sequence always: DG_ATTN_PAGED goes with DG_ATTN_SEQ, and the caller says so (there is no scalar-position paged
+ *   flavour); the position, length and slot guards are the _seq ones.  Whatever the table holds, nothing outside the pools is indexed: an
+ *   entry outside [0, num_pages) is read as page 0 (that sequence's output is then unspecified), and a row whose OWN entry is outside
+ *   [0, num_pages) is not written -- neither pool changes.  Pages of different sequences that are written by one call must be distinct
+ *   (the caller's obligation, as distinct slots are).  The kernels walk the context in units that a page holds whole (32- / 64-row
+ *   iterations, 64-position tiles); paging changes where a unit's base comes from (one scalar table read) and nothing else: partition of
+ *   work, order of every sum, masks and rounding points are the _seq namesakes', so for tables that map the same rows the cache rows
+ *   written and the output rows are, bit for bit, theirs.
+ *
+ * DG_ATTN_PAGED | DG_ATTN_MX8 -- paged mx8 KV cache: 8-bit page pools behind the block table.  Per layer FOUR pools behind the one table:
+ *   k_cache / v_cache [num_pages][kvl][page_size][d] hold one E4M3 code BYTE per element, k_exp / v_exp [num_pages][kvl][page_size][d / 32]
+ *   one E8M0 exponent byte per 32 consecutive elements of a row (the mx8 format above); logical position p of the sequence in slot s is row
+ *   p % page_size of page table[s][p / page_size] in all four.  A page holds at least 64 rows, so the codes and the exponents of a (page,
+ *   kv head) begin on 16-byte boundaries when the pools do.
+ *     dg_rope_attn_online_mx8_paged   always the one-barrier kernel with nsplit blocks per head (nsplit = 1: neither partials nor counters
+ *                                     are used), the one decode flavour
+ *     dg_prefill_attn_mx8_paged       dg_prefill_attn_paged on the four pools
+ *   Both obey the paged AND the mx8 rules, in the order null, dtype, shape, alignment: a null pointer (table, k_exp, v_exp, scratch
+ *   included) is TG_E_NULL; d other than 64 / 128, a page_size that is no power of two in [64, max_seq] or does not divide max_seq,
+ *   num_pages <= 0, nsplit outside 1 ... 64 or a scratch that is too small TG_E_SHAPE; pools, exponents, table, scratch, qkv, cos or sin
+ *   off a 16-byte boundary TG_E_ALIGN; nothing is touched in any of these cases.  The page lookup is the paged flavours' (an entry outside
+ *   [0, num_pages) reads page 0; a row whose OWN entry is outside the pool writes neither codes nor exponent bytes), the rows' bytes and
+ *   the arithmetic are the contiguous mx8 flavours': for tables that map the same rows, the bytes written and the output rows are, bit
+ *   for bit, those of dg_rope_attn_online_mx8_seq (same nsplit) / dg_prefill_attn_mx8_seq. */
+#define DG_ATTN_SEQ 1u
+#define DG_ATTN_MX8 2u
+#define DG_ATTN_PAGED 4u
+#define DG_ATTN_ONE_BARRIER 8u
 
-/* dg_prefill_attn with position, length and cache slot per sequence.  qkv [n * T][(hl + 2 kvl) * d]: row i * T + t = token t of
- * chunk-sequence i, rows padded to the common T; out [n * T][hl * d] likewise.  All three arrays are int64 on the device:
- *   pos  [n]           position of token 0 of sequence i
- *   len  [n] or NULL   only tokens t < min(len[i], T) exist (NULL: all T); later rows write nothing, are seen by nobody and leave
- *                      their output rows unwritten; len[i] <= 0 makes sequence i a no-op
- *   slot [n] or NULL   sequence i lives in k_cache[slot[i]] / v_cache[slot[i]] of caches [cache_bs][kvl][max_seq][d] (NULL: slot i,
- *                      and n == cache_bs is required); a slot outside [0, cache_bs) makes sequence i a no-op.  Slots must be
- *                      distinct (the caller's obligation); whatever the three arrays hold, nothing outside the caches is indexed.
- * Everything else is dg_prefill_attn's: two launches, no scratch, no atomics; rows above a token's own position are never read,
- * tile rows beyond a workgroup's last valid position are zero-filled on chip; d = 64 / 128, max_seq <= 8192, n <= 65535.  For an
- * existing token the cache rows and the output row are, bit for bit, dg_prefill_attn's for that sequence alone with T = len[i]. */
-TG_API int dg_prefill_attn_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
-                               const int64_t* slot, void* k_cache, void* v_cache, void* out, int64_t n, int64_t T, int64_t cache_bs,
-                               int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device, tg_stream_t stream);
+/* The accepted calls: X(name up to ABI 8, kernel, flags).  Every other pair is TG_E_LAYOUT. */
+#define DG_ATTN_FLAVOURS(X)                                                                                         \
+  X(dg_rope_attn, DG_ATTN_GENERAL, 0)                                                                               \
+  X(dg_rope_attn_seq, DG_ATTN_GENERAL, DG_ATTN_SEQ)                                                                 \
+  X(dg_rope_attn_online, DG_ATTN_ONLINE, 0)                                                                         \
+  X(dg_rope_attn_online_seq, DG_ATTN_ONLINE, DG_ATTN_SEQ)                                                           \
+  X(dg_rope_attn_online_paged, DG_ATTN_ONLINE, DG_ATTN_SEQ | DG_ATTN_PAGED)                                         \
+  X(dg_rope_attn_split, DG_ATTN_SPLIT, 0)                                                                           \
+  X(dg_rope_attn_split_seq, DG_ATTN_SPLIT, DG_ATTN_SEQ)                                                             \
+  X(dg_rope_attn_split_mx8, DG_ATTN_SPLIT, DG_ATTN_MX8)                                                             \
+  X(dg_rope_attn_split_mx8_seq, DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_SEQ)                                           \
+  X(dg_rope_attn_online_mx8, DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER)                                      \
+  X(dg_rope_attn_online_mx8_seq, DG_ATTN_SPLIT, DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER | DG_ATTN_SEQ)                    \
+  X(dg_rope_attn_split_paged, DG_ATTN_SPLIT, DG_ATTN_SEQ | DG_ATTN_PAGED)                                           \
+  X(dg_rope_attn_online_mx8_paged, DG_ATTN_SPLIT, DG_ATTN_SEQ | DG_ATTN_PAGED | DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER)  \
+  X(dg_prefill_attn, DG_ATTN_PREFILL, 0)                                                                            \
+  X(dg_prefill_attn_seq, DG_ATTN_PREFILL, DG_ATTN_SEQ)                                                              \
+  X(dg_prefill_attn_mx8, DG_ATTN_PREFILL, DG_ATTN_MX8)                                                              \
+  X(dg_prefill_attn_mx8_seq, DG_ATTN_PREFILL, DG_ATTN_MX8 | DG_ATTN_SEQ)                                            \
+  X(dg_prefill_attn_paged, DG_ATTN_PREFILL, DG_ATTN_SEQ | DG_ATTN_PAGED)                                            \
+  X(dg_prefill_attn_mx8_paged, DG_ATTN_PREFILL, DG_ATTN_SEQ | DG_ATTN_PAGED | DG_ATTN_MX8)
 
-/* ---- mx8 KV cache: block-scaled 8-bit rows (OCP MXFP8; any4_amd/kvcache.py mx8_encode is the definition) ----
- * k_cache / v_cache [bs][kvl][max_seq][d] hold one E4M3 code per element, k_exp / v_exp [bs][kvl][max_seq][d / 32] one E8M0 exponent byte
- * per 32 consecutive elements of a row: value = code * 2^(E - 127); E = 255 marks a block with a non-finite element, which reads as NaN
- * in all 32 places.  The four entry points take their namesakes' arguments plus the two exponent tensors (behind v_cache) and keep their
- * namesakes' guards, scratch protocol and rounding points:
- *   writers  the roped k row keeps dg_rope_kv's 16-bit bits; that row and the raw v row are encoded per block -- byte for byte
- *            mx8_encode(rope(k)) / mx8_encode(v).  Rows that are not written keep their codes AND their exponent bytes.
- *   readers  a cached row is converted to the 16-bit type (exact) and enters the namesake's arithmetic in the namesake's order.  In
- *            dg_rope_attn_split_mx8 the new token's own k / v enter the scores and the value sum as their DECODED rows (what later
- *            steps read), not as the unquantised ones.
- * dg_rope_attn_split_mx8(_seq) always run the 256-thread split kernel (dg_rope_attn_split's for a d other than 64 / 128): nsplit = 1 is
- * accepted, max_seq / nsplit <= ~15000; d % 32 == 0 (TG_E_SHAPE otherwise, nothing is touched).  dg_prefill_attn_mx8(_seq): d = 64 / 128.
- * All four tensors 16-byte aligned.  fp16 stacks whose |k|, |v| exceed fp16's range after decoding are out of contract. */
-TG_API int dg_rope_attn_split_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                                  void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                  int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-TG_API int dg_rope_attn_split_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                                      void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                      int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-TG_API int dg_prefill_attn_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                               void* k_exp, void* v_exp, void* out, int64_t bs, int64_t T, int hl, int kvl, int d, int64_t max_seq, float scale,
-                               int dtype, int device, tg_stream_t stream);
-TG_API int dg_prefill_attn_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
-                                   const int64_t* slot, void* k_cache, void* v_cache, void* k_exp, void* v_exp, void* out, int64_t n, int64_t T,
-                                   int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, float scale, int dtype, int device,
-                                   tg_stream_t stream);
+/* One call.  C: `struct dg_attn a = {sizeof a};`.  A field that the call's kernel and flags do not use is not read: k_exp / v_exp
+ * without DG_ATTN_MX8; table, page_size, num_pages without DG_ATTN_PAGED; scratch, scratch_bytes, nsplit outside DG_ATTN_SPLIT; T outside
+ * DG_ATTN_PREFILL; len, slot, cache_bs outside DG_ATTN_PREFILL with DG_ATTN_SEQ.  Pointers and 64-bit fields stand in front of the 32-bit
+ * ones, so the struct has no hidden padding. */
+typedef struct dg_attn {
+  uint32_t struct_bytes;  /* sizeof(struct dg_attn); anything else is TG_E_STRUCT (the first version: there is no shorter prefix) */
+  int32_t kernel;         /* DG_ATTN_GENERAL ... DG_ATTN_PREFILL */
+  const void* qkv;        /* [bs * T][(hl + 2 kvl) * d], 16-bit */
+  const float* cos;       /* float32 [max_seq][d] */
+  const float* sin;
+  const int64_t* pos;     /* on the device: one position, or [bs] with DG_ATTN_SEQ */
+  void* k_cache;          /* the caches; with DG_ATTN_PAGED the pools */
+  void* v_cache;
+  void* out;              /* [bs * T][hl * d] */
+  void* k_exp;            /* DG_ATTN_MX8: the exponent bytes of the caches / pools */
+  void* v_exp;
+  const int64_t* len;     /* DG_ATTN_PREFILL with DG_ATTN_SEQ: [bs] or NULL */
+  const int64_t* slot;    /* DG_ATTN_PREFILL with DG_ATTN_SEQ: [bs] or NULL */
+  const int32_t* table;   /* DG_ATTN_PAGED: int32 [cache_bs][max_seq / page_size] */
+  void* scratch;          /* DG_ATTN_SPLIT */
+  int64_t scratch_bytes;  /* DG_ATTN_SPLIT: at least dg_rope_attn_split_scratch_bytes */
+  int64_t bs;             /* sequences of the call */
+  int64_t T;              /* DG_ATTN_PREFILL: tokens per sequence */
+  int64_t cache_bs;       /* DG_ATTN_PREFILL with DG_ATTN_SEQ: sequences the caches hold / rows of the table */
+  int64_t max_seq;
+  int64_t page_size;      /* DG_ATTN_PAGED */
+  int64_t num_pages;      /* DG_ATTN_PAGED */
+  uint32_t flags;         /* DG_ATTN_SEQ | DG_ATTN_MX8 | DG_ATTN_PAGED | DG_ATTN_ONE_BARRIER */
+  int32_t hl;             /* query heads, kv heads (hl % kvl == 0), head dimension */
+  int32_t kvl;
+  int32_t d;
+  int32_t nsplit;         /* DG_ATTN_SPLIT: blocks per head, 1 ... 64 */
+  int32_t dtype;          /* TG_BF16 / TG_F16 */
+  float scale;
+  uint32_t reserved;      /* padding to 8 bytes; not read */
+} dg_attn;
 
-/* ---- mx8 KV cache on the one-barrier kernel ----
- * dg_rope_attn_online_mx8(_seq): the argument list of dg_rope_attn_split_mx8(_seq), and always dg_rope_attn_online's one-barrier kernel
- * in its 8-bit flavour with `nsplit` blocks per head (nsplit = 1: neither partials nor counters are used; the scratch layout and protocol
- * are dg_rope_attn_split's).  A row lies across d / 8 lanes as the 16-bit rows do: a lane's piece is 8 code bytes and the exponent byte
- * of its block, every wave-load is contiguous, the first 256 rows are requested before `pos` is known; pieces are converted to the
- * 16-bit type on use, and behind the conversion every sum and rounding point is the 16-bit kernel's -- on a 16-bit cache that holds the
- * decoded values dg_rope_attn_online(_seq) (nsplit = 1) / dg_rope_attn_split(_seq) give the same output bit for bit.  Writer and new
- * token as in dg_rope_attn_split_mx8: byte for byte mx8_encode(rope(k)) / mx8_encode(v), entering the sums as the DECODED rows; rows that
- * are not written keep their codes and exponent bytes, and whatever `pos` holds nothing outside [0, max_seq) of the four tensors is
- * indexed.  In this order: a null pointer (k_exp, v_exp, scratch included) is TG_E_NULL; d other than 64 / 128, nsplit outside 1 ... 64,
- * max_seq > 65536 or a scratch that is too small TG_E_SHAPE; caches, exponents, scratch, qkv, cos or sin off a 16-byte boundary
- * TG_E_ALIGN; nothing is touched in any of these cases.  (Paged mx8 pools: dg_rope_attn_online_mx8_paged, at the end of this header.)
- * Exported like every other symbol; declared with a macro of their own because they are bound as a group of their own
- * (any4_amd/_lib.py: KV8_ONLINE_SYMBOLS). */
-#define DG_KV8_API TG_API /* (exported) */
-DG_KV8_API int dg_rope_attn_online_mx8(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                                       void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                       int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-DG_KV8_API int dg_rope_attn_online_mx8_seq(const void* qkv, const float* cos, const float* sin, const int64_t* pos, void* k_cache, void* v_cache,
-                                           void* k_exp, void* v_exp, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                           int d, int64_t max_seq, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-
-/* ---- paged KV cache: a pool of fixed-size pages behind a block table ----
- * Per layer k_pool / v_pool are [num_pages][kvl][page_size][d] in the 16-bit type; one table, int32 [cache_bs][max_seq / page_size] on the
- * device, serves every layer: logical position p of the sequence in cache slot s is row p % page_size of page table[s][p / page_size]
- * (-1: unmapped, by convention).  page_size is a power of two, 64 <= page_size <= max_seq, max_seq % page_size == 0, num_pages > 0
- * (TG_E_SHAPE otherwise); d = 64 / 128 in all three; max_seq <= 65536 for the decode entry points, <= 8192 for prefill; the table 16-byte
- * aligned like the other tensors (TG_E_ALIGN), not null (TG_E_NULL); in every such case nothing is touched.  The contiguous caches
- * [bs][kvl][max_seq][d] ARE the pool with page_size = max_seq and the identity table.
- *   dg_rope_attn_online_paged   dg_rope_attn_online_seq's arguments, `table` in front of the pools, page_size / num_pages behind max_seq
- *   dg_rope_attn_split_paged    the same on dg_rope_attn_split_seq; always the one-barrier kernel with nsplit blocks per head
- *   dg_prefill_attn_paged       the same on dg_prefill_attn_seq; slot[i] picks the table ROW, cache_bs is the number of table rows
- * A position per sequence always (there is no scalar-position paged flavour); the position, length and slot guards are the _seq ones.
- * Whatever the table holds, nothing outside the pools is indexed: an entry outside [0, num_pages) is read as page 0 (that sequence's
- * output is then unspecified), and a row whose OWN entry is outside [0, num_pages) is not written -- neither pool changes.  Pages of
- * different sequences that are written by one call must be distinct (the caller's obligation, as distinct slots are).
- * The kernels walk the context in units that a page holds whole (32- / 64-row iterations, 64-position tiles); paging changes where a
- * unit's base comes from (one scalar table read) and nothing else: partition of work, order of every sum, masks and rounding points are
- * the _seq namesakes', so for tables that map the same rows the cache rows written and the output rows are, bit for bit, theirs.
- * The three are exported like every other symbol; they are declared with a macro of their own because they are bound as a group of
- * their own (any4_amd/_lib.py: PAGED_SYMBOLS, next to SYMBOLS, which stays the list of the twelve unpaged attention entry points). */
-#define DG_PAGED_API TG_API /* (exported) */
-DG_PAGED_API int dg_rope_attn_online_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
-                                           void* k_pool, void* v_pool, void* out, int64_t bs, int hl, int kvl, int d, int64_t max_seq,
-                                           int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream);
-DG_PAGED_API int dg_rope_attn_split_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
-                                          void* k_pool, void* v_pool, void* out, void* scratch, int64_t scratch_bytes, int64_t bs, int hl, int kvl,
-                                          int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale, int nsplit, int dtype,
-                                          int device, tg_stream_t stream);
-DG_PAGED_API int dg_prefill_attn_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
-                                       const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* out, int64_t n, int64_t T,
-                                       int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size, int64_t num_pages, float scale,
-                                       int dtype, int device, tg_stream_t stream);
-
-/* ---- paged mx8 KV cache: 8-bit page pools behind the block table ----
- * Per layer FOUR pools behind the one table: k_pool / v_pool [num_pages][kvl][page_size][d] hold one E4M3 code BYTE per element, k_exp /
- * v_exp [num_pages][kvl][page_size][d / 32] one E8M0 exponent byte per 32 consecutive elements of a row (the mx8 format above); logical
- * position p of the sequence in slot s is row p % page_size of page table[s][p / page_size] in all four.  A page holds at least 64 rows,
- * so the codes and the exponents of a (page, kv head) begin on 16-byte boundaries when the pools do.
- *   dg_rope_attn_online_mx8_paged   dg_rope_attn_split_paged's arguments with k_exp / v_exp behind the pools: always the one-barrier kernel
- *                                   with nsplit blocks per head (nsplit = 1: neither partials nor counters are used), the one decode entry point
- *   dg_prefill_attn_mx8_paged       dg_prefill_attn_paged's arguments with k_exp / v_exp behind the pools
- * Both obey the paged AND the mx8 rules, in the order null, dtype, shape, alignment: a null pointer (table, k_exp, v_exp, scratch included)
- * is TG_E_NULL; d other than 64 / 128, a page_size that is no power of two in [64, max_seq] or does not divide max_seq, num_pages <= 0,
- * nsplit outside 1 ... 64 or a scratch that is too small TG_E_SHAPE; pools, exponents, table, scratch, qkv, cos or sin off a 16-byte boundary
- * TG_E_ALIGN; nothing is touched in any of these cases.  The page lookup is the paged entry points' (an entry outside [0, num_pages) reads
- * page 0; a row whose OWN entry is outside the pool writes neither codes nor exponent bytes), the rows' bytes and the arithmetic are the
- * contiguous mx8 entry points': for tables that map the same rows, the bytes written and the output rows are, bit for bit, those of
- * dg_rope_attn_online_mx8_seq (same nsplit) / dg_prefill_attn_mx8_seq.
- * Exported like every other symbol; declared with a macro of their own because they are bound as a group of their own
- * (any4_amd/_lib.py: PAGED_MX8_SYMBOLS). */
-#define DG_PAGED_KV8_API TG_API /* (exported) */
-DG_PAGED_KV8_API int dg_rope_attn_online_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int32_t* table,
-                                                   void* k_pool, void* v_pool, void* k_exp, void* v_exp, void* out, void* scratch,
-                                                   int64_t scratch_bytes, int64_t bs, int hl, int kvl, int d, int64_t max_seq, int64_t page_size,
-                                                   int64_t num_pages, float scale, int nsplit, int dtype, int device, tg_stream_t stream);
-DG_PAGED_KV8_API int dg_prefill_attn_mx8_paged(const void* qkv, const float* cos, const float* sin, const int64_t* pos, const int64_t* len,
-                                               const int64_t* slot, const int32_t* table, void* k_pool, void* v_pool, void* k_exp, void* v_exp,
-                                               void* out, int64_t n, int64_t T, int64_t cache_bs, int hl, int kvl, int d, int64_t max_seq,
-                                               int64_t page_size, int64_t num_pages, float scale, int dtype, int device, tg_stream_t stream);
+/* In this order: call == NULL is TG_E_NULL; struct_bytes != sizeof(struct dg_attn) is TG_E_STRUCT; a kernel outside the four, a flag bit
+ * outside the four or a (kernel, flags) pair that DG_ATTN_FLAVOURS does not list is TG_E_LAYOUT, before any other field is read; then
+ * the kernel's own checks -- null, dtype, shape, alignment -- and the launch. */
+TG_API int dg_attn_launch(const dg_attn* call, int device, tg_stream_t stream);
+TG_API int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit);
 
 /* ---- sampling: temperature, top-k, top-p (nucleus) and a counter-based draw, one launch per step ----
  * The definition is any4_amd/sampling.py (sample_ref, uniform, philox4x32_10), in float64; this is its kernel.  Per row b of

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 8
+#define TG_ABI_VERSION 9
 
 #if defined(__GNUC__)
 #define TG_API __attribute__((visibility("default")))
@@ -99,9 +99,9 @@ enum {
   TG_E_DEVICE = -9,    /* hipSetDevice failed / no such device                             */
   TG_E_SIZE = -10,     /* one problem's operand exceeds the kernels' 32-bit byte offsets   */
   TG_E_INTERNAL = -11, /* build inconsistency (should not happen)                          */
-  TG_E_LAYOUT = -12,   /* x_layout / y_layout not available for this problem               */
+  TG_E_LAYOUT = -12,   /* no kernel for this layout / cache layout: x_layout / y_layout, dg_attn (kernel, flags) */
   TG_E_FUSION = -13,   /* norm_weight / epilogue: no kernel with that fused stage for this problem (issue it as its own launch) */
-  TG_E_STRUCT = -14    /* tg_w4_gemm.struct_bytes: smaller than the ABI-1 prefix of the struct, or larger than this library's struct */
+  TG_E_STRUCT = -14    /* tg_w4_gemm.struct_bytes: smaller than the ABI-1 prefix of the struct, or larger than this library's struct; dg_attn.struct_bytes: not this library's */
 };
 
 TG_API int tg_abi_version(void);

@@ -14,6 +14,7 @@ tests/test_glue_ref_cpu.py).
 
 Lines starting with GLUE_F64 / GLUE_ROPE are the error table: dev/glue_f64_table.py condenses a run's `-s` output into
 profiles/glue_f64_errors.txt."""
+import ctypes
 import math
 
 import pytest
@@ -374,16 +375,14 @@ def test_rejected_shapes_return_tg_e_shape_and_touch_nothing(dtype):
             rc = lib.dg_rope_kv(p(qkv), p(cos), p(sin), p(pos), p(q), p(kc), p(vc), bs, hl, kvl, d, S, dt, dev, st)
         elif entry == "decode_attn":
             rc = lib.dg_decode_attn(p(q), p(kc), p(vc), p(pos), p(out), bs, hl, kvl, d, S, scale, dt, dev, st)
-        elif entry == "rope_attn":
-            rc = lib.dg_rope_attn(p(qkv), p(cos), p(sin), p(pos), p(kc), p(vc), p(out), bs, hl, kvl, d, S, scale, dt, dev, st)
-        elif entry == "rope_attn_online":
-            rc = lib.dg_rope_attn_online(p(qkv), p(cos), p(sin), p(pos), p(kc), p(vc), p(out), bs, hl, kvl, d, S, scale, dt, dev, st)
-        elif entry == "rope_attn_split":
+        else:  # the fused kernels: one dg_attn_launch each
             scr = torch.zeros(1 << 16, dtype=torch.int32, device=DEV)
-            rc = lib.dg_rope_attn_split(p(qkv), p(cos), p(sin), p(pos), p(kc), p(vc), p(out), p(scr), scr.numel() * 4, bs, hl, kvl, d, S,
-                                        scale, 2, dt, dev, st)
-        else:
-            rc = lib.dg_prefill_attn(p(qkv), p(cos), p(sin), p(pos), p(kc), p(vc), p(out), bs, 1, hl, kvl, d, S, scale, dt, dev, st)
+            kernel = {"rope_attn": _lib.DG_ATTN_GENERAL, "rope_attn_online": _lib.DG_ATTN_ONLINE, "rope_attn_split": _lib.DG_ATTN_SPLIT,
+                      "prefill_attn": _lib.DG_ATTN_PREFILL}[entry]
+            call = _lib.Attn(kernel=kernel, qkv=p(qkv), cos=p(cos), sin=p(sin), pos=p(pos), k_cache=p(kc), v_cache=p(vc), out=p(out),
+                             scratch=p(scr), scratch_bytes=scr.numel() * 4, bs=bs, T=1, hl=hl, kvl=kvl, d=d, max_seq=S, scale=scale, nsplit=2,
+                             dtype=dt)
+            rc = lib.dg_attn_launch(ctypes.byref(call), dev, st)
         torch.cuda.synchronize()
         clean = bool((kc == 1.5).all() and (vc == -2.5).all() and (out == 7.0).all() and (q == 3.0).all())
         return rc, clean

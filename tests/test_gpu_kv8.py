@@ -1,4 +1,4 @@
-"""GPU suite: the mx8 KV cache (any4_amd/kvcache.py) on the HIP kernels -- dg_rope_attn_split_mx8(_seq) and dg_prefill_attn_mx8(_seq):
+"""GPU suite: the mx8 KV cache (any4_amd/kvcache.py) on the HIP kernels -- the dg_rope_attn_split_mx8 / _mx8_seq and dg_prefill_attn_mx8 / _mx8_seq flavours of dg_attn_launch:
   1. the bytes they write are mx8_encode's (codes and exponents), nothing else is written, guard bytes behind all four tensors stay;
   2. their outputs equal their 16-bit namesakes' bit for bit on a 16-bit cache that holds the decoded values (identity rope tables and a
      new token whose rows are decoded values themselves, so re-quantising changes nothing).  At head_dim 64 / 128 dg_rope_attn_split
@@ -486,10 +486,11 @@ def test_mx8_graph_replays_with_new_positions():
 # ---------------------------------------------------------------- 6. rejected shapes
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_rejected_shapes_return_tg_e_shape_and_touch_nothing(dtype):
-    """head_dim 16 (a multiple of 8 the 16-bit split kernel takes, not of 32) at the split entry points; head_dim 32 and 96 at the
+    """head_dim 16 (a multiple of 8 the 16-bit split kernel takes, not of 32) at the split flavours; head_dim 32 and 96 at the
     prefill ones (64 / 128 only).  Raw calls: the Python front end refuses these before the library sees them."""
     from any4_amd import _lib
     from any4_amd import decode_ops as G
+    from tests import attn_abi
 
     lib = _lib.load()
     TG_E_SHAPE = -7
@@ -508,14 +509,12 @@ def test_rejected_shapes_return_tg_e_shape_and_touch_nothing(dtype):
         out = torch.full((rows, hl * d), SENTINEL, device=DEV, dtype=dtype)
         scr = G.rope_attn_split_scratch(bs, hl, 64, 2, DEV)
         st = torch.cuda.current_stream().cuda_stream
-        front = (qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr())
-        caches = (kc.data_ptr(), vc.data_ptr(), ke.data_ptr(), ve.data_ptr(), out.data_ptr())
-        if not prefill:
-            rc = getattr(lib, entry)(*front, *caches, scr.data_ptr(), scr.numel() * 4, bs, hl, kvl, d, S, 0.125, 2, dt, 0, st)
-        elif entry.endswith("_seq"):
-            rc = getattr(lib, entry)(*front, None, None, *caches, bs, T, bs, hl, kvl, d, S, 0.125, dt, 0, st)
-        else:
-            rc = getattr(lib, entry)(*front, *caches, bs, T, hl, kvl, d, S, 0.125, dt, 0, st)
+        # (the split kernel's fields, the prefill kernel's -- len = slot = NULL, the caches' own batch -- and what they share; a flavour
+        #  reads its own)
+        rc = attn_abi.launch(lib, entry, 0, st, qkv=qkv.data_ptr(), cos=cos.data_ptr(), sin=sin.data_ptr(), pos=pos.data_ptr(),
+                             k_cache=kc.data_ptr(), v_cache=vc.data_ptr(), k_exp=ke.data_ptr(), v_exp=ve.data_ptr(), out=out.data_ptr(),
+                             scratch=scr.data_ptr(), scratch_bytes=scr.numel() * 4, nsplit=2, bs=bs, T=T, cache_bs=bs, hl=hl, kvl=kvl, d=d,
+                             max_seq=S, scale=0.125, dtype=dt)
         torch.cuda.synchronize()
         assert rc == TG_E_SHAPE, (entry, d, rc)
         assert (kc == CODE_FILL).all() and (vc == CODE_FILL).all() and (ke == EXP_FILL).all() and (ve == EXP_FILL).all(), (entry, d)

@@ -1,4 +1,4 @@
-"""GPU suite: the one-barrier decode attention kernel on an mx8 KV cache -- dg_rope_attn_online_mx8(_seq), decode_ops.rope_attn_online_mx8,
+"""GPU suite: the one-barrier decode attention kernel on an mx8 KV cache -- the dg_rope_attn_online_mx8 / _mx8_seq flavours of dg_attn_launch, decode_ops.rope_attn_online_mx8,
 DecodeStack(..., kv_cache="mx8", mx8_attention="online"):
   1. the bytes it writes are mx8_encode's (codes and exponents), nothing else is written, guard bytes behind all four tensors stay;
   2. its outputs equal the 16-bit one-barrier kernel's bit for bit on a 16-bit cache that holds the decoded values (identity rope tables,
@@ -199,9 +199,10 @@ def test_a_split_launch_repeated_on_one_scratch_gives_the_same_bits(dtype, geome
 # ---------------------------------------------------------------- 6. rejected calls
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_rejected_calls_return_their_code_and_touch_nothing(dtype):
-    """head_dim 96 and nsplit 65 (TG_E_SHAPE), exponent tensors 4 bytes off a 16-byte boundary (TG_E_ALIGN); raw calls of both entry points."""
+    """head_dim 96 and nsplit 65 (TG_E_SHAPE), exponent tensors 4 bytes off a 16-byte boundary (TG_E_ALIGN); raw calls of both flavours."""
     from any4_amd import _lib
     from any4_amd import decode_ops as G
+    from tests import attn_abi
 
     lib = _lib.load()
     TG_E_SHAPE, TG_E_ALIGN = -7, -8
@@ -220,8 +221,10 @@ def test_rejected_calls_return_their_code_and_touch_nothing(dtype):
             out = torch.full((bs, hl * d), SENTINEL, device=DEV, dtype=dtype)
             scr = G.rope_attn_split_scratch(bs, hl, 128, 64, DEV)
             st = torch.cuda.current_stream().cuda_stream
-            rc = getattr(lib, entry)(qkv.data_ptr(), cos.data_ptr(), sin.data_ptr(), pos.data_ptr(), kc.data_ptr(), vc.data_ptr(), ke.data_ptr(),
-                                     ve.data_ptr(), out.data_ptr(), scr.data_ptr(), scr.numel() * 4, bs, hl, kvl, d, S, 0.125, ns, dt, 0, st)
+            rc = attn_abi.launch(lib, entry, 0, st, qkv=qkv.data_ptr(), cos=cos.data_ptr(), sin=sin.data_ptr(), pos=pos.data_ptr(),
+                                 k_cache=kc.data_ptr(), v_cache=vc.data_ptr(), k_exp=ke.data_ptr(), v_exp=ve.data_ptr(), out=out.data_ptr(),
+                                 scratch=scr.data_ptr(), scratch_bytes=scr.numel() * 4, bs=bs, hl=hl, kvl=kvl, d=d, max_seq=S, scale=0.125,
+                                 nsplit=ns, dtype=dt)
             torch.cuda.synchronize()
             assert rc == code, (entry, d, ns, off, rc)
             assert (kc == CODE_FILL).all() and (vc == CODE_FILL).all() and all((b == EXP_FILL).all() for b in ebuf), (entry, d, ns, off)

@@ -30,34 +30,81 @@ def test_c_abi_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/*.h but not exported"
     assert set(syms) == set(_lib.SYMBOLS), "ctypes binding and header disagree"
-    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 8
+    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 9
 
 
-def test_attention_signatures_are_the_headers_prototypes():
-    """_lib.attn_signature builds the twelve fused attention argument lists from named pieces, and decode_ops places a call's values by
-    those names: name for name and type for type they are the prototypes of include/decode_glue_hip.h."""
+def test_attention_struct_is_the_headers():
+    """_lib.Attn mirrors `struct dg_attn` of include/decode_glue_hip.h field for field -- name, C type and order -- without hidden padding;
+    the kernel and flag constants and the table of accepted calls are the header's; the library takes its own sizeof and nothing else."""
     from any4_amd import _lib
+    from tests import attn_abi
 
-    header = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
-    ctype = {"int64_t": _lib._i64, "int": ctypes.c_int, "float": ctypes.c_float, "tg_stream_t": _lib._vp}
-    seen = set()
-    for base, has_mx8 in _lib.ATTN_BASES.items():
-        for seq in (False, True):
-            for mx8 in (False, True) if has_mx8 else (False,):
-                entry, args = _lib.attn_signature(base, seq, mx8)
-                m = re.search(r"TG_API int " + entry + r"\(([^;]*)\);", header)
-                assert m, entry
-                declared = []
-                for param in m.group(1).replace("\n", " ").split(","):
-                    kind, name = param.strip().rsplit(" ", 1)
-                    declared.append(("bs" if name == "n" else name, _lib._vp if kind.endswith("*") else ctype[kind]))
-                assert list(args) == declared, entry
-                assert _lib.SYMBOLS[entry] == [t for _, t in declared], entry
-                seen.add(entry)
-        if not has_mx8:
-            with pytest.raises(KeyError):
-                _lib.attn_signature(base, False, True)
-    assert len(seen) == 12 and seen == {s for s in _lib.SYMBOLS if s.startswith(("dg_rope_attn", "dg_prefill_attn")) and not s.endswith("_bytes")}
+    fields = attn_abi.header_fields()
+    assert _lib.Attn._fields_ == fields and fields[0][0] == "struct_bytes"
+    assert ctypes.sizeof(_lib.Attn) == sum(ctypes.sizeof(t) for _, t in fields) and ctypes.sizeof(_lib.Attn) % 8 == 0
+    consts = attn_abi.header_constants()
+    assert len(consts) == 8 and all(getattr(_lib, name) == value for name, value in consts.items()), consts
+    assert sorted(consts[k] for k in ("DG_ATTN_GENERAL", "DG_ATTN_ONLINE", "DG_ATTN_SPLIT", "DG_ATTN_PREFILL")) == [0, 1, 2, 3]
+    assert sorted(consts[k] for k in ("DG_ATTN_SEQ", "DG_ATTN_MX8", "DG_ATTN_PAGED", "DG_ATTN_ONE_BARRIER")) == [1, 2, 4, 8]
+    flavours = attn_abi.header_flavours()
+    assert len(flavours) == 19 and {pair: name for name, pair in flavours.items()} == _lib.ATTN_FLAVOURS
+    L, size = _lib.load(), ctypes.sizeof(_lib.Attn)
+    assert _lib.Attn().struct_bytes == size
+    assert attn_abi.launch(L, "dg_rope_attn") == -1                              # accepted: on to the call's own checks (TG_E_NULL)
+    for bad in (size - 8, size + 8, 0):
+        assert attn_abi.launch(L, "dg_rope_attn", struct_bytes=bad) == _lib.TG_E_STRUCT, bad
+    assert L.dg_attn_launch(None, 0, None) == -1
+
+
+def _attn_fields():
+    """(fields every one of the nineteen calls accepts -- fake pointers, nothing is launched --, the 16-byte aligned address they hold)"""
+    buf = (ctypes.c_int32 * 64)()
+    base = ctypes.addressof(buf)
+    p = base + (-base) % 16
+    ok = dict(qkv=p, cos=p, sin=p, pos=p, len=p, slot=p, table=p, k_cache=p, v_cache=p, k_exp=p, v_exp=p, out=p, scratch=p, scratch_bytes=1 << 20,
+              bs=2, T=4, cache_bs=2, hl=4, kvl=2, d=64, max_seq=256, page_size=64, num_pages=5, scale=0.125, nsplit=4, dtype=0)
+    return ok, p, buf
+
+
+def test_every_pair_outside_the_headers_table_is_refused():
+    """4 kernels x 16 flag sets - 19 = 45 pairs, an unknown flag bit and an unknown kernel value: TG_E_LAYOUT with otherwise valid fields
+    -- and before any of them is read: with every other field zero as well."""
+    from any4_amd import _lib
+    from tests import attn_abi
+
+    L = _lib.load()
+    ok, _, _buf = _attn_fields()
+    refused = [(k, f) for k in range(4) for f in range(16) if (k, f) not in _lib.ATTN_FLAVOURS]
+    assert len(refused) == 45 and (_lib.DG_ATTN_ONLINE, _lib.DG_ATTN_PAGED) in refused       # PAGED without SEQ: the caller says both
+    for pair in refused + [(k, 16) for k in range(4)] + [(k, f | 1 << 31) for k, f in _lib.ATTN_FLAVOURS] + [(4, 0), (-1, 0), (1 << 20, 1)]:
+        assert attn_abi.launch(L, pair, **ok) == _lib.TG_E_LAYOUT, pair
+        assert attn_abi.launch(L, pair) == _lib.TG_E_LAYOUT, pair
+    assert attn_abi.launch(L, (4, 0), struct_bytes=8) == _lib.TG_E_STRUCT                    # the struct's length is judged first
+    assert b"cache layout" in L.tg_error_string(_lib.TG_E_LAYOUT)
+
+
+def test_a_field_that_a_call_does_not_use_is_not_read():
+    """Values that are TG_E_SHAPE where a call reads them change nothing in a call whose kernel and flags do not use the field (the
+    positional entry points up to ABI 8 did not have the parameter).  Every call here ends in an error code, so nothing is launched: a
+    misaligned qkv / out, which is judged after every shape, shows that the shapes passed."""
+    from any4_amd import _lib
+    from tests import attn_abi
+
+    L = _lib.load()
+    ok, p, _buf = _attn_fields()
+    odd = p + 4
+    junk = dict(page_size=3, num_pages=-1, scratch_bytes=-1, nsplit=99, T=0, cache_bs=-5, k_exp=None, v_exp=None, table=None, scratch=None,
+                len=None, slot=None)
+    for name in ("dg_rope_attn_online", "dg_rope_attn_online_seq"):
+        assert attn_abi.launch(L, name, **dict(ok, **junk, qkv=odd)) == -8, name
+    assert attn_abi.launch(L, "dg_prefill_attn", **dict(ok, **dict(junk, T=4), out=odd)) == -8                     # (T is prefill's own)
+    assert attn_abi.launch(L, "dg_rope_attn_online_paged", **dict(ok, scratch=None, nsplit=99, k_exp=None, T=0, qkv=odd)) == -8
+    # ... and where a call uses the field, the same value is refused
+    for name, field in (("dg_rope_attn_split", "nsplit"), ("dg_rope_attn_split", "scratch_bytes"), ("dg_rope_attn_online_paged", "page_size"),
+                        ("dg_rope_attn_online_paged", "num_pages"), ("dg_prefill_attn", "T"), ("dg_prefill_attn_seq", "cache_bs")):
+        assert attn_abi.launch(L, name, **dict(ok, **{field: junk[field]}, qkv=odd, out=odd)) == -7, (name, field)
+    for name, field in (("dg_rope_attn_split_mx8", "k_exp"), ("dg_rope_attn_online_paged", "table"), ("dg_rope_attn_split", "scratch")):
+        assert attn_abi.launch(L, name, **dict(ok, **{field: None}, qkv=odd)) == -1, (name, field)
 
 
 def test_peer_gather_preconditions_fail_before_any_launch():

@@ -240,24 +240,23 @@ def test_host_refusals():
                           kc, kc, 1, 1, 32, 1.0, torch.zeros(64, dtype=torch.int32), 1, k_exp=ke, v_exp=ke)
 
 
-def test_entry_points_are_declared_exported_and_bound():
+def test_mx8_flavours_refuse_null_tensors_before_any_launch():
+    """The four DG_ATTN_MX8 flavours of the split and the prefill kernel: preconditions come before any launch -- null tensors are TG_E_NULL
+    (-1), no device is touched; the flag is what asks for the exponents, so a call that says MX8 and brings none stays TG_E_NULL."""
+    import ctypes
     import re
 
     from any4_amd import _lib
+    from tests import attn_abi
 
-    header = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
-    assert _lib.TG_ABI_VERSION == 8 and re.search(r"#define\s+TG_ABI_VERSION\s+8\b", open(os.path.join(ROOT, "include", "tinygemm_hip.h")).read())
+    assert _lib.TG_ABI_VERSION == 9 and re.search(r"#define\s+TG_ABI_VERSION\s+9\b", open(os.path.join(ROOT, "include", "tinygemm_hip.h")).read())
+    lib = _lib.load()
+    buf = (ctypes.c_int32 * 64)()
+    p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16
+    ok = dict(qkv=p, cos=p, sin=p, pos=p, k_cache=p, v_cache=p, k_exp=p, v_exp=p, out=p, scratch=p, scratch_bytes=1 << 20, bs=2, T=4, hl=4,
+              kvl=2, d=64, max_seq=128, scale=0.125, nsplit=4, dtype=2)
     for name in ENTRIES:
-        m = re.search(r"TG_API int " + name + r"\(([^;]*)\);", header)
-        assert m, name
-        params = [p.strip() for p in m.group(1).replace("\n", " ").split(",")]
-        base = re.search(r"TG_API int " + name.replace("_mx8", "") + r"\(([^;]*)\);", header)
-        base = [p.strip() for p in base.group(1).replace("\n", " ").split(",")]
-        at = base.index("void* v_cache") + 1
-        assert params == base[:at] + ["void* k_exp", "void* v_exp"] + base[at:], name  # the namesake's list plus the two tensors
-        assert len(_lib.SYMBOLS[name]) == len(params), name
-        assert len(_lib.SYMBOLS[name]) == len(_lib.SYMBOLS[name.replace("_mx8", "")]) + 2, name
-    if os.path.exists(_lib.LIB_PATH):
-        lib = _lib.load()
-        for name in ENTRIES:  # preconditions come before any launch: null tensors are TG_E_NULL (-1), no device is touched
-            assert getattr(lib, name)(*[None if t is _lib._vp else 0 for t in _lib.SYMBOLS[name]]) == -1, name
+        assert attn_abi.launch(lib, name) == -1, name
+        assert attn_abi.launch(lib, name, **ok) == -5, name                    # (every pointer there: on to the dtype, which is none)
+        for exp in ("k_exp", "v_exp"):
+            assert attn_abi.launch(lib, name, **dict(ok, **{exp: None})) == -1, (name, exp)

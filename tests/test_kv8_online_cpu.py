@@ -1,10 +1,7 @@
-"""CPU suite: the one-barrier kernel's mx8 entry points, dg_rope_attn_online_mx8(_seq), up to where a GPU is needed -- declared
-(DG_KV8_API), exported, bound as a group of their own (KV8_ONLINE_SYMBOLS), header and binding name for name and type for type, the ABI
-version, every argument check before the first HIP call (null stream, no GPU) -- and DecodeStack(..., kv_cache="mx8", mx8_attention=...):
+"""CPU suite: the one-barrier kernel on an mx8 cache, the dg_rope_attn_online_mx8 / _mx8_seq flavours of dg_attn_launch, up to where a GPU
+is needed -- which (kernel, flags) pairs they are, the ABI version, every argument check before the first HIP call (null stream, no GPU) -- and DecodeStack(..., kv_cache="mx8", mx8_attention=...):
 the constructor's refusals, and the plain-torch formulation, which is the same for "split" and "online"."""
 import ctypes
-import os
-import re
 
 import pytest
 import torch
@@ -12,44 +9,29 @@ import torch
 from any4_amd.decode import DecodeConfig, DecodeLayer, DecodeStack
 from tests.test_decode_cpu import CFG, SeededDense
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dg_rope_attn_online_mx8", "dg_rope_attn_online_mx8_seq")
 TG_E_NULL, TG_E_DTYPE, TG_E_SHAPE, TG_E_ALIGN = -1, -5, -7, -8
 CFG8 = dict(CFG, head_dim=32, max_seq=256)  # (the suite's tiny configuration has head_dim 16: below one mx8 block)
 
 
-def test_symbols_are_declared_exported_and_bound_as_a_group_of_their_own():
+def test_the_flavours_are_the_split_kind_held_to_the_one_barrier_kernel():
+    """DG_ATTN_SPLIT | DG_ATTN_MX8 | DG_ATTN_ONE_BARRIER, with or without DG_ATTN_SEQ; the plain one-barrier kind (DG_ATTN_ONLINE: no
+    scratch, no split) has no mx8 flavour, and the library is what refuses it."""
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
-    with open(os.path.join(ROOT, "include", "decode_glue_hip.h")) as f:
-        header = f.read()
     L = _lib.load()
-    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 8
-    assert re.search(r"#define DG_KV8_API TG_API\b", header)
-    assert tuple(_lib.KV8_ONLINE_SYMBOLS) == NAMES
-    ctype = {"int64_t": _lib._i64, "int": ctypes.c_int, "float": ctypes.c_float, "tg_stream_t": _lib._vp}
-    for seq, name in enumerate(NAMES):
-        m = re.search(r"DG_KV8_API int " + name + r"\(([^;]*)\);", header)
-        assert m and not re.search(r"TG_API int " + name + r"\(", header), name
-        assert name not in _lib.SYMBOLS and name not in _lib.PAGED_SYMBOLS and callable(getattr(L, name)), name
-        assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name             # exported
-        entry, args = _lib.kv8_online_signature(bool(seq))
-        assert entry == name
-        declared = []
-        for param in m.group(1).replace("\n", " ").split(","):
-            kind, arg = param.strip().rsplit(" ", 1)
-            declared.append((arg, _lib._vp if kind.endswith("*") else ctype[kind]))
-        assert list(args) == declared and _lib.KV8_ONLINE_SYMBOLS[name] == [t for _, t in declared], name
-        # the argument list of dg_rope_attn_split_mx8(_seq)
-        assert args == _lib.attn_signature("dg_rope_attn_split", bool(seq), mx8=True)[1], name
+    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 9
+    held = _lib.DG_ATTN_MX8 | _lib.DG_ATTN_ONE_BARRIER
+    assert [attn_abi.PAIR[name] for name in NAMES] == [(_lib.DG_ATTN_SPLIT, held), (_lib.DG_ATTN_SPLIT, held | _lib.DG_ATTN_SEQ)]
     assert callable(decode_ops.rope_attn_online_mx8)
-    with pytest.raises(KeyError):
-        _lib.attn_signature("dg_rope_attn_online", mx8=True)               # the twelve and their KeyErrors stay what they were
-    assert "dg_rope_attn_online" in _lib.ATTN_BASES and not _lib.ATTN_BASES["dg_rope_attn_online"]
+    for flags in (_lib.DG_ATTN_MX8, _lib.DG_ATTN_MX8 | _lib.DG_ATTN_SEQ, held, held | _lib.DG_ATTN_SEQ):
+        assert attn_abi.launch(L, (_lib.DG_ATTN_ONLINE, flags)) == _lib.TG_E_LAYOUT, flags
 
 
 def test_argument_checks_return_their_codes_before_any_launch():
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
     L = _lib.load()
     buf = (ctypes.c_int32 * 64)()
@@ -61,7 +43,7 @@ def test_argument_checks_return_their_codes_before_any_launch():
 
     def call(name, **kw):
         a = dict(ok, **kw)
-        return getattr(L, name)(*[a[arg] for arg, _ in _lib.kv8_online_signature(name.endswith("_seq"))[1]])
+        return attn_abi.launch(L, name, a.pop("device"), a.pop("stream"), **a)
 
     need = L.dg_rope_attn_split_scratch_bytes(2, 4, 64, 4)
     for name in NAMES:

@@ -228,35 +228,21 @@ def test_tensor_parallel_paged_gloo():
     assert max(results.values()) < ATOL, dict(results)
 
 
-PAGED_SYMBOLS = ("dg_rope_attn_online_paged", "dg_rope_attn_split_paged", "dg_prefill_attn_paged")
+PAGED_FLAVOURS = ("dg_rope_attn_online_paged", "dg_rope_attn_split_paged", "dg_prefill_attn_paged")
 
 
 def test_paged_abi_preconditions_fail_before_any_launch():
-    """The three symbols are declared, exported and bound; the ABI version is still 8; argument validation returns its TG_E_* code before
-    the first HIP call (null stream, no GPU)."""
+    """The three paged 16-bit flavours of dg_attn_launch (DG_ATTN_SEQ | DG_ATTN_PAGED on the one-barrier, the split and the prefill kernel):
+    argument validation returns its TG_E_* code before the first HIP call (null stream, no GPU)."""
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
-    with open(os.path.join(ROOT, "include", "decode_glue_hip.h")) as f:
-        header = f.read()
     L = _lib.load()
-    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 8
-    for base, name in zip(_lib.ATTN_PAGED_BASES, PAGED_SYMBOLS):
-        m = re.search(r"DG_PAGED_API int " + name + r"\(([^;]*)\);", header)
-        assert m and name in _lib.PAGED_SYMBOLS and name not in _lib.SYMBOLS and callable(getattr(L, name)), name
-        assert hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name             # exported
-        entry, args = _lib.attn_signature(base, paged=True)
-        assert entry == name and callable(getattr(decode_ops, name[3:]))
-        # name for name and type for type the header's prototype (what tests/test_host_cpu.py checks for the unpaged twelve)
-        ctype = {"int64_t": _lib._i64, "int": ctypes.c_int, "float": ctypes.c_float, "tg_stream_t": _lib._vp}
-        declared = []
-        for param in m.group(1).replace("\n", " ").split(","):
-            kind, arg = param.strip().rsplit(" ", 1)
-            declared.append(("bs" if arg == "n" else arg, _lib._vp if kind.endswith("*") else ctype[kind]))
-        assert list(args) == declared and _lib.PAGED_SYMBOLS[name] == [t for _, t in declared], name
-    with pytest.raises(KeyError):
-        _lib.attn_signature("dg_rope_attn", paged=True)                    # no paged flavour of the 256-thread kernels
-    with pytest.raises(KeyError):
-        _lib.attn_signature("dg_prefill_attn", mx8=True, paged=True)       # nor of the mx8 caches
+    for name in PAGED_FLAVOURS:
+        assert callable(getattr(decode_ops, name[3:])), name
+    paged = _lib.DG_ATTN_SEQ | _lib.DG_ATTN_PAGED
+    assert attn_abi.launch(L, (_lib.DG_ATTN_GENERAL, paged)) == _lib.TG_E_LAYOUT               # no paged flavour of the 256-thread kernels
+    assert attn_abi.launch(L, (_lib.DG_ATTN_GENERAL, paged | _lib.DG_ATTN_MX8)) == _lib.TG_E_LAYOUT   # nor of their mx8 caches
 
     buf = (ctypes.c_int32 * 64)()
     base = ctypes.addressof(buf)
@@ -267,9 +253,9 @@ def test_paged_abi_preconditions_fail_before_any_launch():
 
     def call(name, **kw):
         a = dict(ok, **kw)
-        return getattr(L, name)(*[a[arg] for arg, _ in _lib.attn_signature(name[: -len("_paged")], paged=True)[1]])
+        return attn_abi.launch(L, name, a.pop("device"), a.pop("stream"), **a)
 
-    for name in PAGED_SYMBOLS:
+    for name in PAGED_FLAVOURS:
         for arg in ("table", "qkv", "pos", "k_pool", "v_pool", "out"):
             assert call(name, **{arg: None}) == -1, (name, arg)             # TG_E_NULL
         assert call(name, dtype=2) == -5, name                              # TG_E_DTYPE

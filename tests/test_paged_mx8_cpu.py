@@ -1,13 +1,11 @@
 """CPU suite: the paged mx8 KV cache, DecodeStack(..., ragged=True, kv_cache="mx8", kv_pages=N) -- four pools (E4M3 codes and exponent
-bytes) behind the one block table -- up to where a GPU is needed.  The two entry points dg_rope_attn_online_mx8_paged and
-dg_prefill_attn_mx8_paged: declared (DG_PAGED_KV8_API), exported, bound as a group of their own (PAGED_MX8_SYMBOLS), header and binding
-name for name and type for type, every argument check before the first HIP call (null stream, no GPU; the cases of
+bytes) behind the one block table -- up to where a GPU is needed.  The two flavours dg_rope_attn_online_mx8_paged and
+dg_prefill_attn_mx8_paged of dg_attn_launch: which (kernel, flags) pairs they are, every argument check before the first HIP call (null stream, no GPU; the cases of
 tests/test_paged_cpu.py and tests/test_kv8_online_cpu.py, merged).  The unfused float32 stack at head_dim 64 in the scenario of
 tests/test_paged_cpu.py against the contiguous ragged mx8 stack, bit for bit; release and reuse, fork, exhaustion, the shared-page
 refusal, tensor parallelism over gloo; and the refusal that stays (head_dim 16 / 32)."""
 import ctypes
 import os
-import re
 
 import pytest
 import torch
@@ -15,9 +13,7 @@ import torch
 from any4_amd.decode import DecodeConfig, DecodeLayer, DecodeStack
 from tests.test_decode_cpu import CFG, SeededDense
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("dg_rope_attn_online_mx8_paged", "dg_prefill_attn_mx8_paged")
-BASES = ("dg_rope_attn_online", "dg_prefill_attn")
 TG_E_NULL, TG_E_DTYPE, TG_E_SHAPE, TG_E_ALIGN = -1, -5, -7, -8
 ATOL = 1e-4  # tests/test_decode_cpu.py's tolerance for logits of the float32 stack (rows that were computed in batches of other shapes)
 PCFG = dict(CFG, head_dim=64, max_seq=512)  # (paged mx8 pools exist for head_dim 64 / 128; the rest is the suite's tiny configuration)
@@ -28,45 +24,28 @@ POOLS = ("k_pool", "v_pool", "k_exp_pool", "v_exp_pool")
 FLAT = ("k_cache", "v_cache", "k_exp", "v_exp")
 
 
-def test_symbols_are_declared_exported_and_bound_as_a_group_of_their_own():
+def test_the_flavours_and_the_pairs_next_to_them_that_the_library_refuses():
+    """DG_ATTN_SEQ | DG_ATTN_PAGED | DG_ATTN_MX8 on the prefill kernel and, held to the one-barrier kernel, on the split kind; what lies
+    next to them does not exist, and the library is what refuses it."""
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
-    with open(os.path.join(ROOT, "include", "decode_glue_hip.h")) as f:
-        header = f.read()
     L = _lib.load()
-    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 8
-    assert re.search(r"#define DG_PAGED_KV8_API TG_API\b", header)
-    assert tuple(_lib.PAGED_MX8_SYMBOLS) == NAMES
-    ctype = {"int64_t": _lib._i64, "int": ctypes.c_int, "float": ctypes.c_float, "tg_stream_t": _lib._vp}
-    for base, name in zip(BASES, NAMES):
-        m = re.search(r"DG_PAGED_KV8_API int " + name + r"\(([^;]*)\);", header)
-        assert m and not re.search(r"(TG_API|DG_PAGED_API|DG_KV8_API) int " + name + r"\(", header), name
-        assert name not in _lib.SYMBOLS and name not in _lib.PAGED_SYMBOLS and name not in _lib.KV8_ONLINE_SYMBOLS, name
-        assert callable(getattr(L, name)) and hasattr(ctypes.CDLL(_lib.LIB_PATH), name), name   # bound, exported
-        entry, args = _lib.paged_mx8_signature(base)
-        assert entry == name and callable(getattr(decode_ops, name[3:]))
-        declared = []
-        for param in m.group(1).replace("\n", " ").split(","):
-            kind, arg = param.strip().rsplit(" ", 1)
-            declared.append(("bs" if arg == "n" else arg, _lib._vp if kind.endswith("*") else ctype[kind]))
-        assert list(args) == declared and _lib.PAGED_MX8_SYMBOLS[name] == [t for _, t in declared], name
-    # the `_paged` lists with the exponent pools behind the code pools
-    for name, paged_base in zip(NAMES, ("dg_rope_attn_split", "dg_prefill_attn")):
-        want = [a for a, _ in _lib.attn_signature(paged_base, paged=True)[1]]
-        want[want.index("v_pool") + 1: want.index("v_pool") + 1] = ["k_exp", "v_exp"]
-        assert [a for a, _ in _lib.paged_mx8_signature(name[: -len("_mx8_paged")])[1]] == want, name
-    # the three existing groups and their KeyErrors are what they were
-    assert len(_lib.PAGED_SYMBOLS) == 3 and len(_lib.KV8_ONLINE_SYMBOLS) == 2
-    assert sum(n.startswith(("dg_rope_attn", "dg_prefill_attn")) and n != "dg_rope_attn_split_scratch_bytes" for n in _lib.SYMBOLS) == 12
-    for bad in (lambda: _lib.attn_signature("dg_prefill_attn", mx8=True, paged=True), lambda: _lib.attn_signature("dg_rope_attn_split", mx8=True, paged=True),
-                lambda: _lib.attn_signature("dg_rope_attn_online", mx8=True), lambda: _lib.paged_mx8_signature("dg_rope_attn_split"),
-                lambda: _lib.paged_mx8_signature("dg_rope_attn")):
-        with pytest.raises(KeyError):
-            bad()
+    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 9
+    pools8 = _lib.DG_ATTN_SEQ | _lib.DG_ATTN_PAGED | _lib.DG_ATTN_MX8
+    assert [attn_abi.PAIR[name] for name in NAMES] == [(_lib.DG_ATTN_SPLIT, pools8 | _lib.DG_ATTN_ONE_BARRIER), (_lib.DG_ATTN_PREFILL, pools8)]
+    for name in NAMES:
+        assert callable(getattr(decode_ops, name[3:])), name
+    for pair in ((_lib.DG_ATTN_SPLIT, pools8),                              # no paged-mx8 flavour of the 256-thread split kernel
+                 (_lib.DG_ATTN_ONLINE, pools8), (_lib.DG_ATTN_ONLINE, _lib.DG_ATTN_MX8),   # no mx8 flavour of the plain one-barrier kind
+                 (_lib.DG_ATTN_GENERAL, pools8), (_lib.DG_ATTN_GENERAL, pools8 | _lib.DG_ATTN_ONE_BARRIER),
+                 (_lib.DG_ATTN_PREFILL, pools8 | _lib.DG_ATTN_ONE_BARRIER), (_lib.DG_ATTN_PREFILL, pools8 & ~_lib.DG_ATTN_SEQ)):
+        assert attn_abi.launch(L, pair) == _lib.TG_E_LAYOUT, pair
 
 
 def test_argument_checks_return_their_codes_before_any_launch():
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
     L = _lib.load()
     buf = (ctypes.c_int32 * 64)()
@@ -79,7 +58,7 @@ def test_argument_checks_return_their_codes_before_any_launch():
 
     def call(name, **kw):
         a = dict(ok, **kw)
-        return getattr(L, name)(*[a[arg] for arg, _ in _lib.paged_mx8_signature(name[: -len("_mx8_paged")])[1]])
+        return attn_abi.launch(L, name, a.pop("device"), a.pop("stream"), **a)
 
     decode, prefill = NAMES
     need = L.dg_rope_attn_split_scratch_bytes(2, 4, 64, 4)

@@ -129,12 +129,12 @@ def test_tensor_parallel_prefill_gloo():
 
 
 def test_dg_prefill_attn_abi_preconditions_fail_before_any_launch():
-    """The symbol is exported and bound; argument validation returns its TG_E_* code before the first HIP call (null stream, no GPU)."""
+    """DG_ATTN_PREFILL with no flags: argument validation returns its TG_E_* code before the first HIP call (null stream, no GPU)."""
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
-    assert "dg_prefill_attn" in _lib.SYMBOLS and callable(decode_ops.prefill_attn)
+    assert callable(decode_ops.prefill_attn)
     L = _lib.load()
-    f = L.dg_prefill_attn
     buf = (ctypes.c_int32 * 64)()
     base = ctypes.addressof(buf)
     p = ctypes.c_void_p(base + (-base) % 16)      # 16-byte aligned
@@ -142,9 +142,7 @@ def test_dg_prefill_attn_abi_preconditions_fail_before_any_launch():
     ok = dict(qkv=p, cos=p, sin=p, pos=p, k=p, v=p, out=p, bs=1, T=4, hl=4, kvl=2, d=64, max_seq=128, scale=0.125, dtype=0)
 
     def call(**kw):
-        a = dict(ok, **kw)
-        return f(a["qkv"], a["cos"], a["sin"], a["pos"], a["k"], a["v"], a["out"], a["bs"], a["T"], a["hl"], a["kvl"], a["d"],
-                 a["max_seq"], a["scale"], a["dtype"], 0, None)
+        return attn_abi.launch(L, "dg_prefill_attn", **dict(ok, **kw))
 
     for name in ("qkv", "cos", "sin", "pos", "k", "v", "out"):
         assert call(**{name: None}) == -1, name                      # TG_E_NULL

@@ -250,18 +250,14 @@ SEQ_SYMBOLS = ("dg_rope_attn_seq", "dg_rope_attn_online_seq", "dg_rope_attn_spli
 
 
 def test_per_sequence_abi_preconditions_fail_before_any_launch():
-    """The four symbols are declared, exported and bound; argument validation returns its TG_E_* code before the first HIP call
-    (null stream, no GPU)."""
+    """The four per-sequence flavours of dg_attn_launch (DG_ATTN_SEQ on each kernel): argument validation returns its TG_E_* code before
+    the first HIP call (null stream, no GPU)."""
     import inspect
 
     from any4_amd import _lib, decode_ops
+    from tests import attn_abi
 
-    with open(os.path.join(ROOT, "include", "decode_glue_hip.h")) as f:
-        header = f.read()
     L = _lib.load()
-    assert L.tg_abi_version() == 8
-    for name in SEQ_SYMBOLS:
-        assert f"TG_API int {name}(" in header and name in _lib.SYMBOLS and callable(getattr(L, name)), name
     for fn in (decode_ops.rope_attn, decode_ops.rope_attn_online, decode_ops.rope_attn_split, decode_ops.prefill_attn):
         assert inspect.signature(fn).parameters["per_sequence"].default is False
     for name in ("lengths", "slots"):
@@ -276,9 +272,7 @@ def test_per_sequence_abi_preconditions_fail_before_any_launch():
               dtype=0)
 
     def prefill(**kw):
-        a = dict(ok, **kw)
-        return L.dg_prefill_attn_seq(a["qkv"], a["cos"], a["sin"], a["pos"], a["len"], a["slot"], a["k"], a["v"], a["out"], a["n"], a["T"],
-                                     a["cache_bs"], a["hl"], a["kvl"], a["d"], a["max_seq"], a["scale"], a["dtype"], 0, None)
+        return attn_abi.launch(L, "dg_prefill_attn_seq", **dict(ok, **kw))
 
     for name in ("qkv", "cos", "sin", "pos", "k", "v", "out"):
         assert prefill(**{name: None}) == -1, name                   # TG_E_NULL
@@ -290,12 +284,7 @@ def test_per_sequence_abi_preconditions_fail_before_any_launch():
         assert prefill(**{name: odd}) == -8, name                    # TG_E_ALIGN
 
     def step(name, **kw):
-        a = dict(dict(ok, bs=2, scratch=p, scratch_bytes=1 << 20, nsplit=4), **kw)
-        head = (a["qkv"], a["cos"], a["sin"], a["pos"], a["k"], a["v"], a["out"])
-        tail = (a["bs"], a["hl"], a["kvl"], a["d"], a["max_seq"], a["scale"])
-        if name == "dg_rope_attn_split_seq":
-            return getattr(L, name)(*head, a["scratch"], a["scratch_bytes"], *tail, a["nsplit"], a["dtype"], 0, None)
-        return getattr(L, name)(*head, *tail, a["dtype"], 0, None)
+        return attn_abi.launch(L, name, **dict(dict(ok, bs=2, scratch=p, scratch_bytes=1 << 20, nsplit=4), **kw))
 
     for name in SEQ_SYMBOLS[:3]:
         assert step(name, pos=None) == -1, name

@@ -42,7 +42,7 @@ position near 512, 4096 and the end of an 8192-position cache; one JSON line per
     python tools/llama_decode_bench.py --config llama3_8b --paged --kv-cache mx8 [--out profiles/paged_mx8_bench.jsonl]
 
 --paged --kv-cache mx8 (one GPU): the same two legs with mx8 stacks -- leg (a) alternates the contiguous mx8 stack
-with mx8_attention="online" (dg_rope_attn_online_mx8_seq) against the paged mx8 stack (dg_rope_attn_online_mx8_paged), the same kernel
+with mx8_attention="online" (the dg_rope_attn_online_mx8_seq flavour of dg_attn_launch) against the paged mx8 stack (dg_rope_attn_online_mx8_paged), the same kernel
 with and without the page lookup; leg (b) reports the bytes of the four mx8 pools for the eight prompts.
 
     python tools/llama_decode_bench.py --config llama3_8b --sample [--out profiles/sample_bench.jsonl]

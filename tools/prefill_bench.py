@@ -1,11 +1,11 @@
-"""Prompt prefill: dg_prefill_attn at the kernel level and DecodeStack.prefill at the stack level.  Needs a GPU.
+"""Prompt prefill: the prefill kernel (DG_ATTN_PREFILL of dg_attn_launch) at the kernel level and DecodeStack.prefill at the stack level.  Needs a GPU.
 
     python tools/prefill_bench.py [--kernel] [--stack] [--config llama3_8b] [--baseline] [--profile] [--iters 20] [--rounds 5]
 
 Kernel level (--kernel): Llama-3-8B heads (32 / 8 x 128) and Llama-2 heads (32 / 32 x 128), bs = 1, bf16, max_seq 4096, T = 128 / 512 /
 2048 / 4096 at p0 = 0 and the chunked case T = 2048 at p0 = 2048.  Two legs ALTERNATING in one process (rounds x iters launches each, CUDA
 events, the median round reported):
-  prefill_attn  dg_prefill_attn (rope + cache append + causal flash attention, two launches)
+  prefill_attn  decode_ops.prefill_attn (rope + cache append + causal flash attention, two launches)
   sdpa          what torch offers for the same step: rope of q and k with the table rows, index_copy_ of the T rows into the caches,
                 torch.nn.functional.scaled_dot_product_attention over cache[:, :, :p0 + T] (is_causal=True at p0 = 0, a mask otherwise)
 TFLOP/s counts 4 d hl (number of unmasked (t, s) pairs); `peak_frac` is against the 2.5 PFLOP/s bf16 MFMA peak.
