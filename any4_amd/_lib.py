@@ -88,6 +88,25 @@ class Attn(ctypes.Structure):
             self.struct_bytes = ctypes.sizeof(Attn)
 
 
+DG_MOE_GATE_UP, DG_MOE_DOWN = 0, 1
+
+
+class MoeW4(ctypes.Structure):
+    """struct dg_moe_w4 (include/decode_glue_hip.h)"""
+
+    _fields_ = [
+        ("struct_bytes", _u32), ("stage", _i32),
+        ("x", _vp), ("w", _vp), ("qinfo", _vp), ("lut", _vp), ("y", _vp), ("ids", _vp), ("gates", _vp), ("residual", _vp),
+        ("stride_w", _i64), ("stride_qinfo", _i64), ("stride_lut", _i64), ("m", _i64), ("wrows", _i64), ("k", _i64),
+        ("E", _i32), ("top_k", _i32), ("group", _i32), ("qtype", _i32), ("dtype", _i32), ("inner_k_tiles", _i32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = ctypes.sizeof(MoeW4)
+
+
 # (kernel, flags) -> the name the call had as an entry point of its own up to ABI 8: DG_ATTN_FLAVOURS of the header, which is what
 # dg_attn_launch accepts; error messages keep these names.  A copy written by hand (the header is not read at run time): a new flavour
 # gets its row here as well as there, and tests/test_host_cpu.py fails until the two agree.
@@ -167,6 +186,10 @@ SYMBOLS = {
     "dg_lora_shrink": [_vp] * 5 + [_i64] * 5 + [ctypes.c_float, ctypes.c_int, ctypes.c_int, _vp],
     # t, B, scale, idx, y, m, n, r, ldy, n_adapters, rows_per_id, dtype, device, stream
     "dg_lora_expand": [_vp] * 5 + [_i64] * 6 + [ctypes.c_int, ctypes.c_int, _vp],
+    # mixture of experts: x, router_w, ids, gates, m, k, E, top_k, dtype, device, stream
+    "dg_moe_route": [_vp] * 4 + [_i64] * 4 + [ctypes.c_int, ctypes.c_int, _vp],
+    "dg_moe_w4_launch": [ctypes.POINTER(MoeW4), ctypes.c_int, _vp],
+    "dg_moe_w4_plan": [ctypes.POINTER(MoeW4), ctypes.c_int, ctypes.POINTER(_i32)],
 }
 # Up to ABI 8 three groups of attention entry points were bound from tables of their own.  Nothing is any more, and nothing in this
 # tree reads these; the names stay, empty, so that a module written against that binding, which merges the four tables when it is

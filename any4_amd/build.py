@@ -37,6 +37,7 @@ UNITS = [
     ("tg_prefill", "tg_prefill.hip", []),
     ("tg_sample", "tg_sample.hip", []),
     ("tg_lora", "tg_lora.hip", []),
+    ("tg_moe", "tg_moe.hip", []),
     ("tinygemm_hip", "tinygemm_hip.hip", []),
 ]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-comment", "-Wno-int-to-pointer-cast"]

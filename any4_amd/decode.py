@@ -71,6 +71,10 @@ class DecodeConfig:
     # rows, the order the GEMM's fused SwiGLU epilogue wants (tg_w4_gemm.epilogue): a gate row and its up row then meet in one
     # 16-row tile of one workgroup.  `shard_rows` returns the row indices in this order, so a loader needs nothing else.
     gate_up_interleave: int = 0
+    # mixture of experts (any4_amd/moe.py): 0 = a dense MLP (nothing changes anywhere); E > 0 = every layer holds E gate_up / down pairs and
+    # a router, and a token runs `experts_per_token` of them.  Needs gate_up_interleave = 8 (the stacked experts' row order).
+    experts: int = 0
+    experts_per_token: int = 2
 
     @classmethod
     def llama3_8b(cls, **kw) -> "DecodeConfig":
@@ -82,6 +86,13 @@ class DecodeConfig:
         return cls(hidden=4096, inter=11008, layers=32, heads=32, kv_heads=32, head_dim=128, vocab=32000,
                    rope_theta=10000.0, **kw)
 
+    @classmethod
+    def mixtral_8x7b(cls, **kw) -> "DecodeConfig":
+        # the mixture-of-experts model of the reference's results table (README: Mixtral-8x7B-Instruct)
+        kw = {**dict(hidden=4096, inter=14336, layers=32, heads=32, kv_heads=8, head_dim=128, vocab=32000, rope_theta=1e6, experts=8,
+                     experts_per_token=2, gate_up_interleave=8), **kw}
+        return cls(**kw)
+
     def linear_shapes(self):
         """(name, out_features, in_features) of the four fused linears of one layer."""
         qkv = (self.heads + 2 * self.kv_heads) * self.head_dim
@@ -91,8 +102,12 @@ class DecodeConfig:
     def weight_bytes_4bit(self) -> int:
         """Algorithmic bytes one decode step streams through the quantized linears (bench.py formula, m=1)."""
         total = 0
-        for _, n, k in self.linear_shapes():
-            total += n * k // 2 + (k // self.group_size) * n * 4 + 32 * n + k * 2 + n * 2
+        for name, n, k in self.linear_shapes():
+            one = n * k // 2 + (k // self.group_size) * n * 4 + 32 * n + k * 2 + n * 2
+            # (experts: a token streams the experts the router selected, and the 16-bit router)
+            total += one * self.experts_per_token if self.experts and name in ("gate_up", "down") else one
+        if self.experts:
+            total += self.experts * self.hidden * 2
         return total * self.layers
 
 
@@ -289,8 +304,23 @@ class DecodeLayer(torch.nn.Module):
         d = cfg.head_dim
         self.qkv = factory("qkv", idx, cfg.hidden, (self.hl + 2 * self.kvl) * d)
         self.o = factory("o", idx, cfg.heads * d, cfg.hidden // world)
-        self.gate_up = factory("gate_up", idx, cfg.hidden, 2 * cfg.inter // world)
-        self.down = factory("down", idx, cfg.inter, cfg.hidden // world)
+        self.moe = None
+        if cfg.experts:
+            # E gate_up / down pairs from the factory, stacked (expert e at base + e * stride) and dropped; the router from its generator
+            from .moe import MoEMLP, MoEWeights
+
+            if world > 1:
+                raise ValueError("experts with world > 1: tensor parallelism for experts is not built yet")
+            if cfg.gate_up_interleave != 8:
+                raise ValueError("experts need gate_up_interleave = 8 (the row order of the stacked gate / up weights)")
+            gus = [factory("gate_up", idx, cfg.hidden, 2 * cfg.inter) for _ in range(cfg.experts)]
+            downs = [factory("down", idx, cfg.inter, cfg.hidden) for _ in range(cfg.experts)]
+            router = torch.randn(cfg.experts, cfg.hidden, device=device, generator=getattr(factory, "gen", None)) / math.sqrt(cfg.hidden)
+            self.moe = MoEMLP(router.to(dtype), MoEWeights.from_linears(gus, downs), cfg.experts_per_token)
+            self.gate_up = self.down = None
+        else:
+            self.gate_up = factory("gate_up", idx, cfg.hidden, 2 * cfg.inter // world)
+            self.down = factory("down", idx, cfg.inter, cfg.hidden // world)
         self.norm1 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.norm2 = RMSNorm(cfg.hidden, cfg.rms_eps, device, dtype)
         self.kv = KVCache(cfg, self.kvl, bs, device, dtype, kv_cache, kv_pages, page_size, mx8_attention)  # (refuses what check_cache_config refuses)
@@ -366,6 +396,8 @@ class DecodeLayer(torch.nn.Module):
     def _mlp_torch(self, h, gather, lora=None):
         """The plain-torch MLP block behind either attention: h + down(silu(gate) * up) of norm2(h)."""
         xn = self.norm2(h)
+        if self.moe is not None:
+            return self.moe(xn, residual=h, fused=False)
         gu = self._split_gate_up(self._adapted(lora, "gate_up", xn, self.gate_up(xn)))
         il = self.cfg.inter // self.world
         act = gather(torch.nn.functional.silu(gu[:, :il]) * gu[:, il:])
@@ -391,6 +423,8 @@ class DecodeLayer(torch.nn.Module):
         h, y = G.add_rmsnorm(h, delta, self.norm1.weight, self.norm1.eps)
         ctx = gather(attention(self._adapted(lora, "qkv", y, self.qkv(y)), pos, cos_tab, sin_tab))
         h, y = G.add_rmsnorm(h, gather(self._adapted(lora, "o", ctx, self.o(ctx))), self.norm2.weight, self.norm2.eps)
+        if self.moe is not None:  # route, gate_up, down: the block's output is the layer's delta
+            return h, self.moe(y)
         act = gather(G.swiglu(self._split_gate_up(self._adapted(lora, "gate_up", y, self.gate_up(y))).contiguous()))
         return h, gather(self._adapted(lora, "down", act, self.down(act)))
 
@@ -417,6 +451,9 @@ class DecodeLayer(torch.nn.Module):
     def launches(self) -> int:
         """Kernel launches of one decode step of this layer on the fused path (after the first step has settled `_fuse`)."""
         f = self._fuse
+        if self.moe is not None:
+            # qkv GEMM, attention, o GEMM (+ residual), norm2, route, gate_up, down (+ residual); norm1 as in the dense layer
+            return 7 + (0 if f.get("norm1") else 1) + (0 if self.adapters is None else 2 * len(self.adapters.targets))
         n = 5  # qkv GEMM, attention, o GEMM (+ residual), gate_up GEMM, down GEMM (+ residual)
         n += 0 if f.get("norm1") else 1                      # RMSNorm in front of qkv as its own launch
         if not f.get("mlp"):
@@ -430,7 +467,8 @@ class DecodeLayer(torch.nn.Module):
         """The four linears hold Bint4 weights behind the row-major weights-on-the-right kernel (what w4_linear_fused drives)."""
         ok = ("linear_y_f16RM_x_f16RM_W_any4TC", "linear_y_f16RM_x_f16RM_W_int4TC")
         return all(getattr(m, "kernel", None) in ok and getattr(m, "weight_reshaped", False) and getattr(m, "bias", None) is None
-                   for m in (self.qkv, self.o, self.gate_up, self.down))
+                   for m in ((self.qkv, self.o) if self.moe is not None else (self.qkv, self.o, self.gate_up, self.down))) and \
+            (self.moe is None or not self.moe.weights.dense)
 
     def _split_gate_up(self, gu):
         """[bs, 2 il] in the weight's row order -> contiguous [gate | up] halves (what dg_swiglu reads)."""
@@ -462,6 +500,8 @@ class DecodeLayer(torch.nn.Module):
             G.add_rmsnorm(h, self._adapted(lora, "o", ctx, self.o(ctx)), n2.weight, n2.eps, want_norm=False)
         else:
             self._adapted(lora, "o", ctx, h)
+        if self.moe is not None:  # norm2 as its own launch, then route, gate_up, down with the residual add in its store
+            return self.moe(G.add_rmsnorm(h, None, n2.weight, n2.eps)[1], residual=h, out=h)
         # MLP block: norm2 + SwiGLU inside the gate_up launch ("mlp"; the store needs the 8 + 8 row order); else whichever of the two
         # the library can fuse (a block too large to stage on chip has no fused norm, "norm2", but still the SwiGLU store, "swiglu")
         il8 = self.cfg.gate_up_interleave == 8 and not (lora is not None and lora.has("gate_up"))
@@ -545,6 +585,8 @@ class DecodeStack(torch.nn.Module):
         check_cache_config(cfg, kv_cache, kv_pages, page_size, mx8_attention)
         self.kv_cache, self.mx8_attention = kv_cache, mx8_attention
         if adapters is not None:
+            if cfg.experts and {"gate_up", "down"} & set(adapters.targets):
+                raise ValueError("adapters on gate_up / down with experts: LoRA on expert linears is not built yet")
             if world > 1:
                 raise ValueError("adapters need world == 1 (row-sharding an adapter's B across ranks is not implemented)")
             want = {name: (n, k) for name, n, k in cfg.linear_shapes() if name in adapters.targets}

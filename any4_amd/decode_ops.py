@@ -405,6 +405,92 @@ def lora_expand(t: torch.Tensor, B: torch.Tensor, scale: torch.Tensor, idx: torc
     return y
 
 
+def moe_route(x: torch.Tensor, router_w: torch.Tensor, top_k: int, ids: torch.Tensor = None, gates: torch.Tensor = None):
+    """(ids int32 [m, top_k], gates float32 [m, top_k]) of the top-k router (any4_amd/moe.py: moe_ref is the definition): x [m, k] 16-bit
+    (normed), router_w [E, k] of x's dtype; f32 logits, softmax over all E, the top_k by (p descending, index ascending), gates
+    renormalised over the selected.  ids / gates: the buffers to fill."""
+    _gpu(x, router_w, ids, gates)
+    if x.dim() != 2 or router_w.dim() != 2 or router_w.shape[1] != x.shape[1] or router_w.dtype != x.dtype:
+        raise RuntimeError(f"moe_route: x [m, k] and router_w [E, k] of one 16-bit dtype needed, got {tuple(x.shape)} {x.dtype} and "
+                           f"{tuple(router_w.shape)} {router_w.dtype}")
+    m, k = x.shape
+    E, top_k = router_w.shape[0], int(top_k)
+    if ids is None:
+        ids = torch.empty((m, top_k), dtype=torch.int32, device=x.device)
+    if gates is None:
+        gates = torch.empty((m, top_k), dtype=torch.float32, device=x.device)
+    if ids.dtype != torch.int32 or gates.dtype != torch.float32 or tuple(ids.shape) != (m, top_k) or tuple(gates.shape) != (m, top_k):
+        raise RuntimeError(f"moe_route: ids int32 and gates float32 [{m}, {top_k}] needed")
+    _lib.check(_lib.load().dg_moe_route(x.data_ptr(), router_w.data_ptr(), ids.data_ptr(), gates.data_ptr(), m, k, E, top_k, _dt(x),
+                                        x.device.index, _stream(x)), "dg_moe_route")
+    return ids, gates
+
+
+def moe_call(stage: int, x, stack, ids, gates=None, residual=None, y=None, m=None) -> "_lib.MoeW4":
+    """struct dg_moe_w4 for one stage on an `any4_amd.moe.ExpertStack` (its tensors are contiguous: a stride is one expert's bytes)."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    per = lambda t: 0 if t is None else t[0].numel() * t.element_size()
+    return _lib.MoeW4(stage=stage, x=ptr(x), w=ptr(stack.words), qinfo=ptr(stack.qinfo), lut=ptr(stack.lut), y=ptr(y), ids=ptr(ids),
+                      gates=ptr(gates), residual=ptr(residual), stride_w=per(stack.words), stride_qinfo=per(stack.qinfo),
+                      stride_lut=per(stack.lut), m=ids.shape[0] if m is None else m, wrows=stack.n, k=stack.k, E=stack.E, top_k=ids.shape[1],
+                      group=stack.group, qtype=stack.qtype, dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16,
+                      inner_k_tiles=4)
+
+
+def _moe_check(what, x, stack, ids, rows):
+    _gpu(x, stack.words, stack.qinfo, stack.lut, ids)
+    if ids.dtype != torch.int32 or ids.dim() != 2:
+        raise RuntimeError(f"{what}: ids must be int32 [m, top_k], got {ids.dtype} {tuple(ids.shape)}")
+    if x.dim() != 2 or tuple(x.shape) != (rows, stack.k) or x.dtype != stack.dtype:
+        raise RuntimeError(f"{what}: x must be [{rows}, {stack.k}] {stack.dtype}, got {tuple(x.shape)} {x.dtype}")
+
+
+def moe_gate_up(x: torch.Tensor, stack, ids: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """act [m * top_k, il]: row i * top_k + s = SwiGLU of x[i] through the gate / up weights of expert ids[i, s] (DG_MOE_GATE_UP; `stack`
+    an ExpertStack [2 il, k] with rows in blocks of 8 gate + 8 up).  A pair whose id is outside [0, E) gets zeros."""
+    m, top_k = ids.shape
+    _moe_check("moe_gate_up", x, stack, ids, m)
+    if out is None:
+        out = torch.empty((m * top_k, stack.n // 2), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or tuple(out.shape) != (m * top_k, stack.n // 2) or not out.is_contiguous():
+        raise RuntimeError(f"moe_gate_up: out must be contiguous [{m * top_k}, {stack.n // 2}] {x.dtype}")
+    call = moe_call(_lib.DG_MOE_GATE_UP, x, stack, ids, y=out)
+    _lib.check(_lib.load().dg_moe_w4_launch(ctypes.byref(call), x.device.index, _stream(x)), "dg_moe_w4_launch")
+    return out
+
+
+def moe_down(act: torch.Tensor, stack, ids: torch.Tensor, gates: torch.Tensor, residual: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
+    """y [m, n] = RNE16(sum_s gates[i, s] * (act[i * top_k + s] through the down weights of expert ids[i, s]) (+ residual[i]))
+    (DG_MOE_DOWN).  out may be `residual` itself (the residual stream, updated in place: an element is read and written by one thread)."""
+    m, top_k = ids.shape
+    _moe_check("moe_down", act, stack, ids, m * top_k)
+    _gpu(gates, residual, out)
+    if gates.dtype != torch.float32 or tuple(gates.shape) != (m, top_k):
+        raise RuntimeError(f"moe_down: gates must be float32 [{m}, {top_k}]")
+    if residual is not None and (residual.dtype != act.dtype or tuple(residual.shape) != (m, stack.n)):
+        raise RuntimeError(f"moe_down: residual must be [{m}, {stack.n}] {act.dtype}")
+    if out is None:
+        out = torch.empty((m, stack.n), dtype=act.dtype, device=act.device)
+    elif out.dtype != act.dtype or tuple(out.shape) != (m, stack.n):
+        raise RuntimeError(f"moe_down: out must be [{m}, {stack.n}] {act.dtype}")
+    call = moe_call(_lib.DG_MOE_DOWN, act, stack, ids, gates, residual, out)
+    _lib.check(_lib.load().dg_moe_w4_launch(ctypes.byref(call), act.device.index, _stream(act)), "dg_moe_w4_launch")
+    return out
+
+
+def moe_plan(stage: int, stack, m: int, top_k: int, device: int = -1):
+    """(workgroups, 16-row units per workgroup, pairs per sweep, waves that own part of k) of a launch (dg_moe_w4_plan; nothing is
+    launched; device < 0: planned for 256 compute units, no GPU needed)."""
+    buf = ctypes.create_string_buffer(256)
+    p = (ctypes.addressof(buf) + 63) & ~63  # a non-NULL, aligned dummy: the planner dereferences nothing
+    call = _lib.MoeW4(stage=stage, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=m,
+                      wrows=stack.n, k=stack.k, E=stack.E, top_k=top_k, group=stack.group, qtype=stack.qtype,
+                      dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
+    out = (ctypes.c_int32 * 4)()
+    _lib.check(_lib.load().dg_moe_w4_plan(ctypes.byref(call), device, out), "dg_moe_w4_plan")
+    return tuple(out)
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """gu [bs, 2 il] = [gate | up] -> silu(gate) * up [bs, il]."""
     _gpu(gu)

@@ -301,6 +301,77 @@ TG_API int dg_lora_shrink(const void* x, const void* norm_weight, const void* A,
 TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, const int32_t* idx, void* y, int64_t m, int64_t n, int64_t r,
                           int64_t ldy, int64_t n_adapters, int64_t rows_per_id, int dtype, int device, tg_stream_t stream);
 
+/* ---- mixture of experts (MoE) for a decode step: a top-k router and a 4-bit GEMV whose weights are picked by expert ids on the device ----
+ * The definition is any4_amd/moe.py: moe_ref.  Three launches serve one sparse MLP block: route, gate_up, down; all three read their
+ * indices on the device, so a captured graph follows the router from replay to replay.  New symbols within ABI 9: probe for them.
+ *
+ * dg_moe_route   x [m][k] 16-bit (already normed), router_w [E][k] 16-bit.  l[i][e] = sum_c router_w[e][c] x[i][c] in f32, NOT rounded to
+ *   16 bit; p = softmax(l[i]) over all E in f32; the top_k largest p ordered by (p descending, expert index ascending: a tie goes to the
+ *   lower index) -> ids int32 [m][top_k]; gates float [m][top_k], g[i][s] = p_s / (p_0 + ... + p_{top_k-1}), the sum in slot order.
+ *   E in 1 ... 64, top_k in 1 ... min(E, 8), k % 8 == 0 (TG_E_K_DIV), any m >= 1.  NaN or infinite logits are out of contract; even then
+ *   every id written is in [0, E) and a row's ids are distinct.  Sums run in a fixed order: the same inputs give the same bits.
+ *   TG_E_NULL, TG_E_DTYPE, TG_E_SHAPE, TG_E_K_DIV, TG_E_SIZE (k > 2^20), TG_E_ALIGN (x, router_w off 16 bytes; ids, gates off 4).
+ *
+ * dg_moe_w4_launch   one layer's experts are STACKED: expert e of an operand sits at base + e * stride (bytes, a multiple of 16):
+ *     w      Bint4 words [E][wrows / 8][k / 64][32][2] int32 (tg_convert_to_Bint4 at innerKTiles 4, per expert)
+ *     qinfo  scales_and_zeros [E][k / group][wrows][2] 16-bit
+ *     lut    [E][wrows][16] (TG_Q_ANY4_ROWWISE) or [E][16] (TG_Q_ANY4_GLOBAL) 16-bit; not read for TG_Q_INT4
+ *   ids int32 [m][top_k]: pair (i, s) = activation row i, slot s.  An id outside [0, E) is never turned into an address.
+ *   Numerics are TG_NUM_FAST's: f32 sums of the looked-up values times the activations per group, the group's scale and zero applied to
+ *   the partial sums.
+ *   stage DG_MOE_GATE_UP   x [m][k] (the top_k slots of a row share it); weight rows in blocks of 16 = 8 gate + 8 up rows (TG_EPI_SWIGLU's
+ *                          order); y [m * top_k][wrows / 2], row i * top_k + s = RNE16(RNE16(silu(RNE16(gate))) RNE16(up)) of expert
+ *                          ids[i][s] (dg_swiglu's rounding points).  A pair with an invalid id gets a row of zeros.
+ *   stage DG_MOE_DOWN      x [m * top_k][k], one row per pair; gates float [m][top_k]; residual [m][wrows] 16-bit or NULL;
+ *                          y[i] = RNE16(sum_s gates[i][s] d_s (+ residual[i])), d_s the unrounded f32 sum of pair (i, s).  The terms are
+ *                          added by fused multiply-add in the order (expert id ascending, then slot ascending), the residual last: the
+ *                          order depends on ids alone, so the same inputs give the same bits on every launch.  A pair with an invalid
+ *                          id contributes nothing; a row without a valid pair gets RNE16(residual), or zeros.
+ *   int4 and any4, inner_k_tiles 4, group 64 / 128 / 256, k % 64 == 0, wrows % 16 == 0.  m <= 8 is one launch; larger m is issued as
+ *   ceil(m / 8) launches on the caller's stream (every block of 8 rows re-reads its experts: prefill is correct, not fast).
+ *   Within a launch a selected expert's rows cross the memory interface once per workgroup range as long as at most `pairs per sweep`
+ *   (dg_moe_w4_plan: 8; fewer from k of about 4800 on, because the sweep's activation rows are staged in LDS) pairs chose it; an unselected
+ *   expert's bytes are never requested.  No atomics, no scratch, no allocation, no synchronisation.
+ *   In this order: call == NULL TG_E_NULL; struct_bytes TG_E_STRUCT; stage TG_E_LAYOUT; a required pointer (x, w, qinfo, y, ids; lut for
+ *   any4; gates for DOWN) TG_E_NULL; TG_E_DTYPE; TG_E_QTYPE (mx4, int8); TG_E_SHAPE (m < 1, E outside 1 ... 64, top_k outside
+ *   1 ... min(E, 8), k % 64, wrows % 16); TG_E_SIZE (an expert beyond 2^31 bytes, k beyond what LDS stages); TG_E_INNER_K; TG_E_GROUP;
+ *   TG_E_ALIGN (an operand off 16 bytes, ids or gates off 4, a stride that is no multiple of 16).  Nothing is launched in these cases.
+ * dg_moe_w4_plan   the launch plan of the call's first row block, for tests and tools: out[0] workgroups, out[1] 16-row units per
+ *   workgroup, out[2] pairs per sweep, out[3] waves that own part of k.  device < 0: planned for 256 compute units, without a device. */
+#define DG_MOE_GATE_UP 0
+#define DG_MOE_DOWN 1
+
+/* One call.  C: `struct dg_moe_w4 c = {sizeof c};`.  Pointers and 64-bit fields stand in front of the 32-bit ones: no hidden padding. */
+typedef struct dg_moe_w4 {
+  uint32_t struct_bytes;  /* sizeof(struct dg_moe_w4); anything else is TG_E_STRUCT */
+  int32_t stage;          /* DG_MOE_GATE_UP / DG_MOE_DOWN */
+  const void* x;
+  const void* w;
+  const void* qinfo;
+  const void* lut;
+  void* y;
+  const int32_t* ids;
+  const float* gates;     /* DG_MOE_DOWN */
+  const void* residual;   /* DG_MOE_DOWN, optional */
+  int64_t stride_w;       /* bytes between experts */
+  int64_t stride_qinfo;
+  int64_t stride_lut;
+  int64_t m;
+  int64_t wrows;
+  int64_t k;
+  int32_t E;
+  int32_t top_k;
+  int32_t group;
+  int32_t qtype;          /* TG_Q_INT4 / TG_Q_ANY4_GLOBAL / TG_Q_ANY4_ROWWISE */
+  int32_t dtype;          /* TG_BF16 / TG_F16 */
+  int32_t inner_k_tiles;  /* 4 */
+} dg_moe_w4;
+
+TG_API int dg_moe_route(const void* x, const void* router_w, int32_t* ids, float* gates, int64_t m, int64_t k, int64_t E, int64_t top_k,
+                        int dtype, int device, tg_stream_t stream);
+TG_API int dg_moe_w4_launch(const dg_moe_w4* call, int device, tg_stream_t stream);
+TG_API int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -59,6 +59,14 @@ appended to --out: the captured step near position 512 (a) without adapters, (b)
 of the eight added launches per layer --, (c) every sequence on adapter 0, (d) a different adapter per sequence (bs = 8), (e) the torch
 formulation of the deltas (index_select + bmm) behind the same fused step.  The legs alternate in one process, three runs each, the order
 rotating; (b), (c) and (d) replay one captured graph and differ only in `adapter_ids`.
+
+    python tools/llama_decode_bench.py --moe [--layers N] [--out profiles/moe_bench.jsonl]
+
+--moe (one GPU): mixture of experts at the Mixtral-8x7B shape (8 experts, 2 per token), two JSON lines per batch size
+(1 and 8), appended to --out: the captured step on dg_moe_route / dg_moe_w4_launch against the formulation that is possible without them
+(every expert through the module GEMVs, a device-side mask: it captures too), alternating, three runs each; and dg_moe_w4_launch GATE_UP /
+DOWN against the module GEMV on ONE expert's linears at the same m, one pair per layer and graph, with the effective bandwidth over the
+bytes of the experts the seeded router selected (computed from shapes, `moe_bytes`).
 """
 import argparse
 import json
@@ -203,6 +211,139 @@ def lora_bench(a, cfg, device):
                          adapter_work_us_per_layer=round((med("c_all_on_adapter_0") - med("b_attached_all_off")) * 1e3 / cfg.layers, 2),
                          kernels_vs_torch=round(med("c_all_on_adapter_0") / med("e_torch_all_on_adapter_0"), 4)))
         del plain, kern, ref, runs
+        torch.cuda.empty_cache()
+    return legs
+
+
+def moe_bytes(stack, n_experts):
+    """Bytes `n_experts` experts of one stacked linear hold: packed words, scale | zero words, LUT rows -- from shapes alone."""
+    lut = 0 if stack.lut is None else stack.n * 32 if stack.lut.dim() == 3 else 32
+    return n_experts * (stack.n * stack.k // 2 + (stack.k // stack.group) * stack.n * 4 + lut)
+
+
+def moe_bench(a, cfg, device):
+    """--moe: (1) the captured step of a stack with experts on dg_moe_route / dg_moe_w4_launch against the formulation that is possible
+    WITHOUT them -- every expert through the module GEMVs (w4_linear_fused: SwiGLU in gate_up's store), combined with a device-side mask,
+    the router in torch; nothing read on the host, so it captures too -- at bs 1 and 8, alternating in one process, three runs each.
+    (2) dg_moe_w4_launch GATE_UP + DOWN back to back against the module GEMVs on ONE expert's two linears at the same m, as graphs of one
+    pair per layer (every pair reads another layer's weights: nothing is served from a cache), alternating, three runs; the effective
+    bandwidth is over the bytes of the experts the seeded router selected (moe_bytes: from shapes)."""
+    from any4_amd import decode_ops as G, ops
+    from any4_amd.decode import Any4Factory, DecodeStack
+    from any4_amd.moe import route_ref
+
+    class AllExperts(torch.nn.Module):
+        """The block without the feature: E x (gate_up + SwiGLU, down) on the existing kernels and a mask."""
+
+        def __init__(self, moe):
+            super().__init__()
+            self.m, self.weights, self.router, self.top_k = moe, moe.weights, moe.router, moe.top_k   # (what DecodeLayer reads of its block)
+
+        def forward(self, x, residual=None, fused=True, out=None):
+            W, top_k = self.m.weights, self.m.top_k
+            ids, gates = route_ref(x.float() @ self.m.router.float().t(), top_k)
+            acc = torch.zeros(x.shape[0], W.down.n, dtype=torch.float32, device=x.device)
+            for e in range(W.E):
+                act = ops.w4_linear_fused(x, W.gate_up.words[e], W.gate_up.group, W.gate_up.qinfo[e], W.gate_up.lut[e], swiglu=True)
+                d = ops.w4_linear_fused(act, W.down.words[e], W.down.group, W.down.qinfo[e], W.down.lut[e])
+                acc += (gates * (ids == e)).sum(dim=1, keepdim=True) * d.float()
+            y = (acc if residual is None else acc + residual.float()).to(x.dtype)
+            return y if out is None else out.copy_(y)
+
+    base = {"config": a.config, "layers": cfg.layers, "experts": cfg.experts, "experts_per_token": cfg.experts_per_token, "hidden": cfg.hidden,
+            "inter": cfg.inter, "max_seq": cfg.max_seq, "data": "synthetic (random weights, random tokens)", "steps": a.steps,
+            "warmup": a.warmup, "start_pos": a.start_pos, "rounds": a.rounds}
+    stat = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "series": v}
+    legs = []
+    for bs in (1, 8):
+        def stack(all_experts):
+            st = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs,
+                             fuse_gemm_stages=not a.no_fuse)
+            if all_experts:
+                for layer in st.layers:
+                    layer.moe = AllExperts(layer.moe)
+            st.capture()
+            return st
+
+        new, old = stack(False), stack(True)
+        runs = {"moe_kernels": new, "all_experts_masked": old}
+        series = {k: [] for k in runs}
+        order = list(runs)
+        for r in range(a.rounds):
+            for k in order[r % 2:] + order[: r % 2]:
+                series[k].append(round(time_steps(runs[k], a.steps, a.warmup, a.start_pos) * 1e3, 4))
+        ms = {k: stat(v) for k, v in series.items()}
+        legs.append(dict(base, leg="captured step: dg_moe kernels / all experts through the module GEMVs and a mask", bs=bs,
+                         kernels_per_layer=getattr(new, "kernels_per_layer", None), ms_per_step=ms,
+                         ratio_new_over_old=round(ms["moe_kernels"]["median"] / ms["all_experts_masked"]["median"], 4)))
+        del old, runs
+
+        # (2) the two GEMV stages alone, one (gate_up, down) pair per layer and graph
+        layers = [layer.moe for layer in new.layers]
+        gen = torch.Generator(device=device).manual_seed(7)
+        x = torch.randn(bs, cfg.hidden, device=device, generator=gen).bfloat16()
+        picks = [G.moe_route(x, m.router, m.top_k) for m in layers]
+        distinct = [int(torch.unique(ids).numel()) for ids, _ in picks]
+        act1 = torch.randn(bs, cfg.inter, device=device, generator=gen).bfloat16()
+
+        def moe_pairs():
+            for m, (ids, gates) in zip(layers, picks):
+                G.moe_down(G.moe_gate_up(x, m.weights.gate_up, ids), m.weights.down, ids, gates)
+
+        def gemv_pairs():
+            for m in layers:
+                gu, dn = m.weights.gate_up, m.weights.down
+                ops.w4_linear_fused(ops.w4_linear_fused(x, gu.words[0], gu.group, gu.qinfo[0], gu.lut[0], swiglu=True), dn.words[0], dn.group,
+                                    dn.qinfo[0], dn.lut[0])
+
+        def stage_only(fn):
+            return lambda: [fn(m, p) for m, p in zip(layers, picks)]
+
+        fns = {"moe_gate_up+down": moe_pairs, "gemv_gate_up+down_one_expert": gemv_pairs,
+               "moe_gate_up": stage_only(lambda m, p: G.moe_gate_up(x, m.weights.gate_up, p[0])),
+               "moe_down": stage_only(lambda m, p: G.moe_down(act1.repeat_interleave(m.top_k, dim=0), m.weights.down, p[0], p[1])),
+               "gemv_gate_up": stage_only(lambda m, p: ops.w4_linear_fused(x, m.weights.gate_up.words[0], m.weights.gate_up.group,
+                                                                            m.weights.gate_up.qinfo[0], m.weights.gate_up.lut[0], swiglu=True)),
+               "gemv_down": stage_only(lambda m, p: ops.w4_linear_fused(act1, m.weights.down.words[0], m.weights.down.group,
+                                                                         m.weights.down.qinfo[0], m.weights.down.lut[0]))}
+        graphs = {}
+        for k, fn in fns.items():
+            fn()
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fn()
+            graphs[k] = g
+
+        def timed(g, reps=20):
+            for _ in range(3):
+                g.replay()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(reps):
+                g.replay()
+            torch.cuda.synchronize()
+            return (time.perf_counter() - t0) / reps / len(layers) * 1e6   # us per layer
+
+        series = {k: [] for k in graphs}
+        order = list(graphs)
+        for r in range(a.rounds):
+            for k in order[r % len(order):] + order[: r % len(order)]:
+                series[k].append(round(timed(graphs[k]), 3))
+        us = {k: stat(v) for k, v in series.items()}
+        gu0, dn0 = layers[0].weights.gate_up, layers[0].weights.down
+        mean_distinct = sum(distinct) / len(distinct)
+        sel = {"gate_up": moe_bytes(gu0, mean_distinct), "down": moe_bytes(dn0, mean_distinct)}
+        one = {"gate_up": moe_bytes(gu0, 1), "down": moe_bytes(dn0, 1)}
+        tbs = lambda nbytes, k: round(nbytes / (us[k]["median"] * 1e-6) / 1e12, 3)
+        legs.append(dict(base, leg="kernels: dg_moe_w4 GATE_UP / DOWN against the module GEMV on one expert, one pair per layer and graph", bs=bs,
+                         distinct_experts_per_layer=distinct, us_per_layer=us,
+                         selected_bytes_per_layer={k: int(v) for k, v in sel.items()}, one_expert_bytes=one,
+                         effective_TBps={"moe_gate_up": tbs(sel["gate_up"], "moe_gate_up"), "moe_down": tbs(sel["down"], "moe_down"),
+                                         "moe_pair": tbs(sel["gate_up"] + sel["down"], "moe_gate_up+down"),
+                                         "gemv_gate_up": tbs(one["gate_up"], "gemv_gate_up"), "gemv_down": tbs(one["down"], "gemv_down"),
+                                         "gemv_pair": tbs(one["gate_up"] + one["down"], "gemv_gate_up+down_one_expert")}))
+        del new, graphs, layers, picks
         torch.cuda.empty_cache()
     return legs
 
@@ -401,7 +542,7 @@ def paged_bench(a, cfg, device):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "tiny"])
+    ap.add_argument("--config", default="llama3_8b", choices=["llama3_8b", "llama2_7b", "mixtral_8x7b", "tiny"])
     ap.add_argument("--layers", type=int, default=None, help="override the number of decoder layers")
     ap.add_argument("--bs", type=int, default=1)
     ap.add_argument("--steps", type=int, default=None, help="timed steps (default 100; with --mx8-attention online 30)")
@@ -437,6 +578,9 @@ def main():
     ap.add_argument("--lora", type=int, default=0, metavar="RANK",
                     help="per-sequence LoRA adapters of this rank on the four fused linears (DESIGN.md section 20; see the module docstring); one GPU")
     ap.add_argument("--adapters", type=int, default=8, help="--lora: adapters resident in the set")
+    ap.add_argument("--moe", action="store_true",
+                    help="mixture of experts (DESIGN.md section 22): the Mixtral-8x7B shape (--layers N for fewer layers; --config tiny: a small "
+                         "one) on the dg_moe kernels against all experts through the module GEMVs and a mask, and the two GEMV stages alone")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
                                                 "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl, with both profiles/paged_mx8_bench.jsonl)")
     a = ap.parse_args()
@@ -445,8 +589,11 @@ def main():
     three_way = a.mx8_attention == "online"
     a.steps = a.steps if a.steps is not None else 30 if three_way else 100
     a.warmup = a.warmup if a.warmup is not None else 10 if three_way else 20
-    a.rounds = a.rounds if a.rounds is not None else 3 if a.lora else 5 if three_way else 7  # (--lora: three runs per leg)
+    a.rounds = a.rounds if a.rounds is not None else 3 if a.lora or a.moe else 5 if three_way else 7  # (--lora: three runs per leg)
     a.start_pos = a.start_pos if a.start_pos is not None else 512 if a.lora else 128
+    if a.moe:
+        a.out = a.out or os.path.join(ROOT, "profiles", "moe_bench.jsonl")
+        a.config = "mixtral_8x7b" if a.config == "llama3_8b" else a.config
     if a.lora:
         a.out = a.out or os.path.join(ROOT, "profiles", "lora_bench.jsonl")
     if a.out is None and a.sample:
@@ -473,12 +620,24 @@ def main():
 
     if a.config == "tiny":
         cfg = DecodeConfig(hidden=512, inter=1024, layers=2, heads=8, kv_heads=8, head_dim=64, vocab=1024, max_seq=a.max_seq)
+        if a.moe:
+            cfg.experts, cfg.experts_per_token, cfg.gate_up_interleave = 4, 2, 8
     else:
         cfg = getattr(DecodeConfig, a.config)(max_seq=a.max_seq)
     if a.layers is not None:
         cfg.layers = a.layers
     if a.interleave:
         cfg.gate_up_interleave = 8
+
+    if a.moe:
+        if world > 1 or not cfg.experts:
+            raise SystemExit("--moe runs on one GPU, with a configuration that has experts (mixtral_8x7b, tiny)")
+        with open(a.out, "a") as f:
+            for leg in moe_bench(a, cfg, device):
+                line = json.dumps(leg)
+                print(line, flush=True)
+                f.write(line + "\n")
+        return
 
     if a.lora:
         if world > 1:
