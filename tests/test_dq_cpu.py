@@ -174,3 +174,44 @@ def test_tune_quant_params_refuses_what_it_cannot_tune():
         tune_quant_params(modules.MX4Linear(64, 16, bias=False), x, torch.zeros(2, 16))
     with pytest.raises(ValueError, match="packed int4 / any4"):
         tune_quant_params(modules.Int4Linear(64, 16, bias=False, group_size=32), x, torch.zeros(2, 16))   # not packed yet
+
+
+# ------------------------------------------------------------------------------------------------
+# the tile and step counts tests/grad_ref.DQ_CASES claims
+# ------------------------------------------------------------------------------------------------
+
+def _dq_cases():
+    from tests import grad_ref
+
+    return grad_ref.DQ_CASES, grad_ref.dq_case_id
+
+
+@pytest.mark.parametrize("case", _dq_cases()[0], ids=_dq_cases()[1])
+def test_dq_cases_reach_the_tiles_and_steps_they_claim(case):
+    from tests import grad_ref as G
+
+    c = case
+    assert c.tiles == (G.cdiv(c.wrows, G.DQ_BR), G.cdiv(c.k, G.DQ_BK))
+    assert c.steps == G.cdiv(c.m, G.DQ_BA)
+    assert c.k % c.g == 0 and c.k % 32 == 0 and c.wrows % (8 if c.on_right else 16) == 0
+    # the library accepts the problem and sizes H for it: [k / min(g, 128)][wrows][16] f32 (+ the per-row tables of a global LUT)
+    need = (c.k // min(c.g, 128)) * c.wrows * 16 * 4 + (c.wrows * 16 * 4 if c.qtype == "any4_global" else 0)
+    assert G.dq_workspace_bytes(c.m, c.wrows, c.k, c.g, c.qtype, c.dtype, c.on_right, c.inner) == need
+
+
+def test_dq_cases_cover_what_they_are_for():
+    from tests import grad_ref as G
+
+    C = G.DQ_CASES
+    assert {c.m for c in C} >= {63, 64, 65, 129}
+    assert {c.dtype for c in C} == {G.BF16, G.F16} and {c.on_right for c in C} == {True, False}
+    for k, g, tiles_k in ((160, 32, 2), (416, 32, 4), (768, 256, 6)):
+        hit = [c for c in C if (c.k, c.g) == (k, g)]
+        assert hit and all(c.tiles[1] == tiles_k for c in hit) and {c.on_right for c in hit} == {True, False}, k
+    assert 160 % 128 == 32 and 416 % 128 == 32                      # the ragged last k tile is 32 columns wide
+    assert any(c.wrows == 264 and c.tiles[0] == 3 for c in C) and 264 - 2 * G.DQ_BR == 8
+    rs = [c for c in C if c.qtype == "any4_global" and c.wrows == 2056]
+    assert rs and all(c.tiles[0] == 17 for c in rs) and 2056 % 16 != 0   # dq_rowsum_kernel: 16 chains of unequal length
+    n = G.DQ_NONFINITE
+    assert n["r0"] == n["wrows"] - 1 and n["wrows"] % G.DQ_BR != 0 and n["a0"] == n["m"] - 1 == G.DQ_BA
+    assert n["j0"] == n["k"] - 1 and n["k"] % G.DQ_BK == 32

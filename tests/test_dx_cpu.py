@@ -147,3 +147,87 @@ def test_modules_route_row_major_4bit_kernels_only():
     assert modules.NF4Linear._DX_KERNELS is modules.Any4Linear._DX_KERNELS
     assert set(modules.MX4Linear._DX_KERNELS) == {"linear_y_f16RM_x_f16RM_W_mx4TC", "linear_y_f16RM_W_mx4TC_x_f16RM"}
     assert modules.Int8Linear._DX_KERNELS == {}
+
+
+# ------------------------------------------------------------------------------------------------
+# the split regimes tests/grad_ref.DX_SPLIT_CASES claims, against the library's own answer
+# ------------------------------------------------------------------------------------------------
+
+def _dx_case_id(c):
+    return f"m{c.m}-r{c.wrows}-k{c.k}"
+
+
+def _dx_cases():
+    from tests import grad_ref
+
+    return grad_ref.DX_SPLIT_CASES
+
+
+@pytest.mark.parametrize("case", _dx_cases(), ids=_dx_case_id)
+def test_dx_split_cases_reach_the_regime_they_claim(case):
+    from tests import grad_ref as G
+
+    c = case
+    # the library: every launch of the case splits as claimed (the split does not depend on weight kind, group, dtype, side or word order)
+    assert c.runs
+    for r in c.runs:
+        wrows = c.wrows if r.on_right else c.wrows_left
+        assert G.dx_splits(c.m, wrows, c.k, r.g, r.qtype, r.dtype, r.on_right, r.inner) == c.splits, r
+    # plain arithmetic on the shape: tiles, steps, steps of every split, the ragged edges
+    assert c.bm == (32 if c.m <= 32 else 64 if c.m <= 64 else 128)
+    assert c.tiles == (G.cdiv(c.m, c.bm), G.cdiv(c.k, G.DX_BK))
+    assert c.steps == G.cdiv(c.wrows, G.DX_BR)
+    assert c.sps == G.cdiv(c.steps, c.splits)
+    assert len(c.split_steps) == c.splits and sum(c.split_steps) == c.steps
+    assert c.split_steps == G.split_steps(c.steps, c.splits)
+    assert c.last_step_rows == c.wrows - (c.steps - 1) * G.DX_BR
+    assert c.last_k_cols == c.k - (c.tiles[1] - 1) * G.DX_BK
+    # weights on the left: rows padded to 16 -- the nearest such count with the same steps
+    assert c.wrows_left % 16 == 0 and abs(c.wrows_left - c.wrows) <= 8 and G.cdiv(c.wrows_left, G.DX_BR) == c.steps
+    assert c.wrows % 8 == 0 and c.k % 32 == 0
+
+
+def test_dx_split_cases_cover_what_they_are_for():
+    from tests import grad_ref as G
+
+    by = {c.m: c for c in G.DX_SPLIT_CASES}
+    assert [c.splits for c in G.DX_SPLIT_CASES] == [2, 4, 4, 8, 16]
+    assert by[40].bm == 64 and by[40].last_step_rows == 8
+    assert by[33].split_steps == (5, 5, 5, 2) and by[33].last_step_rows == 8
+    assert by[130].tiles == (2, 17) and by[130].m - 128 == 2 and by[130].last_k_cols == 32 and by[130].split_steps[-1] == 6
+    assert by[16].split_steps[6:] == (3, 0)
+    assert by[7].split_steps[13:] == (0, 0, 0) and 0 not in by[7].split_steps[:13]
+    # the tile limit, not the step limit, stops the m = 130 case: its steps alone would allow 8 splits
+    assert G.dx_splits(16, by[130].wrows, 128) == 8
+    runs = [r for c in G.DX_SPLIT_CASES for r in c.runs]
+    assert {r.qtype for r in runs} == {"int4", "any4_global", "any4_rowwise", "mx4"}
+    for q in ("int4", "any4_global", "any4_rowwise"):
+        assert {r.dtype for r in runs if r.qtype == q} == {G.BF16, G.F16}, q
+    assert all(r.dtype == G.BF16 and r.g == 32 for r in runs if r.qtype == "mx4")
+    for c in G.DX_SPLIT_CASES:
+        allowed = {i for i in (2, 4, 8) if c.k % (16 * i) == 0}
+        assert {r.inner for r in c.runs if r.on_right} == allowed, c.k
+        assert any(not r.on_right for r in c.runs)
+        assert all(c.k % r.g == 0 for r in c.runs)
+
+
+def test_dx_probe_shapes_run_the_regime_they_name():
+    from tests import grad_ref as G
+
+    for wrows, k, splits in (G.DX_IDENTITY_SMALL, G.DX_IDENTITY_LARGE):
+        assert G.dx_splits(wrows, wrows, k) == splits
+    wrows, k, _ = G.DX_IDENTITY_LARGE
+    assert (G.cdiv(wrows, 128), G.cdiv(k, G.DX_BK), G.cdiv(wrows, G.DX_BR)) == (17, 2, 33)
+    n = G.DX_NONFINITE
+    assert G.dx_splits(n["m"], n["wrows"], n["k"]) == n["splits"] == 4
+    assert n["row"] == n["m"] - 1 and 32 < n["m"] <= 64                    # BM = 64: tile rows 33 ... 63 are clamped copies of row 32
+    assert (G.cdiv(n["wrows"], G.DX_BR) - 1) * G.DX_BR <= n["r0"] < n["wrows"]   # r0 in the ragged last step
+
+
+@pytest.mark.parametrize("inner", [2, 4, 8])
+def test_dx_inner_and_split_shapes_really_split(inner):
+    """what test_gpu_dx.test_dx_inner_and_split says in its comment: with the workspace these launches split"""
+    from tests import grad_ref as G
+
+    for n, k, g, m, qtype, dtype, on_right, inn in G.dx_inner_and_split_shapes(inner):
+        assert G.dx_splits(m, n, k, g, qtype, dtype, on_right, inn) == 8, (n, k)

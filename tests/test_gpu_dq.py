@@ -12,6 +12,8 @@ import numpy as np
 import pytest
 import torch
 
+from tests import grad_ref
+from tests.grad_ref import dq_reference as reference
 from tests.test_gpu_parity import assert_gemm_close, oracle_weights, rand_problem, ulp16
 
 pytestmark = pytest.mark.gpu
@@ -36,42 +38,13 @@ def _pack(T, codes, on_right, inner):
         return T.convert_matrix_to_m16n8k16_Aint4_layout(codes.to(DEV), inner)
 
 
-def _lut_rows(lut, n, dtype64=torch.float64):
-    """the table of every row as [n][16] float64 (int4: code - 8; a global table: repeated)"""
-    if lut is None:
-        return (torch.arange(16, dtype=dtype64) - 8).expand(n, 16)
-    lut = lut.detach().cpu().to(dtype64)
-    return lut.expand(n, 16) if lut.dim() == 1 else lut
-
-
-def reference(codes, x, dy, qinfo, lut, g):
-    """(d_qinfo [k/g][n][2], d_lut [n][16] / [16] / None) and the matching sums of absolute values, float64"""
-    n, k = codes.shape
-    x64, dy64 = x.detach().cpu().double(), dy.detach().cpu().double()
-    onehot = torch.nn.functional.one_hot(codes.long(), 16).double().view(n, k // g, g, 16)
-    lt = _lut_rows(lut, n)
-    s = qinfo.detach().cpu()[..., 0].double().t()   # [n][k/g]
-    out = []
-    for G, l, sc in ((dy64.t() @ x64, lt, s), (dy64.abs().t() @ x64.abs(), lt.abs(), s.abs())):
-        H = (G.view(n, k // g, g, 1) * onehot).sum(2)   # [n][k/g][16]
-        dz = H.sum(2)
-        ds = (H * l[:, None, :]).sum(2)
-        dq = torch.stack([ds.t(), dz.t()], 2)            # [k/g][n][2]
-        dl = (H * sc[:, :, None]).sum(1)                 # [n][16]
-        if lut is None:
-            dl = None
-        elif lut.dim() == 1:
-            dl = dl.sum(0)
-        out.append((dq, dl))
-    return out
-
-
 def assert_close_f32(got, want, S, what):
     err = (got.detach().double().cpu() - want).abs()
     tol = 4e-6 * S + 1e-37
     print(f"{what}: max err / tol = {float((err / tol).max()):.4f}")
     bad = err > tol
     assert not bad.any(), f"{what}: {int(bad.sum())} / {bad.numel()} outside tolerance; worst err / tol {float((err / tol).max())}"
+    return float((err / tol).max())
 
 
 def assert_close_16(got, want, S, dtype, what):
@@ -96,12 +69,13 @@ def _check_op(T, n, k, g, m, qtype, dtype, on_right, inner, seed=0):
     dq, dl = _dq(T, d(x), d(dy), w, g, d(qinfo), d(lut), on_right)
     assert dq.shape == qinfo.shape and dq.dtype == torch.float32
     (wq, wl), (sq, sl) = reference(codes, x, dy, qinfo, lut, g)
-    assert_close_f32(dq, wq, sq, "d_qinfo")
+    worst = assert_close_f32(dq, wq, sq, "d_qinfo")
     if lut is None:
         assert dl is None
     else:
         assert dl.shape == lut.shape and dl.dtype == torch.float32
-        assert_close_f32(dl, wl, sl, "d_lut")
+        worst = max(worst, assert_close_f32(dl, wl, sl, "d_lut"))
+    return worst
 
 
 QTYPES = [(q, d) for q in ("int4", "any4_global", "any4_rowwise") for d in (torch.bfloat16, torch.float16)]
@@ -130,6 +104,71 @@ def test_dq_edges(T):
     _check_op(T, 8, 128, 64, 5, "any4_global", torch.float16, True, 8)
     # one group over the whole of k, wider than the kernel's column tile
     _check_op(T, 72, 256, 256, 40, "any4_rowwise", torch.bfloat16, True, 4)
+
+
+DQ_WORST = {}   # case id -> its largest err / tol (printed; DESIGN section 14 records the maximum)
+
+
+@pytest.mark.parametrize("case", grad_ref.DQ_CASES, ids=grad_ref.dq_case_id)
+def test_dq_cases_vs_float64(T, case):
+    """ragged k tiles among several, three and seventeen row tiles, the step boundary of the activation rows (tests/grad_ref.DQ_CASES;
+    test_dq_cpu holds the claimed tile and step counts to the shapes)"""
+    c = case
+    DQ_WORST[grad_ref.dq_case_id(c)] = _check_op(T, c.wrows, c.k, c.g, c.m, c.qtype, c.dtype, c.on_right, c.inner, seed=c.m)
+    print(f"dq {grad_ref.dq_case_id(c)}: max err / tol {DQ_WORST[grad_ref.dq_case_id(c)]:.4f}; largest so far {max(DQ_WORST.values()):.4f}")
+
+
+def _nonfinite_problem(T):
+    """any4 row-wise, fp16: code 5 is absent from group 2 of row r0 (present in its other groups), code 11 from the whole row"""
+    N = grad_ref.DQ_NONFINITE
+    n, k, g, m, r0 = N["wrows"], N["k"], N["g"], N["m"], N["r0"]
+    codes, x, qinfo, lut = rand_problem(n, k, g, m, "any4_rowwise", torch.float16, seed=11)
+    row = codes[r0]
+    row[row == 11] = 12
+    grp = row[2 * g:3 * g]
+    grp[grp == 5] = 6
+    row[0], row[4 * g] = 5, 5
+    assert not (row == 11).any() and not (row[2 * g:3 * g] == 5).any() and (row == 5).any()
+    dy = torch.randn(m, n, generator=torch.Generator().manual_seed(12)).half()
+    w = _pack(T, codes, True, 2)
+    run = lambda x_, dy_: tuple(t.cpu() for t in T.tinygemm_dq_f16RM_x_f16RM_w_any4TC(x_.to(DEV), dy_.to(DEV), w, g, qinfo.to(DEV), lut.to(DEV), True))
+    return N, codes, x, dy, run
+
+
+@pytest.mark.parametrize("value", [float("inf"), float("nan")])
+def test_dq_nonfinite_dy_reaches_its_row_and_no_other(T, value):
+    """dY[64][r0] non-finite, r0 = 199 the last row of a ragged row tile (rows 200 ... 255 of the tile load clamped copies of real rows),
+    row 64 the last activation row, alone in its step.  By the definition (select by code, then sum) every G[r0][j] is non-finite, so
+    every d_qinfo[g][r0] and every d_lut[r0][c] of a code present in the row is; a code absent from the row sums nothing and stays 0; no
+    other row sees the value."""
+    N, codes, x, dy, run = _nonfinite_problem(T)
+    r0, a0 = N["r0"], N["a0"]
+    dq0, dl0 = run(x, dy)
+    assert torch.isfinite(dq0).all() and torch.isfinite(dl0).all()
+    dy[a0, r0] = value
+    dq, dl = run(x, dy)
+    assert not torch.isfinite(dq[:, r0, :]).any(), dq[:, r0, :]
+    present = torch.bincount(codes[r0], minlength=16) > 0
+    assert int(present.sum()) == 15 and not present[11]
+    assert not torch.isfinite(dl[r0][present]).any(), dl[r0]
+    assert dl[r0][11] == 0.0
+    others = torch.arange(N["wrows"]) != r0
+    assert torch.equal(dq[:, others].view(torch.int32), dq0[:, others].view(torch.int32))
+    assert torch.equal(dl[others].view(torch.int32), dl0[others].view(torch.int32))
+
+
+@pytest.mark.parametrize("value", [float("nan"), float("inf")])
+def test_dq_nonfinite_x_reaches_its_group_and_no_other(T, value):
+    """x[64][159] non-finite: the last column of the ragged k tile (columns 160 ... 255 of the tile load clamped copies of real columns).
+    G[r][159] is non-finite for every row, so d_qinfo[g(159)][r] is; every other group is untouched."""
+    N, codes, x, dy, run = _nonfinite_problem(T)
+    g0 = N["j0"] // N["g"]
+    dq0, _ = run(x, dy)
+    x[N["a0"], N["j0"]] = value
+    dq, _ = run(x, dy)
+    assert not torch.isfinite(dq[g0]).any(), f"{int(torch.isfinite(dq[g0]).sum())} finite values in group {g0}"
+    others = torch.arange(N["k"] // N["g"]) != g0
+    assert torch.equal(dq[others].view(torch.int32), dq0[others].view(torch.int32))
 
 
 @pytest.mark.parametrize("on_right,inner", [(True, 2), (True, 4), (True, 8), (False, 2)])

@@ -1,11 +1,13 @@
 """Input gradient of the 4-bit GEMMs on the GPU: the dx ops against the oracle's weights contracted in float64, autograd through the
-row-major ops and the modules, determinism, mx4 NaN, a LoRA chain and graph capture."""
+row-major ops and the modules, every split regime of tests/grad_ref.DX_SPLIT_CASES split and unsplit, the identity probe of the word maps
+(exact), non-finite dY, determinism, mx4 NaN, a LoRA chain and graph capture."""
 import warnings
 
 import numpy as np
 import pytest
 import torch
 
+from tests import grad_ref
 from tests.conftest import from_bits16
 from tests.test_gpu_parity import assert_gemm_close, oracle_weights, rand_problem
 
@@ -96,9 +98,10 @@ def test_dx_inner_and_split(T, oracle, inner, split, monkeypatch):
 
     if not split:
         monkeypatch.setattr(ops, "_WS_BYTES", _NoWorkspace())
-    # many k tiles (k = 1024) and 2048 weight rows: with the workspace the launch splits over the weight rows (m = 16 fills few CUs)
-    _check_grad(T, oracle, 2048, 1024, 128, 16, "int4", torch.bfloat16, True, inner)
-    _check_grad(T, oracle, 2048, 96 if inner == 2 else 1024, 32, 16, "any4_global", torch.float16, True, inner if inner == 2 else 4)
+    # many k tiles (k = 1024) and 2048 weight rows: with the workspace the launch splits over the weight rows (m = 16 fills few CUs;
+    # test_dx_cpu.test_dx_inner_and_split_shapes_really_split holds the library to it)
+    for shape in grad_ref.dx_inner_and_split_shapes(inner):
+        _check_grad(T, oracle, *shape)
 
 
 def test_dx_k_of_one_step_and_ragged(T, oracle):
@@ -115,6 +118,101 @@ def test_dx_deterministic(T):
     a = _dx(T, dy, w, 128, "any4_rowwise", qinfo.to(DEV), lut.to(DEV), True)
     b = _dx(T, dy, w, 128, "any4_rowwise", qinfo.to(DEV), lut.to(DEV), True)
     assert torch.equal(a.view(torch.int16), b.view(torch.int16))
+
+
+# ------------------------------------------------------------------------------------------------
+# every split regime (tests/grad_ref.DX_SPLIT_CASES; test_dx_cpu holds the table to the library), exact probes, non-finite dY
+# ------------------------------------------------------------------------------------------------
+
+def _dev_problem(T, n, k, m, run, seed=0):
+    """(codes, dy on the CPU; packed words, qinfo, lut on the GPU) of one launch of a case"""
+    codes, _, qinfo, lut = rand_problem(n, k, run.g, 1, run.qtype, run.dtype, seed=seed)
+    dy = torch.randn(m, n, generator=torch.Generator().manual_seed(seed + 1)).to(run.dtype)
+    d = lambda t: None if t is None else t.to(DEV)
+    return codes, dy, qinfo, lut, _pack(T, codes, run.on_right, run.inner), d(qinfo), d(lut)
+
+
+DX_WORST = {}   # case id -> the largest err / tol of its split and unsplit results (printed; DESIGN section 11 records the maximum)
+
+
+@pytest.mark.parametrize("case,run", grad_ref.DX_SPLIT_RUNS, ids=[grad_ref.dx_run_id(cr) for cr in grad_ref.DX_SPLIT_RUNS])
+def test_dx_split_regimes_vs_float64(T, oracle, case, run, monkeypatch):
+    """each regime three ways: split (the op with its workspace), split again (the same bits), unsplit (no workspace); both results
+    against the oracle's weights contracted in float64 under the project's GEMM bound"""
+    from any4_amd import ops
+
+    n = case.wrows if run.on_right else case.wrows_left
+    assert grad_ref.dx_splits(case.m, n, case.k, run.g, run.qtype, run.dtype, run.on_right, run.inner) == case.splits
+    codes, dy, qinfo, lut, w, q, l = _dev_problem(T, n, case.k, case.m, run, seed=case.m)
+    split = _dx(T, dy.to(DEV), w, run.g, run.qtype, q, l, run.on_right)
+    again = _dx(T, dy.to(DEV), w, run.g, run.qtype, q, l, run.on_right)
+    monkeypatch.setattr(ops, "_WS_BYTES", _NoWorkspace())
+    unsplit = _dx(T, dy.to(DEV), w, run.g, run.qtype, q, l, run.on_right)
+    assert split.shape == (case.m, case.k) and split.dtype == run.dtype
+    assert torch.equal(split.view(torch.int16), again.view(torch.int16))
+    wt = np.ascontiguousarray(oracle_weights(oracle, codes, run.g, run.qtype, qinfo, lut, run.dtype).T)   # dX = dY . W
+    worst = {name: grad_ref.gemm_err_over_tol(got, dy, wt, run.dtype) for name, got in (("split", split), ("unsplit", unsplit))}
+    DX_WORST[grad_ref.dx_run_id((case, run))] = max(worst.values())
+    print(f"dx {grad_ref.dx_run_id((case, run))} ({case.splits} splits): max err / tol split {worst['split']:.4f}, unsplit {worst['unsplit']:.4f}; "
+          f"largest so far {max(DX_WORST.values()):.4f}")
+    assert_gemm_close(split, dy, wt, run.dtype)
+    assert_gemm_close(unsplit, dy, wt, run.dtype)
+
+
+def _identity_probe(T, oracle, n, k, g, qtype, dtype, on_right, inner, splits):
+    """dY = I: dX is the dequantised weight matrix itself, bit for bit (every product is 1 w or 0 w, every f32 sum is exact in any
+    order); -0 weights come out as +0, the sums start at +0.  (rand_problem keeps the mx4 exponents in 120 ... 130: no NaN weight.)"""
+    assert grad_ref.dx_splits(n, n, k, g, qtype, dtype, on_right, inner) == splits
+    codes, _, qinfo, lut = rand_problem(n, k, g, 1, qtype, dtype, seed=n + k + g)
+    d = lambda t: None if t is None else t.to(DEV)
+    dx = _dx(T, torch.eye(n, dtype=dtype, device=DEV), _pack(T, codes, on_right, inner), g, qtype, d(qinfo), d(lut), on_right)
+    want = from_bits16(oracle_weights(oracle, codes, g, qtype, qinfo, lut, dtype), dtype) + 0.0
+    assert want.shape == (n, k) and torch.isfinite(want.float()).all()
+    got = dx.cpu()
+    bad = got.view(torch.int16) != want.view(torch.int16)
+    assert not bad.any(), f"{int(bad.sum())} / {bad.numel()} weights differ; first at (row, column) {bad.nonzero()[0].tolist()}"
+
+
+# the word maps: Bint4 innerKTiles 2 / 4 / 8 and the convert op's 1 / 2 / 4 on the left (k = 512: native words of innerKTiles 4); the
+# last entry is the other native order, that of k % 64 != 0 (innerKTiles 2)
+WORDS = [(True, 2, 512, 32), (True, 4, 512, 64), (True, 8, 512, 128), (False, 1, 512, 32), (False, 2, 512, 64), (False, 4, 512, 128),
+         (False, 2, 224, 32)]
+
+
+@pytest.mark.parametrize("on_right,inner,k,g", WORDS)
+@pytest.mark.parametrize("qtype,dtype", QTYPES)
+def test_dx_identity_is_the_weight_matrix_bit_for_bit(T, oracle, qtype, dtype, on_right, inner, k, g):
+    n, _, splits = grad_ref.DX_IDENTITY_SMALL
+    _identity_probe(T, oracle, n, k, 32 if qtype == "mx4" else g, qtype, dtype, on_right, inner, splits)
+
+
+@pytest.mark.parametrize("qtype,inner", [("any4_rowwise", 4), ("mx4", 2)])
+def test_dx_identity_through_a_split(T, oracle, qtype, inner):
+    # 17 x 2 tiles, 33 steps, 4 splits (test_dx_cpu.test_dx_probe_shapes_run_the_regime_they_name)
+    n, k, splits = grad_ref.DX_IDENTITY_LARGE
+    _identity_probe(T, oracle, n, k, 32, qtype, torch.bfloat16, True, inner, splits)
+
+
+@pytest.mark.parametrize("split", [True, False])
+@pytest.mark.parametrize("value", [float("inf"), float("nan")])
+def test_dx_nonfinite_dy_reaches_its_row_and_no_other(T, value, split, monkeypatch):
+    """fp16 training: an Inf / NaN in dY must reach dX (the loss scaler looks for it) and must stay in its row.  m = 33 on a BM = 64
+    tile: tile rows 33 ... 63 are clamped copies of row 32, computed and discarded."""
+    from any4_amd import ops
+
+    N = grad_ref.DX_NONFINITE
+    m, n, k, row, r0 = N["m"], N["wrows"], N["k"], N["row"], N["r0"]
+    run = grad_ref.Run("any4_rowwise", 64, torch.float16, True, 4)
+    assert grad_ref.dx_splits(m, n, k, run.g, run.qtype, run.dtype, True, run.inner) == N["splits"]
+    if not split:
+        monkeypatch.setattr(ops, "_WS_BYTES", _NoWorkspace())
+    _, dy, _, _, w, q, l = _dev_problem(T, n, k, m, run, seed=7)
+    clean = _dx(T, dy.to(DEV), w, run.g, run.qtype, q, l, True).cpu()
+    assert torch.isfinite(clean.float()).all()
+    dy[row, r0] = value
+    dx = _dx(T, dy.to(DEV), w, run.g, run.qtype, q, l, True).cpu()
+    assert not torch.isfinite(dx[row].float()).any(), f"{int(torch.isfinite(dx[row].float()).sum())} finite columns in row {row}"
+    assert torch.equal(dx[:row].view(torch.int16), clean[:row].view(torch.int16))
 
 
 def test_dx_stride0_dy(T, oracle):
