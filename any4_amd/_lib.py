@@ -190,6 +190,11 @@ SYMBOLS = {
     "dg_moe_route": [_vp] * 4 + [_i64] * 4 + [ctypes.c_int, ctypes.c_int, _vp],
     "dg_moe_w4_launch": [ctypes.POINTER(MoeW4), ctypes.c_int, _vp],
     "dg_moe_w4_plan": [ctypes.POINTER(MoeW4), ctypes.c_int, ctypes.POINTER(_i32)],
+    # the quantizer's k-means: x, w, w_row_stride, c0, assign, centers, sse, iters, rows, k, C, S, max_iter, tol, device, stream
+    "tg_kmeans_rows": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                       ctypes.c_int, _vp],
+    # rows, k, C, S, max_iter, tol, weighted, out[2]
+    "tg_kmeans_rows_plan": [_i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.POINTER(_i64)],
 }
 # Up to ABI 8 three groups of attention entry points were bound from tables of their own.  Nothing is any more, and nothing in this
 # tree reads these; the names stay, empty, so that a module written against that binding, which merges the four tables when it is

@@ -38,6 +38,7 @@ UNITS = [
     ("tg_sample", "tg_sample.hip", []),
     ("tg_lora", "tg_lora.hip", []),
     ("tg_moe", "tg_moe.hip", []),
+    ("tg_kmeans", "tg_kmeans.hip", ["-ffp-contract=off"]),  # (IEEE f64, one operation per rounding: kmeans.cuh)
     ("tinygemm_hip", "tinygemm_hip.hip", []),
 ]
 FLAGS = [f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-fvisibility=hidden", "-Wno-comment", "-Wno-int-to-pointer-cast"]

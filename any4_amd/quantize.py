@@ -188,9 +188,137 @@ def _lloyd(x, wts, xw, c, span, max_iter: int, tol: float):
     return assign, c, sse
 
 
+def _prefix_f64(v: torch.Tensor, order: str) -> torch.Tensor:
+    """[rows][k] f64 -> [rows][k + 1] exclusive-then-total prefix sums, in one of two summation orders."""
+    rows, k = v.shape
+    zero = torch.zeros(rows, 1, dtype=torch.float64, device=v.device)
+    if order == "sequential":
+        return torch.cat([zero, v.cumsum(1)], dim=1)
+    if order != "blocked":
+        raise ValueError(f"unknown prefix order {order!r}")
+    nb = (k + 31) // 32  # block totals by a pairwise tree, the blocks' prefix and the inside of a block sequential
+    blk = torch.cat([v, torch.zeros(rows, nb * 32 - k, dtype=torch.float64, device=v.device)], dim=1).reshape(rows, nb, 32)
+    tot = blk
+    while tot.shape[2] > 1:
+        tot = tot[:, :, 0::2] + tot[:, :, 1::2]
+    base = torch.cat([zero, tot[:, :, 0].cumsum(1)[:, :-1]], dim=1)
+    return torch.cat([zero, (base[:, :, None] + blk.cumsum(2)).reshape(rows, nb * 32)[:, :k]], dim=1)
+
+
+@torch.no_grad()
+def lloyd_rows_ref(x: torch.Tensor, wts: Optional[torch.Tensor], c0: torch.Tensor, max_iter: int = 300, tol: float = 1e-6, *,
+                   prefix: str = "sequential"):
+    """The definition of the fused k-means kernel (csrc/kmeans.cuh, tg_kmeans_rows), in float64: weighted 1-D Lloyd iterations on every
+    row of x f32 [rows][k] from the seed centres c0 f32 [rows][C] of ONE seeding; wts f32 [rows][k], already abs().clamp_min(1e-12), or None.
+
+    Per row: sort the row ascending, carrying the weights; f64 prefix sums of w and of x w (the product formed in f64);
+    span = max(x_max - x_min, 1e-12).  An iteration sorts the centres, takes the midpoints (c[j+1] + c[j]) * 0.5, gives cluster j the
+    points with mid[j-1] < x <= mid[j] (`searchsorted(mid, x)`) and moves its centre to tot / cnt, both differences of prefix sums.  A
+    cluster with no points keeps its centre; then the j-th empty cluster of the row (j < k) is re-seeded at the point with the j-th
+    largest |x - c[assign]| * w (ties: the lower position in the sorted row), where that error is > 0.  The row stops when no centre
+    moved by more than tol * span, or after max_iter iterations.  Then the centres are sorted and the points assigned, in their
+    original order, against the final f64 midpoints.
+
+    Two decisions differ from `_lloyd` on purpose:
+      * a row stops on its OWN criterion, not when the slowest row of the batch has converged;
+      * sums are in f64 and in a fixed order (prefix sums over the sorted row), not f32 scatter_adds.
+    `prefix` picks the order of the prefix summation ("sequential" | "blocked"): on inputs whose sums are exact in f64 the result does
+    not depend on it, which is what lets the kernel keep block prefixes.
+
+    Returns (assign int32 [rows][k], centres f32 [rows][C] ascending -- one rounding from f64, weighted SSE f64 [rows] against the f64
+    centres, iterations run int32 [rows]).
+    """
+    rows, k = x.shape
+    C = c0.shape[1]
+    dev = x.device
+    xd = x.double()
+    xs, order = torch.sort(xd, dim=1, stable=True)
+    wd = torch.ones_like(xd) if wts is None else wts.double()
+    ws = wd.gather(1, order)
+    PW, PX = _prefix_f64(ws, prefix), _prefix_f64(xs * ws, prefix)
+    thr = (xs[:, -1] - xs[:, 0]).clamp_min(1e-12) * tol
+    c = c0.double().clone()
+    active = torch.ones(rows, dtype=torch.bool, device=dev)
+    iters = torch.zeros(rows, dtype=torch.int32, device=dev)
+    pos = torch.arange(k, device=dev).expand(rows, k).contiguous()
+    zero_col = torch.zeros(rows, 1, dtype=torch.long, device=dev)
+    k_col = torch.full((rows, 1), k, dtype=torch.long, device=dev)
+    m = min(C, k)
+    for _ in range(max_iter):
+        if not bool(active.any()):
+            break
+        cs = torch.sort(c, dim=1).values
+        mid = ((cs[:, 1:] + cs[:, :-1]) * 0.5).contiguous()
+        b = torch.searchsorted(xs, mid, right=True)                 # points <= mid[j]
+        B = torch.cat([zero_col, b, k_col], dim=1)
+        n = B[:, 1:] - B[:, :-1]
+        cnt = PW.gather(1, B[:, 1:]) - PW.gather(1, B[:, :-1])
+        tot = PX.gather(1, B[:, 1:]) - PX.gather(1, B[:, :-1])
+        ok = (n > 0) & (cnt > 0)
+        new = torch.where(ok, tot / torch.where(ok, cnt, torch.ones_like(cnt)), cs)
+        empty = n <= 0
+        if bool((empty & active[:, None]).any()):
+            a_s = torch.searchsorted(b.contiguous(), pos, right=True)  # the cluster of sorted position i: boundaries <= i
+            err = (xs - new.gather(1, a_s)).abs() * ws
+            se, si = torch.sort(err, dim=1, descending=True, stable=True)
+            rank = torch.cumsum(empty.long(), dim=1) - 1
+            r = rank.clamp(0, m - 1)
+            cand_e = se[:, :m].gather(1, r)
+            cand = xs.gather(1, si[:, :m]).gather(1, r)
+            new = torch.where(empty & (rank < m) & (cand_e > 0), cand, new)
+        moved = ((new - cs).abs() > thr[:, None]).any(1)
+        c = torch.where(active[:, None], new, c)
+        iters += active.to(torch.int32)
+        active = active & moved
+    cs = torch.sort(c, dim=1).values
+    mid = ((cs[:, 1:] + cs[:, :-1]) * 0.5).contiguous()
+    assign = torch.searchsorted(mid, xd.contiguous())
+    sse = ((xd - cs.gather(1, assign)) ** 2 * wd).sum(1)
+    return assign.to(torch.int32), cs.float(), sse, iters
+
+
+KMEANS_FUSED_MAX_K = 16384  # the row (and its weights) stay in the LDS of one workgroup: csrc/kmeans.cuh KM_MAX_K
+KMEANS_FUSED_MAX_C = 16
+KMEANS_FUSED_MAX_S = 4
+
+
+def kmeans_rows_launch(x: torch.Tensor, wts: Optional[torch.Tensor], c0: torch.Tensor, max_iter: int = 300, tol: float = 1e-6):
+    """One tg_kmeans_rows launch: x f32 [rows][k] on the GPU, wts None / f32 [k] (shared) / f32 [rows][k] -- already abs().clamp_min(1e-12)
+    --, c0 f32 [S][rows][C] (or [rows][C]: one seeding).  -> (assign int32, centres f32, sse f64, iters int32) as lloyd_rows_ref,
+    the seeding with the strictly smallest SSE kept; iters is summed over the seedings."""
+    from . import _lib
+
+    if c0.dim() == 2:
+        c0 = c0[None]
+    rows, k = x.shape
+    S, _, C = c0.shape
+    if not x.is_cuda:
+        raise ValueError("the fused k-means runs on the GPU only (there is no CPU fallback): move the tensor to the device, or pass fused=False")
+    if x.dtype != torch.float32 or c0.dtype != torch.float32 or tuple(c0.shape[1:]) != (rows, C) or c0.device != x.device:
+        raise ValueError("kmeans_rows_launch: x f32 [rows][k] and c0 f32 [S][rows][C] on one device")
+    x, c0 = x.contiguous(), c0.contiguous()
+    stride = 0
+    if wts is not None:
+        if wts.dtype != torch.float32 or wts.device != x.device or tuple(wts.shape) not in ((k,), (rows, k)):
+            raise ValueError("kmeans_rows_launch: weights f32 [k] or [rows][k] on x's device")
+        wts = wts.contiguous()
+        stride = k if wts.dim() == 2 else 0
+    assign = torch.empty(rows, k, dtype=torch.int32, device=x.device)
+    centers = torch.empty(rows, C, dtype=torch.float32, device=x.device)
+    sse = torch.empty(rows, dtype=torch.float64, device=x.device)
+    iters = torch.empty(rows, dtype=torch.int32, device=x.device)
+    rc = _lib.load().tg_kmeans_rows(x.data_ptr(), 0 if wts is None else wts.data_ptr(), stride, c0.data_ptr(), assign.data_ptr(),
+                                    centers.data_ptr(), sse.data_ptr(), iters.data_ptr(), rows, k, C, S, int(max_iter), float(tol),
+                                    x.device.index if x.device.index is not None else torch.cuda.current_device(),
+                                    torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.check(rc, "tg_kmeans_rows")
+    return assign, centers, sse, iters
+
+
 @torch.no_grad()
 def kmeans_rows(x: torch.Tensor, n_clusters: int = 16, sample_weight: Optional[torch.Tensor] = None,
-                max_iter: int = 300, tol: float = 1e-6, init=("uniform", "density", "quantile")):
+                max_iter: int = 300, tol: float = 1e-6, init=("uniform", "density", "quantile"), fused: bool = False,
+                return_stats: bool = False):
     """Independent 1-D k-means on every row of x [rows][k] (float32, any device).
 
     sample_weight: None, [k] (shared by all rows -- activation-aware any4, quantize.py:483-489) or [rows][k].
@@ -199,16 +327,43 @@ def kmeans_rows(x: torch.Tensor, n_clusters: int = 16, sample_weight: Optional[t
     Empty clusters are re-seeded at the points with the largest weighted error, so a row with at most C distinct
     values is reproduced exactly.  Stops when no centroid moves by more than tol * row range (max_iter as sklearn).
     Returns (assign int32 [rows][k], centers float32 [rows][C] sorted ascending).
+
+    fused=True: the iterations of all seedings run in ONE launch of the HIP kernel (csrc/kmeans.cuh; its definition is lloyd_rows_ref):
+    no host sync, every row stops on its own criterion, f64 sums in a fixed order -- the same bits from run to run.  Weights and seeds
+    are prepared exactly as below, in torch.  GPU only, finite values, n_clusters <= 16, rows of at most 16384 points, at most 4
+    seedings: anything else raises ValueError before a launch.  return_stats=True (fused only) additionally returns
+    (weighted SSE f64 [rows], iterations summed over the seedings int32 [rows]).
     """
+    if return_stats and not fused:
+        raise ValueError("kmeans_rows: return_stats needs fused=True")
+    if fused:  # (the reasons that do not depend on the device first: each can be told apart without a GPU)
+        if n_clusters > KMEANS_FUSED_MAX_C or n_clusters < 1:
+            raise ValueError(f"kmeans_rows(fused=True): n_clusters must be 1 ... {KMEANS_FUSED_MAX_C}, got {n_clusters}")
+        if x.dim() != 2 or x.shape[1] < 1 or x.shape[1] > KMEANS_FUSED_MAX_K:
+            raise ValueError(f"kmeans_rows(fused=True): a row holds 1 ... {KMEANS_FUSED_MAX_K} points (it stays in one workgroup's LDS), "
+                             f"got shape {tuple(x.shape)}; longer rows (per_row=False) stay on fused=False")
+        if not bool(torch.isfinite(x).all()):
+            raise ValueError("kmeans_rows(fused=True): non-finite values in the tensor")
+        if not x.is_cuda:
+            raise ValueError("kmeans_rows(fused=True) runs on the GPU only (there is no CPU fallback): move the tensor to the device, or pass fused=False")
     x = x.float().contiguous()
     rows, k = x.shape
+    shared_w = None
     if sample_weight is None:
-        wts = torch.ones_like(x)
+        wts = None if fused else torch.ones_like(x)
     else:
         wts = sample_weight.to(x.device, torch.float32).abs()
-        wts = (wts.reshape(1, k).expand(rows, k) if wts.dim() == 1 else wts.reshape(rows, k)).contiguous()
-        wts = wts.clamp_min(1e-12)  # a zero weight must not orphan a point (kmeans.py run_kmeans: sample_weight_eps)
-    xw = x * wts
+        if fused and wts.dim() == 1:
+            shared_w = wts.reshape(k).clamp_min(1e-12).contiguous()  # one [k] vector for all rows: never expanded
+            wts = None
+        else:
+            wts = (wts.reshape(1, k).expand(rows, k) if wts.dim() == 1 else wts.reshape(rows, k)).contiguous()
+            wts = wts.clamp_min(1e-12)  # a zero weight must not orphan a point (kmeans.py run_kmeans: sample_weight_eps)
+    if fused:
+        w_any = shared_w if shared_w is not None else wts
+        if w_any is not None and not bool(torch.isfinite(w_any).all()):
+            raise ValueError("kmeans_rows(fused=True): non-finite values in the sample weights")
+    xw = None if fused else x * wts
     xs = torch.sort(x, dim=1).values
     lo = xs[:, :1]
     span = (xs[:, -1:] - lo).clamp_min(1e-12)
@@ -221,6 +376,14 @@ def kmeans_rows(x: torch.Tensor, n_clusters: int = 16, sample_weight: Optional[t
             warnings.warn(f"kmeans_rows: init={init!r} is scikit-learn's seeding; this batched Lloyd has no random state and "
                           f"uses its deterministic seedings {_SEEDINGS} instead (results do not depend on a seed)", stacklevel=2)
         init = _SEEDINGS
+    if fused:
+        kinds = (init,) if isinstance(init, str) else tuple(init)
+        if not 1 <= len(kinds) <= KMEANS_FUSED_MAX_S:
+            raise ValueError(f"kmeans_rows(fused=True): 1 ... {KMEANS_FUSED_MAX_S} seedings, got {len(kinds)}")
+        c0 = torch.stack([_init_centers(kind, x, xs, lo, span, n_clusters).expand(rows, n_clusters) for kind in kinds])
+        del xs
+        a, c, sse, iters = kmeans_rows_launch(x, shared_w if shared_w is not None else wts, c0, max_iter, tol)
+        return (a, c, sse, iters) if return_stats else (a, c)
     for kind in ((init,) if isinstance(init, str) else tuple(init)):
         a, c, sse = _lloyd(x, wts, xw, _init_centers(kind, x, xs, lo, span, n_clusters), span, max_iter, tol)
         if best is None:
@@ -245,10 +408,12 @@ _WARNED_INIT: set = set()  # scikit-learn seeding names already warned about (km
 def anyq_quantize_tensor(W: torch.Tensor, n_bit: int = 4, q_group_size: int = 128, per_row: bool = True,
                          zero_point: bool = True, scale_only: bool = False, sample_weight=None,
                          scale_sample_weight: bool = False, abs_weight_sample_weight: bool = False,
-                         init=("uniform", "density", "quantile"), max_iter: int = 300, device=None, **_):
+                         init=("uniform", "density", "quantile"), max_iter: int = 300, device=None, fused: bool = False, **_):
     """-> (assign int32 [n][k], any4 LUT [n][2^n_bit] (or [2^n_bit] when per_row=False) in the group-scaled
     [0, 2^n_bit - 1] domain, scales_and_zeros [k/g][n][2]); LUT and scales in W's dtype, on W's device.
-    `device` = where to do the work (default: W's device; pass "cuda" to cluster a CPU checkpoint on the GPU)."""
+    `device` = where to do the work (default: W's device; pass "cuda" to cluster a CPU checkpoint on the GPU).
+    `fused` = cluster with the HIP k-means kernel (kmeans_rows(fused=True): GPU only, rows of at most 16384 weights, so not
+    per_row=False; ValueError otherwise); grouping, sample weights and seeding are the same torch code either way."""
     orig_device, dtype = W.device, W.dtype
     if device is not None:
         W = W.to(device)
@@ -276,7 +441,7 @@ def anyq_quantize_tensor(W: torch.Tensor, n_bit: int = 4, q_group_size: int = 12
         sw = (torch.ones_like(W[0], dtype=torch.float32) if sw is None else sw) * W.abs().float()
     if sw is not None and not per_row:
         sw = sw.expand(orig_shape).reshape(1, -1) if sw.dim() == 1 else sw.reshape(1, -1)
-    assign, any4 = kmeans_rows(Wg, n_clusters=2 ** n_bit, sample_weight=sw, max_iter=max_iter, init=init)
+    assign, any4 = kmeans_rows(Wg, n_clusters=2 ** n_bit, sample_weight=sw, max_iter=max_iter, init=init, fused=fused)
     if not per_row:
         assign = assign.reshape(orig_shape)
         any4 = any4.squeeze(0)

@@ -346,6 +346,30 @@ TG_API int64_t tg_gemm_w8_workspace_bytes(const tg_w4_gemm* args);
 TG_API int tg_gemm_f16(const void* x, const void* w, void* y, int64_t m, int64_t wrows, int64_t k, int dtype,
                 int w_on_right, int inner_k_tiles, int device, tg_stream_t stream);
 
+/*
+ * The any4 quantizer's clustering step: an independent weighted 1-D k-means (Lloyd) on every row of x, one launch, one workgroup per
+ * row with the row sorted and resident in LDS (any4_amd/csrc/kmeans.cuh).  The definition, operation by operation in float64, is
+ * any4_amd/quantize.py: lloyd_rows_ref.  Added without an ABI version bump: callers probe for the symbol.
+ *   x        f32 [rows][k]
+ *   w        f32 weights, already |.| and > 0, or NULL (all 1); w_row_stride = k: [rows][k], 0: one [k] vector shared by all rows
+ *   c0       f32 [S][rows][C]: the seed centres of S seedings; the seeding with the strictly smallest weighted SSE is kept, in order
+ *   assign   int32 [rows][k]: the cluster of every point against the midpoints of the final centres (x <= mid[j] -> j)
+ *   centers  f32 [rows][C], ascending, one rounding from f64
+ *   sse      f64 [rows] or NULL: weighted squared error of the kept seeding
+ *   iters    int32 [rows] or NULL: Lloyd iterations run, summed over the S seedings
+ *   A row stops when no centre moved by more than tol * max(row range, 1e-12), or after max_iter iterations.
+ * Sums are f64 in a fixed order, no atomics: the same bits from launch to launch.
+ * Refusals, before any HIP call: rows < 0, k < 1, C outside 1..16, S outside 1..4, max_iter outside 1..10000, tol negative or not
+ * finite, w_row_stride neither 0 nor k: TG_E_SHAPE; k > 16384 (the row no longer fits the LDS): TG_E_SIZE; a required pointer NULL:
+ * TG_E_NULL; a pointer not aligned to its element: TG_E_ALIGN.  rows == 0 succeeds and launches nothing.
+ */
+TG_API int tg_kmeans_rows(const float* x, const float* w, int64_t w_row_stride, const float* c0, int32_t* assign, float* centers,
+                          double* sse, int32_t* iters, int64_t rows, int64_t k, int C, int S, int max_iter, double tol, int device,
+                          tg_stream_t stream);
+/* What tg_kmeans_rows would launch, without a GPU: out[0] = workgroups, out[1] = dynamic LDS bytes of each; or the negative TG_E_* code
+ * the launch would return for these sizes (weighted: w != NULL). */
+TG_API int tg_kmeans_rows_plan(int64_t rows, int64_t k, int C, int S, int max_iter, double tol, int weighted, int64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
