@@ -107,6 +107,24 @@ class MoeW4(ctypes.Structure):
             self.struct_bytes = ctypes.sizeof(MoeW4)
 
 
+class MoeGrouped(ctypes.Structure):
+    """struct dg_moe_grouped (include/decode_glue_hip.h)"""
+
+    _fields_ = [
+        ("struct_bytes", _u32), ("stage", _i32),
+        ("x", _vp), ("w", _vp), ("qinfo", _vp), ("lut", _vp), ("y", _vp), ("ids", _vp), ("gates", _vp), ("residual", _vp),
+        ("group_ws", _vp), ("f32_ws", _vp),
+        ("stride_w", _i64), ("stride_qinfo", _i64), ("stride_lut", _i64), ("m", _i64), ("wrows", _i64), ("k", _i64),
+        ("group_ws_bytes", _i64), ("f32_ws_bytes", _i64),
+        ("E", _i32), ("top_k", _i32), ("group", _i32), ("qtype", _i32), ("dtype", _i32), ("inner_k_tiles", _i32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = ctypes.sizeof(MoeGrouped)
+
+
 # (kernel, flags) -> the name the call had as an entry point of its own up to ABI 8: DG_ATTN_FLAVOURS of the header, which is what
 # dg_attn_launch accepts; error messages keep these names.  A copy written by hand (the header is not read at run time): a new flavour
 # gets its row here as well as there, and tests/test_host_cpu.py fails until the two agree.
@@ -190,6 +208,10 @@ SYMBOLS = {
     "dg_moe_route": [_vp] * 4 + [_i64] * 4 + [ctypes.c_int, ctypes.c_int, _vp],
     "dg_moe_w4_launch": [ctypes.POINTER(MoeW4), ctypes.c_int, _vp],
     "dg_moe_w4_plan": [ctypes.POINTER(MoeW4), ctypes.c_int, ctypes.POINTER(_i32)],
+    # mixture of experts, many rows: ids, group_ws, group_ws_bytes, m, top_k, E, bm, device, stream
+    "dg_moe_group": [_vp, _vp] + [_i64] * 5 + [ctypes.c_int, _vp],
+    "dg_moe_grouped_launch": [ctypes.POINTER(MoeGrouped), ctypes.c_int, _vp],
+    "dg_moe_grouped_plan": [ctypes.POINTER(MoeGrouped), ctypes.c_int, ctypes.POINTER(_i64)],
     # the quantizer's k-means: x, w, w_row_stride, c0, assign, centers, sse, iters, rows, k, C, S, max_iter, tol, device, stream
     "tg_kmeans_rows": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                        ctypes.c_int, _vp],

@@ -32,6 +32,7 @@ UNITS = [
     ("tg_splitk", "tg_splitk.hip", []),
     ("tg_gemv", "tg_gemv.hip", []),
     ("tg_tile", "tg_tile.hip", []),
+    ("tg_moe_tile", "tg_moe_tile.hip", []),
     ("tg_dx", "tg_dx.hip", []),
     ("tg_dq", "tg_dq.hip", []),
     ("tg_prefill", "tg_prefill.hip", []),

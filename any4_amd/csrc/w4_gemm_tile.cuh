@@ -38,9 +38,18 @@
 //              tile_split_sum_kernel (below) adds the splits in order, applies the bias and rounds once.  Why: a tile's k-steps are a chain
 //              of dependent LDS round trips, 0.6-0.9 us per 128 k whatever the tile holds -- a launch with 64 tiles takes as long as one with
 //              256 (tg_tile.hip chooses the splits; profiles/r06_tile_splitk.txt).
+//   grouped    template parameter GRP (mixture-of-experts prefill, dg_moe_grouped_launch; moe_grouped.cuh holds its parameter block PT, the
+//              group kernel that writes the tile list and the combine): a workgroup's m tile is entry `tm` of a tile list on the device
+//              -- (expert, first position in perm, rows <= BM) --, its weight, qinfo and LUT bases are the expert's, activation row r is
+//              GATHERED (the DMA's per-lane source address: x[perm[first + r] / top_k] for GRP = 1, x[perm[first + r]] for GRP = 2) and
+//              the store SCATTERS to the pair's own row: GRP = 1 (gate_up) the SwiGLU of gate row r and up row r + 8 of a 16-row tile,
+//              which sit 32 lanes apart (one v_permlane32_swap per accumulator register), GRP = 2 (down) the f32 sums.  A workgroup whose
+//              tile index is >= n_tiles exits before it touches memory.  Every GRP line is an `if constexpr`: the GRP = 0 instantiations
+//              keep their code.
 //   mx4        template flag QMX: the table entries are fp4[code] * 2^(e - 127) (exact in bf16; e = 255: NaN), the exponents one byte per row
 //              and 32-k group.  A flavour of its own because as a run-time branch it cost the other formats registers (128 x 128 tile: spill).
 #pragma once
+#include "w4_helpers.cuh"   // (swiglu16: the grouped gate_up store)
 
 struct TileParams {
   const char* x;       // [m][k] 16-bit, row-major
@@ -98,8 +107,10 @@ __device__ __forceinline__ void tile_barrier() {
 //       (m0, k0) (m1, k0) (m0, k0 + 1) (m1, k0 + 1), the second word at k0 + 8; m0 = t / 4, m1 = m0 + 8, k0 = 2q).  No tables: the
 //       dequantising waves compute w = RNE16(fma(byte - 128, scale, zero)) (Dequantization.cuh:262-330) in the vector ALU -- 2.75 operations
 //       per weight against one LDS lookup -- from scale / zero words they prefetch themselves; one quantisation group per step (g >= 64 KS).
-template <typename DT, int BM, int BN, int DX = 3, int NDW = 8, int KS = 1, int NCW = 4, bool QMX = false, int W8 = 0>
-__global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(const TileParams p) {
+// GRP = 0: the dense GEMM; 1 / 2: the grouped gate_up / down GEMM of dg_moe_grouped_launch, PT = GroupedTileParams (moe_grouped.cuh)
+template <typename DT, int BM, int BN, int DX = 3, int NDW = 8, int KS = 1, int NCW = 4, bool QMX = false, int W8 = 0, int GRP = 0, typename PT = TileParams>
+__global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(const PT p) {
+  static_assert(GRP == 0 || (!QMX && W8 == 0 && BN == 64), "grouped flavour: 4-bit words, BN = 64 (two 16-row tiles per consumer wave)");
   constexpr int WN = BN / 2;             // weight rows of a consumer wave
   constexpr int NT = WN / 16;            // its 16-row tiles
   constexpr int WMR = BM / (NCW / 2);    // activation rows of a consumer wave
@@ -126,7 +137,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
 
   const int lane = threadIdx.x & 63, wave_all = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   // ---- tile of this workgroup: consecutive tiles on ONE XCD (block b runs on XCD b % 8) ----
-  const int nsplit = p.splits > 1 ? p.splits : 1;
+  const int nsplit = GRP != 0 ? 1 : p.splits > 1 ? p.splits : 1;
   const int ntot = p.tiles_m * p.tiles_n * nsplit;
   int tile;
   {
@@ -136,7 +147,21 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
   // (n tile, split, m tile): the m tiles of one n tile and k range next to each other
   const int tns = tile / p.tiles_m, tm = tile - tns * p.tiles_m;
   const int tn = tns / nsplit, split = tns - tn * nsplit;
-  const int m0 = tm * BM, n0 = tn * BN;
+  const int m0 = GRP != 0 ? 0 : tm * BM, n0 = tn * BN;
+  // (grouped) this workgroup's entry of the tile list: the expert whose operands it reads, its rows of perm
+  int g_e = 0, g_first = 0, g_rows = BM;
+  if constexpr (GRP != 0) {
+    if constexpr (GRP == 1) {  // rows of pairs without a valid expert: +0, the columns of this n tile, dealt over the m-extent of the grid
+      const int n_inv = p.grp[1], half = p.wrows >> 1, col = (n0 >> 1) + (int)threadIdx.x;
+      if ((int)threadIdx.x < BN / 2 && col < half)
+        for (int j = tm; j < n_inv; j += p.tiles_m) *reinterpret_cast<uint16_t*>(p.y + ((int64_t)p.grp[p.inv_off + j] * half + col) * 2) = 0;
+    }
+    if (tm >= p.grp[0]) return;  // (uniform: the grid's m-extent is the bound, n_tiles is the router's)
+    const int32_t* te = p.grp + p.tiles_off + 3 * tm;
+    g_e = te[0];
+    g_first = te[1];
+    g_rows = te[2];
+  }
   const int ksuper_l = p.ksuper / nsplit;                      // this workgroup's super-tiles: split * ksuper_l ... (host: divides, a multiple of KS
   const int ks0 = split * ksuper_l;                            // and of the quantisation group)
   const int ksteps = ksuper_l >> KSH;                          // KS super-tiles of 64 k per step
@@ -273,7 +298,9 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
       const int t8 = dw * WPT + u;
       int gt = (n0 >> 3) + t8;
       gt = gt < ntiles8 ? gt : ntiles8 - 1;
-      wsrc[u] = reinterpret_cast<const uint32_t*>(p.w) + (((int64_t)gt * p.ksuper + ks0) * 32 + 4 * drow8 + di) * 2 + dj;
+      const char* wb = p.w;
+      if constexpr (GRP != 0) wb += (int64_t)g_e * p.stride_w;
+      wsrc[u] = reinterpret_cast<const uint32_t*>(wb) + (((int64_t)gt * p.ksuper + ks0) * 32 + 4 * drow8 + di) * 2 + dj;
       const int row = t8 * 8 + drow8;
 #pragma unroll
       for (int h = 0; h < 4; ++h) dst0[u][h] = (uint32_t)(row * 128 + 4 * di) + (((uint32_t)(4 * dj + h) ^ (uint32_t)((row >> 1) & 7)) << 4);
@@ -343,6 +370,10 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
     for (int q = 0; q < XPW; ++q) {
       const int row = (xw * XPW + q) * 8 + (lane >> 3);
       int mr = m0 + row;
+      if constexpr (GRP != 0) {                                 // gathered: the pair at this row of the tile (rows beyond the tile's: its last row again, never stored)
+        mr = p.grp[p.perm_off + g_first + (row < g_rows ? row : g_rows - 1)];
+        if constexpr (GRP == 1) mr /= p.top_k;
+      } else
       mr = mr < p.m ? mr : p.m - 1;                             // (rows beyond m: a valid row, never stored)
       const int chunk = (lane & 7) ^ ((row >> 1) & 7);          // LDS slot lane & 7 <- global chunk slot ^ f(row)
       xsrc[q] = p.x + ((int64_t)mr * p.x_pitch + ks0 * 64) * 2 + chunk * 16;
@@ -382,6 +413,7 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
     gr = gr < p.wrows ? gr : p.wrows - 1;
     // (mx4, bf16 only: one exponent byte per row and 32-k group, row-major; the table entry is fp4[code] * 2^(e - 127), exact)
     if constexpr (QMX) qsrc[v] = reinterpret_cast<const uint32_t*>(p.qinfo + (int64_t)gr * (p.k >> 5) + g0);
+    else if constexpr (GRP != 0) qsrc[v] = reinterpret_cast<const uint32_t*>(p.qinfo + (int64_t)g_e * p.stride_qinfo) + (int64_t)g0 * p.wrows + gr;
     else qsrc[v] = reinterpret_cast<const uint32_t*>(p.qinfo) + (int64_t)g0 * p.wrows + gr;
     const int e4 = (tid & 3) * 4;
     if constexpr (W8 != 0) {      // (int8: no tables)
@@ -397,7 +429,9 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
         lv[v][e] = (c & 8 ? -1.f : 1.f) * (mag < 5 ? 0.5f * mag : (mag == 5 ? 3.f : mag == 6 ? 4.f : 6.f));   // fp4-e2m1 (FloatDefs.cuh:18-34)
       }
     } else {
-      const u32x2 pr = *reinterpret_cast<const u32x2*>(p.lut + ((p.qtype == TG_Q_ANY4_ROWWISE ? (int64_t)gr * 16 : 0) + e4) * 2);
+      const char* lb = p.lut;
+      if constexpr (GRP != 0) lb += (int64_t)g_e * p.stride_lut;
+      const u32x2 pr = *reinterpret_cast<const u32x2*>(lb + ((p.qtype == TG_Q_ANY4_ROWWISE ? (int64_t)gr * 16 : 0) + e4) * 2);
       lv[v][0] = DT::lo_f32(pr[0]); lv[v][1] = DT::hi_f32(pr[0]); lv[v][2] = DT::lo_f32(pr[1]); lv[v][3] = DT::hi_f32(pr[1]);
     }
   }
@@ -516,6 +550,44 @@ __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(cons
     }
   }
 
+  if constexpr (GRP != 0) {
+    // ---- grouped store: row fi of tile b belongs to pair perm[first + row] and goes to that pair's own row ----
+#pragma unroll
+    for (int b = 0; b < MT; ++b) {
+      const int row = wm * WMR + b * 16 + fi;
+      if constexpr (GRP == 1) {
+        // gate rows 0 ... 7 of a 16-row tile are in lanes 0 ... 31 (kq = 0, 1), its up rows 8 ... 15 in lanes 32 ... 63.  One swap per register of
+        // tiles (0, 1): lanes 0 ... 31 then hold gate and up of tile 0, lanes 32 ... 63 those of tile 1, rows 4 (kq & 1) ... + 3 of the block.
+        // (every lane takes part: the row test comes after the swaps)
+        static_assert(NT == 2, "two 16-row tiles per consumer wave");
+        float gt[4], up[4];
+#pragma unroll
+        for (int v = 0; v < 4; ++v) {
+          const float a0 = acc[0][b][v], a1 = acc[1][b][v];   // (by value: a bit_cast of the vector element itself read element 0)
+          const auto s = __builtin_amdgcn_permlane32_swap(__builtin_bit_cast(uint32_t, a0), __builtin_bit_cast(uint32_t, a1), false, false);
+          gt[v] = __builtin_bit_cast(float, (uint32_t)s[0]);
+          up[v] = __builtin_bit_cast(float, (uint32_t)s[1]);
+        }
+        const int nr = n0 + wn * WN + (kq >> 1) * 16;
+        if (row < g_rows && nr < p.wrows) {  // (wrows is a multiple of 16: a gate / up block is inside or outside)
+          const int64_t pr = p.grp[p.perm_off + g_first + row];
+          const u32x2 o = {(uint32_t)swiglu16<DT>(gt[0], up[0]) | ((uint32_t)swiglu16<DT>(gt[1], up[1]) << 16),
+                           (uint32_t)swiglu16<DT>(gt[2], up[2]) | ((uint32_t)swiglu16<DT>(gt[3], up[3]) << 16)};
+          *reinterpret_cast<u32x2*>(p.y + (pr * (p.wrows >> 1) + (nr >> 1) + 4 * (kq & 1)) * 2) = o;
+        }
+      } else {
+        if (row >= g_rows) continue;
+        const int64_t pr = p.grp[p.perm_off + g_first + row];
+#pragma unroll
+        for (int a = 0; a < NT; ++a) {
+          const int nr = n0 + wn * WN + a * 16 + 4 * kq;
+          if (nr >= p.wrows) continue;
+          *reinterpret_cast<f32x4*>(p.part + pr * p.wrows + nr) = acc[a][b];   // the unrounded f32 sums d[pair][wrows]
+        }
+      }
+    }
+    return;
+  }
   // ---- store: lane (j = activation row fi of tile b, weight rows 4 kq ... 4 kq + 3 of tile a) ----
 #pragma unroll
   for (int b = 0; b < MT; ++b) {

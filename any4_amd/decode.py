@@ -75,6 +75,9 @@ class DecodeConfig:
     # a router, and a token runs `experts_per_token` of them.  Needs gate_up_interleave = 8 (the stacked experts' row order).
     experts: int = 0
     experts_per_token: int = 2
+    # calls of the sparse MLP block with this many rows or more (a prompt) run the grouped path (any4_amd/moe.py: MoEMLP(grouped_from=...),
+    # numerics of moe_grouped_ref); 0 = off: every call runs the GEMV launches in blocks of 8 rows
+    moe_grouped_from: int = 0
 
     @classmethod
     def llama3_8b(cls, **kw) -> "DecodeConfig":
@@ -316,7 +319,8 @@ class DecodeLayer(torch.nn.Module):
             gus = [factory("gate_up", idx, cfg.hidden, 2 * cfg.inter) for _ in range(cfg.experts)]
             downs = [factory("down", idx, cfg.inter, cfg.hidden) for _ in range(cfg.experts)]
             router = torch.randn(cfg.experts, cfg.hidden, device=device, generator=getattr(factory, "gen", None)) / math.sqrt(cfg.hidden)
-            self.moe = MoEMLP(router.to(dtype), MoEWeights.from_linears(gus, downs), cfg.experts_per_token)
+            self.moe = MoEMLP(router.to(dtype), MoEWeights.from_linears(gus, downs), cfg.experts_per_token,
+                              grouped_from=cfg.moe_grouped_from or None)
             self.gate_up = self.down = None
         else:
             self.gate_up = factory("gate_up", idx, cfg.hidden, 2 * cfg.inter // world)

@@ -491,6 +491,95 @@ def moe_plan(stage: int, stack, m: int, top_k: int, device: int = -1):
     return tuple(out)
 
 
+def moe_grouped_plan(stage: int, stack, m: int, top_k: int, device: int = -1):
+    """(bm, bn, the grid's m-extent bound, n tiles, 64-k super-tiles per step, group workspace bytes, f32 workspace bytes) of a grouped launch
+    (dg_moe_grouped_plan; nothing is launched; device < 0: no GPU needed).  bm is the tile height dg_moe_group sorts for."""
+    buf = ctypes.create_string_buffer(256)
+    p = (ctypes.addressof(buf) + 63) & ~63  # a non-NULL, aligned dummy: the planner dereferences nothing
+    call = _lib.MoeGrouped(stage=stage, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=m,
+                           wrows=stack.n, k=stack.k, E=stack.E, top_k=top_k, group=stack.group, qtype=stack.qtype,
+                           dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
+    out = (ctypes.c_int64 * 7)()
+    _lib.check(_lib.load().dg_moe_grouped_plan(ctypes.byref(call), device, out), "dg_moe_grouped_plan")
+    return tuple(out)
+
+
+def moe_group(ids: torch.Tensor, E: int, bm: int, out: torch.Tensor = None) -> torch.Tensor:
+    """The group workspace (int32, include/decode_glue_hip.h: dg_moe_group; any4_amd/moe.py: group_ref is the definition) of ids int32
+    [m, top_k]: the pairs sorted by expert and the tile list the grouped GEMMs walk.  bm: moe_grouped_plan()[0].  out: the buffer to fill."""
+    _gpu(ids, out)
+    if ids.dtype != torch.int32 or ids.dim() != 2:
+        raise RuntimeError(f"moe_group: ids must be int32 [m, top_k], got {ids.dtype} {tuple(ids.shape)}")
+    m, top_k = ids.shape
+    P = m * top_k
+    need = 136 + 2 * P + 3 * (-(-P // bm) + min(E, P))
+    if out is None:
+        out = torch.empty(need, dtype=torch.int32, device=ids.device)
+    elif out.dtype != torch.int32 or out.dim() != 1:
+        raise RuntimeError("moe_group: out must be a flat int32 tensor")
+    _lib.check(_lib.load().dg_moe_group(ids.data_ptr(), out.data_ptr(), out.numel() * 4, m, top_k, E, bm, ids.device.index, _stream(ids)),
+               "dg_moe_group")
+    return out
+
+
+def moe_grouped_call(stage: int, x, stack, ids, group_ws, gates=None, residual=None, y=None, f32_ws=None) -> "_lib.MoeGrouped":
+    """struct dg_moe_grouped for one stage on an `any4_amd.moe.ExpertStack`."""
+    ptr = lambda t: None if t is None else t.data_ptr()
+    per = lambda t: 0 if t is None else t[0].numel() * t.element_size()
+    nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()
+    return _lib.MoeGrouped(stage=stage, x=ptr(x), w=ptr(stack.words), qinfo=ptr(stack.qinfo), lut=ptr(stack.lut), y=ptr(y), ids=ptr(ids),
+                           gates=ptr(gates), residual=ptr(residual), group_ws=ptr(group_ws), f32_ws=ptr(f32_ws), stride_w=per(stack.words),
+                           stride_qinfo=per(stack.qinfo), stride_lut=per(stack.lut), m=ids.shape[0], wrows=stack.n, k=stack.k,
+                           group_ws_bytes=nbytes(group_ws), f32_ws_bytes=nbytes(f32_ws), E=stack.E, top_k=ids.shape[1], group=stack.group,
+                           qtype=stack.qtype, dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
+
+
+def _group_ws_check(what, group_ws):
+    _gpu(group_ws)
+    if group_ws is None or group_ws.dtype != torch.int32:
+        raise RuntimeError(f"{what}: group_ws must be the int32 workspace moe_group filled")
+
+
+def moe_gate_up_grouped(x: torch.Tensor, stack, ids: torch.Tensor, group_ws: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
+    """moe_gate_up for many rows (dg_moe_grouped_launch, DG_MOE_GATE_UP): the tile GEMM over the pairs sorted by expert; its numerics are
+    any4_amd/moe.py: moe_grouped_ref's (16-bit weights).  group_ws: moe_group(ids, ...)."""
+    m, top_k = ids.shape
+    _moe_check("moe_gate_up_grouped", x, stack, ids, m)
+    _group_ws_check("moe_gate_up_grouped", group_ws)
+    if out is None:
+        out = torch.empty((m * top_k, stack.n // 2), dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or tuple(out.shape) != (m * top_k, stack.n // 2) or not out.is_contiguous():
+        raise RuntimeError(f"moe_gate_up_grouped: out must be contiguous [{m * top_k}, {stack.n // 2}] {x.dtype}")
+    call = moe_grouped_call(_lib.DG_MOE_GATE_UP, x, stack, ids, group_ws, y=out)
+    _lib.check(_lib.load().dg_moe_grouped_launch(ctypes.byref(call), x.device.index, _stream(x)), "dg_moe_grouped_launch")
+    return out
+
+
+def moe_down_grouped(act: torch.Tensor, stack, ids: torch.Tensor, gates: torch.Tensor, group_ws: torch.Tensor, residual: torch.Tensor = None,
+                     out: torch.Tensor = None, f32_ws: torch.Tensor = None) -> torch.Tensor:
+    """moe_down for many rows (dg_moe_grouped_launch, DG_MOE_DOWN: the tile GEMM into f32_ws [m * top_k, n] float32, then the combine).
+    out may be `residual` itself.  f32_ws: the workspace to use (it is not cleared and need not be)."""
+    m, top_k = ids.shape
+    _moe_check("moe_down_grouped", act, stack, ids, m * top_k)
+    _group_ws_check("moe_down_grouped", group_ws)
+    _gpu(gates, residual, out, f32_ws)
+    if gates.dtype != torch.float32 or tuple(gates.shape) != (m, top_k):
+        raise RuntimeError(f"moe_down_grouped: gates must be float32 [{m}, {top_k}]")
+    if residual is not None and (residual.dtype != act.dtype or tuple(residual.shape) != (m, stack.n)):
+        raise RuntimeError(f"moe_down_grouped: residual must be [{m}, {stack.n}] {act.dtype}")
+    if out is None:
+        out = torch.empty((m, stack.n), dtype=act.dtype, device=act.device)
+    elif out.dtype != act.dtype or tuple(out.shape) != (m, stack.n):
+        raise RuntimeError(f"moe_down_grouped: out must be [{m}, {stack.n}] {act.dtype}")
+    if f32_ws is None:
+        f32_ws = torch.empty((m * top_k, stack.n), dtype=torch.float32, device=act.device)
+    elif f32_ws.dtype != torch.float32 or f32_ws.numel() < m * top_k * stack.n:
+        raise RuntimeError(f"moe_down_grouped: f32_ws must hold {m * top_k} x {stack.n} float32")
+    call = moe_grouped_call(_lib.DG_MOE_DOWN, act, stack, ids, group_ws, gates, residual, out, f32_ws)
+    _lib.check(_lib.load().dg_moe_grouped_launch(ctypes.byref(call), act.device.index, _stream(act)), "dg_moe_grouped_launch")
+    return out
+
+
 def swiglu(gu: torch.Tensor) -> torch.Tensor:
     """gu [bs, 2 il] = [gate | up] -> silu(gate) * up [bs, il]."""
     _gpu(gu)

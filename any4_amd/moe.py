@@ -9,6 +9,10 @@ A sparse MLP block replaces a layer's one gate_up / down pair by E of them and a
     (gate_up in the 8 + 8 interleaved row order of `DecodeConfig.gate_up_interleave = 8`, and down).
   * `MoEMLP(router_w, weights, top_k)` is the block: `forward(x, residual)` runs the three launches, `forward(..., fused=False)` a
     plain-torch formulation that runs ALL experts and combines them with a mask (no value is read on the host either way).
+  * Many rows (a prompt): `MoEMLP(..., grouped_from=R)` runs calls of R rows or more as route, dg_moe_group, dg_moe_grouped_launch twice: the
+    pairs sorted by expert (`group_ref` is the definition of that workspace) and a tile GEMM that reads a selected expert once per 128 of
+    its rows.  A tile GEMM dequantises into LDS, so its weights are the 16-bit ones, w = RNE16(fma(lut[code], scale, zero)), as in the dense
+    stack's prefill: `moe_grouped_ref` (= moe_ref(..., weights="rounded")) is the definition of that path, everything else as below.
 
 For activation row i (16-bit, already RMS-normed):
   logits   l[i][e] = sum_c router_w[e][c] x[i][c]             f32 sums, NOT rounded to 16 bit
@@ -78,6 +82,13 @@ class ExpertStack:
         zero = q[:, :, 1].t().repeat_interleave(self.group, dim=1)
         return v * scale + zero
 
+    def weights_rounded64(self, e: int) -> torch.Tensor:
+        """[n][k] float64: the 16-bit weights RNE16(fma(f32(lut[code]), f32(scale), f32(zero))) a tile GEMM multiplies by.  (The float64
+        scale * lut + zero of 16-bit factors is exact up to the last of 53 bits; rounding it to f32 is the fma.)"""
+        if self.dense is not None:
+            return self.dense[e].double()
+        return self.weights64(e).float().to(self.dtype).double()
+
     def weights16(self, e: int) -> torch.Tensor:
         """[n][k] in the stack's 16-bit type: what the plain-torch formulation multiplies by (on a GPU: tg_dequant_w4)."""
         if self.dense is not None:
@@ -135,8 +146,12 @@ def route_ref(logits: torch.Tensor, top_k: int):
     return ids, ps / ps.sum(dim=-1, keepdim=True)
 
 
-def moe_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: bool = False):
-    """The definition (module docstring), float64: y [m][hidden] in x's dtype; parts: (y, ids, gates, logits) with the float64 values."""
+def moe_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: bool = False, weights: str = "exact"):
+    """The definition (module docstring), float64: y [m][hidden] in x's dtype; parts: (y, ids, gates, logits) with the float64 values.
+    weights: "exact" -- scale * lut[code] + zero, not rounded: the GEMV path -- or "rounded" -- the 16-bit weights of the grouped path."""
+    if weights not in ("exact", "rounded"):
+        raise ValueError(f'weights must be "exact" or "rounded", got {weights!r}')
+    w64 = (lambda st, e: st.weights64(e)) if weights == "exact" else (lambda st, e: st.weights_rounded64(e))
     dt = x.dtype
     x64 = x.double()
     logits = x64 @ router_w.double().t()
@@ -148,15 +163,66 @@ def moe_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: 
         rows = hit.any(dim=1).nonzero().flatten()
         if rows.numel() == 0:
             continue
-        g, u = _split8(x64[rows] @ experts.gate_up.weights64(e).t())
+        g, u = _split8(x64[rows] @ w64(experts.gate_up, e).t())
         g16, u16 = g.to(dt).double(), u.to(dt).double()
         a = ((g16 / (1.0 + torch.exp(-g16))).to(dt).double() * u16).to(dt).double()
-        d = a @ experts.down.weights64(e).t()
+        d = a @ w64(experts.down, e).t()
         acc[rows] += (gates[rows] * hit[rows]).sum(dim=1, keepdim=True) * d
     if residual is not None:
         acc = acc + residual.double()
     y = acc.to(dt)
     return (y, ids, gates, logits) if parts else y
+
+
+def moe_grouped_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: bool = False):
+    """The definition of the GROUPED path (MoEMLP(grouped_from=...), dg_moe_grouped_launch), float64: moe_ref over the 16-bit weights
+    w = RNE16(fma(lut[code], scale, zero)) -- what a tile GEMM holds in LDS --, with moe_ref's rounding points for SwiGLU and the combine."""
+    return moe_ref(x, router_w, experts, top_k, residual, parts, weights="rounded")
+
+
+GROUP_PERM = 136  # int32 units in front of perm in the group workspace: n_tiles, n_invalid, n_valid, bm; count[64]; offset[68]
+
+
+def group_ref(ids, E: int, BM: int):
+    """The definition of dg_moe_group's workspace, plain numpy: ids [m][top_k] -> a namespace of int32 arrays
+      perm [P]       the pairs p = i top_k + s with an id in [0, E), sorted by (expert ascending, pair ascending) (stable); -1 from n_valid on
+      invalid [P]    the other pairs, ascending; -1 from n_invalid on
+      count [E], offset [E + 1] (its prefix)
+      tiles [bound][3]  (expert, first position in perm, rows <= BM), ceil(count[e] / BM) per expert, experts ascending; zeros from n_tiles on
+      n_tiles, n_invalid, n_valid, bound = ceil(P / BM) + min(E, P)
+      workspace      the whole int32 image as the kernel writes it (include/decode_glue_hip.h)"""
+    import numpy as np
+    from types import SimpleNamespace
+
+    a = (ids.detach().cpu().numpy() if isinstance(ids, torch.Tensor) else np.asarray(ids)).astype(np.int64).reshape(-1)
+    P = a.size
+    ok = (a >= 0) & (a < E)
+    pairs = np.arange(P, dtype=np.int64)
+    valid = pairs[ok]
+    order = valid[np.argsort(a[valid], kind="stable")]
+    bad = pairs[~ok]
+    count = np.bincount(a[valid], minlength=E)[:E].astype(np.int32) if valid.size else np.zeros(E, np.int32)
+    offset = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
+    bound = -(-P // BM) + min(E, P)
+    tiles = np.zeros((bound, 3), np.int32)
+    n = 0
+    for e in range(E):
+        for t in range(0, int(count[e]), BM):
+            tiles[n] = (e, offset[e] + t, min(BM, int(count[e]) - t))
+            n += 1
+    perm = np.full(P, -1, np.int32)
+    perm[:order.size] = order
+    invalid = np.full(P, -1, np.int32)
+    invalid[:bad.size] = bad
+    ws = np.zeros(GROUP_PERM + 2 * P + 3 * bound, np.int32)
+    ws[:4] = (n, bad.size, order.size, BM)
+    ws[4:4 + E] = count
+    ws[68:68 + E + 1] = offset
+    ws[GROUP_PERM:GROUP_PERM + P] = perm
+    ws[GROUP_PERM + P:GROUP_PERM + 2 * P] = invalid
+    ws[GROUP_PERM + 2 * P:] = tiles.reshape(-1)
+    return SimpleNamespace(perm=perm, invalid=invalid, count=count, offset=offset, tiles=tiles, n_tiles=n, n_invalid=int(bad.size),
+                           n_valid=int(order.size), bound=bound, workspace=ws)
 
 
 class MoEMLP(torch.nn.Module):
@@ -165,7 +231,9 @@ class MoEMLP(torch.nn.Module):
     record: an optional list; the plain-torch path appends (its f32 logits [rows][E], the activations x) to it at every call (tests
     assert the router's margins on them)."""
 
-    def __init__(self, router_w: torch.Tensor, weights: MoEWeights, top_k: int):
+    def __init__(self, router_w: torch.Tensor, weights: MoEWeights, top_k: int, grouped_from: int = None):
+        """grouped_from = R: forward(fused=True) on R rows or more runs the grouped path (module docstring; its numerics are
+        moe_grouped_ref's); None: every call runs the GEMV launches."""
         super().__init__()
         E = weights.E
         if router_w.dim() != 2 or router_w.shape[0] != E or router_w.shape[1] != weights.gate_up.k:
@@ -173,7 +241,11 @@ class MoEMLP(torch.nn.Module):
         if not 1 <= E <= 64 or not 1 <= top_k <= min(E, 8):
             raise ValueError(f"1 <= E <= 64 and 1 <= top_k <= min(E, 8) needed, got E = {E}, top_k = {top_k}")
         self.router = torch.nn.Parameter(router_w, requires_grad=False)
+        if grouped_from is not None and grouped_from < 1:
+            raise ValueError(f"grouped_from must be None or >= 1, got {grouped_from}")
         self.weights, self.top_k, self.record = weights, int(top_k), None
+        self.grouped_from = grouped_from
+        self._grouped = {}  # rows -> (bm, ids, gates, group workspace, act, f32 workspace): allocated at the first call with that row count
 
     def forward(self, x, residual=None, fused: bool = True, out=None):
         """out (the kernels only): where the result goes; it may be `residual` itself -- the residual stream, updated in place."""
@@ -183,9 +255,31 @@ class MoEMLP(torch.nn.Module):
             raise RuntimeError("MoEMLP: the kernels need 4-bit experts; 16-bit experts run with fused=False only")
         from . import decode_ops as G
 
+        if self.grouped_from is not None and x.shape[0] >= self.grouped_from:
+            return self._forward_grouped(x, residual, out)
         ids, gates = G.moe_route(x, self.router, self.top_k)
         act = G.moe_gate_up(x, self.weights.gate_up, ids)
         return G.moe_down(act, self.weights.down, ids, gates, residual, out)
+
+    def _forward_grouped(self, x, residual, out):
+        """route, group, grouped gate_up, grouped down (+ combine).  The buffers between the launches are kept per row count: no allocation
+        at steady state, and a captured graph replays on the buffers it was captured with."""
+        from . import decode_ops as G
+
+        W, rows, k = self.weights, x.shape[0], self.top_k
+        buf = self._grouped.get(rows)
+        if buf is None:
+            plan = G.moe_grouped_plan(1, W.down, rows, k)
+            dev = x.device
+            buf = self._grouped[rows] = (
+                int(plan[0]), torch.empty((rows, k), dtype=torch.int32, device=dev), torch.empty((rows, k), dtype=torch.float32, device=dev),
+                torch.empty(int(plan[5]) // 4, dtype=torch.int32, device=dev), torch.empty((rows * k, W.down.k), dtype=x.dtype, device=dev),
+                torch.empty((rows * k, W.down.n), dtype=torch.float32, device=dev))
+        bm, ids, gates, gws, act, fws = buf
+        G.moe_route(x, self.router, k, ids, gates)
+        G.moe_group(ids, W.E, bm, gws)
+        G.moe_gate_up_grouped(x, W.gate_up, ids, gws, act)
+        return G.moe_down_grouped(act, W.down, ids, gates, gws, residual, out, fws)
 
     def _torch(self, x, residual=None):
         """All E experts on every row, combined with a device-side mask: E times the work, nothing read on the host."""

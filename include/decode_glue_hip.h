@@ -328,7 +328,8 @@ TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, con
  *                          order depends on ids alone, so the same inputs give the same bits on every launch.  A pair with an invalid
  *                          id contributes nothing; a row without a valid pair gets RNE16(residual), or zeros.
  *   int4 and any4, inner_k_tiles 4, group 64 / 128 / 256, k % 64 == 0, wrows % 16 == 0.  m <= 8 is one launch; larger m is issued as
- *   ceil(m / 8) launches on the caller's stream (every block of 8 rows re-reads its experts: prefill is correct, not fast).
+ *   ceil(m / 8) launches on the caller's stream (every block of 8 rows re-reads its experts: for many rows -- a prompt -- there is
+ *   dg_moe_grouped_launch below, which reads a selected expert once per 128 of its rows).
  *   Within a launch a selected expert's rows cross the memory interface once per workgroup range as long as at most `pairs per sweep`
  *   (dg_moe_w4_plan: 8; fewer from k of about 4800 on, because the sweep's activation rows are staged in LDS) pairs chose it; an unselected
  *   expert's bytes are never requested.  No atomics, no scratch, no allocation, no synchronisation.
@@ -371,6 +372,79 @@ TG_API int dg_moe_route(const void* x, const void* router_w, int32_t* ids, float
                         int dtype, int device, tg_stream_t stream);
 TG_API int dg_moe_w4_launch(const dg_moe_w4* call, int device, tg_stream_t stream);
 TG_API int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out);
+
+/* ---- mixture of experts for MANY rows (a prompt): the pairs sorted by expert, then a grouped 4-bit tile GEMM ----
+ * The definition is any4_amd/moe.py: moe_grouped_ref (the group workspace's: group_ref).  Four launches serve one sparse MLP block: dg_moe_route
+ * (above), dg_moe_group, dg_moe_grouped_launch twice (DG_MOE_GATE_UP; DG_MOE_DOWN, which issues the combine behind its GEMM).  Nothing is
+ * read on the host: the grid is sized by a bound, so a captured graph follows the router.  New symbols within ABI 9: probe for them.
+ *
+ * NUMERICS are the tile GEMM's (tg_gemm_w4 at many rows), NOT dg_moe_w4's: a weight is w = RNE16(fma(f32(lut[row][code]), f32(scale),
+ *   f32(zero))) (int4: lut = code - 8), products are summed in f32 (v_mfma_f32_16x16x32), k ascending in 64-k super-tiles, never split: the
+ *   bits of a row's sums do not depend on m, on the tile the row landed in or on the other rows.
+ *
+ * dg_moe_group   ids int32 [m][top_k] -> the group workspace (int32; P = m top_k pairs, pair p = i top_k + s; one launch of one workgroup,
+ *   no atomics, the same ids give the same bytes):
+ *     [0] n_tiles  [1] n_invalid  [2] n_valid  [3] bm
+ *     [4 ... 67]    count[e]   pairs of expert e (0 from E on)
+ *     [68 ... 135]  offset[e]  prefix of count, offset[E] = n_valid (0 beyond)
+ *     [136 ...]     perm[P]    the pairs with an id in [0, E), sorted by (expert ascending, pair ascending) -- a stable counting sort --; -1 from
+ *                              n_valid on
+ *     then          invalid[P] the pairs whose id is outside [0, E), ascending; -1 from n_invalid on.  Such an id is never turned into an address.
+ *     then          tiles[bound][3]  (expert, first position in perm, rows <= bm): an expert with c pairs has ceil(c / bm) tiles, experts
+ *                              ascending; zeros from n_tiles on.  bound = ceil(P / bm) + min(E, P) >= n_tiles is the m-extent of the GEMM's grid.
+ *   group_ws_bytes >= 4 * (136 + 2 P + 3 bound).  bm: the GEMM's tile height (dg_moe_grouped_plan out[0]).
+ *   TG_E_NULL; TG_E_SHAPE (m < 1, E outside 1 ... 64, top_k outside 1 ... min(E, 8), bm not the GEMM's); TG_E_SIZE (P > 65536, workspace too
+ *   small); TG_E_ALIGN (ids, group_ws off 4 bytes).  Nothing is launched in these cases.
+ *
+ * dg_moe_grouped_launch   operands as dg_moe_w4 (stacked experts: base + e * stride); group_ws as dg_moe_group left it for the same ids.
+ *   An LDS-tiled MFMA GEMM, one workgroup per (tile of the list, n tile); a workgroup whose tile index is >= n_tiles exits before it touches
+ *   memory; rows beyond a tile's `rows` are not stored.  Activation rows are gathered, results scattered to the pair's own row:
+ *   stage DG_MOE_GATE_UP   x [m][k]; y [P][wrows / 2], row p = RNE16(RNE16(silu(RNE16(gate))) RNE16(up)) of expert ids[p]; rows of the pairs in
+ *                          invalid[] are written as +0.
+ *   stage DG_MOE_DOWN      x [P][k]; the GEMM stores the unrounded f32 sums d [P][wrows] to f32_ws (f32_ws_bytes >= 4 P wrows, 16-byte
+ *                          aligned, not cleared: the row of an invalid pair is never read), then the combine: y[i] = RNE16(sum_s gates[i][s]
+ *                          d[i top_k + s] (+ residual[i])), fused multiply-adds from 0 in the order (expert id ascending, then slot
+ *                          ascending), the residual last -- DG_MOE_DOWN's order in dg_moe_w4.  y may be residual.
+ *   int4 and any4, inner_k_tiles 4, group 64 / 128 / 256, k % 64 == 0, wrows % 16 == 0, any m >= 1 with P <= 65536.  No atomics, no scratch,
+ *   no allocation, no synchronisation.
+ *   Refusals in dg_moe_w4's order with its codes; the workspaces join them: group_ws (f32_ws for DOWN) NULL with the required pointers
+ *   (TG_E_NULL), P > 65536 or a workspace too small with TG_E_SIZE, group_ws off 4 / f32_ws off 16 bytes with TG_E_ALIGN.
+ * dg_moe_grouped_plan   nothing launched, the workspaces are not looked at; out[0] bm (pairs per tile), out[1] weight rows per tile, out[2] the
+ *   grid's m-extent (bound), out[3] n tiles, out[4] 64-k super-tiles per step (2 when k % 128 == 0), out[5] bytes of the group workspace,
+ *   out[6] bytes of the f32 workspace (0 for GATE_UP).  device < 0: without a device. */
+typedef struct dg_moe_grouped {
+  uint32_t struct_bytes;  /* sizeof(struct dg_moe_grouped); anything else is TG_E_STRUCT */
+  int32_t stage;          /* DG_MOE_GATE_UP / DG_MOE_DOWN */
+  const void* x;
+  const void* w;
+  const void* qinfo;
+  const void* lut;
+  void* y;
+  const int32_t* ids;
+  const float* gates;     /* DG_MOE_DOWN */
+  const void* residual;   /* DG_MOE_DOWN, optional */
+  const int32_t* group_ws;
+  float* f32_ws;          /* DG_MOE_DOWN */
+  int64_t stride_w;       /* bytes between experts */
+  int64_t stride_qinfo;
+  int64_t stride_lut;
+  int64_t m;
+  int64_t wrows;
+  int64_t k;
+  int64_t group_ws_bytes;
+  int64_t f32_ws_bytes;
+  int32_t E;
+  int32_t top_k;
+  int32_t group;
+  int32_t qtype;          /* TG_Q_INT4 / TG_Q_ANY4_GLOBAL / TG_Q_ANY4_ROWWISE */
+  int32_t dtype;          /* TG_BF16 / TG_F16 */
+  int32_t inner_k_tiles;  /* 4 */
+} dg_moe_grouped;
+
+TG_API int dg_moe_group(const int32_t* ids, int32_t* group_ws, int64_t group_ws_bytes, int64_t m, int64_t top_k, int64_t E, int64_t bm,
+                        int device, tg_stream_t stream);
+TG_API int dg_moe_grouped_launch(const dg_moe_grouped* call, int device, tg_stream_t stream);
+TG_API int dg_moe_grouped_plan(const dg_moe_grouped* call, int device, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -62,6 +62,11 @@ rotating; (b), (c) and (d) replay one captured graph and differ only in `adapter
 
     python tools/llama_decode_bench.py --moe [--layers N] [--out profiles/moe_bench.jsonl]
 
+    python tools/llama_decode_bench.py --moe --moe-prefill [--layers N] [--out profiles/moe_grouped_bench.jsonl]
+
+--moe --moe-prefill (one GPU): `prefill` of 64 / 128 / 512 tokens at bs 1 and of 128 at bs 8 at the Mixtral-8x7B shape (8 layers by default),
+the grouped path against the row blocks of 8 rows on the same stack, alternating, three runs each, median (min - max).
+
 --moe (one GPU): mixture of experts at the Mixtral-8x7B shape (8 experts, 2 per token), two JSON lines per batch size
 (1 and 8), appended to --out: the captured step on dg_moe_route / dg_moe_w4_launch against the formulation that is possible without them
 (every expert through the module GEMVs, a device-side mask: it captures too), alternating, three runs each; and dg_moe_w4_launch GATE_UP /
@@ -348,6 +353,52 @@ def moe_bench(a, cfg, device):
     return legs
 
 
+def moe_prefill_bench(a, cfg, device):
+    """--moe --moe-prefill: `prefill` of T tokens on a stack with experts, the grouped path (MoEMLP.grouped_from = 1: route, dg_moe_group,
+    dg_moe_grouped_launch twice) against the row-block path (grouped_from = None: dg_moe_w4_launch in blocks of 8 rows) on the SAME stack
+    and weights, alternating in one process, three runs each.  The row-block path's kernels are the ones this library had before the grouped
+    path existed, so in the same build it stands for the earlier library.  One JSON line per (T, bs) leg."""
+    from any4_amd.decode import Any4Factory, DecodeStack
+
+    base = {"config": a.config, "layers": cfg.layers, "experts": cfg.experts, "experts_per_token": cfg.experts_per_token, "hidden": cfg.hidden,
+            "inter": cfg.inter, "group_size": cfg.group_size, "kernel": a.kernel, "dtype": "bf16",
+            "data": "synthetic (random weights, random tokens)", "rounds": a.rounds}
+    stat = lambda v: {"median": sorted(v)[len(v) // 2], "min": min(v), "max": max(v), "series": v}
+    legs = []
+    stacks = {}
+    for T, bs in ((64, 1), (128, 1), (512, 1), (128, 8)):
+        if bs not in stacks:
+            stacks.clear()
+            stacks[bs] = DecodeStack(cfg, Any4Factory(cfg, device, torch.bfloat16, seed=1, kernel=a.kernel), device, torch.bfloat16, bs=bs)
+        st = stacks[bs]
+        toks = torch.randint(0, cfg.vocab, (bs, T), generator=torch.Generator().manual_seed(T)).to(device)
+
+        def run(grouped, reps):
+            for layer in st.layers:
+                layer.moe.grouped_from = 1 if grouped else None
+            st.prefill(toks, position=0)   # warm-up (and the grouped buffers of this row count)
+            torch.cuda.synchronize()
+            t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            t0.record()
+            for _ in range(reps):
+                st.prefill(toks, position=0)
+            t1.record()
+            torch.cuda.synchronize()
+            return round(t0.elapsed_time(t1) / reps, 4)
+
+        series = {"grouped": [], "row_blocks": []}
+        order = list(series)
+        for r in range(a.rounds):
+            for k in order[r % 2:] + order[: r % 2]:
+                series[k].append(run(k == "grouped", 5 if k == "grouped" else 2))
+        ms = {k: stat(v) for k, v in series.items()}
+        spread = max(ms[k]["max"] - ms[k]["min"] for k in ms)
+        legs.append(dict(base, leg="prefill: grouped tile GEMM / row blocks of 8 (dg_moe_w4_launch)", T=T, bs=bs, rows=T * bs, ms_per_prefill=ms,
+                         speedup_grouped=round(ms["row_blocks"]["median"] / ms["grouped"]["median"], 3),
+                         grouped_faster_by_more_than_the_larger_spread=bool(ms["row_blocks"]["median"] - ms["grouped"]["median"] > spread)))
+    return legs
+
+
 def ragged_bench(a, cfg, device):
     """The two legs of --ragged; returns the JSON-able results."""
     from any4_amd.decode import Any4Factory, DecodeStack
@@ -581,6 +632,9 @@ def main():
     ap.add_argument("--moe", action="store_true",
                     help="mixture of experts (DESIGN.md section 22): the Mixtral-8x7B shape (--layers N for fewer layers; --config tiny: a small "
                          "one) on the dg_moe kernels against all experts through the module GEMVs and a mask, and the two GEMV stages alone")
+    ap.add_argument("--moe-prefill", action="store_true",
+                    help="with --moe: prefill of 64 / 128 / 512 tokens at bs 1 and 128 at bs 8 (8 layers unless --layers), the grouped tile GEMM "
+                         "(MoEMLP.grouped_from) against the row blocks of 8, one line per leg appended to profiles/moe_grouped_bench.jsonl")
     ap.add_argument("--out", default=None, help="--ragged / --kv-cache / --paged: the file the JSON lines are appended to (default "
                                                 "profiles/ragged_bench.jsonl, with --kv-cache profiles/kv8_bench.jsonl, with --paged profiles/paged_bench.jsonl, with both profiles/paged_mx8_bench.jsonl)")
     a = ap.parse_args()
@@ -592,7 +646,9 @@ def main():
     a.rounds = a.rounds if a.rounds is not None else 3 if a.lora or a.moe else 5 if three_way else 7  # (--lora: three runs per leg)
     a.start_pos = a.start_pos if a.start_pos is not None else 512 if a.lora else 128
     if a.moe:
-        a.out = a.out or os.path.join(ROOT, "profiles", "moe_bench.jsonl")
+        a.out = a.out or os.path.join(ROOT, "profiles", "moe_grouped_bench.jsonl" if a.moe_prefill else "moe_bench.jsonl")
+        if a.moe_prefill and a.layers is None:
+            a.layers = 8
         a.config = "mixtral_8x7b" if a.config == "llama3_8b" else a.config
     if a.lora:
         a.out = a.out or os.path.join(ROOT, "profiles", "lora_bench.jsonl")
@@ -633,7 +689,7 @@ def main():
         if world > 1 or not cfg.experts:
             raise SystemExit("--moe runs on one GPU, with a configuration that has experts (mixtral_8x7b, tiny)")
         with open(a.out, "a") as f:
-            for leg in moe_bench(a, cfg, device):
+            for leg in (moe_prefill_bench if a.moe_prefill else moe_bench)(a, cfg, device):
                 line = json.dumps(leg)
                 print(line, flush=True)
                 f.write(line + "\n")
