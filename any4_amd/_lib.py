@@ -11,7 +11,7 @@ LIB_PATH = os.path.join(_HERE, "lib", "libtinygemm_hip.so")
 TG_BF16, TG_F16 = 0, 1
 TG_Q_INT4, TG_Q_ANY4_GLOBAL, TG_Q_ANY4_ROWWISE, TG_Q_MX4, TG_Q_INT8 = 0, 1, 2, 3, 4
 TG_NUM_FAST, TG_NUM_REFERENCE, TG_NUM_FAST_MFMA, TG_NUM_FAST_DOT2 = 0, 1, 2, 3
-TG_ABI_VERSION = 9
+TG_ABI_VERSION = 10
 TG_PLAN_SPLITK, TG_PLAN_STREAM, TG_PLAN_PAIR, TG_PLAN_PAIR_XR, TG_PLAN_GEMV, TG_PLAN_TILE = 1, 2, 3, 4, 5, 6
 TG_PLAN_PAIR_M1_LEAN = 7  # tg_gemm_w4_plan_detail only
 TG_LAYOUT_RM, TG_LAYOUT_TC_A = 0, 1
@@ -88,41 +88,28 @@ class Attn(ctypes.Structure):
             self.struct_bytes = ctypes.sizeof(Attn)
 
 
+# The mixture-of-experts call of include/decode_glue_hip.h: two kernels, two stages, one struct
 DG_MOE_GATE_UP, DG_MOE_DOWN = 0, 1
+DG_MOE_GEMV, DG_MOE_GROUPED = 0, 1
 
 
-class MoeW4(ctypes.Structure):
-    """struct dg_moe_w4 (include/decode_glue_hip.h)"""
-
-    _fields_ = [
-        ("struct_bytes", _u32), ("stage", _i32),
-        ("x", _vp), ("w", _vp), ("qinfo", _vp), ("lut", _vp), ("y", _vp), ("ids", _vp), ("gates", _vp), ("residual", _vp),
-        ("stride_w", _i64), ("stride_qinfo", _i64), ("stride_lut", _i64), ("m", _i64), ("wrows", _i64), ("k", _i64),
-        ("E", _i32), ("top_k", _i32), ("group", _i32), ("qtype", _i32), ("dtype", _i32), ("inner_k_tiles", _i32),
-    ]
-
-    def __init__(self, *args, **kw):
-        super().__init__(*args, **kw)
-        if "struct_bytes" not in kw:
-            self.struct_bytes = ctypes.sizeof(MoeW4)
-
-
-class MoeGrouped(ctypes.Structure):
-    """struct dg_moe_grouped (include/decode_glue_hip.h)"""
+class Moe(ctypes.Structure):
+    """struct dg_moe (include/decode_glue_hip.h)"""
 
     _fields_ = [
-        ("struct_bytes", _u32), ("stage", _i32),
+        ("struct_bytes", _u32), ("kernel", _i32),
         ("x", _vp), ("w", _vp), ("qinfo", _vp), ("lut", _vp), ("y", _vp), ("ids", _vp), ("gates", _vp), ("residual", _vp),
         ("group_ws", _vp), ("f32_ws", _vp),
         ("stride_w", _i64), ("stride_qinfo", _i64), ("stride_lut", _i64), ("m", _i64), ("wrows", _i64), ("k", _i64),
         ("group_ws_bytes", _i64), ("f32_ws_bytes", _i64),
-        ("E", _i32), ("top_k", _i32), ("group", _i32), ("qtype", _i32), ("dtype", _i32), ("inner_k_tiles", _i32),
+        ("stage", _i32), ("E", _i32), ("top_k", _i32), ("group", _i32), ("qtype", _i32), ("dtype", _i32), ("inner_k_tiles", _i32),
+        ("reserved", _u32),
     ]
 
     def __init__(self, *args, **kw):
         super().__init__(*args, **kw)
         if "struct_bytes" not in kw:
-            self.struct_bytes = ctypes.sizeof(MoeGrouped)
+            self.struct_bytes = ctypes.sizeof(Moe)
 
 
 # (kernel, flags) -> the name the call had as an entry point of its own up to ABI 8: DG_ATTN_FLAVOURS of the header, which is what
@@ -206,12 +193,10 @@ SYMBOLS = {
     "dg_lora_expand": [_vp] * 5 + [_i64] * 6 + [ctypes.c_int, ctypes.c_int, _vp],
     # mixture of experts: x, router_w, ids, gates, m, k, E, top_k, dtype, device, stream
     "dg_moe_route": [_vp] * 4 + [_i64] * 4 + [ctypes.c_int, ctypes.c_int, _vp],
-    "dg_moe_w4_launch": [ctypes.POINTER(MoeW4), ctypes.c_int, _vp],
-    "dg_moe_w4_plan": [ctypes.POINTER(MoeW4), ctypes.c_int, ctypes.POINTER(_i32)],
+    "dg_moe_launch": [ctypes.POINTER(Moe), ctypes.c_int, _vp],
+    "dg_moe_plan": [ctypes.POINTER(Moe), ctypes.c_int, ctypes.POINTER(_i64)],
     # mixture of experts, many rows: ids, group_ws, group_ws_bytes, m, top_k, E, bm, device, stream
     "dg_moe_group": [_vp, _vp] + [_i64] * 5 + [ctypes.c_int, _vp],
-    "dg_moe_grouped_launch": [ctypes.POINTER(MoeGrouped), ctypes.c_int, _vp],
-    "dg_moe_grouped_plan": [ctypes.POINTER(MoeGrouped), ctypes.c_int, ctypes.POINTER(_i64)],
     # the quantizer's k-means: x, w, w_row_stride, c0, assign, centers, sse, iters, rows, k, C, S, max_iter, tol, device, stream
     "tg_kmeans_rows": [_vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                        ctypes.c_int, _vp],

@@ -1,4 +1,4 @@
-// moe.cuh -- mixture-of-experts decode (dg_moe_route / dg_moe_w4, include/decode_glue_hip.h): the top-k router and the expert-indexed
+// moe.cuh -- mixture-of-experts decode (dg_moe_route / dg_moe_launch's DG_MOE_GEMV, include/decode_glue_hip.h): the top-k router and the expert-indexed
 // W4A16 GEMV.  Included inside tg_moe.hip's anonymous namespace.  The definition is any4_amd/moe.py: moe_ref.
 //
 //   moe_route_kernel   l[i][e] = sum_c router_w[e][c] x[i][c] (f32, not rounded), p = softmax(l[i]) over all E, the top_k largest p by

@@ -1,6 +1,7 @@
-// moe_grouped.cuh -- mixture-of-experts PREFILL (dg_moe_group / dg_moe_grouped_launch, include/decode_glue_hip.h): what the grouped
+// moe_grouped.cuh -- mixture-of-experts PREFILL (dg_moe_group / dg_moe_launch's DG_MOE_GROUPED, include/decode_glue_hip.h): what the grouped
 // flavour of w4_gemm_tile_kernel (w4_gemm_tile.cuh, template parameter GRP) needs around it.  Included inside tg_moe_tile.hip's anonymous
-// namespace.  The definition is any4_amd/moe.py: moe_grouped_ref; the group workspace's is group_ref.
+// namespace, behind moe_call.cuh (the group workspace's layout: MG_*).  The definition is any4_amd/moe.py: moe_grouped_ref; the group
+// workspace's is group_ref.
 //
 //   GroupedTileParams    the tile kernel's parameter block for GRP != 0: TileParams' fields under their names, the experts' strides, the
 //                        group workspace and where perm / invalid / tiles start in it.
@@ -31,19 +32,6 @@ struct GroupedTileParams {
   int64_t stride_w, stride_qinfo, stride_lut;
   int32_t top_k, perm_off, inv_off, tiles_off;   // offsets in int32 units
 };
-
-// ---- layout of the group workspace (int32 units) ----
-constexpr int MG_HDR = 0;        // n_tiles, n_invalid, n_valid, BM
-constexpr int MG_COUNT = 4;      // [64]
-constexpr int MG_OFFSET = 68;    // [65], padded to 68
-constexpr int MG_PERM = 136;     // [P]; then invalid [P]; then tiles [bound][3]
-constexpr int MG_THREADS = 256;
-constexpr int MG_MAX_PAIRS = 65536;
-constexpr int MG_BM = 128;       // the tile height of the grouped GEMM
-constexpr int MG_BN = 64;
-
-inline int64_t mg_bound(int64_t P, int64_t E, int64_t bm) { return (P + bm - 1) / bm + (E < P ? E : P); }
-inline int64_t mg_ints(int64_t P, int64_t E, int64_t bm) { return MG_PERM + 2 * P + 3 * mg_bound(P, E, bm); }
 
 struct MoeGroupParams {
   const int32_t* ids;  // [P]

@@ -18,14 +18,15 @@
 //   tg_prefill.hip     prefill_attn_kernel       (attn_prefill.cuh)        prompt prefill: rope + cache append + causal flash attention (DG_ATTN_PREFILL)
 //   tg_sample.hip      sample_kernel             (sample.cuh)              temperature / top-k / top-p sampling of the logits (dg_sample)
 //   tg_lora.hip        lora_shrink_kernel, lora_expand_kernel (lora.cuh)   per-sequence LoRA adapters on a linear's output (dg_lora_shrink / dg_lora_expand)
-//   tg_moe.hip         moe_route_kernel, moe_w4_kernel (moe.cuh)               mixture-of-experts decode: the top-k router and the expert-indexed 4-bit GEMV (dg_moe_route / dg_moe_w4_launch)
-//   tg_moe_tile.hip    w4_gemm_tile_kernel<GRP>, moe_group_kernel, moe_combine_kernel (w4_gemm_tile.cuh, moe_grouped.cuh)  mixture-of-experts prefill: pairs sorted by expert, grouped tile GEMM (dg_moe_group / dg_moe_grouped_launch)
+//   tg_moe.hip         moe_route_kernel, moe_w4_kernel (moe.cuh)               mixture-of-experts decode: the top-k router and the expert-indexed 4-bit GEMV (dg_moe_route / dg_moe_launch / dg_moe_plan: the one front of both MoE kernels)
+//   tg_moe_tile.hip    w4_gemm_tile_kernel<GRP>, moe_group_kernel, moe_combine_kernel (w4_gemm_tile.cuh, moe_grouped.cuh)  mixture-of-experts prefill: pairs sorted by expert, grouped tile GEMM (dg_moe_group / DG_MOE_GROUPED's launcher)
 //   tg_kmeans.hip      kmeans_rows_kernel        (kmeans.cuh)              the any4 quantizer's per-row weighted 1-D k-means (tg_kmeans_rows); compiled with -ffp-contract=off
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.
 // attn_call.cuh is the attention side's GemmParams: what the library does with one attention call of the decode stack (dg_attn, the public struct): the accepted
 // (kernel, flags) pairs, its validation for all five kinds of kernel (check_attn) and the split kernels' scratch layout (split_scratch); included by decode_glue.cuh and tg_prefill.hip.
+// moe_call.cuh is the same for one mixture-of-experts call (dg_moe, the public struct): its validation for both kernels (check_moe) and the group workspace's layout; included by tg_moe.hip and tg_moe_tile.hip.
 // Kernels and their helpers stay in each unit's anonymous namespace (one device code object per unit, no symbol shared between
 // them); only GemmParams and the tgx:: functions cross unit boundaries.
 #pragma once

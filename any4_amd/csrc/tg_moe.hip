@@ -1,12 +1,17 @@
-// tg_moe.hip -- dg_moe_route / dg_moe_w4_launch (include/decode_glue_hip.h): mixture-of-experts decode -- the top-k router and the 4-bit GEMV
-// whose weights are picked by expert ids on the device (moe.cuh); see tg_common.cuh
+// tg_moe.hip -- dg_moe_route / dg_moe_launch / dg_moe_plan (include/decode_glue_hip.h): mixture-of-experts decode -- the top-k router and
+// the 4-bit GEMV whose weights are picked by expert ids on the device (moe.cuh) --, and the one front of both MoE kernels: a call is
+// checked here (moe_call.cuh), DG_MOE_GROUPED then goes to its launcher in tg_moe_tile.hip; see tg_common.cuh
 #include "tg_common.cuh"
 #include "../../include/decode_glue_hip.h"
+
+// DG_MOE_GROUPED's launcher and planner, for a call that check_moe accepted: defined in tg_moe_tile.hip, where the tile kernel is compiled; not exported
+__attribute__((visibility("hidden"))) int moe_grouped_launch(const dg_moe& c, int device, tg_stream_t stream);
+__attribute__((visibility("hidden"))) void moe_grouped_plan(const dg_moe& c, int64_t* out);
+
 namespace {
 #include "w4_helpers.cuh"
 #include "moe.cuh"
-
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) == 0; }
+#include "moe_call.cuh"
 
 // The plan of one launch of up to 8 activation rows: workgroups, 16-row units per workgroup, pairs per sweep, LDS layout.
 // One workgroup per CU streams from the first cycle; more than MW_MAX_UPW units per workgroup are not planned (the DOWN accumulators).
@@ -31,28 +36,69 @@ int plan_moe(MoeW4Params& P, int cus) {
   return 0;
 }
 
-// everything of a call that needs no device; fills the sizes of P
-int check_moe(const dg_moe_w4* c, MoeW4Params& P) {
+// call == NULL, struct_bytes, then everything else of a call that needs no device
+int check_call(const dg_moe* c, bool plan) {
   if (!c) return TG_E_NULL;
-  if (c->struct_bytes != sizeof(dg_moe_w4)) return TG_E_STRUCT;
-  if (c->stage != DG_MOE_GATE_UP && c->stage != DG_MOE_DOWN) return TG_E_LAYOUT;
-  const bool any4 = c->qtype == TG_Q_ANY4_GLOBAL || c->qtype == TG_Q_ANY4_ROWWISE;
-  if (!c->x || !c->w || !c->qinfo || !c->y || !c->ids || (any4 && !c->lut) || (c->stage == DG_MOE_DOWN && !c->gates)) return TG_E_NULL;
-  if (c->dtype != TG_BF16 && c->dtype != TG_F16) return TG_E_DTYPE;
-  if (c->qtype != TG_Q_INT4 && !any4) return TG_E_QTYPE;
-  if (c->m < 1 || c->E < 1 || c->E > MOE_MAX_E || c->top_k < 1 || c->top_k > MOE_MAX_TOPK || c->top_k > c->E) return TG_E_SHAPE;
-  if (c->k < 64 || (c->k % 64) != 0 || c->wrows < 16 || (c->wrows % 16) != 0) return TG_E_SHAPE;
-  if (c->m * c->top_k > INT32_MAX / 2 || c->wrows > (1 << 24) || c->wrows * c->k / 2 > INT32_MAX) return TG_E_SIZE;
-  if (c->inner_k_tiles != 4) return TG_E_INNER_K;
-  if ((c->group != 64 && c->group != 128 && c->group != 256) || (c->k % c->group) != 0) return TG_E_GROUP;
-  if (!aligned16(c->x) || !aligned16(c->w) || !aligned16(c->qinfo) || !aligned16(c->lut) || !aligned16(c->y) || !aligned16(c->residual) ||
-      !aligned4(c->ids) || !aligned4(c->gates) || (c->stride_w % 16) != 0 || (c->stride_qinfo % 16) != 0 || (c->stride_lut % 16) != 0)
-    return TG_E_ALIGN;
-  P.w = (const char*)c->w; P.qinfo = (const char*)c->qinfo; P.lut = any4 ? (const char*)c->lut : nullptr;
-  P.stride_w = c->stride_w; P.stride_qinfo = c->stride_qinfo; P.stride_lut = c->stride_lut;
-  P.top_k = c->top_k; P.E = c->E; P.wrows = (int32_t)c->wrows; P.k = (int32_t)c->k; P.qtype = c->qtype;
-  P.sg_shift = group_shift(c->group) - 6;
-  P.stage = c->stage;
+  if (c->struct_bytes != sizeof(dg_moe)) return TG_E_STRUCT;
+  return check_moe(*c, plan);
+}
+
+// The GEMV's parameter block of an accepted call: everything but a row block's operands (x, y, ids, gates, residual) and plan; m is the first block's
+MoeW4Params gemv_params(const dg_moe& c) {
+  MoeW4Params P = {};
+  P.w = (const char*)c.w; P.qinfo = (const char*)c.qinfo;
+  P.lut = c.qtype == TG_Q_INT4 ? nullptr : (const char*)c.lut;
+  P.stride_w = c.stride_w; P.stride_qinfo = c.stride_qinfo; P.stride_lut = c.stride_lut;
+  P.top_k = c.top_k; P.E = c.E; P.wrows = (int32_t)c.wrows; P.k = (int32_t)c.k; P.qtype = c.qtype;
+  P.sg_shift = group_shift(c.group) - 6;
+  P.stage = c.stage;
+  P.m = (int32_t)(c.m < 8 ? c.m : 8);
+  return P;
+}
+
+int gemv_launch(const dg_moe& c, int device, tg_stream_t stream) {
+  MoeW4Params P = gemv_params(c);
+  int rc = plan_moe(P, 256);  // (the sizes alone decide whether a plan exists)
+  if (rc != 0) return rc;
+  DeviceScope ds(device);
+  if (!ds.ok) return TG_E_DEVICE;
+  const bool down = P.stage == DG_MOE_DOWN;
+  const int64_t xrow = down ? (int64_t)P.top_k * P.k * 2 : (int64_t)P.k * 2;                   // bytes of x per activation row
+  const int64_t yrow = down ? (int64_t)P.wrows * 2 : (int64_t)P.top_k * (P.wrows / 2) * 2;  // ... of y
+  for (int64_t r0 = 0; r0 < c.m; r0 += 8) {  // larger m: blocks of 8 rows on the caller's stream, as tg_gemm_w4's row blocks
+    P.m = (int32_t)(c.m - r0 < 8 ? c.m - r0 : 8);
+    rc = plan_moe(P, cu_count());
+    if (rc != 0) return rc;
+    P.x = (const char*)c.x + r0 * xrow;
+    P.y = (char*)c.y + r0 * yrow;
+    P.ids = c.ids + r0 * P.top_k;
+    P.gates = down ? c.gates + r0 * P.top_k : nullptr;
+    P.residual = down && c.residual ? (const char*)c.residual + r0 * P.wrows * 2 : nullptr;
+    const dim3 grid((unsigned)cdiv(P.units, P.upw));
+    const unsigned lds = (unsigned)P.lds_acc + (unsigned)(down ? P.m * P.upw * 16 * 4 : 0);
+    rc = pick_dt(c.dtype, [&](auto DT_) {
+      return launch_lds_kernel<moe_w4_kernel<decltype(DT_)>>(grid, dim3(MW_THREADS), lds, (hipStream_t)stream, P, false);
+    });
+    if (rc != 0) return rc;
+  }
+  return 0;
+}
+
+// the launch plan of the call's first row block; device < 0: planned for 256 compute units
+int gemv_plan(const dg_moe& c, int device, int64_t* out) {
+  MoeW4Params P = gemv_params(c);
+  int cus = 256;
+  if (device >= 0) {
+    DeviceScope ds(device);
+    if (!ds.ok) return TG_E_DEVICE;
+    cus = cu_count();
+  }
+  const int rc = plan_moe(P, cus);
+  if (rc != 0) return rc;
+  out[0] = cdiv(P.units, P.upw);   // workgroups
+  out[1] = P.upw;                  // 16-row units per workgroup (the last one may own fewer)
+  out[2] = P.np;                   // pairs per sweep
+  out[3] = cdiv(P.ksuper, P.spw);  // waves that own some k
   return 0;
 }
 
@@ -77,53 +123,22 @@ extern "C" int dg_moe_route(const void* x, const void* router_w, int32_t* ids, f
   });
 }
 
-extern "C" int dg_moe_w4_launch(const dg_moe_w4* call, int device, tg_stream_t stream) {
-  MoeW4Params P = {};
-  int rc = check_moe(call, P);
+extern "C" int dg_moe_launch(const dg_moe* call, int device, tg_stream_t stream) {
+  const int rc = check_call(call, false);
   if (rc != 0) return rc;
-  P.m = (int32_t)(call->m < 8 ? call->m : 8);
-  rc = plan_moe(P, 256);  // (the sizes alone decide whether a plan exists)
-  if (rc != 0) return rc;
-  DeviceScope ds(device);
-  if (!ds.ok) return TG_E_DEVICE;
-  const int64_t xrow = P.stage == DG_MOE_DOWN ? (int64_t)P.top_k * P.k * 2 : (int64_t)P.k * 2;           // bytes of x per activation row
-  const int64_t yrow = P.stage == DG_MOE_DOWN ? (int64_t)P.wrows * 2 : (int64_t)P.top_k * (P.wrows / 2) * 2;  // ... of y
-  for (int64_t r0 = 0; r0 < call->m; r0 += 8) {  // larger m: blocks of 8 rows on the caller's stream, as tg_gemm_w4's row blocks
-    P.m = (int32_t)(call->m - r0 < 8 ? call->m - r0 : 8);
-    rc = plan_moe(P, cu_count());
-    if (rc != 0) return rc;
-    P.x = (const char*)call->x + r0 * xrow;
-    P.y = (char*)call->y + r0 * yrow;
-    P.ids = call->ids + r0 * P.top_k;
-    P.gates = call->gates ? call->gates + r0 * P.top_k : nullptr;
-    P.residual = call->residual ? (const char*)call->residual + r0 * P.wrows * 2 : nullptr;
-    const dim3 grid((unsigned)cdiv(P.units, P.upw));
-    const unsigned lds = (unsigned)P.lds_acc + (unsigned)(P.stage == DG_MOE_DOWN ? P.m * P.upw * 16 * 4 : 0);
-    rc = pick_dt(call->dtype, [&](auto DT_) {
-      return launch_lds_kernel<moe_w4_kernel<decltype(DT_)>>(grid, dim3(MW_THREADS), lds, (hipStream_t)stream, P, false);
-    });
-    if (rc != 0) return rc;
-  }
-  return 0;
+  return call->kernel == DG_MOE_GROUPED ? moe_grouped_launch(*call, device, stream) : gemv_launch(*call, device, stream);
 }
 
-extern "C" int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out) {
+extern "C" int dg_moe_plan(const dg_moe* call, int device, int64_t* out) {
   if (!out) return TG_E_NULL;
-  MoeW4Params P = {};
-  int rc = check_moe(call, P);
+  const int rc = check_call(call, true);
   if (rc != 0) return rc;
-  P.m = (int32_t)(call->m < 8 ? call->m : 8);
-  int cus = 256;
-  if (device >= 0) {
+  for (int i = 0; i < 8; ++i) out[i] = 0;
+  if (call->kernel == DG_MOE_GEMV) return gemv_plan(*call, device, out);
+  if (device >= 0) {  // (the grouped plan does not depend on the device's compute units; a device is only checked)
     DeviceScope ds(device);
     if (!ds.ok) return TG_E_DEVICE;
-    cus = cu_count();
   }
-  rc = plan_moe(P, cus);
-  if (rc != 0) return rc;
-  out[0] = (int32_t)cdiv(P.units, P.upw);  // workgroups
-  out[1] = P.upw;                          // 16-row units per workgroup (the last one may own fewer)
-  out[2] = P.np;                           // pairs per sweep
-  out[3] = (int32_t)cdiv(P.ksuper, P.spw); // waves that own some k
+  moe_grouped_plan(*call, out);
   return 0;
 }

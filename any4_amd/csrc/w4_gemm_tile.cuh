@@ -38,7 +38,7 @@
 //              tile_split_sum_kernel (below) adds the splits in order, applies the bias and rounds once.  Why: a tile's k-steps are a chain
 //              of dependent LDS round trips, 0.6-0.9 us per 128 k whatever the tile holds -- a launch with 64 tiles takes as long as one with
 //              256 (tg_tile.hip chooses the splits; profiles/r06_tile_splitk.txt).
-//   grouped    template parameter GRP (mixture-of-experts prefill, dg_moe_grouped_launch; moe_grouped.cuh holds its parameter block PT, the
+//   grouped    template parameter GRP (mixture-of-experts prefill, dg_moe_launch's DG_MOE_GROUPED; moe_grouped.cuh holds its parameter block PT, the
 //              group kernel that writes the tile list and the combine): a workgroup's m tile is entry `tm` of a tile list on the device
 //              -- (expert, first position in perm, rows <= BM) --, its weight, qinfo and LUT bases are the expert's, activation row r is
 //              GATHERED (the DMA's per-lane source address: x[perm[first + r] / top_k] for GRP = 1, x[perm[first + r]] for GRP = 2) and
@@ -107,7 +107,7 @@ __device__ __forceinline__ void tile_barrier() {
 //       (m0, k0) (m1, k0) (m0, k0 + 1) (m1, k0 + 1), the second word at k0 + 8; m0 = t / 4, m1 = m0 + 8, k0 = 2q).  No tables: the
 //       dequantising waves compute w = RNE16(fma(byte - 128, scale, zero)) (Dequantization.cuh:262-330) in the vector ALU -- 2.75 operations
 //       per weight against one LDS lookup -- from scale / zero words they prefetch themselves; one quantisation group per step (g >= 64 KS).
-// GRP = 0: the dense GEMM; 1 / 2: the grouped gate_up / down GEMM of dg_moe_grouped_launch, PT = GroupedTileParams (moe_grouped.cuh)
+// GRP = 0: the dense GEMM; 1 / 2: the grouped gate_up / down GEMM of DG_MOE_GROUPED, PT = GroupedTileParams (moe_grouped.cuh)
 template <typename DT, int BM, int BN, int DX = 3, int NDW = 8, int KS = 1, int NCW = 4, bool QMX = false, int W8 = 0, int GRP = 0, typename PT = TileParams>
 __global__ void __launch_bounds__(64 * (NCW + 4 + NDW)) w4_gemm_tile_kernel(const PT p) {
   static_assert(GRP == 0 || (!QMX && W8 == 0 && BN == 64), "grouped flavour: 4-bit words, BN = 64 (two 16-row tiles per consumer wave)");

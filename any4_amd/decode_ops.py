@@ -426,95 +426,99 @@ def moe_route(x: torch.Tensor, router_w: torch.Tensor, top_k: int, ids: torch.Te
     return ids, gates
 
 
-def moe_call(stage: int, x, stack, ids, gates=None, residual=None, y=None, m=None) -> "_lib.MoeW4":
-    """struct dg_moe_w4 for one stage on an `any4_amd.moe.ExpertStack` (its tensors are contiguous: a stride is one expert's bytes)."""
-    ptr = lambda t: None if t is None else t.data_ptr()
-    per = lambda t: 0 if t is None else t[0].numel() * t.element_size()
-    return _lib.MoeW4(stage=stage, x=ptr(x), w=ptr(stack.words), qinfo=ptr(stack.qinfo), lut=ptr(stack.lut), y=ptr(y), ids=ptr(ids),
-                      gates=ptr(gates), residual=ptr(residual), stride_w=per(stack.words), stride_qinfo=per(stack.qinfo),
-                      stride_lut=per(stack.lut), m=ids.shape[0] if m is None else m, wrows=stack.n, k=stack.k, E=stack.E, top_k=ids.shape[1],
-                      group=stack.group, qtype=stack.qtype, dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16,
-                      inner_k_tiles=4)
+def _moe_struct(kernel: int, stage: int, stack, m: int, top_k: int, x=None, y=None, ids=None, gates=None, residual=None, group_ws=None,
+                f32_ws=None, plan: bool = False) -> "_lib.Moe":
+    """struct dg_moe for one stage on an `any4_amd.moe.ExpertStack` (its tensors are contiguous: a stride is one expert's bytes).  plan:
+    the planner's call -- `stack` need only name the sizes, the pointers are non-NULL, aligned dummies (the planner dereferences nothing)."""
+    if plan:
+        operands = dict(x=64, w=64, qinfo=64, lut=64, y=64, ids=64, gates=64, stride_w=16, stride_qinfo=16, stride_lut=16)
+    else:
+        ptr = lambda t: None if t is None else t.data_ptr()
+        per = lambda t: 0 if t is None else t.numel() // t.shape[0] * t.element_size()
+        nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()
+        operands = dict(x=ptr(x), w=ptr(stack.words), qinfo=ptr(stack.qinfo), lut=ptr(stack.lut), y=ptr(y), ids=ptr(ids), gates=ptr(gates),
+                        residual=ptr(residual), group_ws=ptr(group_ws), f32_ws=ptr(f32_ws), stride_w=per(stack.words),
+                        stride_qinfo=per(stack.qinfo), stride_lut=per(stack.lut), group_ws_bytes=nbytes(group_ws), f32_ws_bytes=nbytes(f32_ws))
+    return _lib.Moe(kernel=kernel, stage=stage, m=m, wrows=stack.n, k=stack.k, E=stack.E, top_k=top_k, group=stack.group, qtype=stack.qtype,
+                    dtype=_dt(stack), inner_k_tiles=4, **operands)
 
 
-def _moe_check(what, x, stack, ids, rows):
+def _moe_stage(what, kernel, stage, x, stack, ids, gates=None, residual=None, out=None, group_ws=None, f32_ws=None):
+    """One stage of either kernel: the tensor checks, the call, the launch.  what: the public wrapper's name, for its messages."""
+    down, grouped = stage == _lib.DG_MOE_DOWN, kernel == _lib.DG_MOE_GROUPED
+    m, top_k = ids.shape
+    rows, shape = (m * top_k, (m, stack.n)) if down else (m, (m * top_k, stack.n // 2))
     _gpu(x, stack.words, stack.qinfo, stack.lut, ids)
     if ids.dtype != torch.int32 or ids.dim() != 2:
         raise RuntimeError(f"{what}: ids must be int32 [m, top_k], got {ids.dtype} {tuple(ids.shape)}")
     if x.dim() != 2 or tuple(x.shape) != (rows, stack.k) or x.dtype != stack.dtype:
         raise RuntimeError(f"{what}: x must be [{rows}, {stack.k}] {stack.dtype}, got {tuple(x.shape)} {x.dtype}")
+    if grouped:
+        _gpu(group_ws)
+        if group_ws is None or group_ws.dtype != torch.int32:
+            raise RuntimeError(f"{what}: group_ws must be the int32 workspace moe_group filled")
+    if down:
+        _gpu(gates, residual, out, f32_ws)
+        if gates.dtype != torch.float32 or tuple(gates.shape) != (m, top_k):
+            raise RuntimeError(f"{what}: gates must be float32 [{m}, {top_k}]")
+        if residual is not None and (residual.dtype != x.dtype or tuple(residual.shape) != shape):
+            raise RuntimeError(f"{what}: residual must be [{m}, {stack.n}] {x.dtype}")
+    if out is None:
+        out = torch.empty(shape, dtype=x.dtype, device=x.device)
+    elif out.dtype != x.dtype or tuple(out.shape) != shape or not out.is_contiguous():
+        raise RuntimeError(f"{what}: out must be contiguous [{shape[0]}, {shape[1]}] {x.dtype}")
+    if grouped and down:
+        if f32_ws is None:
+            f32_ws = torch.empty((rows, stack.n), dtype=torch.float32, device=x.device)
+        elif f32_ws.dtype != torch.float32 or f32_ws.numel() < rows * stack.n:
+            raise RuntimeError(f"{what}: f32_ws must hold {rows} x {stack.n} float32")
+    call = _moe_struct(kernel, stage, stack, m, top_k, x, out, ids, gates, residual, group_ws, f32_ws)
+    _lib.check(_lib.load().dg_moe_launch(ctypes.byref(call), x.device.index, _stream(x)), "dg_moe_launch")
+    return out
+
+
+def _moe_plan(kernel, stage, stack, m, top_k, device, n):
+    out = (ctypes.c_int64 * 8)()
+    _lib.check(_lib.load().dg_moe_plan(ctypes.byref(_moe_struct(kernel, stage, stack, m, top_k, plan=True)), device, out), "dg_moe_plan")
+    return tuple(out)[:n]
 
 
 def moe_gate_up(x: torch.Tensor, stack, ids: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-    """act [m * top_k, il]: row i * top_k + s = SwiGLU of x[i] through the gate / up weights of expert ids[i, s] (DG_MOE_GATE_UP; `stack`
-    an ExpertStack [2 il, k] with rows in blocks of 8 gate + 8 up).  A pair whose id is outside [0, E) gets zeros."""
-    m, top_k = ids.shape
-    _moe_check("moe_gate_up", x, stack, ids, m)
-    if out is None:
-        out = torch.empty((m * top_k, stack.n // 2), dtype=x.dtype, device=x.device)
-    elif out.dtype != x.dtype or tuple(out.shape) != (m * top_k, stack.n // 2) or not out.is_contiguous():
-        raise RuntimeError(f"moe_gate_up: out must be contiguous [{m * top_k}, {stack.n // 2}] {x.dtype}")
-    call = moe_call(_lib.DG_MOE_GATE_UP, x, stack, ids, y=out)
-    _lib.check(_lib.load().dg_moe_w4_launch(ctypes.byref(call), x.device.index, _stream(x)), "dg_moe_w4_launch")
-    return out
+    """act [m * top_k, il]: row i * top_k + s = SwiGLU of x[i] through the gate / up weights of expert ids[i, s] (DG_MOE_GEMV,
+    DG_MOE_GATE_UP; `stack` an ExpertStack [2 il, k] with rows in blocks of 8 gate + 8 up).  A pair whose id is outside [0, E) gets zeros."""
+    return _moe_stage("moe_gate_up", _lib.DG_MOE_GEMV, _lib.DG_MOE_GATE_UP, x, stack, ids, out=out)
 
 
 def moe_down(act: torch.Tensor, stack, ids: torch.Tensor, gates: torch.Tensor, residual: torch.Tensor = None, out: torch.Tensor = None) -> torch.Tensor:
     """y [m, n] = RNE16(sum_s gates[i, s] * (act[i * top_k + s] through the down weights of expert ids[i, s]) (+ residual[i]))
-    (DG_MOE_DOWN).  out may be `residual` itself (the residual stream, updated in place: an element is read and written by one thread)."""
-    m, top_k = ids.shape
-    _moe_check("moe_down", act, stack, ids, m * top_k)
-    _gpu(gates, residual, out)
-    if gates.dtype != torch.float32 or tuple(gates.shape) != (m, top_k):
-        raise RuntimeError(f"moe_down: gates must be float32 [{m}, {top_k}]")
-    if residual is not None and (residual.dtype != act.dtype or tuple(residual.shape) != (m, stack.n)):
-        raise RuntimeError(f"moe_down: residual must be [{m}, {stack.n}] {act.dtype}")
-    if out is None:
-        out = torch.empty((m, stack.n), dtype=act.dtype, device=act.device)
-    elif out.dtype != act.dtype or tuple(out.shape) != (m, stack.n):
-        raise RuntimeError(f"moe_down: out must be [{m}, {stack.n}] {act.dtype}")
-    call = moe_call(_lib.DG_MOE_DOWN, act, stack, ids, gates, residual, out)
-    _lib.check(_lib.load().dg_moe_w4_launch(ctypes.byref(call), act.device.index, _stream(act)), "dg_moe_w4_launch")
-    return out
+    (DG_MOE_GEMV, DG_MOE_DOWN).  out may be `residual` itself (the residual stream, updated in place: an element is read and written by
+    one thread)."""
+    return _moe_stage("moe_down", _lib.DG_MOE_GEMV, _lib.DG_MOE_DOWN, act, stack, ids, gates, residual, out)
 
 
 def moe_plan(stage: int, stack, m: int, top_k: int, device: int = -1):
-    """(workgroups, 16-row units per workgroup, pairs per sweep, waves that own part of k) of a launch (dg_moe_w4_plan; nothing is
-    launched; device < 0: planned for 256 compute units, no GPU needed)."""
-    buf = ctypes.create_string_buffer(256)
-    p = (ctypes.addressof(buf) + 63) & ~63  # a non-NULL, aligned dummy: the planner dereferences nothing
-    call = _lib.MoeW4(stage=stage, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=m,
-                      wrows=stack.n, k=stack.k, E=stack.E, top_k=top_k, group=stack.group, qtype=stack.qtype,
-                      dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
-    out = (ctypes.c_int32 * 4)()
-    _lib.check(_lib.load().dg_moe_w4_plan(ctypes.byref(call), device, out), "dg_moe_w4_plan")
-    return tuple(out)
+    """(workgroups, 16-row units per workgroup, pairs per sweep, waves that own part of k) of a GEMV launch (dg_moe_plan, DG_MOE_GEMV;
+    nothing is launched; device < 0: planned for 256 compute units, no GPU needed)."""
+    return _moe_plan(_lib.DG_MOE_GEMV, stage, stack, m, top_k, device, 4)
 
 
 def moe_grouped_plan(stage: int, stack, m: int, top_k: int, device: int = -1):
     """(bm, bn, the grid's m-extent bound, n tiles, 64-k super-tiles per step, group workspace bytes, f32 workspace bytes) of a grouped launch
-    (dg_moe_grouped_plan; nothing is launched; device < 0: no GPU needed).  bm is the tile height dg_moe_group sorts for."""
-    buf = ctypes.create_string_buffer(256)
-    p = (ctypes.addressof(buf) + 63) & ~63  # a non-NULL, aligned dummy: the planner dereferences nothing
-    call = _lib.MoeGrouped(stage=stage, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=m,
-                           wrows=stack.n, k=stack.k, E=stack.E, top_k=top_k, group=stack.group, qtype=stack.qtype,
-                           dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
-    out = (ctypes.c_int64 * 7)()
-    _lib.check(_lib.load().dg_moe_grouped_plan(ctypes.byref(call), device, out), "dg_moe_grouped_plan")
-    return tuple(out)
+    (dg_moe_plan, DG_MOE_GROUPED; nothing is launched; device < 0: no GPU needed).  bm is the tile height dg_moe_group sorts for."""
+    return _moe_plan(_lib.DG_MOE_GROUPED, stage, stack, m, top_k, device, 7)
 
 
 def moe_group(ids: torch.Tensor, E: int, bm: int, out: torch.Tensor = None) -> torch.Tensor:
     """The group workspace (int32, include/decode_glue_hip.h: dg_moe_group; any4_amd/moe.py: group_ref is the definition) of ids int32
     [m, top_k]: the pairs sorted by expert and the tile list the grouped GEMMs walk.  bm: moe_grouped_plan()[0].  out: the buffer to fill."""
+    from .moe import group_ws_ints
+
     _gpu(ids, out)
     if ids.dtype != torch.int32 or ids.dim() != 2:
         raise RuntimeError(f"moe_group: ids must be int32 [m, top_k], got {ids.dtype} {tuple(ids.shape)}")
     m, top_k = ids.shape
-    P = m * top_k
-    need = 136 + 2 * P + 3 * (-(-P // bm) + min(E, P))
     if out is None:
-        out = torch.empty(need, dtype=torch.int32, device=ids.device)
+        out = torch.empty(group_ws_ints(m * top_k, E, bm), dtype=torch.int32, device=ids.device)
     elif out.dtype != torch.int32 or out.dim() != 1:
         raise RuntimeError("moe_group: out must be a flat int32 tensor")
     _lib.check(_lib.load().dg_moe_group(ids.data_ptr(), out.data_ptr(), out.numel() * 4, m, top_k, E, bm, ids.device.index, _stream(ids)),
@@ -522,62 +526,17 @@ def moe_group(ids: torch.Tensor, E: int, bm: int, out: torch.Tensor = None) -> t
     return out
 
 
-def moe_grouped_call(stage: int, x, stack, ids, group_ws, gates=None, residual=None, y=None, f32_ws=None) -> "_lib.MoeGrouped":
-    """struct dg_moe_grouped for one stage on an `any4_amd.moe.ExpertStack`."""
-    ptr = lambda t: None if t is None else t.data_ptr()
-    per = lambda t: 0 if t is None else t[0].numel() * t.element_size()
-    nbytes = lambda t: 0 if t is None else t.numel() * t.element_size()
-    return _lib.MoeGrouped(stage=stage, x=ptr(x), w=ptr(stack.words), qinfo=ptr(stack.qinfo), lut=ptr(stack.lut), y=ptr(y), ids=ptr(ids),
-                           gates=ptr(gates), residual=ptr(residual), group_ws=ptr(group_ws), f32_ws=ptr(f32_ws), stride_w=per(stack.words),
-                           stride_qinfo=per(stack.qinfo), stride_lut=per(stack.lut), m=ids.shape[0], wrows=stack.n, k=stack.k,
-                           group_ws_bytes=nbytes(group_ws), f32_ws_bytes=nbytes(f32_ws), E=stack.E, top_k=ids.shape[1], group=stack.group,
-                           qtype=stack.qtype, dtype=_lib.TG_BF16 if stack.dtype == torch.bfloat16 else _lib.TG_F16, inner_k_tiles=4)
-
-
-def _group_ws_check(what, group_ws):
-    _gpu(group_ws)
-    if group_ws is None or group_ws.dtype != torch.int32:
-        raise RuntimeError(f"{what}: group_ws must be the int32 workspace moe_group filled")
-
-
 def moe_gate_up_grouped(x: torch.Tensor, stack, ids: torch.Tensor, group_ws: torch.Tensor, out: torch.Tensor = None) -> torch.Tensor:
-    """moe_gate_up for many rows (dg_moe_grouped_launch, DG_MOE_GATE_UP): the tile GEMM over the pairs sorted by expert; its numerics are
+    """moe_gate_up for many rows (DG_MOE_GROUPED, DG_MOE_GATE_UP): the tile GEMM over the pairs sorted by expert; its numerics are
     any4_amd/moe.py: moe_grouped_ref's (16-bit weights).  group_ws: moe_group(ids, ...)."""
-    m, top_k = ids.shape
-    _moe_check("moe_gate_up_grouped", x, stack, ids, m)
-    _group_ws_check("moe_gate_up_grouped", group_ws)
-    if out is None:
-        out = torch.empty((m * top_k, stack.n // 2), dtype=x.dtype, device=x.device)
-    elif out.dtype != x.dtype or tuple(out.shape) != (m * top_k, stack.n // 2) or not out.is_contiguous():
-        raise RuntimeError(f"moe_gate_up_grouped: out must be contiguous [{m * top_k}, {stack.n // 2}] {x.dtype}")
-    call = moe_grouped_call(_lib.DG_MOE_GATE_UP, x, stack, ids, group_ws, y=out)
-    _lib.check(_lib.load().dg_moe_grouped_launch(ctypes.byref(call), x.device.index, _stream(x)), "dg_moe_grouped_launch")
-    return out
+    return _moe_stage("moe_gate_up_grouped", _lib.DG_MOE_GROUPED, _lib.DG_MOE_GATE_UP, x, stack, ids, out=out, group_ws=group_ws)
 
 
 def moe_down_grouped(act: torch.Tensor, stack, ids: torch.Tensor, gates: torch.Tensor, group_ws: torch.Tensor, residual: torch.Tensor = None,
                      out: torch.Tensor = None, f32_ws: torch.Tensor = None) -> torch.Tensor:
-    """moe_down for many rows (dg_moe_grouped_launch, DG_MOE_DOWN: the tile GEMM into f32_ws [m * top_k, n] float32, then the combine).
+    """moe_down for many rows (DG_MOE_GROUPED, DG_MOE_DOWN: the tile GEMM into f32_ws [m * top_k, n] float32, then the combine).
     out may be `residual` itself.  f32_ws: the workspace to use (it is not cleared and need not be)."""
-    m, top_k = ids.shape
-    _moe_check("moe_down_grouped", act, stack, ids, m * top_k)
-    _group_ws_check("moe_down_grouped", group_ws)
-    _gpu(gates, residual, out, f32_ws)
-    if gates.dtype != torch.float32 or tuple(gates.shape) != (m, top_k):
-        raise RuntimeError(f"moe_down_grouped: gates must be float32 [{m}, {top_k}]")
-    if residual is not None and (residual.dtype != act.dtype or tuple(residual.shape) != (m, stack.n)):
-        raise RuntimeError(f"moe_down_grouped: residual must be [{m}, {stack.n}] {act.dtype}")
-    if out is None:
-        out = torch.empty((m, stack.n), dtype=act.dtype, device=act.device)
-    elif out.dtype != act.dtype or tuple(out.shape) != (m, stack.n):
-        raise RuntimeError(f"moe_down_grouped: out must be [{m}, {stack.n}] {act.dtype}")
-    if f32_ws is None:
-        f32_ws = torch.empty((m * top_k, stack.n), dtype=torch.float32, device=act.device)
-    elif f32_ws.dtype != torch.float32 or f32_ws.numel() < m * top_k * stack.n:
-        raise RuntimeError(f"moe_down_grouped: f32_ws must hold {m * top_k} x {stack.n} float32")
-    call = moe_grouped_call(_lib.DG_MOE_DOWN, act, stack, ids, group_ws, gates, residual, out, f32_ws)
-    _lib.check(_lib.load().dg_moe_grouped_launch(ctypes.byref(call), act.device.index, _stream(act)), "dg_moe_grouped_launch")
-    return out
+    return _moe_stage("moe_down_grouped", _lib.DG_MOE_GROUPED, _lib.DG_MOE_DOWN, act, stack, ids, gates, residual, out, group_ws, f32_ws)
 
 
 def swiglu(gu: torch.Tensor) -> torch.Tensor:

@@ -1,7 +1,7 @@
 """Mixture of experts (MoE) for the decode stack: a top-k router and expert MLPs whose 4-bit weights are picked on the device.
 
 A sparse MLP block replaces a layer's one gate_up / down pair by E of them and a router [E, hidden]; every token runs `top_k` of the E
-(Mixtral-8x7B: 8 experts, 2 per token).  Three launches serve it (include/decode_glue_hip.h): dg_moe_route, then dg_moe_w4_launch twice
+(Mixtral-8x7B: 8 experts, 2 per token).  Three launches serve it (include/decode_glue_hip.h): dg_moe_route, then dg_moe_launch (DG_MOE_GEMV) twice
 (DG_MOE_GATE_UP, DG_MOE_DOWN); all three read their indices on the device, so a captured step follows the router from replay to replay.
 
   * `moe_ref` is the definition, plain torch in float64: what the kernels and the plain-torch formulation are tested against.
@@ -9,7 +9,7 @@ A sparse MLP block replaces a layer's one gate_up / down pair by E of them and a
     (gate_up in the 8 + 8 interleaved row order of `DecodeConfig.gate_up_interleave = 8`, and down).
   * `MoEMLP(router_w, weights, top_k)` is the block: `forward(x, residual)` runs the three launches, `forward(..., fused=False)` a
     plain-torch formulation that runs ALL experts and combines them with a mask (no value is read on the host either way).
-  * Many rows (a prompt): `MoEMLP(..., grouped_from=R)` runs calls of R rows or more as route, dg_moe_group, dg_moe_grouped_launch twice: the
+  * Many rows (a prompt): `MoEMLP(..., grouped_from=R)` runs calls of R rows or more as route, dg_moe_group, dg_moe_launch (DG_MOE_GROUPED) twice: the
     pairs sorted by expert (`group_ref` is the definition of that workspace) and a tile GEMM that reads a selected expert once per 128 of
     its rows.  A tile GEMM dequantises into LDS, so its weights are the 16-bit ones, w = RNE16(fma(lut[code], scale, zero)), as in the dense
     stack's prefill: `moe_grouped_ref` (= moe_ref(..., weights="rounded")) is the definition of that path, everything else as below.
@@ -175,12 +175,22 @@ def moe_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: 
 
 
 def moe_grouped_ref(x, router_w, experts: MoEWeights, top_k: int, residual=None, parts: bool = False):
-    """The definition of the GROUPED path (MoEMLP(grouped_from=...), dg_moe_grouped_launch), float64: moe_ref over the 16-bit weights
+    """The definition of the GROUPED path (MoEMLP(grouped_from=...), dg_moe_launch's DG_MOE_GROUPED), float64: moe_ref over the 16-bit weights
     w = RNE16(fma(lut[code], scale, zero)) -- what a tile GEMM holds in LDS --, with moe_ref's rounding points for SwiGLU and the combine."""
     return moe_ref(x, router_w, experts, top_k, residual, parts, weights="rounded")
 
 
 GROUP_PERM = 136  # int32 units in front of perm in the group workspace: n_tiles, n_invalid, n_valid, bm; count[64]; offset[68]
+
+
+def group_bound(P: int, E: int, BM: int) -> int:
+    """The m-extent of the grouped GEMM's grid: no list of tiles of P pairs over E experts is longer."""
+    return -(-P // BM) + min(E, P)
+
+
+def group_ws_ints(P: int, E: int, BM: int) -> int:
+    """int32 units of dg_moe_group's workspace: the header, perm [P], invalid [P], tiles [bound][3]."""
+    return GROUP_PERM + 2 * P + 3 * group_bound(P, E, BM)
 
 
 def group_ref(ids, E: int, BM: int):
@@ -203,7 +213,7 @@ def group_ref(ids, E: int, BM: int):
     bad = pairs[~ok]
     count = np.bincount(a[valid], minlength=E)[:E].astype(np.int32) if valid.size else np.zeros(E, np.int32)
     offset = np.concatenate([[0], np.cumsum(count)]).astype(np.int32)
-    bound = -(-P // BM) + min(E, P)
+    bound = group_bound(P, E, BM)
     tiles = np.zeros((bound, 3), np.int32)
     n = 0
     for e in range(E):
@@ -214,7 +224,7 @@ def group_ref(ids, E: int, BM: int):
     perm[:order.size] = order
     invalid = np.full(P, -1, np.int32)
     invalid[:bad.size] = bad
-    ws = np.zeros(GROUP_PERM + 2 * P + 3 * bound, np.int32)
+    ws = np.zeros(group_ws_ints(P, E, BM), np.int32)
     ws[:4] = (n, bad.size, order.size, BM)
     ws[4:4 + E] = count
     ws[68:68 + E + 1] = offset

@@ -1,8 +1,11 @@
 """What the C ABI answers over a grid of calls, as a digest (developer tool; needs no GPU: the planner and all validation run before any HIP call):
     python dev/plan_sweep.py [--lib PATH/libtinygemm_hip.so] [--quick]     the planner: workspace bytes and kernel family of every case
-    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...] [--abi8]  return codes of N broken structs per GEMM entry point, then of
-                                                                           N // 25 broken calls of dg_decode_attn and of each of the
-                                                                           nineteen accepted calls of dg_attn_launch
+    python dev/plan_sweep.py --errors [N] [--seed S] [--lib ...] [--abi8 | --abi9]
+                                                                           return codes of N broken structs per GEMM entry point, then of
+                                                                           N // 25 broken calls of dg_decode_attn, of each of the
+                                                                           nineteen accepted calls of dg_attn_launch, of each (kernel,
+                                                                           stage) of dg_moe_launch, of dg_moe_plan, dg_moe_route and
+                                                                           dg_moe_group
 Prints the number of cases, a histogram of the answers and a sha256 over their sequence.  Two builds route / validate alike when they
 print the same digest for the same script; run it before and after a change of the host launch path (or with --lib on an older build).
 No digest is recorded anywhere: a performance change may move the routing on purpose.
@@ -26,6 +29,7 @@ ap.add_argument("--quick", action="store_true", help="a 1/96 sub-grid of the pla
 ap.add_argument("--errors", nargs="?", type=int, const=100000, default=0, metavar="N")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--abi8", action="store_true", help="--errors: --lib is a build up to ABI 8; make the attention calls through its positional entry points")
+ap.add_argument("--abi9", action="store_true", help="--errors: --lib is a build of ABI 9; make the mixture-of-experts calls through its dg_moe_w4_* / dg_moe_grouped_* entry points")
 opt = ap.parse_args()
 lib = ctypes.CDLL(opt.lib)
 P = ctypes.POINTER(L.W4Gemm)
@@ -234,8 +238,150 @@ def attn_errors(n):
         report(entry, out)
 
 
+# ---- the mixture-of-experts calls: start from a valid call, break none, one or two fields ----
+# The fields in the order of ABI 9's two structs (dg_moe_w4; dg_moe_grouped = that plus the workspaces), which is the order the sweep
+# draws in, so that --abi9 makes the same cases through that build's two structs.
+_MOE_PTRS = ("x", "w", "qinfo", "lut", "y", "ids", "gates", "residual")
+_MOE_I64 = ("stride_w", "stride_qinfo", "stride_lut", "m", "wrows", "k")
+_MOE_I32 = ("E", "top_k", "group", "qtype", "dtype", "inner_k_tiles")
+
+
+def _abi9_struct(grouped):
+    ptrs, i64 = (_MOE_PTRS + ("group_ws", "f32_ws"), _MOE_I64 + ("group_ws_bytes", "f32_ws_bytes")) if grouped else (_MOE_PTRS, _MOE_I64)
+
+    class Abi9Moe(ctypes.Structure):
+        _fields_ = ([("struct_bytes", ctypes.c_uint32), ("stage", ctypes.c_int32)] + [(f, ctypes.c_void_p) for f in ptrs] +
+                    [(f, ctypes.c_int64) for f in i64] + [(f, ctypes.c_int32) for f in _MOE_I32])
+    return Abi9Moe
+
+
+_STRIDE16 = (0, 16, 8, 24, 32)
+MOE_BREAKS = {
+    "m": (0, -1, 1, 8, 9, 19, 32768, 32769, 65536, 65537, 1 << 30, 1 << 31), "wrows": (0, 16, 24, 64, 4096, 1 << 24, (1 << 24) + 16),
+    "k": (0, 64, 96, 128, 192, 4096, 65536, 1 << 20), "E": (0, 1, 2, 4, 64, 65), "top_k": (0, 1, 2, 3, 8, 9),
+    "group": (0, 32, 64, 128, 256, 512, 96), "qtype": (-1, 0, 1, 2, 3, 4, 5), "dtype": (-1, 0, 1, 2), "inner_k_tiles": (0, 2, 4, 8),
+    "stride_w": _STRIDE16, "stride_qinfo": _STRIDE16, "stride_lut": _STRIDE16,
+    "struct_bytes": (None, -8, 0, 8),            # nothing, or relative to the size of the struct the build has
+    "group_ws_bytes": (0, -1, -4, 4096), "f32_ws_bytes": (0, -1, -4, 4096),   # relative to what the (broken) sizes need
+}
+
+
+def moe_fields(grouped, stage):
+    """The fields of a (kernel, stage) call in ABI 9's order, and those of them the call has: GATE_UP has neither gates nor a residual,
+    and its grouped flavour no f32 workspace (ABI 9 checked the alignment of such a pointer all the same; ABI 10 does not read it)."""
+    ptrs, i64 = (_MOE_PTRS + ("group_ws", "f32_ws"), _MOE_I64 + ("group_ws_bytes", "f32_ws_bytes")) if grouped else (_MOE_PTRS, _MOE_I64)
+    order = ("struct_bytes",) + ptrs + i64 + _MOE_I32
+    absent = () if stage == L.DG_MOE_DOWN else ("gates", "residual", "f32_ws", "f32_ws_bytes")
+    return order, [f for f in order if f not in absent]
+
+
+def moe_draw(rng, grouped, stage, plan):
+    """One call's fields by name; a broken pointer is NULL or 2, 4 or 8 bytes off"""
+    order, has = moe_fields(grouped, stage)
+    v = dict(m=2, wrows=64, k=128, E=4, top_k=2, group=64, qtype=2, dtype=0, inner_k_tiles=4, stride_w=16, stride_qinfo=16, stride_lut=16)
+    v.update((name, (i + 1) * BASE) for i, name in enumerate(f for f in order if f not in v and not f.endswith("_bytes")))
+    slack = dict(group_ws_bytes=0, f32_ws_bytes=0)
+    struct_bytes = 0
+    for f in rng.sample(has, rng.choice((0, 1, 2))):
+        if f == "struct_bytes":
+            struct_bytes = rng.choice(MOE_BREAKS[f])
+        elif f in slack:
+            slack[f] = rng.choice(MOE_BREAKS[f])
+        else:
+            v[f] = rng.choice(MOE_BREAKS[f]) if f in MOE_BREAKS else rng.choice((None, v[f] + 2, v[f] + 4, v[f] + 8, v[f]))
+    if grouped:
+        clamp = lambda b: max(-(1 << 62), min(1 << 62, b))
+        pairs = v["m"] * v["top_k"]
+        v["group_ws_bytes"] = clamp(4 * (136 + 2 * pairs + 3 * (-(-pairs // 128) + min(v["E"], pairs))) + slack["group_ws_bytes"])
+        v["f32_ws_bytes"] = clamp(4 * pairs * v["wrows"] + slack["f32_ws_bytes"])
+    if stage != L.DG_MOE_DOWN:
+        v["gates"] = v["residual"] = None
+        if grouped:
+            v["f32_ws"], v["f32_ws_bytes"] = None, 0
+    if plan and grouped:
+        v["group_ws"] = v["f32_ws"] = None   # (the planner looks at neither)
+    return v, struct_bytes
+
+
+def moe_struct(grouped, stage, v, struct_bytes):
+    cls = _abi9_struct(grouped) if opt.abi9 else L.Moe
+    kw = dict(v, stage=stage) if opt.abi9 else dict(v, stage=stage, kernel=L.DG_MOE_GROUPED if grouped else L.DG_MOE_GEMV)
+    return cls(struct_bytes=0 if struct_bytes is None else ctypes.sizeof(cls) + struct_bytes, **kw)
+
+
+def moe_errors(n):
+    """dg_moe_launch per (kernel, stage), dg_moe_plan over all four, dg_moe_route, dg_moe_group.  --abi9: the same cases through
+    dg_moe_w4_launch / dg_moe_grouped_launch and their planners of a build of ABI 9 (--lib)."""
+    def entry(grouped, what):
+        name = (("dg_moe_grouped_" if grouped else "dg_moe_w4_") if opt.abi9 else "dg_moe_") + what
+        fn = getattr(lib, name)
+        fn.argtypes = None   # (the struct's class differs from case to case under --abi9: passed by reference)
+        return fn
+
+    e = 0
+    for grouped in (False, True):
+        for stage in (L.DG_MOE_GATE_UP, L.DG_MOE_DOWN):
+            rng = random.Random(1000 * opt.seed + 200 + e)
+            e += 1
+            out = array("q")
+            fn = entry(grouped, "launch")
+            for _ in range(n):
+                call = moe_struct(grouped, stage, *moe_draw(rng, grouped, stage, False))
+                rc = fn(ctypes.byref(call), ctypes.c_int(NO_DEVICE), ctypes.c_void_p(None))
+                if rc >= 0:
+                    sys.exit(f"dg_moe_launch: answer {rc}: a call of this sweep got past DeviceScope")
+                out.append(rc)
+            report(f"dg_moe_launch {'DG_MOE_GROUPED' if grouped else 'DG_MOE_GEMV'} {'DG_MOE_DOWN' if stage else 'DG_MOE_GATE_UP'}", out)
+    # the planner: the code, and behind a 0 the plan (four values of the GEMV, seven of the grouped kernel)
+    rng = random.Random(1000 * opt.seed + 210)
+    out = array("q")
+    for _ in range(n):
+        grouped, stage = rng.choice((False, True)), rng.choice((L.DG_MOE_GATE_UP, L.DG_MOE_DOWN))
+        call = moe_struct(grouped, stage, *moe_draw(rng, grouped, stage, True))
+        plan = ((ctypes.c_int64 * 7) if grouped else (ctypes.c_int32 * 4))() if opt.abi9 else (ctypes.c_int64 * 8)()
+        rc = entry(grouped, "plan")(ctypes.byref(call), ctypes.c_int(-1), plan)
+        out.append(rc)
+        if rc == 0:
+            out.extend(plan[:7 if grouped else 4])
+            if any(plan[7 if grouped else 4:]):
+                sys.exit(f"dg_moe_plan: {list(plan)}: not zero behind the plan")
+    report("dg_moe_plan", out)
+    # the two positional entry points, alike in both ABIs
+    i64, vp = ctypes.c_int64, ctypes.c_void_p
+    lib.dg_moe_route.argtypes = [vp] * 4 + [i64] * 4 + [ctypes.c_int, ctypes.c_int, vp]
+    lib.dg_moe_group.argtypes = [vp, vp] + [i64] * 5 + [ctypes.c_int, vp]
+    ptr = lambda rng, p: rng.choice((None, p + 2, p + 4, p + 8, p))
+    route = dict(m=(0, -1, 1, 19, 1 << 31, (1 << 31) - 1), k=(0, 4, 8, 64, 68, 4096, 1 << 20, (1 << 20) + 8), E=MOE_BREAKS["E"], top_k=MOE_BREAKS["top_k"],
+                 dtype=MOE_BREAKS["dtype"])
+    rng = random.Random(1000 * opt.seed + 211)
+    out = array("q")
+    for _ in range(n):
+        v = dict(x=BASE, router_w=2 * BASE, ids=3 * BASE, gates=4 * BASE, m=2, k=128, E=4, top_k=2, dtype=0)
+        for f in rng.sample(list(v), rng.choice((0, 1, 2))):
+            v[f] = rng.choice(route[f]) if f in route else ptr(rng, v[f])
+        out.append(lib.dg_moe_route(*v.values(), NO_DEVICE, None))
+    report("dg_moe_route", out)
+    rng = random.Random(1000 * opt.seed + 212)
+    out = array("q")
+    for _ in range(n):
+        v = dict(ids=BASE, group_ws=2 * BASE, group_ws_bytes=0, m=2, top_k=2, E=4, bm=128)
+        slack = 0
+        for f in rng.sample(list(v), rng.choice((0, 1, 2))):
+            if f == "group_ws_bytes":
+                slack = rng.choice(MOE_BREAKS[f])
+            else:
+                v[f] = rng.choice(MOE_BREAKS[f]) if f in MOE_BREAKS else rng.choice((0, 64, 127, 128, 256)) if f == "bm" else ptr(rng, v[f])
+        pairs, bm = v["m"] * v["top_k"], max(1, v["bm"])
+        v["group_ws_bytes"] = 4 * (136 + 2 * pairs + 3 * (-(-pairs // bm) + min(v["E"], pairs))) + slack
+        out.append(lib.dg_moe_group(*v.values(), NO_DEVICE, None))
+    report("dg_moe_group", out)
+    if min(out) >= 0:
+        sys.exit("dg_moe_group: a call of this sweep got past DeviceScope")
+
+
 if opt.errors:
     errors(opt.errors)
     attn_errors(max(1, opt.errors // 25))
+    moe_errors(max(1, opt.errors // 25))
 else:
     planner()

@@ -303,7 +303,8 @@ TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, con
 
 /* ---- mixture of experts (MoE) for a decode step: a top-k router and a 4-bit GEMV whose weights are picked by expert ids on the device ----
  * The definition is any4_amd/moe.py: moe_ref.  Three launches serve one sparse MLP block: route, gate_up, down; all three read their
- * indices on the device, so a captured graph follows the router from replay to replay.  New symbols within ABI 9: probe for them.
+ * indices on the device, so a captured graph follows the router from replay to replay.  ONE call struct serves this path and the many-row path below
+ * (struct dg_moe, dg_moe_launch, dg_moe_plan: ABI 10); the caller names the kernel, nothing is inferred from NULL pointers.
  *
  * dg_moe_route   x [m][k] 16-bit (already normed), router_w [E][k] 16-bit.  l[i][e] = sum_c router_w[e][c] x[i][c] in f32, NOT rounded to
  *   16 bit; p = softmax(l[i]) over all E in f32; the top_k largest p ordered by (p descending, expert index ascending: a tie goes to the
@@ -312,7 +313,7 @@ TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, con
  *   every id written is in [0, E) and a row's ids are distinct.  Sums run in a fixed order: the same inputs give the same bits.
  *   TG_E_NULL, TG_E_DTYPE, TG_E_SHAPE, TG_E_K_DIV, TG_E_SIZE (k > 2^20), TG_E_ALIGN (x, router_w off 16 bytes; ids, gates off 4).
  *
- * dg_moe_w4_launch   one layer's experts are STACKED: expert e of an operand sits at base + e * stride (bytes, a multiple of 16):
+ * dg_moe_launch, kernel DG_MOE_GEMV   one layer's experts are STACKED: expert e of an operand sits at base + e * stride (bytes, a multiple of 16):
  *     w      Bint4 words [E][wrows / 8][k / 64][32][2] int32 (tg_convert_to_Bint4 at innerKTiles 4, per expert)
  *     qinfo  scales_and_zeros [E][k / group][wrows][2] 16-bit
  *     lut    [E][wrows][16] (TG_Q_ANY4_ROWWISE) or [E][16] (TG_Q_ANY4_GLOBAL) 16-bit; not read for TG_Q_INT4
@@ -329,56 +330,67 @@ TG_API int dg_lora_expand(const float* t, const void* B, const float* scale, con
  *                          id contributes nothing; a row without a valid pair gets RNE16(residual), or zeros.
  *   int4 and any4, inner_k_tiles 4, group 64 / 128 / 256, k % 64 == 0, wrows % 16 == 0.  m <= 8 is one launch; larger m is issued as
  *   ceil(m / 8) launches on the caller's stream (every block of 8 rows re-reads its experts: for many rows -- a prompt -- there is
- *   dg_moe_grouped_launch below, which reads a selected expert once per 128 of its rows).
+ *   kernel DG_MOE_GROUPED below, which reads a selected expert once per 128 of its rows).
  *   Within a launch a selected expert's rows cross the memory interface once per workgroup range as long as at most `pairs per sweep`
- *   (dg_moe_w4_plan: 8; fewer from k of about 4800 on, because the sweep's activation rows are staged in LDS) pairs chose it; an unselected
+ *   (dg_moe_plan: 8; fewer from k of about 4800 on, because the sweep's activation rows are staged in LDS) pairs chose it; an unselected
  *   expert's bytes are never requested.  No atomics, no scratch, no allocation, no synchronisation.
- *   In this order: call == NULL TG_E_NULL; struct_bytes TG_E_STRUCT; stage TG_E_LAYOUT; a required pointer (x, w, qinfo, y, ids; lut for
+ *   In this order: call == NULL TG_E_NULL; struct_bytes TG_E_STRUCT; kernel or stage TG_E_LAYOUT; a required pointer (x, w, qinfo, y, ids; lut for
  *   any4; gates for DOWN) TG_E_NULL; TG_E_DTYPE; TG_E_QTYPE (mx4, int8); TG_E_SHAPE (m < 1, E outside 1 ... 64, top_k outside
  *   1 ... min(E, 8), k % 64, wrows % 16); TG_E_SIZE (an expert beyond 2^31 bytes, k beyond what LDS stages); TG_E_INNER_K; TG_E_GROUP;
  *   TG_E_ALIGN (an operand off 16 bytes, ids or gates off 4, a stride that is no multiple of 16).  Nothing is launched in these cases.
- * dg_moe_w4_plan   the launch plan of the call's first row block, for tests and tools: out[0] workgroups, out[1] 16-row units per
- *   workgroup, out[2] pairs per sweep, out[3] waves that own part of k.  device < 0: planned for 256 compute units, without a device. */
+ *   group_ws, f32_ws and their sizes are not read.
+ * dg_moe_plan, kernel DG_MOE_GEMV   the launch plan of the call's first row block, for tests and tools: out[0] workgroups, out[1] 16-row
+ *   units per workgroup, out[2] pairs per sweep, out[3] waves that own part of k, out[4 ... 7] 0.  device < 0: planned for 256 compute
+ *   units, without a device.  out == NULL: TG_E_NULL. */
 #define DG_MOE_GATE_UP 0
 #define DG_MOE_DOWN 1
+#define DG_MOE_GEMV 0     /* dg_moe::kernel: the expert-indexed GEMV, a decode step's few rows */
+#define DG_MOE_GROUPED 1  /* the grouped tile GEMM over the pairs dg_moe_group sorted, a prompt's many rows (below) */
 
-/* One call.  C: `struct dg_moe_w4 c = {sizeof c};`.  Pointers and 64-bit fields stand in front of the 32-bit ones: no hidden padding. */
-typedef struct dg_moe_w4 {
-  uint32_t struct_bytes;  /* sizeof(struct dg_moe_w4); anything else is TG_E_STRUCT */
-  int32_t stage;          /* DG_MOE_GATE_UP / DG_MOE_DOWN */
+/* One call.  C: `struct dg_moe c = {sizeof c};`.  Pointers and 64-bit fields stand in front of the 32-bit ones: no hidden padding.  A field
+ * that the call's kernel and stage do not use is not read. */
+typedef struct dg_moe {
+  uint32_t struct_bytes;    /* sizeof(struct dg_moe); anything else is TG_E_STRUCT */
+  int32_t kernel;           /* DG_MOE_GEMV / DG_MOE_GROUPED */
   const void* x;
   const void* w;
   const void* qinfo;
   const void* lut;
   void* y;
   const int32_t* ids;
-  const float* gates;     /* DG_MOE_DOWN */
-  const void* residual;   /* DG_MOE_DOWN, optional */
-  int64_t stride_w;       /* bytes between experts */
+  const float* gates;       /* DG_MOE_DOWN */
+  const void* residual;     /* DG_MOE_DOWN, optional */
+  const int32_t* group_ws;  /* DG_MOE_GROUPED */
+  float* f32_ws;            /* DG_MOE_GROUPED, DG_MOE_DOWN */
+  int64_t stride_w;         /* bytes between experts */
   int64_t stride_qinfo;
   int64_t stride_lut;
   int64_t m;
   int64_t wrows;
   int64_t k;
+  int64_t group_ws_bytes;   /* DG_MOE_GROUPED */
+  int64_t f32_ws_bytes;     /* DG_MOE_GROUPED, DG_MOE_DOWN */
+  int32_t stage;            /* DG_MOE_GATE_UP / DG_MOE_DOWN */
   int32_t E;
   int32_t top_k;
   int32_t group;
-  int32_t qtype;          /* TG_Q_INT4 / TG_Q_ANY4_GLOBAL / TG_Q_ANY4_ROWWISE */
-  int32_t dtype;          /* TG_BF16 / TG_F16 */
-  int32_t inner_k_tiles;  /* 4 */
-} dg_moe_w4;
+  int32_t qtype;            /* TG_Q_INT4 / TG_Q_ANY4_GLOBAL / TG_Q_ANY4_ROWWISE */
+  int32_t dtype;            /* TG_BF16 / TG_F16 */
+  int32_t inner_k_tiles;    /* 4 */
+  uint32_t reserved;        /* padding to 8 bytes; not read */
+} dg_moe;
 
 TG_API int dg_moe_route(const void* x, const void* router_w, int32_t* ids, float* gates, int64_t m, int64_t k, int64_t E, int64_t top_k,
                         int dtype, int device, tg_stream_t stream);
-TG_API int dg_moe_w4_launch(const dg_moe_w4* call, int device, tg_stream_t stream);
-TG_API int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out);
+TG_API int dg_moe_launch(const dg_moe* call, int device, tg_stream_t stream);
+TG_API int dg_moe_plan(const dg_moe* call, int device, int64_t* out /* [8] */);
 
 /* ---- mixture of experts for MANY rows (a prompt): the pairs sorted by expert, then a grouped 4-bit tile GEMM ----
  * The definition is any4_amd/moe.py: moe_grouped_ref (the group workspace's: group_ref).  Four launches serve one sparse MLP block: dg_moe_route
- * (above), dg_moe_group, dg_moe_grouped_launch twice (DG_MOE_GATE_UP; DG_MOE_DOWN, which issues the combine behind its GEMM).  Nothing is
- * read on the host: the grid is sized by a bound, so a captured graph follows the router.  New symbols within ABI 9: probe for them.
+ * (above), dg_moe_group, dg_moe_launch with kernel DG_MOE_GROUPED twice (DG_MOE_GATE_UP; DG_MOE_DOWN, which issues the combine behind its
+ * GEMM).  Nothing is read on the host: the grid is sized by a bound, so a captured graph follows the router.
  *
- * NUMERICS are the tile GEMM's (tg_gemm_w4 at many rows), NOT dg_moe_w4's: a weight is w = RNE16(fma(f32(lut[row][code]), f32(scale),
+ * NUMERICS are the tile GEMM's (tg_gemm_w4 at many rows), NOT DG_MOE_GEMV's: a weight is w = RNE16(fma(f32(lut[row][code]), f32(scale),
  *   f32(zero))) (int4: lut = code - 8), products are summed in f32 (v_mfma_f32_16x16x32), k ascending in 64-k super-tiles, never split: the
  *   bits of a row's sums do not depend on m, on the tile the row landed in or on the other rows.
  *
@@ -392,11 +404,12 @@ TG_API int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out);
  *     then          invalid[P] the pairs whose id is outside [0, E), ascending; -1 from n_invalid on.  Such an id is never turned into an address.
  *     then          tiles[bound][3]  (expert, first position in perm, rows <= bm): an expert with c pairs has ceil(c / bm) tiles, experts
  *                              ascending; zeros from n_tiles on.  bound = ceil(P / bm) + min(E, P) >= n_tiles is the m-extent of the GEMM's grid.
- *   group_ws_bytes >= 4 * (136 + 2 P + 3 bound).  bm: the GEMM's tile height (dg_moe_grouped_plan out[0]).
+ *   group_ws_bytes >= 4 * (136 + 2 P + 3 bound).  bm: the GEMM's tile height (dg_moe_plan out[0]).
  *   TG_E_NULL; TG_E_SHAPE (m < 1, E outside 1 ... 64, top_k outside 1 ... min(E, 8), bm not the GEMM's); TG_E_SIZE (P > 65536, workspace too
  *   small); TG_E_ALIGN (ids, group_ws off 4 bytes).  Nothing is launched in these cases.
  *
- * dg_moe_grouped_launch   operands as dg_moe_w4 (stacked experts: base + e * stride); group_ws as dg_moe_group left it for the same ids.
+ * dg_moe_launch, kernel DG_MOE_GROUPED   the one struct, operands as DG_MOE_GEMV's (stacked experts: base + e * stride); group_ws as
+ *   dg_moe_group left it for the same ids.
  *   An LDS-tiled MFMA GEMM, one workgroup per (tile of the list, n tile); a workgroup whose tile index is >= n_tiles exits before it touches
  *   memory; rows beyond a tile's `rows` are not stored.  Activation rows are gathered, results scattered to the pair's own row:
  *   stage DG_MOE_GATE_UP   x [m][k]; y [P][wrows / 2], row p = RNE16(RNE16(silu(RNE16(gate))) RNE16(up)) of expert ids[p]; rows of the pairs in
@@ -404,47 +417,17 @@ TG_API int dg_moe_w4_plan(const dg_moe_w4* call, int device, int32_t* out);
  *   stage DG_MOE_DOWN      x [P][k]; the GEMM stores the unrounded f32 sums d [P][wrows] to f32_ws (f32_ws_bytes >= 4 P wrows, 16-byte
  *                          aligned, not cleared: the row of an invalid pair is never read), then the combine: y[i] = RNE16(sum_s gates[i][s]
  *                          d[i top_k + s] (+ residual[i])), fused multiply-adds from 0 in the order (expert id ascending, then slot
- *                          ascending), the residual last -- DG_MOE_DOWN's order in dg_moe_w4.  y may be residual.
+ *                          ascending), the residual last -- DG_MOE_DOWN's order under DG_MOE_GEMV.  y may be residual.
  *   int4 and any4, inner_k_tiles 4, group 64 / 128 / 256, k % 64 == 0, wrows % 16 == 0, any m >= 1 with P <= 65536.  No atomics, no scratch,
  *   no allocation, no synchronisation.
- *   Refusals in dg_moe_w4's order with its codes; the workspaces join them: group_ws (f32_ws for DOWN) NULL with the required pointers
- *   (TG_E_NULL), P > 65536 or a workspace too small with TG_E_SIZE, group_ws off 4 / f32_ws off 16 bytes with TG_E_ALIGN.
- * dg_moe_grouped_plan   nothing launched, the workspaces are not looked at; out[0] bm (pairs per tile), out[1] weight rows per tile, out[2] the
+ *   Refusals in DG_MOE_GEMV's order with its codes (no k that LDS cannot stage); the workspaces join them: group_ws (f32_ws for DOWN) NULL with the required pointers
+ *   (TG_E_NULL), P > 65536 or a workspace too small with TG_E_SIZE, group_ws off 4 / f32_ws off 16 bytes with TG_E_ALIGN.  GATE_UP does not
+ *   read f32_ws or its size.
+ * dg_moe_plan, kernel DG_MOE_GROUPED   nothing launched, the workspaces are not looked at; out[0] bm (pairs per tile), out[1] weight rows per tile, out[2] the
  *   grid's m-extent (bound), out[3] n tiles, out[4] 64-k super-tiles per step (2 when k % 128 == 0), out[5] bytes of the group workspace,
- *   out[6] bytes of the f32 workspace (0 for GATE_UP).  device < 0: without a device. */
-typedef struct dg_moe_grouped {
-  uint32_t struct_bytes;  /* sizeof(struct dg_moe_grouped); anything else is TG_E_STRUCT */
-  int32_t stage;          /* DG_MOE_GATE_UP / DG_MOE_DOWN */
-  const void* x;
-  const void* w;
-  const void* qinfo;
-  const void* lut;
-  void* y;
-  const int32_t* ids;
-  const float* gates;     /* DG_MOE_DOWN */
-  const void* residual;   /* DG_MOE_DOWN, optional */
-  const int32_t* group_ws;
-  float* f32_ws;          /* DG_MOE_DOWN */
-  int64_t stride_w;       /* bytes between experts */
-  int64_t stride_qinfo;
-  int64_t stride_lut;
-  int64_t m;
-  int64_t wrows;
-  int64_t k;
-  int64_t group_ws_bytes;
-  int64_t f32_ws_bytes;
-  int32_t E;
-  int32_t top_k;
-  int32_t group;
-  int32_t qtype;          /* TG_Q_INT4 / TG_Q_ANY4_GLOBAL / TG_Q_ANY4_ROWWISE */
-  int32_t dtype;          /* TG_BF16 / TG_F16 */
-  int32_t inner_k_tiles;  /* 4 */
-} dg_moe_grouped;
-
+ *   out[6] bytes of the f32 workspace (0 for GATE_UP), out[7] 0.  device < 0: without a device. */
 TG_API int dg_moe_group(const int32_t* ids, int32_t* group_ws, int64_t group_ws_bytes, int64_t m, int64_t top_k, int64_t E, int64_t bm,
                         int device, tg_stream_t stream);
-TG_API int dg_moe_grouped_launch(const dg_moe_grouped* call, int device, tg_stream_t stream);
-TG_API int dg_moe_grouped_plan(const dg_moe_grouped* call, int device, int64_t* out);
 
 #ifdef __cplusplus
 }

@@ -39,7 +39,7 @@
 extern "C" {
 #endif
 
-#define TG_ABI_VERSION 9
+#define TG_ABI_VERSION 10
 
 #if defined(__GNUC__)
 #define TG_API __attribute__((visibility("default")))

@@ -1,4 +1,4 @@
-"""Float64 references, crafted inputs and bounds for the GROUPED mixture-of-experts path (dg_moe_group, dg_moe_grouped_launch; any4_amd/moe.py:
+"""Float64 references, crafted inputs and bounds for the GROUPED mixture-of-experts path (dg_moe_group, dg_moe_launch with DG_MOE_GROUPED; any4_amd/moe.py:
 moe_grouped_ref and group_ref are the definitions).  A plain helper module (not a conftest), in the style of tests/moe_ref.py, from which it
 takes stacks, inputs and the router's references; tests/test_moe_grouped_cpu.py checks it on the CPU, tests/test_gpu_moe_grouped.py runs the
 kernels against it.

@@ -1,4 +1,4 @@
-"""Float64 references, input builders and bounds for the mixture-of-experts kernels (dg_moe_route, dg_moe_w4_launch; any4_amd/moe.py:
+"""Float64 references, input builders and bounds for the mixture-of-experts kernels (dg_moe_route, dg_moe_launch with DG_MOE_GEMV; any4_amd/moe.py:
 moe_ref is the definition).  A plain helper module (not a conftest), in the style of tests/lora_ref.py and tests/fused_ref.py;
 tests/test_moe_cpu.py checks it on the CPU, tests/test_gpu_moe.py runs the kernels against it.
 

@@ -24,7 +24,7 @@ def test_dx_symbols_exported_declared_and_abi_unchanged():
         assert hasattr(ctypes.CDLL(_lib.LIB_PATH), sym), f"{sym} not exported"
         assert sym in _lib.SYMBOLS
     assert _lib.load().tg_gemm_w4_dx_workspace_bytes.restype is ctypes.c_int64
-    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 9
+    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 10
 
 
 def _args(**kw):

@@ -1,4 +1,4 @@
-"""Mixture-of-experts kernels on the GPU (dg_moe_route, dg_moe_w4_launch) against the float64 references and bounds of tests/moe_ref.py,
+"""Mixture-of-experts kernels on the GPU (dg_moe_route, dg_moe_launch with DG_MOE_GEMV) against the float64 references and bounds of tests/moe_ref.py,
 exact lookup probes, graph replay, and the decode stack with experts against its plain-torch path.  Run: pytest -m gpu."""
 import numpy as np
 import pytest

@@ -1,4 +1,4 @@
-"""The grouped mixture-of-experts path on the GPU (dg_moe_group, dg_moe_grouped_launch) against group_ref in every int and the float64
+"""The grouped mixture-of-experts path on the GPU (dg_moe_group, dg_moe_launch with DG_MOE_GROUPED) against group_ref in every int and the float64
 references and bounds of tests/moe_grouped_ref.py; exact probes, row independence, determinism, the block and the decode stack with
 moe_grouped_from.  Tile sizes come from the plan, never from a literal.  Run: pytest -m gpu."""
 import functools

@@ -169,8 +169,8 @@ def test_symbols_declared_exported_bound():
     lib = ctypes.CDLL(_lib.LIB_PATH)
     for s in ("tg_kmeans_rows", "tg_kmeans_rows_plan"):
         assert re.search(r"TG_API\s+int\s+" + s + r"\s*\(", hdr) and hasattr(lib, s) and s in _lib.SYMBOLS
-    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 9
-    assert re.search(r"#define\s+TG_ABI_VERSION\s+9\b", hdr)
+    assert _lib.load().tg_abi_version() == _lib.TG_ABI_VERSION == 10
+    assert re.search(r"#define\s+TG_ABI_VERSION\s+10\b", hdr)
 
 
 def plan(rows, k, C, S, max_iter=300, tol=1e-6, weighted=1):

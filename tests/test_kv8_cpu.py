@@ -249,7 +249,7 @@ def test_mx8_flavours_refuse_null_tensors_before_any_launch():
     from any4_amd import _lib
     from tests import attn_abi
 
-    assert _lib.TG_ABI_VERSION == 9 and re.search(r"#define\s+TG_ABI_VERSION\s+9\b", open(os.path.join(ROOT, "include", "tinygemm_hip.h")).read())
+    assert _lib.TG_ABI_VERSION == 10 and re.search(r"#define\s+TG_ABI_VERSION\s+10\b", open(os.path.join(ROOT, "include", "tinygemm_hip.h")).read())
     lib = _lib.load()
     buf = (ctypes.c_int32 * 64)()
     p = ctypes.addressof(buf) + (-ctypes.addressof(buf)) % 16

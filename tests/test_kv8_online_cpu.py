@@ -21,7 +21,7 @@ def test_the_flavours_are_the_split_kind_held_to_the_one_barrier_kernel():
     from tests import attn_abi
 
     L = _lib.load()
-    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 9
+    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 10
     held = _lib.DG_ATTN_MX8 | _lib.DG_ATTN_ONE_BARRIER
     assert [attn_abi.PAIR[name] for name in NAMES] == [(_lib.DG_ATTN_SPLIT, held), (_lib.DG_ATTN_SPLIT, held | _lib.DG_ATTN_SEQ)]
     assert callable(decode_ops.rope_attn_online_mx8)

@@ -1,5 +1,5 @@
 """Mixture of experts without a GPU: the definition (any4_amd/moe.py: moe_ref) against an independent per-token loop, ties, gates, the C
-ABI (symbols, struct mirror, every refusal before a launch), the configuration and the plain-torch layer.  Run: pytest -m "not gpu"."""
+ABI (symbols, the one struct's mirror, every refusal of the GEMV kernel before a launch, the fields a call does not read), the configuration and the plain-torch layer.  Run: pytest -m "not gpu"."""
 import ctypes
 import os
 import re
@@ -87,27 +87,34 @@ def test_symbols_are_declared_exported_and_bound():
 
     hdr = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
     lib = _lib.load()
-    for name in ("dg_moe_route", "dg_moe_w4_launch", "dg_moe_w4_plan"):
+    for name in ("dg_moe_route", "dg_moe_launch", "dg_moe_plan"):
         assert re.search(r"TG_API\s+int\s+" + name + r"\s*\(", hdr), name
         assert name in _lib.SYMBOLS and getattr(lib, name).argtypes == _lib.SYMBOLS[name]
-    assert lib.tg_abi_version() == _lib.TG_ABI_VERSION == 9
-    assert (_lib.DG_MOE_GATE_UP, _lib.DG_MOE_DOWN) == tuple(int(re.search(rf"#define {n} (\d+)", hdr).group(1)) for n in ("DG_MOE_GATE_UP", "DG_MOE_DOWN"))
+    for name in ("dg_moe_w4_launch", "dg_moe_w4_plan", "dg_moe_grouped_launch", "dg_moe_grouped_plan"):   # ABI 9's four: removed, not kept as shims
+        assert name not in hdr and name not in _lib.SYMBOLS and not hasattr(lib, name), name
+    assert lib.tg_abi_version() == _lib.TG_ABI_VERSION == 10
+    names = ("DG_MOE_GATE_UP", "DG_MOE_DOWN", "DG_MOE_GEMV", "DG_MOE_GROUPED")
+    assert tuple(getattr(_lib, n) for n in names) == tuple(int(re.search(rf"#define {n} (\d+)", hdr).group(1)) for n in names) == (0, 1, 0, 1)
 
 
 def test_struct_mirror_is_the_headers():
+    """The one struct of both kernels, field for field."""
     from any4_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
-    body = re.search(r"typedef struct dg_moe_w4 \{(.*?)\} dg_moe_w4;", hdr, re.S).group(1)
+    assert len(re.findall(r"typedef struct dg_moe\w*", hdr)) == 1 and not hasattr(_lib, "MoeW4") and not hasattr(_lib, "MoeGrouped")
+    body = re.search(r"typedef struct dg_moe \{(.*?)\} dg_moe;", hdr, re.S).group(1)
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = []
     for decl in filter(None, (d.strip() for d in body.split(";"))):
         ctype, name = re.match(r"(.*?)(\w+)$", decl).groups()
         ctype = ctype.replace("const", "").strip()
         fields.append((name, ctypes.c_void_p if ctype.endswith("*") else {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}[ctype]))
-    assert [(n, t) for n, t in _lib.MoeW4._fields_] == fields
-    assert ctypes.sizeof(_lib.MoeW4) == sum(ctypes.sizeof(t) for _, t in fields) == 144      # no hidden padding
-    assert fields[0][0] == "struct_bytes" and _lib.MoeW4().struct_bytes == 144
+    assert [(n, t) for n, t in _lib.Moe._fields_] == fields
+    assert ctypes.sizeof(_lib.Moe) == sum(ctypes.sizeof(t) for _, t in fields) == 184      # no hidden padding
+    assert [f[0] for f in fields[:2]] == ["struct_bytes", "kernel"] and _lib.Moe().struct_bytes == 184
+    sizes = [ctypes.sizeof(t) for _, t in fields[2:]]
+    assert sizes == sorted(sizes, reverse=True)                      # pointers and 64-bit fields in front of the 32-bit ones
 
 
 def _call(**over):
@@ -115,10 +122,10 @@ def _call(**over):
 
     buf = ctypes.create_string_buffer(512)
     p = (ctypes.addressof(buf) + 63) & ~63
-    kw = dict(stage=_lib.DG_MOE_DOWN, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, residual=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=2,
+    kw = dict(kernel=_lib.DG_MOE_GEMV, stage=_lib.DG_MOE_DOWN, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, residual=p, stride_w=16, stride_qinfo=16, stride_lut=16, m=2,
               wrows=64, k=128, E=4, top_k=2, group=64, qtype=2, dtype=_lib.TG_BF16, inner_k_tiles=4)
     kw.update({k: (p + v[1] if isinstance(v, tuple) else v) for k, v in over.items()})
-    c = _lib.MoeW4(**kw)
+    c = _lib.Moe(**kw)
     c._keep = buf
     return c
 
@@ -129,11 +136,17 @@ def test_every_refusal_comes_before_a_launch():
 
     L = _lib.load()
     E = dict(null=-1, inner=-2, kdiv=-3, group=-4, dtype=-5, qtype=-6, shape=-7, align=-8, size=-10, layout=-12, struct=-14)
-    launch = lambda c: L.dg_moe_w4_launch(ctypes.byref(c), 0, None)
-    assert L.dg_moe_w4_launch(None, 0, None) == E["null"]
-    assert launch(_call(struct_bytes=136)) == E["struct"]
+    launch = lambda c: L.dg_moe_launch(ctypes.byref(c), 0, None)
+    assert L.dg_moe_launch(None, 0, None) == E["null"]
+    for n in (136, 144, 176):                                               # ABI 9's two structs among them
+        assert launch(_call(struct_bytes=n)) == E["struct"], n
     assert launch(_call(struct_bytes=152, x=None)) == E["struct"]          # struct before the pointers
+    assert launch(_call(struct_bytes=152, kernel=2)) == E["struct"]        # ... and before the kernel
     assert launch(_call(stage=2)) == E["layout"]
+    for kern in (2, -1):
+        assert launch(_call(kernel=kern)) == E["layout"], kern
+        assert launch(_call(kernel=kern, x=None)) == E["layout"], kern      # the kernel before the pointers
+    assert launch(_call(stage=2, x=None)) == E["layout"]
     for f in ("x", "w", "qinfo", "lut", "y", "ids", "gates"):
         assert launch(_call(**{f: None})) == E["null"], f
     assert launch(_call(lut=None, qtype=0, dtype=7)) == E["dtype"]          # int4 needs no LUT; null before dtype
@@ -159,9 +172,11 @@ def test_every_refusal_comes_before_a_launch():
     for f in ("stride_w", "stride_qinfo", "stride_lut"):
         assert launch(_call(**{f: 24})) == E["align"], f
     assert launch(_call(k=65536, wrows=16)) == E["size"]                    # one activation row no longer fits the staging
-    out = (ctypes.c_int32 * 4)()
-    assert L.dg_moe_w4_plan(ctypes.byref(_call(group=32)), -1, out) == E["group"]
-    assert L.dg_moe_w4_plan(ctypes.byref(_call()), -1, None) == E["null"]
+    out = (ctypes.c_int64 * 8)()
+    assert L.dg_moe_plan(ctypes.byref(_call(group=32)), -1, out) == E["group"]
+    assert L.dg_moe_plan(ctypes.byref(_call()), -1, None) == E["null"]
+    assert L.dg_moe_plan(ctypes.byref(_call(kernel=2)), -1, out) == E["layout"]
+    assert L.dg_moe_plan(ctypes.byref(_call(k=65536, wrows=16)), -1, out) == E["size"]
     # the router
     buf = ctypes.create_string_buffer(256)
     p = (ctypes.addressof(buf) + 63) & ~63
@@ -173,6 +188,36 @@ def test_every_refusal_comes_before_a_launch():
         assert route(**kw) == E["shape"], kw
     assert route(k=68) == E["kdiv"]
     assert route(x=p + 8) == E["align"] and route(w=p + 8) == E["align"] and route(i=p + 2) == E["align"] and route(g=p + 2) == E["align"]
+
+
+def test_fields_the_call_does_not_use_are_not_read():
+    """A GEMV call answers what it answers without workspaces whatever group_ws / f32_ws and their sizes hold, and a grouped GATE_UP call
+    whatever f32_ws holds.  Every call ends in an error code: the group that no kernel has, or a device index that no machine has."""
+    from any4_amd import _lib
+
+    L = _lib.load()
+    no_device = 1 << 20
+    garbage = [dict(group_ws=None, f32_ws=None), dict(group_ws=("off", 2), f32_ws=("off", 2)), dict(group_ws=("off", 8), f32_ws=("off", 8)),
+               dict(group_ws_bytes=-1, f32_ws_bytes=-1), dict(group_ws=("off", 2), f32_ws=None, group_ws_bytes=-1, f32_ws_bytes=-1)]
+    for stage in (_lib.DG_MOE_GATE_UP, _lib.DG_MOE_DOWN):
+        for ws in [{}] + garbage:
+            assert L.dg_moe_launch(ctypes.byref(_call(stage=stage, group=32, **ws)), 0, None) == -4, (stage, ws)       # TG_E_GROUP
+            assert L.dg_moe_launch(ctypes.byref(_call(stage=stage, **ws)), no_device, None) == -9, (stage, ws)         # TG_E_DEVICE
+    grouped = dict(kernel=_lib.DG_MOE_GROUPED, stage=_lib.DG_MOE_GATE_UP, group_ws=("off", 0), group_ws_bytes=1 << 20)
+    for ws in (dict(f32_ws=None), dict(f32_ws=("off", 2)), dict(f32_ws=("off", 8)), dict(f32_ws_bytes=-1), dict(f32_ws=("off", 2), f32_ws_bytes=-1)):
+        assert L.dg_moe_launch(ctypes.byref(_call(**grouped, group=32, **ws)), 0, None) == -4, ws
+        assert L.dg_moe_launch(ctypes.byref(_call(**grouped, **ws)), no_device, None) == -9, ws
+    assert L.dg_moe_launch(ctypes.byref(_call(**{**grouped, "group_ws": ("off", 2)})), no_device, None) == -8          # (its own workspace is read)
+    # GATE_UP has neither gates nor a residual
+    for kern in ({}, grouped):
+        for f in ("gates", "residual"):
+            assert L.dg_moe_launch(ctypes.byref(_call(**{"stage": _lib.DG_MOE_GATE_UP, **kern, f: ("off", 2)})), no_device, None) == -9, (kern, f)
+    # the planner fills eight int64: four for the GEMV, seven for the grouped kernel, zeros behind them
+    out = (ctypes.c_int64 * 8)(*[-1] * 8)
+    assert L.dg_moe_plan(ctypes.byref(_call()), -1, out) == 0 and all(v > 0 for v in out[:4]) and list(out[4:]) == [0] * 4
+    out = (ctypes.c_int64 * 8)(*[-1] * 8)
+    assert L.dg_moe_plan(ctypes.byref(_call(kernel=_lib.DG_MOE_GROUPED, group_ws=None, f32_ws=None)), -1, out) == 0
+    assert all(v > 0 for v in out[:7]) and out[7] == 0
 
 
 def test_planner_regimes():

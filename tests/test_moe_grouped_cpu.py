@@ -1,5 +1,5 @@
 """The grouped mixture-of-experts path without a GPU: group_ref's properties, moe_grouped_ref against an independent per-token loop, the
-helper's references (tests/moe_grouped_ref.py) against it, the plan, the C ABI (symbols, struct mirror, every refusal before a launch) and the
+helper's references (tests/moe_grouped_ref.py) against it, the plan, the C ABI (symbols, every refusal of the grouped kernel before a launch) and the
 defaults that keep the module on its GEMV launches.  Run: pytest -m "not gpu"."""
 import ctypes
 import os
@@ -190,27 +190,16 @@ def test_plan_for_the_mixtral_shape():
     assert GR.plan(GR.GU, 384, 512, 1, 1, E=8)[2] == 1 + 1            # min(E, P) = 1
 
 
-def test_symbols_and_struct_mirror():
+def test_symbols_are_declared_exported_and_bound():
+    """(the struct's mirror: tests/test_moe_cpu.py -- both kernels share struct dg_moe)"""
     from any4_amd import _lib
 
     hdr = open(os.path.join(ROOT, "include", "decode_glue_hip.h")).read()
     lib = _lib.load()
-    for name in ("dg_moe_group", "dg_moe_grouped_launch", "dg_moe_grouped_plan"):
+    for name in ("dg_moe_group", "dg_moe_launch", "dg_moe_plan"):
         assert re.search(r"TG_API\s+int\s+" + name + r"\s*\(", hdr), name
         assert name in _lib.SYMBOLS and getattr(lib, name).argtypes == _lib.SYMBOLS[name]
-    assert lib.tg_abi_version() == _lib.TG_ABI_VERSION == 9
-    body = re.search(r"typedef struct dg_moe_grouped \{(.*?)\} dg_moe_grouped;", hdr, re.S).group(1)
-    body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
-    fields = []
-    for decl in filter(None, (d.strip() for d in body.split(";"))):
-        ctype, name = re.match(r"(.*?)(\w+)$", decl).groups()
-        ctype = ctype.replace("const", "").strip()
-        fields.append((name, ctypes.c_void_p if ctype.endswith("*") else {"uint32_t": ctypes.c_uint32, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64}[ctype]))
-    assert [(n, t) for n, t in _lib.MoeGrouped._fields_] == fields
-    assert ctypes.sizeof(_lib.MoeGrouped) == sum(ctypes.sizeof(t) for _, t in fields) == 176      # no hidden padding
-    assert fields[0][0] == "struct_bytes" and _lib.MoeGrouped().struct_bytes == 176
-    sizes = [ctypes.sizeof(t) for _, t in fields[2:]]
-    assert sizes == sorted(sizes, reverse=True)                      # pointers and 64-bit fields in front of the 32-bit ones
+    assert lib.tg_abi_version() == _lib.TG_ABI_VERSION == 10
 
 
 def _gws(P, E):
@@ -223,26 +212,27 @@ def _call(**over):
 
     buf = ctypes.create_string_buffer(512)
     p = (ctypes.addressof(buf) + 63) & ~63
-    kw = dict(stage=_lib.DG_MOE_DOWN, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, residual=p, group_ws=p, f32_ws=p, stride_w=16,
+    kw = dict(kernel=_lib.DG_MOE_GROUPED, stage=_lib.DG_MOE_DOWN, x=p, w=p, qinfo=p, lut=p, y=p, ids=p, gates=p, residual=p, group_ws=p, f32_ws=p, stride_w=16,
               stride_qinfo=16, stride_lut=16, m=2, wrows=64, k=128, group_ws_bytes=_gws(4, 4), f32_ws_bytes=4 * 4 * 64, E=4, top_k=2,
               group=64, qtype=2, dtype=_lib.TG_BF16, inner_k_tiles=4)
     kw.update({k: (p + v[1] if isinstance(v, tuple) else v) for k, v in over.items()})
-    c = _lib.MoeGrouped(**kw)
+    c = _lib.Moe(**kw)
     c._keep = buf
     return c
 
 
 def test_every_refusal_comes_before_a_launch():
     """Dummy pointers: a call that got as far as a launch would fault or fail on a machine without a GPU; each answers its own code, in
-    dg_moe_w4's order, the workspaces among them."""
+    the GEMV kernel's order (the one check_moe), the workspaces among them."""
     from any4_amd import _lib
 
     L = _lib.load()
     E = dict(null=-1, inner=-2, kdiv=-3, group=-4, dtype=-5, qtype=-6, shape=-7, align=-8, size=-10, layout=-12, struct=-14)
-    launch = lambda c: L.dg_moe_grouped_launch(ctypes.byref(c), 0, None)
-    assert L.dg_moe_grouped_launch(None, 0, None) == E["null"]
-    assert launch(_call(struct_bytes=144)) == E["struct"]                   # dg_moe_w4's size
-    assert launch(_call(struct_bytes=184, x=None)) == E["struct"]          # struct before the pointers
+    launch = lambda c: L.dg_moe_launch(ctypes.byref(c), 0, None)
+    assert L.dg_moe_launch(None, 0, None) == E["null"]
+    assert launch(_call(struct_bytes=144)) == E["struct"]                   # ABI 9's dg_moe_w4
+    assert launch(_call(struct_bytes=176)) == E["struct"]                   # ... and dg_moe_grouped
+    assert launch(_call(struct_bytes=ctypes.sizeof(_lib.Moe) + 8, x=None)) == E["struct"]   # struct before the pointers
     assert launch(_call(stage=2)) == E["layout"]
     for f in ("x", "w", "qinfo", "lut", "y", "ids", "gates", "group_ws", "f32_ws"):
         assert launch(_call(**{f: None})) == E["null"], f
@@ -277,11 +267,11 @@ def test_every_refusal_comes_before_a_launch():
     for f in ("stride_w", "stride_qinfo", "stride_lut"):
         assert launch(_call(**{f: 24})) == E["align"], f
     # the plan: no workspace is looked at
-    out = (ctypes.c_int64 * 7)()
-    assert L.dg_moe_grouped_plan(ctypes.byref(_call(group=32)), -1, out) == E["group"]
-    assert L.dg_moe_grouped_plan(ctypes.byref(_call()), -1, None) == E["null"]
-    assert L.dg_moe_grouped_plan(ctypes.byref(_call(group_ws=None, f32_ws=None, group_ws_bytes=0, f32_ws_bytes=0)), -1, out) == 0
-    assert tuple(out)[5:] == (_gws(4, 4), 4 * 4 * 64)
+    out = (ctypes.c_int64 * 8)()
+    assert L.dg_moe_plan(ctypes.byref(_call(group=32)), -1, out) == E["group"]
+    assert L.dg_moe_plan(ctypes.byref(_call()), -1, None) == E["null"]
+    assert L.dg_moe_plan(ctypes.byref(_call(group_ws=None, f32_ws=None, group_ws_bytes=0, f32_ws_bytes=0)), -1, out) == 0
+    assert tuple(out)[5:] == (_gws(4, 4), 4 * 4 * 64, 0)
     # dg_moe_group
     buf = ctypes.create_string_buffer(4096)
     p = (ctypes.addressof(buf) + 63) & ~63

@@ -31,7 +31,7 @@ def test_the_flavours_and_the_pairs_next_to_them_that_the_library_refuses():
     from tests import attn_abi
 
     L = _lib.load()
-    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 9
+    assert L.tg_abi_version() == _lib.TG_ABI_VERSION == 10
     pools8 = _lib.DG_ATTN_SEQ | _lib.DG_ATTN_PAGED | _lib.DG_ATTN_MX8
     assert [attn_abi.PAIR[name] for name in NAMES] == [(_lib.DG_ATTN_SPLIT, pools8 | _lib.DG_ATTN_ONE_BARRIER), (_lib.DG_ATTN_PREFILL, pools8)]
     for name in NAMES:

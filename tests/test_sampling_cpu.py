@@ -121,7 +121,7 @@ def test_dg_sample_is_exported_and_refuses_bad_calls_before_any_launch():
 
     lib = _lib.load()
     assert "dg_sample" in _lib.SYMBOLS and "dg_sample_scratch_bytes" in _lib.SYMBOLS and callable(decode_ops.sample)
-    assert lib.tg_abi_version() == 9
+    assert lib.tg_abi_version() == 10
     assert lib.dg_sample_scratch_bytes(8, 128256) == 0
     P = 0x10000  # never dereferenced: every call below is refused on the host
     good = dict(logits=P, ctr=P, temperature=P, top_k=P, top_p=P, seed=P, u_in=None, token_out=P, u_out=None, scratch=None, scratch_bytes=0,

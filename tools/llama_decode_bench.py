@@ -68,8 +68,8 @@ rotating; (b), (c) and (d) replay one captured graph and differ only in `adapter
 the grouped path against the row blocks of 8 rows on the same stack, alternating, three runs each, median (min - max).
 
 --moe (one GPU): mixture of experts at the Mixtral-8x7B shape (8 experts, 2 per token), two JSON lines per batch size
-(1 and 8), appended to --out: the captured step on dg_moe_route / dg_moe_w4_launch against the formulation that is possible without them
-(every expert through the module GEMVs, a device-side mask: it captures too), alternating, three runs each; and dg_moe_w4_launch GATE_UP /
+(1 and 8), appended to --out: the captured step on dg_moe_route / dg_moe_launch (DG_MOE_GEMV) against the formulation that is possible without them
+(every expert through the module GEMVs, a device-side mask: it captures too), alternating, three runs each; and DG_MOE_GEMV GATE_UP /
 DOWN against the module GEMV on ONE expert's linears at the same m, one pair per layer and graph, with the effective bandwidth over the
 bytes of the experts the seeded router selected (computed from shapes, `moe_bytes`).
 """
@@ -227,10 +227,10 @@ def moe_bytes(stack, n_experts):
 
 
 def moe_bench(a, cfg, device):
-    """--moe: (1) the captured step of a stack with experts on dg_moe_route / dg_moe_w4_launch against the formulation that is possible
+    """--moe: (1) the captured step of a stack with experts on dg_moe_route / dg_moe_launch (DG_MOE_GEMV) against the formulation that is possible
     WITHOUT them -- every expert through the module GEMVs (w4_linear_fused: SwiGLU in gate_up's store), combined with a device-side mask,
     the router in torch; nothing read on the host, so it captures too -- at bs 1 and 8, alternating in one process, three runs each.
-    (2) dg_moe_w4_launch GATE_UP + DOWN back to back against the module GEMVs on ONE expert's two linears at the same m, as graphs of one
+    (2) DG_MOE_GEMV GATE_UP + DOWN back to back against the module GEMVs on ONE expert's two linears at the same m, as graphs of one
     pair per layer (every pair reads another layer's weights: nothing is served from a cache), alternating, three runs; the effective
     bandwidth is over the bytes of the experts the seeded router selected (moe_bytes: from shapes)."""
     from any4_amd import decode_ops as G, ops
@@ -341,7 +341,7 @@ def moe_bench(a, cfg, device):
         sel = {"gate_up": moe_bytes(gu0, mean_distinct), "down": moe_bytes(dn0, mean_distinct)}
         one = {"gate_up": moe_bytes(gu0, 1), "down": moe_bytes(dn0, 1)}
         tbs = lambda nbytes, k: round(nbytes / (us[k]["median"] * 1e-6) / 1e12, 3)
-        legs.append(dict(base, leg="kernels: dg_moe_w4 GATE_UP / DOWN against the module GEMV on one expert, one pair per layer and graph", bs=bs,
+        legs.append(dict(base, leg="kernels: DG_MOE_GEMV GATE_UP / DOWN against the module GEMV on one expert, one pair per layer and graph", bs=bs,
                          distinct_experts_per_layer=distinct, us_per_layer=us,
                          selected_bytes_per_layer={k: int(v) for k, v in sel.items()}, one_expert_bytes=one,
                          effective_TBps={"moe_gate_up": tbs(sel["gate_up"], "moe_gate_up"), "moe_down": tbs(sel["down"], "moe_down"),
@@ -355,7 +355,7 @@ def moe_bench(a, cfg, device):
 
 def moe_prefill_bench(a, cfg, device):
     """--moe --moe-prefill: `prefill` of T tokens on a stack with experts, the grouped path (MoEMLP.grouped_from = 1: route, dg_moe_group,
-    dg_moe_grouped_launch twice) against the row-block path (grouped_from = None: dg_moe_w4_launch in blocks of 8 rows) on the SAME stack
+    dg_moe_launch with DG_MOE_GROUPED twice) against the row-block path (grouped_from = None: DG_MOE_GEMV in blocks of 8 rows) on the SAME stack
     and weights, alternating in one process, three runs each.  The row-block path's kernels are the ones this library had before the grouped
     path existed, so in the same build it stands for the earlier library.  One JSON line per (T, bs) leg."""
     from any4_amd.decode import Any4Factory, DecodeStack
@@ -393,7 +393,7 @@ def moe_prefill_bench(a, cfg, device):
                 series[k].append(run(k == "grouped", 5 if k == "grouped" else 2))
         ms = {k: stat(v) for k, v in series.items()}
         spread = max(ms[k]["max"] - ms[k]["min"] for k in ms)
-        legs.append(dict(base, leg="prefill: grouped tile GEMM / row blocks of 8 (dg_moe_w4_launch)", T=T, bs=bs, rows=T * bs, ms_per_prefill=ms,
+        legs.append(dict(base, leg="prefill: grouped tile GEMM / row blocks of 8 (DG_MOE_GEMV)", T=T, bs=bs, rows=T * bs, ms_per_prefill=ms,
                          speedup_grouped=round(ms["row_blocks"]["median"] / ms["grouped"]["median"], 3),
                          grouped_faster_by_more_than_the_larger_spread=bool(ms["row_blocks"]["median"] - ms["grouped"]["median"] > spread)))
     return legs
