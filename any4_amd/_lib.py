@@ -47,6 +47,22 @@ class W4Gemm(ctypes.Structure):
             self.struct_bytes = ctypes.sizeof(W4Gemm)
 
 
+class MxGemm(ctypes.Structure):
+    """struct tg_mx_gemm (include/tinygemm_hip.h)"""
+
+    _fields_ = [
+        ("struct_bytes", ctypes.c_uint32), ("struct_reserved", ctypes.c_uint32),
+        ("x_codes", _vp), ("x_exps", _vp), ("w", _vp), ("w_exps", _vp), ("bias", _vp), ("y", _vp),
+        ("m", _i64), ("wrows", _i64), ("k", _i64),
+        ("w_on_right", _i32), ("w_format", _i32), ("inner_k_tiles", _i32), ("reserved", _i32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = ctypes.sizeof(MxGemm)
+
+
 TG_PEER_MAX_WORLD = 16
 
 
@@ -161,6 +177,9 @@ SYMBOLS = {
     "tg_gemm_w4_dx_workspace_bytes": [ctypes.POINTER(W4Gemm)],
     "tg_gemm_w4_dq": [ctypes.POINTER(W4Gemm), _vp, _vp, _vp, ctypes.c_int, _vp],
     "tg_gemm_w4_dq_workspace_bytes": [ctypes.POINTER(W4Gemm)],
+    # MX4 weights x MXFP8 activations: x, m, k, codes, exps, device, stream / the call struct
+    "tg_quant_mx8_rows": [_vp, _i64, _i64, _vp, _vp, ctypes.c_int, _vp],
+    "tg_gemm_mx4a8": [ctypes.POINTER(MxGemm), ctypes.c_int, _vp],
     "tg_gemm_f16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
     "tg_convert_to_Bint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],
     "tg_convert_to_Aint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],

@@ -51,6 +51,17 @@ __device__ __forceinline__ uint32_t mx8_e4m3_rne(float y) {
   return sign | c;
 }
 
+// The exponent rule of a 32-element block, from the f32 bits `u` of its maximum magnitude (infinite when an element is not finite): the
+// exponent byte E (255: the block is marked, its codes are 0x7F) and the exact power of two the elements are multiplied by before rounding.
+// amax = m 2^ex, m in [0.5, 1): ex = biased - 126; the byte is ex - 9 + 127, one more when m > 0.875 (mantissa above 1.75), clamped at 0
+__device__ __forceinline__ float mx8_block_scale(uint32_t u, uint32_t& E, bool& bad) {
+  int e = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
+  e = e < 0 ? 0 : e;
+  bad = u >= 0x7f800000u;
+  E = bad ? 255u : (uint32_t)e;
+  return u2f((uint32_t)(254 - e) << 23);
+}
+
 // One element per lane, a 32-element block = 32 ALIGNED lanes of a wave; every lane of the wave must be here (lanes without an element
 // pass 0).  Returns the lane's code and the block's exponent byte.
 __device__ __forceinline__ void mx8_encode_lane(float x, uint32_t& code, uint32_t& E) {
@@ -58,14 +69,9 @@ __device__ __forceinline__ void mx8_encode_lane(float x, uint32_t& code, uint32_
   a = a < INFINITY ? a : INFINITY;  // (a NaN too: the block is marked, fmaxf would drop it)
   float m = tgl::row_max(a), p, q;
   tgl::rows16(m, p, q);
-  const uint32_t u = f2u(fmaxf(p, q));
-  // amax = m 2^ex, m in [0.5, 1): ex = biased - 126; the byte is ex - 9 + 127, one more when m > 0.875 (mantissa above 1.75), clamped at 0
-  int e = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = e < 0 ? 0 : e;
-  const bool bad = u >= 0x7f800000u;
-  const float y = fminf(fmaxf(x * u2f((uint32_t)(254 - e) << 23), -448.f), 448.f);
-  code = bad ? 0x7fu : mx8_e4m3_rne(y);
-  E = bad ? 255u : (uint32_t)e;
+  bool bad;
+  const float s = mx8_block_scale(f2u(fmaxf(p, q)), E, bad);
+  code = bad ? 0x7fu : mx8_e4m3_rne(fminf(fmaxf(x * s, -448.f), 448.f));
 }
 // ... and the value the cache row now holds in this place (f32 of the 16-bit type)
 template <typename DT>
@@ -103,15 +109,11 @@ __device__ __forceinline__ u32x4 mx8_encode_piece(const u32x4& v, u32x2& codes, 
   }
   m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0xB1, 0xf, 0xf, true)));  // quad_perm [1,0,3,2]
   m = fmaxf(m, __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, m), 0x4E, 0xf, 0xf, true)));  // quad_perm [2,3,0,1]
-  const uint32_t u = f2u(m);
-  int e = (int)(u >> 23) - 8 + ((u & 0x7fffffu) > 0x600000u ? 1 : 0);
-  e = e < 0 ? 0 : e;
-  const bool bad = u >= 0x7f800000u;
-  const float s = u2f((uint32_t)(254 - e) << 23);
+  bool bad;
+  const float s = mx8_block_scale(f2u(m), E, bad);
   uint32_t c[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) c[j] = bad ? 0x7fu : mx8_e4m3_rne(fminf(fmaxf(x[j] * s, -448.f), 448.f));
   codes = u32x2{c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24), c[4] | (c[5] << 8) | (c[6] << 16) | (c[7] << 24)};
-  E = bad ? 255u : (uint32_t)e;
   return mx8_to16<DT>(codes, E);
 }

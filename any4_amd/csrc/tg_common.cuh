@@ -21,6 +21,7 @@
 //   tg_moe.hip         moe_route_kernel, moe_w4_kernel (moe.cuh)               mixture-of-experts decode: the top-k router and the expert-indexed 4-bit GEMV (dg_moe_route / dg_moe_launch / dg_moe_plan: the one front of both MoE kernels)
 //   tg_moe_tile.hip    w4_gemm_tile_kernel<GRP>, moe_group_kernel, moe_combine_kernel (w4_gemm_tile.cuh, moe_grouped.cuh)  mixture-of-experts prefill: pairs sorted by expert, grouped tile GEMM (dg_moe_group / DG_MOE_GROUPED's launcher)
 //   tg_kmeans.hip      kmeans_rows_kernel        (kmeans.cuh)              the any4 quantizer's per-row weighted 1-D k-means (tg_kmeans_rows); compiled with -ffp-contract=off
+//   tg_mx.hip          mx8_rows_kernel, mx4a8_gemm_kernel (w4a8_gemm_mx.cuh)   MX4 weights x MXFP8 activations on the block-scaled MFMA (tg_quant_mx8_rows / tg_gemm_mx4a8)
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);
 // tg_trace.cuh is the developer trace (-DGEMV_TRACE=1), included here.

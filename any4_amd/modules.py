@@ -391,12 +391,44 @@ class MX4Linear(_PackedLinear):
         return self.exponents
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
-                 group_size: int = 32, kernel: str = "linear_y_f16RM_x_f16RM_W_mx4TC", w_inner_k: int = 4) -> None:
+                 group_size: int = 32, kernel: str = "linear_y_f16RM_x_f16RM_W_mx4TC", w_inner_k: int = 4, activations: str | None = None) -> None:
         super().__init__()
+        if activations not in (None, "mx8"):
+            raise ValueError(f"activations must be None (16-bit activations) or 'mx8', got {activations!r}")
+        if activations == "mx8":
+            # W4A8 on the block-scaled matrix instruction (ops.gemm_mx4_a8): what its kernel reads, refused here and not at the first forward
+            if group_size != 32:
+                raise ValueError(f"activations='mx8' needs group_size 32 (one exponent per hardware block), got {group_size}")
+            if in_features % 128:
+                raise ValueError(f"activations='mx8' needs in_features % 128 == 0 (128 k per matrix instruction), got {in_features}")
+            if w_inner_k != 4:
+                raise ValueError(f"activations='mx8' needs w_inner_k = 4 (the packed words the kernel reads in place), got {w_inner_k}")
+            if dtype != torch.bfloat16:
+                raise ValueError(f"activations='mx8' needs dtype=torch.bfloat16, got {dtype}")
+            if kernel not in self._PACKERS:
+                raise ValueError(f"Unsupported kernel type {kernel}")
+        self.activations = activations
         self._make_common(in_features, out_features, bias, device, dtype, group_size, kernel, w_inner_k, zero_init=True)
         del self.scales_and_zeros
         self.exponents = torch.nn.Parameter(torch.full((out_features, in_features // group_size), 127, dtype=torch.uint8, device=device),
                                             requires_grad=False)
+
+    def forward(self, input: torch.Tensor) -> torch.Tensor:
+        if self.activations is None:
+            return self._forward(input)
+        if torch.is_grad_enabled() and input.requires_grad:
+            raise RuntimeError("MX4Linear(activations='mx8') has no input gradient (the activations are quantised to MXFP8 on the way in): "
+                               "run it under torch.no_grad(), or build the module with activations=None to train through it")
+        if not self.weight_reshaped:
+            self.reshape_weight(self.w_inner_k)
+        if self.__dict__.get("_relayout_pending") and self.weight.is_cuda:
+            self._auto_relayout()
+        x2d = input.reshape(-1, input.shape[-1]).contiguous()
+        fused = self.bias is not None and self.bias.numel() == self.exponents.size(0)   # (one value per tile-padded weight row)
+        y = _ops.gemm_mx4_a8(x2d, self.weight, self.exponents, self.kernel == "linear_y_f16RM_x_f16RM_W_mx4TC", self.bias if fused else None)
+        if self.bias is not None and not fused:
+            y = y + self.bias
+        return y.view(*input.shape[:-1], y.shape[-1])
 
     def _gemm(self, x):
         if self.kernel not in self._PACKERS:

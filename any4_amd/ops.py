@@ -1189,6 +1189,45 @@ _IMPLS = {
     "tinygemm_dq_f16RM_x_f16RM_w_any4TC": tinygemm_dq_f16RM_x_f16RM_w_any4TC,
 }
 
+# ---------------------------------------------------------------------------------------------
+# MX4 weights x MXFP8 activations (W4A8) on the block-scaled matrix instruction: opt-in, it changes the activations' numerics
+# ---------------------------------------------------------------------------------------------
+
+def quantize_mx8_rows(x: torch.Tensor):
+    """bf16 x [m][k] (k % 32 == 0) -> (codes uint8 [m][k], exps uint8 [m][k / 32]): the MXFP8 rows tg_gemm_mx4a8 reads; utils.mx8_rows_ref
+    gives the same bytes in plain torch (kvcache.mx8_encode with the 32 codes of every block in the packed weights' order)."""
+    _check(x.dim() == 2 and x.is_contiguous() and x.dtype == torch.bfloat16, "quantize_mx8_rows: x must be a contiguous 2-D bfloat16 matrix")
+    m, k = x.shape
+    if x.data_ptr() % 16:
+        x = x.clone()
+    codes = torch.empty((m, k), dtype=torch.uint8, device=x.device)
+    exps = torch.empty((m, k // 32), dtype=torch.uint8, device=x.device)
+    if m:
+        _lib.check(_L.tg_quant_mx8_rows(x.data_ptr(), m, k, codes.data_ptr(), exps.data_ptr(), _dev(x), _stream(x)), "quantize_mx8_rows")
+    return codes, exps
+
+
+def gemm_mx4_a8(x: torch.Tensor, w: torch.Tensor, exponents: torch.Tensor, weight_on_right: bool, bias: torch.Tensor | None = None) -> torch.Tensor:
+    """y [m][wrows] = mx8(x) . mx4(w)^T (utils.mx4a8_ref is the definition): x bf16 [m][k], k % 128 == 0, quantised to MXFP8 rows in one
+    launch and multiplied in a second one with the packed MX4 weights an MX4Linear holds (Bint4 words of innerKTiles 4, or the native
+    weights-on-the-left tensor), exponents uint8 [wrows][k / 32].  Both launches go to the current stream; the call can be captured."""
+    _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
+    m, k = x.shape
+    inner, wrows, w_format, _, exponents, _ = _w4_operands(x, k, w, 32, exponents, None, TG_Q_MX4, weight_on_right, aint4=False)
+    if bias is not None:
+        _check(bias.dtype == x.dtype and bias.device == x.device and bias.dim() == 1 and bias.numel() == wrows and bias.is_contiguous(),
+               "bias must be a contiguous bfloat16 vector of one value per (tile-padded) weight row")
+    y = torch.empty((m, wrows), dtype=x.dtype, device=x.device)
+    if m == 0:
+        return y
+    codes, exps = quantize_mx8_rows(x)
+    args = _lib.MxGemm(x_codes=codes.data_ptr(), x_exps=exps.data_ptr(), w=w.data_ptr(), w_exps=exponents.data_ptr(),
+                       bias=(bias.data_ptr() if bias is not None else None), y=y.data_ptr(), m=m, wrows=wrows, k=k,
+                       w_on_right=1 if weight_on_right else 0, w_format=w_format, inner_k_tiles=inner)
+    _lib.check(_L.tg_gemm_mx4a8(ctypes.byref(args), _dev(x), _stream(x)), "gemm_mx4_a8")
+    return y
+
+
 _library = None
 
 

@@ -87,3 +87,30 @@ def dequantize_mx4(q: torch.Tensor, e: torch.Tensor) -> torch.Tensor:
     mags = torch.tensor(_MX4_MAGNITUDES + tuple(-m for m in _MX4_MAGNITUDES), dtype=torch.float32, device=q.device)
     v = mags[q.long()].reshape(q.size(0), groups, -1)
     return (v * (2.0 ** (e.float() - 127)).unsqueeze(-1)).reshape(q.shape)
+
+
+# ---- MX4 weights x MXFP8 activations (ops.gemm_mx4_a8) ----
+# Operand position p of a 32-element block holds element MX8_ROWS_PI[p]: the order in which the packed 4-bit words hold a block's weights
+# (word q of the block, nibble n: k offset 2 q + 8 (n % 4) + n / 4), which the activation codes follow so that the matrix instruction
+# contracts both operands as they are stored.
+MX8_ROWS_PI = tuple(2 * (p // 8) + 8 * (p % 4) + (p % 8) // 4 for p in range(32))
+
+
+def mx8_rows_ref(x: torch.Tensor):
+    """x [m][k] -> (codes uint8 [m][k], exps uint8 [m][k / 32]): the exact bytes of ops.quantize_mx8_rows.  kvcache.mx8_encode's
+    exponents as they are, its codes with the 32 positions of every block permuted by MX8_ROWS_PI."""
+    from .kvcache import mx8_encode
+    codes, exps = mx8_encode(x)
+    m, k = x.shape
+    pi = torch.tensor(MX8_ROWS_PI, device=x.device)
+    return codes.view(torch.uint8).reshape(m, k // 32, 32)[:, :, pi].reshape(m, k).contiguous(), exps
+
+
+def mx4a8_ref(x: torch.Tensor, codes: torch.Tensor, exponents: torch.Tensor) -> torch.Tensor:
+    """The definition of the MX4 x MXFP8 product in float64: y[a][r] = sum_k x^[a][k] * w[r][k], x^ = mx8_decode(mx8_encode(x)),
+    w = dequantize_mx4(codes [rows][k], exponents [rows][k / 32]) (an exponent of 255: NaN, as the kernels have it)."""
+    from .kvcache import mx8_decode, mx8_encode
+    xh = mx8_decode(*mx8_encode(x), torch.float64)
+    w = dequantize_mx4(codes, exponents).double()
+    w = torch.where(expand_q_groups(exponents == 255, codes.shape, 32), torch.full_like(w, float("nan")), w)
+    return xh @ w.t()

@@ -370,6 +370,46 @@ TG_API int tg_kmeans_rows(const float* x, const float* w, int64_t w_row_stride, 
  * the launch would return for these sizes (weighted: w != NULL). */
 TG_API int tg_kmeans_rows_plan(int64_t rows, int64_t k, int C, int S, int max_iter, double tol, int weighted, int64_t* out);
 
+/*
+ * MX4 weights x MXFP8 activations (W4A8, MX on both sides) on gfx950's block-scaled matrix instruction,
+ * v_mfma_scale_f32_16x16x128_f8f6f4 (any4_amd/csrc/w4a8_gemm_mx.cuh).  No counterpart in the reference.  Opt-in: it changes the
+ * activations' numerics.  Added without an ABI version bump: callers probe for the symbols.
+ *
+ * tg_quant_mx8_rows: bf16 x [m][k] -> E4M3 codes [m][k] (bytes) and E8M0 exponents [m][k / 32], one exponent per 32 consecutive k.  The
+ *   format of the mx8 KV cache (any4_amd/kvcache.py: mx8_encode -- same exponent rule, same saturation at +-448, a block with a non-finite
+ *   element: codes 0x7F, exponent 255), exponents byte for byte; the 32 codes of a block are stored in the order in which the packed 4-bit
+ *   words hold a block's weights: position p holds element PI(p) = 2 (p / 8) + 8 (p % 4) + (p % 8) / 4 (any4_amd/utils.py: mx8_rows_ref
+ *   produces the kernel's exact bytes).  x, codes 16-byte aligned; k % 32 == 0 (TG_E_K_DIV); m * k * 2 < 2 GiB (TG_E_SIZE).
+ *
+ * tg_gemm_mx4a8:  y[a][r] = RNE16( sum over 32-k blocks b of 2^(Ex[a][b] + Ew[r][b] - 254) * sum_j fp8(x_codes[a][b][j]) * fp4(w[r][b][j]) ),
+ *   with a bias RNE16(RNE16(sum) + bias[r]).  The weights are the tensors an MX4 linear already holds: Bint4 words of innerKTiles 4
+ *   (w_on_right = 1) or the same words as TG_WFMT_ROWS (w_on_right = 0), exponents [wrows][k / 32].  An exponent byte of 255 on either side
+ *   makes exactly that weight row's / activation row's outputs NaN.  One workgroup per 64 x 256 output tile, k never split: a row's bits do
+ *   not depend on m.  Any m >= 1, tuned for m >= 64.
+ *   Refused before any HIP call: a required pointer NULL (bias may be): TG_E_NULL; x_codes / w not 16-byte, the exponents not 4-byte, y / bias
+ *   not 8-byte aligned: TG_E_ALIGN; k % 128 != 0: TG_E_K_DIV; inner_k_tiles != 4: TG_E_INNER_K; the reference's Aint4 words (w_on_right = 0,
+ *   TG_WFMT_M16N8K16): TG_E_LAYOUT; struct_bytes not this library's, or a reserved field not 0: TG_E_STRUCT; an operand of 2 GiB or more:
+ *   TG_E_SIZE; sizes not positive, wrows not whole tiles (8 / 16), an unknown w_format: TG_E_SHAPE.
+ */
+typedef struct tg_mx_gemm {
+  uint32_t struct_bytes;    /* sizeof(struct tg_mx_gemm) as the caller was compiled */
+  uint32_t struct_reserved; /* must be 0 */
+  const void* x_codes;      /* [m][k] E4M3 codes as tg_quant_mx8_rows writes them */
+  const void* x_exps;       /* [m][k / 32] E8M0 */
+  const void* w;            /* packed fp4-e2m1 codes (see above) */
+  const void* w_exps;       /* [wrows][k / 32] E8M0 */
+  const void* bias;         /* optional bf16 [wrows]; NULL = none */
+  void* y;                  /* out, bf16 [m][wrows] */
+  int64_t m, wrows, k;      /* wrows INCLUDING tile padding, as in tg_w4_gemm */
+  int32_t w_on_right;
+  int32_t w_format;         /* TG_WFMT_* (w_on_right = 0 only) */
+  int32_t inner_k_tiles;    /* 4 */
+  int32_t reserved;         /* must be 0 */
+} tg_mx_gemm;
+
+TG_API int tg_quant_mx8_rows(const void* x, int64_t m, int64_t k, void* codes, void* exps, int device, tg_stream_t stream);
+TG_API int tg_gemm_mx4a8(const tg_mx_gemm* args, int device, tg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
