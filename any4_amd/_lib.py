@@ -104,6 +104,23 @@ class Attn(ctypes.Structure):
             self.struct_bytes = ctypes.sizeof(Attn)
 
 
+class Verify(ctypes.Structure):
+    """struct dg_verify (include/decode_glue_hip.h)"""
+
+    _fields_ = [
+        ("struct_bytes", _u32), ("reserved0", _u32),
+        ("qkv", _vp), ("cos", _vp), ("sin", _vp), ("pos", _vp), ("len", _vp), ("slot", _vp), ("k_cache", _vp), ("v_cache", _vp), ("out", _vp),
+        ("scratch", _vp),
+        ("scratch_bytes", _i64), ("bs", _i64), ("cache_bs", _i64), ("max_seq", _i64),
+        ("T", _i32), ("hl", _i32), ("kvl", _i32), ("d", _i32), ("nsplit", _i32), ("dtype", _i32), ("scale", _f32), ("reserved", _u32),
+    ]
+
+    def __init__(self, *args, **kw):
+        super().__init__(*args, **kw)
+        if "struct_bytes" not in kw:
+            self.struct_bytes = ctypes.sizeof(Verify)
+
+
 # The mixture-of-experts call of include/decode_glue_hip.h: two kernels, two stages, one struct
 DG_MOE_GATE_UP, DG_MOE_DOWN = 0, 1
 DG_MOE_GEMV, DG_MOE_GROUPED = 0, 1
@@ -200,6 +217,9 @@ SYMBOLS = {
                        ctypes.c_int, ctypes.c_int, _vp],
     "dg_attn_launch": [ctypes.POINTER(Attn), ctypes.c_int, _vp],
     "dg_rope_attn_split_scratch_bytes": [_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int],
+    # the verify pass of speculative decoding: the call struct / bs, hl, d, T, nsplit
+    "dg_verify_attn": [ctypes.POINTER(Verify), ctypes.c_int, _vp],
+    "dg_verify_attn_scratch_bytes": [_i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int],
     "dg_swiglu": [_vp, _vp, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     "dg_linear16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, _vp],
     # the sampler: logits, ctr, temperature, top_k, top_p, seed, u_in, token_out, u_out, scratch, scratch_bytes, bs, vocab, ld,
@@ -248,7 +268,7 @@ def load() -> ctypes.CDLL:
             raise ImportError(f"{LIB_PATH} does not export {name}; rebuild with `python -m any4_amd.build`") from e
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "tg_error_string" else
-                      ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "dg_sample_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
+                      ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "dg_verify_attn_scratch_bytes", "dg_sample_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
                                                                                           "tg_gemm_w4_dx_workspace_bytes", "tg_gemm_w4_dq_workspace_bytes") else ctypes.c_int)
     if lib.tg_abi_version() != TG_ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.tg_abi_version()} != {TG_ABI_VERSION}; rebuild")

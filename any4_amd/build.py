@@ -37,6 +37,7 @@ UNITS = [
     # results on MI355X parts.  Here the only use would be the bias add of the output store (32 v_pk_add_f32 without the flag, scalar adds with
     # it: same bits, same 244 registers), so the flag costs nothing; the host pass warns that it does not know the feature.
     ("tg_mx", "tg_mx.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),
+    ("tg_verify", "tg_verify.hip", ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]),  # (as tg_mx: a new unit)
     ("tg_dx", "tg_dx.hip", []),
     ("tg_dq", "tg_dq.hip", []),
     ("tg_prefill", "tg_prefill.hip", []),

@@ -418,6 +418,18 @@ class DecodeLayer(torch.nn.Module):
         appended, causal.  per_sequence: `pos`, `lengths`, `slots` [n] on the device."""
         return self.kv.prefill_attention(qkv, pos, cos_tab, sin_tab, self.hl, T, lengths, slots, per_sequence)
 
+    def verify_attention(self, qkv, pos, cos_tab, sin_tab, T: int, lengths=None, slots=None, nsplit: int = 1, scratch=None):
+        """prefill_attention's per-sequence call for the T <= 8 draft tokens of a verify pass, on the kernel that splits the cached
+        context over `nsplit` blocks (decode_ops.verify_attn; `scratch`: verify_attn_scratch).  Contiguous 16-bit caches only."""
+        from . import decode_ops as G
+
+        kv = self.kv
+        if kv.mx8 or kv.paged:
+            raise ValueError("verify attention on an mx8 or paged KV cache is not built yet")
+        out = qkv.new_zeros(qkv.shape[0], self.hl * self.cfg.head_dim)  # (the context rows of tokens that do not exist are zero)
+        return G.verify_attn(qkv, cos_tab, sin_tab, pos, kv.k, kv.v, self.hl, self.kvl, self.cfg.head_dim, 1.0 / math.sqrt(self.cfg.head_dim),
+                             T, nsplit, scratch, out=out, lengths=lengths, slots=slots)
+
     def forward_fused(self, h, delta, attention, pos, cos_tab, sin_tab, gather, lora=None):
         """Same layer on the HIP glue kernels (include/decode_glue_hip.h): 4 launches + 4 GEMMs, for one token or a prefill chunk
         (the linears are called as modules, so the library routes them by row count).  `h` is the residual stream (updated in
@@ -674,6 +686,13 @@ class DecodeStack(torch.nn.Module):
                 self._attn_split = max(1, int(os.environ["ANY4_ATTN_SPLIT"]))
             if self._attn_split > 1 or kv_cache == "mx8":
                 self._attn_scratch = G.rope_attn_split_scratch(bs, hl, cfg.head_dim, self._attn_split, device)
+        # the verify pass (speculative decoding): `_attn_split`'s rule for the workgroups of its kernel -- one per (sequence, kv head, group of
+        # 4 query heads) --; the scratch itself is made by the first `verify` call
+        kvl_ = max(1, cfg.kv_heads // world)
+        rep_ = max(1, (cfg.heads // world) // kvl_)
+        want = 1 if cfg.max_seq <= 1024 else 4 if cfg.max_seq <= 4096 else 8
+        self._verify_split = max(1, min(want, 256 // max(1, bs * kvl_ * -(-rep_ // min(rep_, 4)))))
+        self._verify_scratch = {}  # sequences of a pass -> its scratch (the counters' extent follows the number of sequences)
         for layer in self.layers:  # what the stack owns of every layer's cache (as built: no table, no scratch, one block per head)
             layer.kv.table, layer.kv.scratch, layer.kv.nsplit = self.block_table if self.paged else None, self._attn_scratch, self._attn_split
 
@@ -1033,11 +1052,12 @@ class DecodeStack(torch.nn.Module):
         """_gather for bs * T rows: always the all_gather branch (the peer-write buffers are sized for `bs` rows)."""
         return self._gather(y, peer_ok=False)
 
-    def _prefill_chunk(self, toks, positions, lengths, slots, per_sequence):
+    def _prefill_chunk(self, toks, positions, lengths, slots, per_sequence, verify=False):
         """A chunk `toks` [n, T] through every layer; `positions`, `lengths`, `slots`: n host ints each.  Returns the last layer's
         (h, delta), [n * T, hidden] (delta: its not-yet-added MLP output on the fused path, else None).  The fused attention launch is
         the scalar entry point on `prefill_pos` (set to positions[0] here; positions None: left as the caller set it) or, per_sequence,
-        the _seq one on the first n of `prefill_pos_seq` / `prefill_len` / `prefill_slot`."""
+        the _seq one on the first n of `prefill_pos_seq` / `prefill_len` / `prefill_slot` (positions None: left as the caller set them).
+        verify (per_sequence): the fused attention launch is the verify pass's split-KV kernel (DecodeLayer.verify_attention)."""
         n, T = toks.shape
         if not per_sequence and positions is not None:
             self.prefill_pos.fill_(positions[0])
@@ -1046,15 +1066,19 @@ class DecodeStack(torch.nn.Module):
         pos = self.prefill_pos
         if per_sequence and self.fused:
             pos, dev_len, dev_slot = [buf[:n] for buf in (self.prefill_pos_seq, self.prefill_len, self.prefill_slot)]
-            for buf, vals in zip((pos, dev_len, dev_slot), (positions, lengths, slots)):
-                buf.copy_(torch.tensor(vals, dtype=torch.long))
+            if positions is not None:
+                for buf, vals in zip((pos, dev_len, dev_slot), (positions, lengths, slots)):
+                    buf.copy_(torch.tensor(vals, dtype=torch.long))
         for layer in self.layers:
             if not self.fused:  # plain torch needs the positions on the host (prefill() refuses position=None on this path)
                 h = layer.forward_prefill(h, positions, lengths, slots, T, self.cos, self.sin, self._gather_rows, lora=lora)
                 continue
             # the eight launches of a decode step at n * T rows, with the chunk's attention
             attention = layer.prefill_attention
-            if per_sequence:
+            if verify:
+                attention = partial(layer.verify_attention, T=T, lengths=dev_len, slots=dev_slot, nsplit=self._verify_split,
+                                    scratch=self._verify_scratch.get(n))
+            elif per_sequence:
                 attention = partial(attention, T=T, lengths=dev_len, slots=dev_slot, per_sequence=True)
             h, delta = layer.forward_fused(h, delta, attention, pos, self.cos, self.sin, self._gather_rows, lora=lora)
         return h, delta
@@ -1152,6 +1176,63 @@ class DecodeStack(torch.nn.Module):
             rows = [None if t is None else t.view(n, Tc, -1).gather(1, idx.expand(n, 1, t.shape[-1])).squeeze(1) for t in hd]
             keep = rows if keep is None else [None if r is None else torch.where(here, r, k) for r, k in zip(rows, keep)]
         return self._head(*[None if t is None else t.contiguous() for t in keep])
+
+    @torch.no_grad()
+    def verify(self, tokens: torch.Tensor, position, lengths=None, slots=None) -> torch.Tensor:
+        """The verify pass of speculative decoding: `tokens` [n, T], T <= 8 -- per sequence the last real token followed by T - 1 draft
+        tokens -- at positions position[i] ... position[i] + T - 1, in ONE pass; returns the logits of EVERY row, [n, T, vocab] (the final
+        hidden states when built without LM head).  Row t holds what a `decode` of tokens[i, t] at position[i] + t would have returned,
+        had tokens[i, :t] been decoded in front of it (within the numeric contract of the fused path: the attention sums run in another
+        order).  A ragged stack with a contiguous 16-bit cache; `position`, `lengths`, `slots` as in `prefill` (host ints per sequence).
+        The pass is `prefill`'s fused layer body with the attention of DecodeLayer.verify_attention, which splits the cached context
+        over the GPU as the decode step's attention does; the LM head runs on all n * T rows.
+        All T cache rows of a sequence are written.  Rows of draft tokens that are rejected afterwards simply stay above the sequence's
+        next position: no kernel reads a cache row above a token's own position, so they are dead until a later token overwrites them,
+        and nothing has to be rolled back.
+        position=None (fused path): `prefill_pos_seq` / `prefill_len` / `prefill_slot` [:n] are left as the caller set them and nothing is
+        copied from the host, so a verify pass of fixed T can be captured in a graph (after one eager call, which makes the scratch).
+        The plain-torch path (fused=False) runs DecodeLayer.forward_prefill and is the reference formulation."""
+        if not self.ragged:
+            raise ValueError("verify on a stack without a position per sequence is not built yet: DecodeStack(..., ragged=True)")
+        if self.kv_cache == "mx8":
+            raise ValueError("verify on an mx8 KV cache is not built yet")
+        if self.paged:
+            raise ValueError("verify on a paged KV cache (kv_pages) is not built yet")
+        if tokens.dim() != 2 or tokens.shape[1] < 1 or not 1 <= tokens.shape[0] <= self.bs:
+            raise ValueError(f"tokens must be [1 <= n <= bs = {self.bs}, 1 <= T <= 8], got {tuple(tokens.shape)}")
+        n, T = tokens.shape
+        if T > 8:
+            raise ValueError(f"verify of more than 8 tokens per sequence is not built yet, got T = {T}")
+        S = self.cfg.max_seq
+        if position is None:
+            if not self.fused or lengths is not None or slots is not None:
+                raise ValueError("position=None (the caller owns the prefill buffers) needs the fused path and goes without lengths / slots")
+        else:
+            def ints(x, what):
+                if isinstance(x, torch.Tensor):
+                    x = x.tolist()
+                vals = [operator.index(v) for v in x] if isinstance(x, (list, tuple)) else [operator.index(x)] * n
+                if len(vals) != n:
+                    raise ValueError(f"{what}: {len(vals)} values for {n} sequences")
+                return vals
+
+            position, lengths = ints(position, "position"), ints(T if lengths is None else lengths, "lengths")
+            if slots is None and n != self.bs:
+                raise ValueError(f"{n} sequences in a stack of bs = {self.bs} need `slots`")
+            slots = ints(list(range(self.bs)) if slots is None else slots, "slots")
+            if any(not 0 <= x <= T for x in lengths):
+                raise ValueError(f"lengths {lengths}: each must be in [0, T = {T}]")
+            if any(p < 0 or p + x > S for p, x in zip(position, lengths)):
+                raise ValueError(f"positions {position} + lengths {lengths} outside the KV cache [0, {S})")
+            if any(not 0 <= x < self.bs for x in slots) or len(set(slots)) != n:
+                raise ValueError(f"slots {slots}: {n} distinct values in [0, bs = {self.bs}) needed")
+        if self.fused and self._verify_split > 1 and n not in self._verify_scratch:
+            from . import decode_ops as G
+
+            self._verify_scratch[n] = G.verify_attn_scratch(n, self.cfg.heads // self.world, self.cfg.head_dim, 8, self._verify_split,
+                                                            self.tokens.device)
+        out = self._head(*self._prefill_chunk(tokens, position, lengths, slots, True, verify=True))
+        return out.view(n, T, -1)
 
     def _picked(self, logits):
         """The sampled tokens of the decode step that returned `logits`: the captured sampler has written them, else one launch does."""

@@ -310,6 +310,46 @@ def prefill_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: t
     return out
 
 
+def verify_attn_scratch(n: int, hl: int, d: int, T: int, nsplit: int, device) -> torch.Tensor:
+    """Zeroed scratch buffer for verify_attn with nsplit > 1 (counters + per-split partials); reusable by stream-ordered launches.
+    nsplit = 1 needs none: an empty tensor."""
+    b = _lib.load().dg_verify_attn_scratch_bytes(n, hl, d, T, nsplit)
+    return torch.zeros((b + 3) // 4, dtype=torch.int32, device=device)
+
+
+def verify_attn(qkv: torch.Tensor, cos: torch.Tensor, sin: torch.Tensor, pos: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                hl: int, kvl: int, d: int, scale: float, T: int, nsplit: int = 1, scratch: torch.Tensor = None, out: torch.Tensor = None,
+                lengths: torch.Tensor = None, slots: torch.Tensor = None) -> torch.Tensor:
+    """The verify pass of speculative decoding: prefill_attn's per-sequence call for T = 1 ... 8 draft tokens on contiguous 16-bit caches,
+    one launch that splits the cached context over `nsplit` blocks (1 ... 64) per (sequence, kv head, group of 4 query heads).  qkv
+    [n * T, (hl + 2 kvl) d] (row i * T + t) -> context [n * T, hl * d]; `pos` int64 [n] on the device is the position of token 0 of each
+    sequence; `lengths` / `slots` as in prefill_attn.  scratch: verify_attn_scratch(...) for nsplit > 1.  The cache rows are
+    prefill_attn's bit for bit, the context agrees with it within 16-bit rounding (the split changes the order of the sums)."""
+    out, rows, max_seq = _rope_front(qkv, cos, sin, pos, k_cache, v_cache, hl, d, lengths, slots, scratch, out=out)
+    T, nsplit = int(T), int(nsplit)
+    cache_bs = k_cache.shape[0]
+    if k_cache.dtype != qkv.dtype or v_cache.dtype != qkv.dtype or k_cache.shape != v_cache.shape or tuple(k_cache.shape[1::2]) != (kvl, d):
+        raise RuntimeError(f"verify_attn: the caches must be {qkv.dtype} [cache_bs, {kvl}, max_seq, {d}], got {k_cache.dtype} {tuple(k_cache.shape)}")
+    if T < 1 or qkv.dim() != 2 or rows % T or (rows // T != cache_bs and slots is None):
+        raise RuntimeError(f"verify_attn: qkv must be [n * T, ...] with T = {T} and n = {cache_bs} (the caches'), got {tuple(qkv.shape)}")
+    if out.shape != (rows, hl * d) or out.dtype != qkv.dtype:
+        raise RuntimeError(f"verify_attn: out must be [{rows}, {hl * d}] {qkv.dtype}")
+    n = rows // T
+    _per_sequence(pos, n, "verify_attn")
+    for name, t in (("lengths", lengths), ("slots", slots)):
+        if t is not None and (t.dtype != torch.int64 or t.numel() != n):
+            raise RuntimeError(f"verify_attn: {name} must be int64 with {n} elements (one per sequence)")
+    if nsplit > 1 and (scratch is None or scratch.dtype != torch.int32):
+        raise RuntimeError("verify_attn: nsplit > 1 needs the int32 scratch of verify_attn_scratch")
+    ptr = lambda t: None if t is None else t.data_ptr()
+    call = _lib.Verify(qkv=ptr(qkv), cos=ptr(cos), sin=ptr(sin), pos=ptr(pos), len=ptr(lengths), slot=ptr(slots), k_cache=ptr(k_cache),
+                       v_cache=ptr(v_cache), out=ptr(out), scratch=ptr(scratch) if nsplit > 1 else None,
+                       scratch_bytes=scratch.numel() * 4 if nsplit > 1 else 0, bs=n, cache_bs=cache_bs, max_seq=max_seq, T=T, hl=hl, kvl=kvl,
+                       d=d, nsplit=nsplit, dtype=_dt(qkv), scale=float(scale))
+    _lib.check(_lib.load().dg_verify_attn(ctypes.byref(call), qkv.device.index, _stream(qkv)), "dg_verify_attn")
+    return out
+
+
 def sample(logits: torch.Tensor, ctr: torch.Tensor, temperature: torch.Tensor, top_k: torch.Tensor, top_p: torch.Tensor,
            seed: torch.Tensor = None, ctr_add: int = 1, u: torch.Tensor = None, token_out: torch.Tensor = None, u_out: torch.Tensor = None,
            scratch: torch.Tensor = None, vocab: int = None) -> torch.Tensor:

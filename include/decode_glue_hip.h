@@ -252,6 +252,63 @@ typedef struct dg_attn {
 TG_API int dg_attn_launch(const dg_attn* call, int device, tg_stream_t stream);
 TG_API int64_t dg_rope_attn_split_scratch_bytes(int64_t bs, int hl, int d, int nsplit);
 
+/* ---- speculative decoding: the verify pass's attention, a few draft tokens per sequence over a long cache, split over the context ----
+ * dg_verify_attn has the call semantics of dg_prefill_attn_seq (above) for T = 1 ... 8 on contiguous 16-bit caches, in ONE launch whose grid
+ * splits the cached context; it is an entry point of its own, not a kernel of dg_attn_launch.
+ *   qkv [bs * T][(hl + 2 kvl) * d], row i * T + t = token t of sequence i (q heads, k heads, v heads); out [bs * T][hl * d] likewise.
+ *   pos [bs] int64 on the device: position p0 of token 0 of sequence i; len [bs] or NULL (every length is T); slot [bs] or NULL (sequence i
+ *   lives in slot i, and bs == cache_bs is required); caches [cache_bs][kvl][max_seq][d].  Token t of sequence i EXISTS iff
+ *   t < min(len[i], T) and 0 <= p0 + t < max_seq; len[i] <= 0 or a slot outside [0, cache_bs) makes the sequence a no-op.
+ *     k_cache[slot][kv][p0 + t][:] = rope(k, p0 + t);  v_cache[slot][kv][p0 + t][:] = v        -- the bits dg_rope_kv writes
+ *     out[i * T + t][h * d ...] = softmax_{s <= p0 + t}( (rope(q) . K[s]) * scale ) applied to V, K / V = cache rows [0, p0) that earlier
+ *     calls wrote and the chunk's own rows [p0, p0 + t], which are taken from qkv and never read back from the cache inside the launch.
+ *   A token that does not exist writes no cache row, is seen by nobody and leaves its output row unwritten; cache rows outside
+ *   [p0, p0 + T) are not written, rows at or above p0 are not read (a 64-position tile's rows from p0 on are zero-filled on chip), and
+ *   whatever pos / len / slot hold, nothing outside the caches is indexed.  Slots must be distinct (the caller's obligation).
+ * Arithmetic is dg_prefill_attn's: q and k roped as dg_rope_kv ropes and rounded to 16 bit, scores and softmax statistics in f32 (online
+ *   over 64-position tiles), probabilities rounded to 16 bit for the value product, f32 accumulation, normalised once, one rounding.  The
+ *   ORDER of the sums is this kernel's: block x of `nsplit` takes a contiguous slice of the 64-position tiles of [0, p0), its four waves
+ *   every fourth tile of the slice, the chunk's own tokens are one more tile; waves are merged in wave order, blocks in split order by the
+ *   last block to arrive.  So the output agrees with dg_prefill_attn_seq's within 16-bit rounding, not bit for bit, and the same call
+ *   gives the same bits on every launch.  Cache rows are bit-equal to dg_prefill_attn_seq's.
+ * scratch: nsplit > 1 only -- dg_verify_attn_scratch_bytes(bs, hl, d, T, nsplit) bytes, 16-byte aligned, ZEROED ONCE by the caller before
+ *   the first launch (the kernel leaves its counters at zero again, so a captured launch replays); launches sharing a scratch must be
+ *   stream-ordered and agree in bs and hl (which place the counters).  With nsplit = 1 scratch is not read (it may be NULL) and the answer of dg_verify_attn_scratch_bytes is 0.
+ * In this order: call == NULL TG_E_NULL; struct_bytes != sizeof(struct dg_verify) TG_E_STRUCT; a required pointer NULL (qkv, cos, sin, pos,
+ *   the caches, out; scratch with nsplit > 1) TG_E_NULL; TG_E_DTYPE; TG_E_SHAPE: d other than 64 / 128, T outside 1 ... 8, nsplit outside
+ *   1 ... 64, bs or hl outside 1 ... 65535, hl % kvl != 0, max_seq outside 1 ... 65536, cache_bs < 1, bs != cache_bs without slot; TG_E_ALIGN:
+ *   qkv, cos, sin, a cache, out or the scratch off a 16-byte boundary; TG_E_SHAPE: a scratch that is too small.  Nothing is touched in
+ *   any of these cases.  No allocation, no synchronisation, graph-capturable. */
+typedef struct dg_verify {
+  uint32_t struct_bytes;  /* sizeof(struct dg_verify); anything else is TG_E_STRUCT */
+  uint32_t reserved0;     /* padding to 8 bytes; not read */
+  const void* qkv;        /* [bs * T][(hl + 2 kvl) * d], 16-bit */
+  const float* cos;       /* float32 [max_seq][d] */
+  const float* sin;
+  const int64_t* pos;     /* [bs] on the device */
+  const int64_t* len;     /* [bs] or NULL */
+  const int64_t* slot;    /* [bs] or NULL */
+  void* k_cache;          /* [cache_bs][kvl][max_seq][d], 16-bit */
+  void* v_cache;
+  void* out;              /* [bs * T][hl * d] */
+  void* scratch;          /* nsplit > 1 */
+  int64_t scratch_bytes;  /* nsplit > 1: at least dg_verify_attn_scratch_bytes */
+  int64_t bs;             /* sequences of the call */
+  int64_t cache_bs;       /* sequences the caches hold */
+  int64_t max_seq;
+  int32_t T;              /* tokens per sequence, 1 ... 8 */
+  int32_t hl;             /* query heads, kv heads (hl % kvl == 0), head dimension */
+  int32_t kvl;
+  int32_t d;
+  int32_t nsplit;         /* blocks over the cached context, 1 ... 64 */
+  int32_t dtype;          /* TG_BF16 / TG_F16 */
+  float scale;
+  uint32_t reserved;      /* padding to 8 bytes; not read */
+} dg_verify;
+
+TG_API int dg_verify_attn(const dg_verify* call, int device, tg_stream_t stream);
+TG_API int64_t dg_verify_attn_scratch_bytes(int64_t bs, int hl, int d, int T, int nsplit);
+
 /* ---- sampling: temperature, top-k, top-p (nucleus) and a counter-based draw, one launch per step ----
  * The definition is any4_amd/sampling.py (sample_ref, uniform, philox4x32_10), in float64; this is its kernel.  Per row b of
  * logits [bs][ld] (16-bit, ld >= vocab; rows need no alignment beyond 2 bytes):
