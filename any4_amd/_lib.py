@@ -197,6 +197,10 @@ SYMBOLS = {
     # MX4 weights x MXFP8 activations: x, m, k, codes, exps, device, stream / the call struct
     "tg_quant_mx8_rows": [_vp, _i64, _i64, _vp, _vp, ctypes.c_int, _vp],
     "tg_gemm_mx4a8": [ctypes.POINTER(MxGemm), ctypes.c_int, _vp],
+    # ... at 1 ... 64 rows: m, wrows, k / the call struct, workspace, workspace_bytes, device, stream / m, wrows, k, out[4]
+    "tg_gemm_mx4a8_rows_workspace_bytes": [_i64, _i64, _i64],
+    "tg_gemm_mx4a8_rows": [ctypes.POINTER(MxGemm), _vp, _i64, ctypes.c_int, _vp],
+    "tg_gemm_mx4a8_rows_plan": [_i64, _i64, _i64, ctypes.POINTER(_i64)],
     "tg_gemm_f16": [_vp, _vp, _vp, _i64, _i64, _i64, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp],
     "tg_convert_to_Bint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],
     "tg_convert_to_Aint8": [_vp, _i64, _i64, ctypes.c_int, _vp, ctypes.c_int, _vp],
@@ -269,7 +273,7 @@ def load() -> ctypes.CDLL:
         fn.argtypes = argtypes
         fn.restype = (ctypes.c_char_p if name == "tg_error_string" else
                       ctypes.c_int64 if name in ("dg_rope_attn_split_scratch_bytes", "dg_verify_attn_scratch_bytes", "dg_sample_scratch_bytes", "tg_gemm_w4_workspace_bytes", "tg_gemm_w8_workspace_bytes",
-                                                                                          "tg_gemm_w4_dx_workspace_bytes", "tg_gemm_w4_dq_workspace_bytes") else ctypes.c_int)
+                                                                                          "tg_gemm_w4_dx_workspace_bytes", "tg_gemm_w4_dq_workspace_bytes", "tg_gemm_mx4a8_rows_workspace_bytes") else ctypes.c_int)
     if lib.tg_abi_version() != TG_ABI_VERSION:
         raise ImportError(f"{LIB_PATH}: ABI version {lib.tg_abi_version()} != {TG_ABI_VERSION}; rebuild")
     _lib = lib

@@ -22,6 +22,7 @@
 //   tg_moe_tile.hip    w4_gemm_tile_kernel<GRP>, moe_group_kernel, moe_combine_kernel (w4_gemm_tile.cuh, moe_grouped.cuh)  mixture-of-experts prefill: pairs sorted by expert, grouped tile GEMM (dg_moe_group / DG_MOE_GROUPED's launcher)
 //   tg_kmeans.hip      kmeans_rows_kernel        (kmeans.cuh)              the any4 quantizer's per-row weighted 1-D k-means (tg_kmeans_rows); compiled with -ffp-contract=off
 //   tg_mx.hip          mx8_rows_kernel, mx4a8_gemm_kernel (w4a8_gemm_mx.cuh)   MX4 weights x MXFP8 activations on the block-scaled MFMA (tg_quant_mx8_rows / tg_gemm_mx4a8)
+//                      mx4a8_rows_kernel         (w4a8_rows_mx.cuh)        ... at 1 ... 64 activation rows: weights streamed, activations in registers, k windows (tg_gemm_mx4a8_rows)
 //   tg_verify.hip      verify_attn_kernel        (attn_verify.cuh)         speculative decoding's verify pass: split-KV attention for 1 ... 8 draft tokens per sequence (dg_verify_attn); compiled without packed f32 ALU forms
 // Shared by several units' kernels, included inside the unit's anonymous namespace: w4_helpers.cuh (fragment-order addressing, mx4 converters,
 // MFMA / v_dot2 wrappers, the stages fused into a GEMM), stage_math.cuh (the arithmetic of rope, RMSNorm and SwiGLU: one definition each), kv8.cuh (the mx8 KV-cache format: decode_glue.cuh, attn_prefill.cuh);

@@ -36,8 +36,9 @@
 //              64 VGPRs; the weight ring 2 x (4 tiles x 16 + 4 exponent words) = 136; fragments and addresses ~40: 1 wave per SIMD at <= 256.
 //              LDS: 3 x (32 KiB + 1 KiB) = 99 KiB.  Per step a wave issues 64 MFMAs and reads 16 fragments x 2 KiB = 32 KiB of LDS: 2 MFMAs
 //              (2 x 32768 products) per KiB read; the tile GEMM's bf16 MFMAs get 1 (of 8192 products) per KiB.
-//   ragged     rows beyond m / wrows load a valid row again and are never stored.  Any m >= 1; tuned for m >= 64.  Split-K for launches that do not
-//              fill the chip is out of scope: a 4096^2 layer at m = 512 is 128 workgroups.
+//   ragged     rows beyond m / wrows load a valid row again and are never stored.  Any m >= 1; tuned for m >= 64.  This kernel never splits k:
+//              a 4096^2 layer at m = 512 is 128 workgroups, at m <= 64 it is 16.  Launches of 1 ... 64 rows have a kernel of their own,
+//              mx4a8_rows_kernel (w4a8_rows_mx.cuh, tg_gemm_mx4a8_rows): 16-row tiles, k in windows, the partials summed in a fixed order.
 //   NaN        an exponent byte of 255 is E8M0's NaN: the instruction's product is NaN for exactly that (weight row, activation row) pair's block,
 //              so the row / column of the output is NaN and nothing else (tests/test_gpu_mx4a8.py holds it to that).
 #pragma once

@@ -391,10 +391,13 @@ class MX4Linear(_PackedLinear):
         return self.exponents
 
     def __init__(self, in_features: int, out_features: int, bias: bool = True, device=None, dtype=None,
-                 group_size: int = 32, kernel: str = "linear_y_f16RM_x_f16RM_W_mx4TC", w_inner_k: int = 4, activations: str | None = None) -> None:
+                 group_size: int = 32, kernel: str = "linear_y_f16RM_x_f16RM_W_mx4TC", w_inner_k: int = 4, activations: str | None = None,
+                 small_batch: bool = False) -> None:
         super().__init__()
         if activations not in (None, "mx8"):
             raise ValueError(f"activations must be None (16-bit activations) or 'mx8', got {activations!r}")
+        if small_batch and activations != "mx8":
+            raise ValueError("small_batch=True selects the W4A8 kernel for 1 ... 64 rows: it needs activations='mx8'")
         if activations == "mx8":
             # W4A8 on the block-scaled matrix instruction (ops.gemm_mx4_a8): what its kernel reads, refused here and not at the first forward
             if group_size != 32:
@@ -408,6 +411,7 @@ class MX4Linear(_PackedLinear):
             if kernel not in self._PACKERS:
                 raise ValueError(f"Unsupported kernel type {kernel}")
         self.activations = activations
+        self.small_batch = bool(small_batch)   # forward at <= 64 rows on ops.gemm_mx4_a8(kernel="rows"): same definition, other bits; off by default
         self._make_common(in_features, out_features, bias, device, dtype, group_size, kernel, w_inner_k, zero_init=True)
         del self.scales_and_zeros
         self.exponents = torch.nn.Parameter(torch.full((out_features, in_features // group_size), 127, dtype=torch.uint8, device=device),
@@ -425,7 +429,8 @@ class MX4Linear(_PackedLinear):
             self._auto_relayout()
         x2d = input.reshape(-1, input.shape[-1]).contiguous()
         fused = self.bias is not None and self.bias.numel() == self.exponents.size(0)   # (one value per tile-padded weight row)
-        y = _ops.gemm_mx4_a8(x2d, self.weight, self.exponents, self.kernel == "linear_y_f16RM_x_f16RM_W_mx4TC", self.bias if fused else None)
+        y = _ops.gemm_mx4_a8(x2d, self.weight, self.exponents, self.kernel == "linear_y_f16RM_x_f16RM_W_mx4TC", self.bias if fused else None,
+                              kernel="auto" if self.small_batch else "tile")
         if self.bias is not None and not fused:
             y = y + self.bias
         return y.view(*input.shape[:-1], y.shape[-1])

@@ -1207,16 +1207,48 @@ def quantize_mx8_rows(x: torch.Tensor):
     return codes, exps
 
 
-def gemm_mx4_a8(x: torch.Tensor, w: torch.Tensor, exponents: torch.Tensor, weight_on_right: bool, bias: torch.Tensor | None = None) -> torch.Tensor:
+MX4A8_ROWS_MAX_M = 64   # activation rows up to which tg_gemm_mx4a8_rows takes a call
+_MX_ROWS_WS: dict = {}  # (device index, bytes) -> the zeroed workspace of tg_gemm_mx4a8_rows: every call leaves its counters zero
+
+
+def _mx_rows_workspace(x: torch.Tensor, m: int, wrows: int, k: int):
+    """(pointer, bytes) of the rows kernel's workspace for this shape: nothing where k is one window; else one zeroed buffer per (device,
+    bytes), made by the first call and shared by the stream-ordered calls after it (a call that is being captured cannot make it)."""
+    need = _L.tg_gemm_mx4a8_rows_workspace_bytes(m, wrows, k)
+    _lib.check(need if need < 0 else 0, "gemm_mx4_a8")
+    if need == 0:
+        return None, 0
+    key = (_dev(x), need)
+    ws = _MX_ROWS_WS.get(key)
+    if ws is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("gemm_mx4_a8(kernel='rows'): the workspace of this shape is made by the first call; make that call before capturing")
+        ws = _MX_ROWS_WS[key] = torch.zeros(need, dtype=torch.uint8, device=x.device)
+    return ws.data_ptr(), need
+
+
+def gemm_mx4_a8(x: torch.Tensor, w: torch.Tensor, exponents: torch.Tensor, weight_on_right: bool, bias: torch.Tensor | None = None,
+                kernel: str = "tile") -> torch.Tensor:
     """y [m][wrows] = mx8(x) . mx4(w)^T (utils.mx4a8_ref is the definition): x bf16 [m][k], k % 128 == 0, quantised to MXFP8 rows in one
     launch and multiplied in a second one with the packed MX4 weights an MX4Linear holds (Bint4 words of innerKTiles 4, or the native
-    weights-on-the-left tensor), exponents uint8 [wrows][k / 32].  Both launches go to the current stream; the call can be captured."""
+    weights-on-the-left tensor), exponents uint8 [wrows][k / 32].  Both launches go to the current stream; the call can be captured.
+    kernel: "tile" (tg_gemm_mx4a8: 64 x 256 tiles, any m), "rows" (tg_gemm_mx4a8_rows: the weight-streaming kernel for m <= 64, ValueError
+    beyond) or "auto" (rows up to 32 rows, and up to 64 rows on at most 4096 weight rows; tile otherwise: where each was measured ahead; at
+    33 ... 64 rows on more than 4096 weight rows only 14336 x 4096 was measured, so "tile" there is a guess for other shapes: pass "rows" to try).  The two kernels sum in different orders: same definition, not the same bits."""
     _check(x.dim() == 2 and x.is_contiguous(), "activations must be a contiguous 2-D matrix")
     m, k = x.shape
+    if kernel not in ("tile", "rows", "auto"):
+        raise ValueError(f"gemm_mx4_a8: kernel must be 'tile', 'rows' or 'auto', got {kernel!r}")
+    if kernel == "rows" and m > MX4A8_ROWS_MAX_M:
+        raise ValueError(f"gemm_mx4_a8(kernel='rows') takes at most {MX4A8_ROWS_MAX_M} activation rows, got {m}: use 'tile' or 'auto'")
     inner, wrows, w_format, _, exponents, _ = _w4_operands(x, k, w, 32, exponents, None, TG_Q_MX4, weight_on_right, aint4=False)
     if bias is not None:
         _check(bias.dtype == x.dtype and bias.device == x.device and bias.dim() == 1 and bias.numel() == wrows and bias.is_contiguous(),
                "bias must be a contiguous bfloat16 vector of one value per (tile-padded) weight row")
+    # auto: where the rows kernel was measured ahead of the tile kernel (DESIGN.md section 26.1): up to 32 rows, and up to 64 on 4096 weight rows
+    # (k = 4096 and 14336); at 64 rows x 14336 weight rows x k = 4096 the tile kernel is ahead (28.3 against 30.5 us).  NOT measured: 33 ... 64 rows
+    # on 4096 < wrows < 14336, and on wrows > 4096 at k > 4096 (rows may well be ahead there: it was, 65 against 81 us, at wrows = 4096, k = 14336)
+    rows = kernel == "rows" or (kernel == "auto" and (m <= 32 or (m <= MX4A8_ROWS_MAX_M and wrows <= 4096)))
     y = torch.empty((m, wrows), dtype=x.dtype, device=x.device)
     if m == 0:
         return y
@@ -1224,7 +1256,11 @@ def gemm_mx4_a8(x: torch.Tensor, w: torch.Tensor, exponents: torch.Tensor, weigh
     args = _lib.MxGemm(x_codes=codes.data_ptr(), x_exps=exps.data_ptr(), w=w.data_ptr(), w_exps=exponents.data_ptr(),
                        bias=(bias.data_ptr() if bias is not None else None), y=y.data_ptr(), m=m, wrows=wrows, k=k,
                        w_on_right=1 if weight_on_right else 0, w_format=w_format, inner_k_tiles=inner)
-    _lib.check(_L.tg_gemm_mx4a8(ctypes.byref(args), _dev(x), _stream(x)), "gemm_mx4_a8")
+    if rows:
+        ws, ws_bytes = _mx_rows_workspace(x, m, wrows, k)
+        _lib.check(_L.tg_gemm_mx4a8_rows(ctypes.byref(args), ws, ws_bytes, _dev(x), _stream(x)), "gemm_mx4_a8")
+    else:
+        _lib.check(_L.tg_gemm_mx4a8(ctypes.byref(args), _dev(x), _stream(x)), "gemm_mx4_a8")
     return y
 
 

@@ -3,7 +3,8 @@
 Compiles the unit with -Rpass-analysis=kernel-resource-usage (any4_amd/build.py's flags) and prints one line per kernel.
 --check: exit 1 when a listed kernel uses scratch memory (spills); the kernels that must stay free of it:
     python dev/kernel_resources.py tg_prefill.hip prefill --check      # prefill_attn_kernel / prefill_rope_kv_kernel
-    python dev/kernel_resources.py tg_verify.hip verify --check        # verify_attn_kernel"""
+    python dev/kernel_resources.py tg_verify.hip verify --check        # verify_attn_kernel
+    python dev/kernel_resources.py tg_mx.hip rows --check              # mx4a8_rows_kernel"""
 import os
 import re
 import subprocess

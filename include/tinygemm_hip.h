@@ -385,7 +385,7 @@ TG_API int tg_kmeans_rows_plan(int64_t rows, int64_t k, int C, int S, int max_it
  *   with a bias RNE16(RNE16(sum) + bias[r]).  The weights are the tensors an MX4 linear already holds: Bint4 words of innerKTiles 4
  *   (w_on_right = 1) or the same words as TG_WFMT_ROWS (w_on_right = 0), exponents [wrows][k / 32].  An exponent byte of 255 on either side
  *   makes exactly that weight row's / activation row's outputs NaN.  One workgroup per 64 x 256 output tile, k never split: a row's bits do
- *   not depend on m.  Any m >= 1, tuned for m >= 64.
+ *   not depend on m.  Any m >= 1, tuned for m >= 64; for m <= 64 see tg_gemm_mx4a8_rows below.
  *   Refused before any HIP call: a required pointer NULL (bias may be): TG_E_NULL; x_codes / w not 16-byte, the exponents not 4-byte, y / bias
  *   not 8-byte aligned: TG_E_ALIGN; k % 128 != 0: TG_E_K_DIV; inner_k_tiles != 4: TG_E_INNER_K; the reference's Aint4 words (w_on_right = 0,
  *   TG_WFMT_M16N8K16): TG_E_LAYOUT; struct_bytes not this library's, or a reserved field not 0: TG_E_STRUCT; an operand of 2 GiB or more:
@@ -409,6 +409,25 @@ typedef struct tg_mx_gemm {
 
 TG_API int tg_quant_mx8_rows(const void* x, int64_t m, int64_t k, void* codes, void* exps, int device, tg_stream_t stream);
 TG_API int tg_gemm_mx4a8(const tg_mx_gemm* args, int device, tg_stream_t stream);
+
+/*
+ * tg_gemm_mx4a8_rows: the same operands, the same definition and the same struct for m = 1 ... 64 (any4_amd/csrc/w4a8_rows_mx.cuh): one
+ *   workgroup per 16 weight rows x 16 activation rows x 4096 k, weights streamed global -> register -> matrix instruction, the activations
+ *   resident in registers.  k is cut by a rule of k alone (512-k steps dealt to four waves, 4096-k windows to workgroups), every sum is made
+ *   in a fixed order and the output is rounded once: a row's bits depend neither on m, nor on wrows, nor on the device -- but they are not
+ *   tg_gemm_mx4a8's bits (another order of the f32 sums).  Opt-in; added without an ABI version bump: callers probe for the symbols.
+ *   k > 4096 needs a workspace of tg_gemm_mx4a8_rows_workspace_bytes(m, wrows, k) bytes (0 where k is one window; < 0: a TG_E_* code), 16-byte
+ *   aligned, whose first (m + 15) / 16 * ((wrows + 15) / 16) int32 are ZERO before the first call; every call leaves them zero, so the
+ *   workspace serves stream-ordered calls and graph replays without being cleared again.
+ *   Refused before any HIP call: everything tg_gemm_mx4a8 refuses, in its order; then m > 64: TG_E_SHAPE; more than 65535 windows (k > 2^28 - 4096):
+ *   TG_E_SIZE; where bytes are needed, workspace
+ *   NULL: TG_E_NULL, not 16-byte aligned or workspace_bytes < 0: TG_E_ALIGN, workspace_bytes too small: TG_E_SHAPE.
+ * tg_gemm_mx4a8_rows_plan: the launch such a call makes, without a device: out[0] = workgroups that share the row tiles of an activation
+ *   block (each walks the tiles b, b + out[0], ...: at most 512, the tiles dealt evenly), out[1] = blocks of 16 activation rows, out[2] = k windows, out[3] = k of a window.
+ */
+TG_API int64_t tg_gemm_mx4a8_rows_workspace_bytes(int64_t m, int64_t wrows, int64_t k);
+TG_API int tg_gemm_mx4a8_rows(const tg_mx_gemm* args, void* workspace, int64_t workspace_bytes, int device, tg_stream_t stream);
+TG_API int tg_gemm_mx4a8_rows_plan(int64_t m, int64_t wrows, int64_t k, int64_t* out);
 
 #ifdef __cplusplus
 }
